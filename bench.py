@@ -39,6 +39,21 @@ def make_frames(n, w, h, seed0, content="natural"):
     return frames
 
 
+def dump_outputs(dirname, per_frame, limit_bytes=64 << 20):
+    """--dump-outputs: what the last timed step returned to its caller (one (k_i, 4) rectangle array per frame), as float64
+    .npy files -- rects.npy: (n, 5) rows [frame, x, y, w, h] in frame order; rects_per_frame.npy: k_i of every frame. Above
+    limit_bytes, rects.npy holds a fixed, seeded sample of its rows (in order)."""
+    os.makedirs(dirname, exist_ok=True)
+    counts = np.array([len(r) for r in per_frame], np.float64)
+    rows = [np.column_stack([np.full(len(r), i, np.float64), np.asarray(r, np.float64).reshape(-1, 4)]) for i, r in enumerate(per_frame)]
+    rects = np.concatenate(rows) if rows else np.zeros((0, 5), np.float64)
+    keep = max(1, (limit_bytes - counts.nbytes) // rects[:1].nbytes) if len(rects) else 0
+    if len(rects) > keep:
+        rects = rects[np.sort(np.random.default_rng(0).choice(len(rects), keep, replace=False))]
+    np.save(os.path.join(dirname, "rects.npy"), rects)
+    np.save(os.path.join(dirname, "rects_per_frame.npy"), counts)
+
+
 def usable_cores():
     """Host cores this process may really use: the affinity mask, capped by the cgroup CPU quota if there is one."""
     n = len(os.sched_getaffinity(0))
@@ -498,7 +513,13 @@ def main():
     ap.add_argument("--rehearse-gather", action="store_true", help="no detector, no GPU: every rank makes up the rectangles of its "
                                                                    "--frames frames and the ranks run the N > 1 leg only (rendezvous, communicator, "
                                                                    "trial gather, gathers, max-over-ranks timing); prints a line marked as a rehearsal")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the rectangles the last timed step returned "
+                                                         "to DIR/*.npy (float64; see dump_outputs); rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.device_only or args.rehearse_gather):
+        ap.error("--dump-outputs: --device-only and --rehearse-gather return no detections to dump")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: this process never touches the GPU; it starts one rank per GPU as child
@@ -601,6 +622,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     # Where the step time goes that is not kernel time: the same step without copy-back and grouping (device pipeline
     # only), and the step fed from HOST frames (the reference's call shape, tools/detection/Cpp/main.cpp:27-45: the image is

@@ -103,3 +103,37 @@ def test_bench_two_ranks_gather_through_the_c_abi_communicator(monkeypatch):
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["value"] > 0
     assert out["config"]["gather"].startswith("cc_gather_detections (C ABI, loopback TCP")
+
+
+def test_dump_outputs_and_steps_are_checked_before_any_work(tmp_path):
+    """--steps below 1 and --dump-outputs on a leg that returns no detections are refused at argument parsing."""
+    r = _run(["--steps", "0"], timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+    r = _run(["--device-only", "--dump-outputs", str(tmp_path)], timeout=120)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+    assert not os.listdir(str(tmp_path))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_rectangles(tmp_path):
+    """--dump-outputs writes what the last timed step returned, as float64 [frame, x, y, w, h] rows plus per-frame counts:
+    the same rectangles the CPU oracle finds on bench.py's seeded frames."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    from oracle import oracle as orc
+    r = _run(["--frames", "2", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "480", "--cpu-frames", "0",
+              "--no-extra", "--dump-outputs", str(tmp_path)], timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    rects = np.load(str(tmp_path / "rects.npy"))
+    counts = np.load(str(tmp_path / "rects_per_frame.npy"))
+    assert rects.dtype == np.float64 and counts.dtype == np.float64 and rects.shape == (int(counts.sum()), 5)
+    o = orc.load_cascade_xml(os.path.join(ROOT, "data", "haarcascade_frontalface_synthetic.xml"))
+    frames = bench.make_frames(2, 640, 480, seed0=0)
+    for i in range(2):
+        want = orc.detect_multiscale(o, frames[i], 1.1, 3, nthreads=4)
+        got = rects[rects[:, 0] == i, 1:]
+        assert counts[i] == len(want) and (got == want).all(), (i, got, want)
