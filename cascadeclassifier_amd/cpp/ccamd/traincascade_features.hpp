@@ -27,6 +27,9 @@
 #define CC_FEATURE_PARAMS "featureParams"  // cascadeclassifier.h:58
 #define HFP_NAME "haarFeatureParams"       // haarfeatures.h:21
 #define LBPF_NAME "lbpFeatureParams"       // lbpfeatures.h:18
+#define HOGF_NAME "HOGFeatureParams"       // HOGfeatures.h:13
+#define N_BINS 9                           // HOGfeatures.h:15-16
+#define N_CELLS 4
 
 // traincascade_features.h:105-122, features.cpp:27-32: the polymorphic base every parameter struct of the trainer derives
 // from (the driver iterates them for params.xml and the command line: traincascade.cpp:59-81,141, cascadeclassifier.cpp:200,359-400)
@@ -72,6 +75,10 @@ struct CvLBPFeatureParams : CvFeatureParams {  // lbpfeatures.h:22-26, lbpfeatur
   CvLBPFeatureParams();
 };
 
+struct CvHOGFeatureParams : CvFeatureParams {  // HOGfeatures.h:28-31, HOGfeatures.cpp:9-14
+  CvHOGFeatureParams();
+};
+
 class CvFeatureEvaluator {  // traincascade_features.h:155-188
  public:
   CvFeatureEvaluator();
@@ -109,6 +116,8 @@ class CvFeatureEvaluator {  // traincascade_features.h:155-188
   virtual void generateFeatures() = 0;
   virtual int featureType() const = 0;
   virtual int haarMode() const { return 0; }
+  // range of operator()'s first argument: features (Haar, LBP) or variables, numFeatures * 36 (HOG)
+  virtual int numVariables() const { return numFeatures; }
   float cachedValue(int featureIdx, int sampleIdx) const;
 
   int npos, nneg;
@@ -172,6 +181,36 @@ class CvLBPEvaluator : public CvFeatureEvaluator {  // lbpfeatures.h:37-68
  protected:
   void generateFeatures() override;
   int featureType() const override { return CvFeatureParams::LBP; }
+};
+
+// HOGfeatures.h:43-82. operator()(varIdx, sampleIdx): varIdx in [0, getNumFeatures() * getFeatureSize()), block
+// varIdx / 36, cell (varIdx % 36) / 9, bin varIdx % 9 (HOGfeatures.h:84-90); values come from the device planes (or the
+// host mirror of the window set last), bit-identical to the restated CvHOGEvaluator.
+class CvHOGEvaluator : public CvFeatureEvaluator {
+ public:
+  ~CvHOGEvaluator() override {}
+  void init(const CvFeatureParams* _featureParams, int _maxSampleCount, cv::Size _winSize) override;
+  void setImage(const cv::Mat& img, uchar clsLabel, int idx) override { CvFeatureEvaluator::setImage(img, clsLabel, idx); }
+  float operator()(int varIdx, int sampleIdx) const override { return cachedValue(varIdx, sampleIdx); }
+  void writeFeatures(cv::FileStorage& fs, const cv::Mat& featureMap) const override;
+
+  class Feature {  // HOGfeatures.h:59-76: a block of 2x2 cells
+   public:
+    Feature();
+    Feature(int offset, int x, int y, int cellW, int cellH);
+    void write(cv::FileStorage& fs) const;
+    void write(cv::FileStorage& fs, int featComponentIdx) const;
+    cv::Rect rect[N_CELLS];
+    struct {
+      int p0, p1, p2, p3;
+    } fastRect[N_CELLS];
+  };
+  Feature featureAt(int fi) const;
+
+ protected:
+  void generateFeatures() override;
+  int featureType() const override { return CvFeatureParams::HOG; }
+  int numVariables() const override { return numFeatures * N_BINS * N_CELLS; }
 };
 
 namespace ccamd {

@@ -325,9 +325,10 @@ bool CvFeatureParams::read(const cv::FileNode& node) {  // features.cpp:53-60
   return maxCatCount >= 0 && featSize >= 1;
 }
 
-cv::Ptr<CvFeatureParams> CvFeatureParams::create(int featureType) {  // features.cpp:62-68 (HOG: outside this path)
+cv::Ptr<CvFeatureParams> CvFeatureParams::create(int featureType) {  // features.cpp:62-68
   return featureType == HAAR ? cv::Ptr<CvFeatureParams>(new CvHaarFeatureParams)
          : featureType == LBP ? cv::Ptr<CvFeatureParams>(new CvLBPFeatureParams)
+         : featureType == HOG ? cv::Ptr<CvFeatureParams>(new CvHOGFeatureParams)
                               : cv::Ptr<CvFeatureParams>();
 }
 
@@ -383,6 +384,12 @@ bool CvHaarFeatureParams::scanAttr(const std::string prmName, const std::string 
 CvLBPFeatureParams::CvLBPFeatureParams() {  // lbpfeatures.cpp:9-13
   maxCatCount = 256;
   name = LBPF_NAME;
+}
+
+CvHOGFeatureParams::CvHOGFeatureParams() {  // HOGfeatures.cpp:9-14
+  maxCatCount = 0;
+  name = HOGF_NAME;
+  featSize = N_BINS * N_CELLS;
 }
 
 // ---------------------------------------------------------------- evaluator base
@@ -457,14 +464,14 @@ void CvFeatureEvaluator::calcBatchSorted(int fiBegin, int fiEnd, int nSamples, f
 
 float CvFeatureEvaluator::cachedValue(int featureIdx, int sampleIdx) const {
   CV_Assert(sampleIdx >= 0 && sampleIdx < maxSampleCount);
-  CV_Assert(featureIdx >= 0 && featureIdx < numFeatures);
+  CV_Assert(featureIdx >= 0 && featureIdx < numVariables());
   if (lastSetMirrored && sampleIdx == lastSetIdx) {  // the window set last: the library answers from its host mirror
     float v = 0.f;
     check(cc_eval_calc(h, featureIdx, sampleIdx, &v), "CvFeatureEvaluator::operator()");
     return v;
   }
   ValueCache& c = g_cache;
-  const ccamd::ValueCacheIndex::Access a = c.ix.access(featureIdx, sampleIdx, uid, generation, lastSetIdx, numFeatures);
+  const ccamd::ValueCacheIndex::Access a = c.ix.access(featureIdx, sampleIdx, uid, generation, lastSetIdx, numVariables());
   try {
     switch (a) {
       case ccamd::ValueCacheIndex::HIT_ROW:
@@ -492,6 +499,7 @@ float CvFeatureEvaluator::cachedValue(int featureIdx, int sampleIdx) const {
 cv::Ptr<CvFeatureEvaluator> CvFeatureEvaluator::create(int type) {  // features.cpp:91-97
   return type == CvFeatureParams::HAAR  ? cv::Ptr<CvFeatureEvaluator>(new CvHaarEvaluator)
          : type == CvFeatureParams::LBP ? cv::Ptr<CvFeatureEvaluator>(new CvLBPEvaluator)
+         : type == CvFeatureParams::HOG ? cv::Ptr<CvFeatureEvaluator>(new CvHOGEvaluator)
                                         : cv::Ptr<CvFeatureEvaluator>();
 }
 
@@ -710,3 +718,61 @@ void CascadeClassifier::detectMultiScale(const cv::Mat& image, std::vector<cv::R
 }
 
 }  // namespace ccamd
+
+// ---------------------------------------------------------------- HOG
+void CvHOGEvaluator::init(const CvFeatureParams* _featureParams, int _maxSampleCount, cv::Size _winSize) {
+  CV_Assert(_maxSampleCount > 0);  // HOGfeatures.cpp:18
+  CvFeatureEvaluator::init(_featureParams, _maxSampleCount, _winSize);
+}
+
+void CvHOGEvaluator::generateFeatures() { numFeatures = cc_eval_num_features(h); }  // blocks; catalog built by the library
+
+CvHOGEvaluator::Feature CvHOGEvaluator::featureAt(int fi) const {
+  int32_t c[16];
+  check(cc_eval_hog_feature_geometry(h, fi, c), "CvHOGEvaluator::featureAt");
+  return Feature(winSize.width + 1, c[0], c[1], c[2], c[3]);
+}
+
+// HOGfeatures.cpp:49-65: one {rect: [x y w h componentIdx]} per used variable, with cell 0's rect
+void CvHOGEvaluator::writeFeatures(cv::FileStorage& fs, const cv::Mat& featureMap) const {
+  const int fsz = N_BINS * N_CELLS;
+  fs << FEATURES << "[";
+  for (int fi = 0; fi < featureMap.cols; fi++)
+    if (featureMap.at<int>(0, fi) >= 0) {
+      fs << "{";
+      featureAt(fi / fsz).write(fs, fi % fsz);
+      fs << "}";
+    }
+  fs << "]";
+}
+
+CvHOGEvaluator::Feature::Feature() {  // HOGfeatures.cpp:108-118
+  for (int i = 0; i < N_CELLS; i++) {
+    rect[i] = cv::Rect(0, 0, 0, 0);
+    fastRect[i].p0 = fastRect[i].p1 = fastRect[i].p2 = fastRect[i].p3 = 0;
+  }
+}
+
+CvHOGEvaluator::Feature::Feature(int offset, int x, int y, int cellW, int cellH) {  // HOGfeatures.cpp:120-131
+  rect[0] = cv::Rect(x, y, cellW, cellH);
+  rect[1] = cv::Rect(x + cellW, y, cellW, cellH);
+  rect[2] = cv::Rect(x, y + cellH, cellW, cellH);
+  rect[3] = cv::Rect(x + cellW, y + cellH, cellW, cellH);
+  for (int i = 0; i < N_CELLS; i++) {  // CV_SUM_OFFSETS
+    const cv::Rect& r = rect[i];
+    fastRect[i].p0 = r.x + offset * r.y;
+    fastRect[i].p1 = r.x + r.width + offset * r.y;
+    fastRect[i].p2 = r.x + offset * (r.y + r.height);
+    fastRect[i].p3 = r.x + r.width + offset * (r.y + r.height);
+  }
+}
+
+void CvHOGEvaluator::Feature::write(cv::FileStorage& fs) const {  // HOGfeatures.cpp:133-141
+  fs << CC_RECTS << "[";
+  for (const auto& r : rect) fs << "[:" << r.x << r.y << r.width << r.height << "]";
+  fs << "]";
+}
+
+void CvHOGEvaluator::Feature::write(cv::FileStorage& fs, int featComponentIdx) const {  // HOGfeatures.cpp:155-160
+  fs << CC_RECT << "[:" << rect[0].x << rect[0].y << rect[0].width << rect[0].height << featComponentIdx << "]";
+}

@@ -557,6 +557,7 @@ cc_status eval_device(cc_evaluator* e) {
 
 cc_status launch_batch(cc_evaluator* e, bool haar, const void* feats, int fb, int fe, const int32_t* d_idx, int ns,
                        float* d_out_ptr, int normalized, size_t out_pitch) {
+  if (e->type == CC_FEATURE_HOG) return hog_launch_batch(e, fb, fe, d_idx, ns, d_out_ptr, out_pitch);  // fb, fe: variables
   BatchArgs A;
   A.sum = e->d_sum.p;
   A.tilted = e->use_tilted ? e->d_tilted.p : nullptr;
@@ -638,6 +639,12 @@ cc_status flush_pending_images(cc_evaluator* e) {
   for (int i = 0; i < n;) {
     int j = i + 1;
     while (j < n && e->pend_idx[(size_t)order[(size_t)j]] == e->pend_idx[(size_t)order[(size_t)j - 1]] + 1) j++;
+    if (e->type == CC_FEATURE_HOG) {
+      if (cc_status st = hog_launch_set_images(e, e->d_imgs.p + (size_t)i * px, j - i, e->pend_idx[(size_t)order[(size_t)i]]); st != CC_OK)
+        return st;
+      i = j;
+      continue;
+    }
     hipLaunchKernelGGL(k_set_images, dim3(j - i), dim3(64), lds, e->stream, e->d_imgs.p + (size_t)i * px, e->W, e->H,
                        e->pend_idx[(size_t)order[(size_t)i]], e->d_sum.p, e->use_tilted ? e->d_tilted.p : nullptr, e->d_nf.p,
                        e->type == CC_FEATURE_HAAR ? 1 : 0);
@@ -766,8 +773,7 @@ cc_status cc_debug_division_check(int device, uint64_t n_pairs, uint64_t seed, u
 cc_status cc_eval_create(int feature_type, int haar_mode, int win_w, int win_h, int max_samples, int device, cc_evaluator** out) {
   if (!out) return set_error(CC_ERR_INVALID_ARG, "cc_eval_create: null output");
   *out = nullptr;
-  if (feature_type == CC_FEATURE_HOG) return set_error(CC_ERR_UNSUPPORTED, "cc_eval_create: HOG is outside the accelerated path");
-  if (feature_type != CC_FEATURE_HAAR && feature_type != CC_FEATURE_LBP) return set_error(CC_ERR_INVALID_ARG, "cc_eval_create: unknown feature type %d", feature_type);
+  if (feature_type != CC_FEATURE_HAAR && feature_type != CC_FEATURE_LBP && feature_type != CC_FEATURE_HOG) return set_error(CC_ERR_INVALID_ARG, "cc_eval_create: unknown feature type %d", feature_type);
   if (max_samples <= 0) return set_error(CC_ERR_INVALID_ARG, "cc_eval_create: maxSampleCount must be > 0");  // features.cpp:75
   if (win_w < 3 || win_h < 3 || win_w > 256 || win_h > 256) return set_error(CC_ERR_INVALID_ARG, "cc_eval_create: window %dx%d out of range", win_w, win_h);
   if (feature_type == CC_FEATURE_HAAR && (haar_mode < CC_HAAR_BASIC || haar_mode > CC_HAAR_ALL))
@@ -784,6 +790,16 @@ cc_status cc_eval_create(int feature_type, int haar_mode, int win_w, int win_h, 
   cc_status st = eval_device(e.get());
   if (st != CC_OK) return st;
   e->cls.assign((size_t)max_samples, 0.f);
+  if (feature_type == CC_FEATURE_HOG) {  // haar_mode is ignored; planes and catalog in cc_hog.hip
+    CC_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    CC_HIP(hipEventCreate(&e->ev_a));
+    CC_HIP(hipEventCreate(&e->ev_b));
+    st = hog_init(e.get());
+    if (st != CC_OK) return st;
+    CC_HIP(hipStreamSynchronize(e->stream));
+    *out = e.release();
+    return CC_OK;
+  }
   // samples per LDS tile: largest power of two (<= 32) that keeps the tile within 80 KB (two blocks per CU). With 32
   // samples per tile each 32-lane half of a wavefront is one feature over 32 consecutive samples: LDS reads are
   // conflict-free and every output store is a full 128-byte line.
@@ -838,13 +854,18 @@ void cc_eval_destroy(cc_evaluator* e) {
   delete e;
 }
 
-int cc_eval_num_features(const cc_evaluator* e) { return e ? e->nfeat : 0; }
+int cc_eval_num_features(const cc_evaluator* e) {
+  if (!e) return 0;
+  return e->type == CC_FEATURE_HOG ? (int)(e->hog_blocks.size() / 4) : e->nfeat;  // HOG: blocks (HOGfeatures.cpp:105)
+}
 int cc_eval_max_cat_count(const cc_evaluator* e) { return e && e->type == CC_FEATURE_LBP ? 256 : 0; }
-int cc_eval_feature_size(const cc_evaluator* e) { return e ? 1 : 0; }
+int cc_eval_feature_size(const cc_evaluator* e) { return e ? (e->type == CC_FEATURE_HOG ? 36 : 1) : 0; }  // N_BINS * N_CELLS
 const float* cc_eval_labels(const cc_evaluator* e) { return e ? e->cls.data() : nullptr; }
 
 cc_status cc_eval_feature_geometry(const cc_evaluator* e, int fi, int32_t* rects, float* weights, int* tilted) {
   if (!e || !rects) return set_error(CC_ERR_INVALID_ARG, "cc_eval_feature_geometry: null argument");
+  if (e->type == CC_FEATURE_HOG)  // four cells do not fit the 3-rect output: cc_eval_hog_feature_geometry
+    return set_error(CC_ERR_INVALID_ARG, "cc_eval_feature_geometry: HOG evaluator, use cc_eval_hog_feature_geometry");
   if (fi < 0 || fi >= e->nfeat) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_feature_geometry: feature %d out of range (%d)", fi, e->nfeat);
   if (e->type == CC_FEATURE_HAAR) {
     std::memcpy(rects, e->haar[fi].r, sizeof(int32_t) * 12);
@@ -869,9 +890,14 @@ cc_status cc_eval_set_images(cc_evaluator* e, const uint8_t* imgs, int n, int fi
   const size_t bytes = (size_t)n * e->W * e->H;
   CC_HIP(e->d_imgs.ensure(bytes));
   CC_HIP(hipMemcpyAsync(e->d_imgs.p, imgs, bytes, hipMemcpyHostToDevice, e->stream));
-  const size_t lds = (size_t)e->H * (e->W + 1) * 4;
-  hipLaunchKernelGGL(k_set_images, dim3(n), dim3(64), lds, e->stream, e->d_imgs.p, e->W, e->H, first_idx, e->d_sum.p,
-                     e->use_tilted ? e->d_tilted.p : nullptr, e->d_nf.p, e->type == CC_FEATURE_HAAR ? 1 : 0);
+  if (e->type == CC_FEATURE_HOG) {
+    st = hog_launch_set_images(e, e->d_imgs.p, n, first_idx);
+    if (st != CC_OK) return st;
+  } else {
+    const size_t lds = (size_t)e->H * (e->W + 1) * 4;
+    hipLaunchKernelGGL(k_set_images, dim3(n), dim3(64), lds, e->stream, e->d_imgs.p, e->W, e->H, first_idx, e->d_sum.p,
+                       e->use_tilted ? e->d_tilted.p : nullptr, e->d_nf.p, e->type == CC_FEATURE_HAAR ? 1 : 0);
+  }
   CC_HIP(hipGetLastError());
   CC_HIP(hipStreamSynchronize(e->stream));
   if (labels)
@@ -911,7 +937,10 @@ cc_status cc_eval_set_image(cc_evaluator* e, const uint8_t* img, size_t row_stri
   uint8_t* dst = e->pend_px.data() + (size_t)slot * px;
   for (int y = 0; y < e->H; y++) std::memcpy(dst + (size_t)y * e->W, img + (size_t)y * row_stride, (size_t)e->W);
   e->mirror_idx = -1;
-  host_window_integrals(e, dst, e->mirror_sum, e->mirror_tilted, e->mirror_nf);
+  if (e->type == CC_FEATURE_HOG)
+    hog_host_planes(e, dst, e->mirror_hog);
+  else
+    host_window_integrals(e, dst, e->mirror_sum, e->mirror_tilted, e->mirror_nf);
   e->mirror_idx = idx;
   e->cls[(size_t)idx] = (float)cls_label;
   return CC_OK;
@@ -1046,7 +1075,14 @@ cc_status cc_eval_calc_batch_sorted(cc_evaluator* e, int fi_begin, int fi_end, i
 cc_status cc_eval_calc(cc_evaluator* e, int fi, int si, float* out) {
   if (!e || !out) return set_error(CC_ERR_INVALID_ARG, "cc_eval_calc: null argument");
   if (si < 0 || si >= e->max_samples) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_calc: sample %d out of range (%d)", si, e->max_samples);
-  if (si == e->mirror_idx) {  // the window set last by cc_eval_set_image: answered from its host mirror, no launch
+  if (e->type == CC_FEATURE_HOG) {  // the mirror is read under mu (cc_eval_set_image rewrites it under mu)
+    if (fi < 0 || fi >= e->nfeat) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_calc: variable %d out of range (%d)", fi, e->nfeat);
+    std::unique_lock<std::mutex> lk(e->mu);
+    if (si == e->mirror_idx) {
+      *out = hog_host_value(e, e->mirror_hog.data(), fi);
+      return CC_OK;
+    }
+  } else if (si == e->mirror_idx) {  // the window set last by cc_eval_set_image: answered from its host mirror, no launch
     if (fi < 0 || fi >= e->nfeat) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_calc: feature %d out of range (%d)", fi, e->nfeat);
     host_catalog(e);
     *out = host_mirror_value(e, fi);
@@ -1063,7 +1099,13 @@ cc_status cc_eval_calc_list(cc_evaluator* e, const int32_t* feature_idx, int n_f
   for (int i = 0; i < n_feats; i++)
     if (feature_idx[i] < 0 || feature_idx[i] >= e->nfeat)
       return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_calc_list: feature %d out of range (%d)", feature_idx[i], e->nfeat);
-  if (si == e->mirror_idx) {  // see cc_eval_calc
+  if (e->type == CC_FEATURE_HOG) {  // see cc_eval_calc
+    std::unique_lock<std::mutex> lk(e->mu);
+    if (si == e->mirror_idx) {
+      for (int i = 0; i < n_feats; i++) out[i] = hog_host_value(e, e->mirror_hog.data(), feature_idx[i]);
+      return CC_OK;
+    }
+  } else if (si == e->mirror_idx) {  // see cc_eval_calc
     host_catalog(e);
     for (int i = 0; i < n_feats; i++) out[i] = host_mirror_value(e, feature_idx[i]);
     return CC_OK;
@@ -1075,6 +1117,16 @@ cc_status cc_eval_calc_list(cc_evaluator* e, const int32_t* feature_idx, int n_f
   std::lock_guard<std::mutex> lk(e->mu);
   st = flush_pending_images(e);
   if (st != CC_OK) return st;
+  if (e->type == CC_FEATURE_HOG) {
+    CC_HIP(e->d_idx.ensure((size_t)n_feats));
+    CC_HIP(e->d_out.ensure((size_t)n_feats));
+    CC_HIP(hipMemcpyAsync(e->d_idx.p, feature_idx, (size_t)n_feats * 4, hipMemcpyHostToDevice, e->stream));
+    st = hog_launch_list(e, e->d_idx.p, n_feats, si, e->d_out.p);
+    if (st != CC_OK) return st;
+    CC_HIP(hipMemcpyAsync(out, e->d_out.p, (size_t)n_feats * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    CC_HIP(hipStreamSynchronize(e->stream));
+    return CC_OK;
+  }
   if (haar && !e->d_haar_plain.p) {  // catalog with plain row offsets (row stride W + 1), built once
     std::vector<HaarFeatDev> dev(e->haar.size());
     for (size_t i = 0; i < dev.size(); i++) haar_to_dev(e->haar[i], e->W + 1, dev[i]);
@@ -1197,6 +1249,7 @@ cc_status cc_haar_feature_calc(int device, const cc_haar_feature* feats, int n_f
 cc_status cc_eval_get_sample(cc_evaluator* e, int idx, int32_t* sum, int32_t* tilted, float* normfactor) {
   if (!e) return set_error(CC_ERR_INVALID_ARG, "cc_eval_get_sample: null evaluator");
   if (idx < 0 || idx >= e->max_samples) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_get_sample: idx %d out of range", idx);
+  if (e->type == CC_FEATURE_HOG) return set_error(CC_ERR_INVALID_ARG, "cc_eval_get_sample: HOG evaluator, use cc_eval_get_hog_sample");
   cc_status st = eval_device(e);
   if (st != CC_OK) return st;
   std::lock_guard<std::mutex> lk(e->mu);

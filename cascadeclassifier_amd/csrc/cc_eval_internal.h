@@ -92,6 +92,19 @@ cc_status launch_batch(cc_evaluator* e, bool haar, const void* feats, int fb, in
 // Every entry point that reads stored samples on the device calls it first. Caller holds e->mu.
 cc_status flush_pending_images(cc_evaluator* e);
 
+// HOG (cc_hog.hip). Catalog blocks as (x, y, cell w, cell h); variables are block * 36 + cell * 9 + bin.
+void hog_catalog(int W, int H, std::vector<int32_t>& blocks);
+// Builds the catalog, sets nfeat to the variable count and allocates the planes. Called by cc_eval_create.
+cc_status hog_init(cc_evaluator* e);
+// setImage of n images already on the device (e->stream), samples [first_idx, first_idx + n). Caller holds e->mu.
+cc_status hog_launch_set_images(cc_evaluator* e, const uint8_t* d_imgs, int n, int first_idx);
+// operator() for variables [vb, ve) x ns samples into d_out[(vi - vb) * pitch + s] (pitch 0 = ns). Caller holds e->mu.
+cc_status hog_launch_batch(cc_evaluator* e, int vb, int ve, const int32_t* d_idx, int ns, float* d_out, size_t out_pitch);
+cc_status hog_launch_list(cc_evaluator* e, const int32_t* d_list, int n, int si, float* d_out);
+// Host mirror: the ten planes of one window ([cols][10], the device layout) and one variable's value on them.
+void hog_host_planes(const cc_evaluator* e, const uint8_t* px, std::vector<float>& planes);
+float hog_host_value(const cc_evaluator* e, const float* planes, int vi);
+
 }  // namespace ccamd
 
 struct cc_evaluator {
@@ -152,6 +165,13 @@ struct cc_evaluator {
   std::once_flag host_catalog_once;
   std::vector<HaarFeatDev> h_haar;  // catalog with plain fastRect offsets (row stride W + 1)
   std::vector<LbpFeatDev> h_lbp;
+  // HOG (cc_hog.hip): catalog blocks [n][4] = x, y, cell w, cell h; planes [max_samples][cols][10] (9 bins, then norm);
+  // nfeat counts variables (blocks * 36). mirror_hog is the host mirror of the last window, read and written under mu.
+  std::vector<int32_t> hog_blocks;
+  EBuf<int32_t> d_hog_blocks;
+  EBuf<float> d_hog;
+  int hog_planes_per_pass = 0;
+  std::vector<float> mirror_hog;
   ~cc_evaluator() {
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);

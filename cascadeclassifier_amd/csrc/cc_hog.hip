@@ -1,0 +1,394 @@
+// HOG feature evaluator on gfx950: batched setImage (gradient, orientation bin, ten float integral planes per sample) and
+// bulk operator() over (variable range x samples). Replaces CvHOGEvaluator (traincascade/lib/include/HOGfeatures.h:43-112,
+// traincascade/lib/src/HOGfeatures.cpp:16-256) behind section 4 of the C ABI.
+//
+// Plane layout in HBM: [max_samples][(W+1)*(H+1)][10] float, the ten planes of one integral entry side by side: channels
+// 0..8 are the per-bin integral histograms (`hist[bin]`), channel 9 is the magnitude integral (`normSum`). 40 * (W+1)(H+1)
+// bytes per sample (43 560 at 32x32). A variable reads one bin at the four corners of a cell; the 36 variables of a block
+// read the 9 bins at the block's 3x3 corner lattice plus the norm at its 4 outer corners, so one (sample, block) is 9
+// lattice points x 40 contiguous bytes: 45 eight-byte loads per lane instead of 288 scattered reads.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <mutex>
+
+#include "cc_eval_internal.h"
+
+namespace ccamd {
+
+// ------------------------------------------------------------------------------------------------
+// Per-pixel gradient and orientation bin (HOGfeatures.cpp:209-231). One definition for the device kernels and the host
+// mirror: every operation is an IEEE basic operation or an explicit fused multiply-add, so both give the same bits.
+// ------------------------------------------------------------------------------------------------
+// cv::cartToPolar(..., false) -> hal::fastAtan32f (OpenCV 4.6.0, core/src/mathfuncs_core.simd.hpp): polynomial
+// coefficients atan2_p1..p7 pre-scaled to degrees, each product rounded to float.
+constexpr float kHogP1 = 0.9997878412794807f * (float)(180 / M_PI);
+constexpr float kHogP3 = -0.3258083974640975f * (float)(180 / M_PI);
+constexpr float kHogP5 = 0.1555786518463281f * (float)(180 / M_PI);
+constexpr float kHogP7 = -0.04432655554792128f * (float)(180 / M_PI);
+
+__host__ __device__ inline float hog_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// dx, dy: integer central differences in [-255, 255]. Writes the magnitude and returns the bin in [0, 9).
+__host__ __device__ inline int hog_grad_bin(int dx, int dy, float* mag) {
+  const float fx = (float)dx, fy = (float)dy;
+  *mag = sqrtf(fx * fx + fy * fy);  // hal::magnitude32f; dx^2 + dy^2 < 2^24 is exact in float
+  // v_atan_f32::compute: the SIMD body (v_fma, fused on AVX2 / NEON dispatch) is the form restated here
+  const float ax = fabsf(fx), ay = fabsf(fy);
+  const float c = fminf(ax, ay) / (fmaxf(ax, ay) + (float)DBL_EPSILON);
+  const float cc = c * c;
+  float a = hog_fma(hog_fma(hog_fma(cc, kHogP7, kHogP5), cc, kHogP3), cc, kHogP1) * c;
+  if (ax < ay) a = 90.f - a;
+  if (fx < 0.f) a = 180.f - a;
+  if (fy < 0.f) a = 360.f - a;
+  const float angle = a * (float)(M_PI / 180);  // fastAtan32f's scale for radians
+  // HOGfeatures.cpp:218-226: angleScale = (float)(nbins / CV_PI); cvFloor(angle * angleScale - 0.5f), wrapped once
+  const float t = angle * (float)(9 / M_PI) - 0.5f;
+  int b = (int)floorf(t);
+  if (b < 0)
+    b += 9;
+  else if (b >= 9)
+    b -= 9;
+  return b;
+}
+
+// operator() of one variable (HOGfeatures.h:84-112) on one sample's interleaved planes. Lattice point (i, j) of the block
+// (i, j in 0..2 along x, y) is entry (y + j * ch) * (W + 1) + x + i * cw.
+__host__ __device__ inline float hog_value_from(float res, float nf) { return res > 0.001f ? res / (nf + 0.001f) : 0.f; }
+
+__host__ __device__ inline float hog_var_value(const float* planes, int sw, const int32_t* blk /* x, y, cw, ch */, int comp) {
+  const int cell = comp / 9, bin = comp % 9;
+  const int x = blk[0], y = blk[1], cw = blk[2], ch = blk[3];
+  const int cx = x + (cell & 1) * cw, cy = y + (cell >> 1) * ch;
+  auto at = [&](int px, int py, int chn) { return planes[((size_t)py * sw + px) * 10 + chn]; };
+  const float res = ((at(cx, cy, bin) - at(cx + cw, cy, bin)) - at(cx, cy + ch, bin)) + at(cx + cw, cy + ch, bin);
+  // normFactor: fastRect[0].p0 - fastRect[1].p1 - fastRect[2].p2 + fastRect[3].p3, the block's outer corners
+  const float nf = ((at(x, y, 9) - at(x + 2 * cw, y, 9)) - at(x, y + 2 * ch, 9)) + at(x + 2 * cw, y + 2 * ch, 9);
+  return hog_value_from(res, nf);
+}
+
+// ------------------------------------------------------------------------------------------------
+// setImage for a batch: one block per sample.
+//   1. gradient magnitude and bin of every pixel into LDS (BORDER_REPLICATE: indices clamped);
+//   2. row pass, one lane per (plane, row): the running row sum in float, strictly left to right (the reference's
+//      `strSum += mag`; a parallel scan would reassociate), into LDS;
+//   3. column pass, one lane per (plane, column): integral(y + 1, x) = integral(y, x) + rowsum(y, x), top to bottom,
+//      written to HBM. Lanes of a wavefront cover consecutive (column, plane) pairs: contiguous stores.
+// Planes go through LDS `planes_per_pass` at a time (all ten up to ~40x40 windows at the 64 KB budget).
+// ------------------------------------------------------------------------------------------------
+constexpr int HOG_SET_THREADS = 256;
+
+__global__ __launch_bounds__(HOG_SET_THREADS) void k_hog_set_images(const uint8_t* __restrict__ imgs, int W, int H, int first_idx,
+                                                                    int planes_per_pass, float* __restrict__ planes) {
+  extern __shared__ float lds_f[];
+  const int sw = W + 1, cols = sw * (H + 1);
+  float* mag = lds_f;                                              // [H][W]
+  float* rp = lds_f + (size_t)W * H;                               // [P][H][W + 1], column 0 = 0
+  uint8_t* bins = reinterpret_cast<uint8_t*>(rp + (size_t)planes_per_pass * H * sw);  // [H][W]
+  const uint8_t* img = imgs + (size_t)blockIdx.x * W * H;
+  float* out = planes + (size_t)(first_idx + blockIdx.x) * cols * 10;
+  for (int i = threadIdx.x; i < W * H; i += HOG_SET_THREADS) {
+    const int y = i / W, x = i - y * W;
+    const int xl = max(x - 1, 0), xr = min(x + 1, W - 1), yu = max(y - 1, 0), yd = min(y + 1, H - 1);
+    const int dx = (int)img[y * W + xr] - (int)img[y * W + xl];
+    const int dy = (int)img[yd * W + x] - (int)img[yu * W + x];
+    float m;
+    bins[i] = (uint8_t)hog_grad_bin(dx, dy, &m);
+    mag[i] = m;
+  }
+  __syncthreads();
+  for (int c0 = 0; c0 < 10; c0 += planes_per_pass) {
+    const int P = min(planes_per_pass, 10 - c0);
+    for (int t = threadIdx.x; t < P * H; t += HOG_SET_THREADS) {
+      const int y = t / P, c = c0 + t % P;
+      float* row = rp + ((size_t)(c - c0) * H + y) * sw;
+      const float* mrow = mag + y * W;
+      const uint8_t* brow = bins + y * W;
+      float s = 0.f;
+      row[0] = 0.f;
+      if (c == 9) {
+        for (int x = 0; x < W; x++) {
+          s += mrow[x];
+          row[x + 1] = s;
+        }
+      } else {
+        for (int x = 0; x < W; x++) {
+          if (brow[x] == c) s += mrow[x];
+          row[x + 1] = s;
+        }
+      }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < P * sw; t += HOG_SET_THREADS) {
+      const int x = t / P, c = c0 + t % P;
+      const float* col = rp + (size_t)(c - c0) * H * sw + x;
+      float* o = out + (size_t)x * 10 + c;
+      float acc = 0.f;
+      o[0] = 0.f;
+      for (int y = 0; y < H; y++) {
+        acc = acc + col[(size_t)y * sw];
+        o[(size_t)(y + 1) * sw * 10] = acc;
+      }
+    }
+    __syncthreads();  // rp is rewritten by the next group of planes
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Bulk operator(): a wavefront owns 64 samples (lanes) and walks feature blocks; per block it loads the 3x3 lattice (9 x 10
+// floats) once and emits the block's variables that fall in [vi_begin, vi_end) to out[(vi - vi_begin) * pitch + s]:
+// for a fixed variable the 64 lanes store 256 contiguous bytes.
+// ------------------------------------------------------------------------------------------------
+constexpr int HOG_EVAL_THREADS = 256;
+
+struct HogBatchArgs {
+  const float* planes;
+  const int32_t* blocks;      // [num_blocks][4]: x, y, cell w, cell h
+  const int32_t* sample_idx;  // optional
+  int n_samples, sw, cols;
+  int vi_begin, vi_end;
+  int blk_begin, blk_end;     // blocks overlapping [vi_begin, vi_end)
+  int blks_per_chunk;
+  float* out;
+  size_t out_pitch;
+};
+
+__global__ __launch_bounds__(HOG_EVAL_THREADS) void k_hog_eval_batch(HogBatchArgs A) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  constexpr int WAVES = HOG_EVAL_THREADS / 64;
+  const int s = blockIdx.x * 64 + lane;
+  const bool valid = s < A.n_samples;
+  const int si = valid ? (A.sample_idx ? A.sample_idx[s] : s) : 0;
+  const float* base = A.planes + (size_t)si * A.cols * 10;
+  const int b0 = A.blk_begin + blockIdx.y * A.blks_per_chunk;
+  const int b1 = min(b0 + A.blks_per_chunk, A.blk_end);
+  float* out = A.out + s;
+  for (int b = b0 + wave; b < b1; b += WAVES) {
+    const int x = A.blocks[4 * b], y = A.blocks[4 * b + 1], cw = A.blocks[4 * b + 2], ch = A.blocks[4 * b + 3];
+    float h[9][10];  // lattice point (i, j) -> h[j * 3 + i][channel]
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const float2* p = reinterpret_cast<const float2*>(base + ((size_t)(y + j * ch) * A.sw + x + i * cw) * 10);
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+          const float2 v = p[k];
+          h[j * 3 + i][2 * k] = v.x;
+          h[j * 3 + i][2 * k + 1] = v.y;
+        }
+      }
+    const float nf = ((h[0][9] - h[2][9]) - h[6][9]) + h[8][9];
+    const int v0 = b * 36;
+#pragma unroll
+    for (int cell = 0; cell < 4; cell++) {
+      const int q = (cell >> 1) * 3 + (cell & 1);  // lattice index of the cell's top-left corner
+#pragma unroll
+      for (int bin = 0; bin < 9; bin++) {
+        const int vi = v0 + cell * 9 + bin;
+        if (vi < A.vi_begin || vi >= A.vi_end) continue;  // wave-uniform: ranges that start or end inside a block
+        const float res = ((h[q][bin] - h[q + 1][bin]) - h[q + 3][bin]) + h[q + 4][bin];
+        if (valid) out[(size_t)(vi - A.vi_begin) * A.out_pitch] = hog_value_from(res, nf);
+      }
+    }
+  }
+}
+
+// operator()(vi[k], one stored sample): one thread per list entry.
+__global__ void k_hog_eval_list(const float* __restrict__ planes, const int32_t* __restrict__ blocks, int sw,
+                                const int32_t* __restrict__ list, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int vi = list[i];
+  out[i] = hog_var_value(planes, sw, blocks + 4 * (vi / 36), vi % 36);
+}
+
+// Bin and magnitude of every (dx, dy) in [-255, 255]^2, pair (dx, dy) at (dy + 255) * 511 + dx + 255.
+__global__ void k_hog_bins(uint8_t* __restrict__ bin, float* __restrict__ mag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 511 * 511) return;
+  const int dy = i / 511 - 255, dx = i % 511 - 255;
+  float m;
+  bin[i] = (uint8_t)hog_grad_bin(dx, dy, &m);
+  mag[i] = m;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side
+// ------------------------------------------------------------------------------------------------
+// HOGfeatures.cpp:67-106: cell size t = 8, 16, ... while t <= W / 2; per t three block shapes (2t x 2t, 2t x 4t, 4t x 2t
+// in pixels; cells t x t, t x 2t, 2t x t), each placed with step 4, x outer and y inner.
+void hog_catalog(int W, int H, std::vector<int32_t>& blocks) {
+  blocks.clear();
+  for (int t = 8; t <= W / 2; t += 8) {
+    const int cell[3][2] = {{t, t}, {t, 2 * t}, {2 * t, t}};
+    for (const auto& c : cell)
+      for (int x = 0; x <= W - 2 * c[0]; x += 4)
+        for (int y = 0; y <= H - 2 * c[1]; y += 4) blocks.insert(blocks.end(), {x, y, c[0], c[1]});
+  }
+}
+
+static size_t hog_set_lds(int W, int H, int P) { return (size_t)W * H * 4 + (size_t)P * H * (W + 1) * 4 + (size_t)W * H; }
+
+cc_status hog_init(cc_evaluator* e) {
+  hog_catalog(e->W, e->H, e->hog_blocks);
+  e->nfeat = (int)(e->hog_blocks.size() / 4) * 36;  // the trainer's variable space (o_cvcascadeboosttraindata.cpp:246-247)
+  // planes per LDS pass: all ten within 64 KB where they fit, else as many as 160 KB (one block per CU) holds
+  for (size_t budget : {(size_t)64 * 1024, (size_t)160 * 1024}) {
+    int P = 10;
+    while (P > 0 && hog_set_lds(e->W, e->H, P) > budget) P--;
+    e->hog_planes_per_pass = P;
+    if (P > 0) break;
+  }
+  if (e->hog_planes_per_pass == 0)
+    return set_error(CC_ERR_UNSUPPORTED, "cc_eval_create: HOG window %dx%d too large for the setImage kernel's LDS", e->W, e->H);
+  const size_t lds = hog_set_lds(e->W, e->H, e->hog_planes_per_pass);
+  if (lds > 64 * 1024)
+    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hog_set_images), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  CC_HIP(e->d_hog.ensure((size_t)e->max_samples * e->cols * 10));
+  CC_HIP(hipMemsetAsync(e->d_hog.p, 0, (size_t)e->max_samples * e->cols * 10 * 4, e->stream));
+  CC_HIP(e->d_hog_blocks.ensure(std::max<size_t>(e->hog_blocks.size(), 4)));
+  if (!e->hog_blocks.empty())
+    CC_HIP(copy_sync(e->d_hog_blocks.p, e->hog_blocks.data(), e->hog_blocks.size() * 4, hipMemcpyHostToDevice, e->stream));
+  return CC_OK;
+}
+
+cc_status hog_launch_set_images(cc_evaluator* e, const uint8_t* d_imgs, int n, int first_idx) {
+  const size_t lds = hog_set_lds(e->W, e->H, e->hog_planes_per_pass);
+  hipLaunchKernelGGL(k_hog_set_images, dim3(n), dim3(HOG_SET_THREADS), lds, e->stream, d_imgs, e->W, e->H, first_idx,
+                     e->hog_planes_per_pass, e->d_hog.p);
+  CC_HIP(hipGetLastError());
+  return CC_OK;
+}
+
+cc_status hog_launch_batch(cc_evaluator* e, int vb, int ve, const int32_t* d_idx, int ns, float* d_out, size_t out_pitch) {
+  HogBatchArgs A;
+  A.planes = e->d_hog.p;
+  A.blocks = e->d_hog_blocks.p;
+  A.sample_idx = d_idx;
+  A.n_samples = ns;
+  A.sw = e->W + 1;
+  A.cols = e->cols;
+  A.vi_begin = vb;
+  A.vi_end = ve;
+  A.blk_begin = vb / 36;
+  A.blk_end = (ve + 35) / 36;
+  A.out = d_out;
+  A.out_pitch = out_pitch ? out_pitch : (size_t)ns;
+  const int nblk = A.blk_end - A.blk_begin, tiles = (ns + 63) / 64;
+  // chunks of blocks: enough workgroups for a few rounds over the chip, at least one block per wavefront
+  int chunks = std::max(1, std::min((nblk + 3) / 4, (256 * 8 + tiles - 1) / std::max(tiles, 1)));
+  A.blks_per_chunk = (nblk + chunks - 1) / chunks;
+  chunks = (nblk + A.blks_per_chunk - 1) / A.blks_per_chunk;
+  (void)hipEventRecord(e->ev_a, e->stream);
+  hipLaunchKernelGGL(k_hog_eval_batch, dim3(tiles, chunks), dim3(HOG_EVAL_THREADS), 0, e->stream, A);
+  (void)hipEventRecord(e->ev_b, e->stream);
+  CC_HIP(hipGetLastError());
+  return CC_OK;
+}
+
+cc_status hog_launch_list(cc_evaluator* e, const int32_t* d_list, int n, int si, float* d_out) {
+  hipLaunchKernelGGL(k_hog_eval_list, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->d_hog.p + (size_t)si * e->cols * 10,
+                     e->d_hog_blocks.p, e->W + 1, d_list, n, d_out);
+  CC_HIP(hipGetLastError());
+  return CC_OK;
+}
+
+// The ten planes of one window on the host, entry for entry what k_hog_set_images writes (same per-pixel function, same
+// sequential float sums; this translation unit is compiled with -ffp-contract=off).
+void hog_host_planes(const cc_evaluator* e, const uint8_t* px, std::vector<float>& planes) {
+  const int W = e->W, H = e->H, sw = W + 1;
+  std::vector<float> mag((size_t)W * H);
+  std::vector<uint8_t> bins((size_t)W * H);
+  for (int y = 0; y < H; y++)
+    for (int x = 0; x < W; x++) {
+      const int xl = std::max(x - 1, 0), xr = std::min(x + 1, W - 1), yu = std::max(y - 1, 0), yd = std::min(y + 1, H - 1);
+      const int dx = (int)px[y * W + xr] - (int)px[y * W + xl];
+      const int dy = (int)px[yd * W + x] - (int)px[yu * W + x];
+      bins[(size_t)y * W + x] = (uint8_t)hog_grad_bin(dx, dy, &mag[(size_t)y * W + x]);
+    }
+  planes.assign((size_t)e->cols * 10, 0.f);
+  for (int c = 0; c < 10; c++)
+    for (int y = 0; y < H; y++) {
+      float s = 0.f;
+      for (int x = 0; x < W; x++) {
+        if (c == 9 || bins[(size_t)y * W + x] == c) s += mag[(size_t)y * W + x];
+        planes[((size_t)(y + 1) * sw + x + 1) * 10 + c] = planes[((size_t)y * sw + x + 1) * 10 + c] + s;
+      }
+    }
+}
+
+float hog_host_value(const cc_evaluator* e, const float* planes, int vi) {
+  return hog_var_value(planes, e->W + 1, &e->hog_blocks[(size_t)(vi / 36) * 4], vi % 36);
+}
+
+}  // namespace ccamd
+
+using namespace ccamd;
+
+extern "C" {
+
+cc_status cc_eval_hog_feature_geometry(const cc_evaluator* e, int feature_idx, int32_t* cells) {
+  if (!e || !cells) return set_error(CC_ERR_INVALID_ARG, "cc_eval_hog_feature_geometry: null argument");
+  if (e->type != CC_FEATURE_HOG) return set_error(CC_ERR_INVALID_ARG, "cc_eval_hog_feature_geometry: evaluator is not HOG");
+  const int nb = (int)(e->hog_blocks.size() / 4);
+  if (feature_idx < 0 || feature_idx >= nb)
+    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_hog_feature_geometry: feature %d out of range (%d)", feature_idx, nb);
+  const int32_t* b = &e->hog_blocks[(size_t)feature_idx * 4];
+  for (int c = 0; c < 4; c++) {  // HOGfeatures.cpp:120-131: 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right
+    cells[4 * c] = b[0] + (c & 1) * b[2];
+    cells[4 * c + 1] = b[1] + (c >> 1) * b[3];
+    cells[4 * c + 2] = b[2];
+    cells[4 * c + 3] = b[3];
+  }
+  return CC_OK;
+}
+
+cc_status cc_eval_get_hog_sample(cc_evaluator* e, int idx, float* hist, float* norm) {
+  if (!e) return set_error(CC_ERR_INVALID_ARG, "cc_eval_get_hog_sample: null evaluator");
+  if (e->type != CC_FEATURE_HOG) return set_error(CC_ERR_INVALID_ARG, "cc_eval_get_hog_sample: evaluator is not HOG");
+  if (idx < 0 || idx >= e->max_samples) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_get_hog_sample: idx %d out of range", idx);
+  cc_status st = eval_device(e);
+  if (st != CC_OK) return st;
+  std::lock_guard<std::mutex> lk(e->mu);
+  st = flush_pending_images(e);  // the device's copy is what this call reports, also for a sample set a moment ago
+  if (st != CC_OK) return st;
+  std::vector<float> v((size_t)e->cols * 10);
+  CC_HIP(copy_sync(v.data(), e->d_hog.p + (size_t)idx * e->cols * 10, v.size() * 4, hipMemcpyDeviceToHost, e->stream));
+  for (int p = 0; p < e->cols; p++) {
+    if (hist)
+      for (int b = 0; b < 9; b++) hist[(size_t)b * e->cols + p] = v[(size_t)p * 10 + b];
+    if (norm) norm[p] = v[(size_t)p * 10 + 9];
+  }
+  return CC_OK;
+}
+
+cc_status cc_debug_hog_bins(int device, int32_t* n, uint8_t* bin, float* mag) {
+  if (!n || !bin || !mag) return set_error(CC_ERR_INVALID_ARG, "cc_debug_hog_bins: null output");
+  int nd = 0;
+  hipError_t err = hipGetDeviceCount(&nd);
+  if (err != hipSuccess || nd <= 0) return set_error(CC_ERR_NO_DEVICE, "no usable HIP device; this library has no CPU fallback");
+  if (device < 0 || device >= nd) return set_error(CC_ERR_INVALID_ARG, "device %d out of range (devices: %d)", device, nd);
+  CC_HIP(hipSetDevice(device));
+  constexpr int N = 511 * 511;
+  EBuf<uint8_t> d_bin;
+  EBuf<float> d_mag;
+  CC_HIP(d_bin.ensure(N));
+  CC_HIP(d_mag.ensure(N));
+  OwnStream own;  // not the legacy stream: see copy_sync
+  CC_HIP(own.create());
+  CC_HIP(hipMemsetAsync(d_bin.p, 0xFF, N, own.s));
+  CC_HIP(hipMemsetAsync(d_mag.p, 0, (size_t)N * 4, own.s));
+  hipLaunchKernelGGL(k_hog_bins, dim3((N + 255) / 256), dim3(256), 0, own.s, d_bin.p, d_mag.p);
+  CC_HIP(hipGetLastError());
+  CC_HIP(copy_sync(bin, d_bin.p, N, hipMemcpyDeviceToHost, own.s));
+  CC_HIP(copy_sync(mag, d_mag.p, (size_t)N * 4, hipMemcpyDeviceToHost, own.s));
+  *n = N;
+  return CC_OK;
+}
+
+}  // extern "C"

@@ -704,7 +704,7 @@ cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n
   st = flush_pending_images(e);
   if (st != CC_OK) return st;
   e->presort_n = 0;
-  const bool haar = e->type == CC_FEATURE_HAAR;
+  const bool haar = e->type != CC_FEATURE_LBP;  // HOG variables are ordered: the Haar tables (launch_batch dispatches HOG)
   const int F = fi_end - fi_begin, N = n_samples;
   const void* feats = haar ? (const void*)e->d_haar.p : (const void*)e->d_lbp.p;
   // variables per pass: whole groups of 64, at most 2^28 values per scratch array
@@ -862,7 +862,7 @@ cc_status cc_eval_find_best_split(cc_evaluator* e, const int32_t* sample_idx, in
     if (!(weights[i] >= 0.0)) return set_error(CC_ERR_INVALID_ARG, "cc_eval_find_best_split: weight of sample %d is negative or NaN", i);
   }
   std::lock_guard<std::mutex> lk(e->mu);
-  const bool haar = e->type == CC_FEATURE_HAAR;
+  const bool haar = e->type != CC_FEATURE_LBP;  // ordered variables (Haar, HOG)
   PinnedBuf& pin_in = e->pin_in;
   PinnedBuf& pin_out = e->pin_out;
   if (haar) {

@@ -22,17 +22,18 @@ def _vp(a):
 
 
 class CvFeatureParams:
-    """CvFeatureParams / CvHaarFeatureParams / CvLBPFeatureParams (haarfeatures.h:31-51, lbpfeatures.h:22-26)."""
+    """CvFeatureParams / CvHaarFeatureParams / CvLBPFeatureParams / CvHOGFeatureParams (haarfeatures.h:31-51,
+    lbpfeatures.h:22-26, HOGfeatures.cpp:9-14)."""
 
     def __init__(self, feature_type=HAAR, mode=BASIC):
         self.feature_type = feature_type
         self.mode = mode
         self.maxCatCount = 256 if feature_type == LBP else 0
-        self.featSize = 1
+        self.featSize = 36 if feature_type == HOG else 1  # HOG: N_BINS * N_CELLS variables per feature
 
     @staticmethod
     def create(feature_type):
-        return CvFeatureParams(feature_type) if feature_type in (HAAR, LBP) else None
+        return CvFeatureParams(feature_type) if feature_type in (HAAR, LBP, HOG) else None
 
 
 class CvFeatureEvaluator:
@@ -44,8 +45,10 @@ class CvFeatureEvaluator:
 
     @staticmethod
     def create(feature_type, device=0):
-        """features.cpp:91-97: unknown type -> empty Ptr (None here). HOG is outside the accelerated path."""
-        return CvFeatureEvaluator(feature_type, device) if feature_type in (HAAR, LBP) else None
+        """features.cpp:91-97: unknown type -> empty Ptr (None here). For HOG every feature index of the value methods
+        (__call__, calc_list, calc_batch*, presort, find_best_split's var_idx) is a variable index in
+        [0, getNumFeatures() * getFeatureSize())."""
+        return CvFeatureEvaluator(feature_type, device) if feature_type in (HAAR, LBP, HOG) else None
 
     def init(self, featureParams: CvFeatureParams, maxSampleCount: int, winSize):
         self._release()
@@ -131,7 +134,7 @@ class CvFeatureEvaluator:
         """Evaluate features [fi_begin, fi_end) (default: all) on stored samples [0, n_samples) and keep the sorted
         order (Haar) / the category codes (LBP) resident on the device; call again whenever the stored samples change."""
         n = self.maxSampleCount if n_samples is None else int(n_samples)
-        self._presorted = (int(fi_begin), self.getNumFeatures() if fi_end is None else int(fi_end))
+        self._presorted = (int(fi_begin), self.getNumVariables() if fi_end is None else int(fi_end))
         L.check(L.lib().cc_eval_presort_range(self._e, self._presorted[0], self._presorted[1], n))
 
     def find_best_split(self, weights, *, responses=None, class_labels=None, sample_idx=None, node_value=0.0,
@@ -150,7 +153,7 @@ class CvFeatureEvaluator:
             if a is not None and len(a) != n:
                 raise ValueError("responses / class_labels must hold one value per node sample")
         sp = L.Split()
-        nf = self._presorted[1] - self._presorted[0] if getattr(self, "_presorted", None) else self.getNumFeatures()
+        nf = self._presorted[1] - self._presorted[0] if getattr(self, "_presorted", None) else self.getNumVariables()
         q = np.empty(nf, np.float64) if per_var else None
         pt = np.empty(nf, np.int32) if per_var else None
         L.check(L.lib().cc_eval_find_best_split(self._e, _vp(idx), n, _vp(w), _vp(resp), _vp(lab), float(node_value), int(boost_type),
@@ -161,6 +164,10 @@ class CvFeatureEvaluator:
 
     def getNumFeatures(self) -> int:
         return L.lib().cc_eval_num_features(self._e)
+
+    def getNumVariables(self) -> int:
+        """The trainer's variable count, getNumFeatures() * getFeatureSize() (o_cvcascadeboosttraindata.cpp:246-247)."""
+        return self.getNumFeatures() * self.getFeatureSize()
 
     def getMaxCatCount(self) -> int:
         return L.lib().cc_eval_max_cat_count(self._e)
@@ -174,6 +181,11 @@ class CvFeatureEvaluator:
         return a if si is None else float(a[si])
 
     def feature_geometry(self, fi):
+        """Haar: (rects[3][4], weights[3], tilted); LBP: (cell,); HOG: cells[4][4] (x, y, w, h of cells 0..3)."""
+        if self.feature_type == HOG:
+            cells = np.zeros((4, 4), np.int32)
+            L.check(L.lib().cc_eval_hog_feature_geometry(self._e, int(fi), _vp(cells)))
+            return cells
         rects = np.zeros((3, 4), np.int32)
         w = np.zeros(3, np.float32)
         t = C.c_int(0)
@@ -181,6 +193,13 @@ class CvFeatureEvaluator:
         return (rects[0].copy(),) if self.feature_type == LBP else (rects, w, t.value)
 
     def get_sample(self, idx):
+        """Haar / LBP: (sum, tilted or None, norm factor or None); HOG: (hist[9, H+1, W+1], norm[H+1, W+1])."""
+        if self.feature_type == HOG:
+            shape = (self.winSize[1] + 1, self.winSize[0] + 1)
+            hist = np.empty((9,) + shape, np.float32)
+            norm = np.empty(shape, np.float32)
+            L.check(L.lib().cc_eval_get_hog_sample(self._e, int(idx), _vp(hist), _vp(norm)))
+            return hist, norm
         cols = (self.winSize[0] + 1) * (self.winSize[1] + 1)
         s = np.empty(cols, np.int32)
         haar = self.feature_type == HAAR

@@ -288,6 +288,15 @@ CC_API cc_status cc_group_rectangles(const cc_rect* rects, int n, int group_thre
  *    getNumFeatures/getMaxCatCount/getFeatureSize/getCls -> cc_eval_* getters
  *    writeFeatures needs only the geometry -> cc_eval_feature_geometry (haarfeatures.cpp:311-320, lbpfeatures.cpp:65-68)
  *    bulk consumer CvCascadeBoostTrainData::precalculate (o_cvcascadeboosttraindata.cpp:490-596) -> cc_eval_calc_batch.
+ *
+ *    HOG (CvHOGEvaluator, HOGfeatures.h:43-112, HOGfeatures.cpp:16-256): a feature is a block of 2x2 cells and carries
+ *    36 variables (4 cells x 9 orientation bins). cc_eval_num_features returns blocks, cc_eval_feature_size 36 and
+ *    cc_eval_max_cat_count 0 (every variable ordered). On a HOG evaluator EVERY feature index argument below is a
+ *    VARIABLE index vi in [0, num_features * 36): block vi / 36, cell (vi % 36) / 9, bin vi % 9. That covers cc_eval_calc,
+ *    cc_eval_calc_list, cc_eval_calc_batch, cc_eval_calc_batch_device, cc_eval_calc_batch_sorted, cc_eval_presort_range
+ *    and cc_split.var_idx. cc_eval_feature_geometry, cc_eval_get_sample and cc_eval_calc_custom_haar return
+ *    CC_ERR_INVALID_ARG on a HOG evaluator; HOG cascades are not loadable (cc_cascade_load_xml*), so detection, negative
+ *    mining and cc_eval_predict_cascade stay Haar / LBP.
  * ============================================================================================ */
 typedef struct cc_evaluator cc_evaluator;
 enum { CC_HAAR_BASIC = 0, CC_HAAR_CORE = 1, CC_HAAR_ALL = 2 };
@@ -296,10 +305,13 @@ CC_API cc_status cc_eval_create(int feature_type, int haar_mode, int win_w, int 
                                 cc_evaluator** out);
 CC_API void cc_eval_destroy(cc_evaluator* e);
 CC_API int cc_eval_num_features(const cc_evaluator* e);
-CC_API int cc_eval_max_cat_count(const cc_evaluator* e); /* 0 Haar, 256 LBP */
-CC_API int cc_eval_feature_size(const cc_evaluator* e);  /* 1 */
+CC_API int cc_eval_max_cat_count(const cc_evaluator* e); /* 0 Haar, 256 LBP, 0 HOG */
+CC_API int cc_eval_feature_size(const cc_evaluator* e);  /* 1; HOG: 36 */
 /* Haar: rects int32[3][4], weights float[3], *tilted; LBP: rects[0] = one cell (x y w h), weights/tilted untouched. */
 CC_API cc_status cc_eval_feature_geometry(const cc_evaluator* e, int fi, int32_t* rects, float* weights, int* tilted);
+/* HOG: cells int32[4][4] = x y w h of cell 0 (top-left), 1 (top-right), 2 (bottom-left), 3 (bottom-right) of block
+ * feature_idx (HOGfeatures.cpp:120-131). CC_ERR_INVALID_ARG on a Haar / LBP evaluator. */
+CC_API cc_status cc_eval_hog_feature_geometry(const cc_evaluator* e, int feature_idx, int32_t* cells);
 /* img: win_h rows of win_w bytes, row_stride bytes apart. idx < max_samples.
  * The call does no device work (the trainer makes it per candidate window, cascadeclassifier.cpp:340-347): the pixels are
  * queued -- a later image for the same idx replaces the queued one; the queue reaches the device, runs of consecutive indices
@@ -357,6 +369,13 @@ CC_API cc_status cc_haar_feature_calc(int device, const cc_haar_feature* feats, 
                                       const int32_t* tilted, int n_rows, int row_len, float* out);
 /* Cached per-sample data copied back for parity tests: sum / tilted are (win_w+1)*(win_h+1) int32. */
 CC_API cc_status cc_eval_get_sample(cc_evaluator* e, int idx, int32_t* sum, int32_t* tilted, float* normfactor);
+/* HOG: the integral histograms hist float[9][win_h+1][win_w+1] and the magnitude integral norm float[win_h+1][win_w+1] of
+ * stored sample idx (the reference's hist[bin] / normSum rows). Either output may be NULL. */
+CC_API cc_status cc_eval_get_hog_sample(cc_evaluator* e, int idx, float* hist, float* norm);
+/* Parity instrumentation for HOG: orientation bin and gradient magnitude of every (dx, dy) in [-255, 255]^2 computed on the
+ * device with the setImage kernel's per-pixel function; pair (dx, dy) at (dy + 255) * 511 + dx + 255. bin holds 261 121
+ * bytes, mag 261 121 floats; *n receives 261 121. */
+CC_API cc_status cc_debug_hog_bins(int device, int32_t* n, uint8_t* bin, float* mag);
 /* Training-side cascade predict (CvCascadeClassifier::predict, cascadeclassifier.cpp:297-306 ->
  * boost.cpp:461-477 -> o_cvcascadeboosttree.cpp:16-39) of a stump cascade over stored samples:
  * out[s] = 1 if every stage passes else 0. Feature indices of `c` index the cascade's own <features> list. */
@@ -430,7 +449,7 @@ CC_API cc_status cc_negminer_run_batch(cc_negminer* m, const uint8_t* const* ima
  * ============================================================================================ */
 typedef struct cc_split {
   int32_t found;       /* 1 if a split was found */
-  int32_t var_idx;     /* feature index (catalog order) */
+  int32_t var_idx;     /* feature index (catalog order); HOG: variable index */
   float quality;
   float ord_c;         /* ordered variables: threshold, samples with value <= ord_c go left */
   int32_t split_point; /* ordered variables: position of the last left sample in the node's sorted order */
