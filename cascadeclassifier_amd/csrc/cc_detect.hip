@@ -907,9 +907,7 @@ struct cc_detector {
   size_t lds = 0;  // dynamic LDS bytes per tile (larger of the two layouts)
   size_t lds_spec = 0;  // the same for the installed specialised kernel (smaller when its STEP-2 tiles hold 16-bit entries)
   size_t lds_extra = 0; // CCAMD_DEBUG_EXTRA_LDS (occupancy experiments)
-  int spec_tmode = 0;  // TILE_32 / TILE_16 / TILE_PAIR16 of the installed specialised kernel
   int spec_tile_y = TILE_Y;  // window rows per tile the installed specialised kernel was compiled for (spec_tile_rows)
-  DevBuf<HaarStumpP16> d_haar_p16, d_haar_p16w;  // table-driven stumps of the pair tile: stage order, wave-phase order
   // plans + workspace
   std::vector<std::unique_ptr<Plan>> plans;
   DevBuf<uint8_t> d_frames, d_pyr;
@@ -1215,9 +1213,9 @@ template <int STEP>
 static void build_lbp_stumps(const Cascade& m, std::vector<LbpStumpDev>& out);
 static void build_lbp_stumps16(const Cascade& m, std::vector<LbpStumpDev>& out);
 
-// Layout of the STEP-2 tiles of a specialised kernel: 32-bit entries in two column planes (TileGeom<2>), 16-bit entries
-// (TileGeom16), or packed pairs of 16-bit entries (TileGeomP: two neighbouring windows per LDS read, Haar stumps).
-enum { TILE_32 = 0, TILE_16 = 1, TILE_PAIR16 = 2 };
+// Layout of the STEP-2 tiles of a specialised kernel: 32-bit entries in two column planes (TileGeom<2>) or 16-bit entries
+// (TileGeom16).
+enum { TILE_32 = 0, TILE_16 = 1 };
 
 // A rectangle sum read from 16-bit entries is exact when 255 * area < 2^16.
 static bool fits16(long long area) { return 255LL * area <= 65535LL; }
@@ -1268,62 +1266,6 @@ static bool tile16_eligible(const Cascade& m, int n_stages) {
       if (!fits16((long long)r[2] * r[3])) return false;
     }
   return true;
-}
-
-// Table-driven records of the pair tile: every rectangle as strips whose sums fit 16 bits. False when a stump needs more
-// than P16_PIECES pieces or an offset does not fit the record.
-static bool build_haar_stumps_p16(const Cascade& m, std::vector<HaarStumpP16>& out) {
-  const TileGeomP G(m.win_w, m.win_h);
-  out.assign(m.stump_feature.size(), HaarStumpP16{});
-  for (size_t i = 0; i < out.size(); i++) {
-    HaarStumpP16& d = out[i];
-    std::memset(&d, 0, sizeof(d));
-    const int fi = m.stump_feature[i];
-    if (m.haar_tilted[(size_t)fi]) return false;
-    d.nrect = 2;
-    int np = 0;
-    for (int j = 0; j < 3; j++) {
-      const int32_t* r = &m.haar_rects[(size_t)fi * 12 + j * 4];
-      const float wt = m.haar_weights[(size_t)fi * 3 + j];
-      d.w[j] = wt;
-      const bool used = j < 2 || wt != 0.0f;
-      if (j == 2 && wt != 0.0f) d.nrect = 3;
-      if (!used || r[2] <= 0 || r[3] <= 0) continue;  // an empty rectangle sums to 0: no piece
-      const auto pcs = pieces16(r[0], r[1], r[2], r[3]);
-      if (pcs.empty()) return false;
-      for (const auto& pc : pcs) {
-        if (np >= P16_PIECES) return false;
-        const int o4[4] = {G.at(pc[1], pc[0]), G.at(pc[1], pc[0] + pc[2]), G.at(pc[1] + pc[3], pc[0]), G.at(pc[1] + pc[3], pc[0] + pc[2])};
-        for (int k = 0; k < 4; k++) {
-          if (o4[k] < 0 || o4[k] > 65535) return false;
-          d.ofs[np][k] = (unsigned short)o4[k];
-        }
-        d.rect_of[np++] = (unsigned char)j;
-      }
-    }
-    d.npieces = (unsigned char)np;
-    d.thr = m.stump_threshold[i];
-    d.left = m.stump_left[i];
-    d.right = m.stump_right[i];
-  }
-  return true;
-}
-
-// Can the specialised kernel use the pair tile (TileGeomP) for its STEP-2 tiles? Upright Haar stump cascades whose
-// variance rectangle splits into two halves that fit 16 bits, whose every stump fits the pair tile's record, and whose
-// tile row fits one wavefront of 4-column groups (stage_tile_pair). CCAMD_SPEC_PAIR16=0 / 1 turns it off / on.
-static bool pair16_eligible(const Cascade& m) {
-  if (m.feature_type != CC_FEATURE_HAAR || m.max_nodes_per_tree > 1 || m.has_tilted) return false;
-  const char* on = std::getenv("CCAMD_SPEC_PAIR16");
-  if (!(on && std::atoi(on) != 0)) return false;
-  if (TILE_Y != 2 * EVAL_WAVES || TILE_X != 64) return false;
-  const int nrx = m.win_w - 2, nry = m.win_h - 2;
-  if (nrx < 2 || !fits16((long long)(nrx - (nrx >> 1)) * nry)) return false;
-  if (!fits16(std::max(m.win_w, m.win_h))) return false;
-  const TileGeomP G(m.win_w, m.win_h);
-  if ((G.cols + 3) / 4 > 64) return false;
-  std::vector<HaarStumpP16> tmp;
-  return build_haar_stumps_p16(m, tmp);
 }
 
 static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) {
@@ -1377,7 +1319,6 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
     return mag / q < 2147483647.0;
   };
   std::function<std::string(const HaarStumpDev&, const std::string&, double, SpecStump&)> vote_text;
-  const TileGeomP GP(m.win_w, m.win_h);
   // `reuse`: words the stump evaluated just before this one holds in variables (tile offset -> name): a corner both stumps
   // read is not loaded again. `vars_out` receives this stump's own map for the next one.
   auto stump = [&](const HaarStumpDev& d, int stump_index, int local, const std::string& win, double fixed_q, bool h16,
@@ -1606,28 +1547,22 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
     if (delta_form && fixed_q > 0.) {
       char delta[64];
       const long long lq = (long long)std::llround((double)d.left / fixed_q), rq = (long long)std::llround((double)d.right / fixed_q);
-      // The delta reaches the select through a volatile move (left to itself the compiler hoists hundreds of these
-      // constant moves out of the stage loops and spills them), and the accumulator passes through an empty asm after
-      // every vote: integer adds are associative, and without it the compiler re-associates the chain of votes into a
-      // tree of partial sums that it then has to spill.
       snprintf(delta, sizeof(delta), "0x%08x", (unsigned)(lq - rq));
       char vote[512];
-      if (!std::getenv("CCAMD_SPEC_NO_CMPX")) {
-        // The vote as TWO vector instructions: v_cmpx narrows EXEC to the lanes with v < thr (threshold as a 32-bit
-        // literal operand), the delta is added under that mask (again a literal operand), and a scalar move puts EXEC back.
-        // The plain form below costs four (move of the delta into a register, compare, select, add) plus a scalar move of
-        // the threshold. `thr > v` is the comparison `v < thr` with the operands swapped: false for NaN either way.
-        // (A three-instruction form without EXEC traffic -- compare into VCC, v_cndmask of a literal delta against a zero
-        // register, add -- does not assemble: a VOP2 with a literal AND the implicit VCC read exceeds gfx9's constant bus.)
-        unsigned thr_bits;
-        std::memcpy(&thr_bits, &d.thr, 4);
-        snprintf(vote, sizeof(vote),
-                 "; v *= vnf%s; { unsigned long long sx; asm volatile(\"s_mov_b64 %%1, exec\\n\\tv_cmpx_gt_f32_e32 0x%08x, %%2\\n\\tv_add_u32_e32 %%0, %s, %%0\\n\\ts_mov_b64 exec, %%1\" "
-                 ": \"+v\"(ai%s), \"=&s\"(sx) : \"v\"(v) : \"vcc\"); } }",
-                 win.c_str(), thr_bits, delta, win.c_str());
-      } else
-      snprintf(vote, sizeof(vote), "; v *= vnf%s; { unsigned dq; asm volatile(\"v_mov_b32_e32 %%0, %s\" : \"=v\"(dq)); ai%s += (v < %s ? dq : 0u); asm volatile(\"\" : \"+v\"(ai%s)); } }",
-               win.c_str(), delta, win.c_str(), hexf(d.thr).c_str(), win.c_str());
+      // The vote as TWO vector instructions: v_cmpx narrows EXEC to the lanes with v < thr (threshold as a 32-bit literal
+      // operand), the delta is added under that mask (again a literal operand), and a scalar move puts EXEC back. A compare
+      // and select costs four (move of the delta into a register, compare, select, add) plus a scalar move of the threshold.
+      // `thr > v` is the comparison `v < thr` with the operands swapped: false for NaN either way. As asm the vote also keeps
+      // the compiler from hoisting hundreds of constant deltas out of the stage loops and from re-associating the chain of
+      // integer votes into a tree of partial sums, both of which it then has to spill.
+      // (A three-instruction form without EXEC traffic -- compare into VCC, v_cndmask of a literal delta against a zero
+      // register, add -- does not assemble: a VOP2 with a literal AND the implicit VCC read exceeds gfx9's constant bus.)
+      unsigned thr_bits;
+      std::memcpy(&thr_bits, &d.thr, 4);
+      snprintf(vote, sizeof(vote),
+               "; v *= vnf%s; { unsigned long long sx; asm volatile(\"s_mov_b64 %%1, exec\\n\\tv_cmpx_gt_f32_e32 0x%08x, %%2\\n\\tv_add_u32_e32 %%0, %s, %%0\\n\\ts_mov_b64 exec, %%1\" "
+               ": \"+v\"(ai%s), \"=&s\"(sx) : \"v\"(v) : \"vcc\"); } }",
+               win.c_str(), thr_bits, delta, win.c_str());
       out.base = (double)d.right;
       out.base_q = rq;
       return vote;
@@ -1640,131 +1575,7 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
     }
     return "; v *= vnf" + win + "; acc" + win + " += (double)(v < " + hexf(d.thr) + " ? " + hexf(d.left) + " : " + hexf(d.right) + "); }";
   };
-  // One stump for the two windows of a pair-tile slot (TileGeomP): every corner word is read once and holds both windows'
-  // entries, the corner combinations are packed 16-bit arithmetic, the two halves then go their own way (conversion,
-  // normalisation, vote) into acca / accb. Same cases as the 16-bit tile above.
-  auto stump_pair = [&](int stump_index, int local, double fixed_q) {
-    const HaarStumpDev& d = t[1][(size_t)stump_index];
-    const int fi = m.stump_feature[(size_t)stump_index];
-    bool int_ok = true;
-    double bound = 0;
-    for (int j = 0; j < d.nrect; j++) {
-      const float w = d.w[j];
-      const int32_t* r = &m.haar_rects[(size_t)fi * 12 + j * 4];
-      if (w != std::nearbyint(w) || std::fabs(w) > 64.f) int_ok = false;
-      bound += std::fabs((double)w) * 255.0 * (double)r[2] * (double)r[3];
-    }
-    if (bound >= 16777216.0) int_ok = false;
-    SpecStump out;
-    std::map<int, std::string> var;
-    auto var_of = [&](int ofs) {
-      auto it = var.find(ofs);
-      if (it != var.end()) return it->second;
-      snprintf(buf, sizeof(buf), "x%d_%d", local, (int)var.size());
-      const std::string name = buf;
-      var[ofs] = name;
-      out.decls += (out.decls.empty() ? "cc_us2 " : ", ") + name;
-      snprintf(buf, sizeof(buf), "%s = cc_pk(b[%d]); ", name.c_str(), ofs);
-      out.loads += buf;
-      return name;
-    };
-    long long vmin = 0, vmax = 0;
-    if (int_ok) {
-      std::vector<int> net((size_t)(m.win_w + 1) * (size_t)(m.win_h + 1), 0);
-      for (int j = 0; j < d.nrect; j++) {
-        const int32_t* r = &m.haar_rects[(size_t)fi * 12 + j * 4];
-        for (int yy = r[1]; yy < r[1] + r[3]; yy++)
-          for (int xx = r[0]; xx < r[0] + r[2]; xx++) net[(size_t)yy * (size_t)(m.win_w + 1) + (size_t)xx] += (int)d.w[j];
-      }
-      for (int v : net) (v > 0 ? vmax : vmin) += 255LL * v;
-    }
-    std::string pre, ea, eb;  // packed part, value of the first / second window
-    if (int_ok && vmin >= -32768 && vmax <= 32767) {
-      std::map<int, int> coef;
-      static const int sign[4] = {1, -1, -1, 1};
-      for (int j = 0; j < d.nrect; j++) {
-        const int32_t* r = &m.haar_rects[(size_t)fi * 12 + j * 4];
-        const int o4[4] = {GP.at(r[1], r[0]), GP.at(r[1], r[0] + r[2]), GP.at(r[1] + r[3], r[0]), GP.at(r[1] + r[3], r[0] + r[2])};
-        for (int k = 0; k < 4; k++) coef[o4[k]] += sign[k] * (int)d.w[j];
-      }
-      std::map<int, std::vector<int>> by_coef;
-      for (auto& kv : coef)
-        if (kv.second) by_coef[std::abs(kv.second)].push_back(kv.second > 0 ? kv.first + 1 : -(kv.first + 1));
-      std::string tt;
-      for (auto& g : by_coef) {
-        std::string grp;
-        for (int so : g.second) {
-          grp += so > 0 ? (grp.empty() ? "" : " + ") : " - ";
-          grp += var_of(std::abs(so) - 1);
-        }
-        if (grp.rfind(" - ", 0) == 0) grp = "cc_k2(0)" + grp;
-        if (g.first == 1)
-          tt += (tt.empty() ? "(" : " + (") + grp + ")";
-        else {
-          snprintf(buf, sizeof(buf), "%scc_k2(%d) * (", tt.empty() ? "" : " + ", g.first);
-          tt += buf + grp + ")";
-        }
-      }
-      if (tt.empty()) tt = "cc_k2(0)";
-      pre = "const cc_us2 t = " + tt + "; ";
-      ea = "(float)(int)(short)t.x";
-      eb = "(float)(int)(short)t.y";
-    } else {
-      std::string ia, ib, fa, fb;
-      int np = 0;
-      for (int j = 0; j < d.nrect; j++) {
-        const int32_t* r = &m.haar_rects[(size_t)fi * 12 + j * 4];
-        std::string ra, rb;
-        for (const auto& pc : pieces16(r[0], r[1], r[2], r[3])) {
-          const std::string a = var_of(GP.at(pc[1], pc[0])), b2 = var_of(GP.at(pc[1], pc[0] + pc[2])), c = var_of(GP.at(pc[1] + pc[3], pc[0])),
-                            dd = var_of(GP.at(pc[1] + pc[3], pc[0] + pc[2]));
-          snprintf(buf, sizeof(buf), "q%d", np++);
-          const std::string q = buf;
-          pre += "const cc_us2 " + q + " = " + a + " - " + b2 + " - " + c + " + " + dd + "; ";
-          ra += std::string(ra.empty() ? "" : " + ") + "(int)" + q + ".x";
-          rb += std::string(rb.empty() ? "" : " + ") + "(int)" + q + ".y";
-        }
-        if (ra.empty()) ra = rb = "0";
-        snprintf(buf, sizeof(buf), "%s%d * (", j ? " + " : "", (int)d.w[j]);
-        ia += buf + ra + ")";
-        ib += buf + rb + ")";
-        fa += std::string(j ? " + " : "") + hexf(d.w[j]) + " * (float)(" + ra + ")";
-        fb += std::string(j ? " + " : "") + hexf(d.w[j]) + " * (float)(" + rb + ")";
-      }
-      ea = int_ok ? "(float)(" + ia + ")" : fa;
-      eb = int_ok ? "(float)(" + ib + ")" : fb;
-    }
-    if (!out.decls.empty()) out.decls += ";";
-    SpecStump other;  // both windows vote with the same constants
-    out.compute = "{ " + pre + "{ float v = " + ea + vote_text(d, "a", fixed_q, out) + " { float v = " + eb + vote_text(d, "b", fixed_q, other) + " }";
-    return out;
-  };
   for (int step = 1; step <= 2; step++) {
-    if (step == 2 && tmode == TILE_PAIR16) {  // STEP-2 tiles hold window pairs: one function serves the dense and the thread phase
-      snprintf(buf, sizeof(buf),
-               "template <>\n__device__ %s void spec_stage_pair<2>(int st, int p_lo, int p_hi, const int32_t* b, float vnfa, float vnfb, double& "
-               "acc_a, double& acc_b) {\n  double acca = 0., accb = 0.;\n  switch (st) {\n",
-               spec_stage_inline_attr());
-      o += buf;
-      for (int s = 0; s < n_stages; s++) {
-        snprintf(buf, sizeof(buf), "    case %d: {\n", s);
-        o += buf;
-        std::vector<SpecStump> st;
-        double q = 0.;
-        const bool fixed = delta_form && fixed_point_ok && stage_quantum(s, q);
-        for (int i = 0; i < m.stage_ntrees[(size_t)s]; i++) st.push_back(stump_pair(m.stage_first[(size_t)s] + i, i, fixed ? q : 0.));
-        if (fixed) {
-          o += "      unsigned aia = 0u, aib = 0u;\n";
-          spec_emit_stage(o, st, depth, true, {"aia", "aib"}, true);
-          snprintf(buf, sizeof(buf), "      acca = (double)(int)aia * %a;\n      accb = (double)(int)aib * %a;\n", q, q);
-          o += buf;
-        } else
-          spec_emit_stage(o, st, depth, true, {"acca", "accb"});
-        o += "    } break;\n";
-      }
-      o += "    default: break;\n  }\n  acc_a = acca;\n  acc_b = accb;\n}\n";
-      continue;
-    }
     snprintf(buf, sizeof(buf),
              "template <>\n__device__ %s double spec_stage<%d>(int st, int p_lo, int p_hi, const int32_t* b, float vnf) {\n", spec_stage_inline_attr(), step);
     o += buf;
@@ -1848,23 +1659,12 @@ static std::string spec_stage_source_lbp(const Cascade& m, int n_stages, bool ti
   const int depth = std::min(spec_prefetch_depth(0), 2);  // 16 independent words per stump already: no explicit pipelining measured best (7.8 ms per 32 frames; one stump ahead 8.2, two 8.9)
   std::string o;
   char buf[1024];
-  int n_stumps = 0;
-  for (int s = 0; s < n_stages; s++) n_stumps += m.stage_ntrees[(size_t)s];
-  const bool lbp_select_words = std::getenv("CCAMD_SPEC_LBP_TABLE") == nullptr;  // tuning: the table form of round 2
-  o += "static __device__ const int kSpecSubsets[][8] = {\n";
-  for (int i = 0; i < n_stumps; i++) {
-    const LbpStumpDev& d = t[0][(size_t)i];
-    snprintf(buf, sizeof(buf), "  {%d, %d, %d, %d, %d, %d, %d, %d},\n", d.subset[0], d.subset[1], d.subset[2], d.subset[3], d.subset[4], d.subset[5],
-             d.subset[6], d.subset[7]);
-    o += buf;
-  }
-  o += "};\n";
   auto hexf = [&](float v) {
     char b2[64];
     snprintf(b2, sizeof(b2), "%af", (double)v);
     return std::string(b2);
   };
-  auto stump = [&](const LbpStumpDev& d, int index, int local, const std::string& win, bool h16) {
+  auto stump = [&](const LbpStumpDev& d, int local, const std::string& win, bool h16) {
     SpecStump out;
     std::string P[16];
     for (int k = 0; k < 16; k++) {
@@ -1877,90 +1677,74 @@ static std::string spec_stage_source_lbp(const Cascade& m, int n_stages, bool ti
     out.decls += ";";
     // 16-bit tile: a cell sum is the low half of the corner combination (exact: 255 * cell area < 2^16, tile16_eligible)
     // Cells from horizontal differences: the 12 differences of neighbouring lattice points of a row, then one subtraction
-    // per cell (21 integer operations instead of 27). CCAMD_SPEC_LBP_PLAIN_CELLS: every cell from its four corners.
-    static const bool row_diffs = !std::getenv("CCAMD_SPEC_LBP_PLAIN_CELLS");
-    std::string diffs;
-    if (row_diffs) {
-      diffs = "const int ";
-      bool firstd = true;
-      for (int k = 0; k < 15; k++) {
-        if (k % 4 == 3) continue;
-        snprintf(buf, sizeof(buf), "%sh%d_%d%s = %s - %s", firstd ? "" : ", ", local, k, win.c_str(), P[k].c_str(), P[k + 1].c_str());
-        diffs += buf;
-        firstd = false;
-      }
-      diffs += "; ";
+    // per cell (21 integer operations instead of 27).
+    std::string diffs = "const int ";
+    bool firstd = true;
+    for (int k = 0; k < 15; k++) {
+      if (k % 4 == 3) continue;
+      snprintf(buf, sizeof(buf), "%sh%d_%d%s = %s - %s", firstd ? "" : ", ", local, k, win.c_str(), P[k].c_str(), P[k + 1].c_str());
+      diffs += buf;
+      firstd = false;
     }
-    auto cell = [&](int a, int b2, int c, int dd) {
-      std::string v = P[a] + " - " + P[b2] + " - " + P[c] + " + " + P[dd];
-      if (row_diffs) {
-        char hb[96];
-        snprintf(hb, sizeof(hb), "h%d_%d%s - h%d_%d%s", local, a, win.c_str(), local, c, win.c_str());
-        v = hb;
-      }
+    diffs += "; ";
+    // the cell with corners a, a + 1 (top) and c, c + 1 (bottom): h_a - h_c
+    auto cell = [&](int a, int /*a + 1*/, int c, int /*c + 1*/) {
+      char hb[96];
+      snprintf(hb, sizeof(hb), "h%d_%d%s - h%d_%d%s", local, a, win.c_str(), local, c, win.c_str());
+      const std::string v = hb;
       return h16 ? "((" + v + ") & 0xffff)" : v;
     };
-    std::string e = "{ " + diffs + "const int c = " + cell(5, 6, 9, 10) + "; const int lbp = (" + cell(0, 1, 4, 5) + " >= c ? 128 : 0) | (" + cell(1, 2, 5, 6) +
-                    " >= c ? 64 : 0) | (" + cell(2, 3, 6, 7) + " >= c ? 32 : 0) | (" + cell(6, 7, 10, 11) + " >= c ? 16 : 0) | (" +
+    // The 256-bit subset as eight literals picked by the three top bits of the code -- the results of the first three
+    // comparisons -- through seven unconditional selects, instead of a load from a table: the table word depends on the
+    // lane's own code, so it is a vector memory load whose latency sits in every stump's dependency chain, and the late
+    // stages (a handful of windows per tile) are nothing but that chain.
+    const int* w = d.subset;
+    std::string t = "{ " + diffs + "const int c = " + cell(5, 6, 9, 10) + "; const bool b7 = " + cell(0, 1, 4, 5) + " >= c, b6 = " + cell(1, 2, 5, 6) +
+                    " >= c, b5 = " + cell(2, 3, 6, 7) + " >= c; const int lo = (" + cell(6, 7, 10, 11) + " >= c ? 16 : 0) | (" +
                     cell(10, 11, 14, 15) + " >= c ? 8 : 0) | (" + cell(9, 10, 13, 14) + " >= c ? 4 : 0) | (" + cell(8, 9, 12, 13) +
                     " >= c ? 2 : 0) | (" + cell(4, 5, 8, 9) + " >= c ? 1 : 0); ";
-    if (lbp_select_words) {
-      // The 256-bit subset as eight literals picked by the three top bits of the code -- the results of the first three
-      // comparisons -- through seven unconditional selects, instead of a load from a table: the table word depends on the
-      // lane's own code, so it is a vector memory load whose latency sits in every stump's dependency chain, and the late
-      // stages (a handful of windows per tile) are nothing but that chain.
-      const int* w = d.subset;
-      std::string t = "{ " + diffs + "const int c = " + cell(5, 6, 9, 10) + "; const bool b7 = " + cell(0, 1, 4, 5) + " >= c, b6 = " + cell(1, 2, 5, 6) +
-                      " >= c, b5 = " + cell(2, 3, 6, 7) + " >= c; const int lo = (" + cell(6, 7, 10, 11) + " >= c ? 16 : 0) | (" +
-                      cell(10, 11, 14, 15) + " >= c ? 8 : 0) | (" + cell(9, 10, 13, 14) + " >= c ? 4 : 0) | (" + cell(8, 9, 12, 13) +
-                      " >= c ? 2 : 0) | (" + cell(4, 5, 8, 9) + " >= c ? 1 : 0); ";
-      snprintf(buf, sizeof(buf),
-               "const unsigned l0 = b5 ? 0x%08xu : 0x%08xu, l1 = b5 ? 0x%08xu : 0x%08xu, l2 = b5 ? 0x%08xu : 0x%08xu, l3 = b5 ? 0x%08xu : 0x%08xu; "
-               "const unsigned m0 = b6 ? l1 : l0, m1 = b6 ? l3 : l2; const unsigned sw = b7 ? m1 : m0; "
-               "acc%s += (double)(((sw >> lo) & 1u) ? %s : %s); }",
-               (unsigned)w[1], (unsigned)w[0], (unsigned)w[3], (unsigned)w[2], (unsigned)w[5], (unsigned)w[4], (unsigned)w[7], (unsigned)w[6],
-               win.c_str(), hexf(d.left).c_str(), hexf(d.right).c_str());
-      out.compute = t + buf;
-      if (const char* dbg = std::getenv("CCAMD_DEBUG_SPEC_MODE")) {
-        // Sensitivity experiments (as for Haar above): 3 = every corner read issued twice, 4 = the stump's arithmetic done
-        // twice on operands XOR-ed with a value the compiler cannot fold; results thrown away, decisions unchanged.
-        const int mode = std::atoi(dbg);
-        if (mode == 3) {
-          std::string dup;
-          for (int k = 0; k < 16; k++) {
-            snprintf(buf, sizeof(buf), "{ unsigned dz%d = (unsigned)%s%s[%d]; asm volatile(\"\" :: \"v\"(dz%d)); } ", k, h16 ? "h" : "b", win.c_str(), d.ofs[k] ^ 1, k);
-            dup += buf;
-          }
-          out.compute = dup + out.compute;
-        } else if (mode == 4) {
-          std::string dup = "{ const int zz = (int)__float_as_uint(vnf" + win + ") ^ 0x3f800001; double accd = 0.; int ";
-          for (int k = 0; k < 16; k++) dup += std::string(k ? ", " : "") + "d" + P[k] + " = " + P[k] + " ^ zz";
-          dup += "; ";
-          std::string body = out.compute;
-          for (int k = 15; k >= 0; k--) {  // p<local>_<k><win> -> dp...; longest names first so that p0_1 does not hit p0_10
-            size_t pos = 0;
-            while ((pos = body.find(P[k], pos)) != std::string::npos) {
-              const char next = pos + P[k].size() < body.size() ? body[pos + P[k].size()] : ' ';
-              const bool whole = !(next >= '0' && next <= '9') && (pos == 0 || body[pos - 1] != 'd');
-              if (whole) {
-                body.insert(pos, "d");
-                pos += P[k].size() + 1;
-              } else
-                pos += P[k].size();
-            }
-          }
-          const std::string accname = "acc" + win + " +=";
-          const size_t ap = body.find(accname);
-          if (ap != std::string::npos) body.replace(ap, accname.size(), "accd +=");
-          dup += body + " asm volatile(\"\" :: \"v\"(accd)); } ";
-          out.compute = dup + out.compute;
+    snprintf(buf, sizeof(buf),
+             "const unsigned l0 = b5 ? 0x%08xu : 0x%08xu, l1 = b5 ? 0x%08xu : 0x%08xu, l2 = b5 ? 0x%08xu : 0x%08xu, l3 = b5 ? 0x%08xu : 0x%08xu; "
+             "const unsigned m0 = b6 ? l1 : l0, m1 = b6 ? l3 : l2; const unsigned sw = b7 ? m1 : m0; "
+             "acc%s += (double)(((sw >> lo) & 1u) ? %s : %s); }",
+             (unsigned)w[1], (unsigned)w[0], (unsigned)w[3], (unsigned)w[2], (unsigned)w[5], (unsigned)w[4], (unsigned)w[7], (unsigned)w[6],
+             win.c_str(), hexf(d.left).c_str(), hexf(d.right).c_str());
+    out.compute = t + buf;
+    if (const char* dbg = std::getenv("CCAMD_DEBUG_SPEC_MODE")) {
+      // Sensitivity experiments (as for Haar above): 3 = every corner read issued twice, 4 = the stump's arithmetic done
+      // twice on operands XOR-ed with a value the compiler cannot fold; results thrown away, decisions unchanged.
+      const int mode = std::atoi(dbg);
+      if (mode == 3) {
+        std::string dup;
+        for (int k = 0; k < 16; k++) {
+          snprintf(buf, sizeof(buf), "{ unsigned dz%d = (unsigned)%s%s[%d]; asm volatile(\"\" :: \"v\"(dz%d)); } ", k, h16 ? "h" : "b", win.c_str(), d.ofs[k] ^ 1, k);
+          dup += buf;
         }
+        out.compute = dup + out.compute;
+      } else if (mode == 4) {
+        std::string dup = "{ const int zz = (int)__float_as_uint(vnf" + win + ") ^ 0x3f800001; double accd = 0.; int ";
+        for (int k = 0; k < 16; k++) dup += std::string(k ? ", " : "") + "d" + P[k] + " = " + P[k] + " ^ zz";
+        dup += "; ";
+        std::string body = out.compute;
+        for (int k = 15; k >= 0; k--) {  // p<local>_<k><win> -> dp...; longest names first so that p0_1 does not hit p0_10
+          size_t pos = 0;
+          while ((pos = body.find(P[k], pos)) != std::string::npos) {
+            const char next = pos + P[k].size() < body.size() ? body[pos + P[k].size()] : ' ';
+            const bool whole = !(next >= '0' && next <= '9') && (pos == 0 || body[pos - 1] != 'd');
+            if (whole) {
+              body.insert(pos, "d");
+              pos += P[k].size() + 1;
+            } else
+              pos += P[k].size();
+          }
+        }
+        const std::string accname = "acc" + win + " +=";
+        const size_t ap = body.find(accname);
+        if (ap != std::string::npos) body.replace(ap, accname.size(), "accd +=");
+        dup += body + " asm volatile(\"\" :: \"v\"(accd)); } ";
+        out.compute = dup + out.compute;
       }
-      return out;
-    } else
-    snprintf(buf, sizeof(buf), "acc%s += (double)((kSpecSubsets[%d][lbp >> 5] & (1 << (lbp & 31))) ? %s : %s); }", win.c_str(), index,
-             hexf(d.left).c_str(), hexf(d.right).c_str());
-    out.compute = e + buf;
+    }
     return out;
   };
   for (int step = 1; step <= 2; step++) {
@@ -1976,7 +1760,7 @@ static std::string spec_stage_source_lbp(const Cascade& m, int n_stages, bool ti
       std::vector<SpecStump> st;
       for (int i = 0; i < m.stage_ntrees[(size_t)s]; i++) {
         const int idx = m.stage_first[(size_t)s] + i;
-        st.push_back(stump(t[step - 1][(size_t)idx], idx, i, "", h16));
+        st.push_back(stump(t[step - 1][(size_t)idx], i, "", h16));
       }
       spec_emit_stage(o, st, depth, true, {"acc"});
       o += "    } break;\n";
@@ -1993,7 +1777,7 @@ static std::string spec_stage_source_lbp(const Cascade& m, int n_stages, bool ti
       std::vector<SpecStump> st;
       for (int i = 0; i < m.stage_ntrees[0]; i++) {
         const int idx = m.stage_first[0] + i;
-        SpecStump a = stump(t[step - 1][(size_t)idx], idx, i, "a", h16), b2 = stump(t[step - 1][(size_t)idx], idx, i, "b", h16);
+        SpecStump a = stump(t[step - 1][(size_t)idx], i, "a", h16), b2 = stump(t[step - 1][(size_t)idx], i, "b", h16);
         st.push_back(SpecStump{a.loads + b2.loads, a.decls + " " + b2.decls, a.compute + " " + b2.compute});
       }
       spec_emit_stage(o, st, std::min(depth, 1), false, {"acca", "accb"});
@@ -2462,10 +2246,6 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
     A.gstumps = haar ? (const void*)d->d_haar_g.p : (const void*)d->d_lbp_g.p;
     A.lbp16_all = d->lbp16_all;
     if (!haar && d->d_lbp16.p) A.wstumps2 = d->d_lbp16.p;  // LBP wave phase of kernels with 16-bit tiles
-    if (d->spec_fn && d->spec_tmode == TILE_PAIR16) {      // pair tile: its own record format for the table-driven stages
-      A.gstumps = d->d_haar_p16.p;
-      A.wstumps2 = d->d_haar_p16w.p;
-    }
     A.trees = d->m.max_nodes_per_tree > 1 ? 1 : 0;
     A.nodes1 = haar ? (const void*)d->d_hnode1.p : (const void*)d->d_lnode1.p;
     A.nodes2 = haar ? (const void*)d->d_hnode2.p : (const void*)d->d_lnode2.p;
@@ -3077,7 +2857,7 @@ static const char kSpecPrelude[] =
 //   block; in a launch of their own the STEP-1 tiles run at 6 blocks per CU. ms per 32 Full-HD frames alone, one run
 //   (tools/r4_h.sh): one module at 8 rows 8.35; two modules at 8 / 8 rows 7.82, 12 / 8 rows 7.32, 12 / 12 rows 7.49,
 //   16 / 12 rows 7.77, 12 / 16 rows 8.11 (STEP-1 / STEP-2; a 32-bit STEP-2 tile of 12 rows leaves 4 blocks per CU).
-// * everything else (pair tile, Haar with 16-bit tiles): one module at the library's 8 rows.
+// * everything else (Haar with 16-bit tiles): one module at the library's 8 rows.
 // CCAMD_SPEC_TILE_Y sets every module's rows, CCAMD_SPEC_TILE_Y1 / _Y2 the STEP-1 / STEP-2 module's, CCAMD_SPEC_ONE_MODULE=1
 // forces a single module (tuning).
 struct SpecModulePlan {
@@ -3092,7 +2872,7 @@ static std::vector<SpecModulePlan> spec_modules(const Cascade& m, int tmode) {
   };
   // (cascades with tilted features keep the library's tile height: their records and generated offsets carry the distance
   // between the sum tile and the tilted tile behind it, which depends on the tile's rows)
-  if (tmode == TILE_PAIR16 || m.has_tilted) return {{0, TILE_Y}};
+  if (m.has_tilted) return {{0, TILE_Y}};
   const bool lbp16 = m.feature_type == CC_FEATURE_LBP && tmode == TILE_16;
   const bool haar32 = tmode == TILE_32 && m.feature_type == CC_FEATURE_HAAR;
   const bool rows_given = std::getenv("CCAMD_SPEC_TILE_Y") != nullptr;
@@ -3119,7 +2899,6 @@ static cc_status compile_specialised(const std::string& src, const std::string& 
   if (only_step) optv.push_back(o_step.c_str());
   if (lbp) optv.push_back("-DCC_SPEC_LBP");
   if (tile16) optv.push_back("-DCC_SPEC_TILE16");
-  if (tmode == TILE_PAIR16) optv.push_back("-DCC_SPEC_PAIR16");
   std::vector<std::string> extra;  // tuning: further compiler options, space-separated
   if (const char* e = std::getenv("CCAMD_SPEC_EXTRA_FLAGS")) {
     std::istringstream is(e);
@@ -3265,7 +3044,7 @@ static cc_status spec_build(const Cascade& m, int n_stages, const std::string& a
   const std::string marker = "//@@CC_SPEC_FUNCTIONS@@";
   const size_t pos = src.find(marker);
   if (pos == std::string::npos) return set_error(CC_ERR_HIP, "cc_detector_specialize: kernel source has no specialisation marker");
-  const int tmode = pair16_eligible(m) ? TILE_PAIR16 : tile16_eligible(m, k) ? TILE_16 : TILE_32;
+  const int tmode = tile16_eligible(m, k) ? TILE_16 : TILE_32;
   src.replace(pos, marker.size(), spec_stage_source(m, k, tmode));
   k_out = k;
   tmode_out = tmode;
@@ -3321,24 +3100,6 @@ static cc_status spec_install(cc_detector* d, const std::vector<SpecCode>& codes
       const TileGeom<1> G1(d->m.win_w, d->m.win_h, ty);
       const TileGeom16 G2(d->m.win_w, d->m.win_h, ty);
       x.lds = eval_lds_bytes(std::max(G1.words(), G2.words()), false, haar_k, ty) + d->lds_extra;
-    } else if (tmode == TILE_PAIR16) {  // STEP-2 tile of window pairs, with partial sums for both windows of a slot
-      const TileGeom<1> G1(d->m.win_w, d->m.win_h);
-      const TileGeomP G2(d->m.win_w, d->m.win_h);
-      x.lds = std::max(eval_lds_bytes(G1.words(), false), eval_lds_bytes_pair(G2.words())) + d->lds_extra;
-      if (!d->d_haar_p16.p) {
-        std::vector<HaarStumpP16> tp, tw;
-        build_haar_stumps_p16(d->m, tp);
-        // wave phase: the stage's stumps in the bank-aware order computed for this geometry's offsets (the records carry
-        // their stump's index in `pad`)
-        std::vector<HaarStumpDev> geo;
-        build_haar_stumps_at(d->m, geo, [&](int y, int x2) { return G2.at(y, x2); }, 0);
-        const std::vector<HaarStumpDev> order = d->wave_below > 0 && !std::getenv("CCAMD_NO_WAVE_SCHEDULE") ? schedule_for_wave_phase(d->m, geo) : geo;
-        tw.reserve(order.size());
-        for (const HaarStumpDev& r : order) tw.push_back(tp[(size_t)r.pad]);
-        CC_HIP(d->d_haar_p16.upload(tp, d->stream));
-        CC_HIP(d->d_haar_p16w.upload(tw, d->stream));
-        CC_HIP(hipStreamSynchronize(d->stream));
-      }
     }
     if (x.lds > 64 * 1024) {  // same opt-in as the ahead-of-time kernels (cc_detector_create)
       const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(x.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds);
@@ -3379,7 +3140,6 @@ static cc_status spec_install(cc_detector* d, const std::vector<SpecCode>& codes
     d->spec_tile_y1 = sec->tile_y;
   }
   d->spec_stages = k;
-  d->spec_tmode = tmode;
   return CC_OK;
 }
 

@@ -166,46 +166,6 @@ struct TileGeom16 {
   __host__ __device__ int words() const { return rows * row_stride; }
 };
 
-// STEP-2 tile of WINDOW PAIRS (run-time specialised Haar kernels, CC_SPEC_PAIR16). Word i of a plane holds the low halves
-// of entries i and i + 1 of that plane: lo16 = I[r][c], hi16 = I[r][c + 2]. Two windows two pixels apart -- the neighbours
-// (lx, lx + 1) of a tile row -- then find every corner in the SAME word at the same offset: one ds_read_b32 and packed 16-bit
-// arithmetic (v_pk_add_u16 / v_pk_sub_u16) evaluate a stump for both, and a single window simply ignores the upper half.
-// (ds_read_b64 on the 32-bit tile cannot do this: half of the corners would sit on an odd word, and a misaligned 8-byte
-// LDS read is serialised lane by lane -- profiles/r03_microbench_lds16.txt.) Sums are exact modulo 2^16 as in TileGeom16.
-// Every second tile row starts one word later (at() adds r >> 1): window rows are then an ODD number of words apart, so
-// the 16 pairs of a window row (even words) and the 16 pairs of the next row (odd words) that a half-wavefront reads in the
-// dense phase fall on 32 different banks, and offsets relative to a window's base stay constants.
-struct TileGeomP {
-  static constexpr bool k16 = false;
-  int cols, rows, plane, row_stride, wrow;  // wrow: words between the bases of consecutive window rows
-  __host__ __device__ TileGeomP(int W0, int H0) {
-    cols = (TILE_X - 1) * 2 + W0 + 1;
-    rows = (TILE_Y - 1) * 2 + H0 + 1;
-    plane = ((cols + 3) / 4 * 4) / 2;
-    row_stride = 2 * plane;
-    // bank skew between window rows = wrow mod 32 (odd): keep it away from +-1 and 16 +- 1, where near neighbours share a class
-    for (;; row_stride += 2) {
-      const int k = (2 * row_stride + 1) & 31;
-      if (k == 21 || k == 25 || k == 9 || k == 13 || k == 5) break;
-    }
-    wrow = 2 * row_stride + 1;
-  }
-  __host__ __device__ int at(int r, int c) const { return r * row_stride + (r >> 1) + (c & 1) * plane + (c >> 1); }
-  __host__ __device__ int words() const { return rows * row_stride + (rows >> 1) + 2; }
-};
-
-// Table-driven stump of the pair tile: up to 6 pieces (a rectangle whose sum can exceed 16 bits is cut into strips that
-// cannot), piece p belongs to rectangle rect_of[p]; offsets are words from the window's tile base, read as low halves.
-constexpr int P16_PIECES = 6;
-struct HaarStumpP16 {
-  unsigned short ofs[P16_PIECES][4];
-  float w[3];
-  float thr, left, right;
-  unsigned char rect_of[P16_PIECES];
-  unsigned char npieces, nrect;
-};
-static_assert(sizeof(HaarStumpP16) == 80, "HaarStumpP16 is loaded dword by dword");
-
 constexpr int TILE_WINDOWS = TILE_X * TILE_Y;  // 512
 constexpr int MAX_STAGES = 64;                 // stage index limit of the kernels (result codes, specialisation switch)
 constexpr int PART_DOUBLES = (EVAL_WAVES - 1) * 64;  // partial stage sums of the stump-split phase: (slices-1) x windows
@@ -218,12 +178,6 @@ __host__ __device__ inline int tile_words_padded(int tile_words) { return (tile_
 __host__ __device__ inline size_t eval_lds_bytes(int tile_words, bool tilted, bool haar = true, int tile_y = TILE_Y) {
   return (size_t)tile_words_padded(tile_words) * 4 * (tilted ? 2 : 1) + PART_DOUBLES * 8 + (haar ? tile_y * VNF_PITCH * 4 : 0) +
          2 * (tile_y * TILE_X) * 2 + 3 * 32 * 4;
-}
-// pair tile: partial sums for both windows of a slot; a stage is split into at most 2 slices there (PAIR_PART entries per
-// window), which keeps the block at the 32-bit tile's footprint: 5 blocks per CU
-constexpr int PAIR_PART = EVAL_THREADS / 2;
-__host__ __device__ inline size_t eval_lds_bytes_pair(int tile_words) {
-  return eval_lds_bytes(tile_words, false) - PART_DOUBLES * 8 + 2 * PAIR_PART * 8;
 }
 
 // Stages the tile of the integral into LDS: one wavefront per tile row, lanes = groups of 4 consecutive entries
@@ -516,15 +470,6 @@ template <int STEP>
 __device__ __forceinline__ double spec_stage(int st, int p_lo, int p_hi, const int32_t* b, float vnf);
 template <int STEP>
 __device__ __forceinline__ void spec_stage0_x2(const int32_t* ba, const int32_t* bb, float vnfa, float vnfb, double& acc_a, double& acc_b);
-#ifdef CC_SPEC_PAIR16
-// Pair tile (TileGeomP): one call evaluates the stage for the two windows of a slot; `b` = the slot's tile base, the
-// packed words' low halves belong to the first window (sum -> acc_a), the high halves to its right neighbour (acc_b).
-using cc_us2 = unsigned short __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ cc_us2 cc_pk(int v) { return __builtin_bit_cast(cc_us2, v); }
-__device__ __forceinline__ cc_us2 cc_k2(int k) { return cc_us2{(unsigned short)k, (unsigned short)k}; }
-template <int STEP>
-__device__ __forceinline__ void spec_stage_pair(int st, int p_lo, int p_hi, const int32_t* b, float vnfa, float vnfb, double& acc_a, double& acc_b);
-#endif
 //@@CC_SPEC_FUNCTIONS@@
 #endif
 
@@ -1164,468 +1109,6 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
   stamp(STAMP_SLOTS - 1);
 }
 
-
-#ifdef CC_SPEC_PAIR16
-// ------------------------------------------------------------------------------------------------
-// The cascade kernel on the PAIR tile (TileGeomP): STEP-2 tiles of a specialised Haar stump cascade. Same phases and the
-// same results as eval_tile; the unit of work of the dense and the thread phase is a SLOT = a window or two neighbouring
-// windows (lx, lx + 1) of a tile row, whose corner words are shared (see TileGeomP). Queue entries: window id of the
-// slot's first window, bit 15 = the right neighbour is alive too. A stage keeps a pair together while both windows
-// pass; when one fails the slot goes on as a single window.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void stage_tile_pair(int32_t* lds, const TileGeomP& G, const int32_t* __restrict__ sum, const ScaleDev& S, int x0, int y0) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int quads = (G.cols + 3) >> 2;                // <= 64 (host check): a lane's right neighbour holds the next four columns
-  const bool right_edge = x0 + quads * 4 - 1 > S.w;  // block-uniform
-  const int c = lane * 4, gc = x0 + c;
-  const bool in_tile = lane < quads;
-  const bool col_ok = in_tile && gc <= S.w;
-  auto pack = [](int lo, int hi) { return (lo & 0xffff) | (hi << 16); };
-  for (int rb = wave; rb < G.rows; rb += EVAL_WAVES * STAGE_ROWS) {
-    int4 v[STAGE_ROWS];
-#pragma unroll
-    for (int k = 0; k < STAGE_ROWS; k++) {
-      const int r = rb + k * EVAL_WAVES, gr = y0 + r;
-      v[k] = make_int4(0, 0, 0, 0);
-      if (r < G.rows && gr <= S.h && col_ok) v[k] = *reinterpret_cast<const int4*>(sum + (size_t)gr * S.pitchI + gc);
-    }
-#pragma unroll
-    for (int k = 0; k < STAGE_ROWS; k++) {
-      const int r = rb + k * EVAL_WAVES;
-      int4 w = v[k];
-      if (right_edge) {
-        if (gc + 1 > S.w) w.y = 0;
-        if (gc + 2 > S.w) w.z = 0;
-        if (gc + 3 > S.w) w.w = 0;
-      }
-      const int nx = __shfl_down(w.x, 1), ny = __shfl_down(w.y, 1);  // columns c + 4, c + 5 (every lane takes part)
-      if (r < G.rows && in_tile) {
-        int32_t* row = lds + r * G.row_stride + (r >> 1) + (c >> 1);
-        row[0] = pack(w.x, w.z);
-        row[1] = pack(w.z, nx);
-        row[G.plane] = pack(w.y, w.w);
-        row[G.plane + 1] = pack(w.w, ny);
-      }
-    }
-  }
-}
-
-// vote of one table-driven stump for the window whose tile base is `b` (low halves of the words)
-__device__ __forceinline__ double vote_p16(const int32_t* b, const HaarStumpP16& sp, float vnf) {
-  int r0 = 0, r1 = 0, r2 = 0;
-#pragma unroll
-  for (int p = 0; p < P16_PIECES; p++) {
-    if (p < sp.npieces) {
-      const int s = (b[sp.ofs[p][0]] - b[sp.ofs[p][1]] - b[sp.ofs[p][2]] + b[sp.ofs[p][3]]) & 0xffff;
-      const int k = sp.rect_of[p];
-      r0 += k == 0 ? s : 0;
-      r1 += k == 1 ? s : 0;
-      r2 += k == 2 ? s : 0;
-    }
-  }
-  float v = sp.w[0] * (float)r0 + sp.w[1] * (float)r1;
-  if (sp.nrect == 3) v += sp.w[2] * (float)r2;
-  v *= vnf;
-  return (double)(v < sp.thr ? sp.left : sp.right);
-}
-
-__device__ __forceinline__ unsigned long long spread_bits(unsigned v) {  // bit i -> bit 2 i
-  unsigned long long x = v;
-  x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
-  x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
-  x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
-  x = (x | (x << 2)) & 0x3333333333333333ull;
-  x = (x | (x << 1)) & 0x5555555555555555ull;
-  return x;
-}
-
-__device__ __forceinline__ void eval_tile_pair(const EvalArgs& A, int32_t* lds, const int4 T, const ScaleDev& S) {
-  static_assert(WIN_PER_THREAD == 2 && TILE_X == 64, "the dense phase of the pair tile gives every thread one pair");
-  constexpr int W0 = CC_SPEC_W0, H0 = CC_SPEC_H0;
-  constexpr int STEP = 2;
-  constexpr int PAIR = 0x8000, ID_MASK = 0x1ff;
-  const TileGeomP G(W0, H0);
-  double* s_part = reinterpret_cast<double*>(lds + tile_words_padded(G.words()));  // [2][PAIR_PART]: first / second window of a slot
-  float* s_vnf = reinterpret_cast<float*>(s_part + 2 * PAIR_PART);
-  unsigned short* s_q = reinterpret_cast<unsigned short*>(s_vnf + TILE_Y * VNF_PITCH);
-  int* s_cnt = reinterpret_cast<int*>(s_q + 2 * TILE_WINDOWS);
-  const int frame = blockIdx.y;
-  const int32_t* sum = A.integ + ((size_t)frame * A.nchan + 0) * A.int_frame_elems + S.int_ofs;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int gx0 = T.y * TILE_X, gy0 = T.z * TILE_Y;
-  const HaarStumpP16 CC_CONST* stumps = as_const_table(reinterpret_cast<const HaarStumpP16*>(A.gstumps));
-  const int CC_CONST* stage_first = as_const_table(A.stage_first);
-  const int CC_CONST* stage_ntrees = as_const_table(A.stage_ntrees);
-  const float CC_CONST* stage_thr = as_const_table(A.stage_thr);
-  const int CC_CONST* group_first = as_const_table(A.group_first);
-  const bool dbg = A.dbg_codes != nullptr && frame == 0;
-  auto stamp = [&](int slot) {
-    if (A.stamps && threadIdx.x == 0)
-      A.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * STAMP_SLOTS + slot] = __builtin_amdgcn_s_memtime();
-  };
-  stamp(0);
-
-  // dense phase: thread = the pair (lxa, lxa + 1) of window row ly. A half-wavefront holds 16 pairs of one window row and the
-  // 16 pairs below them (see TileGeomP for the banks).
-  const int dsub = (lane >> 4) & 1, lxa = ((lane >> 5) * 16 + (lane & 15)) * 2, ly = wave * 2 + dsub;
-  const int ida = ly * 64 + lxa;
-  unsigned valsq_pre[2];
-  {
-    const unsigned* sq = reinterpret_cast<const unsigned*>(A.integ + ((size_t)frame * A.nchan + 1) * A.int_frame_elems + S.int_ofs);
-    const int nrx = W0 - 2, nry = H0 - 2;
-    const int gy = min(gy0 + ly, S.ny - 1);
-    unsigned sq_raw[2][4];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-      const int gx = min(gx0 + lxa + k, S.nx - 1);
-      size_t q0;
-      int dx;
-      if (A.sq_compact) {
-        q0 = (size_t)(gy * 2 + 1) * S.pitchI + gx;
-        dx = nrx >> 1;
-      } else {
-        q0 = (size_t)(gy * STEP + 1) * S.pitchI + (gx * STEP + 1);
-        dx = nrx;
-      }
-      sq_raw[k][0] = sq[q0];
-      sq_raw[k][1] = sq[q0 + dx];
-      sq_raw[k][2] = sq[q0 + (size_t)nry * S.pitchI];
-      sq_raw[k][3] = sq[q0 + (size_t)nry * S.pitchI + dx];
-    }
-    stage_tile_pair(lds, G, sum, S, gx0 * STEP, gy0 * STEP);
-    if (threadIdx.x < 3 * 32) s_cnt[threadIdx.x] = 0;
-#pragma unroll
-    for (int k = 0; k < 2; k++) valsq_pre[k] = sq_raw[k][0] - sq_raw[k][1] - sq_raw[k][2] + sq_raw[k][3];
-  }
-  __syncthreads();
-  stamp(1);
-  if (A.stop_after == -2) return;
-
-  auto window_base = [&](int id) { return (id >> 6) * G.wrow + (id & 63); };
-  auto report = [&](int id, int code, double last) {
-    const size_t o = (size_t)S.win_ofs + (size_t)(gy0 + (id >> 6)) * S.nx + (gx0 + (id & 63));
-    A.dbg_codes[o] = code;
-    if (A.dbg_sums) A.dbg_sums[o] = last;
-  };
-  auto emit_candidate = [&](int id, double last_sum) {
-    const int slot = atomicAdd(A.cand_count, 1);
-    if (slot < A.cand_cap) A.cands[slot] = CandRaw{frame, T.x, gx0 + (id & 63), gy0 + (id >> 6), last_sum};
-  };
-  const int skew = G.wrow & 31;
-  auto win_class = [&](int id) { return ((id & 63) + skew * (id >> 6)) & 31; };
-  auto vnf_slot = [&](int id) { return (id >> 6) * (TILE_X + skew) + (id & 63); };
-  // appends slot `e` (first window id, PAIR bit) to the queue of group g; its class is that of its first window
-  auto enqueue = [&](bool pass, int e, int g) {
-    if (pass) {
-      const int c = win_class(e & ID_MASK);
-      const int row = atomicAdd(&s_cnt[(g % 3) * 32 + c], 1);
-      s_q[(g & 1) * TILE_WINDOWS + row * 32 + c] = (unsigned short)e;
-    }
-  };
-  // what is left of slot (id, id + 1) after a stage
-  auto requeue = [&](bool na, bool nb, int id, int g) { enqueue(na || nb, na ? (id | (nb ? PAIR : 0)) : id + 1, g); };
-  // stage s for the two windows of the slot at `b`, each sum in stump order
-  auto stage_sum2 = [&](int s, const int32_t* b, float vnfa, float vnfb, bool want_b, double& sa, double& sb) {
-    if (s < CC_SPEC_STAGES) {
-      spec_stage_pair<STEP>(s, 0, SPEC_PARTS, b, vnfa, vnfb, sa, sb);
-      return;
-    }
-    const int first = stage_first[s], nt = stage_ntrees[s];
-    sa = 0.;
-    sb = 0.;
-    const bool any_b = __any(want_b);
-    HaarStumpP16 cur = load_record(stumps + first);
-    for (int j = 0; j < nt; j++) {
-      const HaarStumpP16 nxt = load_record(stumps + first + min(j + 1, nt - 1));
-      sa += vote_p16(b, cur, vnfa);
-      if (any_b) sb += vote_p16(b + 1, cur, vnfb);
-      cur = nxt;
-    }
-  };
-
-  // ---------------- phase D --------------------------------------------------------------------------------------
-  {
-    const int32_t* b = lds + window_base(ida);
-    float vnf[2] = {1.f, 1.f};
-    bool alive[2];
-    const int gy = gy0 + ly;
-    {
-      const int nrx = W0 - 2, nry = H0 - 2, hx = nrx >> 1;
-      const double area = (double)(nrx * nry);
-      // the variance rectangle as its left and right half, each exact modulo 2^16 (host check), both windows at once
-      const cc_us2 a0 = cc_pk(b[G.at(1, 1)]), a1 = cc_pk(b[G.at(1, 1 + hx)]), a2 = cc_pk(b[G.at(1, 1 + nrx)]);
-      const cc_us2 c0 = cc_pk(b[G.at(1 + nry, 1)]), c1 = cc_pk(b[G.at(1 + nry, 1 + hx)]), c2 = cc_pk(b[G.at(1 + nry, 1 + nrx)]);
-      const cc_us2 t1 = a0 - a1 - c0 + c1, t2 = a1 - a2 - c1 + c2;
-      const int valsum[2] = {(int)t1.x + (int)t2.x, (int)t1.y + (int)t2.y};
-#pragma unroll
-      for (int k = 0; k < 2; k++) {
-        alive[k] = false;
-        if (gx0 + lxa + k < S.nx && gy < S.ny) {
-          double nf = area * (double)valsq_pre[k] - (double)valsum[k] * (double)valsum[k];
-          if (nf > 0.) {
-            vnf[k] = inv_sqrt_as_float(nf);
-            alive[k] = area * (double)vnf[k] < 1e-1;
-          }
-          if (dbg && !alive[k]) report(ida + k, -1, 0.0);
-        }
-      }
-    }
-    if (A.stop_after == -3) {  // timing experiments: staging + variance test only
-      const float sink = (alive[0] ? vnf[0] : 0.f) + (alive[1] ? vnf[1] : 0.f);
-      if (sink == 12345.f) s_vnf[0] = sink;
-      return;
-    }
-    double acc[2] = {0., 0.};
-    if (__any(alive[0] || alive[1])) spec_stage_pair<STEP>(0, 0, SPEC_PARTS, b, vnf[0], vnf[1], acc[0], acc[1]);
-    const double thr = (double)stage_thr[0];
-    bool pass[2], rej0[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-      pass[k] = alive[k] && !(acc[k] < thr);
-      rej0[k] = alive[k] && !pass[k];
-      if (dbg && rej0[k]) report(ida + k, 0, acc[k]);
-    }
-    // 64-bit mask of a window row from the ballots of the first / second windows of its 32 pairs (row s of this wavefront)
-    auto row_mask = [&](unsigned long long ma, unsigned long long mb, int s) {
-      const unsigned a = (unsigned)((ma >> (16 * s)) & 0xffffull) | ((unsigned)((ma >> (32 + 16 * s)) & 0xffffull) << 16);
-      const unsigned b2 = (unsigned)((mb >> (16 * s)) & 0xffffull) | ((unsigned)((mb >> (32 + 16 * s)) & 0xffffull) << 16);
-      return spread_bits(a) | (spread_bits(b2) << 1);
-    };
-    {
-      const unsigned long long ra = __ballot(rej0[0]), rb = __ballot(rej0[1]);
-      const unsigned long long m0 = row_mask(ra, rb, 0), m1 = row_mask(ra, rb, 1);
-      if (lane == 0) {
-        unsigned long long* mrow = A.masks + (size_t)frame * A.mask_frame_words + S.mask_ofs + T.y;
-        if (gy0 + wave * 2 < S.ny) mrow[(size_t)(gy0 + wave * 2) * S.nxw] = m0;
-        if (gy0 + wave * 2 + 1 < S.ny) mrow[(size_t)(gy0 + wave * 2 + 1) * S.nxw] = m1;
-      }
-      if (!dbg && A.early_skip) {  // stage-0 skip rule, as in eval_tile
-        const unsigned long long m = dsub ? m1 : m0;
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-          const int x = lxa + k;
-          const unsigned long long zeros_below = ~m & ((1ull << x) - 1ull);
-          int run;
-          bool known;
-          if (zeros_below) {
-            run = x - 1 - (63 - __clzll((long long)zeros_below));
-            known = true;
-          } else {
-            run = x;
-            known = T.y == 0;
-          }
-          if (known && (run & 1)) pass[k] = false;
-        }
-      }
-    }
-    if (A.nstages == 1) {
-#pragma unroll
-      for (int k = 0; k < 2; k++)
-        if (pass[k]) {
-          emit_candidate(ida + k, acc[k]);
-          if (dbg) report(ida + k, 1, acc[k]);
-        }
-    } else {
-      // Survivors of a row pair up greedily from the left end of every run of consecutive survivors: a window an even
-      // distance from its run's start opens a slot and takes its right neighbour along if that one survived.
-      const unsigned long long pa = __ballot(pass[0]), pb = __ballot(pass[1]);
-      const unsigned long long al = dsub ? row_mask(pa, pb, 1) : row_mask(pa, pb, 0);
-#pragma unroll
-      for (int k = 0; k < 2; k++) {
-        const int x = lxa + k;
-        if (pass[k]) s_vnf[vnf_slot(ida + k)] = vnf[k];
-        const unsigned long long dead_below = ~al & ((1ull << x) - 1ull);
-        const int start = dead_below ? 64 - __clzll((long long)dead_below) : 0;
-        const bool opens = pass[k] && !((x - start) & 1);
-        const bool with_right = x < 63 && ((al >> (x + 1)) & 1ull);
-        enqueue(opens, (ida + k) | (with_right ? PAIR : 0), 1);
-      }
-    }
-  }
-  stamp(2);
-
-  // ---------------- phase T: one thread per queued slot, stage by stage ------------------------------------------
-  const int half = lane >> 5, cls = lane & 31;
-  int st = 1, qg = 1;
-  int n = 0, rows = 0, my_rows = 0;
-  for (; qg < A.ngroups; qg++) {
-    st = group_first[qg];
-    const int st_end = group_first[qg + 1];
-    if (A.stop_after >= 0 && st > A.stop_after) return;
-    __syncthreads();
-    my_rows = s_cnt[(qg % 3) * 32 + cls];
-    if (threadIdx.x < 32) s_cnt[((qg + 2) % 3) * 32 + threadIdx.x] = 0;
-    rows = wave_max_u32(my_rows);
-    n = wave_sum_u32(my_rows) >> 1;  // slots
-    if (st + 2 < STAMP_SLOTS - 1) stamp(st + 2);
-    if (n == 0 || n < A.wave_below) break;
-    const unsigned short* q = s_q + (qg & 1) * TILE_WINDOWS;
-    const bool last_group = st_end >= A.nstages;
-    const int groups = (rows + 1) >> 1;
-    const int first = stage_first[st], nt = stage_ntrees[st];
-    const double thr = (double)stage_thr[st];
-    const bool may_split = A.split_stumps && st_end - st == 1;
-    const int g_split = may_split ? groups - groups % EVAL_WAVES : groups;
-    const int rem = groups - g_split;
-    const int ns = rem > 0 && 2 * rem <= EVAL_WAVES ? 2 : 1;  // at most two slices (s_part holds PAIR_PART sums per window)
-    {
-      const int g_end = ns == 1 ? groups : g_split;
-      for (int g = wave; g < g_end; g += EVAL_WAVES) {
-        const int row = g * 2 + half;
-        const bool valid = row < my_rows;
-        const int e = valid ? q[row * 32 + cls] : cls;  // a lane without a slot evaluates window `cls` of its own class
-        const int id = e & ID_MASK;
-        const int32_t* b = lds + window_base(id);
-        const float vnfa = s_vnf[vnf_slot(id)], vnfb = s_vnf[vnf_slot(id + 1)];
-        bool alive_a = valid, alive_b = valid && (e & PAIR);
-        double acc_a = 0., acc_b = 0.;
-        for (int s2 = st; s2 < st_end; s2++) {
-          if (s2 > st && !__any(alive_a || alive_b)) break;
-          double sa, sb;
-          stage_sum2(s2, b, vnfa, vnfb, alive_b, sa, sb);
-          const double t2 = (double)stage_thr[s2];
-          const bool pass_a = alive_a && !(sa < t2), pass_b = alive_b && !(sb < t2);
-          if (dbg && alive_a && !pass_a) report(id, -s2, sa);
-          if (dbg && alive_b && !pass_b) report(id + 1, -s2, sb);
-          if (alive_a) acc_a = sa;
-          if (alive_b) acc_b = sb;
-          alive_a = pass_a;
-          alive_b = pass_b;
-        }
-        if (last_group) {
-          if (alive_a) {
-            emit_candidate(id, acc_a);
-            if (dbg) report(id, 1, acc_a);
-          }
-          if (alive_b) {
-            emit_candidate(id + 1, acc_b);
-            if (dbg) report(id + 1, 1, acc_b);
-          }
-        } else
-          requeue(alive_a, alive_b, id, qg + 1);
-      }
-    }
-    if (ns > 1) {  // leftover row groups: the wavefronts split the stage's stumps (see eval_tile)
-      const int slice = wave % ns, grp = wave / ns;
-      const int row = (g_split + grp) * 2 + half;
-      const int i = grp * 64 + lane;
-      const bool valid = row < my_rows;
-      const int e = valid ? q[min(row, QUEUE_ROWS - 1) * 32 + cls] : cls;
-      const int id = e & ID_MASK;
-      const bool has_b = valid && (e & PAIR);
-      double acc_a = 0., acc_b = 0.;
-      if (grp < rem) {
-        const int32_t* b = lds + window_base(id);
-        const float vnfa = s_vnf[vnf_slot(id)], vnfb = s_vnf[vnf_slot(id + 1)];
-        if (st < CC_SPEC_STAGES) {
-          spec_stage_pair<STEP>(st, slice * (SPEC_PARTS / ns), (slice + 1) * (SPEC_PARTS / ns), b, vnfa, vnfb, acc_a, acc_b);
-        } else if (slice < nt) {
-          const bool any_b = __any(has_b);
-          HaarStumpP16 cur = load_record(stumps + first + slice);
-          for (int j = slice; j < nt; j += ns) {
-            const HaarStumpP16 nxt = load_record(stumps + first + min(j + ns, nt - 1));
-            acc_a += vote_p16(b, cur, vnfa);
-            if (any_b) acc_b += vote_p16(b + 1, cur, vnfb);
-            cur = nxt;
-          }
-        }
-        if (slice) {
-          s_part[(slice - 1) * (EVAL_THREADS / ns) + i] = acc_a;
-          s_part[PAIR_PART + (slice - 1) * (EVAL_THREADS / ns) + i] = acc_b;
-        }
-      }
-      __syncthreads();
-      if (grp < rem && slice == 0) {
-        for (int k = 1; k < ns; k++) {
-          acc_a += s_part[(k - 1) * (EVAL_THREADS / ns) + i];
-          acc_b += s_part[PAIR_PART + (k - 1) * (EVAL_THREADS / ns) + i];
-        }
-        const bool pass_a = valid && !(acc_a < thr), pass_b = has_b && !(acc_b < thr);
-        if (dbg && valid && !pass_a) report(id, -st, acc_a);
-        if (dbg && has_b && !pass_b) report(id + 1, -st, acc_b);
-        if (last_group) {
-          if (pass_a) {
-            emit_candidate(id, acc_a);
-            if (dbg) report(id, 1, acc_a);
-          }
-          if (pass_b) {
-            emit_candidate(id + 1, acc_b);
-            if (dbg) report(id + 1, 1, acc_b);
-          }
-        } else
-          requeue(pass_a, pass_b, id, qg + 1);
-      }
-    }
-  }
-  if (qg >= A.ngroups || n == 0) {
-    stamp(STAMP_SLOTS - 1);
-    return;
-  }
-
-  // ---------------- phase W: one wavefront per window, lanes split the stumps (as in eval_tile) ------------------
-  {
-    const unsigned short* q = s_q + (qg & 1) * TILE_WINDOWS;
-    const HaarStumpP16* wstumps = reinterpret_cast<const HaarStumpP16*>(A.wstumps2);
-    // the slots' windows are numbered in table order and dealt round-robin; fewer than wave_below <= 64 slots are left,
-    // i.e. fewer than 128 windows: a wavefront's share fits its 64 lanes
-    unsigned short* my_list = reinterpret_cast<unsigned short*>(s_part) + wave * 64;
-    int numbered = 0;
-    for (int r0 = 0; r0 < rows; r0 += 2) {
-      const int row = r0 + half;
-      const bool valid = row < my_rows;
-      const int e = valid ? q[row * 32 + cls] : 0;
-      const bool pair = valid && (e & PAIR);
-      const int id = e & ID_MASK;
-      const unsigned long long mv = __ballot(valid), mp = __ballot(pair);
-      const int number = numbered + __builtin_amdgcn_mbcnt_hi((unsigned)(mv >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mv, 0)) +
-                         __builtin_amdgcn_mbcnt_hi((unsigned)(mp >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mp, 0));
-      if (valid && number % EVAL_WAVES == wave) my_list[number / EVAL_WAVES] = (unsigned short)id;
-      if (pair && (number + 1) % EVAL_WAVES == wave) my_list[(number + 1) / EVAL_WAVES] = (unsigned short)(id + 1);
-      numbered += __builtin_popcountll(mv) + __builtin_popcountll(mp);
-    }
-    const int cnt = (numbered - wave + EVAL_WAVES - 1) / EVAL_WAVES;
-    const int my_id = lane < cnt ? my_list[lane] : 0;
-    unsigned long long alive = cnt >= 64 ? ~0ull : ((1ull << cnt) - 1ull);
-    const bool w_stamps = st + 2 < 30;
-    if (w_stamps) stamp(30);
-    double tot = 0., last = 0.;
-    int rej = 0;
-    int s2 = st;
-    for (; s2 < A.nstages && alive; s2++) {
-      if (A.stop_after >= 0 && s2 > A.stop_after) break;
-      const int first = stage_first[s2], nt = stage_ntrees[s2];
-      for (int c = 0; c < nt; c += 64) {
-        const int j = c + lane;
-        const HaarStumpP16 rec = wstumps[first + min(j, nt - 1)];
-        for (unsigned long long m = alive; m; m &= m - 1ull) {
-          const int k = __builtin_ctzll(m);
-          const int id = __builtin_amdgcn_readlane(my_id, k);
-          const float vnf = s_vnf[vnf_slot(id)];
-          const double part = j < nt ? vote_p16(lds + window_base(id), rec, vnf) : 0.;
-          const double total = wave_sum_f64(part);
-          if (lane == k) tot += total;
-        }
-      }
-      const bool mine = (alive >> lane) & 1ull;
-      const bool pass = mine && !(tot < (double)stage_thr[s2]);
-      if (mine) {
-        last = tot;
-        if (!pass) rej = s2;
-      }
-      tot = 0.;
-      alive = __ballot(pass);
-      if (w_stamps && s2 - st < 8) stamp(31 + s2 - st);
-    }
-    const bool accepted = s2 == A.nstages && ((alive >> lane) & 1ull);
-    if (lane < cnt) {
-      if (accepted) emit_candidate(my_id, last);
-      if (dbg && (accepted || !((alive >> lane) & 1ull))) report(my_id, accepted ? 1 : -rej, last);
-    }
-  }
-  stamp(STAMP_SLOTS - 1);
-}
-#endif  // CC_SPEC_PAIR16
-
 #ifndef CC_SPEC_STAGES
 // One launch covers every scale: the tile's scale decides (block-uniformly) which layout it uses.
 // keep the register budget of the LDS-bound occupancy (CC_EVAL_MIN_WAVES_PER_EU wavefronts per SIMD)
@@ -1686,11 +1169,6 @@ extern "C" __global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_wave
     eval_tile<2, false, false>(A, lds, T, S);
   else if (kDo1)
     eval_tile<1, false, false>(A, lds, T, S);
-#elif defined(CC_SPEC_PAIR16)
-  if (kDo2 && (!kDo1 || S.ystep == 2))
-    eval_tile_pair(A, lds, T, S);
-  else if (kDo1)
-    eval_tile<1, true, false>(A, lds, T, S);
 #else
   if (kDo2 && (!kDo1 || S.ystep == 2))
     eval_tile<2, true, false>(A, lds, T, S);

@@ -36,7 +36,7 @@ def main():
         path = f"/tmp/stress_{seed}.xml"
         open(path, "w").write(xml)
         o = orc.load_cascade_xml(path)
-        for env in ({}, {"CCAMD_SPEC_TILE16": "1"}, {"CCAMD_SPEC_PAIR16": "1"}, {"CCAMD_SPEC_ONE_MODULE": "1"},
+        for env in ({}, {"CCAMD_SPEC_TILE16": "1"}, {"CCAMD_SPEC_ONE_MODULE": "1"},
                     {"CCAMD_SPEC_TILE_Y1": "8", "CCAMD_SPEC_TILE_Y2": "12"}, {"CCAMD_DENSE_FROM": "1"}):
             os.environ.update(env)
             p = cc.CascadeClassifier(path)
@@ -50,7 +50,7 @@ def main():
                 windows += len(codes)
             for kk in env:
                 del os.environ[kk]
-        print(f"cascade {seed}: stages {sizes}, {k} specialised: identical (32-bit, 16-bit and pair tiles; one module, other tile heights, list queue)", flush=True)
+        print(f"cascade {seed}: stages {sizes}, {k} specialised: identical (32-bit and 16-bit tiles; one module, other tile heights, list queue)", flush=True)
         os.remove(path)
     for seed in range(seed0, seed0 + n_cascades):
         rng = np.random.default_rng(5000 + seed)

@@ -20,8 +20,6 @@ lbp=""; grep -q '<featureType>LBP' "$xml" && lbp="-DCC_SPEC_LBP"
 # the library compiles kernels with 16-bit STEP-2 tiles for 7 wavefronts per SIMD (their LDS footprint allows it) and defines CC_SPEC_TILE16
 t16=""; dw=5
 if [ "$(grep -c 'reinterpret_cast<const unsigned short\*>(b)' $out.hip)" -gt 1 ]; then t16="-DCC_SPEC_TILE16"; dw=7; fi
-# pair tile (CCAMD_SPEC_PAIR16=1): the generated source specialises spec_stage_pair
-if grep -q 'void spec_stage_pair<2>' $out.hip; then t16="-DCC_SPEC_PAIR16"; fi
 # LBP kernels with 16-bit tiles are compiled for tiles of 16 window rows (spec_tile_rows in cc_detect.hip)
 if [ -n "$lbp" ] && [ "$t16" = "-DCC_SPEC_TILE16" ] && [ -z "$CC_TILE_Y" ]; then CC_TILE_Y=${CCAMD_SPEC_TILE_Y:-20}; dw=6; fi
 W=$(grep -o '<width>[0-9]*' "$xml" | head -1 | grep -o '[0-9]*'); H=$(grep -o '<height>[0-9]*' "$xml" | head -1 | grep -o '[0-9]*')
