@@ -28,16 +28,10 @@
 #include <thread>
 #include <vector>
 
+#include "cc_hip_util.h"
 #include "cc_internal.h"
 
 using namespace ccamd;
-
-#define CC_HIP(expr)                                                                                         \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return set_error(CC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                           __FILE__, __LINE__);                                              \
-  } while (0)
 
 namespace {
 

@@ -36,18 +36,12 @@
 #include <mutex>
 #include <unordered_set>
 
+#include "cc_hip_util.h"
 #include "cc_internal.h"
 
 namespace ccamd {
 
 #include "build/cc_eval_kernel_src.h"  // kEvalKernelSrc: the text of cc_eval_kernel.inc
-
-#define CC_HIP(expr)                                                                                         \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return set_error(CC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                           __FILE__, __LINE__);                                              \
-  } while (0)
 
 #include "cc_eval_kernel.inc"
 
@@ -552,31 +546,84 @@ struct MineArgs {
   int nchan;       // channels per image in integ: image f starts at integ + f * nchan * chan_elems (blockIdx.y = image)
 };
 
+// Window i of the stream: its ladder level, and in (x, y) its top-left corner in that level.
+__device__ __forceinline__ MineLevel mine_window(const MineLevel* levels, int n_levels, long long i, int ox, int oy, int sx, int sy, int& x,
+                                                 int& y) {
+  int l = 0;
+  while (l + 1 < n_levels && levels[l + 1].win_first <= i) l++;
+  const MineLevel L = levels[l];
+  const int k = (int)(i - L.win_first);
+  const int gy = k / L.nx, gx = k - gy * L.nx;
+  x = ox + gx * sx;
+  y = oy + gy * sy;
+  return L;
+}
+
+// calcNormFactor, features.cpp:13-25 (the 4-corner difference of the wrapped squared sums is exact)
+__device__ __forceinline__ float mine_norm_factor(const int32_t* sum, const unsigned* sq, size_t base, int P, int W0, int H0) {
+  const int nw = W0 - 2, nh = H0 - 2;
+  const size_t q = base + P + 1;
+  const int vs = sum[q] - sum[q + nw] - sum[q + (size_t)nh * P] + sum[q + (size_t)nh * P + nw];
+  const unsigned vq = sq[q] - sq[q + nw] - sq[q + (size_t)nh * P] + sq[q + (size_t)nh * P + nw];
+  const double area = (double)(nw * nh);
+  return (float)sqrt((double)(area * (double)vq - (double)vs * (double)vs));
+}
+
+// Node n's decision for the window at `base` of a level with integral pitch P. Haar: value = calc / normfactor, `<=` goes left;
+// LBP: the 3x3-cell code is in the node's subset.
+template <bool HAAR>
+__device__ __forceinline__ bool mine_go_left(const MineNode* n, const int32_t* sum, const int32_t* til, size_t base, int P, float nf) {
+  if (HAAR) {
+    const int32_t* b = (n->tilted ? til : sum) + base;
+    float ret = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      if (j == 2 && n->w[2] == 0.0f) break;
+      const int rx = n->r[j][0], ry = n->r[j][1], rw = n->r[j][2], rh = n->r[j][3];
+      int p0, p1, p2, p3;
+      if (!n->tilted) {  // CV_SUM_OFFSETS
+        p0 = rx + P * ry;
+        p1 = rx + rw + P * ry;
+        p2 = rx + P * (ry + rh);
+        p3 = rx + rw + P * (ry + rh);
+      } else {  // CV_TILTED_OFFSETS
+        p0 = rx + P * ry;
+        p1 = rx - rh + P * (ry + rh);
+        p2 = rx + rw + P * (ry + rw);
+        p3 = rx + rw - rh + P * (ry + rw + rh);
+      }
+      const float term = n->w[j] * (float)(b[p0] - b[p1] - b[p2] + b[p3]);
+      ret = j == 0 ? term : ret + term;
+    }
+    const float val = nf == 0.0f ? 0.0f : ret / nf;
+    return val <= n->thr;
+  }
+  const int32_t* b = sum + base;
+  int p[16];
+#pragma unroll
+  for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+    for (int cc = 0; cc < 4; cc++) p[4 * rr + cc] = b[(n->r[0][0] + cc * n->r[0][2]) + P * (n->r[0][1] + rr * n->r[0][3])];
+  const int c = p[5] - p[6] - p[9] + p[10];
+  const int code = (p[0] - p[1] - p[4] + p[5] >= c ? 128 : 0) | (p[1] - p[2] - p[5] + p[6] >= c ? 64 : 0) |
+                   (p[2] - p[3] - p[6] + p[7] >= c ? 32 : 0) | (p[6] - p[7] - p[10] + p[11] >= c ? 16 : 0) |
+                   (p[10] - p[11] - p[14] + p[15] >= c ? 8 : 0) | (p[9] - p[10] - p[13] + p[14] >= c ? 4 : 0) |
+                   (p[8] - p[9] - p[12] + p[13] >= c ? 2 : 0) | (p[4] - p[5] - p[8] + p[9] >= c ? 1 : 0);
+  return (n->subset[code >> 5] & (1 << (code & 31))) != 0;
+}
+
 template <bool HAAR>
 __global__ __launch_bounds__(256) void k_negmine_windows(MineArgs A) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= A.n_windows) return;
-  int l = 0;
-  while (l + 1 < A.n_levels && A.levels[l + 1].win_first <= i) l++;
-  const MineLevel L = A.levels[l];
-  const int k = (int)(i - L.win_first);
-  const int gy = k / L.nx, gx = k - gy * L.nx;
-  const int x = A.ox + gx * A.sx, y = A.oy + gy * A.sy;
+  int x, y;
+  const MineLevel L = mine_window(A.levels, A.n_levels, i, A.ox, A.oy, A.sx, A.sy, x, y);
   const int32_t* integ = A.integ + (size_t)blockIdx.y * A.nchan * A.chan_elems;
   const int32_t* sum = integ + L.int_ofs;
   const int32_t* til = integ + 2 * A.chan_elems + L.int_ofs;
   const int P = L.pitchI;
   const size_t base = (size_t)y * P + x;
-  float nf = 1.f;
-  if (HAAR) {  // calcNormFactor, features.cpp:13-25 (the 4-corner difference of the wrapped squared sums is exact)
-    const unsigned* sq = reinterpret_cast<const unsigned*>(integ + A.chan_elems + L.int_ofs);
-    const int nw = A.W0 - 2, nh = A.H0 - 2;
-    const size_t q = base + P + 1;
-    const int vs = sum[q] - sum[q + nw] - sum[q + (size_t)nh * P] + sum[q + (size_t)nh * P + nw];
-    const unsigned vq = sq[q] - sq[q + nw] - sq[q + (size_t)nh * P] + sq[q + (size_t)nh * P + nw];
-    const double area = (double)(nw * nh);
-    nf = (float)sqrt((double)(area * (double)vq - (double)vs * (double)vs));
-  }
+  const float nf = HAAR ? mine_norm_factor(sum, reinterpret_cast<const unsigned*>(integ + A.chan_elems + L.int_ofs), base, P, A.W0, A.H0) : 1.f;
   uint8_t pass = 1;
   for (int st = 0; st < A.nstages && pass; st++) {
     double acc = 0;
@@ -586,46 +633,7 @@ __global__ __launch_bounds__(256) void k_negmine_windows(MineArgs A) {
       const int root = A.tree_root[t];
       do {
         const MineNode* n = A.nodes + root + idx;
-        bool go_left;
-        if (HAAR) {
-          const int32_t* b = (n->tilted ? til : sum) + base;
-          float ret = 0.f;
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            if (j == 2 && n->w[2] == 0.0f) break;
-            const int rx = n->r[j][0], ry = n->r[j][1], rw = n->r[j][2], rh = n->r[j][3];
-            int p0, p1, p2, p3;
-            if (!n->tilted) {  // CV_SUM_OFFSETS
-              p0 = rx + P * ry;
-              p1 = rx + rw + P * ry;
-              p2 = rx + P * (ry + rh);
-              p3 = rx + rw + P * (ry + rh);
-            } else {  // CV_TILTED_OFFSETS
-              p0 = rx + P * ry;
-              p1 = rx - rh + P * (ry + rh);
-              p2 = rx + rw + P * (ry + rw);
-              p3 = rx + rw - rh + P * (ry + rw + rh);
-            }
-            const float term = n->w[j] * (float)(b[p0] - b[p1] - b[p2] + b[p3]);
-            ret = j == 0 ? term : ret + term;
-          }
-          const float val = nf == 0.0f ? 0.0f : ret / nf;
-          go_left = val <= n->thr;
-        } else {
-          const int32_t* b = sum + base;
-          int p[16];
-#pragma unroll
-          for (int rr = 0; rr < 4; rr++)
-#pragma unroll
-            for (int cc = 0; cc < 4; cc++) p[4 * rr + cc] = b[(n->r[0][0] + cc * n->r[0][2]) + P * (n->r[0][1] + rr * n->r[0][3])];
-          const int c = p[5] - p[6] - p[9] + p[10];
-          const int code = (p[0] - p[1] - p[4] + p[5] >= c ? 128 : 0) | (p[1] - p[2] - p[5] + p[6] >= c ? 64 : 0) |
-                           (p[2] - p[3] - p[6] + p[7] >= c ? 32 : 0) | (p[6] - p[7] - p[10] + p[11] >= c ? 16 : 0) |
-                           (p[10] - p[11] - p[14] + p[15] >= c ? 8 : 0) | (p[9] - p[10] - p[13] + p[14] >= c ? 4 : 0) |
-                           (p[8] - p[9] - p[12] + p[13] >= c ? 2 : 0) | (p[4] - p[5] - p[8] + p[9] >= c ? 1 : 0);
-          go_left = (n->subset[code >> 5] & (1 << (code & 31))) != 0;
-        }
-        idx = go_left ? n->left : n->right;
+        idx = mine_go_left<HAAR>(n, sum, til, base, P, nf) ? n->left : n->right;
       } while (idx > 0);
       acc += (double)A.leaves[A.tree_leaf0[t] - idx];
     }
@@ -644,72 +652,21 @@ __global__ __launch_bounds__(256) void k_negmine_wave(MineArgs A) {
   const int lane = threadIdx.x & 63;
   const long long i = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (i >= A.n_windows) return;  // wave-uniform
-  int l = 0;
-  while (l + 1 < A.n_levels && A.levels[l + 1].win_first <= i) l++;
-  const MineLevel L = A.levels[l];
-  const int k = (int)(i - L.win_first);
-  const int gy = k / L.nx, gx = k - gy * L.nx;
-  const int x = A.ox + gx * A.sx, y = A.oy + gy * A.sy;
+  int x, y;
+  const MineLevel L = mine_window(A.levels, A.n_levels, i, A.ox, A.oy, A.sx, A.sy, x, y);
   const int32_t* integ = A.integ + (size_t)blockIdx.y * A.nchan * A.chan_elems;
   const int32_t* sum = integ + L.int_ofs;
   const int32_t* til = integ + 2 * A.chan_elems + L.int_ofs;
   const int P = L.pitchI;
   const size_t base = (size_t)y * P + x;
-  float nf = 1.f;
-  if (HAAR) {
-    const unsigned* sq = reinterpret_cast<const unsigned*>(integ + A.chan_elems + L.int_ofs);
-    const int nw = A.W0 - 2, nh = A.H0 - 2;
-    const size_t q = base + P + 1;
-    const int vs = sum[q] - sum[q + nw] - sum[q + (size_t)nh * P] + sum[q + (size_t)nh * P + nw];
-    const unsigned vq = sq[q] - sq[q + nw] - sq[q + (size_t)nh * P] + sq[q + (size_t)nh * P + nw];
-    const double area = (double)(nw * nh);
-    nf = (float)sqrt((double)(area * (double)vq - (double)vs * (double)vs));
-  }
+  const float nf = HAAR ? mine_norm_factor(sum, reinterpret_cast<const unsigned*>(integ + A.chan_elems + L.int_ofs), base, P, A.W0, A.H0) : 1.f;
   uint8_t pass = 1;
   for (int st = 0; st < A.nstages; st++) {
     const int first = A.stage_first[st], nt = A.stage_ntrees[st];
     double part = 0;
     for (int t = first + lane; t < first + nt; t += 64) {
       const MineNode* n = A.nodes + A.tree_root[t];
-      bool go_left;
-      if (HAAR) {
-        const int32_t* b = (n->tilted ? til : sum) + base;
-        float ret = 0.f;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          if (j == 2 && n->w[2] == 0.0f) break;
-          const int rx = n->r[j][0], ry = n->r[j][1], rw = n->r[j][2], rh = n->r[j][3];
-          int p0, p1, p2, p3;
-          if (!n->tilted) {
-            p0 = rx + P * ry;
-            p1 = rx + rw + P * ry;
-            p2 = rx + P * (ry + rh);
-            p3 = rx + rw + P * (ry + rh);
-          } else {
-            p0 = rx + P * ry;
-            p1 = rx - rh + P * (ry + rh);
-            p2 = rx + rw + P * (ry + rw);
-            p3 = rx + rw - rh + P * (ry + rw + rh);
-          }
-          const float term = n->w[j] * (float)(b[p0] - b[p1] - b[p2] + b[p3]);
-          ret = j == 0 ? term : ret + term;
-        }
-        const float val = nf == 0.0f ? 0.0f : ret / nf;
-        go_left = val <= n->thr;
-      } else {
-        const int32_t* b = sum + base;
-        int p[16];
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++)
-#pragma unroll
-          for (int cc = 0; cc < 4; cc++) p[4 * rr + cc] = b[(n->r[0][0] + cc * n->r[0][2]) + P * (n->r[0][1] + rr * n->r[0][3])];
-        const int c = p[5] - p[6] - p[9] + p[10];
-        const int code = (p[0] - p[1] - p[4] + p[5] >= c ? 128 : 0) | (p[1] - p[2] - p[5] + p[6] >= c ? 64 : 0) |
-                         (p[2] - p[3] - p[6] + p[7] >= c ? 32 : 0) | (p[6] - p[7] - p[10] + p[11] >= c ? 16 : 0) |
-                         (p[10] - p[11] - p[14] + p[15] >= c ? 8 : 0) | (p[9] - p[10] - p[13] + p[14] >= c ? 4 : 0) |
-                         (p[8] - p[9] - p[12] + p[13] >= c ? 2 : 0) | (p[4] - p[5] - p[8] + p[9] >= c ? 1 : 0);
-        go_left = (n->subset[code >> 5] & (1 << (code & 31))) != 0;
-      }
+      const bool go_left = mine_go_left<HAAR>(n, sum, til, base, P, nf);
       part += (double)A.leaves[A.tree_leaf0[t] - (go_left ? n->left : n->right)];
     }
     if (wave_sum_f64(part) < (double)A.stage_thr[st]) {
@@ -728,12 +685,9 @@ __global__ __launch_bounds__(64) void k_negmine_gather(const uint8_t* __restrict
   const long long gi = keep[blockIdx.x];  // image * n_windows + stream index
   const long long img = gi / n_windows, i = gi - img * n_windows;
   pyr += (size_t)img * pyr_image_bytes;
-  int l = 0;
-  while (l + 1 < n_levels && levels[l + 1].win_first <= i) l++;
-  const MineLevel L = levels[l];
-  const int k = (int)(i - L.win_first);
-  const int gy = k / L.nx, gx = k - gy * L.nx;
-  const uint8_t* src = pyr + L.img_ofs + (size_t)(oy + gy * sy) * L.pitch8 + (ox + gx * sx);
+  int x, y;
+  const MineLevel L = mine_window(levels, n_levels, i, ox, oy, sx, sy, x, y);
+  const uint8_t* src = pyr + L.img_ofs + (size_t)y * L.pitch8 + x;
   for (int e = threadIdx.x; e < W0 * H0; e += 64) {
     const int yy = e / W0, xx = e - yy * W0;
     out[(size_t)blockIdx.x * W0 * H0 + e] = src[(size_t)yy * L.pitch8 + xx];
@@ -769,64 +723,165 @@ struct DevBuf {
 
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
-// Segment totals of the tilted front end (k_diag_sums / k_tilted_cols): where each scale's totals start, per frame.
-struct TiltPlan {
-  DevBuf<long long> d_ofs;
-  size_t frame_elems = 0;
-  int max_nseg = 0;
-  hipError_t build(const std::vector<ScaleDev>& sd, hipStream_t st) {
-    std::vector<long long> ofs(sd.size() + 1, 0);
-    max_nseg = 0;
-    for (size_t i = 0; i < sd.size(); i++) {
-      const TiltSegs T(sd[i].w, sd[i].h);
-      ofs[i + 1] = ofs[i] + (long long)T.elems();
-      max_nseg = std::max(max_nseg, T.nseg);
+// ------------------------------------------------------------------------------------------------
+// Front end: pyramid (k_resize), integral images (k_integral_band, k_integral_carry) and tilted integral (k_diag_sums,
+// k_tilted_cols) of every level of nf frames. The detector, the negative miner and the building-block entry points all
+// lay it out with front_layout, upload it with FrontTables::upload and launch it with launch_front.
+// ------------------------------------------------------------------------------------------------
+// Host tables of the front end for levels of the given sizes, each resized from a src_w x src_h source.
+struct FrontLayout {
+  int src_w = 0, src_h = 0;
+  std::vector<ScaleDev> sd;  // front-end fields set (w h pitch8 pitchI img_ofs int_ofs h_ofs nbands xtab_ofs ytab_ofs), the rest 0
+  // block maps, ns + 1 entries: first block (band, group) of each level, the total last
+  std::vector<int> resize_first, band_first, col_first, diag_first, tcol_first;
+  std::vector<int> xofs, yofs;  // resize taps: columns (padded, see append_column_taps), rows
+  std::vector<uint16_t> xw1, yw1;
+  std::vector<long long> tseg_ofs;  // tilted only: where each level's segment totals start in a frame's, ns + 1 entries
+  int max_nseg = 0;                 // tilted only: segments of the tallest level (0: no tilted integral)
+  // per frame: pyramid bytes, integral elements per channel, band-total elements per channel, segment-total elements
+  size_t pyr_frame_bytes = 0, int_frame_elems = 0, h_frame_elems = 0, tseg_frame_elems = 0;
+};
+
+static FrontLayout front_layout(int src_w, int src_h, const std::vector<int2>& sizes, bool tilted) {
+  const int ns = (int)sizes.size();
+  FrontLayout L;
+  L.src_w = src_w;
+  L.src_h = src_h;
+  L.sd.resize(ns);
+  for (std::vector<int>* v : {&L.resize_first, &L.band_first, &L.col_first, &L.diag_first, &L.tcol_first}) v->assign(ns + 1, 0);
+  if (tilted) L.tseg_ofs.assign(ns + 1, 0);
+  long long img_ofs = 0, int_ofs = 0, h_ofs = 0;
+  for (int i = 0; i < ns; i++) {
+    ScaleDev& S = L.sd[i];
+    S.w = sizes[i].x;
+    S.h = sizes[i].y;
+    S.pitch8 = align_up(S.w, 4);
+    S.pitchI = align_up(S.w + 1, 4);
+    S.img_ofs = img_ofs;
+    S.int_ofs = int_ofs;
+    S.h_ofs = h_ofs;
+    S.nbands = (S.h + INT_BAND - 1) / INT_BAND;
+    AxisTaps tx, ty;
+    linear_exact_taps(src_w, S.w, tx);
+    linear_exact_taps(src_h, S.h, ty);
+    S.xtab_ofs = append_column_taps(tx, L.xofs, L.xw1);
+    S.ytab_ofs = (int)L.yofs.size();
+    L.yofs.insert(L.yofs.end(), ty.ofs.begin(), ty.ofs.end());
+    L.yw1.insert(L.yw1.end(), ty.w1.begin(), ty.w1.end());
+    img_ofs += (long long)align_up(S.pitch8 * S.h, 16);
+    int_ofs += (long long)S.pitchI * (S.h + 1);
+    h_ofs += (long long)S.nbands * S.pitchI;
+    L.resize_first[i + 1] = L.resize_first[i] + resize_blocks(S.pitch8, S.h);
+    L.band_first[i + 1] = L.band_first[i] + S.nbands;
+    L.col_first[i + 1] = L.col_first[i] + (S.pitchI / 4 + 63) / 64;
+    L.diag_first[i + 1] = L.diag_first[i] + (S.w + S.h - 1 + 255) / 256;  // k_diag_sums: a thread walks 4 diagonals
+    L.tcol_first[i + 1] = L.tcol_first[i] + (S.w + 1 + 63) / 64;
+    if (tilted) {
+      const TiltSegs T(S.w, S.h);
+      L.tseg_ofs[i + 1] = L.tseg_ofs[i] + (long long)T.elems();
+      L.max_nseg = std::max(L.max_nseg, T.nseg);
     }
-    frame_elems = (size_t)ofs[sd.size()];
-    hipError_t e = d_ofs.upload(ofs, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // `ofs` goes out of scope
-    return e;
+  }
+  L.pyr_frame_bytes = (size_t)((img_ofs + 15) & ~15LL);
+  L.int_frame_elems = (size_t)int_ofs;
+  L.h_frame_elems = (size_t)h_ofs;
+  if (tilted) L.tseg_frame_elems = (size_t)L.tseg_ofs[ns];
+  return L;
+}
+
+// A layout and its tables on the device. Callers set the layout, add their own ScaleDev fields, then upload once: the
+// detector's captured hipGraph replays these pointers, so a plan's tables are never reallocated.
+struct FrontTables {
+  FrontLayout L;
+  DevBuf<ScaleDev> d_sd;
+  DevBuf<int> d_resize_first, d_band_first, d_col_first, d_diag_first, d_tcol_first, d_xofs, d_yofs;
+  DevBuf<uint16_t> d_xw1, d_yw1;
+  DevBuf<long long> d_tseg_ofs;
+  // Ends with a synchronisation of `st`, so earlier uploads of the caller on `st` have landed too.
+  hipError_t upload(hipStream_t st) {
+    for (hipError_t e : {d_sd.upload(L.sd, st), d_resize_first.upload(L.resize_first, st), d_band_first.upload(L.band_first, st),
+                         d_col_first.upload(L.col_first, st), d_diag_first.upload(L.diag_first, st), d_tcol_first.upload(L.tcol_first, st),
+                         d_xofs.upload(L.xofs, st), d_yofs.upload(L.yofs, st), d_xw1.upload(L.xw1, st), d_yw1.upload(L.yw1, st),
+                         L.tseg_ofs.empty() ? hipSuccess : d_tseg_ofs.upload(L.tseg_ofs, st)})
+      if (e != hipSuccess) return e;
+    return hipStreamSynchronize(st);
   }
 };
 
-// Tilted integral of every scale of nf frames into channel tilt_chan of `integ` (diag: 2 x int_frame_elems per frame of
-// scratch for the diagonal sums, tseg: tp.frame_elems per frame for the segment totals).
-static void launch_tilted(hipStream_t st, const TiltPlan& tp, int32_t* tseg, const uint8_t* pyr, size_t pyr_frame_bytes, int32_t* diag,
-                          int32_t* integ, size_t int_frame_elems, int nchan, int tilt_chan, const ScaleDev* sd, int ns,
-                          const int* diag_first, int n_diag_blocks, const int* tcol_first, int n_tcol_blocks, int nf) {
-  if (tp.max_nseg == 0 || nf == 0) return;
-  const dim3 gd((n_diag_blocks + TILT_GROUPS - 1) / TILT_GROUPS, nf, 2 * tp.max_nseg), gc((n_tcol_blocks + TILT_GROUPS - 1) / TILT_GROUPS, nf, tp.max_nseg);
+enum { FRONT_RESIZE = 1, FRONT_INTEGRALS = 2 };  // launch_front parts
+
+// Caller-owned buffers of launch_front, frame f of each at f times its per-frame size.
+struct FrontIO {
+  const uint8_t* src = nullptr;  // FRONT_RESIZE: the source frames, src_w x src_h
+  size_t row_stride = 0, frame_stride = 0;
+  uint8_t* pyr = nullptr;      // L.pyr_frame_bytes per frame: the levels (FRONT_INTEGRALS alone: filled by the caller)
+  int32_t* integ = nullptr;    // nchan x L.int_frame_elems per frame: channel 0 sum, 1 sqsum (sq), tilt_chan tilted (tilted layouts)
+  int32_t* hbuf = nullptr;     // nchan x L.h_frame_elems per frame: band totals
+  int32_t* diag = nullptr;     // tilted: 2 x L.int_frame_elems per frame, diagonal sums
+  int32_t* tseg = nullptr;     // tilted: L.tseg_frame_elems per frame, segment totals
+  int nchan = 1, tilt_chan = 2;
+  bool sq = false;
+  int sq_odd_rows_only = 0;  // k_integral_band: squared sums of ystep-2 levels only where the detector reads them
+};
+
+// Launches the front end's `parts` for nf frames on `st`. Only launches: no allocation, no synchronisation (the detector
+// runs it inside a hipGraph capture).
+static void launch_front(hipStream_t st, const FrontTables& T, const FrontIO& io, int nf, int parts) {
+  const FrontLayout& L = T.L;
+  const int ns = (int)L.sd.size();
+  if (ns == 0 || nf == 0) return;
+  if (parts & FRONT_RESIZE)
+    hipLaunchKernelGGL(k_resize, dim3(L.resize_first[ns], nf), dim3(256), 0, st, io.src, io.row_stride, io.frame_stride, L.src_w, L.src_h,
+                       io.pyr, L.pyr_frame_bytes, T.d_sd.p, ns, T.d_resize_first.p, T.d_xofs.p, T.d_xw1.p, T.d_yofs.p, T.d_yw1.p);
+  if (!(parts & FRONT_INTEGRALS)) return;
+  // integral images: band totals, carry down the bands, finished integral
+  const int n_bands = L.band_first[ns];
+  const dim3 grid((n_bands + 3) / 4, nf);
+  if (io.sq)
+    hipLaunchKernelGGL((k_integral_band<true, false>), grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
+                       io.hbuf, L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p, n_bands, 0);
+  else
+    hipLaunchKernelGGL((k_integral_band<false, false>), grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
+                       io.hbuf, L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p, n_bands, 0);
+  hipLaunchKernelGGL(k_integral_carry, dim3(L.col_first[ns], nf, io.sq ? 2 : 1), dim3(64), 0, st, io.hbuf, L.h_frame_elems, io.nchan, T.d_sd.p,
+                     ns, T.d_col_first.p);
+  if (io.sq)
+    hipLaunchKernelGGL((k_integral_band<true, true>), grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
+                       io.hbuf, L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p, n_bands, io.sq_odd_rows_only);
+  else
+    hipLaunchKernelGGL((k_integral_band<false, true>), grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
+                       io.hbuf, L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p, n_bands, io.sq_odd_rows_only);
+  if (L.max_nseg == 0) return;
+  // tilted integral into channel tilt_chan: diagonal sums, then the column recurrence, each as segment totals + final pass
+  const int n_diag = L.diag_first[ns], n_tcol = L.tcol_first[ns];
+  const dim3 gd((n_diag + TILT_GROUPS - 1) / TILT_GROUPS, nf, 2 * L.max_nseg), gc((n_tcol + TILT_GROUPS - 1) / TILT_GROUPS, nf, L.max_nseg);
   const dim3 bt(64 * TILT_GROUPS);
-  hipLaunchKernelGGL(k_diag_sums<false>, gd, bt, 0, st, pyr, pyr_frame_bytes, diag, int_frame_elems, tseg, tp.frame_elems, tp.d_ofs.p, sd, ns,
-                     diag_first, n_diag_blocks);
-  hipLaunchKernelGGL(k_diag_sums<true>, gd, bt, 0, st, pyr, pyr_frame_bytes, diag, int_frame_elems, tseg, tp.frame_elems, tp.d_ofs.p, sd, ns,
-                     diag_first, n_diag_blocks);
-  hipLaunchKernelGGL(k_tilted_cols<false>, gc, bt, 0, st, pyr, pyr_frame_bytes, diag, integ, int_frame_elems, nchan, tilt_chan, tseg,
-                     tp.frame_elems, tp.d_ofs.p, sd, ns, tcol_first, n_tcol_blocks);
-  hipLaunchKernelGGL(k_tilted_cols<true>, gc, bt, 0, st, pyr, pyr_frame_bytes, diag, integ, int_frame_elems, nchan, tilt_chan, tseg,
-                     tp.frame_elems, tp.d_ofs.p, sd, ns, tcol_first, n_tcol_blocks);
+  hipLaunchKernelGGL(k_diag_sums<false>, gd, bt, 0, st, io.pyr, L.pyr_frame_bytes, io.diag, L.int_frame_elems, io.tseg, L.tseg_frame_elems,
+                     T.d_tseg_ofs.p, T.d_sd.p, ns, T.d_diag_first.p, n_diag);
+  hipLaunchKernelGGL(k_diag_sums<true>, gd, bt, 0, st, io.pyr, L.pyr_frame_bytes, io.diag, L.int_frame_elems, io.tseg, L.tseg_frame_elems,
+                     T.d_tseg_ofs.p, T.d_sd.p, ns, T.d_diag_first.p, n_diag);
+  hipLaunchKernelGGL(k_tilted_cols<false>, gc, bt, 0, st, io.pyr, L.pyr_frame_bytes, io.diag, io.integ, L.int_frame_elems, io.nchan, io.tilt_chan,
+                     io.tseg, L.tseg_frame_elems, T.d_tseg_ofs.p, T.d_sd.p, ns, T.d_tcol_first.p, n_tcol);
+  hipLaunchKernelGGL(k_tilted_cols<true>, gc, bt, 0, st, io.pyr, L.pyr_frame_bytes, io.diag, io.integ, L.int_frame_elems, io.nchan, io.tilt_chan,
+                     io.tseg, L.tseg_frame_elems, T.d_tseg_ofs.p, T.d_sd.p, ns, T.d_tcol_first.p, n_tcol);
 }
 
 struct Plan {
   int w = 0, h = 0;
   cc_detect_params p{};
   std::vector<ScaleGeom> geom;
-  std::vector<ScaleDev> sd;
-  size_t pyr_frame_bytes = 0, int_frame_elems = 0, mask_frame_words = 0;
+  FrontTables front;  // its ScaleDev records carry the detector's fields too (mask_ofs win_ofs ystep nx ny nxw scale win_w win_h)
+  size_t mask_frame_words = 0;
   long long windows = 0, integral_elems = 0;
-  int n_resize_blocks = 0, n_bands = 0, n_col_blocks = 0, n_grid_rows = 0, n_diag_blocks = 0, n_tcol_blocks = 0;
-  size_t h_frame_elems = 0;
+  int n_grid_rows = 0;
   int n_tiles = 0;  // tiles of TILE_Y window rows (the ahead-of-time kernels); other heights: tiles_for
   struct TileList {
     int n = 0;
     DevBuf<int4> d;
   };
   std::map<int, std::unique_ptr<TileList>> other_tiles;  // tile lists of the specialised kernel's modules, key = tile_list_key(rows, step)
-  DevBuf<ScaleDev> d_sd;
-  DevBuf<int> d_resize_first, d_band_first, d_col_first, d_gridrow_first, d_diag_first, d_tcol_first, d_xofs, d_yofs;
-  DevBuf<uint16_t> d_xw1, d_yw1;
+  DevBuf<int> d_gridrow_first;
   DevBuf<int4> d_tiles;
-  TiltPlan tilt;
   // Single-image calls (the detection tool's shape) are launch-bound: ~10 launches, memsets and copies for well under a
   // millisecond of device work. After a first ordinary call has sized every buffer, the whole pass (H2D copy of the
   // image, pyramid, integrals, cascade kernel, skip filter, copy-back of the counters) is captured into a hipGraph and
@@ -1012,18 +1067,14 @@ struct cc_negminer {
   // per-image workspace
   DevBuf<uint8_t> d_src, d_pyr, d_pass, d_pix;
   DevBuf<int32_t> d_integ, d_hbuf, d_diag, d_tseg;
-  TiltPlan tilt;
-  DevBuf<ScaleDev> d_sd;
-  DevBuf<MineLevel> d_levels;
-  DevBuf<int> d_resize_first, d_band_first, d_col_first, d_diag_first, d_tcol_first, d_xofs, d_yofs;
-  DevBuf<uint16_t> d_xw1, d_yw1;
   DevBuf<long long> d_keep;
-  // The tables above depend on (image size, offset) only: consecutive images of a background set share them, so they are
+  // The tables below depend on (image size, offset) only: consecutive images of a background set share them, so they are
   // built and uploaded when that key changes, not per call.
+  FrontTables front;  // the ladder's levels
+  DevBuf<MineLevel> d_levels;
   struct Plan {
     int width = -1, height = -1, ox = -1, oy = -1;
-    int nl = 0, n_resize = 0, n_bands = 0, n_cols = 0, n_diag = 0, n_tcol = 0;
-    long long pyr_bytes = 0, chan_elems = 0, h_elems = 0, wins = 0;
+    long long wins = 0;
   } plan;
   uint8_t* h_src = nullptr;   // pinned: the images of a call, tight rows of align4(width)
   uint8_t* h_pass = nullptr;  // pinned: pass flags on their way back
@@ -1980,22 +2031,14 @@ static cc_status build_plan(cc_detector* d, int w, int h, const cc_detect_params
   P->p = p;
   scale_plan(d->m.win_w, d->m.win_h, w, h, p, P->geom);
   const int ns = (int)P->geom.size();
-  std::vector<int> resize_first(ns + 1, 0), band_first(ns + 1, 0), col_first(ns + 1, 0), gridrow_first(ns + 1, 0);
-  std::vector<int> diag_first(ns + 1, 0), tcol_first(ns + 1, 0);
-  long long h_ofs = 0;
-  std::vector<int> xofs, yofs;
-  std::vector<uint16_t> xw1, yw1;
-  long long img_ofs = 0, int_ofs = 0, mask_ofs = 0, win_ofs = 0;
-  P->sd.resize(ns);
+  std::vector<int2> sizes(ns);
+  for (int i = 0; i < ns; i++) sizes[i] = make_int2(P->geom[i].w, P->geom[i].h);
+  P->front.L = front_layout(w, h, sizes, d->m.feature_type == CC_FEATURE_HAAR && d->m.has_tilted);
+  std::vector<int> gridrow_first(ns + 1, 0);
+  long long mask_ofs = 0, win_ofs = 0;
   for (int i = 0; i < ns; i++) {
     const ScaleGeom& g = P->geom[i];
-    ScaleDev& S = P->sd[i];
-    S.w = g.w;
-    S.h = g.h;
-    S.pitch8 = align_up(g.w, 4);
-    S.pitchI = align_up(g.w + 1, 4);
-    S.img_ofs = img_ofs;
-    S.int_ofs = int_ofs;
+    ScaleDev& S = P->front.L.sd[i];
     S.mask_ofs = mask_ofs;
     S.win_ofs = win_ofs;
     S.ystep = g.ystep;
@@ -2005,56 +2048,20 @@ static cc_status build_plan(cc_detector* d, int w, int h, const cc_detect_params
     S.scale = g.scale;
     S.win_w = g.win_w;
     S.win_h = g.win_h;
-    S.ytab_ofs = (int)yofs.size();
-    AxisTaps tx, ty;
-    linear_exact_taps(w, g.w, tx);
-    linear_exact_taps(h, g.h, ty);
-    S.xtab_ofs = append_column_taps(tx, xofs, xw1);
-    yofs.insert(yofs.end(), ty.ofs.begin(), ty.ofs.end());
-    yw1.insert(yw1.end(), ty.w1.begin(), ty.w1.end());
-    img_ofs += (long long)align_up(S.pitch8 * g.h, 16);
-    int_ofs += (long long)S.pitchI * (g.h + 1);
     mask_ofs += (long long)S.nxw * g.ny;
     win_ofs += (long long)g.nx * g.ny;
     P->integral_elems += (long long)(g.w + 1) * (g.h + 1);
-    resize_first[i + 1] = resize_first[i] + resize_blocks(S.pitch8, g.h);
-    S.nbands = (g.h + INT_BAND - 1) / INT_BAND;
-    S.h_ofs = h_ofs;
-    h_ofs += (long long)S.nbands * S.pitchI;
-    band_first[i + 1] = band_first[i] + S.nbands;
-    col_first[i + 1] = col_first[i] + (S.pitchI / 4 + 63) / 64;
     gridrow_first[i + 1] = gridrow_first[i] + g.ny;
-    diag_first[i + 1] = diag_first[i] + (g.w + g.h - 1 + 255) / 256;  // k_diag_sums: a thread walks 4 diagonals
-    tcol_first[i + 1] = tcol_first[i] + (g.w + 1 + 63) / 64;
   }
-  P->pyr_frame_bytes = (size_t)((img_ofs + 15) & ~15LL);
-  P->int_frame_elems = (size_t)int_ofs;
   P->mask_frame_words = (size_t)mask_ofs;
   P->windows = win_ofs;
-  P->n_resize_blocks = resize_first[ns];
-  P->n_bands = band_first[ns];
-  P->h_frame_elems = (size_t)h_ofs;
-  P->n_col_blocks = col_first[ns];
   P->n_grid_rows = gridrow_first[ns];
-  P->n_diag_blocks = diag_first[ns];
-  P->n_tcol_blocks = tcol_first[ns];
   std::vector<int4> tiles = plan_tile_list(P->geom, TILE_Y);
   P->n_tiles = (int)tiles.size();
   hipStream_t st = d->stream;
-  CC_HIP(P->d_sd.upload(P->sd, st));
-  CC_HIP(P->d_resize_first.upload(resize_first, st));
-  CC_HIP(P->d_band_first.upload(band_first, st));
-  CC_HIP(P->d_col_first.upload(col_first, st));
   CC_HIP(P->d_gridrow_first.upload(gridrow_first, st));
-  CC_HIP(P->d_diag_first.upload(diag_first, st));
-  CC_HIP(P->d_tcol_first.upload(tcol_first, st));
-  CC_HIP(P->d_xofs.upload(xofs, st));
-  CC_HIP(P->d_yofs.upload(yofs, st));
-  CC_HIP(P->d_xw1.upload(xw1, st));
-  CC_HIP(P->d_yw1.upload(yw1, st));
   CC_HIP(P->d_tiles.upload(tiles, st));
-  if (d->m.feature_type == CC_FEATURE_HAAR && d->m.has_tilted) CC_HIP(P->tilt.build(P->sd, st));
-  CC_HIP(hipStreamSynchronize(st));  // host vectors go out of scope
+  CC_HIP(P->front.upload(st));  // synchronises: the host vectors above go out of scope
   *out = P.get();
   if (d->plans.size() >= 8) d->plans.erase(d->plans.begin());
   d->plans.push_back(std::move(P));
@@ -2101,31 +2108,12 @@ static void collect_events(cc_detector* d) {
   d->events.clear();
 }
 
-// Integral images of every scale of nf frames: band totals, carry down the bands, finished integral.
-static void launch_integral(hipStream_t st, bool sq, const uint8_t* pyr, size_t pyr_frame_bytes, int32_t* integ,
-                            size_t int_frame_elems, int nchan /* channel stride of integ / hbuf */, int32_t* hbuf, size_t h_frame_elems, const ScaleDev* sd, int ns,
-                            const int* band_first, int n_bands, const int* col_first, int n_col_blocks, int nf, int sq_odd_rows_only = 0) {
-  const dim3 grid((n_bands + 3) / 4, nf);
-  if (sq)
-    hipLaunchKernelGGL((k_integral_band<true, false>), grid, dim3(256), 0, st, pyr, pyr_frame_bytes, integ, int_frame_elems, nchan,
-                       hbuf, h_frame_elems, sd, ns, band_first, n_bands, 0);
-  else
-    hipLaunchKernelGGL((k_integral_band<false, false>), grid, dim3(256), 0, st, pyr, pyr_frame_bytes, integ, int_frame_elems, nchan,
-                       hbuf, h_frame_elems, sd, ns, band_first, n_bands, 0);
-  hipLaunchKernelGGL(k_integral_carry, dim3(n_col_blocks, nf, sq ? 2 : 1), dim3(64), 0, st, hbuf, h_frame_elems, nchan, sd, ns, col_first);
-  if (sq)
-    hipLaunchKernelGGL((k_integral_band<true, true>), grid, dim3(256), 0, st, pyr, pyr_frame_bytes, integ, int_frame_elems, nchan,
-                       hbuf, h_frame_elems, sd, ns, band_first, n_bands, sq_odd_rows_only);
-  else
-    hipLaunchKernelGGL((k_integral_band<false, true>), grid, dim3(256), 0, st, pyr, pyr_frame_bytes, integ, int_frame_elems, nchan,
-                       hbuf, h_frame_elems, sd, ns, band_first, n_bands, sq_odd_rows_only);
-}
-
 // Device pipeline for up to max_batch frames already resident on the device. Leaves the filtered candidate list
 // (d_out[slot], d_counts[slot][1]) on the device; no synchronisation.
 static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes, int nf, size_t row_stride,
                                  size_t frame_stride, bool debug, int slot, bool single_stream = false) {
-  const int ns = (int)P->sd.size();
+  const FrontLayout& FL = P->front.L;
+  const int ns = (int)FL.sd.size();
   hipStream_t st = d->stream;
   hipStream_t fs = d->overlap_front && !single_stream ? d->front_stream : d->stream;  // pyramid + integrals
   const bool haar = d->m.feature_type == CC_FEATURE_HAAR;
@@ -2136,12 +2124,12 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
   if (ns == 0 || nf == 0) return CC_OK;
   // even window sizes: the variance rectangle's corners of step-2 scales sit on odd rows and odd columns only
   const int sq_compact = (haar && d->m.win_w % 2 == 0 && d->m.win_h % 2 == 0 && !d->full_sqsum) ? 1 : 0;
-  CC_HIP(d->d_pyr.ensure(P->pyr_frame_bytes * (size_t)d->pass_capacity));
-  CC_HIP(d->d_integ[slot].ensure(P->int_frame_elems * (size_t)nchan * (size_t)d->pass_capacity));
-  CC_HIP(d->d_hbuf.ensure(std::max<size_t>(P->h_frame_elems * (size_t)nchan * (size_t)d->pass_capacity, 4)));
+  CC_HIP(d->d_pyr.ensure(FL.pyr_frame_bytes * (size_t)d->pass_capacity));
+  CC_HIP(d->d_integ[slot].ensure(FL.int_frame_elems * (size_t)nchan * (size_t)d->pass_capacity));
+  CC_HIP(d->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)nchan * (size_t)d->pass_capacity, 4)));
   if (tilt) {
-    CC_HIP(d->d_diag.ensure(P->int_frame_elems * 2 * (size_t)d->pass_capacity));
-    CC_HIP(d->d_tseg.ensure(std::max<size_t>(P->tilt.frame_elems * (size_t)d->pass_capacity, 1)));
+    CC_HIP(d->d_diag.ensure(FL.int_frame_elems * 2 * (size_t)d->pass_capacity));
+    CC_HIP(d->d_tseg.ensure(std::max<size_t>(FL.tseg_frame_elems * (size_t)d->pass_capacity, 1)));
   }
   CC_HIP(d->d_masks[slot].ensure(std::max<size_t>(P->mask_frame_words * (size_t)d->pass_capacity, 1)));
   if (d->cand_cap == 0) d->cand_cap = 1 << 18;
@@ -2154,21 +2142,25 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
   }
   // this slot's integrals may still be read by the cascade kernel launched two passes ago
   if (fs != st && d->eval_pending[slot]) CC_HIP(hipStreamWaitEvent(fs, d->eval_done[slot], 0));
+  FrontIO io;
+  io.src = dframes;
+  io.row_stride = row_stride;
+  io.frame_stride = frame_stride;
+  io.pyr = d->d_pyr.p;
+  io.integ = d->d_integ[slot].p;
+  io.hbuf = d->d_hbuf.p;
+  io.diag = d->d_diag.p;
+  io.tseg = d->d_tseg.p;
+  io.nchan = nchan;
+  io.sq = haar;
+  io.sq_odd_rows_only = sq_compact;
   {
     EvScope ev(d, EV_RESIZE, fs);
-    hipLaunchKernelGGL(k_resize, dim3(P->n_resize_blocks, nf), dim3(256), 0, fs, dframes, row_stride, frame_stride, P->w,
-                       P->h, d->d_pyr.p, P->pyr_frame_bytes, P->d_sd.p, ns, P->d_resize_first.p, P->d_xofs.p, P->d_xw1.p,
-                       P->d_yofs.p, P->d_yw1.p);
+    launch_front(fs, P->front, io, nf, FRONT_RESIZE);
   }
   {
     EvScope ev(d, EV_INTEGRAL, fs);
-    launch_integral(fs, haar, d->d_pyr.p, P->pyr_frame_bytes, d->d_integ[slot].p, P->int_frame_elems, nchan, d->d_hbuf.p,
-                    P->h_frame_elems, P->d_sd.p, ns, P->d_band_first.p, P->n_bands, P->d_col_first.p, P->n_col_blocks, nf,
-                    /*sq_odd_rows_only=*/sq_compact);
-    if (tilt) {
-      launch_tilted(fs, P->tilt, d->d_tseg.p, d->d_pyr.p, P->pyr_frame_bytes, d->d_diag.p, d->d_integ[slot].p, P->int_frame_elems, nchan, 2,
-                    P->d_sd.p, ns, P->d_diag_first.p, P->n_diag_blocks, P->d_tcol_first.p, P->n_tcol_blocks, nf);
-    }
+    launch_front(fs, P->front, io, nf, FRONT_INTEGRALS);
   }
   if (fs != st) {
     CC_HIP(hipEventRecord(d->front_done[slot], fs));
@@ -2178,10 +2170,10 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
     EvScope ev(d, EV_EVAL, st);
     EvalArgs A;
     A.integ = d->d_integ[slot].p;
-    A.int_frame_elems = P->int_frame_elems;
+    A.int_frame_elems = FL.int_frame_elems;
     A.nchan = nchan;
     A.tilt_chan = tilt ? 2 : -1;
-    A.sd = P->d_sd.p;
+    A.sd = P->front.d_sd.p;
     A.W0 = d->m.win_w;
     A.H0 = d->m.win_h;
     A.nstages = (int)d->m.stage_ntrees.size();
@@ -2275,10 +2267,10 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
   }
   {
     EvScope ev(d, EV_FILTER, st);
-    hipLaunchKernelGGL(k_filter_candidates, dim3(64), dim3(256), 0, st, d->d_cands[slot].p, d->d_counts[slot].p, d->cand_cap, P->d_sd.p,
+    hipLaunchKernelGGL(k_filter_candidates, dim3(64), dim3(256), 0, st, d->d_cands[slot].p, d->d_counts[slot].p, d->cand_cap, P->front.d_sd.p,
                        d->d_masks[slot].p, P->mask_frame_words, d->d_out[slot].p, d->d_counts[slot].p + 1);
     if (debug && P->n_grid_rows)
-      hipLaunchKernelGGL(k_debug_visited, dim3(P->n_grid_rows), dim3(256), 0, st, P->d_sd.p, ns, P->d_gridrow_first.p,
+      hipLaunchKernelGGL(k_debug_visited, dim3(P->n_grid_rows), dim3(256), 0, st, P->front.d_sd.p, ns, P->d_gridrow_first.p,
                          d->d_masks[slot].p, d->d_dbg_visited.p);
   }
   CC_HIP(hipGetLastError());
@@ -3804,38 +3796,24 @@ cc_status cc_resize_linear_exact_u8(int device, const uint8_t* src, int sw, int 
     return set_error(CC_ERR_INVALID_ARG, "cc_resize_linear_exact_u8: bad argument");
   cc_status st = ensure_device(device);
   if (st != CC_OK) return st;
-  ScaleDev S;
-  std::memset(&S, 0, sizeof(S));
-  S.w = dw;
-  S.h = dh;
-  S.pitch8 = align_up(dw, 4);
-  AxisTaps tx, ty;
-  linear_exact_taps(sw, dw, tx);
-  linear_exact_taps(sh, dh, ty);
-  std::vector<int> xofs_pad;
-  std::vector<uint16_t> xw1_pad;
-  S.xtab_ofs = append_column_taps(tx, xofs_pad, xw1_pad);
-  std::vector<ScaleDev> sd{S};
-  const int nblk = resize_blocks(S.pitch8, dh);
-  std::vector<int> first{0, nblk};
-  DevBuf<ScaleDev> d_sd;
-  DevBuf<int> d_first, d_xofs, d_yofs;
-  DevBuf<uint16_t> d_xw1, d_yw1;
+  OwnStream own;  // not the legacy stream: see copy_sync
+  CC_HIP(own.create());
+  FrontTables T;
+  T.L = front_layout(sw, sh, {make_int2(dw, dh)}, false);
+  CC_HIP(T.upload(own.s));
   DevBuf<uint8_t> d_src, d_dst;
   const size_t spitch = (size_t)align_up(sw, 4);
-  CC_HIP(d_sd.upload(sd, nullptr));
-  CC_HIP(d_first.upload(first, nullptr));
-  CC_HIP(d_xofs.upload(xofs_pad, nullptr));
-  CC_HIP(d_yofs.upload(ty.ofs, nullptr));
-  CC_HIP(d_xw1.upload(xw1_pad, nullptr));
-  CC_HIP(d_yw1.upload(ty.w1, nullptr));
   CC_HIP(d_src.ensure(spitch * sh));
-  CC_HIP(d_dst.ensure((size_t)S.pitch8 * dh));
-  CC_HIP(hipMemcpy2D(d_src.p, spitch, src, sstride, sw, sh, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_resize, dim3(nblk, 1), dim3(256), 0, nullptr, d_src.p, spitch, (size_t)0, sw, sh, d_dst.p, (size_t)0,
-                     d_sd.p, 1, d_first.p, d_xofs.p, d_xw1.p, d_yofs.p, d_yw1.p);
+  CC_HIP(d_dst.ensure(T.L.pyr_frame_bytes));
+  CC_HIP(hipMemcpy2DAsync(d_src.p, spitch, src, sstride, sw, sh, hipMemcpyHostToDevice, own.s));
+  FrontIO io;
+  io.src = d_src.p;
+  io.row_stride = spitch;
+  io.pyr = d_dst.p;
+  launch_front(own.s, T, io, 1, FRONT_RESIZE);
   CC_HIP(hipGetLastError());
-  CC_HIP(hipMemcpy2D(dst, dstride, d_dst.p, S.pitch8, dw, dh, hipMemcpyDeviceToHost));
+  CC_HIP(hipMemcpy2DAsync(dst, dstride, d_dst.p, T.L.sd[0].pitch8, dw, dh, hipMemcpyDeviceToHost, own.s));
+  CC_HIP(hipStreamSynchronize(own.s));
   return CC_OK;
 }
 
@@ -3865,51 +3843,40 @@ cc_status cc_integral_u8(int device, const uint8_t* img, int width, int height, 
   if (!img || width < 1 || height < 1 || row_stride < (size_t)width) return set_error(CC_ERR_INVALID_ARG, "cc_integral_u8: bad argument");
   cc_status st = ensure_device(device);
   if (st != CC_OK) return st;
-  ScaleDev S;
-  std::memset(&S, 0, sizeof(S));
-  S.w = width;
-  S.h = height;
-  S.pitch8 = align_up(width, 4);
-  S.pitchI = align_up(width + 1, 4);
-  S.nbands = (height + INT_BAND - 1) / INT_BAND;
-  S.h_ofs = 0;
-  std::vector<ScaleDev> sd{S};
-  std::vector<int> band_first{0, S.nbands}, col_first{0, (S.pitchI / 4 + 63) / 64};
-  DevBuf<ScaleDev> d_sd;
-  DevBuf<int> d_band_first, d_col_first;
+  OwnStream own;  // not the legacy stream: see copy_sync
+  CC_HIP(own.create());
+  FrontTables T;  // one level: the image itself, no resize
+  T.L = front_layout(width, height, {make_int2(width, height)}, tilted != nullptr);
+  CC_HIP(T.upload(own.s));
+  const FrontLayout& L = T.L;
+  const int nchan = tilted ? 3 : 2;  // sum, sqsum, tilted (same kernels as the detection pipeline)
   DevBuf<uint8_t> d_img;
-  DevBuf<int32_t> d_int, d_h, d_tilt;
-  const size_t elems = (size_t)S.pitchI * (height + 1), helems = (size_t)S.pitchI * S.nbands;
-  CC_HIP(d_sd.upload(sd, nullptr));
-  CC_HIP(d_band_first.upload(band_first, nullptr));
-  CC_HIP(d_col_first.upload(col_first, nullptr));
-  CC_HIP(d_img.ensure((size_t)S.pitch8 * height));
-  CC_HIP(d_int.ensure(elems * 2));
-  CC_HIP(d_h.ensure(helems * 2));
-  CC_HIP(hipMemcpy2D(d_img.p, S.pitch8, img, row_stride, width, height, hipMemcpyHostToDevice));
-  launch_integral(nullptr, true, d_img.p, 0, d_int.p, elems, 2, d_h.p, helems, d_sd.p, 1, d_band_first.p, S.nbands, d_col_first.p,
-                  col_first[1], 1);
+  DevBuf<int32_t> d_int, d_h, d_diag, d_tseg;
+  CC_HIP(d_img.ensure(L.pyr_frame_bytes));
+  CC_HIP(d_int.ensure(L.int_frame_elems * nchan));
+  CC_HIP(d_h.ensure(L.h_frame_elems * nchan));
+  if (tilted) {
+    CC_HIP(d_diag.ensure(L.int_frame_elems * 2));
+    CC_HIP(d_tseg.ensure(std::max<size_t>(L.tseg_frame_elems, 1)));
+  }
+  CC_HIP(hipMemcpy2DAsync(d_img.p, L.sd[0].pitch8, img, row_stride, width, height, hipMemcpyHostToDevice, own.s));
+  FrontIO io;
+  io.pyr = d_img.p;
+  io.integ = d_int.p;
+  io.hbuf = d_h.p;
+  io.diag = d_diag.p;
+  io.tseg = d_tseg.p;
+  io.nchan = nchan;
+  io.sq = true;
+  launch_front(own.s, T, io, 1, FRONT_INTEGRALS);
   CC_HIP(hipGetLastError());
   const size_t opitch = (size_t)(width + 1) * 4;
-  if (sum) CC_HIP(hipMemcpy2D(sum, opitch, d_int.p, (size_t)S.pitchI * 4, opitch, height + 1, hipMemcpyDeviceToHost));
-  if (sqsum) CC_HIP(hipMemcpy2D(sqsum, opitch, d_int.p + elems, (size_t)S.pitchI * 4, opitch, height + 1, hipMemcpyDeviceToHost));
-  if (tilted) {  // same kernels as the detection pipeline
-    DevBuf<int32_t> d_diag;
-    std::vector<int> diag_first{0, (width + height - 1 + 255) / 256}, tcol_first{0, (width + 1 + 63) / 64};
-    DevBuf<int> d_diag_first, d_tcol_first;
-    CC_HIP(d_diag_first.upload(diag_first, nullptr));
-    CC_HIP(d_tcol_first.upload(tcol_first, nullptr));
-    CC_HIP(d_diag.ensure(elems * 2));
-    CC_HIP(d_tilt.ensure(elems));
-    TiltPlan tp;
-    CC_HIP(tp.build(std::vector<ScaleDev>(1, S), nullptr));
-    DevBuf<int32_t> d_tseg;
-    CC_HIP(d_tseg.ensure(std::max<size_t>(tp.frame_elems, 1)));
-    launch_tilted(nullptr, tp, d_tseg.p, d_img.p, (size_t)0, d_diag.p, d_tilt.p, elems, 1, 0, d_sd.p, 1, d_diag_first.p, diag_first[1],
-                  d_tcol_first.p, tcol_first[1], 1);
-    CC_HIP(hipGetLastError());
-    CC_HIP(hipMemcpy2D(tilted, opitch, d_tilt.p, (size_t)S.pitchI * 4, opitch, height + 1, hipMemcpyDeviceToHost));
-  }
+  int32_t* const out[3] = {sum, sqsum, tilted};
+  for (int c = 0; c < nchan; c++)
+    if (out[c])
+      CC_HIP(hipMemcpy2DAsync(out[c], opitch, d_int.p + c * L.int_frame_elems, (size_t)L.sd[0].pitchI * 4, opitch, height + 1,
+                              hipMemcpyDeviceToHost, own.s));
+  CC_HIP(hipStreamSynchronize(own.s));
   return CC_OK;
 }
 
@@ -4042,36 +4009,20 @@ static cc_status mine_plan(cc_negminer* m, int width, int height, int ox, int oy
   if (P.width == width && P.height == height && P.ox == ox && P.oy == oy) return CC_OK;
   P.width = -1;  // invalid until everything below has succeeded
   const Cascade& M = m->m;
-  const int W0 = M.win_w, H0 = M.win_h;
-  const bool haar = M.feature_type == CC_FEATURE_HAAR, tilt = haar && M.has_tilted;
   std::vector<MineGeom> g;
-  mine_ladder(W0, H0, width, height, ox, oy, g);
+  mine_ladder(M.win_w, M.win_h, width, height, ox, oy, g);
   const int nl = (int)g.size();
-  std::vector<ScaleDev> sd((size_t)nl);
-  std::vector<MineLevel> lv((size_t)nl);
-  std::vector<int> resize_first(nl + 1, 0), band_first(nl + 1, 0), col_first(nl + 1, 0), diag_first(nl + 1, 0), tcol_first(nl + 1, 0);
-  std::vector<int> xofs, yofs;
-  std::vector<uint16_t> xw1, yw1;
-  long long img_ofs = 0, int_ofs = 0, h_ofs = 0, wins = 0;
+  std::vector<int2> sizes((size_t)nl);
   for (int i = 0; i < nl; i++) {
-    ScaleDev& S = sd[(size_t)i];
-    std::memset(&S, 0, sizeof(S));
-    S.w = g[i].w;
-    S.h = g[i].h;
-    if (S.w < W0 + ox || S.h < H0 + oy) return set_error(CC_ERR_INVALID_ARG, "%s: ladder level %d (%dx%d) smaller than window + offset", who, i, S.w, S.h);
-    S.pitch8 = align_up(S.w, 4);
-    S.pitchI = align_up(S.w + 1, 4);
-    S.img_ofs = img_ofs;
-    S.int_ofs = int_ofs;
-    S.h_ofs = h_ofs;
-    S.nbands = (S.h + INT_BAND - 1) / INT_BAND;
-    S.ytab_ofs = (int)yofs.size();
-    AxisTaps tx, ty;
-    linear_exact_taps(width, S.w, tx);
-    linear_exact_taps(height, S.h, ty);
-    S.xtab_ofs = append_column_taps(tx, xofs, xw1);
-    yofs.insert(yofs.end(), ty.ofs.begin(), ty.ofs.end());
-    yw1.insert(yw1.end(), ty.w1.begin(), ty.w1.end());
+    if (g[i].w < M.win_w + ox || g[i].h < M.win_h + oy)
+      return set_error(CC_ERR_INVALID_ARG, "%s: ladder level %d (%dx%d) smaller than window + offset", who, i, g[i].w, g[i].h);
+    sizes[(size_t)i] = make_int2(g[i].w, g[i].h);
+  }
+  m->front.L = front_layout(width, height, sizes, M.feature_type == CC_FEATURE_HAAR && M.has_tilted);
+  std::vector<MineLevel> lv((size_t)nl);
+  long long wins = 0;
+  for (int i = 0; i < nl; i++) {
+    const ScaleDev& S = m->front.L.sd[(size_t)i];
     MineLevel& L = lv[(size_t)i];
     L.w = S.w;
     L.h = S.h;
@@ -4079,43 +4030,14 @@ static cc_status mine_plan(cc_negminer* m, int width, int height, int ox, int oy
     L.pitch8 = S.pitch8;
     L.nx = g[i].nx;
     L.ny = g[i].ny;
-    L.int_ofs = int_ofs;
-    L.img_ofs = img_ofs;
+    L.int_ofs = S.int_ofs;
+    L.img_ofs = S.img_ofs;
     L.win_first = wins;
     L.pad = 0;
     wins += (long long)g[i].nx * g[i].ny;
-    img_ofs += (long long)align_up(S.pitch8 * S.h, 16);
-    int_ofs += (long long)S.pitchI * (S.h + 1);
-    h_ofs += (long long)S.nbands * S.pitchI;
-    resize_first[i + 1] = resize_first[i] + resize_blocks(S.pitch8, S.h);
-    band_first[i + 1] = band_first[i] + S.nbands;
-    col_first[i + 1] = col_first[i] + (S.pitchI / 4 + 63) / 64;
-    diag_first[i + 1] = diag_first[i] + (S.w + S.h - 1 + 255) / 256;
-    tcol_first[i + 1] = tcol_first[i] + (S.w + 1 + 63) / 64;
   }
-  hipStream_t s = m->stream;
-  CC_HIP(m->d_sd.upload(sd, s));
-  CC_HIP(m->d_levels.upload(lv, s));
-  CC_HIP(m->d_resize_first.upload(resize_first, s));
-  CC_HIP(m->d_band_first.upload(band_first, s));
-  CC_HIP(m->d_col_first.upload(col_first, s));
-  CC_HIP(m->d_diag_first.upload(diag_first, s));
-  CC_HIP(m->d_tcol_first.upload(tcol_first, s));
-  CC_HIP(m->d_xofs.upload(xofs, s));
-  CC_HIP(m->d_yofs.upload(yofs, s));
-  CC_HIP(m->d_xw1.upload(xw1, s));
-  CC_HIP(m->d_yw1.upload(yw1, s));
-  if (tilt) CC_HIP(m->tilt.build(sd, s));
-  CC_HIP(hipStreamSynchronize(s));  // the uploads read host vectors that end here
-  P.nl = nl;
-  P.n_resize = resize_first[nl];
-  P.n_bands = band_first[nl];
-  P.n_cols = col_first[nl];
-  P.n_diag = diag_first[nl];
-  P.n_tcol = tcol_first[nl];
-  P.pyr_bytes = (img_ofs + 15) & ~15LL;
-  P.chan_elems = int_ofs;
-  P.h_elems = h_ofs;
+  CC_HIP(m->d_levels.upload(lv, m->stream));
+  CC_HIP(m->front.upload(m->stream));  // synchronises: `lv` ends here
   P.wins = wins;
   P.ox = ox;
   P.oy = oy;
@@ -4150,19 +4072,20 @@ static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n
   st = mine_plan(m, width, height, ox, oy, who);
   if (st != CC_OK) return st;
   const cc_negminer::Plan& P = m->plan;
+  const FrontLayout& FL = m->front.L;
   const Cascade& M = m->m;
-  const int W0 = M.win_w, H0 = M.win_h, nl = P.nl, K = n_images;
+  const int W0 = M.win_w, H0 = M.win_h, nl = (int)FL.sd.size(), K = n_images;
   const bool haar = M.feature_type == CC_FEATURE_HAAR, tilt = haar && M.has_tilted;
   const long long wins = P.wins;
   *n_windows = wins;
   if (wins * K > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "%s: %lld windows (%d images), capacity %lld", who, wins * K, K, (long long)cap);
   hipStream_t s = m->stream;
   const int nchan = haar ? (tilt ? 3 : 2) : 1;
-  const size_t chan_elems = (size_t)P.chan_elems, spitch = (size_t)align_up(width, 4), src_bytes = spitch * (size_t)height;
+  const size_t chan_elems = FL.int_frame_elems, spitch = (size_t)align_up(width, 4), src_bytes = spitch * (size_t)height;
   CC_HIP(m->d_src.ensure(src_bytes * K));
-  CC_HIP(m->d_pyr.ensure((size_t)P.pyr_bytes * K));
+  CC_HIP(m->d_pyr.ensure(FL.pyr_frame_bytes * K));
   CC_HIP(m->d_integ.ensure(chan_elems * (size_t)nchan * K));
-  CC_HIP(m->d_hbuf.ensure(std::max<size_t>((size_t)P.h_elems * (size_t)nchan * K, 4)));
+  CC_HIP(m->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)nchan * K, 4)));
   CC_HIP(m->d_pass.ensure((size_t)std::max<long long>(wins * K, 1)));
   st = pinned_ensure(&m->h_src, &m->h_src_bytes, src_bytes * K);
   if (st != CC_OK) return st;
@@ -4192,25 +4115,29 @@ static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n
   A.pass = m->d_pass.p;
   if (tilt) {
     CC_HIP(m->d_diag.ensure(chan_elems * 2 * K));
-    CC_HIP(m->d_tseg.ensure(std::max<size_t>(m->tilt.frame_elems * K, 1)));
+    CC_HIP(m->d_tseg.ensure(std::max<size_t>(FL.tseg_frame_elems * K, 1)));
   }
   // one wavefront per window where the parallel stage sum is exact (stumps, order-independent sums); else one thread per window
   const bool wave_mode = M.max_nodes_per_tree == 1 && stage_sums_order_independent(M) && !std::getenv("CCAMD_NEGMINE_THREAD_PER_WINDOW");
   // Every kernel over the images [k0, k0 + n): the front-end kernels and the window kernels take the image as blockIdx.y.
   auto launch_images = [&](int k0, int n) {
-    const uint8_t* src = m->d_src.p + (size_t)k0 * src_bytes;
-    uint8_t* pyr = m->d_pyr.p + (size_t)k0 * (size_t)P.pyr_bytes;
-    int32_t* integ = m->d_integ.p + (size_t)k0 * nchan * chan_elems;
-    hipLaunchKernelGGL(k_resize, dim3(P.n_resize, n), dim3(256), 0, s, src, spitch, src_bytes, width, height, pyr, (size_t)P.pyr_bytes,
-                       m->d_sd.p, nl, m->d_resize_first.p, m->d_xofs.p, m->d_xw1.p, m->d_yofs.p, m->d_yw1.p);
-    launch_integral(s, haar, pyr, (size_t)P.pyr_bytes, integ, chan_elems, nchan, m->d_hbuf.p + (size_t)k0 * nchan * (size_t)P.h_elems, (size_t)P.h_elems,
-                    m->d_sd.p, nl, m->d_band_first.p, P.n_bands, m->d_col_first.p, P.n_cols, n);
-    if (tilt)
-      launch_tilted(s, m->tilt, m->d_tseg.p + (size_t)k0 * m->tilt.frame_elems, pyr, (size_t)P.pyr_bytes, m->d_diag.p + (size_t)k0 * 2 * chan_elems, integ,
-                    chan_elems, nchan, 2, m->d_sd.p, nl, m->d_diag_first.p, P.n_diag, m->d_tcol_first.p, P.n_tcol, n);
+    FrontIO io;
+    io.src = m->d_src.p + (size_t)k0 * src_bytes;
+    io.row_stride = spitch;
+    io.frame_stride = src_bytes;
+    io.pyr = m->d_pyr.p + (size_t)k0 * FL.pyr_frame_bytes;
+    io.integ = m->d_integ.p + (size_t)k0 * nchan * chan_elems;
+    io.hbuf = m->d_hbuf.p + (size_t)k0 * nchan * FL.h_frame_elems;
+    if (tilt) {
+      io.diag = m->d_diag.p + (size_t)k0 * 2 * chan_elems;
+      io.tseg = m->d_tseg.p + (size_t)k0 * FL.tseg_frame_elems;
+    }
+    io.nchan = nchan;
+    io.sq = haar;
+    launch_front(s, m->front, io, n, FRONT_RESIZE | FRONT_INTEGRALS);
     if (wins == 0) return;
     MineArgs B = A;
-    B.integ = integ;
+    B.integ = io.integ;
     B.pass = m->d_pass.p + (size_t)k0 * (size_t)wins;
     if (wave_mode) {
       const unsigned nb = (unsigned)((wins + 3) / 4);
@@ -4287,7 +4214,7 @@ static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n
       const size_t wsz = (size_t)W0 * H0;
       CC_HIP(m->d_keep.upload(keep, s));
       CC_HIP(m->d_pix.ensure(keep.size() * wsz));
-      hipLaunchKernelGGL(k_negmine_gather, dim3((unsigned)keep.size()), dim3(64), 0, s, m->d_pyr.p, (size_t)P.pyr_bytes, wins, m->d_levels.p, nl,
+      hipLaunchKernelGGL(k_negmine_gather, dim3((unsigned)keep.size()), dim3(64), 0, s, m->d_pyr.p, FL.pyr_frame_bytes, wins, m->d_levels.p, nl,
                          m->d_keep.p, W0, H0, ox, oy, A.sx, A.sy, m->d_pix.p);
       CC_HIP(hipGetLastError());
       CC_HIP(hipMemcpyAsync(pixels, m->d_pix.p, keep.size() * wsz, hipMemcpyDeviceToHost, s));
