@@ -99,7 +99,7 @@ cc_status cascade_from_xml(const XmlNode& root, Cascade& c) {
   else if (fts == "LBP")
     c.feature_type = CC_FEATURE_LBP;
   else if (fts == "HOG")
-    return set_error(CC_ERR_UNSUPPORTED, "cascade XML: HOG cascades are outside the accelerated path (Haar/LBP only)");
+    c.feature_type = CC_FEATURE_HOG;
   else
     return set_error(CC_ERR_PARSE, "cascade XML: unknown featureType '%s'", fts.c_str());
   int32_t w = 0, h = 0;
@@ -115,6 +115,12 @@ cc_status cascade_from_xml(const XmlNode& root, Cascade& c) {
   if (maxcat < 0 || maxcat > 256 || (c.feature_type == CC_FEATURE_LBP && maxcat != 256) ||
       (c.feature_type == CC_FEATURE_HAAR && maxcat != 0))
     return set_error(CC_ERR_PARSE, "cascade XML: maxCatCount %d does not match featureType %s", maxcat, fts.c_str());
+  if (c.feature_type == CC_FEATURE_HOG) {  // a HOG variable is one of N_BINS * N_CELLS components (HOGfeatures.cpp:9-14)
+    if (maxcat != 0) return set_error(CC_ERR_PARSE, "cascade XML: maxCatCount %d does not match featureType HOG", maxcat);
+    int32_t fs = 36;
+    if (fp && fp->child("featSize") && !node_int(fp->child("featSize"), fs)) return set_error(CC_ERR_PARSE, "cascade XML: bad <featSize>");
+    if (fs != 36) return set_error(CC_ERR_PARSE, "cascade XML: featSize %d does not match featureType HOG (36)", fs);
+  }
   c.max_cat_count = maxcat;
   c.subset_size = maxcat > 0 ? (maxcat + 31) / 32 : 0;
   const int node_step = 3 + (maxcat > 0 ? c.subset_size : 1);
@@ -162,7 +168,7 @@ cc_status cascade_from_xml(const XmlNode& root, Cascade& c) {
       }
       c.haar_tilted.push_back(tilted);
       c.has_tilted = c.has_tilted || tilted;
-    } else {
+    } else if (c.feature_type == CC_FEATURE_LBP) {
       const XmlNode* rn = f.child("rect");
       int32_t r[4];
       if (!rn) return set_error(CC_ERR_PARSE, "cascade XML: LBP feature without <rect>");
@@ -172,6 +178,20 @@ cc_status cascade_from_xml(const XmlNode& root, Cascade& c) {
       if (r[0] < 0 || r[1] < 0 || r[2] < 1 || r[3] < 1 || r[0] + 3 * r[2] > w || r[1] + 3 * r[3] > h)
         return set_error(CC_ERR_PARSE, "cascade XML: LBP rect (%d %d %d %d) leaves the %dx%d window", r[0], r[1], r[2], r[3], w, h);
       for (int k = 0; k < 4; k++) c.lbp_rects.push_back(r[k]);
+    } else {
+      // HOG: cell 0 of the block and the component (HOGfeatures.cpp:155-160); the block is 2 x 2 cells
+      const XmlNode* rn = f.child("rect");
+      int32_t r[5];
+      if (!rn) return set_error(CC_ERR_PARSE, "cascade XML: HOG feature without <rect>");
+      split_tokens(rn->text, tk);
+      if (tk.size() != 5 || !to_int(tk[0], r[0]) || !to_int(tk[1], r[1]) || !to_int(tk[2], r[2]) || !to_int(tk[3], r[3]) ||
+          !to_int(tk[4], r[4]))
+        return set_error(CC_ERR_PARSE, "cascade XML: malformed HOG rect '%s'", rn->text.c_str());
+      if (r[4] < 0 || r[4] >= 36) return set_error(CC_ERR_PARSE, "cascade XML: HOG component %d outside [0, 36)", r[4]);
+      // the device kernels index the window's planes with these numbers: the whole block must lie inside the window
+      if (r[0] < 0 || r[1] < 0 || r[2] < 1 || r[3] < 1 || r[2] > w || r[3] > h || r[0] + 2 * r[2] > w || r[1] + 2 * r[3] > h)
+        return set_error(CC_ERR_PARSE, "cascade XML: HOG block of cell (%d %d %d %d) leaves the %dx%d window", r[0], r[1], r[2], r[3], w, h);
+      for (int k = 0; k < 5; k++) c.hog_feats.push_back(r[k]);
     }
   }
   const int nfeat = c.n_features();
@@ -336,15 +356,16 @@ cc_status cc_cascade_save_xml(const cc_cascade* c, const char* path) {
   const CNumericLocale c_numbers;  // "%.8e" / strtod must not follow the host program's LC_NUMERIC
   if (!c || !path) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_save_xml: null argument");
   const Cascade& m = c->m;
-  const bool haar = m.feature_type == CC_FEATURE_HAAR;
+  const bool haar = m.feature_type == CC_FEATURE_HAAR, hog = m.feature_type == CC_FEATURE_HOG;
   std::ostringstream o;
   int max_weak = 0;
   for (int n : m.stage_ntrees) max_weak = std::max(max_weak, n);
   o << "<?xml version=\"1.0\"?>\n<opencv_storage>\n<cascade>\n";
-  o << "  <stageType>BOOST</stageType>\n  <featureType>" << (haar ? "HAAR" : "LBP") << "</featureType>\n";
+  o << "  <stageType>BOOST</stageType>\n  <featureType>" << (haar ? "HAAR" : hog ? "HOG" : "LBP") << "</featureType>\n";
   o << "  <height>" << m.win_h << "</height>\n  <width>" << m.win_w << "</width>\n";
   o << "  <stageParams>\n    <maxWeakCount>" << max_weak << "</maxWeakCount></stageParams>\n";
-  o << "  <featureParams>\n    <maxCatCount>" << m.max_cat_count << "</maxCatCount>\n    <featSize>1</featSize></featureParams>\n";
+  o << "  <featureParams>\n    <maxCatCount>" << m.max_cat_count << "</maxCatCount>\n    <featSize>" << (hog ? 36 : 1)
+    << "</featSize></featureParams>\n";
   o << "  <stageNum>" << m.stage_ntrees.size() << "</stageNum>\n  <stages>\n";
   for (size_t s = 0; s < m.stage_ntrees.size(); s++) {
     // the model keeps (float)stageThreshold - 1e-5f; write back a value that parses to the same float after the
@@ -383,6 +404,9 @@ cc_status cc_cascade_save_xml(const cc_cascade* c, const char* path) {
         o << "        <_>\n          " << r[0] << " " << r[1] << " " << r[2] << " " << r[3] << " " << real_text(w) << "</_>\n";
       }
       o << "      </rects>\n      <tilted>" << (m.haar_tilted[f] ? 1 : 0) << "</tilted></_>\n";
+    } else if (hog) {
+      const int32_t* r = &m.hog_feats[(size_t)f * 5];
+      o << "    <_>\n      <rect>\n        " << r[0] << " " << r[1] << " " << r[2] << " " << r[3] << " " << r[4] << "</rect></_>\n";
     } else {
       const int32_t* r = &m.lbp_rects[(size_t)f * 4];
       o << "    <_>\n      <rect>\n        " << r[0] << " " << r[1] << " " << r[2] << " " << r[3] << "</rect></_>\n";
@@ -539,6 +563,10 @@ cc_status cc_cascade_features(const cc_cascade* c, const int32_t** rects, const 
     if (rects) *rects = c->m.haar_rects.data();
     if (weights) *weights = c->m.haar_weights.data();
     if (tilted) *tilted = c->m.haar_tilted.data();
+  } else if (c->m.feature_type == CC_FEATURE_HOG) {
+    if (rects) *rects = c->m.hog_feats.data();
+    if (weights) *weights = nullptr;
+    if (tilted) *tilted = nullptr;
   } else {
     if (rects) *rects = c->m.lbp_rects.data();
     if (weights) *weights = nullptr;

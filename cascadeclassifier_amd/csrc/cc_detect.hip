@@ -37,6 +37,7 @@
 #include <unordered_set>
 
 #include "cc_hip_util.h"
+#include "cc_hog_device.h"
 #include "cc_internal.h"
 
 namespace ccamd {
@@ -694,6 +695,101 @@ __global__ __launch_bounds__(64) void k_negmine_gather(const uint8_t* __restrict
   }
 }
 
+// HOG cascades. NegReader::get copies each window out of its ladder level and setImage takes its border from that copy
+// (HOGfeatures.cpp:173-183), so the outer ring of every window has gradients of its own: planes cannot be shared between
+// overlapping windows or computed once per level. One workgroup per stream window builds the window's ten integral planes
+// in LDS with the evaluator's setImage code (cc_hog_device.h) and walks the trained stages on them.
+struct HogMineNode {  // a tree node with its variable as LDS offsets into the window's planes
+  int cell[4];  // bin plane at the cell's corners: top-left, top-right, bottom-left, bottom-right
+  int norm[4];  // norm plane at the block's outer corners, same order
+  float thr;
+  int left, right;  // child > 0: node index inside the tree; child <= 0: leaf index -child
+  int pad;
+};
+struct HogMineArgs {
+  const uint8_t* pyr;  // ladder levels, image f at pyr + f * pyr_image_bytes (blockIdx.y = image)
+  size_t pyr_image_bytes;
+  const MineLevel* levels;
+  int n_levels;
+  long long n_windows;
+  int W0, H0, ox, oy, sx, sy;
+  int nstages;
+  const int* stage_first;
+  const int* stage_ntrees;
+  const float* stage_thr;
+  const HogMineNode* nodes;
+  const int* tree_root;
+  const int* tree_leaf0;
+  const float* leaves;
+  uint8_t* pass;  // [image][n_windows]
+  int wave;       // 1: stumps of a stage across the lanes of wavefront 0 (order-independent sums); 0: one lane walks
+};
+constexpr int HOG_MINE_THREADS = 256;
+
+// operator() of one variable (hog_var_value's arithmetic, corners already resolved to LDS offsets)
+__device__ __forceinline__ float hog_mine_value(const float* P, const HogMineNode& n) {
+  const float res = ((P[n.cell[0]] - P[n.cell[1]]) - P[n.cell[2]]) + P[n.cell[3]];
+  const float nf = ((P[n.norm[0]] - P[n.norm[1]]) - P[n.norm[2]]) + P[n.norm[3]];
+  return hog_value_from(res, nf);
+}
+
+// LDS: planes [10][H0 + 1][W0 + 1] float, magnitudes [H0][W0] float, bins [H0][W0] bytes (hog_mine_lds_bytes)
+__global__ __launch_bounds__(HOG_MINE_THREADS) void k_negmine_hog(HogMineArgs A) {
+  extern __shared__ float hog_lds[];
+  const long long i = blockIdx.x;
+  int x, y;
+  const MineLevel L = mine_window(A.levels, A.n_levels, i, A.ox, A.oy, A.sx, A.sy, x, y);
+  const int W = A.W0, H = A.H0, sw = W + 1;
+  const size_t plane = (size_t)sw * (H + 1);
+  float* planes = hog_lds;
+  float* mag = planes + 10 * plane;
+  uint8_t* bins = reinterpret_cast<uint8_t*>(mag + (size_t)W * H);
+  const uint8_t* px = A.pyr + (size_t)blockIdx.y * A.pyr_image_bytes + L.img_ofs + (size_t)y * L.pitch8 + x;
+  hog_window_grad(px, (size_t)L.pitch8, W, H, mag, bins, threadIdx.x, HOG_MINE_THREADS);
+  __syncthreads();
+  // row sums go to rows 1..H of each plane; the column pass turns them into the integral in place
+  hog_row_pass(mag, bins, W, H, 0, 10, planes + sw, plane, threadIdx.x, HOG_MINE_THREADS);
+  __syncthreads();
+  hog_col_pass(planes + sw, plane, W, H, 0, 10, [=](int c, int xx, int yy) { return planes + c * plane + (size_t)yy * sw + xx; },
+               threadIdx.x, HOG_MINE_THREADS);
+  __syncthreads();
+  if (threadIdx.x >= 64) return;  // wavefront 0 walks the stages
+  const int lane = threadIdx.x;
+  uint8_t pass = 1;
+  if (A.wave) {
+    for (int st = 0; st < A.nstages; st++) {
+      const int first = A.stage_first[st], nt = A.stage_ntrees[st];
+      double part = 0;
+      for (int t = first + lane; t < first + nt; t += 64) {
+        const HogMineNode& n = A.nodes[A.tree_root[t]];
+        part += (double)A.leaves[A.tree_leaf0[t] - (hog_mine_value(planes, n) <= n.thr ? n.left : n.right)];
+      }
+      if (wave_sum_f64(part) < (double)A.stage_thr[st]) {
+        pass = 0;
+        break;
+      }
+    }
+  } else if (lane == 0) {
+    for (int st = 0; st < A.nstages && pass; st++) {
+      double acc = 0;
+      const int first = A.stage_first[st], nt = A.stage_ntrees[st];
+      for (int t = first; t < first + nt; t++) {
+        const int root = A.tree_root[t];
+        int idx = 0;
+        do {
+          const HogMineNode& n = A.nodes[root + idx];
+          idx = hog_mine_value(planes, n) <= n.thr ? n.left : n.right;
+        } while (idx > 0);
+        acc += (double)A.leaves[A.tree_leaf0[t] - idx];
+      }
+      if (acc < (double)A.stage_thr[st]) pass = 0;
+    }
+  }
+  if (lane == 0) A.pass[(size_t)blockIdx.y * A.n_windows + i] = pass;
+}
+
+static size_t hog_mine_lds_bytes(int W, int H) { return (size_t)10 * (W + 1) * (H + 1) * 4 + (size_t)W * H * 5; }
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -1062,6 +1158,8 @@ struct cc_negminer {
   int device = 0;
   hipStream_t stream = nullptr;
   DevBuf<MineNode> d_nodes;
+  DevBuf<HogMineNode> d_hog_nodes;  // HOG cascades (k_negmine_hog)
+  size_t hog_lds = 0;               // k_negmine_hog's dynamic LDS per workgroup
   DevBuf<int> d_stage_first, d_stage_ntrees, d_tree_root, d_tree_leaf0;
   DevBuf<float> d_stage_thr, d_leaves;
   // per-image workspace
@@ -1091,6 +1189,15 @@ struct cc_negminer {
 };
 
 namespace ccamd {
+
+// Detection and its run-time specialisation are Haar / LBP only: nothing in the reference defines detection with a HOG
+// cascade. Every detector entry point calls this before the model reaches a kernel or a table builder (the LBP branches
+// would read lbp_rects, which a HOG model leaves empty).
+static cc_status refuse_hog(const Cascade& m, const char* who) {
+  if (m.feature_type == CC_FEATURE_HAAR || m.feature_type == CC_FEATURE_LBP) return CC_OK;
+  return set_error(CC_ERR_UNSUPPORTED, "%s: %s cascades are not supported for detection (Haar and LBP only)", who,
+                   m.feature_type == CC_FEATURE_HOG ? "HOG" : "unknown-type");
+}
 
 static cc_status ensure_device(int device) {
   int n = 0;
@@ -3023,6 +3130,7 @@ static cc_status compile_specialised(const std::string& src, const std::string& 
 // Host half of the specialisation: source for the first stages (whole stages within the code-size budget) compiled for
 // `arch`. No device calls: safe on a background thread.
 static cc_status spec_build(const Cascade& m, int n_stages, const std::string& arch, std::vector<SpecCode>& codes, int& k_out, int& tmode_out) {
+  if (cc_status hs = refuse_hog(m, "cc_detector_specialize"); hs != CC_OK) return hs;
   if (m.max_nodes_per_tree > 1) return set_error(CC_ERR_UNSUPPORTED, "cc_detector_specialize: stump cascades only");
   int k = 0, stumps = 0;
   int budget = 320;  // instruction cache: more stages measured no faster, 12 stages slower
@@ -3247,6 +3355,7 @@ cc_status cc_detector_create(const cc_cascade* c, int device, int max_batch, cc_
   if (!c || !out) return set_error(CC_ERR_INVALID_ARG, "cc_detector_create: null argument");
   *out = nullptr;
   if (max_batch < 1 || max_batch > 4096) return set_error(CC_ERR_INVALID_ARG, "cc_detector_create: max_batch %d out of range", max_batch);
+  if (cc_status hs = refuse_hog(c->m, "cc_detector_create"); hs != CC_OK) return hs;
 
   cc_status st = ensure_device(device);
   if (st != CC_OK) return st;
@@ -3442,6 +3551,7 @@ cc_status cc_detector_set_stream(cc_detector* d, void* hip_stream) {
 
 cc_status cc_detector_specialize(cc_detector* d, int n_stages) {
   if (!d) return set_error(CC_ERR_INVALID_ARG, "cc_detector_specialize: null detector");
+  if (cc_status hs = refuse_hog(d->m, "cc_detector_specialize"); hs != CC_OK) return hs;
   cc_status st = ensure_device(d->device);
   if (st != CC_OK) return st;
   if (d->spec_thread.joinable()) d->spec_thread.join();  // a background build, if any, is superseded
@@ -3470,6 +3580,7 @@ cc_status cc_detector_specialize(cc_detector* d, int n_stages) {
 cc_status cc_detector_specialize_async(cc_detector* d, int n_stages) {
   if (!d) return set_error(CC_ERR_INVALID_ARG, "cc_detector_specialize_async: null detector");
   if (n_stages <= 0) return set_error(CC_ERR_INVALID_ARG, "cc_detector_specialize_async: n_stages must be positive");
+  if (cc_status hs = refuse_hog(d->m, "cc_detector_specialize_async"); hs != CC_OK) return hs;
   cc_status st = ensure_device(d->device);
   if (st != CC_OK) return st;
   return spec_start_background(d, n_stages);
@@ -3479,6 +3590,7 @@ int cc_detector_specialized_stages(const cc_detector* d) { return d ? d->spec_st
 
 cc_status cc_cascade_compile_specialized(const cc_cascade* c, int n_stages, const char* arch, size_t* code_bytes) {
   if (!c || !arch || !code_bytes) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_compile_specialized: null argument");
+  if (cc_status hs = refuse_hog(c->m, "cc_cascade_compile_specialized"); hs != CC_OK) return hs;
   std::vector<SpecCode> code;
   int k = 0;
   int tmode = 0;
@@ -3938,8 +4050,40 @@ cc_status cc_negminer_create(const cc_cascade* c, int device, cc_negminer** out)
   CC_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
   CC_HIP(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
   const Cascade& M = m->m;
-  const bool haar = M.feature_type == CC_FEATURE_HAAR;
-  std::vector<MineNode> nodes(M.node_feature.size());
+  const bool haar = M.feature_type == CC_FEATURE_HAAR, hog = M.feature_type == CC_FEATURE_HOG;
+  if (!haar && !hog && M.feature_type != CC_FEATURE_LBP)
+    return set_error(CC_ERR_UNSUPPORTED, "cc_negminer_create: feature type %d", M.feature_type);
+  if (hog) {
+    m->hog_lds = hog_mine_lds_bytes(M.win_w, M.win_h);
+    if (m->hog_lds > 160 * 1024)
+      return set_error(CC_ERR_UNSUPPORTED, "cc_negminer_create: HOG window %dx%d needs %zu bytes of LDS per window (limit %d)", M.win_w,
+                       M.win_h, m->hog_lds, 160 * 1024);
+    if (m->hog_lds > 64 * 1024)
+      CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_negmine_hog), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->hog_lds));
+    const int sw = M.win_w + 1, plane = sw * (M.win_h + 1);
+    std::vector<HogMineNode> hn(M.node_feature.size());
+    for (size_t i = 0; i < hn.size(); i++) {
+      HogMineNode& n = hn[i];
+      std::memset(&n, 0, sizeof(n));
+      // the block lies inside the window (checked at load), so every offset is inside the planes
+      const int32_t* f = &M.hog_feats[(size_t)M.node_feature[i] * 5];
+      const int x = f[0], y = f[1], cw = f[2], ch = f[3], cell = f[4] / 9, bin = f[4] % 9;
+      const int cx = x + (cell & 1) * cw, cy = y + (cell >> 1) * ch;
+      n.cell[0] = bin * plane + cy * sw + cx;
+      n.cell[1] = bin * plane + cy * sw + cx + cw;
+      n.cell[2] = bin * plane + (cy + ch) * sw + cx;
+      n.cell[3] = bin * plane + (cy + ch) * sw + cx + cw;
+      n.norm[0] = 9 * plane + y * sw + x;
+      n.norm[1] = 9 * plane + y * sw + x + 2 * cw;
+      n.norm[2] = 9 * plane + (y + 2 * ch) * sw + x;
+      n.norm[3] = 9 * plane + (y + 2 * ch) * sw + x + 2 * cw;
+      n.thr = M.node_threshold[i];
+      n.left = M.node_left[i];
+      n.right = M.node_right[i];
+    }
+    CC_HIP(m->d_hog_nodes.upload(hn, m->stream));
+  }
+  std::vector<MineNode> nodes(hog ? 0 : M.node_feature.size());
   for (size_t i = 0; i < nodes.size(); i++) {
     MineNode& n = nodes[i];
     std::memset(&n, 0, sizeof(n));
@@ -4075,7 +4219,7 @@ static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n
   const FrontLayout& FL = m->front.L;
   const Cascade& M = m->m;
   const int W0 = M.win_w, H0 = M.win_h, nl = (int)FL.sd.size(), K = n_images;
-  const bool haar = M.feature_type == CC_FEATURE_HAAR, tilt = haar && M.has_tilted;
+  const bool haar = M.feature_type == CC_FEATURE_HAAR, tilt = haar && M.has_tilted, hog = M.feature_type == CC_FEATURE_HOG;
   const long long wins = P.wins;
   *n_windows = wins;
   if (wins * K > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "%s: %lld windows (%d images), capacity %lld", who, wins * K, K, (long long)cap);
@@ -4084,8 +4228,10 @@ static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n
   const size_t chan_elems = FL.int_frame_elems, spitch = (size_t)align_up(width, 4), src_bytes = spitch * (size_t)height;
   CC_HIP(m->d_src.ensure(src_bytes * K));
   CC_HIP(m->d_pyr.ensure(FL.pyr_frame_bytes * K));
-  CC_HIP(m->d_integ.ensure(chan_elems * (size_t)nchan * K));
-  CC_HIP(m->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)nchan * K, 4)));
+  if (!hog) {  // HOG windows build their planes from the levels' pixels: no integral images
+    CC_HIP(m->d_integ.ensure(chan_elems * (size_t)nchan * K));
+    CC_HIP(m->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)nchan * K, 4)));
+  }
   CC_HIP(m->d_pass.ensure((size_t)std::max<long long>(wins * K, 1)));
   st = pinned_ensure(&m->h_src, &m->h_src_bytes, src_bytes * K);
   if (st != CC_OK) return st;
@@ -4126,16 +4272,44 @@ static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n
     io.row_stride = spitch;
     io.frame_stride = src_bytes;
     io.pyr = m->d_pyr.p + (size_t)k0 * FL.pyr_frame_bytes;
-    io.integ = m->d_integ.p + (size_t)k0 * nchan * chan_elems;
-    io.hbuf = m->d_hbuf.p + (size_t)k0 * nchan * FL.h_frame_elems;
+    if (!hog) {
+      io.integ = m->d_integ.p + (size_t)k0 * nchan * chan_elems;
+      io.hbuf = m->d_hbuf.p + (size_t)k0 * nchan * FL.h_frame_elems;
+    }
     if (tilt) {
       io.diag = m->d_diag.p + (size_t)k0 * 2 * chan_elems;
       io.tseg = m->d_tseg.p + (size_t)k0 * FL.tseg_frame_elems;
     }
     io.nchan = nchan;
     io.sq = haar;
-    launch_front(s, m->front, io, n, FRONT_RESIZE | FRONT_INTEGRALS);
+    launch_front(s, m->front, io, n, hog ? FRONT_RESIZE : FRONT_RESIZE | FRONT_INTEGRALS);
     if (wins == 0) return;
+    if (hog) {
+      HogMineArgs H;
+      H.pyr = io.pyr;
+      H.pyr_image_bytes = FL.pyr_frame_bytes;
+      H.levels = A.levels;
+      H.n_levels = A.n_levels;
+      H.n_windows = wins;
+      H.W0 = W0;
+      H.H0 = H0;
+      H.ox = ox;
+      H.oy = oy;
+      H.sx = A.sx;
+      H.sy = A.sy;
+      H.nstages = A.nstages;
+      H.stage_first = A.stage_first;
+      H.stage_ntrees = A.stage_ntrees;
+      H.stage_thr = A.stage_thr;
+      H.nodes = m->d_hog_nodes.p;
+      H.tree_root = A.tree_root;
+      H.tree_leaf0 = A.tree_leaf0;
+      H.leaves = A.leaves;
+      H.pass = m->d_pass.p + (size_t)k0 * (size_t)wins;
+      H.wave = wave_mode ? 1 : 0;
+      hipLaunchKernelGGL(k_negmine_hog, dim3((unsigned)wins, n), dim3(HOG_MINE_THREADS), m->hog_lds, s, H);
+      return;
+    }
     MineArgs B = A;
     B.integ = io.integ;
     B.pass = m->d_pass.p + (size_t)k0 * (size_t)wins;

@@ -1267,12 +1267,16 @@ cc_status cc_eval_get_sample(cc_evaluator* e, int idx, int32_t* sum, int32_t* ti
   return CC_OK;
 }
 
+static const char* feature_type_name(int t) {
+  return t == CC_FEATURE_HAAR ? "HAAR" : t == CC_FEATURE_LBP ? "LBP" : t == CC_FEATURE_HOG ? "HOG" : "unknown";
+}
+
 cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const int32_t* sample_idx, int n_samples, uint8_t* out) {
   if (!e || !c || !out) return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: null argument");
   const Cascade& m = c->m;
   if (m.feature_type != e->type || m.win_w != e->W || m.win_h != e->H)
-    return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: cascade (%s %dx%d) does not match the evaluator (%dx%d)",
-                     m.feature_type == CC_FEATURE_HAAR ? "HAAR" : "LBP", m.win_w, m.win_h, e->W, e->H);
+    return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: cascade (%s %dx%d) does not match the evaluator (%s %dx%d)",
+                     feature_type_name(m.feature_type), m.win_w, m.win_h, feature_type_name(e->type), e->W, e->H);
   if (m.has_tilted && !e->use_tilted) return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: cascade has tilted features but the evaluator keeps no tilted integrals");
   if (n_samples < 0) return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: negative sample count");
   cc_status st = eval_device(e);
@@ -1283,6 +1287,9 @@ cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const in
   const int32_t* d_idx = nullptr;
   st = upload_indices(e, sample_idx, n_samples, &d_idx);
   if (st != CC_OK) return st;
+  if (e->type == CC_FEATURE_HOG) return hog_predict(e, m, d_idx, n_samples, out);
+  if (e->type != CC_FEATURE_HAAR && e->type != CC_FEATURE_LBP)
+    return set_error(CC_ERR_UNSUPPORTED, "cc_eval_predict_cascade: feature type %d", e->type);
   const bool haar = e->type == CC_FEATURE_HAAR;
   const bool trees = m.max_nodes_per_tree > 1;
   // per-record tables are indexed by stump for stump cascades and by node for general trees

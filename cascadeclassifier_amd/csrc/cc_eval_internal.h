@@ -80,6 +80,9 @@ cc_status hog_launch_set_images(cc_evaluator* e, const uint8_t* d_imgs, int n, i
 // operator() for variables [vb, ve) x ns samples into d_out[(vi - vb) * pitch + s] (pitch 0 = ns). Caller holds e->mu.
 cc_status hog_launch_batch(cc_evaluator* e, int vb, int ve, const int32_t* d_idx, int ns, float* d_out, size_t out_pitch);
 cc_status hog_launch_list(cc_evaluator* e, const int32_t* d_list, int n, int si, float* d_out);
+// CvCascadeClassifier::predict of HOG cascade m (type and window checked by the caller) on ns stored samples (d_idx:
+// device indices or NULL for 0..ns-1) into host out; synchronous. Caller holds e->mu.
+cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, int ns, uint8_t* out);
 // Host mirror: the ten planes of one window ([cols][10], the device layout) and one variable's value on them.
 void hog_host_planes(const cc_evaluator* e, const uint8_t* px, std::vector<float>& planes);
 float hog_host_value(const cc_evaluator* e, const float* planes, int vi);

@@ -17,59 +17,9 @@
 #include <mutex>
 
 #include "cc_eval_internal.h"
+#include "cc_hog_device.h"
 
 namespace ccamd {
-
-// ------------------------------------------------------------------------------------------------
-// Per-pixel gradient and orientation bin (HOGfeatures.cpp:209-231). One definition for the device kernels and the host
-// mirror: every operation is an IEEE basic operation or an explicit fused multiply-add, so both give the same bits.
-// ------------------------------------------------------------------------------------------------
-// cv::cartToPolar(..., false) -> hal::fastAtan32f (OpenCV 4.6.0, core/src/mathfuncs_core.simd.hpp): polynomial
-// coefficients atan2_p1..p7 pre-scaled to degrees, each product rounded to float.
-constexpr float kHogP1 = 0.9997878412794807f * (float)(180 / M_PI);
-constexpr float kHogP3 = -0.3258083974640975f * (float)(180 / M_PI);
-constexpr float kHogP5 = 0.1555786518463281f * (float)(180 / M_PI);
-constexpr float kHogP7 = -0.04432655554792128f * (float)(180 / M_PI);
-
-__host__ __device__ inline float hog_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-
-// dx, dy: integer central differences in [-255, 255]. Writes the magnitude and returns the bin in [0, 9).
-__host__ __device__ inline int hog_grad_bin(int dx, int dy, float* mag) {
-  const float fx = (float)dx, fy = (float)dy;
-  *mag = sqrtf(fx * fx + fy * fy);  // hal::magnitude32f; dx^2 + dy^2 < 2^24 is exact in float
-  // v_atan_f32::compute: the SIMD body (v_fma, fused on AVX2 / NEON dispatch) is the form restated here
-  const float ax = fabsf(fx), ay = fabsf(fy);
-  const float c = fminf(ax, ay) / (fmaxf(ax, ay) + (float)DBL_EPSILON);
-  const float cc = c * c;
-  float a = hog_fma(hog_fma(hog_fma(cc, kHogP7, kHogP5), cc, kHogP3), cc, kHogP1) * c;
-  if (ax < ay) a = 90.f - a;
-  if (fx < 0.f) a = 180.f - a;
-  if (fy < 0.f) a = 360.f - a;
-  const float angle = a * (float)(M_PI / 180);  // fastAtan32f's scale for radians
-  // HOGfeatures.cpp:218-226: angleScale = (float)(nbins / CV_PI); cvFloor(angle * angleScale - 0.5f), wrapped once
-  const float t = angle * (float)(9 / M_PI) - 0.5f;
-  int b = (int)floorf(t);
-  if (b < 0)
-    b += 9;
-  else if (b >= 9)
-    b -= 9;
-  return b;
-}
-
-// operator() of one variable (HOGfeatures.h:84-112) on one sample's interleaved planes. Lattice point (i, j) of the block
-// (i, j in 0..2 along x, y) is entry (y + j * ch) * (W + 1) + x + i * cw.
-__host__ __device__ inline float hog_value_from(float res, float nf) { return res > 0.001f ? res / (nf + 0.001f) : 0.f; }
-
-__host__ __device__ inline float hog_var_value(const float* planes, int sw, const int32_t* blk /* x, y, cw, ch */, int comp) {
-  const int cell = comp / 9, bin = comp % 9;
-  const int x = blk[0], y = blk[1], cw = blk[2], ch = blk[3];
-  const int cx = x + (cell & 1) * cw, cy = y + (cell >> 1) * ch;
-  auto at = [&](int px, int py, int chn) { return planes[((size_t)py * sw + px) * 10 + chn]; };
-  const float res = ((at(cx, cy, bin) - at(cx + cw, cy, bin)) - at(cx, cy + ch, bin)) + at(cx + cw, cy + ch, bin);
-  // normFactor: fastRect[0].p0 - fastRect[1].p1 - fastRect[2].p2 + fastRect[3].p3, the block's outer corners
-  const float nf = ((at(x, y, 9) - at(x + 2 * cw, y, 9)) - at(x, y + 2 * ch, 9)) + at(x + 2 * cw, y + 2 * ch, 9);
-  return hog_value_from(res, nf);
-}
 
 // ------------------------------------------------------------------------------------------------
 // setImage for a batch: one block per sample.
@@ -91,49 +41,15 @@ __global__ __launch_bounds__(HOG_SET_THREADS) void k_hog_set_images(const uint8_
   uint8_t* bins = reinterpret_cast<uint8_t*>(rp + (size_t)planes_per_pass * H * sw);  // [H][W]
   const uint8_t* img = imgs + (size_t)blockIdx.x * W * H;
   float* out = planes + (size_t)(first_idx + blockIdx.x) * cols * 10;
-  for (int i = threadIdx.x; i < W * H; i += HOG_SET_THREADS) {
-    const int y = i / W, x = i - y * W;
-    const int xl = max(x - 1, 0), xr = min(x + 1, W - 1), yu = max(y - 1, 0), yd = min(y + 1, H - 1);
-    const int dx = (int)img[y * W + xr] - (int)img[y * W + xl];
-    const int dy = (int)img[yd * W + x] - (int)img[yu * W + x];
-    float m;
-    bins[i] = (uint8_t)hog_grad_bin(dx, dy, &m);
-    mag[i] = m;
-  }
+  hog_window_grad(img, W, W, H, mag, bins, threadIdx.x, HOG_SET_THREADS);
   __syncthreads();
   for (int c0 = 0; c0 < 10; c0 += planes_per_pass) {
     const int P = min(planes_per_pass, 10 - c0);
-    for (int t = threadIdx.x; t < P * H; t += HOG_SET_THREADS) {
-      const int y = t / P, c = c0 + t % P;
-      float* row = rp + ((size_t)(c - c0) * H + y) * sw;
-      const float* mrow = mag + y * W;
-      const uint8_t* brow = bins + y * W;
-      float s = 0.f;
-      row[0] = 0.f;
-      if (c == 9) {
-        for (int x = 0; x < W; x++) {
-          s += mrow[x];
-          row[x + 1] = s;
-        }
-      } else {
-        for (int x = 0; x < W; x++) {
-          if (brow[x] == c) s += mrow[x];
-          row[x + 1] = s;
-        }
-      }
-    }
+    hog_row_pass(mag, bins, W, H, c0, P, rp, (size_t)H * sw, threadIdx.x, HOG_SET_THREADS);
     __syncthreads();
-    for (int t = threadIdx.x; t < P * sw; t += HOG_SET_THREADS) {
-      const int x = t / P, c = c0 + t % P;
-      const float* col = rp + (size_t)(c - c0) * H * sw + x;
-      float* o = out + (size_t)x * 10 + c;
-      float acc = 0.f;
-      o[0] = 0.f;
-      for (int y = 0; y < H; y++) {
-        acc = acc + col[(size_t)y * sw];
-        o[(size_t)(y + 1) * sw * 10] = acc;
-      }
-    }
+    // lanes of a wavefront cover consecutive (column, plane) pairs: contiguous stores
+    hog_col_pass(rp, (size_t)H * sw, W, H, c0, P, [=](int c, int x, int y) { return out + ((size_t)y * sw + x) * 10 + c; }, threadIdx.x,
+                 HOG_SET_THREADS);
     __syncthreads();  // rp is rewritten by the next group of planes
   }
 }
@@ -205,6 +121,55 @@ __global__ void k_hog_eval_list(const float* __restrict__ planes, const int32_t*
   if (i >= n) return;
   const int vi = list[i];
   out[i] = hog_var_value(planes, sw, blocks + 4 * (vi / 36), vi % 36);
+}
+
+// CvCascadeClassifier::predict on stored samples (boost.cpp:461-477, o_cvcascadeboosttree.cpp:16-39): one thread per
+// sample walks the stages on the sample's planes; a variable's value is operator()'s (hog_var_value), an ordered split
+// goes left on `<=`, the stage sum is a double over float leaves in tree order, a stage fails iff sum < its stored
+// threshold (which already has CV_THRESHOLD_EPS subtracted). Stumps are one-node trees.
+struct HogNodeDev {
+  int32_t blk[4];  // x, y, cell w, cell h of the block
+  int32_t comp;
+  float thr;
+  int32_t left, right;  // child > 0: node index inside the tree; child <= 0: leaf index -child
+};
+
+struct HogPredictArgs {
+  const float* planes;
+  int sw, cols;
+  const int32_t* sample_idx;  // optional
+  int n_samples, nstages;
+  const int* stage_ntrees;
+  const float* stage_thr;
+  const int* tree_root;
+  const int* tree_leaf0;
+  const HogNodeDev* nodes;
+  const float* leaves;
+  uint8_t* out;
+};
+
+__global__ __launch_bounds__(64) void k_hog_predict(HogPredictArgs A) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= A.n_samples) return;
+  const int si = A.sample_idx ? A.sample_idx[s] : s;
+  const float* planes = A.planes + (size_t)si * A.cols * 10;
+  int t = 0;
+  uint8_t pass = 1;
+  for (int st = 0; st < A.nstages && pass; st++) {
+    double acc = 0;
+    const int nt = A.stage_ntrees[st];
+    for (int i = 0; i < nt; i++, t++) {
+      const int root = A.tree_root[t];
+      int idx = 0;
+      do {
+        const HogNodeDev& n = A.nodes[root + idx];
+        idx = hog_var_value(planes, A.sw, n.blk, n.comp) <= n.thr ? n.left : n.right;
+      } while (idx > 0);
+      acc += (double)A.leaves[A.tree_leaf0[t] - idx];
+    }
+    if (acc < (double)A.stage_thr[st]) pass = 0;
+  }
+  A.out[s] = pass;
 }
 
 // Bin and magnitude of every (dx, dy) in [-255, 255]^2, pair (dx, dy) at (dy + 255) * 511 + dx + 255.
@@ -295,6 +260,56 @@ cc_status hog_launch_list(cc_evaluator* e, const int32_t* d_list, int n, int si,
   hipLaunchKernelGGL(k_hog_eval_list, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->d_hog.p + (size_t)si * e->cols * 10,
                      e->d_hog_blocks.p, e->W + 1, d_list, n, d_out);
   CC_HIP(hipGetLastError());
+  return CC_OK;
+}
+
+cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, int ns, uint8_t* out) {
+  std::vector<HogNodeDev> nodes(m.node_feature.size());
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const int32_t* f = &m.hog_feats[(size_t)m.node_feature[i] * 5];  // validated inside the window at load
+    HogNodeDev& n = nodes[i];
+    for (int k = 0; k < 4; k++) n.blk[k] = f[k];
+    n.comp = f[4];
+    n.thr = m.node_threshold[i];
+    n.left = m.node_left[i];
+    n.right = m.node_right[i];
+  }
+  const std::vector<int> ntrees(m.stage_ntrees.begin(), m.stage_ntrees.end());
+  const std::vector<int> root(m.tree_first_node.begin(), m.tree_first_node.end()), leaf0(m.tree_first_leaf.begin(), m.tree_first_leaf.end());
+  EBuf<HogNodeDev> d_nodes;
+  EBuf<int> d_ntrees, d_root, d_leaf0;
+  EBuf<float> d_sthr, d_leaves;
+  CC_HIP(d_nodes.ensure(nodes.size()));
+  CC_HIP(copy_sync(d_nodes.p, nodes.data(), nodes.size() * sizeof(HogNodeDev), hipMemcpyHostToDevice, e->stream));
+  CC_HIP(d_ntrees.ensure(ntrees.size()));
+  CC_HIP(copy_sync(d_ntrees.p, ntrees.data(), ntrees.size() * 4, hipMemcpyHostToDevice, e->stream));
+  CC_HIP(d_sthr.ensure(ntrees.size()));
+  CC_HIP(copy_sync(d_sthr.p, m.stage_threshold.data(), ntrees.size() * 4, hipMemcpyHostToDevice, e->stream));
+  CC_HIP(d_root.ensure(root.size()));
+  CC_HIP(copy_sync(d_root.p, root.data(), root.size() * 4, hipMemcpyHostToDevice, e->stream));
+  CC_HIP(d_leaf0.ensure(leaf0.size()));
+  CC_HIP(copy_sync(d_leaf0.p, leaf0.data(), leaf0.size() * 4, hipMemcpyHostToDevice, e->stream));
+  CC_HIP(d_leaves.ensure(m.leaves.size()));
+  CC_HIP(copy_sync(d_leaves.p, m.leaves.data(), m.leaves.size() * 4, hipMemcpyHostToDevice, e->stream));
+  CC_HIP(e->d_pred.ensure((size_t)ns));
+  HogPredictArgs A;
+  A.planes = e->d_hog.p;
+  A.sw = e->W + 1;
+  A.cols = e->cols;
+  A.sample_idx = d_idx;
+  A.n_samples = ns;
+  A.nstages = (int)ntrees.size();
+  A.stage_ntrees = d_ntrees.p;
+  A.stage_thr = d_sthr.p;
+  A.tree_root = d_root.p;
+  A.tree_leaf0 = d_leaf0.p;
+  A.nodes = d_nodes.p;
+  A.leaves = d_leaves.p;
+  A.out = e->d_pred.p;
+  hipLaunchKernelGGL(k_hog_predict, dim3((ns + 63) / 64), dim3(64), 0, e->stream, A);
+  CC_HIP(hipGetLastError());
+  CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)ns, hipMemcpyDeviceToHost, e->stream));
+  CC_HIP(hipStreamSynchronize(e->stream));  // the tables above are freed on return
   return CC_OK;
 }
 

@@ -78,7 +78,12 @@ struct Cascade {
   std::vector<float> haar_weights;   // [n][3]
   std::vector<int32_t> haar_tilted;  // [n]
   std::vector<int32_t> lbp_rects;    // [n][4]
-  int n_features() const { return feature_type == CC_FEATURE_HAAR ? (int)haar_tilted.size() : (int)(lbp_rects.size() / 4); }
+  std::vector<int32_t> hog_feats;    // [n][5]: x, y, cell w, cell h of the block's cell 0, component in [0, 36)
+  int n_features() const {
+    return feature_type == CC_FEATURE_HAAR ? (int)haar_tilted.size()
+           : feature_type == CC_FEATURE_HOG ? (int)(hog_feats.size() / 5)
+                                            : (int)(lbp_rects.size() / 4);
+  }
 };
 cc_status cascade_from_xml(const XmlNode& root, Cascade& out);
 

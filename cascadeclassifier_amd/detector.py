@@ -144,6 +144,8 @@ class CascadeClassifier:
             rects = _view(r, C.c_int32, nf * 12).reshape(nf, 3, 4)
             weights = _view(w, C.c_float, nf * 3).reshape(nf, 3)
             tilted = _view(t, C.c_int32, nf)
+        elif inf["feature_type"] == L.CC_FEATURE_HOG:  # cell 0 of the block (x y w h) and the component in [0, 36)
+            rects, weights, tilted = _view(r, C.c_int32, nf * 5).reshape(nf, 5), None, None
         else:
             rects, weights, tilted = _view(r, C.c_int32, nf * 4).reshape(nf, 4), None, None
         return CascadeModel(inf, sf, sn, sthr, *stump, rects, weights, tilted)

@@ -86,13 +86,17 @@ CC_API cc_status cc_cascade_stages(const cc_cascade* c, const int32_t** first_we
 CC_API cc_status cc_cascade_stumps(const cc_cascade* c, const int32_t** feature_idx, const float** threshold,
                                    const float** left, const float** right, const int32_t** subsets);
 /* Haar: rects as int32[n_features][3][4] (x y w h), weights float[n_features][3], tilted int32[n_features].
- * LBP:  rects as int32[n_features][4]; weights / tilted are NULL. */
+ * LBP:  rects as int32[n_features][4]; weights / tilted are NULL.
+ * HOG:  rects as int32[n_features][5] = x y w h of the block's cell 0 and the component in [0, 36) (cell comp / 9, bin
+ *       comp % 9; HOGfeatures.cpp:155-160); weights / tilted are NULL. A HOG variable's value is the evaluator's
+ *       (section 4). */
 CC_API cc_status cc_cascade_features(const cc_cascade* c, const int32_t** rects, const float** weights,
                                      const int32_t** tilted);
 
 /* Writes the model back as a new-format cascade.xml (the layout of CvCascadeClassifier::save,
  * traincascade/lib/src/cascadeclassifier.cpp:439-456; stages boost.cpp:520-532, trees o_cvcascadeboosttree.cpp:41-93,
- * features haarfeatures.cpp:311-320 / lbpfeatures.cpp:65-68). Reading the written file yields an identical model. */
+ * features haarfeatures.cpp:311-320 / lbpfeatures.cpp:65-68 / HOGfeatures.cpp:155-160). Reading the written file yields
+ * an identical model. */
 CC_API cc_status cc_cascade_save_xml(const cc_cascade* c, const char* path);
 
 /* The legacy "baseFormat" layout of CvCascadeClassifier::save(filename, true) (cascadeclassifier.cpp:421-437 tag names,
@@ -127,7 +131,9 @@ typedef struct cc_detect_params {
   int32_t max_w, max_h;  /* 0 = image size */
 } cc_detect_params;
 
-/* device: HIP device ordinal. max_batch: frames processed per pass (workspace is sized for it). */
+/* device: HIP device ordinal. max_batch: frames processed per pass (workspace is sized for it). Haar and LBP cascades:
+ * a HOG cascade returns CC_ERR_UNSUPPORTED (nothing in the reference defines detection with one; OpenCV cannot run them
+ * either), as do cc_detector_specialize(_async) and cc_cascade_compile_specialized. */
 CC_API cc_status cc_detector_create(const cc_cascade* c, int device, int max_batch, cc_detector** out);
 CC_API void cc_detector_destroy(cc_detector* d);
 /* Use the caller's HIP stream (hipStream_t) for all work of this detector; NULL = detector's own stream. */
@@ -295,8 +301,8 @@ CC_API cc_status cc_group_rectangles(const cc_rect* rects, int n, int group_thre
  *    VARIABLE index vi in [0, num_features * 36): block vi / 36, cell (vi % 36) / 9, bin vi % 9. That covers cc_eval_calc,
  *    cc_eval_calc_list, cc_eval_calc_batch, cc_eval_calc_batch_device, cc_eval_calc_batch_sorted, cc_eval_presort_range
  *    and cc_split.var_idx. cc_eval_feature_geometry, cc_eval_get_sample and cc_eval_calc_custom_haar return
- *    CC_ERR_INVALID_ARG on a HOG evaluator; HOG cascades are not loadable (cc_cascade_load_xml*), so detection, negative
- *    mining and cc_eval_predict_cascade stay Haar / LBP.
+ *    CC_ERR_INVALID_ARG on a HOG evaluator. cc_eval_predict_cascade takes a HOG cascade on a HOG evaluator of the same
+ *    window size (the cascade's <rect> names a block's cell 0 and a component, section 1).
  * ============================================================================================ */
 typedef struct cc_evaluator cc_evaluator;
 enum { CC_HAAR_BASIC = 0, CC_HAAR_CORE = 1, CC_HAAR_ALL = 2 };
@@ -378,7 +384,9 @@ CC_API cc_status cc_eval_get_hog_sample(cc_evaluator* e, int idx, float* hist, f
 CC_API cc_status cc_debug_hog_bins(int device, int32_t* n, uint8_t* bin, float* mag);
 /* Training-side cascade predict (CvCascadeClassifier::predict, cascadeclassifier.cpp:297-306 ->
  * boost.cpp:461-477 -> o_cvcascadeboosttree.cpp:16-39) of a stump cascade over stored samples:
- * out[s] = 1 if every stage passes else 0. Feature indices of `c` index the cascade's own <features> list. */
+ * out[s] = 1 if every stage passes else 0. Feature indices of `c` index the cascade's own <features> list. The cascade's
+ * type and window size must be the evaluator's (CC_ERR_INVALID_ARG otherwise). HOG: variable values as operator()
+ * computes them on the stored planes, `<=` goes left, stage sums in double over the float leaves. */
 CC_API cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const int32_t* sample_idx, int n_samples,
                                          uint8_t* out);
 CC_API cc_status cc_eval_last_kernel_ms(cc_evaluator* e, double* ms);
@@ -394,6 +402,11 @@ CC_API cc_status cc_eval_last_kernel_ms(cc_evaluator* e, double* ms);
  *    ladder level and its integral images once, and evaluates the trained stages on every window on the device.
  *    Training-side arithmetic: norm factor sqrt(area*sqsum - sum^2) as float, value = calc / nf (0 if nf == 0),
  *    ordered splits go left on `<=`, a stage passes iff sum >= threshold - 1e-5f.
+ *    HOG cascades: no integral images; every window's gradients, bins and ten integral planes are built from the window's
+ *    own pixels with replicate borders INSIDE the window (NegReader::get copies the window out and setImage,
+ *    HOGfeatures.cpp:163-256, takes its border from that copy), by the device code of the evaluator's setImage, so a mined
+ *    window's values are exactly cc_eval_set_image's. cc_negminer_create returns CC_ERR_UNSUPPORTED for a window whose
+ *    planes do not fit 160 KiB of LDS (10 * (win_w + 1) * (win_h + 1) floats + 5 bytes per pixel).
  * ============================================================================================ */
 typedef struct cc_negminer cc_negminer;
 CC_API cc_status cc_negminer_create(const cc_cascade* trained_stages, int device, cc_negminer** out);
