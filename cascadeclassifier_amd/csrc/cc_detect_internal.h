@@ -1,0 +1,186 @@
+// Declarations shared by the detection-side translation units: cc_detect.hip (the detector), cc_front.hip (pyramid and
+// integral images), cc_negmine.hip (negative mining for training) and cc_spec.hip (the run-time specialiser). Only what
+// crosses those files lives here; everything else stays static in the file that uses it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "cc_hip_util.h"
+#include "cc_internal.h"
+
+namespace ccamd {
+
+#include "cc_eval_common.h"
+
+// Scale (or level, or group) of a block: `first` holds the first block of each of the n segments, ascending.
+__device__ __forceinline__ int find_segment(const int* __restrict__ first, int n, int idx) {
+  int s = 0;
+  while (s + 1 < n && first[s + 1] <= idx) s++;  // n <= a few hundred, wave-uniform
+  return s;
+}
+
+inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+
+// ------------------------------------------------------------------------------------------------
+// Front end: pyramid (k_resize), integral images (k_integral_band, k_integral_carry) and tilted integral (k_diag_sums,
+// k_tilted_cols) of every level of nf frames. The detector, the negative miner and the building-block entry points all
+// lay it out with front_layout, upload it with FrontTables::upload and launch it with launch_front.
+// ------------------------------------------------------------------------------------------------
+// Host tables of the front end for levels of the given sizes, each resized from a src_w x src_h source.
+struct FrontLayout {
+  int src_w = 0, src_h = 0;
+  std::vector<ScaleDev> sd;  // front-end fields set (w h pitch8 pitchI img_ofs int_ofs h_ofs nbands xtab_ofs ytab_ofs), the rest 0
+  // block maps, ns + 1 entries: first block (band, group) of each level, the total last
+  std::vector<int> resize_first, band_first, col_first, diag_first, tcol_first;
+  std::vector<int> xofs, yofs;  // resize taps: columns (padded, see append_column_taps), rows
+  std::vector<uint16_t> xw1, yw1;
+  std::vector<long long> tseg_ofs;  // tilted only: where each level's segment totals start in a frame's, ns + 1 entries
+  int max_nseg = 0;                 // tilted only: segments of the tallest level (0: no tilted integral)
+  // per frame: pyramid bytes, integral elements per channel, band-total elements per channel, segment-total elements
+  size_t pyr_frame_bytes = 0, int_frame_elems = 0, h_frame_elems = 0, tseg_frame_elems = 0;
+};
+FrontLayout front_layout(int src_w, int src_h, const std::vector<int2>& sizes, bool tilted);
+
+// A layout and its tables on the device. Callers set the layout, add their own ScaleDev fields, then upload once: the
+// detector's captured hipGraph replays these pointers, so a plan's tables are never reallocated.
+struct FrontTables {
+  FrontLayout L;
+  DevBuf<ScaleDev> d_sd;
+  DevBuf<int> d_resize_first, d_band_first, d_col_first, d_diag_first, d_tcol_first, d_xofs, d_yofs;
+  DevBuf<uint16_t> d_xw1, d_yw1;
+  DevBuf<long long> d_tseg_ofs;
+  // Ends with a synchronisation of `st`, so earlier uploads of the caller on `st` have landed too.
+  hipError_t upload(hipStream_t st) {
+    for (hipError_t e : {d_sd.upload(L.sd, st), d_resize_first.upload(L.resize_first, st), d_band_first.upload(L.band_first, st),
+                         d_col_first.upload(L.col_first, st), d_diag_first.upload(L.diag_first, st), d_tcol_first.upload(L.tcol_first, st),
+                         d_xofs.upload(L.xofs, st), d_yofs.upload(L.yofs, st), d_xw1.upload(L.xw1, st), d_yw1.upload(L.yw1, st),
+                         L.tseg_ofs.empty() ? hipSuccess : d_tseg_ofs.upload(L.tseg_ofs, st)})
+      if (e != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+  }
+};
+
+enum { FRONT_RESIZE = 1, FRONT_INTEGRALS = 2 };  // launch_front parts
+
+// Caller-owned buffers of launch_front, frame f of each at f times its per-frame size.
+struct FrontIO {
+  const uint8_t* src = nullptr;  // FRONT_RESIZE: the source frames, src_w x src_h
+  size_t row_stride = 0, frame_stride = 0;
+  uint8_t* pyr = nullptr;      // L.pyr_frame_bytes per frame: the levels (FRONT_INTEGRALS alone: filled by the caller)
+  int32_t* integ = nullptr;    // nchan x L.int_frame_elems per frame: channel 0 sum, 1 sqsum (sq), tilt_chan tilted (tilted layouts)
+  int32_t* hbuf = nullptr;     // nchan x L.h_frame_elems per frame: band totals
+  int32_t* diag = nullptr;     // tilted: 2 x L.int_frame_elems per frame, diagonal sums
+  int32_t* tseg = nullptr;     // tilted: L.tseg_frame_elems per frame, segment totals
+  int nchan = 1, tilt_chan = 2;
+  bool sq = false;
+  int sq_odd_rows_only = 0;  // k_integral_band: squared sums of ystep-2 levels only where the detector reads them
+};
+
+// Launches the front end's `parts` for nf frames on `st`. Only launches: no allocation, no synchronisation (the detector
+// runs it inside a hipGraph capture).
+void launch_front(hipStream_t st, const FrontTables& T, const FrontIO& io, int nf, int parts);
+
+// ---- checks shared by the entry points (cc_detect.hip) ----
+// Detection and its run-time specialisation are Haar / LBP only: nothing in the reference defines detection with a HOG
+// cascade. Every detector entry point calls this before the model reaches a kernel or a table builder (the LBP branches
+// would read lbp_rects, which a HOG model leaves empty).
+cc_status refuse_hog(const Cascade& m, const char* who);
+cc_status ensure_device(int device);
+
+// True when, for every stage, any partial sum of leaf values is exactly representable in double: all leaves are
+// integer multiples of q = 2^(emin-23) (emin = smallest exponent among the stage's nonzero leaves) and the sum of the
+// larger leaf magnitudes divided by q stays below 2^53. Then the double accumulation never rounds, so its result
+// does not depend on the order of the additions.
+bool stage_sums_order_independent(const Cascade& m, double headroom = 1.0);
+
+// ---- stump tables of the cascade kernels (detector and specialiser) ----
+// `at(y, x)` maps a corner inside the window to what the record stores: an LDS offset of one of the tile layouts, or
+// (y << 16 | x) for the records whose corners are read from global memory (GlobalReader). tilt_shift: distance of the
+// tilted tile behind the sum tile.
+template <class At>
+void build_haar_stumps_at(const Cascade& m, std::vector<HaarStumpDev>& out, At at, int tilt_shift) {
+  out.resize(m.stump_feature.size());
+  for (size_t i = 0; i < out.size(); i++) {
+    HaarStumpDev& d = out[i];
+    std::memset(&d, 0, sizeof(d));
+    const int fi = m.stump_feature[i];
+    d.nrect = 2;
+    for (int j = 0; j < 3; j++) {
+      const int32_t* r = &m.haar_rects[(size_t)fi * 12 + j * 4];
+      const float wt = m.haar_weights[(size_t)fi * 3 + j];
+      d.w[j] = wt;
+      // rects after the first zero weight contribute w*0 upstream (offsets stay 0): keep corner offsets equal
+      const bool used = j < 2 || wt != 0.0f;
+      if (j == 2 && wt != 0.0f) d.nrect = 3;
+      const int x = used ? r[0] : 0, y = used ? r[1] : 0, rw = used ? r[2] : 0, rh = used ? r[3] : 0;
+      if (!m.haar_tilted[fi]) {
+        d.ofs[j][0] = at(y, x);
+        d.ofs[j][1] = at(y, x + rw);
+        d.ofs[j][2] = at(y + rh, x);
+        d.ofs[j][3] = at(y + rh, x + rw);
+      } else {  // corners of the 45-degree rectangle (CV_TILTED_OFFSETS), read from the tilted tile behind the sum tile
+        d.ofs[j][0] = tilt_shift + at(y, x);
+        d.ofs[j][1] = tilt_shift + at(y + rh, x - rh);
+        d.ofs[j][2] = tilt_shift + at(y + rw, x + rw);
+        d.ofs[j][3] = tilt_shift + at(y + rw + rh, x + rw - rh);
+      }
+    }
+    d.thr = m.stump_threshold[i];
+    d.left = m.stump_left[i];
+    d.right = m.stump_right[i];
+    d.pad = (int)i;  // the stump's index: survives the re-ordering of schedule_for_wave_phase
+  }
+}
+template <int STEP>
+void build_haar_stumps(const Cascade& m, std::vector<HaarStumpDev>& out) {
+  const TileGeom<STEP> G(m.win_w, m.win_h);
+  build_haar_stumps_at(m, out, [&](int y, int x) { return G.at(y, x); }, tile_words_padded(G.words()));
+}
+template <class At>
+void build_lbp_stumps_at(const Cascade& m, std::vector<LbpStumpDev>& out, At at) {
+  out.resize(m.stump_feature.size());
+  for (size_t i = 0; i < out.size(); i++) {
+    LbpStumpDev& d = out[i];
+    std::memset(&d, 0, sizeof(d));
+    const int32_t* r = &m.lbp_rects[(size_t)m.stump_feature[i] * 4];
+    for (int rr = 0; rr < 4; rr++)
+      for (int cc = 0; cc < 4; cc++) d.ofs[4 * rr + cc] = at(r[1] + rr * r[3], r[0] + cc * r[2]);
+    d.left = m.stump_left[i];
+    d.right = m.stump_right[i];
+    for (int j = 0; j < 8; j++) d.subset[j] = m.node_subset[i * 8 + j];
+  }
+}
+template <int STEP>
+void build_lbp_stumps(const Cascade& m, std::vector<LbpStumpDev>& out) {
+  const TileGeom<STEP> G(m.win_w, m.win_h);
+  build_lbp_stumps_at(m, out, [&](int y, int x) { return G.at(y, x); });
+}
+inline void build_lbp_stumps16(const Cascade& m, std::vector<LbpStumpDev>& out) {  // STEP-2 tile with 16-bit entries
+  const TileGeom16 G(m.win_w, m.win_h);
+  build_lbp_stumps_at(m, out, [&](int y, int x) { return G.at(y, x); });
+}
+
+// Layout of the STEP-2 tiles of a specialised kernel: 32-bit entries in two column planes (TileGeom<2>) or 16-bit entries
+// (TileGeom16).
+enum { TILE_32 = 0, TILE_16 = 1 };
+
+// A rectangle sum read from 16-bit entries is exact when 255 * area < 2^16.
+inline bool fits16(long long area) { return 255LL * area <= 65535LL; }
+
+// ---- run-time specialisation (cc_spec.hip) ----
+// One compiled module of the run-time specialised kernel: the tiles it covers (0 = all, 1 / 2 = the tiles of STEP-1 / STEP-2
+// scales) and the tile height it was compiled for.
+struct SpecCode {
+  std::vector<char> code;
+  int only_step = 0;
+  int tile_y = TILE_Y;
+};
+
+// Host half of the specialisation: source for the first stages (whole stages within the code-size budget) compiled for
+// `arch`. No device calls: safe on a background thread.
+cc_status spec_build(const Cascade& m, int n_stages, const std::string& arch, std::vector<SpecCode>& codes, int& k_out, int& tmode_out);
+
+}  // namespace ccamd

@@ -1029,10 +1029,10 @@ cc_status cc_eval_calc_batch_sorted(cc_evaluator* e, int fi_begin, int fi_end, i
   const bool haar = e->type == CC_FEATURE_HAAR;
   const size_t total = (size_t)nf * n_samples;
   if (total > (size_t)INT32_MAX) return set_error(CC_ERR_INVALID_ARG, "cc_eval_calc_batch_sorted: block too large (%zu values); use smaller feature ranges", total);
-  EBuf<float> keys_out;
-  EBuf<int> iota, sorted, offsets;
-  EBuf<unsigned short> narrow;
-  EBuf<char> temp;
+  DevBuf<float> keys_out;
+  DevBuf<int> iota, sorted, offsets;
+  DevBuf<unsigned short> narrow;
+  DevBuf<char> temp;
   CC_HIP(e->d_out.ensure(total));
   CC_HIP(keys_out.ensure(total));
   CC_HIP(iota.ensure(total));
@@ -1222,9 +1222,9 @@ cc_status cc_haar_feature_calc(int device, const cc_haar_feature* feats, int n_f
           return set_error(CC_ERR_OUT_OF_RANGE, "cc_haar_feature_calc: feature %d reads offset %d outside the %d-entry integral", i, dev[i].p[j][k], row_len);
   }
   if ((need_sum && !sum) || (need_tilted && !tilted)) return set_error(CC_ERR_INVALID_ARG, "cc_haar_feature_calc: a needed integral image is NULL");
-  EBuf<HaarFeatDev> d_f;
-  EBuf<int32_t> d_s, d_t;
-  EBuf<float> d_o;
+  DevBuf<HaarFeatDev> d_f;
+  DevBuf<int32_t> d_s, d_t;
+  DevBuf<float> d_o;
   const size_t nint = (size_t)n_rows * row_len, nout = (size_t)n_feats * n_rows;
   OwnStream own;  // not the legacy stream: see copy_sync
   CC_HIP(own.create());
@@ -1296,10 +1296,10 @@ cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const in
   const std::vector<int32_t>& rec_feature = trees ? m.node_feature : m.stump_feature;
   const std::vector<float>& rec_thr = trees ? m.node_threshold : m.stump_threshold;
   const size_t ns = rec_feature.size();
-  EBuf<HaarFeatDev> dh;
-  EBuf<LbpFeatDev> dl;
-  EBuf<int> d_ntrees, d_sub;
-  EBuf<float> d_sthr, d_thr, d_left, d_right;
+  DevBuf<HaarFeatDev> dh;
+  DevBuf<LbpFeatDev> dl;
+  DevBuf<int> d_ntrees, d_sub;
+  DevBuf<float> d_sthr, d_thr, d_left, d_right;
   std::vector<int> ntrees(m.stage_ntrees.begin(), m.stage_ntrees.end());
   if (haar) {
     std::vector<HaarFeatDev> dev(ns);
@@ -1327,8 +1327,8 @@ cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const in
   CC_HIP(copy_sync(d_sthr.p, m.stage_threshold.data(), ntrees.size() * 4, hipMemcpyHostToDevice, e->stream));
   CC_HIP(d_thr.ensure(ns));
   CC_HIP(copy_sync(d_thr.p, rec_thr.data(), ns * 4, hipMemcpyHostToDevice, e->stream));
-  EBuf<int> d_root, d_leaf0, d_nl, d_nr;
-  EBuf<float> d_leaves;
+  DevBuf<int> d_root, d_leaf0, d_nl, d_nr;
+  DevBuf<float> d_leaves;
   if (!trees) {
     CC_HIP(d_left.ensure(ns));
     CC_HIP(copy_sync(d_left.p, m.stump_left.data(), ns * 4, hipMemcpyHostToDevice, e->stream));

@@ -22,42 +22,6 @@ struct LbpFeatDev {
   int p[16];
 };
 
-template <class T>
-struct EBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  ~EBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t ensure(size_t count) {
-    if (count <= n) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e == hipSuccess) n = count;
-    return e;
-  }
-};
-
-
-struct PinnedBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~PinnedBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-  hipError_t ensure(size_t b) {
-    if (b <= bytes) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-    hipError_t e = hipHostMalloc(&p, b, hipHostMallocDefault);
-    if (e == hipSuccess) bytes = b;
-    return e;
-  }
-};
-
 cc_status eval_device(cc_evaluator* e);
 // Launches k_eval_batch over `feats` [fb, fe) for ns samples into d_out_ptr (device). Caller holds e->mu.
 // Stable sort of every row of [rows][n] with the sample position as the value, one block per row (cc_split.hip); only for
@@ -92,7 +56,7 @@ float hog_host_value(const cc_evaluator* e, const float* planes, int vi);
 struct cc_evaluator {
   using HaarFeature = ccamd::HaarFeature;
   template <class T>
-  using EBuf = ccamd::EBuf<T>;
+  using DevBuf = ccamd::DevBuf<T>;
   using HaarFeatDev = ccamd::HaarFeatDev;
   using LbpFeatDev = ccamd::LbpFeatDev;
   int type = 0, mode = 0, W = 0, H = 0, max_samples = 0, device = 0, cols = 0;
@@ -102,35 +66,35 @@ struct cc_evaluator {
   std::vector<float> cls;
   int nfeat = 0;
   hipStream_t stream = nullptr;
-  EBuf<int32_t> d_sum, d_tilted;
-  EBuf<float> d_nf;
-  EBuf<HaarFeatDev> d_haar;
-  EBuf<LbpFeatDev> d_lbp;
+  DevBuf<int32_t> d_sum, d_tilted;
+  DevBuf<float> d_nf;
+  DevBuf<HaarFeatDev> d_haar;
+  DevBuf<LbpFeatDev> d_lbp;
   // scratch (guarded by mu: the calc entry points may be called concurrently)
   std::mutex mu;
-  EBuf<uint8_t> d_imgs;
-  EBuf<int32_t> d_idx;
-  EBuf<float> d_out;
-  EBuf<HaarFeatDev> d_custom;
-  EBuf<HaarFeatDev> d_haar_plain;  // catalog with plain fastRect offsets (cc_eval_calc_list), built on first use
-  EBuf<LbpFeatDev> d_lbp_plain;
-  EBuf<uint8_t> d_pred;
+  DevBuf<uint8_t> d_imgs;
+  DevBuf<int32_t> d_idx;
+  DevBuf<float> d_out;
+  DevBuf<HaarFeatDev> d_custom;
+  DevBuf<HaarFeatDev> d_haar_plain;  // catalog with plain fastRect offsets (cc_eval_calc_list), built on first use
+  DevBuf<LbpFeatDev> d_lbp_plain;
+  DevBuf<uint8_t> d_pred;
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
   hipEvent_t ev_piece[8] = {};  // categorical split search: one per piece of the sums on its way back (cc_split.hip)
   double last_ms = 0;
   int S = 16;
   // resident tables of the split search (cc_eval_presort): per group of 64 features the sorted values and sample
   // indices, interleaved so that lane = feature reads are coalesced: [group][rank][64]
-  EBuf<float> d_sorted_val;
-  EBuf<uint16_t> d_sorted_idx16;
-  EBuf<int32_t> d_sorted_idx32;
-  EBuf<uint8_t> d_codes;  // LBP: [feature][sample] codes
+  DevBuf<float> d_sorted_val;
+  DevBuf<uint16_t> d_sorted_idx16;
+  DevBuf<int32_t> d_sorted_idx32;
+  DevBuf<uint8_t> d_codes;  // LBP: [feature][sample] codes
   int cat_sorted_n = 0;          // samples per variable in d_cat_sorted (0: not built)
-  EBuf<uint32_t> d_cat_sorted;  // LBP: (sample << 8 | code) in (code, sample) order, [group][rank][64] (cc_split.hip)
+  DevBuf<uint32_t> d_cat_sorted;  // LBP: (sample << 8 | code) in (code, sample) order, [group][rank][64] (cc_split.hip)
   int presort_n = 0;      // samples covered by the tables (0 = none)
   int presort_f0 = 0, presort_f1 = 0;  // variables covered by the tables
-  EBuf<double> d_split_tab, d_split_out;
-  EBuf<int32_t> d_split_idx;
+  DevBuf<double> d_split_tab, d_split_out;
+  DevBuf<int32_t> d_split_idx;
   ccamd::PinnedBuf pin_in, pin_out;
   // ---- single-image path (cc_eval_set_image / cc_eval_calc / cc_eval_calc_list), see cc_eval.hip ----
   // images set one at a time that the device has not seen yet: pixels (W * H each), sample index, and where a sample's
@@ -150,8 +114,8 @@ struct cc_evaluator {
   // HOG (cc_hog.hip): catalog blocks [n][4] = x, y, cell w, cell h; planes [max_samples][cols][10] (9 bins, then norm);
   // nfeat counts variables (blocks * 36). mirror_hog is the host mirror of the last window, read and written under mu.
   std::vector<int32_t> hog_blocks;
-  EBuf<int32_t> d_hog_blocks;
-  EBuf<float> d_hog;
+  DevBuf<int32_t> d_hog_blocks;
+  DevBuf<float> d_hog;
   int hog_planes_per_pass = 0;
   std::vector<float> mirror_hog;
   ~cc_evaluator() {

@@ -1,7 +1,11 @@
-// HIP helpers shared by the .hip translation units: error plumbing for HIP calls and stream-ordered blocking copies.
+// HIP helpers shared by the .hip translation units: error plumbing for HIP calls, stream-ordered blocking copies and
+// growing device / pinned host buffers.
 // HIP only: the .cpp files (built with -x c++) include cc_internal.h, never this header.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "cc_internal.h"
 
@@ -26,6 +30,50 @@ struct OwnStream {  // for entry points that have no handle to borrow a stream f
   hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
   ~OwnStream() {
     if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+// Device buffer of `n` elements. ensure() only grows (contents are not kept); upload() allocates at least one element, so
+// that a table's pointer is valid even when the table is empty.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+  hipError_t ensure(size_t count) {
+    if (count <= n) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
+    if (e == hipSuccess) n = count;
+    return e;
+  }
+  hipError_t upload(const std::vector<T>& v, hipStream_t st) {
+    hipError_t e = ensure(std::max<size_t>(v.size(), 1));
+    if (e != hipSuccess || v.empty()) return e;
+    return hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st);
+  }
+};
+
+// Pinned host buffer of `bytes` bytes; ensure() only grows (contents are not kept).
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  hipError_t ensure(size_t b) {
+    if (b <= bytes) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+    hipError_t e = hipHostMalloc(&p, b, hipHostMallocDefault);
+    if (e == hipSuccess) bytes = b;
+    return e;
   }
 };
 

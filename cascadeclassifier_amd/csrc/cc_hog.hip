@@ -276,9 +276,9 @@ cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, i
   }
   const std::vector<int> ntrees(m.stage_ntrees.begin(), m.stage_ntrees.end());
   const std::vector<int> root(m.tree_first_node.begin(), m.tree_first_node.end()), leaf0(m.tree_first_leaf.begin(), m.tree_first_leaf.end());
-  EBuf<HogNodeDev> d_nodes;
-  EBuf<int> d_ntrees, d_root, d_leaf0;
-  EBuf<float> d_sthr, d_leaves;
+  DevBuf<HogNodeDev> d_nodes;
+  DevBuf<int> d_ntrees, d_root, d_leaf0;
+  DevBuf<float> d_sthr, d_leaves;
   CC_HIP(d_nodes.ensure(nodes.size()));
   CC_HIP(copy_sync(d_nodes.p, nodes.data(), nodes.size() * sizeof(HogNodeDev), hipMemcpyHostToDevice, e->stream));
   CC_HIP(d_ntrees.ensure(ntrees.size()));
@@ -390,8 +390,8 @@ cc_status cc_debug_hog_bins(int device, int32_t* n, uint8_t* bin, float* mag) {
   if (device < 0 || device >= nd) return set_error(CC_ERR_INVALID_ARG, "device %d out of range (devices: %d)", device, nd);
   CC_HIP(hipSetDevice(device));
   constexpr int N = 511 * 511;
-  EBuf<uint8_t> d_bin;
-  EBuf<float> d_mag;
+  DevBuf<uint8_t> d_bin;
+  DevBuf<float> d_mag;
   CC_HIP(d_bin.ensure(N));
   CC_HIP(d_mag.ensure(N));
   OwnStream own;  // not the legacy stream: see copy_sync

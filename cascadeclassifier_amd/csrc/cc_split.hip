@@ -721,9 +721,9 @@ cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n
   if (resident + scratch > free_b + have)
     return set_error(CC_ERR_UNSUPPORTED, "cc_eval_presort: needs %.1f GB of device memory (%.1f GB free)",
                      (double)(resident + scratch) / 1e9, (double)(free_b + have) / 1e9);
-  EBuf<float> keys_out;
-  EBuf<int> iota, sorted, offsets;
-  EBuf<char> temp;
+  DevBuf<float> keys_out;
+  DevBuf<int> iota, sorted, offsets;
+  DevBuf<char> temp;
   const size_t cap = (size_t)FB * N;
   if (haar || cat_table) {
     CC_HIP(e->d_out.ensure(cap));

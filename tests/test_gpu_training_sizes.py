@@ -6,7 +6,7 @@ restatement (tests/hog_restatement.py). Each test goes past one point where the 
 * LBP sample numbers >= 2^16 in the packed (sample << 8 | code) entries of the categorical tables, and the default number
   of parts per variable at N = 100 000 (97 on 256 CUs; CCAMD_SPLIT_CAT_PARTS cannot go past 64);
 * calc_batch_sorted with 4-byte indices (2-byte indices refused past 65 536);
-* negative-mining batches of several 8 MiB pieces (cc_detect.hip mine_images);
+* negative-mining batches of several 8 MiB pieces (cc_negmine.hip mine_images);
 * HOG windows whose setImage kernel needs more than 64 KB of LDS;
 * more than 4 096 queued setImage windows (the queue is flushed while calls still arrive).
 

@@ -20,7 +20,7 @@ lbp=""; grep -q '<featureType>LBP' "$xml" && lbp="-DCC_SPEC_LBP"
 # the library compiles kernels with 16-bit STEP-2 tiles for 7 wavefronts per SIMD (their LDS footprint allows it) and defines CC_SPEC_TILE16
 t16=""; dw=5
 if [ "$(grep -c 'reinterpret_cast<const unsigned short\*>(b)' $out.hip)" -gt 1 ]; then t16="-DCC_SPEC_TILE16"; dw=7; fi
-# LBP kernels with 16-bit tiles are compiled for tiles of 16 window rows (spec_tile_rows in cc_detect.hip)
+# LBP kernels with 16-bit tiles are compiled for tiles of 20 window rows (spec_modules in cc_spec.hip)
 if [ -n "$lbp" ] && [ "$t16" = "-DCC_SPEC_TILE16" ] && [ -z "$CC_TILE_Y" ]; then CC_TILE_Y=${CCAMD_SPEC_TILE_Y:-20}; dw=6; fi
 W=$(grep -o '<width>[0-9]*' "$xml" | head -1 | grep -o '[0-9]*'); H=$(grep -o '<height>[0-9]*' "$xml" | head -1 | grep -o '[0-9]*')
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -include hip/hip_runtime.h -DCC_SPEC_STAGES=$k \
