@@ -23,6 +23,7 @@ CC_ERR_BUFFER_TOO_SMALL = -7
 CC_ERR_OUT_OF_RANGE = -8
 
 CC_FEATURE_HAAR, CC_FEATURE_LBP, CC_FEATURE_HOG = 0, 1, 2
+CC_PIX_GRAY8, CC_PIX_BGR8, CC_PIX_BGRA8, CC_PIX_RGB8, CC_PIX_RGBA8, CC_PIX_RGB8_PLANAR = 0, 1, 2, 3, 4, 5
 CC_HAAR_BASIC, CC_HAAR_CORE, CC_HAAR_ALL = 0, 1, 2
 
 
@@ -96,6 +97,12 @@ SIGNATURES = {
     "cc_detect_batch_collect": (_i, [_vp, _vp, _vp, _i, _vp]),
     "cc_detect_batch_discard": (_i, [_vp, _vp]),
     "cc_detect_batch_device_only": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, C.POINTER(DetectParams)]),
+    "cc_detect_multiscale_fmt": (_i, [_vp, _vp, _i, _i, _sz, _i, C.POINTER(DetectParams), _vp, _i, C.POINTER(_i)]),
+    "cc_detect_batch_fmt": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _vp, _i, _vp]),
+    "cc_detect_batch_submit_fmt": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _pp]),
+    "cc_detect_multiscale_levels_fmt": (_i, [_vp, _vp, _i, _i, _sz, _i, C.POINTER(DetectParams), _vp, _vp, _vp, _i,
+                                             C.POINTER(_i)]),
+    "cc_to_gray_u8": (_i, [_i, _vp, _i, _i, _i, _sz, _vp, _sz]),
     "cc_detect_multiscale_levels": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(DetectParams), _vp, _vp, _vp, _i, C.POINTER(_i)]),
     "cc_detect_raw": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(DetectParams), _vp, _i, C.POINTER(_i)]),
     "cc_detect_debug_windows": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(DetectParams), _vp, _vp, _vp, C.c_int64,
@@ -107,6 +114,7 @@ SIGNATURES = {
     "cc_cascade_compile_specialized": (_i, [_vp, _i, C.c_char_p, C.POINTER(C.c_size_t)]),
     "cc_detector_set_profiling": (_i, [_vp, _i]),
     "cc_detector_graph_active": (_i, [_vp]),
+    "cc_detector_graph_captures": (C.c_int64, [_vp]),
     "cc_detector_get_timings": (_i, [_vp, C.POINTER(DetectorTimings), _i]),
     "cc_integral_u8": (_i, [_i, _vp, _i, _i, _sz, _vp, _vp, _vp]),
     "cc_resize_linear_exact_u8": (_i, [_i, _vp, _i, _i, _sz, _vp, _i, _i, _sz]),

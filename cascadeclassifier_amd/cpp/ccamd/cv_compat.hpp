@@ -22,6 +22,8 @@ typedef unsigned char uchar;
 #define CV_32S 4
 #define CV_32F 5
 #define CV_8UC1 CV_8U
+#define CV_8UC3 16  // CV_MAKETYPE(CV_8U, 3): channels in bits 3.., as OpenCV numbers them
+#define CV_8UC4 24
 #define CV_32SC1 CV_32S
 #define CV_32FC1 CV_32F
 
@@ -53,7 +55,7 @@ struct Rect {
 
 struct Scalar {
   double v[4];
-  Scalar(double a = 0) : v{a, 0, 0, 0} {}
+  Scalar(double a = 0, double b = 0, double c = 0, double d = 0) : v{a, b, c, d} {}
 };
 
 // Dense 2-D matrix / view: owns its buffer (shared) or wraps external memory.
@@ -83,7 +85,9 @@ class Mat {
   }
   int type() const { return type_; }
   bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
-  size_t elemSize() const { return type_ == CV_8U ? 1 : 4; }
+  int depth() const { return type_ & 7; }
+  int channels() const { return (type_ >> 3) + 1; }
+  size_t elemSize() const { return (size_t)(depth() == CV_8U ? 1 : 4) * (size_t)channels(); }  // bytes per pixel
   size_t step1() const { return step / elemSize(); }
   Size size() const { return Size(cols, rows); }
   template <class T>
@@ -97,7 +101,8 @@ class Mat {
   Mat& setTo(const Scalar& s) {
     for (int r = 0; r < rows; r++)
       for (int c = 0; c < cols; c++) {
-        if (type_ == CV_8U) at<uchar>(r, c) = (uchar)s.v[0];
+        if (depth() == CV_8U)
+          for (int k = 0; k < channels(); k++) ptr<uchar>(r)[(size_t)c * channels() + k] = (uchar)s.v[k < 4 ? k : 3];
         else if (type_ == CV_32S) at<int>(r, c) = (int)s.v[0];
         else at<float>(r, c) = (float)s.v[0];
       }

@@ -225,7 +225,8 @@ class CascadeClassifier {
   CascadeClassifier& operator=(const CascadeClassifier&) = delete;
   bool load(const cv::String& filename);
   bool empty() const { return c == nullptr; }
-  // image: CV_8UC1. Same defaults as cv::CascadeClassifier::detectMultiScale.
+  // image: CV_8UC1, or CV_8UC3 / CV_8UC4 (BGR / BGRA, converted to gray on the device as OpenCV's COLOR_BGR2GRAY does).
+  // Same defaults as cv::CascadeClassifier::detectMultiScale.
   void detectMultiScale(const cv::Mat& image, std::vector<cv::Rect>& objects, double scaleFactor = 1.1, int minNeighbors = 3,
                         int flags = 0, cv::Size minSize = cv::Size(), cv::Size maxSize = cv::Size());
   // the outputRejectLevels overload (levels = number of stages, weights = the last stage's sum of the group's best window)

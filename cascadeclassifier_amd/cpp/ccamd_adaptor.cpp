@@ -654,10 +654,24 @@ int CascadeClassifier::specialize(int nStages) {
   return cc_detector_specialized_stages(d);
 }
 
+// CV_8UC1 is gray; CV_8UC3 / CV_8UC4 are BGR / BGRA, which OpenCV's detectMultiScale converts with COLOR_BGR2GRAY before it
+// builds the pyramid (CascadeClassifierImpl::detectMultiScaleNoGrouping): here the conversion runs on the device
+// (cc_detect_multiscale_fmt). The same with CCAMD_USE_OPENCV, whose cv::Mat has the same type codes (that build is not
+// exercised where OpenCV is not installed).
+static int pixel_format_of(const cv::Mat& image) {
+  switch (image.type()) {
+    case CV_8UC1: return CC_PIX_GRAY8;
+    case CV_8UC3: return CC_PIX_BGR8;
+    case CV_8UC4: return CC_PIX_BGRA8;
+    default: return -1;
+  }
+}
+
 void CascadeClassifier::detectMultiScale(const cv::Mat& image, std::vector<cv::Rect>& objects, double scaleFactor, int minNeighbors,
                                          int /*flags*/, cv::Size minSize, cv::Size maxSize) {
   objects.clear();
-  CV_Assert(scaleFactor > 1 && image.type() == CV_8UC1);  // cascadedetect.cpp: CV_Assert(scaleFactor > 1 && depth == CV_8U)
+  const int fmt = pixel_format_of(image);
+  CV_Assert(scaleFactor > 1 && fmt >= 0);  // cascadedetect.cpp: CV_Assert(scaleFactor > 1 && depth == CV_8U), 1, 3 or 4 channels
   if (empty()) return;
   if (!d) check(cc_detector_create(c, device, 1, &d), "CascadeClassifier::detectMultiScale");
   cc_detect_params p;
@@ -669,10 +683,10 @@ void CascadeClassifier::detectMultiScale(const cv::Mat& image, std::vector<cv::R
   p.max_h = maxSize.height;
   std::vector<cc_rect> out(1024);
   int n = 0;
-  cc_status st = cc_detect_multiscale(d, image.data, image.cols, image.rows, image.step, &p, out.data(), (int)out.size(), &n);
+  cc_status st = cc_detect_multiscale_fmt(d, image.data, image.cols, image.rows, image.step, fmt, &p, out.data(), (int)out.size(), &n);
   if (st == CC_ERR_BUFFER_TOO_SMALL) {
     out.resize((size_t)n);
-    st = cc_detect_multiscale(d, image.data, image.cols, image.rows, image.step, &p, out.data(), (int)out.size(), &n);
+    st = cc_detect_multiscale_fmt(d, image.data, image.cols, image.rows, image.step, fmt, &p, out.data(), (int)out.size(), &n);
   }
   check(st, "CascadeClassifier::detectMultiScale");
   for (int i = 0; i < n; i++) objects.emplace_back(out[i].x, out[i].y, out[i].width, out[i].height);
@@ -688,7 +702,8 @@ void CascadeClassifier::detectMultiScale(const cv::Mat& image, std::vector<cv::R
     return;
   }
   objects.clear();
-  CV_Assert(scaleFactor > 1 && image.type() == CV_8UC1);
+  const int fmt = pixel_format_of(image);
+  CV_Assert(scaleFactor > 1 && fmt >= 0);
   if (empty()) return;
   if (!d) check(cc_detector_create(c, device, 1, &d), "CascadeClassifier::detectMultiScale");
   cc_detect_params p;
@@ -702,12 +717,14 @@ void CascadeClassifier::detectMultiScale(const cv::Mat& image, std::vector<cv::R
   std::vector<int32_t> lv(1024);
   std::vector<double> wt(1024);
   int n = 0;
-  cc_status st = cc_detect_multiscale_levels(d, image.data, image.cols, image.rows, image.step, &p, out.data(), lv.data(), wt.data(), (int)out.size(), &n);
+  cc_status st = cc_detect_multiscale_levels_fmt(d, image.data, image.cols, image.rows, image.step, fmt, &p, out.data(), lv.data(), wt.data(),
+                                                 (int)out.size(), &n);
   if (st == CC_ERR_BUFFER_TOO_SMALL) {
     out.resize((size_t)n);
     lv.resize((size_t)n);
     wt.resize((size_t)n);
-    st = cc_detect_multiscale_levels(d, image.data, image.cols, image.rows, image.step, &p, out.data(), lv.data(), wt.data(), (int)out.size(), &n);
+    st = cc_detect_multiscale_levels_fmt(d, image.data, image.cols, image.rows, image.step, fmt, &p, out.data(), lv.data(), wt.data(),
+                                         (int)out.size(), &n);
   }
   check(st, "CascadeClassifier::detectMultiScale");
   for (int i = 0; i < n; i++) {

@@ -121,12 +121,16 @@ struct Plan {
   // Single-image calls (the detection tool's shape) are launch-bound: ~10 launches, memsets and copies for well under a
   // millisecond of device work. After a first ordinary call has sized every buffer, the whole pass (H2D copy of the
   // image, pyramid, integrals, cascade kernel, skip filter, copy-back of the counters) is captured into a hipGraph and
-  // replayed with one launch for as long as the buffers and kernels it recorded stay the same (`graph_key`).
-  bool graph_warm = false;
-  hipGraphExec_t graph_exec = nullptr;
-  std::vector<const void*> graph_key;
+  // replayed with one launch for as long as the buffers and kernels it recorded stay the same (`graph_key`). One graph per
+  // pixel format (CC_PIX_*; a colour pass starts with the copy of the colour bytes and k_to_gray), so that gray and colour
+  // calls on one plan both stay on graph launches.
+  static constexpr int kFormats = CC_PIX_RGB8_PLANAR + 1;
+  bool graph_warm[kFormats] = {};
+  hipGraphExec_t graph_exec[kFormats] = {};
+  std::vector<const void*> graph_key[kFormats];
   ~Plan() {
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    for (hipGraphExec_t g : graph_exec)
+      if (g) (void)hipGraphExecDestroy(g);
   }
 };
 
@@ -232,8 +236,14 @@ struct cc_detector {
   int* h_counts = nullptr;  // pinned, 2 x 2 ints
   uint8_t* h_frame = nullptr;  // pinned staging copy of a single host image (graph path)
   size_t h_frame_bytes = 0;
+  uint8_t* h_color_frame = nullptr;  // the same for a single colour image (its own buffer: the gray graphs keep theirs)
+  size_t h_color_frame_bytes = 0;
+  // Colour frames from the host land here (stage_host_frames) and k_to_gray writes them into a gray staging slot, both on
+  // the front stream: stream order makes one buffer of pass_capacity frames enough. Allocated on the first colour batch.
+  DevBuf<uint8_t> d_color;
   uint8_t* h_stage = nullptr;  // pinned staging area for batches of host frames, kStageSlots slots like d_frames (stage_host_frames)
-  size_t h_stage_bytes = 0;
+  size_t h_stage_bytes = 0;    // kStageSlots equal slots of h_stage_bytes / kStageSlots bytes, whatever the frames' format
+  long long graph_captures = 0;  // hipGraph captures made (cc_detector_graph_captures)
   int stage_slot = 0;          // staging slot the next pass of host frames takes (round-robin, also across calls)
   int use_graph = 1;
   int early_skip = 1, full_sqsum = 0, pipeline_passes = 4, pipeline_passes_set = 0, even_passes = 0;  // tuning knobs, read once at creation
@@ -281,6 +291,7 @@ struct cc_detector {
       if (e) (void)hipEventDestroy(e);
     if (h_counts) (void)hipHostFree(h_counts);
     if (h_frame) (void)hipHostFree(h_frame);
+    if (h_color_frame) (void)hipHostFree(h_color_frame);
     if (h_stage) (void)hipHostFree(h_stage);
   }
 };
@@ -762,11 +773,19 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
   return CC_OK;
 }
 
+// Colour formats: row_stride counts bytes (width * bytes per pixel at least) and, with more than one frame, frame_stride must
+// hold a whole frame of the format. Gray frames are checked as they always were.
 static cc_status check_frame_args(const cc_detector* d, const uint8_t* frames, int n_frames, int width, int height,
-                                  size_t row_stride, const cc_detect_params* p, const char* who) {
+                                  size_t row_stride, const cc_detect_params* p, const char* who, int fmt = CC_PIX_GRAY8,
+                                  size_t frame_stride = 0) {
   if (!d || !p || (!frames && n_frames > 0)) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
-  if (n_frames < 0 || width < 1 || height < 1 || row_stride < (size_t)width)
+  const int bpp = pix_bytes(fmt);
+  if (bpp == 0) return set_error(CC_ERR_INVALID_ARG, "%s: unknown pixel format %d", who, fmt);
+  if (n_frames < 0 || width < 1 || height < 1 || row_stride < (size_t)width * bpp)
     return set_error(CC_ERR_INVALID_ARG, "%s: bad frame geometry (%dx%d, stride %zu, n %d)", who, width, height, row_stride, n_frames);
+  if (fmt != CC_PIX_GRAY8 && n_frames > 1 &&
+      frame_stride < (size_t)(pix_rows(fmt, height) - 1) * row_stride + (size_t)width * bpp)
+    return set_error(CC_ERR_INVALID_ARG, "%s: frame stride %zu shorter than one frame of pixel format %d", who, frame_stride, fmt);
   if (width > 32768 || height > 32768) return set_error(CC_ERR_UNSUPPORTED, "%s: frames larger than 32768 px per side", who);
   if (!(p->scale_factor > 1.0)) return set_error(CC_ERR_INVALID_ARG, "%s: scaleFactor must be > 1", who);
   return CC_OK;
@@ -866,6 +885,10 @@ static void retire_foreign(cc_detector* d) {
 // reused kStageSlots passes later; run_batch has retired its pass by then (it stages pass i + 1 only after pass i - 2 is
 // retired), so its copy is long complete. Frames that already live in pinned memory (hipHostMalloc / hipHostRegister)
 // skip the staging copy: those must stay valid until the call that retires their pass (include/cascadeclassifier_amd.h).
+// The slots have ONE pitch for all passes (h_stage_bytes / kStageSlots), not the pass's own frame size: gray and colour
+// passes of one plan stage different byte counts per frame, and a pending pass of the other format may still be copying out
+// of its slot when the next call fills its own (a pitch per format would make the slots of the two formats overlap). The
+// area only grows, after the front stream has finished every copy out of it.
 static cc_status stage_host_frames(cc_detector* d, const uint8_t* src, int nf, int width, int height, size_t row_stride,
                                    size_t frame_stride, uint8_t* dev, size_t rs, size_t fs, int slot, hipStream_t front) {
   hipPointerAttribute_t attr;
@@ -882,7 +905,7 @@ static cc_status stage_host_frames(cc_detector* d, const uint8_t* src, int nf, i
     return CC_OK;
   }
   const size_t need = fs * (size_t)d->pass_capacity * kStageSlots;
-  if (d->h_stage_bytes < need) {
+  if (d->h_stage_bytes / kStageSlots < fs * (size_t)d->pass_capacity) {
     if (d->h_stage) {
       CC_HIP(hipStreamSynchronize(front));  // no copy may still be reading the old area
       (void)hipHostFree(d->h_stage);
@@ -892,7 +915,7 @@ static cc_status stage_host_frames(cc_detector* d, const uint8_t* src, int nf, i
     CC_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_stage), need, hipHostMallocDefault));
     d->h_stage_bytes = need;
   }
-  uint8_t* hs = d->h_stage + (size_t)slot * fs * (size_t)d->pass_capacity;
+  uint8_t* hs = d->h_stage + (size_t)slot * (d->h_stage_bytes / kStageSlots);
   auto copy_frames = [&](int fa, int fb) {
     for (int f = fa; f < fb; f++) {
       const uint8_t* sf = src + (size_t)f * frame_stride;
@@ -938,9 +961,10 @@ static void spec_poll(cc_detector* d);  // installs a finished background specia
 // of pass i (copy-back + consume) overlaps the device side of pass i+1.
 // `defer_last`: the batch's last pass stays pending when the call returns (cc_detect_batch_submit); its candidates reach
 // `consume` when the next call -- or cc_detect_batch_collect -- retires it.
+// `fmt` (CC_PIX_*): colour frames become gray frames in the staging slots (stage_pass) before the pass reads them.
 template <class Consume>
 static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
-                           size_t row_stride, size_t frame_stride, const cc_detect_params* p, bool want_results, bool debug,
+                           size_t row_stride, size_t frame_stride, int fmt, const cc_detect_params* p, bool want_results, bool debug,
                            Consume consume_fn, bool defer_last = false, std::shared_ptr<BatchSink> shared_sink = nullptr) {
   cc_status stt = ensure_device(d->device);
   if (stt != CC_OK) return stt;
@@ -993,24 +1017,42 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
   if (n_frames == 1 && !on_device && want_results && !debug && !d->profiling && d->use_graph) {
     // ---- single host image: one pass on one stream, replayed from a hipGraph once the buffers are sized ----
     const size_t rs = (size_t)align_up(width, 4), fs = rs * (size_t)height;
-    if (d->h_frame_bytes < fs) {
-      if (d->h_frame) (void)hipHostFree(d->h_frame);
-      d->h_frame = nullptr;
-      d->h_frame_bytes = 0;
-      CC_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_frame), fs, hipHostMallocDefault));
-      d->h_frame_bytes = fs;
+    const bool color = fmt != CC_PIX_GRAY8;
+    // colour: rows of width * bpp bytes (planar: 3 * height rows of width) at a pitch of their own
+    const int crows = pix_rows(fmt, height);
+    const size_t cw = (size_t)width * pix_bytes(fmt), cpitch = (size_t)align_up((int)cw, 4), cfs = cpitch * (size_t)crows;
+    uint8_t*& hbuf = color ? d->h_color_frame : d->h_frame;
+    size_t& hbytes = color ? d->h_color_frame_bytes : d->h_frame_bytes;
+    const size_t hneed = color ? cfs : fs;
+    if (hbytes < hneed) {
+      if (hbuf) (void)hipHostFree(hbuf);
+      hbuf = nullptr;
+      hbytes = 0;
+      CC_HIP(hipHostMalloc(reinterpret_cast<void**>(&hbuf), hneed, hipHostMallocDefault));
+      hbytes = hneed;
     }
-    for (int y = 0; y < height; y++) std::memcpy(d->h_frame + (size_t)y * rs, frames + (size_t)y * row_stride, (size_t)width);
+    if (color)
+      for (int y = 0; y < crows; y++) std::memcpy(hbuf + (size_t)y * cpitch, frames + (size_t)y * row_stride, cw);
+    else
+      for (int y = 0; y < height; y++) std::memcpy(d->h_frame + (size_t)y * rs, frames + (size_t)y * row_stride, (size_t)width);
     CC_HIP(d->d_frames.ensure(fs * (size_t)d->pass_capacity * 2));
+    if (color) {
+      if (d->d_color.n < cfs && d->d_color.p && d->front_stream) CC_HIP(hipStreamSynchronize(d->front_stream));  // batch conversions
+      CC_HIP(d->d_color.ensure(cfs));
+    }
     auto body = [&]() -> cc_status {
-      CC_HIP(hipMemcpyAsync(d->d_frames.p, d->h_frame, fs, hipMemcpyHostToDevice, d->stream));
+      if (color) {
+        CC_HIP(hipMemcpyAsync(d->d_color.p, d->h_color_frame, cfs, hipMemcpyHostToDevice, d->stream));
+        launch_to_gray(d->stream, fmt, d->d_color.p, cpitch, cfs, width, height, 1, d->d_frames.p, rs, fs);
+      } else
+        CC_HIP(hipMemcpyAsync(d->d_frames.p, d->h_frame, fs, hipMemcpyHostToDevice, d->stream));
       cc_status s2 = run_device_pass(d, P, d->d_frames.p, 1, rs, fs, false, 0, true);
       if (s2 != CC_OK) return s2;
       CC_HIP(hipMemcpyAsync(d->h_counts, d->d_counts[0].p, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
       return CC_OK;
     };
     auto key_now = [&]() {
-      return std::vector<const void*>{d->d_frames.p, d->h_frame, d->d_pyr.p, d->d_integ[0].p, d->d_hbuf.p, d->d_diag.p, d->d_tseg.p, d->d_masks[0].p, d->d_cands[0].p,
+      return std::vector<const void*>{d->d_frames.p, hbuf, color ? d->d_color.p : nullptr, d->d_pyr.p, d->d_integ[0].p, d->d_hbuf.p, d->d_diag.p, d->d_tseg.p, d->d_masks[0].p, d->d_cands[0].p,
                                       d->d_out[0].p, d->d_counts[0].p, d->h_counts, (const void*)d->spec_fn, (const void*)d->spec_fn1, (const void*)d->stream,
                                       (const void*)(size_t)d->cand_cap, (const void*)(size_t)d->wave_below, (const void*)(size_t)(d->stop_after + 16)};
     };
@@ -1020,13 +1062,14 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     }
     bool launched = false;
     d->last_call_graph = 0;
-    if (P->graph_exec && P->graph_key == key_now()) {
-      CC_HIP(hipGraphLaunch(P->graph_exec, d->stream));
+    hipGraphExec_t& gexec = P->graph_exec[fmt];
+    if (gexec && P->graph_key[fmt] == key_now()) {
+      CC_HIP(hipGraphLaunch(gexec, d->stream));
       launched = true;
       d->last_call_graph = 1;
-    } else if (P->graph_warm) {
-      if (P->graph_exec) (void)hipGraphExecDestroy(P->graph_exec);
-      P->graph_exec = nullptr;
+    } else if (P->graph_warm[fmt]) {
+      if (gexec) (void)hipGraphExecDestroy(gexec);
+      gexec = nullptr;
       hipGraph_t graph = nullptr;
       // Relaxed mode: this thread's stream-ordered calls are captured, nobody's legacy-stream calls are policed (other
       // host threads may be inside synchronous copies of their own handles; under the stricter modes HIP fails those
@@ -1044,19 +1087,20 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
           ce = hipStreamEndCapture(d->stream, &graph);
         }
       }
-      if (ce == hipSuccess && s2 == CC_OK && graph) ie = hipGraphInstantiate(&P->graph_exec, graph, nullptr, nullptr, 0);
+      if (ce == hipSuccess && s2 == CC_OK && graph) ie = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
       if (graph) (void)hipGraphDestroy(graph);
-      if (ce != hipSuccess || s2 != CC_OK || ie != hipSuccess || !P->graph_exec) {
+      if (ce != hipSuccess || s2 != CC_OK || ie != hipSuccess || !gexec) {
         // said once per detector, on stderr: the call still succeeds, only the launch-bound single-image path gets slower
         std::fprintf(stderr, "[ccamd] hipGraph capture of the single-image pass failed (begin/end: %s, body status %d, instantiate: %s): "
                              "this detector uses ordinary launches from now on\n",
                      hipGetErrorString(ce), (int)s2, hipGetErrorString(ie));
         (void)hipGetLastError();
-        P->graph_exec = nullptr;
+        gexec = nullptr;
         d->use_graph = 0;  // ordinary launches from now on (this call included)
       } else {
-        P->graph_key = key_now();
-        CC_HIP(hipGraphLaunch(P->graph_exec, d->stream));
+        P->graph_key[fmt] = key_now();
+        d->graph_captures++;
+        CC_HIP(hipGraphLaunch(gexec, d->stream));
         launched = true;
         d->last_call_graph = 1;
       }
@@ -1064,7 +1108,7 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     if (!launched) {
       stt = body();
       if (stt != CC_OK) return stt;
-      P->graph_warm = true;  // every buffer now has its size: the next call can be captured
+      P->graph_warm[fmt] = true;  // every buffer now has its size: the next call can be captured
     }
     CC_HIP(hipStreamSynchronize(d->stream));
     const int raw = d->h_counts[0], kept = d->h_counts[1];
@@ -1126,6 +1170,11 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
   // them. Two slots are not enough for that: the slot of pass i + 1 would be the one of pass i - 1, which is still
   // unfetched at that point and re-reads its frames if it has to be redone (candidate-list overflow). With three, the slot
   // that is overwritten belongs to pass i - 2, fetched when pass i - 1 was launched.
+  // Colour frames take the same slots: k_to_gray writes the pass's gray frames there (from the caller's device buffer, or from
+  // d_color, where stage_host_frames has put host frames), so a redone pass re-reads gray frames like any other. The rule holds
+  // only while every pass uses the same slot pitch: the device slots are gray frames of the plan (a pending pass of another
+  // plan is retired first), the pinned slots have one pitch for every format (stage_host_frames).
+  const bool staged = !on_device || fmt != CC_PIX_GRAY8;
   const uint8_t* prestaged = nullptr;
   auto stage_pass = [&](int pf0, int pnf, const uint8_t** where) -> cc_status {
     const size_t rs = (size_t)align_up(width, 4), fs = rs * (size_t)height;
@@ -1143,9 +1192,32 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     const int sslot = d->stage_slot;
     d->stage_slot = (d->stage_slot + 1) % kStageSlots;
     uint8_t* stage = d->d_frames.p + (size_t)sslot * fs * (size_t)d->pass_capacity;
-    const cc_status st2 = stage_host_frames(d, frames + (size_t)pf0 * frame_stride, pnf, width, height, row_stride, frame_stride, stage, rs, fs,
-                                            sslot, front);
-    if (st2 != CC_OK) return st2;
+    if (fmt == CC_PIX_GRAY8) {
+      const cc_status st2 = stage_host_frames(d, frames + (size_t)pf0 * frame_stride, pnf, width, height, row_stride, frame_stride, stage, rs,
+                                              fs, sslot, front);
+      if (st2 != CC_OK) return st2;
+      *where = stage;
+      return CC_OK;
+    }
+    const uint8_t* csrc = frames + (size_t)pf0 * frame_stride;
+    size_t crs = row_stride, cfs = frame_stride;
+    if (!on_device) {  // the colour bytes travel as they are, like gray frames, into d_color
+      const int crows = pix_rows(fmt, height);
+      const size_t cw = (size_t)width * pix_bytes(fmt);
+      crs = (size_t)align_up((int)cw, 4);
+      cfs = crs * (size_t)crows;
+      const size_t cneed = cfs * (size_t)d->pass_capacity;
+      if (d->d_color.n < cneed && d->d_color.p) CC_HIP(hipStreamSynchronize(front));  // the last k_to_gray may still read it
+      CC_HIP(d->d_color.ensure(cneed));
+      const cc_status st2 = stage_host_frames(d, csrc, pnf, (int)cw, crows, row_stride, frame_stride, d->d_color.p, crs, cfs, sslot, front);
+      if (st2 != CC_OK) return st2;
+      csrc = d->d_color.p;
+    }
+    {
+      EvScope ev(d, EV_RESIZE, front);  // the conversion's time counts as pyramid time (include/cascadeclassifier_amd.h)
+      launch_to_gray(front, fmt, csrc, crs, cfs, width, height, pnf, stage, rs, fs);
+    }
+    CC_HIP(hipGetLastError());
     *where = stage;
     return CC_OK;
   };
@@ -1162,7 +1234,7 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     ps.fs = frame_stride;
     ps.debug = debug;
     ps.sink = sink;
-    if (on_device) {
+    if (!staged) {
       ps.dptr = frames + (size_t)f0 * frame_stride;
     } else {
       ps.rs = (size_t)align_up(width, 4);
@@ -1186,7 +1258,7 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     th("launched");
     ps.cap = d->cand_cap;
     ps.gen = d->list_gen;
-    if (!on_device && pi + 1 < sizes.size() && want_results) {  // the next pass's frames travel while this pass runs
+    if (staged && pi + 1 < sizes.size() && want_results) {  // the next pass's frames travel while this pass runs
       stt = stage_pass(f0 + sizes[pi], sizes[pi + 1], &prestaged);
       if (stt != CC_OK) return stt;
       th("next pass staged");
@@ -1694,6 +1766,11 @@ int cc_detector_graph_active(const cc_detector* d) {
   return d->last_call_graph;
 }
 
+int64_t cc_detector_graph_captures(const cc_detector* d) {
+  if (!d) return (int64_t)set_error(CC_ERR_INVALID_ARG, "cc_detector_graph_captures: null detector");
+  return d->graph_captures;
+}
+
 cc_status cc_detector_set_profiling(cc_detector* d, int enabled) {
   if (!d) return set_error(CC_ERR_INVALID_ARG, "cc_detector_set_profiling: null detector");
   d->profiling = enabled != 0;
@@ -1718,14 +1795,20 @@ cc_status cc_detect_batch_device_only(cc_detector* d, const uint8_t* frames, int
                                       size_t row_stride, size_t frame_stride, const cc_detect_params* p) {
   cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch_device_only");
   if (st != CC_OK) return st;
-  return run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, p, false, false,
+  return run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, CC_PIX_GRAY8, p, false, false,
                    [](int, int, std::vector<CandOut>&) {});
 }
 
 cc_status cc_detect_batch(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
                           size_t row_stride, size_t frame_stride, const cc_detect_params* p, cc_rect* out, int cap,
                           int32_t* offsets) {
-  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch");
+  return cc_detect_batch_fmt(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, CC_PIX_GRAY8, p, out, cap, offsets);
+}
+
+cc_status cc_detect_batch_fmt(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
+                              size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p, cc_rect* out,
+                              int cap, int32_t* offsets) {
+  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch", pixel_format, frame_stride);
   if (st != CC_OK) return st;
   if (!offsets || (cap > 0 && !out) || cap < 0) return set_error(CC_ERR_INVALID_ARG, "cc_detect_batch: bad output buffers");
   const auto t_start = std::chrono::steady_clock::now();
@@ -1739,7 +1822,7 @@ cc_status cc_detect_batch(cc_detector* d, const uint8_t* frames, int on_device, 
     group_pass(min_neighbors, f0, nf, cands, grouped);
     group_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   };
-  st = run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, p, true, false, consume);
+  st = run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format, p, true, false, consume);
   if (st != CC_OK) return st;
   long long total = 0;
   for (int f = 0; f < n_frames; f++) {
@@ -1795,9 +1878,15 @@ static cc_status wait_sink_jobs(BatchSink& sink, const char* who) {
 
 cc_status cc_detect_batch_submit(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
                                  size_t row_stride, size_t frame_stride, const cc_detect_params* p, cc_batch_ticket** ticket) {
+  return cc_detect_batch_submit_fmt(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, CC_PIX_GRAY8, p, ticket);
+}
+
+cc_status cc_detect_batch_submit_fmt(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
+                                     size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p,
+                                     cc_batch_ticket** ticket) {
   if (!ticket) return set_error(CC_ERR_INVALID_ARG, "cc_detect_batch_submit: null ticket pointer");
   *ticket = nullptr;
-  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch_submit");
+  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch_submit", pixel_format, frame_stride);
   if (st != CC_OK) return st;
   std::unique_ptr<cc_batch_ticket> t(new cc_batch_ticket);
   t->owner = d;
@@ -1809,7 +1898,7 @@ cc_status cc_detect_batch_submit(cc_detector* d, const uint8_t* frames, int on_d
   const int min_neighbors = p->min_neighbors;
   t->sink->consume = [grouped, min_neighbors](int f0, int nf, std::vector<CandOut>& cands) { group_pass(min_neighbors, f0, nf, cands, *grouped); };
   t->sink->async_consume = true;  // passes of a batch cover disjoint frames: their helpers never touch the same entry of `grouped`
-  st = run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, p, true, false,
+  st = run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format, p, true, false,
                  [](int, int, std::vector<CandOut>&) {}, /*defer_last=*/true, t->sink);
   if (st != CC_OK) {
     if (d->pending.active && d->pending.sink == t->sink) {  // the batch failed: its unfetched pass delivers to nobody
@@ -1886,9 +1975,15 @@ cc_status cc_detect_batch_discard(cc_detector* d, cc_batch_ticket* t) {
 
 cc_status cc_detect_multiscale(cc_detector* d, const uint8_t* gray, int width, int height, size_t row_stride,
                                const cc_detect_params* p, cc_rect* out, int cap, int* n) {
+  return cc_detect_multiscale_fmt(d, gray, width, height, row_stride, CC_PIX_GRAY8, p, out, cap, n);
+}
+
+cc_status cc_detect_multiscale_fmt(cc_detector* d, const uint8_t* img, int width, int height, size_t row_stride, int pixel_format,
+                                   const cc_detect_params* p, cc_rect* out, int cap, int* n) {
   if (!n) return set_error(CC_ERR_INVALID_ARG, "cc_detect_multiscale: null count pointer");
   int32_t offsets[2] = {0, 0};
-  cc_status st = cc_detect_batch(d, gray, 0, 1, width, height, row_stride, row_stride * (size_t)height, p, out, cap, offsets);
+  cc_status st = cc_detect_batch_fmt(d, img, 0, 1, width, height, row_stride, row_stride * (size_t)pix_rows(pixel_format, height),
+                                     pixel_format, p, out, cap, offsets);
   if (st == CC_OK || st == CC_ERR_BUFFER_TOO_SMALL) *n = offsets[1];
   return st;
 }
@@ -1896,12 +1991,18 @@ cc_status cc_detect_multiscale(cc_detector* d, const uint8_t* gray, int width, i
 cc_status cc_detect_multiscale_levels(cc_detector* d, const uint8_t* gray, int width, int height, size_t row_stride,
                                       const cc_detect_params* p, cc_rect* out, int32_t* reject_levels, double* level_weights,
                                       int cap, int* n) {
-  cc_status st = check_frame_args(d, gray, 1, width, height, row_stride, p, "cc_detect_multiscale_levels");
+  return cc_detect_multiscale_levels_fmt(d, gray, width, height, row_stride, CC_PIX_GRAY8, p, out, reject_levels, level_weights, cap, n);
+}
+
+cc_status cc_detect_multiscale_levels_fmt(cc_detector* d, const uint8_t* img, int width, int height, size_t row_stride,
+                                          int pixel_format, const cc_detect_params* p, cc_rect* out, int32_t* reject_levels,
+                                          double* level_weights, int cap, int* n) {
+  cc_status st = check_frame_args(d, img, 1, width, height, row_stride, p, "cc_detect_multiscale_levels", pixel_format);
   if (st != CC_OK) return st;
   if (!n || cap < 0 || (cap > 0 && (!out || !reject_levels || !level_weights)))
     return set_error(CC_ERR_INVALID_ARG, "cc_detect_multiscale_levels: bad output buffers");
   std::vector<CandOut> cands;
-  st = run_batch(d, gray, 0, 1, width, height, row_stride, row_stride * (size_t)height, p, true, false,
+  st = run_batch(d, img, 0, 1, width, height, row_stride, row_stride * (size_t)pix_rows(pixel_format, height), pixel_format, p, true, false,
                  [&](int, int, std::vector<CandOut>& c) { cands.insert(cands.end(), c.begin(), c.end()); });
   if (st != CC_OK) return st;
   sort_candidates(cands);  // OpenCV's single-threaded order
@@ -1931,7 +2032,7 @@ cc_status cc_detect_raw(cc_detector* d, const uint8_t* gray, int width, int heig
   if (st != CC_OK) return st;
   if (!n || (cap > 0 && !cand)) return set_error(CC_ERR_INVALID_ARG, "cc_detect_raw: bad output buffers");
   std::vector<CandOut> cands;
-  st = run_batch(d, gray, 0, 1, width, height, row_stride, row_stride * (size_t)height, p, true, false,
+  st = run_batch(d, gray, 0, 1, width, height, row_stride, row_stride * (size_t)height, CC_PIX_GRAY8, p, true, false,
                  [&](int, int, std::vector<CandOut>& c) { cands.insert(cands.end(), c.begin(), c.end()); });
   if (st != CC_OK) return st;
   sort_candidates(cands);
@@ -1952,7 +2053,7 @@ cc_status cc_detect_debug_windows(cc_detector* d, const uint8_t* gray, int width
   if (st != CC_OK) return st;
   if (!n_windows) return set_error(CC_ERR_INVALID_ARG, "cc_detect_debug_windows: null count pointer");
   std::vector<CandOut> cands;
-  st = run_batch(d, gray, 0, 1, width, height, row_stride, row_stride * (size_t)height, p, true, true,
+  st = run_batch(d, gray, 0, 1, width, height, row_stride, row_stride * (size_t)height, CC_PIX_GRAY8, p, true, true,
                  [&](int, int, std::vector<CandOut>& c) { cands.insert(cands.end(), c.begin(), c.end()); });
   if (st != CC_OK) return st;
   Plan* P = nullptr;

@@ -83,6 +83,23 @@ struct FrontIO {
 // runs it inside a hipGraph capture).
 void launch_front(hipStream_t st, const FrontTables& T, const FrontIO& io, int nf, int parts);
 
+// ---- colour frames (CC_PIX_*, include/cascadeclassifier_amd.h) ----
+// Bytes per pixel of a row (1 for the planar format, whose planes are rows of one channel); 0 for an unknown format.
+inline int pix_bytes(int fmt) {
+  switch (fmt) {
+    case CC_PIX_GRAY8: case CC_PIX_RGB8_PLANAR: return 1;
+    case CC_PIX_BGR8: case CC_PIX_RGB8: return 3;
+    case CC_PIX_BGRA8: case CC_PIX_RGBA8: return 4;
+    default: return 0;
+  }
+}
+// Rows of `row_stride` bytes that one frame of the format spans (the planar format: three planes of `height` rows).
+inline int pix_rows(int fmt, int height) { return fmt == CC_PIX_RGB8_PLANAR ? 3 * height : height; }
+// k_to_gray: nf frames of format `fmt` (frame f at src + f * frame_stride) -> gray frames at dst + f * dst_frame_stride,
+// rows dst_stride apart. dst and dst_stride must be multiples of 4; src and row_stride may be anything. Only the launch.
+void launch_to_gray(hipStream_t st, int fmt, const uint8_t* src, size_t row_stride, size_t frame_stride, int w, int h, int nf,
+                    uint8_t* dst, size_t dst_stride, size_t dst_frame_stride);
+
 // ---- checks shared by the entry points (cc_detect.hip) ----
 // Detection and its run-time specialisation are Haar / LBP only: nothing in the reference defines detection with a HOG
 // cascade. Every detector entry point calls this before the model reaches a kernel or a table builder (the LBP branches

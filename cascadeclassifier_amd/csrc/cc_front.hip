@@ -399,6 +399,103 @@ __global__ __launch_bounds__(64 * TILT_GROUPS) void k_tilted_cols(const uint8_t*
   if (!FINAL) tot[Tg.col_at(g) + x] = acc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// K0: colour -> gray (COLOR_BGR2GRAY's integer form, include/cascadeclassifier_amd.h), in front of the pyramid: the gray
+// frames land in the detector's staging slots with the layout stage_host_frames gives gray frames, so everything behind
+// this kernel is the gray path unchanged. Memory-bound (3-4 bytes in, 1 out per pixel): a lane takes 16 pixels of a row,
+// reads them with 16-byte loads at whatever alignment the row has (3 or 4 of them interleaved, one per plane for the
+// planar format) and writes one 16-byte store. A row's last width % 16 pixels go byte by byte, by one lane of the row.
+// ------------------------------------------------------------------------------------------------
+struct __attribute__((packed, aligned(4))) Gray16 {  // 16 gray bytes at a multiple of 4 (the staging layout's pitch)
+  unsigned d[4];
+};
+__device__ __forceinline__ unsigned gray_of(unsigned b, unsigned g, unsigned r) { return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14; }
+template <int FMT>
+__global__ __launch_bounds__(256) void k_to_gray(const uint8_t* __restrict__ src, size_t row_stride, size_t frame_stride, int w, int h,
+                                                 int chunks_per_row, uint8_t* __restrict__ dst, size_t dst_stride, size_t dst_frame_stride) {
+  constexpr bool PLANAR = FMT == CC_PIX_RGB8_PLANAR;
+  constexpr int BPP = (FMT == CC_PIX_BGR8 || FMT == CC_PIX_RGB8) ? 3 : (FMT == CC_PIX_BGRA8 || FMT == CC_PIX_RGBA8) ? 4 : 1;
+  // byte of a pixel (planar: plane) that holds B and R; G is byte 1
+  constexpr int CB = (FMT == CC_PIX_BGR8 || FMT == CC_PIX_BGRA8) ? 0 : (FMT == CC_PIX_GRAY8 ? 0 : 2);
+  constexpr int CR = (FMT == CC_PIX_BGR8 || FMT == CC_PIX_BGRA8) ? 2 : 0;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int y = i / chunks_per_row;
+  if (y >= h) return;
+  const int x0 = (i - y * chunks_per_row) * 16;
+  const uint8_t* s = src + (size_t)blockIdx.y * frame_stride + (size_t)y * row_stride;
+  const size_t plane = row_stride * (size_t)h;
+  uint8_t* o = dst + (size_t)blockIdx.y * dst_frame_stride + (size_t)y * dst_stride + x0;
+  auto px = [&](int x, int c) -> unsigned {  // channel c of pixel x, one byte load
+    if (FMT == CC_PIX_GRAY8) return s[x];
+    return PLANAR ? s[(size_t)c * plane + x] : s[(size_t)x * BPP + c];
+  };
+  if (x0 + 16 <= w) {
+    constexpr int NW = PLANAR ? 12 : 4 * BPP;  // words loaded
+    unsigned v[NW];
+    if (PLANAR) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const Bytes16 q = *reinterpret_cast<const Bytes16*>(s + (size_t)c * plane + x0);
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[4 * c + j] = q.d[j];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < BPP; k++) {
+        const Bytes16 q = *reinterpret_cast<const Bytes16*>(s + (size_t)x0 * BPP + 16 * k);
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[4 * k + j] = q.d[j];
+      }
+    }
+    // byte n of the loaded words: interleaved pixel k channel c at n = BPP k + c; planar plane c pixel k at n = 16 c + k
+    auto byte = [&](int n) -> unsigned { return (v[n >> 2] >> (8 * (n & 3))) & 255u; };
+    Gray16 g;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      unsigned word = 0;
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const int k = 4 * j + b;
+        unsigned gv;
+        if (FMT == CC_PIX_GRAY8)
+          gv = byte(k);
+        else if (PLANAR)
+          gv = gray_of(byte(32 + k), byte(16 + k), byte(k));
+        else
+          gv = gray_of(byte(BPP * k + CB), byte(BPP * k + 1), byte(BPP * k + CR));
+        word |= gv << (8 * b);
+      }
+      g.d[j] = word;
+    }
+    *reinterpret_cast<Gray16*>(o) = g;
+  } else {
+    for (int x = x0; x < w; x++)
+      o[x - x0] = FMT == CC_PIX_GRAY8 ? (uint8_t)px(x, 0) : (uint8_t)gray_of(px(x, CB), px(x, 1), px(x, CR));
+  }
+}
+
+void launch_to_gray(hipStream_t st, int fmt, const uint8_t* src, size_t row_stride, size_t frame_stride, int w, int h, int nf,
+                    uint8_t* dst, size_t dst_stride, size_t dst_frame_stride) {
+  if (nf <= 0 || w <= 0 || h <= 0) return;
+  const int cpr = (w + 15) / 16;
+  const dim3 grid((unsigned)(((long long)h * cpr + 255) / 256), (unsigned)nf);
+#define CC_TO_GRAY(F)                                                                                                     \
+  case F:                                                                                                                  \
+    hipLaunchKernelGGL(k_to_gray<F>, grid, dim3(256), 0, st, src, row_stride, frame_stride, w, h, cpr, dst, dst_stride, \
+                       dst_frame_stride);                                                                                  \
+    break;
+  switch (fmt) {
+    CC_TO_GRAY(CC_PIX_GRAY8)
+    CC_TO_GRAY(CC_PIX_BGR8)
+    CC_TO_GRAY(CC_PIX_BGRA8)
+    CC_TO_GRAY(CC_PIX_RGB8)
+    CC_TO_GRAY(CC_PIX_RGBA8)
+    CC_TO_GRAY(CC_PIX_RGB8_PLANAR)
+    default: break;
+  }
+#undef CC_TO_GRAY
+}
+
 FrontLayout front_layout(int src_w, int src_h, const std::vector<int2>& sizes, bool tilted) {
   const int ns = (int)sizes.size();
   FrontLayout L;
@@ -557,6 +654,31 @@ cc_status cc_integral_u8(int device, const uint8_t* img, int width, int height, 
     if (out[c])
       CC_HIP(hipMemcpy2DAsync(out[c], opitch, d_int.p + c * L.int_frame_elems, (size_t)L.sd[0].pitchI * 4, opitch, height + 1,
                               hipMemcpyDeviceToHost, own.s));
+  CC_HIP(hipStreamSynchronize(own.s));
+  return CC_OK;
+}
+
+cc_status cc_to_gray_u8(int device, const uint8_t* src, int pixel_format, int width, int height, size_t row_stride, uint8_t* dst,
+                        size_t dst_stride) {
+  const int bpp = pix_bytes(pixel_format);
+  if (bpp == 0) return set_error(CC_ERR_INVALID_ARG, "cc_to_gray_u8: unknown pixel format %d", pixel_format);
+  if (!src || !dst || width < 1 || height < 1 || row_stride < (size_t)width * bpp || dst_stride < (size_t)width)
+    return set_error(CC_ERR_INVALID_ARG, "cc_to_gray_u8: bad argument");
+  cc_status st = ensure_device(device);
+  if (st != CC_OK) return st;
+  OwnStream own;  // not the legacy stream: see copy_sync
+  CC_HIP(own.create());
+  const int rows = pix_rows(pixel_format, height);
+  const size_t span = (size_t)(rows - 1) * row_stride + (size_t)width * bpp;  // bytes from the first pixel to the last
+  const size_t lead = (size_t)((uintptr_t)src & 15);  // the device copy starts at the same offset within 16 bytes
+  const size_t dpitch = (size_t)align_up(width, 4);
+  DevBuf<uint8_t> d_src, d_dst;
+  CC_HIP(d_src.ensure(lead + span));
+  CC_HIP(d_dst.ensure(dpitch * (size_t)height));
+  CC_HIP(hipMemcpyAsync(d_src.p + lead, src, span, hipMemcpyHostToDevice, own.s));
+  launch_to_gray(own.s, pixel_format, d_src.p + lead, row_stride, 0, width, height, 1, d_dst.p, dpitch, 0);
+  CC_HIP(hipGetLastError());
+  CC_HIP(hipMemcpy2DAsync(dst, dst_stride, d_dst.p, dpitch, width, height, hipMemcpyDeviceToHost, own.s));
   CC_HIP(hipStreamSynchronize(own.s));
   return CC_OK;
 }

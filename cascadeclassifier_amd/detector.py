@@ -60,6 +60,64 @@ def group_rectangles(rects, group_threshold, eps=0.2) -> np.ndarray:
     return out[:n.value].copy()
 
 
+# pixel_format keywords -> CC_PIX_* (include/cascadeclassifier_amd.h). 3- and 4-channel arrays default to cv2's BGR / BGRA.
+PIXEL_FORMATS = {"gray": L.CC_PIX_GRAY8, "bgr": L.CC_PIX_BGR8, "bgra": L.CC_PIX_BGRA8, "rgb": L.CC_PIX_RGB8,
+                 "rgba": L.CC_PIX_RGBA8, "rgb_planar": L.CC_PIX_RGB8_PLANAR}
+_CHANNELS = {L.CC_PIX_GRAY8: 1, L.CC_PIX_BGR8: 3, L.CC_PIX_BGRA8: 4, L.CC_PIX_RGB8: 3, L.CC_PIX_RGBA8: 4,
+             L.CC_PIX_RGB8_PLANAR: 3}
+
+
+def frame_layout(shape, pixel_format=None, batched=False):
+    """Shape of one image or of a batch of frames -> (n, height, width, CC_PIX_* code, row_stride, frame_stride), the
+    strides in bytes of a dense uint8 array of that shape. One image: (H, W) gray, (H, W, 3) / (H, W, 4) colour, or
+    (3, H, W) with pixel_format="rgb_planar". A batch: the same with a leading n. pixel_format (None = what the shape
+    says: gray, "bgr" or "bgra") must agree with the shape; anything else raises CascadeError(CC_ERR_INVALID_ARG)."""
+    def bad(why):
+        return L.CascadeError(L.CC_ERR_INVALID_ARG, f"frame shape {tuple(shape)}, pixel_format {pixel_format!r}: {why}")
+
+    shape = tuple(int(v) for v in shape)
+    if pixel_format is not None and pixel_format not in PIXEL_FORMATS:
+        raise bad(f"unknown pixel format (one of {sorted(PIXEL_FORMATS)})")
+    if batched and len(shape) < 1:
+        raise bad("no frame count")
+    dims = shape[1:] if batched else shape
+    n = shape[0] if batched else 1
+    if len(dims) == 2:
+        fmt = PIXEL_FORMATS[pixel_format or "gray"]
+        if fmt != L.CC_PIX_GRAY8:
+            raise bad("a 2-d frame is gray")
+        h, w = dims
+        rs = w
+    elif len(dims) == 3 and pixel_format == "rgb_planar":
+        c, h, w = dims
+        if c != 3:
+            raise bad("planar frames are (3, H, W)")
+        fmt, rs = L.CC_PIX_RGB8_PLANAR, w
+    elif len(dims) == 3:
+        h, w, c = dims
+        if c not in (3, 4):
+            raise bad("colour frames have 3 or 4 channels")
+        fmt = PIXEL_FORMATS[pixel_format or ("bgr" if c == 3 else "bgra")]
+        if _CHANNELS[fmt] != c or fmt == L.CC_PIX_RGB8_PLANAR:
+            raise bad(f"{c} channels do not match the pixel format")
+        rs = w * c
+    else:
+        raise bad("expected (H, W), (H, W, C) or (3, H, W) per frame")
+    if n < 0 or h < 1 or w < 1:
+        raise bad("empty frame")
+    rows = 3 * h if fmt == L.CC_PIX_RGB8_PLANAR else h
+    return n, h, w, fmt, rs, rs * rows
+
+
+def to_gray(img, pixel_format=None, device=0):
+    """Colour -> gray on the device with the detector's conversion (cc_to_gray_u8): one image as detectMultiScale takes it."""
+    img = np.ascontiguousarray(img, np.uint8)
+    _, h, w, fmt, rs, _ = frame_layout(img.shape, pixel_format)
+    dst = np.empty((h, w), np.uint8)
+    L.check(L.lib().cc_to_gray_u8(device, _vp(img), fmt, w, h, rs, _vp(dst), w))
+    return dst
+
+
 def integral(img, device=0, sqsum=False, tilted=False):
     img = np.ascontiguousarray(img, np.uint8)
     h, w = img.shape
@@ -161,43 +219,52 @@ class CascadeClassifier:
     def set_stream(self, hip_stream: int | None):
         L.check(L.lib().cc_detector_set_stream(self._detector(), C.c_void_p(hip_stream or 0)))
 
-    def detectMultiScale(self, image, scaleFactor=1.1, minNeighbors=3, flags=0, minSize=None, maxSize=None) -> np.ndarray:
-        """image: HxW uint8 (gray). Returns an (n, 4) int32 array of (x, y, w, h) like cv2 does."""
+    def detectMultiScale(self, image, scaleFactor=1.1, minNeighbors=3, flags=0, minSize=None, maxSize=None,
+                         pixel_format=None) -> np.ndarray:
+        """image: HxW uint8 (gray), or HxWx3 / HxWx4 colour -- BGR / BGRA as cv2 takes them, pixel_format="rgb" / "rgba"
+        for the other order, or 3xHxW with pixel_format="rgb_planar" -- converted to gray on the device.
+        Returns an (n, 4) int32 array of (x, y, w, h) like cv2 does."""
         image = np.ascontiguousarray(image, np.uint8)
-        if image.ndim != 2:
-            raise L.CascadeError(L.CC_ERR_INVALID_ARG, "detectMultiScale expects a single-channel 8-bit image")
-        h, w = image.shape
+        _, h, w, fmt, rs, _ = frame_layout(image.shape, pixel_format)
         p = _params(scaleFactor, minNeighbors, minSize, maxSize)
         cap = 1024
         while True:
             out = np.zeros((cap, 4), np.int32)
             n = C.c_int(0)
-            st = L.lib().cc_detect_multiscale(self._detector(), _vp(image), w, h, w, C.byref(p), _vp(out), cap, C.byref(n))
+            st = L.lib().cc_detect_multiscale_fmt(self._detector(), _vp(image), w, h, rs, fmt, C.byref(p), _vp(out), cap,
+                                                  C.byref(n))
             if st == L.CC_ERR_BUFFER_TOO_SMALL:
                 cap = n.value
                 continue
             L.check(st)
             return out[:n.value].copy()
 
-    def detect_batch(self, frames, scaleFactor=1.1, minNeighbors=3, minSize=None, maxSize=None, device_ptr=None,
-                     shape=None, row_stride=None, frame_stride=None):
-        """frames: (n, H, W) uint8 numpy array in host memory, or device_ptr + shape=(n,H,W) for frames already in HBM.
-        Returns a list of (k_i, 4) arrays."""
-        p = _params(scaleFactor, minNeighbors, minSize, maxSize)
+    @staticmethod
+    def _batch_frames(frames, device_ptr, shape, row_stride, frame_stride, pixel_format):
+        """-> (keep-alive array or None, pointer, on_device, n, h, w, format, row_stride, frame_stride)"""
         if device_ptr is None:
             frames = np.ascontiguousarray(frames, np.uint8)
-            n, h, w = frames.shape
-            ptr, on_dev, rs, fs = _vp(frames), 0, w, w * h
-        else:
-            n, h, w = shape
-            ptr, on_dev = C.c_void_p(device_ptr), 1
-            rs = row_stride or w
-            fs = frame_stride or rs * h
+            n, h, w, fmt, rs, fs = frame_layout(frames.shape, pixel_format, batched=True)
+            return frames, _vp(frames), 0, n, h, w, fmt, rs, fs
+        n, h, w, fmt, rs, fs = frame_layout(shape, pixel_format, batched=True)
+        rs = row_stride or rs
+        fs = frame_stride or rs * (3 * h if fmt == L.CC_PIX_RGB8_PLANAR else h)
+        return None, C.c_void_p(device_ptr), 1, n, h, w, fmt, rs, fs
+
+    def detect_batch(self, frames, scaleFactor=1.1, minNeighbors=3, minSize=None, maxSize=None, device_ptr=None,
+                     shape=None, row_stride=None, frame_stride=None, pixel_format=None):
+        """frames: (n, H, W) uint8 numpy array in host memory -- or (n, H, W, C) colour, BGR / BGRA unless pixel_format
+        says "rgb" / "rgba" -- or device_ptr + shape=(n, H, W[, C]) for frames already in HBM (shape=(n, 3, H, W) with
+        pixel_format="rgb_planar"); row_stride / frame_stride in bytes. Returns a list of (k_i, 4) arrays."""
+        p = _params(scaleFactor, minNeighbors, minSize, maxSize)
+        frames, ptr, on_dev, n, h, w, fmt, rs, fs = self._batch_frames(frames, device_ptr, shape, row_stride, frame_stride,
+                                                                         pixel_format)
         cap = max(256 * n, 1024)
         while True:
             out = np.zeros((cap, 4), np.int32)
             offs = np.zeros(n + 1, np.int32)
-            st = L.lib().cc_detect_batch(self._detector(), ptr, on_dev, n, w, h, rs, fs, C.byref(p), _vp(out), cap, _vp(offs))
+            st = L.lib().cc_detect_batch_fmt(self._detector(), ptr, on_dev, n, w, h, rs, fs, fmt, C.byref(p), _vp(out), cap,
+                                             _vp(offs))
             if st == L.CC_ERR_BUFFER_TOO_SMALL:
                 cap = int(offs[n])
                 continue
@@ -205,23 +272,16 @@ class CascadeClassifier:
             return [out[offs[i]:offs[i + 1]].copy() for i in range(n)]
 
     def detect_batch_submit(self, frames, scaleFactor=1.1, minNeighbors=3, minSize=None, maxSize=None, device_ptr=None,
-                            shape=None, row_stride=None, frame_stride=None):
+                            shape=None, row_stride=None, frame_stride=None, pixel_format=None):
         """First half of detect_batch (cc_detect_batch_submit): launches the batch and returns a ticket while its last pass
         still runs. Submit the next batch before collecting this one to overlap them. The frames must stay alive until
-        detect_batch_collect(ticket)."""
+        detect_batch_collect(ticket). Frames, shapes and pixel formats as detect_batch takes them."""
         p = _params(scaleFactor, minNeighbors, minSize, maxSize)
-        keep = None
-        if device_ptr is None:
-            keep = frames = np.ascontiguousarray(frames, np.uint8)
-            n, h, w = frames.shape
-            ptr, on_dev, rs, fs = _vp(frames), 0, w, w * h
-        else:
-            n, h, w = shape
-            ptr, on_dev = C.c_void_p(device_ptr), 1
-            rs = row_stride or w
-            fs = frame_stride or rs * h
+        keep, ptr, on_dev, n, h, w, fmt, rs, fs = self._batch_frames(frames, device_ptr, shape, row_stride, frame_stride,
+                                                                       pixel_format)
         t = C.c_void_p()
-        L.check(L.lib().cc_detect_batch_submit(self._detector(), ptr, on_dev, n, w, h, rs, fs, C.byref(p), C.byref(t)))
+        L.check(L.lib().cc_detect_batch_submit_fmt(self._detector(), ptr, on_dev, n, w, h, rs, fs, fmt, C.byref(p),
+                                                   C.byref(t)))
         return {"ticket": t, "n": n, "frames": keep}
 
     def detect_batch_collect(self, ticket):
@@ -254,13 +314,15 @@ class CascadeClassifier:
         fs = frame_stride or rs * h
         L.check(L.lib().cc_detect_batch_device_only(self._detector(), C.c_void_p(device_ptr), 1, n, w, h, rs, fs, C.byref(p)))
 
-    def detectMultiScale3(self, image, scaleFactor=1.1, minNeighbors=3, flags=0, minSize=None, maxSize=None, outputRejectLevels=True):
-        """cv2.CascadeClassifier.detectMultiScale3: (rects (n, 4) int32, rejectLevels (n,) int32, levelWeights (n,) float64)."""
+    def detectMultiScale3(self, image, scaleFactor=1.1, minNeighbors=3, flags=0, minSize=None, maxSize=None, outputRejectLevels=True,
+                          pixel_format=None):
+        """cv2.CascadeClassifier.detectMultiScale3: (rects (n, 4) int32, rejectLevels (n,) int32, levelWeights (n,) float64).
+        Images as detectMultiScale takes them."""
         if not outputRejectLevels:
-            r = self.detectMultiScale(image, scaleFactor, minNeighbors, flags, minSize, maxSize)
+            r = self.detectMultiScale(image, scaleFactor, minNeighbors, flags, minSize, maxSize, pixel_format=pixel_format)
             return r, np.zeros(0, np.int32), np.zeros(0, np.float64)
         image = np.ascontiguousarray(image, np.uint8)
-        h, w = image.shape
+        _, h, w, fmt, rs, _ = frame_layout(image.shape, pixel_format)
         p = _params(scaleFactor, minNeighbors, minSize, maxSize)
         cap = 1024
         while True:
@@ -268,8 +330,8 @@ class CascadeClassifier:
             levels = np.zeros(cap, np.int32)
             weights = np.zeros(cap, np.float64)
             n = C.c_int(0)
-            st = L.lib().cc_detect_multiscale_levels(self._detector(), _vp(image), w, h, w, C.byref(p), _vp(rects), _vp(levels), _vp(weights),
-                                                     cap, C.byref(n))
+            st = L.lib().cc_detect_multiscale_levels_fmt(self._detector(), _vp(image), w, h, rs, fmt, C.byref(p), _vp(rects),
+                                                         _vp(levels), _vp(weights), cap, C.byref(n))
             if st == L.CC_ERR_BUFFER_TOO_SMALL:
                 cap = n.value
                 continue
@@ -324,6 +386,10 @@ class CascadeClassifier:
     def graph_active(self) -> bool:
         """True if the last single-image detectMultiScale call was one hipGraph launch (cc_detector_graph_active)."""
         return L.lib().cc_detector_graph_active(self._detector()) == 1
+
+    def graph_captures(self) -> int:
+        """hipGraph captures this detector has made (cc_detector_graph_captures); replays do not count."""
+        return int(L.lib().cc_detector_graph_captures(self._detector()))
 
     def set_profiling(self, on: bool):
         L.check(L.lib().cc_detector_set_profiling(self._detector(), 1 if on else 0))

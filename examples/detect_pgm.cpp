@@ -1,16 +1,19 @@
 // The reference's detection tool (tools/detection/Cpp/main.cpp) on the MI355X library, minus the GUI: reads a binary
-// PGM (P5) instead of cv::imread, runs the cascade with the tool's parameters (scaleFactor 4, minNeighbors 50 unless
-// overridden) and prints one "x y w h" line per detection.
-//   usage: detect_pgm <cascade.xml> <image.pgm> [scaleFactor=4] [minNeighbors=50]
+// PGM (P5, gray) or PPM (P6, RGB) instead of cv::imread, runs the cascade with the tool's parameters (scaleFactor 4,
+// minNeighbors 50 unless overridden) and prints one "x y w h" line per detection. A PPM is turned into BGR on load, as
+// cv::imread(IMREAD_COLOR) hands it over, and goes to detectMultiScale as it is: the tool's cvtColor(BGR2GRAY) runs on
+// the device inside the detector.
+//   usage: detect_pgm <cascade.xml> <image.pgm|image.ppm> [scaleFactor=4] [minNeighbors=50]
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ccamd/traincascade_features.hpp"
 
-static bool read_pgm(const char* path, cv::Mat& gray) {
+static bool read_pnm(const char* path, cv::Mat& img) {
   std::ifstream f(path, std::ios::binary);
   std::string magic;
   int w = 0, h = 0, maxv = 0;
@@ -25,9 +28,12 @@ static bool read_pgm(const char* path, cv::Mat& gray) {
   skip();
   f >> maxv;
   f.get();
-  if (!f || magic != "P5" || w < 1 || h < 1 || maxv != 255) return false;
-  gray = cv::Mat(h, w, CV_8UC1);
-  f.read(reinterpret_cast<char*>(gray.data), (std::streamsize)w * h);
+  if (!f || (magic != "P5" && magic != "P6") || w < 1 || h < 1 || maxv != 255) return false;
+  const int cn = magic == "P6" ? 3 : 1;
+  img = cv::Mat(h, w, cn == 3 ? CV_8UC3 : CV_8UC1);
+  f.read(reinterpret_cast<char*>(img.data), (std::streamsize)w * h * cn);
+  if (cn == 3)  // PPM stores R G B; cv::imread gives B G R
+    for (size_t i = 0; i < (size_t)w * h; i++) std::swap(img.data[3 * i], img.data[3 * i + 2]);
   return (bool)f;
 }
 
@@ -41,16 +47,16 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "cannot load cascade: %s\n", cascade.lastError().c_str());
     return 1;
   }
-  cv::Mat gray;
-  if (!read_pgm(argv[2], gray)) {
-    std::fprintf(stderr, "cannot read %s (binary 8-bit PGM expected)\n", argv[2]);
+  cv::Mat img;  // main.cpp:27 imread(IMREAD_COLOR); no cvtColor here: detectMultiScale takes the BGR image
+  if (!read_pnm(argv[2], img)) {
+    std::fprintf(stderr, "cannot read %s (binary 8-bit PGM or PPM expected)\n", argv[2]);
     return 1;
   }
   const double scaleFactor = argc > 3 ? std::atof(argv[3]) : 4.0;
   const int minNeighbors = argc > 4 ? std::atoi(argv[4]) : 50;
   std::vector<cv::Rect> objects;
   try {
-    cascade.detectMultiScale(gray, objects, scaleFactor, minNeighbors);  // main.cpp:45
+    cascade.detectMultiScale(img, objects, scaleFactor, minNeighbors);  // main.cpp:45
   } catch (const cv::Exception& e) {
     std::fprintf(stderr, "%s\n", e.what());
     return 1;

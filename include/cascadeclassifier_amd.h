@@ -145,6 +145,18 @@ CC_API cc_status cc_detector_set_stream(cc_detector* d, void* hip_stream);
 CC_API cc_status cc_detect_multiscale(cc_detector* d, const uint8_t* gray, int width, int height, size_t row_stride,
                                       const cc_detect_params* p, cc_rect* out, int cap, int* n);
 
+/* Pixel formats of the _fmt entry points and cc_to_gray_u8. Colour frames are converted on the device to the gray the
+ * detector runs on, as OpenCV's 8-bit COLOR_BGR2GRAY / COLOR_RGB2GRAY (RGB2Gray<uchar>, color_rgb.simd.hpp) compute it:
+ *   gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14      (exact integer arithmetic; a 4th channel is ignored)
+ * -- which is NOT PIL's convert("L"). Parity with an installed OpenCV is unpinned, like the rest of the detection side
+ * (OpenCV is not part of the build). The gray frames are then exactly what a caller converting on the host would pass.
+ *   CC_PIX_GRAY8        one byte per pixel (the plain entry points)
+ *   CC_PIX_BGR8/BGRA8   interleaved, OpenCV's order (cv::imread, the reference's detection tool)
+ *   CC_PIX_RGB8/RGBA8   interleaved, PIL / PPM / torch HWC order
+ *   CC_PIX_RGB8_PLANAR  CHW: planes R, G, B of row_stride * height bytes each, back to back (torchvision decoders)
+ * row_stride / frame_stride are in BYTES; a row holds width * bytes-per-pixel bytes (width for the planar format). */
+enum { CC_PIX_GRAY8 = 0, CC_PIX_BGR8 = 1, CC_PIX_BGRA8 = 2, CC_PIX_RGB8 = 3, CC_PIX_RGBA8 = 4, CC_PIX_RGB8_PLANAR = 5 };
+
 /* Batch of equally sized frames. frames points to HOST memory (on_device = 0) or to DEVICE memory of the detector's
  * device (on_device = 1; e.g. a torch tensor's data_ptr): frame f starts at frames + f * frame_stride.
  * Output: rectangles of frame f are out[offsets[f] .. offsets[f+1]); offsets has n_frames + 1 entries. */
@@ -183,6 +195,22 @@ CC_API cc_status cc_detect_batch_submit(cc_detector* d, const uint8_t* frames, i
 CC_API cc_status cc_detect_batch_collect(cc_detector* d, cc_batch_ticket* ticket, cc_rect* out, int cap, int32_t* offsets);
 CC_API cc_status cc_detect_batch_discard(cc_detector* d, cc_batch_ticket* ticket);
 
+/* The _fmt twins take frames in any CC_PIX_* format (after the geometry); the plain calls are these with CC_PIX_GRAY8.
+ * CC_ERR_INVALID_ARG for an unknown format, row_stride < width * bytes-per-pixel, or (n_frames > 1) a frame_stride
+ * shorter than one frame of the format. Colour frames become gray on the device in the pass's staging slot: host frames
+ * are copied as they are (one colour buffer on the device, allocated on first use) and converted by a kernel on the
+ * stream that builds the pyramid; device frames are converted straight from the caller's buffer, which must stay valid
+ * until the batch is collected, as for gray. A colour single-image call is one hipGraph launch too (one graph per scale
+ * plan and pixel format). With profiling on the conversion's time counts under resize_ms (and resize_launches). */
+CC_API cc_status cc_detect_multiscale_fmt(cc_detector* d, const uint8_t* img, int width, int height, size_t row_stride,
+                                          int pixel_format, const cc_detect_params* p, cc_rect* out, int cap, int* n);
+CC_API cc_status cc_detect_batch_fmt(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width,
+                                     int height, size_t row_stride, size_t frame_stride, int pixel_format,
+                                     const cc_detect_params* p, cc_rect* out, int cap, int32_t* offsets);
+CC_API cc_status cc_detect_batch_submit_fmt(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width,
+                                            int height, size_t row_stride, size_t frame_stride, int pixel_format,
+                                            const cc_detect_params* p, cc_batch_ticket** ticket);
+
 /* The outputRejectLevels overload of cv::CascadeClassifier::detectMultiScale (objects, rejectLevels, levelWeights,
  * ..., outputRejectLevels = true; OpenCV 4.6.0 objdetect, no call site in the reference: SURVEY.md 8f-4). Windows that
  * pass every stage are reported with level = number of stages and weight = the stage sum of the last stage; the
@@ -191,6 +219,11 @@ CC_API cc_status cc_detect_batch_discard(cc_detector* d, cc_batch_ticket* ticket
 CC_API cc_status cc_detect_multiscale_levels(cc_detector* d, const uint8_t* gray, int width, int height, size_t row_stride,
                                              const cc_detect_params* p, cc_rect* out, int32_t* reject_levels,
                                              double* level_weights, int cap, int* n);
+
+CC_API cc_status cc_detect_multiscale_levels_fmt(cc_detector* d, const uint8_t* img, int width, int height,
+                                                 size_t row_stride, int pixel_format, const cc_detect_params* p,
+                                                 cc_rect* out, int32_t* reject_levels, double* level_weights, int cap,
+                                                 int* n);
 
 /* Ungrouped candidates of one frame, as int32[7] = {scale_idx, gx, gy, x, y, w, h}, sorted (scale, gy, gx). */
 CC_API cc_status cc_detect_raw(cc_detector* d, const uint8_t* gray, int width, int height, size_t row_stride,
@@ -255,6 +288,9 @@ CC_API cc_status cc_detector_get_timings(cc_detector* d, cc_detector_timings* t,
  * call was a graph launch, 0 if it used ordinary launches (first call, changed geometry, graphs switched off, or a
  * capture that did not come out: then the detector stays on ordinary launches), negative cc_status on a null handle. */
 CC_API int cc_detector_graph_active(const cc_detector* d);
+/* Number of hipGraph captures this detector has made (one per scale plan and pixel format while its buffers keep their
+ * sizes): a replayed call does not add to it. Negative cc_status on a null handle. */
+CC_API int64_t cc_detector_graph_captures(const cc_detector* d);
 
 /* ============================================================================================
  * 3. Building blocks exposed for parity tests and roofline measurement (all run on the device).
@@ -267,6 +303,11 @@ CC_API cc_status cc_integral_u8(int device, const uint8_t* img, int width, int h
                                 int32_t* sqsum, int32_t* tilted);
 CC_API cc_status cc_resize_linear_exact_u8(int device, const uint8_t* src, int sw, int sh, size_t sstride, uint8_t* dst,
                                            int dw, int dh, size_t dstride);
+/* The detector's colour conversion (CC_PIX_*, section 2) on one HOST image: dst receives height rows of width gray bytes,
+ * dst_stride apart. The device copy of src keeps its byte offset modulo 16 and its row stride, so that odd base addresses
+ * and strides reach the kernel as they are. CC_PIX_GRAY8 is copied unchanged (its three weights sum to 2^14). */
+CC_API cc_status cc_to_gray_u8(int device, const uint8_t* src, int pixel_format, int width, int height, size_t row_stride,
+                               uint8_t* dst, size_t dst_stride);
 /* Profiling aid: streams n_bytes of device memory once with the cascade kernel's load shape (one dword per lane,
  * 64 consecutive lanes) so that the FETCH_SIZE counter can be calibrated on a known byte count
  * (MI355X_MICROARCH.md, HBM section). *checksum receives the wrapped 32-bit sum of the words read. */
