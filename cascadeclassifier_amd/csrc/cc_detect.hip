@@ -193,7 +193,6 @@ struct cc_detector {
   DevBuf<float> d_leaves;
   size_t lds = 0;  // dynamic LDS bytes per tile (larger of the two layouts)
   size_t lds_spec = 0;  // the same for the installed specialised kernel (smaller when its STEP-2 tiles hold 16-bit entries)
-  size_t lds_extra = 0; // CCAMD_DEBUG_EXTRA_LDS (occupancy experiments)
   int spec_tile_y = TILE_Y;  // window rows per tile the installed specialised kernel was compiled for (spec_tile_rows)
   // plans + workspace
   std::vector<std::unique_ptr<Plan>> plans;
@@ -245,8 +244,8 @@ struct cc_detector {
   size_t h_stage_bytes = 0;    // kStageSlots equal slots of h_stage_bytes / kStageSlots bytes, whatever the frames' format
   long long graph_captures = 0;  // hipGraph captures made (cc_detector_graph_captures)
   int stage_slot = 0;          // staging slot the next pass of host frames takes (round-robin, also across calls)
-  int use_graph = 1;
-  int early_skip = 1, full_sqsum = 0, pipeline_passes = 4, pipeline_passes_set = 0, even_passes = 0;  // tuning knobs, read once at creation
+  int use_graph = 1;  // single-image calls replay a captured hipGraph; cleared when a capture fails
+  int early_skip = 1, pipeline_passes = 4, pipeline_passes_set = 0;  // tuning knobs, read once at creation
   hipStream_t copy_stream = nullptr;
   hipEvent_t pass_done[2] = {nullptr, nullptr};
   int cand_cap = 0;
@@ -471,18 +470,10 @@ static bool same_params(const cc_detect_params& a, const cc_detect_params& b) {
 // one XCD receives are neighbours in the image and share their halo rows/columns in that XCD's L2. Placement only changes
 // speed, never results.
 static int tile_list_key(int tile_y, int only_step) { return tile_y * 4 + only_step; }  // Plan::other_tiles
-static int debug_only_step() {  // timing experiments (CCAMD_DEBUG_ONLY_STEP=1|2): only the tiles of STEP-1 / STEP-2 scales are evaluated
-  static const int v = []() {
-    const char* e = std::getenv("CCAMD_DEBUG_ONLY_STEP");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
 static std::vector<int4> plan_tile_list(const std::vector<ScaleGeom>& geom, int tile_y, int only_step = 0) {
   std::vector<int4> tiles;
   for (size_t i = 0; i < geom.size(); i++) {
     const ScaleGeom& g = geom[i];
-    if (debug_only_step() && g.ystep != debug_only_step()) continue;
     if (only_step && g.ystep != only_step) continue;
     const int ntx = (g.nx + TILE_X - 1) / TILE_X, nty = (g.ny + tile_y - 1) / tile_y;
     for (int ty_ = 0; ty_ < nty; ty_++)
@@ -603,7 +594,7 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
   CC_HIP(hipMemsetAsync(d->d_counts[slot].p, 0, 2 * sizeof(int), st));
   if (ns == 0 || nf == 0) return CC_OK;
   // even window sizes: the variance rectangle's corners of step-2 scales sit on odd rows and odd columns only
-  const int sq_compact = (haar && d->m.win_w % 2 == 0 && d->m.win_h % 2 == 0 && !d->full_sqsum) ? 1 : 0;
+  const int sq_compact = (haar && d->m.win_w % 2 == 0 && d->m.win_h % 2 == 0) ? 1 : 0;
   CC_HIP(d->d_pyr.ensure(FL.pyr_frame_bytes * (size_t)d->pass_capacity));
   CC_HIP(d->d_integ[slot].ensure(FL.int_frame_elems * (size_t)nchan * (size_t)d->pass_capacity));
   CC_HIP(d->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)nchan * (size_t)d->pass_capacity, 4)));
@@ -927,7 +918,6 @@ static cc_status stage_host_frames(cc_detector* d, const uint8_t* src, int nf, i
     }
   };
   static const int want_threads = []() {
-    if (const char* e = std::getenv("CCAMD_STAGE_THREADS")) return std::max(1, std::atoi(e));
     const unsigned hc = std::thread::hardware_concurrency();
     return (int)std::max(1u, std::min(8u, hc / 2));  // 64 Full-HD frames per step: 2 threads 18.2, 4 17.9, 8 17.85 ms (resident frames 17.44)
   }();
@@ -997,14 +987,11 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     {  // the pyramid / integral stream only fills what the cascade kernel leaves idle: lowest priority
       int least = 0, greatest = 0;
       (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-      if (std::getenv("CCAMD_FRONT_SAME_PRIORITY")) least = greatest;
       CC_HIP(hipStreamCreateWithPriority(&d->front_stream, hipStreamNonBlocking, least));
     }
     for (hipEvent_t* e : {&d->front_done[0], &d->front_done[1], &d->eval_done[0], &d->eval_done[1], &d->batch_begin})
       CC_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     d->overlap_front = std::getenv("CCAMD_NO_FRONT_OVERLAP") ? 0 : 1;
-    d->use_graph = std::getenv("CCAMD_NO_GRAPH") ? 0 : 1;
-
   }
   hipStream_t front = d->overlap_front ? d->front_stream : d->stream;
   // Frames produced by earlier work on a stream the CALLER gave us (cc_detector_set_stream) must be complete before the
@@ -1133,26 +1120,16 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
   if (want_results && n_frames >= 2) {
     const bool submitted = defer_last && !d->pipeline_passes_set;
     const int passes = std::min(submitted ? 2 : d->pipeline_passes, n_frames);
-    const char* explicit_sizes = std::getenv("CCAMD_PASS_SIZES");  // tuning: comma-separated sizes
-    if (explicit_sizes && *explicit_sizes) {
-      for (const char* q = explicit_sizes; *q;) {
-        const int v = std::atoi(q);
-        if (v > 0) sizes.push_back(v);
-        while (*q && *q != ',') q++;
-        if (*q == ',') q++;
-      }
-    } else {
-      int per = (n_frames + passes - 1) / passes;
-      if (passes >= 3 && !d->even_passes && !submitted) {
-        const int big = (2 * n_frames + 2 * passes - 2) / (2 * passes - 1);
-        if (big >= 2 && big * (passes - 1) < n_frames) per = big;
-      }
-      for (int f = 0; f < n_frames; f += per) sizes.push_back(std::min(per, n_frames - f));
+    int per = (n_frames + passes - 1) / passes;
+    if (passes >= 3 && !submitted) {
+      const int big = (2 * n_frames + 2 * passes - 2) / (2 * passes - 1);
+      if (big >= 2 && big * (passes - 1) < n_frames) per = big;
     }
+    for (int f = 0; f < n_frames; f += per) sizes.push_back(std::min(per, n_frames - f));
   } else {
     for (int f = 0; f < n_frames; f += d->max_batch) sizes.push_back(std::min(d->max_batch, n_frames - f));
   }
-  {  // normalise: sizes within max_batch, summing to n_frames
+  {  // normalise: sizes within max_batch, summing to n_frames (a batch of more than passes * max_batch frames is cut further)
     std::vector<int> fixed;
     int left = n_frames;
     for (size_t i = 0; left > 0; i++) {
@@ -1361,18 +1338,17 @@ static cc_status spec_install(cc_detector* d, const std::vector<SpecCode>& codes
       return set_error(CC_ERR_HIP, "cc_detector_specialize: the compiled module does not load or has no entry point");
     }
     const int ty = c.tile_y;
-    // tiles this module stages: of the step(s) it covers (CCAMD_DEBUG_ONLY_STEP narrows a single module's request for timing runs)
-    const int step = c.only_step ? c.only_step : debug_only_step();
+    const int step = c.only_step;  // tiles this module stages: of the step(s) it covers
     x.lds = d->lds;
     if (tmode == TILE_32) {
       const TileGeom<1> G1(d->m.win_w, d->m.win_h, ty);
       const TileGeom<2> G2(d->m.win_w, d->m.win_h, ty);
       const int words = step == 1 ? G1.words() : step == 2 ? G2.words() : std::max(G1.words(), G2.words());
-      x.lds = eval_lds_bytes(words, d->m.has_tilted, haar_k, ty) + d->lds_extra;
+      x.lds = eval_lds_bytes(words, d->m.has_tilted, haar_k, ty);
     } else if (tmode == TILE_16) {  // STEP-1 tile in 32 bits, STEP-2 tile in 16 bits
       const TileGeom<1> G1(d->m.win_w, d->m.win_h, ty);
       const TileGeom16 G2(d->m.win_w, d->m.win_h, ty);
-      x.lds = eval_lds_bytes(std::max(G1.words(), G2.words()), false, haar_k, ty) + d->lds_extra;
+      x.lds = eval_lds_bytes(std::max(G1.words(), G2.words()), false, haar_k, ty);
     }
     if (x.lds > 64 * 1024) {  // same opt-in as the ahead-of-time kernels (cc_detector_create)
       const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(x.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds);
@@ -1575,19 +1551,11 @@ cc_status cc_detector_create(const cc_cascade* c, int device, int max_batch, cc_
   if (const char* e = std::getenv("CCAMD_SPLIT_STUMPS")) d->split_stumps = d->split_stumps && std::atoi(e) != 0;
   if (const char* e = std::getenv("CCAMD_DEBUG_STOP_AFTER_STAGE")) d->stop_after = std::atoi(e);  // timing experiments
   d->early_skip = std::getenv("CCAMD_NO_EARLY_SKIP") ? 0 : 1;
-  d->full_sqsum = std::getenv("CCAMD_FULL_SQSUM") ? 1 : 0;
   if (const char* e = std::getenv("CCAMD_PIPELINE_PASSES")) {
     d->pipeline_passes = std::max(1, std::atoi(e));
     d->pipeline_passes_set = 1;
   }
   if (const char* e = std::getenv("CCAMD_CAND_CAP")) d->cand_cap = std::max(16, std::atoi(e));  // initial candidate-list capacity (tests: forces the overflow path)
-  d->even_passes = std::getenv("CCAMD_EVEN_PASSES") ? 1 : 0;
-  if (const char* e = std::getenv("CCAMD_DEBUG_EXTRA_LDS")) {  // occupancy experiments: pad the per-block LDS request
-    d->lds_extra = (size_t)std::max(0, std::atoi(e));
-    d->lds += d->lds_extra;
-    if (d->lds > 64 * 1024)
-      CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(haar ? &k_eval_haar : &k_eval_lbp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->lds));
-  }
   if (const char* e = std::getenv("CCAMD_WAVE_BELOW"))  // tuning knob; only honoured where the wave phase is valid at all
     if (d->wave_below) d->wave_below = std::max(0, std::min(64, std::atoi(e)));  // the wave phase holds one window per lane
   CC_HIP(d->d_stage_thr.upload(d->m.stage_threshold, d->stream));
@@ -1608,9 +1576,9 @@ cc_status cc_detector_create(const cc_cascade* c, int device, int max_batch, cc_
     // <= 20 stumps from stage 2 on 4.91-5.06, 12 from stage 1: 5.04-5.25, one stage per group 5.29, 30 from stage 2: 5.36.
     // Round 4 (list queue from stage 2; specialised kernel on tiles of 20 rows): <= 14 stumps 3.70, <= 20 3.87, <= 30 4.17;
     // at 8 rows 4.84 / 4.87 / 5.13.
-    int budget = lbp ? 14 : 0, from = lbp ? 2 : 1;
+    int budget = lbp ? 14 : 0;
+    const int from = lbp ? 2 : 1;
     if (const char* e = std::getenv("CCAMD_GROUP_STUMPS")) budget = trees ? 0 : std::max(0, std::atoi(e));  // tuning
-    if (const char* e = std::getenv("CCAMD_GROUP_FROM")) from = std::max(1, std::atoi(e));
     std::vector<int> gf;
     const int nst = (int)d->m.stage_ntrees.size();
     for (int s0 = 0; s0 < nst;) {
@@ -1667,7 +1635,7 @@ cc_status cc_detector_create(const cc_cascade* c, int device, int max_batch, cc_
     if (!d->m.has_tilted) build_haar_gstumps(d->m, sg);
     CC_HIP(d->d_haar_g.upload(sg, d->stream));
     CC_HIP(hipStreamSynchronize(d->stream));
-    if (d->wave_below > 0 && !std::getenv("CCAMD_NO_WAVE_SCHEDULE")) {
+    if (d->wave_below > 0) {
       const std::vector<HaarStumpDev> w1 = schedule_for_wave_phase(d->m, s1), w2 = schedule_for_wave_phase(d->m, s2);
       CC_HIP(d->d_haar1w.upload(w1, d->stream));
       CC_HIP(d->d_haar2w.upload(w2, d->stream));

@@ -582,7 +582,6 @@ cc_status launch_batch(cc_evaluator* e, bool haar, const void* feats, int fb, in
   const int per_cu = e->S == 64 ? 1 : 2, rounds = 20;
   int chunks = (256 * per_cu * rounds + tiles - 1) / std::max(tiles, 1);
   chunks = std::max(1, std::min(chunks, (nfe + 2047) / 2048));
-  if (const char* v = std::getenv("CCAMD_EVAL_CHUNKS")) chunks = std::max(1, std::min(std::atoi(v), nfe));  // tuning
   A.feats_per_block = (nfe + chunks - 1) / chunks;
   chunks = (nfe + A.feats_per_block - 1) / A.feats_per_block;
   const size_t lds = (size_t)e->cols * e->S * 4 * (haar && e->use_tilted ? 2 : 1);
@@ -809,7 +808,7 @@ cc_status cc_eval_create(int feature_type, int haar_mode, int win_w, int win_h, 
   while (S > 1 && per_sample * S > budget) S >>= 1;
   if (per_sample * S > budget) return set_error(CC_ERR_UNSUPPORTED, "cc_eval_create: window %dx%d too large for the LDS tile", win_w, win_h);
   // the wide tile (64 samples, the whole 160 KB of a CU, k_eval_batch_wide) where it fits and no tilted tile is needed
-  if (!e->use_tilted && per_sample * 64 <= 160 * 1024 && !std::getenv("CCAMD_EVAL_NARROW_TILE")) S = 64;
+  if (!e->use_tilted && per_sample * 64 <= 160 * 1024) S = 64;
   e->S = S;
   if (per_sample * S > 64 * 1024) {
     CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eval_batch<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(per_sample * S)));

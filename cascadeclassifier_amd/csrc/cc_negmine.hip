@@ -597,7 +597,7 @@ static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n
     CC_HIP(m->d_tseg.ensure(std::max<size_t>(FL.tseg_frame_elems * K, 1)));
   }
   // one wavefront per window where the parallel stage sum is exact (stumps, order-independent sums); else one thread per window
-  const bool wave_mode = M.max_nodes_per_tree == 1 && stage_sums_order_independent(M) && !std::getenv("CCAMD_NEGMINE_THREAD_PER_WINDOW");
+  const bool wave_mode = M.max_nodes_per_tree == 1 && stage_sums_order_independent(M);
   // Every kernel over the images [k0, k0 + n): the front-end kernels and the window kernels take the image as blockIdx.y.
   auto launch_images = [&](int k0, int n) {
     FrontIO io;

@@ -11,7 +11,6 @@
 #include <cstring>
 #include <map>
 #include <mutex>
-#include <sstream>
 
 #include <dlfcn.h>
 #include <sys/stat.h>
@@ -47,11 +46,6 @@ struct SpecStump {
 static const char* spec_stage_inline_attr() {
   const char* e = std::getenv("CCAMD_SPEC_NOINLINE");
   return (e && std::atoi(e) != 0) ? "__noinline__" : "__forceinline__";
-}
-
-static int spec_prefetch_depth(int d = 2) {
-  if (const char* e = std::getenv("CCAMD_SPEC_PREFETCH")) d = std::max(0, std::min(4, std::atoi(e)));  // tuning
-  return d;
 }
 
 // Emits the body of one stage from per-stump pieces (see above). `suffixes` = one accumulator / window per entry.
@@ -164,14 +158,13 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
   build_haar_stumps<2>(m, t[1]);
   const TileGeom16 G16(m.win_w, m.win_h);
   n_stages = std::min<int>(n_stages, (int)m.stage_ntrees.size());
-  const int depth = spec_prefetch_depth();
+  const int depth = 2;  // stumps whose reads are issued ahead of the one being computed
   // Delta form of a vote: `(v < thr ? left : right)` needs both leaf values in registers (a select takes one literal), and
   // the compiler hoists those ~2 registers per stump out of the stage loop until it spills; `right + (v < thr ? left - right
   // : 0)` selects between ONE literal and zero, and the `right`s of a part add up to one constant. Exact -- hence equal to
   // the sequential sum of the votes -- when every partial sum of leaves and differences is representable
   // (stage_sums_order_independent with headroom for the differences); otherwise the plain form is generated.
-  const bool delta_form = stage_sums_order_independent(m, 4.0) && !std::getenv("CCAMD_SPEC_NO_DELTA");
-  const bool fixed_point_ok = !std::getenv("CCAMD_SPEC_NO_FIXED");  // tuning / bisecting
+  const bool delta_form = stage_sums_order_independent(m, 4.0);
   std::string o;
   char buf[512];
   auto hexf = [&](float v) {
@@ -325,40 +318,8 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
     }
     if (out.decls.empty()) out.decls = "";
     else out.decls += ";";
-    if (const char* dbg = std::getenv("CCAMD_DEBUG_SPEC_MODE")) {
-      // Sensitivity experiments (tools/sweeps): extra work whose results are thrown away, decisions unchanged.
-      // 3 = every LDS read issued twice; 4 = the value arithmetic done twice. Measured on the headline bench:
-      // mode 3 costs +68 % kernel time, mode 4 +1 %: the kernel is bound by the LDS pipeline, not by VALU issue.
-      const int mode = std::atoi(dbg);
-      if (mode == 3) {
-        std::string dup;
-        int k = 0;
-        for (auto& kv : var) {
-          snprintf(buf, sizeof(buf), "{ unsigned dz%d = (unsigned)%s[%d]; asm volatile(\"\" :: \"v\"(dz%d)); } ", k, tile_ptr.c_str(), kv.first ^ 1, k);
-          dup += buf;
-          k++;
-        }
-        out.compute = dup + " ";
-      } else if (mode == 4) {
-        // the same operations on operands XOR-ed with a value the compiler cannot see through (an added constant would
-        // cancel in a - b - c + d and the copy would be merged with the original)
-        std::string e2 = e;
-        for (auto& kv : var) {
-          size_t pos = 0;
-          const std::string from = kv.second, to = "(" + kv.second + " ^ __float_as_uint(vnf" + win + "))";
-          while ((pos = e2.find(from, pos)) != std::string::npos) {
-            const char next = pos + from.size() < e2.size() ? e2[pos + from.size()] : ' ';
-            if (next >= '0' && next <= '9') {
-              pos += from.size();
-              continue;
-            }
-            e2.replace(pos, from.size(), to);
-            pos += to.size();
-          }
-        }
-        out.compute = e2 + "; v *= vnf" + win + "; asm volatile(\"\" :: \"v\"(v)); } ";
-      }
-    }
+    // Sensitivity, measured on the headline bench with generated code that issued every LDS read twice (+68 % kernel time)
+    // or did the value arithmetic twice (+1 %): the kernel is bound by the LDS pipeline, not by VALU issue.
     out.compute += e + vote_text(d, win, fixed_q, out);
     if (vars_out) *vars_out = var;
     return out;
@@ -475,7 +436,7 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
       o += buf;
       std::vector<SpecStump> st;
       double q = 0.;
-      const bool fixed = delta_form && fixed_point_ok && stage_quantum(s, q);
+      const bool fixed = delta_form && stage_quantum(s, q);
       if (fixed && share_corners) {
         const int nt = m.stage_ntrees[(size_t)s];
         const std::vector<int> order = sharing_order(s, step);
@@ -515,7 +476,7 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
     {
       std::vector<SpecStump> st;
       double q = 0.;
-      const bool fixed = delta_form && fixed_point_ok && stage_quantum(0, q);
+      const bool fixed = delta_form && stage_quantum(0, q);
       for (int i = 0; i < m.stage_ntrees[0]; i++) {
         const HaarStumpDev& d = t[step - 1][(size_t)m.stage_first[0] + i];
         SpecStump a = stump(d, m.stage_first[0] + i, i, "a", fixed ? q : 0., h16), b2 = stump(d, m.stage_first[0] + i, i, "b", fixed ? q : 0., h16);
@@ -544,7 +505,7 @@ static std::string spec_stage_source_lbp(const Cascade& m, int n_stages, bool ti
   else
     build_lbp_stumps<2>(m, t[1]);
   n_stages = std::min<int>(n_stages, (int)m.stage_ntrees.size());
-  const int depth = std::min(spec_prefetch_depth(0), 2);  // 16 independent words per stump already: no explicit pipelining measured best (7.8 ms per 32 frames; one stump ahead 8.2, two 8.9)
+  const int depth = 0;  // 16 independent words per stump already: no explicit pipelining measured best (7.8 ms per 32 frames; one stump ahead 8.2, two 8.9)
   std::string o;
   char buf[1024];
   auto hexf = [&](float v) {
@@ -598,41 +559,6 @@ static std::string spec_stage_source_lbp(const Cascade& m, int n_stages, bool ti
              (unsigned)w[1], (unsigned)w[0], (unsigned)w[3], (unsigned)w[2], (unsigned)w[5], (unsigned)w[4], (unsigned)w[7], (unsigned)w[6],
              win.c_str(), hexf(d.left).c_str(), hexf(d.right).c_str());
     out.compute = t + buf;
-    if (const char* dbg = std::getenv("CCAMD_DEBUG_SPEC_MODE")) {
-      // Sensitivity experiments (as for Haar above): 3 = every corner read issued twice, 4 = the stump's arithmetic done
-      // twice on operands XOR-ed with a value the compiler cannot fold; results thrown away, decisions unchanged.
-      const int mode = std::atoi(dbg);
-      if (mode == 3) {
-        std::string dup;
-        for (int k = 0; k < 16; k++) {
-          snprintf(buf, sizeof(buf), "{ unsigned dz%d = (unsigned)%s%s[%d]; asm volatile(\"\" :: \"v\"(dz%d)); } ", k, h16 ? "h" : "b", win.c_str(), d.ofs[k] ^ 1, k);
-          dup += buf;
-        }
-        out.compute = dup + out.compute;
-      } else if (mode == 4) {
-        std::string dup = "{ const int zz = (int)__float_as_uint(vnf" + win + ") ^ 0x3f800001; double accd = 0.; int ";
-        for (int k = 0; k < 16; k++) dup += std::string(k ? ", " : "") + "d" + P[k] + " = " + P[k] + " ^ zz";
-        dup += "; ";
-        std::string body = out.compute;
-        for (int k = 15; k >= 0; k--) {  // p<local>_<k><win> -> dp...; longest names first so that p0_1 does not hit p0_10
-          size_t pos = 0;
-          while ((pos = body.find(P[k], pos)) != std::string::npos) {
-            const char next = pos + P[k].size() < body.size() ? body[pos + P[k].size()] : ' ';
-            const bool whole = !(next >= '0' && next <= '9') && (pos == 0 || body[pos - 1] != 'd');
-            if (whole) {
-              body.insert(pos, "d");
-              pos += P[k].size() + 1;
-            } else
-              pos += P[k].size();
-          }
-        }
-        const std::string accname = "acc" + win + " +=";
-        const size_t ap = body.find(accname);
-        if (ap != std::string::npos) body.replace(ap, accname.size(), "accd +=");
-        dup += body + " asm volatile(\"\" :: \"v\"(accd)); } ";
-        out.compute = dup + out.compute;
-      }
-    }
     return out;
   };
   for (int step = 1; step <= 2; step++) {
@@ -668,7 +594,7 @@ static std::string spec_stage_source_lbp(const Cascade& m, int n_stages, bool ti
         SpecStump a = stump(t[step - 1][(size_t)idx], i, "a", h16), b2 = stump(t[step - 1][(size_t)idx], i, "b", h16);
         st.push_back(SpecStump{a.loads + b2.loads, a.decls + " " + b2.decls, a.compute + " " + b2.compute});
       }
-      spec_emit_stage(o, st, std::min(depth, 1), false, {"acca", "accb"});
+      spec_emit_stage(o, st, depth, false, {"acca", "accb"});
     }
     o += "  }\n  acc_a = acca;\n  acc_b = accb;\n}\n";
   }
@@ -724,12 +650,12 @@ static const char kSpecPrelude[] =
 //   threads). A tile's halo rows are staged per 20 instead of per 8 window rows, the per-block work (barrier rounds,
 //   counters, the wave phase's window collection) is paid once per 1 280 windows, and the late stages find 2.5 x the windows per
 //   block to fill their wavefronts with; at 26 KB per block six blocks fit a CU (6 wavefronts per SIMD: 80 VGPRs).
-//   Stock LBP cascade, ms per 32 Full-HD frames alone (tools/r4_g.sh): 8 rows 4.90, 12 rows 4.25, 16 rows 3.96, 20 rows 3.78,
+//   Stock LBP cascade, ms per 32 Full-HD frames alone (round-4 run, script not kept): 8 rows 4.90, 12 rows 4.25, 16 rows 3.96, 20 rows 3.78,
 //   24 rows 3.85, 32 rows 4.12 (each at its best register budget).
 // * Haar kernels with 32-bit tiles: TWO modules, one per step -- 12 rows for the STEP-1 tiles, 8 for the STEP-2 tiles. A
 //   STEP-1 tile is a third of a STEP-2 tile (12.7 KB against 24 KB), but one launch requests the larger of the two for every
 //   block; in a launch of their own the STEP-1 tiles run at 6 blocks per CU. ms per 32 Full-HD frames alone, one run
-//   (tools/r4_h.sh): one module at 8 rows 8.35; two modules at 8 / 8 rows 7.82, 12 / 8 rows 7.32, 12 / 12 rows 7.49,
+//   (round-4 run, script not kept): one module at 8 rows 8.35; two modules at 8 / 8 rows 7.82, 12 / 8 rows 7.32, 12 / 12 rows 7.49,
 //   16 / 12 rows 7.77, 12 / 16 rows 8.11 (STEP-1 / STEP-2; a 32-bit STEP-2 tile of 12 rows leaves 4 blocks per CU).
 // * everything else (Haar with 16-bit tiles): one module at the library's 8 rows.
 // CCAMD_SPEC_TILE_Y sets every module's rows, CCAMD_SPEC_TILE_Y1 / _Y2 the STEP-1 / STEP-2 module's, CCAMD_SPEC_ONE_MODULE=1
@@ -765,20 +691,13 @@ static cc_status compile_specialised(const std::string& src, const std::string& 
   // same code generation rules as the ahead-of-time build (Makefile): no FMA contraction, no fast-math
   // register budget = the occupancy the LDS footprint allows: 5 blocks per CU with the 32-bit tile, 7-8 with the 16-bit one
   // (16-bit tiles of >= 20 rows: 26 KB per block = 6 blocks per CU)
-  std::string o_w = "-DCC_EVAL_MIN_WAVES_PER_EU=" + std::to_string(tile16 ? (tile_y >= 20 ? 6 : 7) : CC_EVAL_MIN_WAVES_PER_EU);
+  const std::string o_w = "-DCC_EVAL_MIN_WAVES_PER_EU=" + std::to_string(tile16 ? (tile_y >= 20 ? 6 : 7) : CC_EVAL_MIN_WAVES_PER_EU);
   const std::string o_step = "-DCC_ONLY_STEP=" + std::to_string(only_step);
-  if (const char* e = std::getenv("CCAMD_SPEC_WAVES_PER_EU")) o_w = "-DCC_EVAL_MIN_WAVES_PER_EU=" + std::to_string(std::max(1, std::min(8, std::atoi(e))));  // tuning
   const std::string o_w0 = "-DCC_SPEC_W0=" + std::to_string(win_w), o_h0 = "-DCC_SPEC_H0=" + std::to_string(win_h);  // tile geometry folds to constants
   std::vector<const char*> optv = {o_arch.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", o_k.c_str(), o_ty.c_str(), o_th.c_str(), o_w.c_str(), o_w0.c_str(), o_h0.c_str()};
   if (only_step) optv.push_back(o_step.c_str());
   if (lbp) optv.push_back("-DCC_SPEC_LBP");
   if (tile16) optv.push_back("-DCC_SPEC_TILE16");
-  std::vector<std::string> extra;  // tuning: further compiler options, space-separated
-  if (const char* e = std::getenv("CCAMD_SPEC_EXTRA_FLAGS")) {
-    std::istringstream is(e);
-    for (std::string w; is >> w;) extra.push_back(w);
-  }
-  for (const std::string& w : extra) optv.push_back(w.c_str());
   const char* const* opts = optv.data();
   const int n_opts = (int)optv.size();
   std::string key;  // everything the code object depends on: compiler version, options, then the source
@@ -907,8 +826,7 @@ cc_status spec_build(const Cascade& m, int n_stages, const std::string& arch, st
   if (cc_status hs = refuse_hog(m, "cc_detector_specialize"); hs != CC_OK) return hs;
   if (m.max_nodes_per_tree > 1) return set_error(CC_ERR_UNSUPPORTED, "cc_detector_specialize: stump cascades only");
   int k = 0, stumps = 0;
-  int budget = 320;  // instruction cache: more stages measured no faster, 12 stages slower
-  if (const char* e = std::getenv("CCAMD_SPEC_BUDGET")) budget = std::max(1, std::atoi(e));  // tuning
+  const int budget = 320;  // instruction cache: more stages measured no faster, 12 stages slower
   while (k < (int)m.stage_ntrees.size() && k < n_stages && k < MAX_STAGES && (k == 0 || stumps + m.stage_ntrees[(size_t)k] <= budget))
     stumps += m.stage_ntrees[(size_t)k++];
   std::string src = kSpecPrelude;

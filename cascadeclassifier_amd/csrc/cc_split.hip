@@ -120,10 +120,7 @@ static hipError_t launch_sort_rows_block(const float* vals, int rows, int n, flo
   return hipGetLastError();
 }
 
-int sort_rows_block_limit() {
-  static const bool device_sort_only = std::getenv("CCAMD_PRESORT_DEVICE_SORT") != nullptr;  // A/B: the device-wide sort for every size
-  return device_sort_only ? 0 : SORT_THREADS * 24;
-}
+int sort_rows_block_limit() { return SORT_THREADS * 24; }
 hipError_t sort_rows_block(const float* vals, int rows, int n, float* keys_out, int* idx_out, hipStream_t st) {
   if (n <= SORT_THREADS * 4) return launch_sort_rows_block<4>(vals, rows, n, keys_out, idx_out, st);
   if (n <= SORT_THREADS * 8) return launch_sort_rows_block<8>(vals, rows, n, keys_out, idx_out, st);
@@ -924,20 +921,19 @@ cc_status cc_eval_find_best_split(cc_evaluator* e, const int32_t* sample_idx, in
     A.dbg_nogather = std::getenv("CCAMD_DEBUG_SPLIT_NOGATHER") ? 1 : 0;
     // wavefronts per block: with the table in LDS one block owns a CU, so spread the groups evenly over the CUs
     // (162 336 variables = 2 537 groups -> 254 blocks of 10 wavefronts on 256 CUs); from global memory, one wavefront
-    // k_split_ord_lean for the regression / GINI searches (Gentle 6.77 against 7.01 ms, GINI 8.91 against 9.31 at configs[4]);
+    // per block. k_split_ord_lean for the regression / GINI searches (Gentle 6.77 against 7.01 ms, GINI 8.91 against 9.31 at configs[4]);
     // the MISCLASS search has no division and nothing to hoist: the round-1 kernel stays (4.46 against 4.76 ms).
-    // CCAMD_SPLIT_BRANCHY=1: the round-1 kernel everywhere (A/B runs).
-    static const bool lean = std::getenv("CCAMD_SPLIT_BRANCHY") == nullptr;
     int wpb = 1;
     if (tab_kind != 0) {
       const int cus = device_cus(e->device);
       wpb = (int)std::min<size_t>(16, std::max<size_t>(1, (groups + cus - 1) / cus));
-      if (const char* v = std::getenv("CCAMD_SPLIT_WAVES")) wpb = std::max(1, std::min(16, std::atoi(v)));
-      if (tab_kind == 2 && lean && mode != 2) wpb = std::min(wpb, SPLIT_LEAN_WAVES);
+      if (tab_kind == 2 && mode != 2) wpb = std::min(wpb, SPLIT_LEAN_WAVES);
     }
     const unsigned blocks = (unsigned)((groups + wpb - 1) / wpb);
     const size_t lds = tab_kind == 0 ? 0 : (size_t)N * entry_bytes;
     (void)hipEventRecord(e->ev_a, e->stream);
+    // TAB8 is the launch for the 8-byte table. The macros name k_split_ord_lean for modes 0 and 1 only and
+    // k_split_ord<M, TI, 2> for mode 2 only, so the code object holds no instantiation that is never launched.
 #define CC_LAUNCH_ORD3(M, TI, T)                                                                                              \
   do {                                                                                                                        \
     if (lds > 64 * 1024)                                                                                                      \
@@ -950,31 +946,31 @@ cc_status cc_eval_find_best_split(cc_evaluator* e, const int32_t* sample_idx, in
       CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_split_ord_lean<M, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
     hipLaunchKernelGGL((k_split_ord_lean<M, TI>), dim3(blocks), dim3(64 * wpb), lds, e->stream, A);                           \
   } while (0)
-#define CC_LAUNCH_ORD2(M, TI)          \
+#define CC_LAUNCH_ORD3_TAB8(M, TI) CC_LAUNCH_ORD3(M, TI, 2)
+#define CC_LAUNCH_ORD2(M, TI, TAB8)    \
   do {                                 \
     if (tab_kind == 0)                 \
       CC_LAUNCH_ORD3(M, TI, 0);        \
     else if (tab_kind == 1)            \
       CC_LAUNCH_ORD3(M, TI, 1);        \
-    else if (lean && M != 2)           \
-      CC_LAUNCH_LEAN(M, TI);           \
     else                               \
-      CC_LAUNCH_ORD3(M, TI, 2);        \
+      TAB8(M, TI);                     \
   } while (0)
-#define CC_LAUNCH_ORD(M)               \
-  do {                                 \
-    if (idx16)                         \
-      CC_LAUNCH_ORD2(M, uint16_t);     \
-    else                               \
-      CC_LAUNCH_ORD2(M, int32_t);      \
+#define CC_LAUNCH_ORD(M, TAB8)           \
+  do {                                   \
+    if (idx16)                           \
+      CC_LAUNCH_ORD2(M, uint16_t, TAB8); \
+    else                                 \
+      CC_LAUNCH_ORD2(M, int32_t, TAB8);  \
   } while (0)
     if (mode == 0)
-      CC_LAUNCH_ORD(0);
+      CC_LAUNCH_ORD(0, CC_LAUNCH_LEAN);
     else if (mode == 1)
-      CC_LAUNCH_ORD(1);
+      CC_LAUNCH_ORD(1, CC_LAUNCH_LEAN);
     else
-      CC_LAUNCH_ORD(2);
+      CC_LAUNCH_ORD(2, CC_LAUNCH_ORD3_TAB8);
 #undef CC_LAUNCH_ORD
+#undef CC_LAUNCH_ORD3_TAB8
 #undef CC_LAUNCH_LEAN
 #undef CC_LAUNCH_ORD2
 #undef CC_LAUNCH_ORD3
