@@ -31,18 +31,19 @@ def haar_xml(feats, stages, mode="ALL", W=24, H=24):
     return "\n".join(L) + "\n"
 
 
-def calibration_values(feats, windows):
-    """Normalised feature values (training-side evaluator of the oracle) of `feats` on 24x24 `windows`."""
+def calibration_values(feats, windows, W=24, H=24):
+    """Normalised feature values (training-side evaluator of the oracle) of `feats` on W x H `windows`."""
+    assert windows.shape[1:] == (H, W), "calibration windows are cut at the cascade's own size"
     s, t, nf = orc.set_images(windows, want_tilted=bool(feats["tilted"].any()))
     ok = nf > 0
-    return orc.haar_eval_batch(feats, 0, len(feats), s, t, nf, 24, 24)[:, ok]
+    return orc.haar_eval_batch(feats, 0, len(feats), s, t, nf, W, H)[:, ok]
 
 
-def tilted_stump_cascade(windows, seed=11, stage_sizes=(6, 10, 14, 20), tilted=True, min_area=16):
-    """Stump cascade whose features are drawn from the ALL catalog with every second one tilted (tilted=False: upright
-    features only, from rectangles of at least min_area pixels)."""
+def tilted_stump_cascade(windows, seed=11, stage_sizes=(6, 10, 14, 20), tilted=True, min_area=16, W=24, H=24):
+    """Stump cascade of a W x H window whose features are drawn from the ALL catalog with every second one tilted
+    (tilted=False: upright features only, from rectangles of at least min_area pixels)."""
     rng = np.random.default_rng(seed)
-    cat = orc.haar_catalog(24, 24, 2)
+    cat = orc.haar_catalog(W, H, 2)
     ui = np.nonzero((cat["tilted"] == 0) & (cat["r"][:, 0, 2] * cat["r"][:, 0, 3] >= min_area))[0]
     ti = np.nonzero(cat["tilted"] == 1)[0] if tilted else ui
     n = sum(stage_sizes)
@@ -50,7 +51,7 @@ def tilted_stump_cascade(windows, seed=11, stage_sizes=(6, 10, 14, 20), tilted=T
     idx[0::2] = rng.choice(ti, len(idx[0::2]), replace=False)
     idx[1::2] = rng.choice(ui, len(idx[1::2]), replace=False)
     feats = cat[idx].copy()
-    v = calibration_values(feats, windows)
+    v = calibration_values(feats, windows, W, H)
     thr = np.median(v, axis=1).astype(np.float32)
     a = rng.uniform(0.25, 1.0, n).astype(np.float32)
     sign = rng.choice([-1.0, 1.0], n).astype(np.float32)
@@ -64,7 +65,7 @@ def tilted_stump_cascade(windows, seed=11, stage_sizes=(6, 10, 14, 20), tilted=T
         weaks = [([(0, -1, k + i, thr[k + i])], [a[k + i] * sign[k + i], -a[k + i] * sign[k + i]]) for i in range(nw)]
         stages.append((st, weaks))
         k += nw
-    return haar_xml(feats, stages, mode="ALL" if tilted else "BASIC")
+    return haar_xml(feats, stages, mode="ALL" if tilted else "BASIC", W=W, H=H)
 
 
 def lbp_xml(rects, stages, W=24, H=24):
@@ -98,14 +99,14 @@ _SHAPES = [
 ]
 
 
-def haar_tree_cascade(windows, seed=21, stage_sizes=(4, 6, 8), with_tilted=False):
+def haar_tree_cascade(windows, seed=21, stage_sizes=(4, 6, 8), with_tilted=False, W=24, H=24):
     rng = np.random.default_rng(seed)
-    cat = orc.haar_catalog(24, 24, 2 if with_tilted else 0)
+    cat = orc.haar_catalog(W, H, 2 if with_tilted else 0)
     pool = np.nonzero(cat["r"][:, 0, 2] * cat["r"][:, 0, 3] >= 16)[0]
     shapes = [_SHAPES[int(rng.integers(0, len(_SHAPES)))] for _ in range(sum(stage_sizes))]
     n_nodes = sum(len(sh) for sh in shapes)
     feats = cat[rng.choice(pool, n_nodes, replace=False)].copy()
-    med = np.median(calibration_values(feats, windows), axis=1).astype(np.float32)
+    med = np.median(calibration_values(feats, windows, W, H), axis=1).astype(np.float32)
     stages, t, fi = [], 0, 0
     for nw in stage_sizes:
         weaks = []
@@ -117,7 +118,7 @@ def haar_tree_cascade(windows, seed=21, stage_sizes=(4, 6, 8), with_tilted=False
             fi += len(sh)
             t += 1
         stages.append((np.float32(-0.15 * nw), weaks))
-    return haar_xml(feats, stages, mode="ALL" if with_tilted else "BASIC")
+    return haar_xml(feats, stages, mode="ALL" if with_tilted else "BASIC", W=W, H=H)
 
 
 def lbp_tree_cascade(seed=31, stage_sizes=(3, 4, 5, 6)):
