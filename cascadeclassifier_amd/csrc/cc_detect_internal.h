@@ -25,7 +25,7 @@ __device__ __forceinline__ int find_segment(const int* __restrict__ first, int n
 inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // ------------------------------------------------------------------------------------------------
-// Front end: pyramid (k_resize), integral images (k_integral_band, k_integral_carry) and tilted integral (k_diag_sums,
+// Front end: pyramid (k_resize), integral images (k_integral_carry, k_integral_band) and tilted integral (k_diag_sums,
 // k_tilted_cols) of every level of nf frames. The detector, the negative miner and the building-block entry points all
 // lay it out with front_layout, upload it with FrontTables::upload and launch it with launch_front.
 // ------------------------------------------------------------------------------------------------
@@ -67,11 +67,16 @@ enum { FRONT_RESIZE = 1, FRONT_INTEGRALS = 2 };  // launch_front parts
 
 // Caller-owned buffers of launch_front, frame f of each at f times its per-frame size.
 struct FrontIO {
-  const uint8_t* src = nullptr;  // FRONT_RESIZE: the source frames, src_w x src_h
+  // FRONT_RESIZE: the source frames, src_w x src_h. FRONT_INTEGRALS: set = FRONT_RESIZE ran with this very FrontIO (in
+  // this call or the one before it on the stream) and left the band column sums in hbuf; null = the caller filled pyr
+  // itself and launch_front adds them up first (k_band_colsums).
+  const uint8_t* src = nullptr;
   size_t row_stride = 0, frame_stride = 0;
   uint8_t* pyr = nullptr;      // L.pyr_frame_bytes per frame: the levels (FRONT_INTEGRALS alone: filled by the caller)
   int32_t* integ = nullptr;    // nchan x L.int_frame_elems per frame: channel 0 sum, 1 sqsum (sq), tilt_chan tilted (tilted layouts)
-  int32_t* hbuf = nullptr;     // nchan x L.h_frame_elems per frame: band totals
+  // nchan x L.h_frame_elems per frame, [band][pitchI] per level: the bands' column sums (sum, and sum of squares when sq),
+  // written by FRONT_RESIZE when set, scanned down the bands in place by FRONT_INTEGRALS. Null: FRONT_RESIZE alone.
+  int32_t* hbuf = nullptr;
   int32_t* diag = nullptr;     // tilted: 2 x L.int_frame_elems per frame, diagonal sums
   int32_t* tseg = nullptr;     // tilted: L.tseg_frame_elems per frame, segment totals
   int nchan = 1, tilt_chan = 2;

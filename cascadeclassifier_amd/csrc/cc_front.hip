@@ -1,5 +1,5 @@
 // Front end of detection and negative mining on gfx950: scale pyramid (bit-exact fixed-point bilinear, k_resize), integral
-// images (sum + wrap-around sqsum, k_integral_band / k_integral_carry) and the tilted integral (k_diag_sums, k_tilted_cols)
+// images (sum + wrap-around sqsum, k_integral_carry / k_integral_band) and the tilted integral (k_diag_sums, k_tilted_cols)
 // of every level of a batch of frames. front_layout lays the levels out, FrontTables::upload puts the tables on the device
 // and launch_front queues the kernels (cc_detect_internal.h). Also the building-block entry points cc_resize_linear_exact_u8
 // and cc_integral_u8, which run the same kernels on one image.
@@ -46,7 +46,8 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ fram
                                                 const ScaleDev* __restrict__ sd, int nscales,
                                                 const int* __restrict__ blk_first, const int* __restrict__ xofs,
                                                 const uint16_t* __restrict__ xw1, const int* __restrict__ yofs,
-                                                const uint16_t* __restrict__ yw1) {
+                                                const uint16_t* __restrict__ yw1, int32_t* __restrict__ hbuf, size_t h_frame_elems,
+                                                int nchan, int sq) {
   const int s = find_segment(blk_first, nscales, blockIdx.x);
   const ScaleDev S = sd[s];
   const int wpr = S.pitch8 >> 2, nxb = (wpr + 63) >> 6;
@@ -100,6 +101,7 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ fram
   };
   unsigned hc[4] = {0, 0, 0, 0};
   int cached = -1;  // source row whose interpolation hc holds
+  unsigned cs[4] = {0, 0, 0, 0}, cq[4] = {0, 0, 0, 0};  // the band's column sums of the pixels and of their squares
   uint8_t* dst = pyr + (size_t)blockIdx.y * pyr_frame_bytes + S.img_ofs;
   const int yb = min(ya + RESIZE_ROWS, S.h);
   for (int y = ya; y < yb; y++) {
@@ -120,26 +122,46 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ fram
     unsigned packed = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      const unsigned v = (h0[k] * wy0 + h1[k] * wy1 + (1u << 15)) >> 16;
-      if (xw * 4 + k < S.w) packed |= v << (8 * k);
+      const unsigned v = (xw * 4 + k < S.w) ? (h0[k] * wy0 + h1[k] * wy1 + (1u << 15)) >> 16 : 0u;
+      packed |= v << (8 * k);
+      cs[k] += v;
+      cq[k] += v * v;
       hc[k] = h1[k];
     }
     cached = y1;
     reinterpret_cast<unsigned*>(dst + (size_t)y * S.pitch8)[xw] = packed;
   }
+  if (!hbuf) return;
+  // Band totals for the integral kernels (K2): a resize band is an integral band, so this thread holds all of H[band]'s
+  // pixels of its 4 columns. The padding columns up to pitchI are written as 0: the quad behind the last pixel word exists
+  // in pitchI but not in pitch8 when w is a multiple of 4 and has no thread of its own.
+  const size_t hofs = S.h_ofs + (size_t)band * S.pitchI + (size_t)xw * 4;
+  const bool pad_quad = xw == wpr - 1 && S.pitchI > S.pitch8;
+  int32_t* hs = hbuf + ((size_t)blockIdx.y * nchan + 0) * h_frame_elems + hofs;
+  *reinterpret_cast<int4*>(hs) = make_int4((int)cs[0], (int)cs[1], (int)cs[2], (int)cs[3]);
+  if (pad_quad) *reinterpret_cast<int4*>(hs + 4) = make_int4(0, 0, 0, 0);
+  if (sq) {
+    int32_t* hq = hbuf + ((size_t)blockIdx.y * nchan + 1) * h_frame_elems + hofs;
+    *reinterpret_cast<int4*>(hq) = make_int4((int)cq[0], (int)cq[1], (int)cq[2], (int)cq[3]);
+    if (pad_quad) *reinterpret_cast<int4*>(hq + 4) = make_int4(0, 0, 0, 0);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
-// K2: integral images in one pass over the pixels (plus a tiny carry pass), ~10.5 B/px instead of 25 B/px for a
-// row pass + column pass. The image is cut into bands of INT_BAND rows; one wavefront owns one band of one scale and
-// walks it left to right in chunks of 256 columns (64 lanes x 4 px): per row an in-register prefix of the lane's 4 px,
-// a DPP wave scan of the lane totals and a carry into the next chunk; rows accumulate downwards in registers.
-//   k_integral_band<.., false>: only the band's column totals H[b][x] (its local integral's last row) are written;
+// K2: integral images in one pass over the pixels (plus a tiny carry pass). The image is cut into bands of INT_BAND rows;
+// H[b][x] = the sum of band b's rows at pixel column x (its column sums), per channel:
+//   k_resize / k_band_colsums : write H[b][x] -- the pyramid kernel has a band's pixels in registers (RESIZE_ROWS ==
+//                               INT_BAND); callers that bring their own level (cc_integral_u8) run k_band_colsums on it;
 //   k_integral_carry          : H[b][x] <- sum of H over the bands above b (exclusive scan down the bands, in place);
-//   k_integral_band<.., true> : recomputes the band-local integral and writes row + H[b][x] (the finished integral).
+//   k_integral_band           : one wavefront owns one band of one scale and walks it left to right in chunks of 256 columns
+//                               (64 lanes x 4 px): per row an in-register prefix of the lane's 4 px, a DPP wave scan of the
+//                               lane totals and a carry into the next chunk; rows accumulate downwards in registers,
+//                               starting from the same prefix of H[b] (the rows above the band: prefix along x and sum down
+//                               the bands commute), and every row is written as the finished integral.
 // sum and sqsum use u32 wrap-around arithmetic throughout (the detector's CV_32S squared sums).
 // ------------------------------------------------------------------------------------------------
 constexpr int INT_BAND = 8;
+static_assert(RESIZE_ROWS == INT_BAND, "k_resize writes the column sums of the integral kernels' bands");
 
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ unsigned dpp_u32(unsigned v) {
@@ -155,11 +177,22 @@ __device__ __forceinline__ unsigned wave_scan_u32(unsigned v) {
   v += dpp_u32<0x143, 0xC>(v);
   return v;
 }
+// One row of a chunk: p = the lane's 4 entries, carry = the row's total over the chunks to the left (updated). Returns
+// the 4 integral entries of the lane's columns: column c holds the sum of the entries < c, {prev lane's last, P0, P1, P2}.
+__device__ __forceinline__ uint4 row_prefix_u32(const unsigned (&p)[4], unsigned& carry, int lane) {
+  const unsigned a0 = p[0], a1 = a0 + p[1], a2 = a1 + p[2], a3 = a2 + p[3];
+  const unsigned base = carry + wave_scan_u32(a3) - a3;
+  const unsigned last = base + a3;
+  unsigned prev = dpp_u32<0x138, 0xF>(last);  // wave_shr:1: value of the previous lane
+  if (lane == 0) prev = carry;
+  carry = (unsigned)__builtin_amdgcn_readlane((int)last, 63);
+  return make_uint4(prev, base + a0, base + a1, base + a2);
+}
 
-template <bool SQ, bool FINAL>
+template <bool SQ>
 __global__ __launch_bounds__(256) void k_integral_band(const uint8_t* __restrict__ pyr, size_t pyr_frame_bytes,
                                                        int32_t* __restrict__ integ, size_t int_frame_elems, int nchan,
-                                                       int32_t* __restrict__ hbuf, size_t h_frame_elems,
+                                                       const int32_t* __restrict__ hbuf, size_t h_frame_elems,
                                                        const ScaleDev* __restrict__ sd, int nscales,
                                                        const int* __restrict__ band_first, int total_bands, int sq_odd_rows_only) {
   const int lane = threadIdx.x & 63;
@@ -174,25 +207,32 @@ __global__ __launch_bounds__(256) void k_integral_band(const uint8_t* __restrict
   const uint8_t* src = pyr + f * pyr_frame_bytes + S.img_ofs + (size_t)r0 * S.pitch8;
   int32_t* osum = integ + (f * nchan + 0) * int_frame_elems + S.int_ofs + (size_t)(r0 + 1) * S.pitchI;
   int32_t* osq = SQ ? integ + (f * nchan + 1) * int_frame_elems + S.int_ofs + (size_t)(r0 + 1) * S.pitchI : nullptr;
-  int32_t* hsum = hbuf + (f * nchan + 0) * h_frame_elems + S.h_ofs + (size_t)bnd * S.pitchI;
-  int32_t* hsq = SQ ? hbuf + (f * nchan + 1) * h_frame_elems + S.h_ofs + (size_t)bnd * S.pitchI : nullptr;
+  const int32_t* hsum = hbuf + (f * nchan + 0) * h_frame_elems + S.h_ofs + (size_t)bnd * S.pitchI;
+  const int32_t* hsq = SQ ? hbuf + (f * nchan + 1) * h_frame_elems + S.h_ofs + (size_t)bnd * S.pitchI : nullptr;
   unsigned carry_s[INT_BAND], carry_q[INT_BAND];
 #pragma unroll
   for (int r = 0; r < INT_BAND; r++) carry_s[r] = carry_q[r] = 0;
+  unsigned carry_hs = 0, carry_hq = 0;
   for (int c0 = 0; c0 < S.pitchI; c0 += 256) {
     const int px = c0 + lane * 4;
     const bool col_ok = px < S.pitchI;
     uint4 vs = make_uint4(0, 0, 0, 0), vq = make_uint4(0, 0, 0, 0);  // running vertical sums of the row prefixes
-    if (FINAL && col_ok) {  // rows above this band
-      const int4 a = *reinterpret_cast<const int4*>(hsum + px);
-      vs = make_uint4((unsigned)a.x, (unsigned)a.y, (unsigned)a.z, (unsigned)a.w);
-      if (SQ) {
-        const int4 q = *reinterpret_cast<const int4*>(hsq + px);
-        vq = make_uint4((unsigned)q.x, (unsigned)q.y, (unsigned)q.z, (unsigned)q.w);
-      }
-      if (bnd == 0) {  // integral row 0 is all zeros
+    if (bnd == 0) {  // no rows above; integral row 0 is all zeros
+      if (col_ok) {
         *reinterpret_cast<int4*>(osum - S.pitchI + px) = make_int4(0, 0, 0, 0);
         if (SQ) *reinterpret_cast<int4*>(osq - S.pitchI + px) = make_int4(0, 0, 0, 0);
+      }
+    } else {  // the rows above this band: the column sums of the bands above it go through the scan like a row of pixels
+      int4 a = make_int4(0, 0, 0, 0), q = make_int4(0, 0, 0, 0);
+      if (col_ok) {
+        a = *reinterpret_cast<const int4*>(hsum + px);
+        if (SQ) q = *reinterpret_cast<const int4*>(hsq + px);
+      }
+      const unsigned ha[4] = {(unsigned)a.x, (unsigned)a.y, (unsigned)a.z, (unsigned)a.w};
+      vs = row_prefix_u32(ha, carry_hs, lane);
+      if (SQ) {
+        const unsigned hq[4] = {(unsigned)q.x, (unsigned)q.y, (unsigned)q.z, (unsigned)q.w};
+        vq = row_prefix_u32(hq, carry_hq, lane);
       }
     }
     unsigned word[INT_BAND];
@@ -201,40 +241,25 @@ __global__ __launch_bounds__(256) void k_integral_band(const uint8_t* __restrict
       word[r] = (r < nrows && px < S.pitch8) ? *reinterpret_cast<const unsigned*>(src + (size_t)r * S.pitch8 + px) : 0u;
 #pragma unroll
     for (int r = 0; r < INT_BAND; r++) {
-      unsigned p[4], a[4], q[4];
+      unsigned p[4], pp[4];
 #pragma unroll
-      for (int k = 0; k < 4; k++) p[k] = (px + k < S.w) ? ((word[r] >> (8 * k)) & 0xffu) : 0u;
-      a[0] = p[0];
-      q[0] = p[0] * p[0];
-#pragma unroll
-      for (int k = 1; k < 4; k++) {
-        a[k] = a[k - 1] + p[k];
-        q[k] = q[k - 1] + p[k] * p[k];
+      for (int k = 0; k < 4; k++) {
+        p[k] = (px + k < S.w) ? ((word[r] >> (8 * k)) & 0xffu) : 0u;
+        pp[k] = p[k] * p[k];
       }
-      const unsigned ts = wave_scan_u32(a[3]);
-      const unsigned base_s = carry_s[r] + ts - a[3];
-      const unsigned last_s = base_s + a[3];
-      unsigned prev_s = dpp_u32<0x138, 0xF>(last_s);  // wave_shr:1: value of the previous lane
-      if (lane == 0) prev_s = carry_s[r];
-      carry_s[r] = (unsigned)__builtin_amdgcn_readlane((int)last_s, 63);
-      // column c of the integral row holds the sum of pixels < c: {prev lane's last, P0, P1, P2}
-      vs.x += prev_s;
-      vs.y += base_s + a[0];
-      vs.z += base_s + a[1];
-      vs.w += base_s + a[2];
+      const uint4 rs = row_prefix_u32(p, carry_s[r], lane);
+      vs.x += rs.x;
+      vs.y += rs.y;
+      vs.z += rs.z;
+      vs.w += rs.w;
       if (SQ) {
-        const unsigned tq = wave_scan_u32(q[3]);
-        const unsigned base_q = carry_q[r] + tq - q[3];
-        const unsigned last_q = base_q + q[3];
-        unsigned prev_q = dpp_u32<0x138, 0xF>(last_q);
-        if (lane == 0) prev_q = carry_q[r];
-        carry_q[r] = (unsigned)__builtin_amdgcn_readlane((int)last_q, 63);
-        vq.x += prev_q;
-        vq.y += base_q + q[0];
-        vq.z += base_q + q[1];
-        vq.w += base_q + q[2];
+        const uint4 rq = row_prefix_u32(pp, carry_q[r], lane);
+        vq.x += rq.x;
+        vq.y += rq.y;
+        vq.z += rq.z;
+        vq.w += rq.w;
       }
-      if (FINAL && col_ok && r < nrows) {
+      if (col_ok && r < nrows) {
         *reinterpret_cast<int4*>(osum + (size_t)r * S.pitchI + px) = make_int4((int)vs.x, (int)vs.y, (int)vs.z, (int)vs.w);
         // The detector reads the squared sums only at the 4 corners of each window's variance rectangle: with a scan
         // step of 2 and an even window height those are odd integral rows; the even rows are never read, so they are
@@ -248,10 +273,39 @@ __global__ __launch_bounds__(256) void k_integral_band(const uint8_t* __restrict
         }
       }
     }
-    if (!FINAL && col_ok) {
-      *reinterpret_cast<int4*>(hsum + px) = make_int4((int)vs.x, (int)vs.y, (int)vs.z, (int)vs.w);
-      if (SQ) *reinterpret_cast<int4*>(hsq + px) = make_int4((int)vq.x, (int)vq.y, (int)vq.z, (int)vq.w);
-    }
+  }
+}
+
+// Column sums of the bands of levels the caller filled in itself (no k_resize ran): block = one band of one scale,
+// thread = 4 adjacent columns, vertical adds only. Same output as k_resize's: H[b][x] per pixel column, 0 from w to pitchI.
+template <bool SQ>
+__global__ __launch_bounds__(256) void k_band_colsums(const uint8_t* __restrict__ pyr, size_t pyr_frame_bytes, int nchan,
+                                                      int32_t* __restrict__ hbuf, size_t h_frame_elems,
+                                                      const ScaleDev* __restrict__ sd, int nscales,
+                                                      const int* __restrict__ band_first) {
+  const int s = find_segment(band_first, nscales, blockIdx.x);
+  const ScaleDev S = sd[s];
+  const int bnd = blockIdx.x - band_first[s];
+  const int r0 = bnd * INT_BAND;
+  const int nrows = min(INT_BAND, S.h - r0);
+  const size_t f = blockIdx.y;
+  const uint8_t* src = pyr + f * pyr_frame_bytes + S.img_ofs + (size_t)r0 * S.pitch8;
+  int32_t* hsum = hbuf + (f * nchan + 0) * h_frame_elems + S.h_ofs + (size_t)bnd * S.pitchI;
+  int32_t* hsq = SQ ? hbuf + (f * nchan + 1) * h_frame_elems + S.h_ofs + (size_t)bnd * S.pitchI : nullptr;
+  for (int px = threadIdx.x * 4; px < S.pitchI; px += 1024) {
+    unsigned cs[4] = {0, 0, 0, 0}, cq[4] = {0, 0, 0, 0};
+    if (px < S.pitch8)
+      for (int r = 0; r < nrows; r++) {
+        const unsigned word = *reinterpret_cast<const unsigned*>(src + (size_t)r * S.pitch8 + px);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const unsigned v = (px + k < S.w) ? ((word >> (8 * k)) & 0xffu) : 0u;
+          cs[k] += v;
+          cq[k] += v * v;
+        }
+      }
+    *reinterpret_cast<int4*>(hsum + px) = make_int4((int)cs[0], (int)cs[1], (int)cs[2], (int)cs[3]);
+    if (SQ) *reinterpret_cast<int4*>(hsq + px) = make_int4((int)cq[0], (int)cq[1], (int)cq[2], (int)cq[3]);
   }
 }
 
@@ -547,26 +601,30 @@ void launch_front(hipStream_t st, const FrontTables& T, const FrontIO& io, int n
   const FrontLayout& L = T.L;
   const int ns = (int)L.sd.size();
   if (ns == 0 || nf == 0) return;
+  // io.hbuf set: the pyramid kernel also writes the column sums of the integral bands
   if (parts & FRONT_RESIZE)
     hipLaunchKernelGGL(k_resize, dim3(L.resize_first[ns], nf), dim3(256), 0, st, io.src, io.row_stride, io.frame_stride, L.src_w, L.src_h,
-                       io.pyr, L.pyr_frame_bytes, T.d_sd.p, ns, T.d_resize_first.p, T.d_xofs.p, T.d_xw1.p, T.d_yofs.p, T.d_yw1.p);
+                       io.pyr, L.pyr_frame_bytes, T.d_sd.p, ns, T.d_resize_first.p, T.d_xofs.p, T.d_xw1.p, T.d_yofs.p, T.d_yw1.p, io.hbuf,
+                       L.h_frame_elems, io.nchan, io.sq ? 1 : 0);
   if (!(parts & FRONT_INTEGRALS)) return;
-  // integral images: band totals, carry down the bands, finished integral
+  // integral images: band column sums (unless k_resize left them: see FrontIO::src), carry down the bands, finished integral
   const int n_bands = L.band_first[ns];
-  const dim3 grid((n_bands + 3) / 4, nf);
-  if (io.sq)
-    hipLaunchKernelGGL((k_integral_band<true, false>), grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
-                       io.hbuf, L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p, n_bands, 0);
-  else
-    hipLaunchKernelGGL((k_integral_band<false, false>), grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
-                       io.hbuf, L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p, n_bands, 0);
+  if (!io.src) {
+    if (io.sq)
+      hipLaunchKernelGGL(k_band_colsums<true>, dim3(n_bands, nf), dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.nchan, io.hbuf,
+                         L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p);
+    else
+      hipLaunchKernelGGL(k_band_colsums<false>, dim3(n_bands, nf), dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.nchan, io.hbuf,
+                         L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p);
+  }
   hipLaunchKernelGGL(k_integral_carry, dim3(L.col_first[ns], nf, io.sq ? 2 : 1), dim3(64), 0, st, io.hbuf, L.h_frame_elems, io.nchan, T.d_sd.p,
                      ns, T.d_col_first.p);
+  const dim3 grid((n_bands + 3) / 4, nf);
   if (io.sq)
-    hipLaunchKernelGGL((k_integral_band<true, true>), grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
+    hipLaunchKernelGGL(k_integral_band<true>, grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
                        io.hbuf, L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p, n_bands, io.sq_odd_rows_only);
   else
-    hipLaunchKernelGGL((k_integral_band<false, true>), grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
+    hipLaunchKernelGGL(k_integral_band<false>, grid, dim3(256), 0, st, io.pyr, L.pyr_frame_bytes, io.integ, L.int_frame_elems, io.nchan,
                        io.hbuf, L.h_frame_elems, T.d_sd.p, ns, T.d_band_first.p, n_bands, io.sq_odd_rows_only);
   if (L.max_nseg == 0) return;
   // tilted integral into channel tilt_chan: diagonal sums, then the column recurrence, each as segment totals + final pass
