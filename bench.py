@@ -7,8 +7,13 @@ images, cascade evaluation, skip-rule filter, copy-back of the candidates, recta
 the detections over RCCL. One process per GPU; frames shard across ranks (weak scaling: --frames per GPU per step).
 
 Prints ONE JSON line on rank 0 (see the driver contract); `roofline` prices the cascade-evaluation kernel against the
-HBM roofline with the algorithmic byte count of SURVEY.md §8d; `cpu_baseline` times the CPU oracle (a restatement of
-the reference path; OpenCV itself is not installed) on the host cores, rank 0 at N = 1 only.
+HBM roofline with the algorithmic byte count of SURVEY.md §8d, from the HIP events of the timed steps.
+
+A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the line. `--full`
+adds everything that takes runs of its own, after the timed region (rank 0; all but the frame-0 counts at N = 1 only):
+`cpu_baseline` times the CPU oracle (a restatement of the reference path; OpenCV itself is not installed) on the host cores
+and compares its rectangles with the GPU's; `host_split`, `value_synchronous` and `host_frames`; the visited-window and
+LDS corner-read counts of frame 0; `extra_workloads`. Without it those fields are null or absent.
 """
 import argparse
 import json
@@ -499,15 +504,20 @@ def main():
     ap.add_argument("--content", choices=["natural", "uniform"], default="natural",
                     help="frame distribution of SURVEY 8d config 2: (ii) natural-like 1/f noise (default, the headline) or (i) "
                          "i.i.d. uniform noise (almost every window dies in stage 0-1)")
-    ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also run everything that is reported beside the headline and takes runs of its "
+                                                        "own: the CPU baseline, the host split and host-frame legs, the visited-window "
+                                                        "and LDS corner-read counts of frame 0, and the extra workloads (LBP cascade, "
+                                                        "uniform-noise frames, training kernels). Without it a run sets up, warms up, "
+                                                        "times its steps and prints the line")
+    ap.add_argument("--cpu-frames", type=int, default=4, help="with --full: frames of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--specialize", type=int, default=7, help="stages compiled into the cascade kernel at load time (hiprtc; 0 = "
                                                               "table-driven kernel only)")
     ap.add_argument("--device-only", action="store_true", help="time the device pipeline only (no copy-back/grouping)")
     ap.add_argument("--sync-steps", action="store_true", help="one synchronous cc_detect_batch call per step instead of pipelined "
                                                             "submit / collect (the headline of rounds 1-2)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the legs reported beside the headline (host split, host-frame "
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the legs reported beside the headline (host split, host-frame "
                                                           "call shape, LBP cascade, uniform-noise frames); rank 0 at N = 1 only")
-    ap.add_argument("--cpu-reps", type=int, default=5, help="repetitions of the CPU-baseline sample (median is reported)")
+    ap.add_argument("--cpu-reps", type=int, default=5, help="with --full: repetitions of the CPU-baseline sample (median is reported)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                                                       "the multi-rank path on a box with fewer GPUs than ranks)")
     ap.add_argument("--rehearse-gather", action="store_true", help="no detector, no GPU: every rank makes up the rectangles of its "
@@ -628,7 +638,7 @@ def main():
     # Where the step time goes that is not kernel time: the same step without copy-back and grouping (device pipeline
     # only), and the step fed from HOST frames (the reference's call shape, tools/detection/Cpp/main.cpp:27-45: the image is
     # in host memory; H2D copies included). Both outside the headline's timed region; rank 0, N = 1.
-    extra_legs = rank == 0 and world == 1 and not args.device_only and not args.no_extra
+    extra_legs = args.full and rank == 0 and world == 1 and not args.device_only and not args.no_extra
     host_split = None
     host_frames_leg = None
     if extra_legs:
@@ -693,7 +703,8 @@ def main():
     # windows the scan actually visits (grid windows minus the positions the stage-0 skip rule jumps over), frame 0,
     # outside the timed region (SURVEY.md §8d asks for it next to the grid count)
     visited0 = None
-    if rank == 0 and not args.device_only and not os.environ.get("CCAMD_BENCH_NO_VISITED"):  # (one extra 1-frame launch)
+    frame0_counts = args.full and rank == 0 and not args.device_only and not os.environ.get("CCAMD_BENCH_NO_VISITED")
+    if frame0_counts:  # (one extra 1-frame launch)
         visited0 = int(clf.debug_windows(frames_host[0], args.scale_factor)[2].sum())
     total_windows = windows_per_frame * B * world * args.steps
     value = total_windows / dt / 1e6
@@ -711,7 +722,7 @@ def main():
     # its scan visits (frame 0: 4 corners of the variance rectangle + 4 per rectangle of every stump the window reaches;
     # LBP: 16 per stump), priced against the LDS gather peak (ds_read_b32: 128 B/clk/CU x 256 CUs x 2.4 GHz).
     lds = None
-    if rank == 0 and not args.device_only and not os.environ.get("CCAMD_BENCH_NO_VISITED") and eval_ms > 0:
+    if frame0_counts and eval_ms > 0:
         reads0 = corner_reads_frame0(clf, frames_host[0], args.scale_factor)
         lds_peak = 256 * 128 * 2.4  # GB/s
         lds_ach = reads0 * 4 * frames_per_launch / (eval_ms * 1e-3) / 1e9
@@ -781,7 +792,7 @@ def main():
             "secondary": secondary,
         },
     }
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:
         from oracle import oracle as orc
         o = orc.load_cascade_xml(args.cascade)
         cores = usable_cores()

@@ -83,7 +83,8 @@ def test_bench_two_ranks_on_one_gpu_gloo():
 
 @pytest.mark.gpu
 def test_bench_single_rank_line_has_roofline_and_cpu_baseline():
-    r = _run(["--frames", "2", "--steps", "1", "--warmup", "1", "--width", "640", "--height", "480", "--cpu-frames", "1"], timeout=900)
+    """`--full`: the legs beside the headline run too (the CPU baseline among them, compared with the GPU's rectangles)."""
+    r = _run(["--full", "--frames", "2", "--steps", "1", "--warmup", "1", "--width", "640", "--height", "480", "--cpu-frames", "1"], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 1
@@ -114,20 +115,31 @@ def test_dump_outputs_and_steps_are_checked_before_any_work(tmp_path):
     assert not os.listdir(str(tmp_path))
 
 
+def test_full_is_an_option_of_its_own():
+    """--full is accepted (the --steps check, which comes after argument parsing, is what refuses this command)."""
+    r = _run(["--full", "--steps", "0"], timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and "unrecognized" not in r.stderr
+
+
 @pytest.mark.gpu
 def test_bench_dump_outputs_are_the_last_steps_rectangles(tmp_path):
     """--dump-outputs writes what the last timed step returned, as float64 [frame, x, y, w, h] rows plus per-frame counts:
-    the same rectangles the CPU oracle finds on bench.py's seeded frames."""
+    the same rectangles the CPU oracle finds on bench.py's seeded frames. The run is a plain one (no --full): its line has
+    the headline's fields and none of the legs that take runs of their own."""
     sys.path.insert(0, ROOT)
     import numpy as np
 
     import bench
     from oracle import oracle as orc
-    r = _run(["--frames", "2", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "480", "--cpu-frames", "0",
-              "--no-extra", "--dump-outputs", str(tmp_path)], timeout=900)
+    r = _run(["--frames", "2", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "480", "--dump-outputs", str(tmp_path)], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert out["value"] > 0 and out["unit"] == "Mwindows/s" and out["higher_is_better"] is True and out["metric"] and out["dtype"]
+    assert out["roofline"]["achieved"] > 0  # from the timed steps' own events
+    assert "cpu_baseline" not in out and "extra_workloads" not in out
+    assert out["host_split"] is None and out["host_frames"] is None and out["value_synchronous"] is None
+    assert out["config"]["visited_windows_frame0"] is None and out["roofline"]["lds"] is None
     rects = np.load(str(tmp_path / "rects.npy"))
     counts = np.load(str(tmp_path / "rects_per_frame.npy"))
     assert rects.dtype == np.float64 and counts.dtype == np.float64 and rects.shape == (int(counts.sum()), 5)

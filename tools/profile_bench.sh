@@ -18,5 +18,5 @@ export CCAMD_NO_FRONT_OVERLAP=1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_rd -- python3 bench.py --cpu-frames 0 --no-extra --steps 2 --warmup 1 "$@" > $out/bench_pmc_rd.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_wr -- python3 bench.py --cpu-frames 0 --no-extra --steps 2 --warmup 1 "$@" > $out/bench_pmc_wr.log 2>&1
 unset CCAMD_NO_FRONT_OVERLAP CCAMD_BENCH_NO_VISITED
-python3 bench.py "$@" > $out/bench_plain.json 2> $out/bench_plain.err
+python3 bench.py --full "$@" > $out/bench_plain.json 2> $out/bench_plain.err
 tail -1 $out/bench_plain.json
