@@ -110,14 +110,15 @@ struct Plan {
   size_t mask_frame_words = 0;
   long long windows = 0, integral_elems = 0;
   int n_grid_rows = 0;
-  int n_tiles = 0;  // tiles of TILE_Y window rows (the ahead-of-time kernels); other heights: tiles_for
   struct TileList {
     int n = 0;
     DevBuf<int4> d;
   };
-  std::map<int, std::unique_ptr<TileList>> other_tiles;  // tile lists of the specialised kernel's modules, key = tile_list_key(rows, step)
+  // Tile lists by (window rows per tile, step of the scales covered or 0 = all), see plan_tiles: (TILE_Y, 0) for the
+  // ahead-of-time kernels, the others for the specialised kernel's modules. An entry is never reallocated or moved while the
+  // plan lives (map nodes stay where they are): captured graphs replay its pointer.
+  std::map<std::pair<int, int>, TileList> tiles;
   DevBuf<int> d_gridrow_first;
-  DevBuf<int4> d_tiles;
   // Single-image calls (the detection tool's shape) are launch-bound: ~10 launches, memsets and copies for well under a
   // millisecond of device work. After a first ordinary call has sized every buffer, the whole pass (H2D copy of the
   // image, pyramid, integrals, cascade kernel, skip filter, copy-back of the counters) is captured into a hipGraph and
@@ -162,7 +163,7 @@ struct BatchSink {
 
 using namespace ccamd;
 
-constexpr int kStageSlots = 3;  // staging slots for host frames (run_batch: why three)
+constexpr int kStageSlots = 3;  // staging slots for host frames (stage_pass: why three)
 
 struct cc_detector {
   Cascade m;
@@ -192,8 +193,6 @@ struct cc_detector {
   DevBuf<int> d_tree_root, d_tree_leaf0;
   DevBuf<float> d_leaves;
   size_t lds = 0;  // dynamic LDS bytes per tile (larger of the two layouts)
-  size_t lds_spec = 0;  // the same for the installed specialised kernel (smaller when its STEP-2 tiles hold 16-bit entries)
-  int spec_tile_y = TILE_Y;  // window rows per tile the installed specialised kernel was compiled for (spec_tile_rows)
   // plans + workspace
   std::vector<std::unique_ptr<Plan>> plans;
   DevBuf<uint8_t> d_frames, d_pyr;
@@ -204,17 +203,11 @@ struct cc_detector {
   hipEvent_t front_done[2] = {nullptr, nullptr}, eval_done[2] = {nullptr, nullptr}, batch_begin = nullptr;
   bool eval_pending[2] = {false, false};
   int overlap_front = 1;
-  // run-time specialised cascade kernel (cc_detector_specialize); null = table-driven kernel
-  hipModule_t spec_mod = nullptr;   // the module that covers every tile, or the tiles of STEP-2 scales when spec_mod1 exists
-  hipFunction_t spec_fn = nullptr;
-  // Optional second module for the tiles of STEP-1 scales (spec_modules: Haar kernels with 32-bit tiles compile one module per
-  // step, each with its own tile height and LDS request)
-  hipModule_t spec_mod1 = nullptr;
-  hipFunction_t spec_fn1 = nullptr;
-  size_t lds_spec1 = 0;
-  int spec_tile_y1 = TILE_Y;
+  // run-time specialised cascade kernel (cc_detector_specialize, spec_load); n_spec 0 = table-driven kernel. spec[0] covers
+  // every tile, or the tiles of STEP-2 scales when spec[1] exists: that one covers the tiles of STEP-1 scales.
+  SpecModule spec[2];
+  int n_spec = 0;
   int last_stamp_tiles = 0;  // CCAMD_DEBUG_STAMPS: tiles of the last pass (all launches)
-  int spec_only_step = 0;  // tiles the primary module covers: 0 = all, 2 = those of STEP-2 scales (then spec_fn1 covers STEP 1)
   int spec_stages = 0;
   // background build of the specialised module (cc_detector_specialize_async / CCAMD_AUTO_SPECIALIZE): a host thread
   // generates and compiles; the next detection call on the owning thread loads the module and switches over
@@ -274,6 +267,12 @@ struct cc_detector {
   std::vector<TimingEvent> events;
   cc_detector_timings tm{};
 
+  void unload_spec() {  // back to the table-driven kernel; the caller has made sure that no launch of the modules is in flight
+    for (int i = 0; i < n_spec; i++) (void)hipModuleUnload(spec[i].mod);
+    spec[0] = spec[1] = SpecModule{};
+    n_spec = 0;
+    spec_stages = 0;
+  }
   ~cc_detector() {
     for (auto& e : events) {
       (void)hipEventDestroy(e.a);
@@ -284,8 +283,7 @@ struct cc_detector {
 
     if (front_stream) (void)hipStreamDestroy(front_stream);
     if (spec_thread.joinable()) spec_thread.join();
-    if (spec_mod) (void)hipModuleUnload(spec_mod);
-    if (spec_mod1) (void)hipModuleUnload(spec_mod1);
+    unload_spec();
     for (hipEvent_t e : {pass_done[0], pass_done[1], front_done[0], front_done[1], eval_done[0], eval_done[1], batch_begin})
       if (e) (void)hipEventDestroy(e);
     if (h_counts) (void)hipHostFree(h_counts);
@@ -469,8 +467,7 @@ static bool same_params(const cc_detect_params& a, const cc_detect_params& b) {
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2): the list is permuted so that the tiles
 // one XCD receives are neighbours in the image and share their halo rows/columns in that XCD's L2. Placement only changes
 // speed, never results.
-static int tile_list_key(int tile_y, int only_step) { return tile_y * 4 + only_step; }  // Plan::other_tiles
-static std::vector<int4> plan_tile_list(const std::vector<ScaleGeom>& geom, int tile_y, int only_step = 0) {
+static std::vector<int4> plan_tile_list(const std::vector<ScaleGeom>& geom, int tile_y, int only_step) {
   std::vector<int4> tiles;
   for (size_t i = 0; i < geom.size(); i++) {
     const ScaleGeom& g = geom[i];
@@ -488,6 +485,29 @@ static std::vector<int4> plan_tile_list(const std::vector<ScaleGeom>& geom, int 
       if (src < n) perm.push_back(tiles[src]);
     }
   return perm;
+}
+
+// The plan's list of tiles of `tile_y` window rows over the scales of step `only_step` (0 = all). `create`: a missing list
+// is built and uploaded -- through the detector's own stream, and waited for there: a copy on the legacy stream (plain
+// hipMemcpy) is refused while ANY thread of the process captures a graph, and fails that thread's capture with it (two
+// detectors on two host threads, one of them capturing its single-image pass). Otherwise a missing list is an error.
+static cc_status plan_tiles(cc_detector* d, Plan* P, int tile_y, int only_step, bool create, const Plan::TileList** out) {
+  const std::pair<int, int> key(tile_y, only_step);
+  auto it = P->tiles.find(key);
+  if (it == P->tiles.end()) {
+    if (!create) return set_error(CC_ERR_HIP, "internal: no tile list for tiles of %d window rows (step %d)", tile_y, only_step);
+    const std::vector<int4> tv = plan_tile_list(P->geom, tile_y, only_step);
+    it = P->tiles.try_emplace(key).first;
+    it->second.n = (int)tv.size();
+    hipError_t e = it->second.d.upload(tv, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);  // tv ends here
+    if (e != hipSuccess) {
+      P->tiles.erase(it);
+      return set_error(CC_ERR_HIP, "uploading a tile list failed: %s", hipGetErrorString(e));
+    }
+  }
+  *out = &it->second;
+  return CC_OK;
 }
 
 static cc_status build_plan(cc_detector* d, int w, int h, const cc_detect_params& p, Plan** out) {
@@ -527,12 +547,11 @@ static cc_status build_plan(cc_detector* d, int w, int h, const cc_detect_params
   P->mask_frame_words = (size_t)mask_ofs;
   P->windows = win_ofs;
   P->n_grid_rows = gridrow_first[ns];
-  std::vector<int4> tiles = plan_tile_list(P->geom, TILE_Y);
-  P->n_tiles = (int)tiles.size();
   hipStream_t st = d->stream;
   CC_HIP(P->d_gridrow_first.upload(gridrow_first, st));
-  CC_HIP(P->d_tiles.upload(tiles, st));
   CC_HIP(P->front.upload(st));  // synchronises: the host vectors above go out of scope
+  const Plan::TileList* own = nullptr;  // the ahead-of-time kernels' list, made like any other
+  if (cc_status ts = plan_tiles(d, P.get(), TILE_Y, 0, true, &own); ts != CC_OK) return ts;
   *out = P.get();
   if (d->plans.size() >= 8) d->plans.erase(d->plans.begin());
   d->plans.push_back(std::move(P));
@@ -579,12 +598,147 @@ static void collect_events(cc_detector* d) {
   d->events.clear();
 }
 
+// The cascade-kernel launches of a pass: one ahead-of-time kernel (fn null) over the plan's TILE_Y tiles, or the specialised
+// kernel's module(s), each over the list of its own tile height (and of its step's tiles when there is a module per step).
+struct EvalLaunch {
+  hipFunction_t fn;
+  size_t lds;
+  int n_tiles;
+  const int4* tiles;
+};
+static cc_status pass_launches(cc_detector* d, Plan* P, bool create_lists, EvalLaunch out[2], int* n_out) {
+  const bool run_spec = d->n_spec > 0 && d->m.max_nodes_per_tree <= 1;
+  const int n = run_spec ? d->n_spec : 1;
+  for (int i = 0; i < n; i++) {
+    const SpecModule aot{nullptr, nullptr, d->lds, TILE_Y, 0};
+    const SpecModule& M = run_spec ? d->spec[i] : aot;
+    const Plan::TileList* tl = nullptr;
+    if (cc_status st = plan_tiles(d, P, M.tile_y, M.only_step, create_lists, &tl); st != CC_OK) return st;
+    out[i] = EvalLaunch{M.fn, M.lds, tl->n, tl->d.p};
+  }
+  *n_out = n;
+  return CC_OK;
+}
+
+// The specialised kernel may use other tile heights than the ahead-of-time kernels: its tile lists are built on first use,
+// before the pass is launched and never from inside a hipGraph capture (run_device_pass only looks them up).
+static cc_status ensure_spec_tiles(cc_detector* d, Plan* P) {
+  EvalLaunch launches[2];
+  int n = 0;
+  return pass_launches(d, P, true, launches, &n);
+}
+
+// Workspace of a pass in `slot`, sized for pass_capacity frames (only allocations, nothing is enqueued).
+static cc_status ensure_pass_workspace(cc_detector* d, const Plan* P, int slot, int nchan, bool tilt, bool debug) {
+  const FrontLayout& FL = P->front.L;
+  const size_t cap = (size_t)d->pass_capacity;
+  CC_HIP(d->d_pyr.ensure(FL.pyr_frame_bytes * cap));
+  CC_HIP(d->d_integ[slot].ensure(FL.int_frame_elems * (size_t)nchan * cap));
+  CC_HIP(d->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)nchan * cap, 4)));
+  if (tilt) {
+    CC_HIP(d->d_diag.ensure(FL.int_frame_elems * 2 * cap));
+    CC_HIP(d->d_tseg.ensure(std::max<size_t>(FL.tseg_frame_elems * cap, 1)));
+  }
+  CC_HIP(d->d_masks[slot].ensure(std::max<size_t>(P->mask_frame_words * cap, 1)));
+  if (d->cand_cap == 0) d->cand_cap = 1 << 18;
+  CC_HIP(d->d_cands[slot].ensure((size_t)d->cand_cap));
+  CC_HIP(d->d_out[slot].ensure((size_t)d->cand_cap));
+  if (debug) {
+    CC_HIP(d->d_dbg_codes.ensure((size_t)std::max<long long>(P->windows, 1)));
+    CC_HIP(d->d_dbg_sums.ensure((size_t)std::max<long long>(P->windows, 1)));
+    CC_HIP(d->d_dbg_visited.ensure((size_t)std::max<long long>(P->windows, 1)));
+  }
+  return CC_OK;
+}
+
+// Arguments of the cascade kernel for a pass in `slot`, all but `tiles` and `stamps` (per launch).
+static EvalArgs eval_args(const cc_detector* d, const Plan* P, int slot, int nchan, bool tilt, int sq_compact, bool debug) {
+  const bool haar = d->m.feature_type == CC_FEATURE_HAAR;
+  EvalArgs A;
+  A.integ = d->d_integ[slot].p;
+  A.int_frame_elems = P->front.L.int_frame_elems;
+  A.nchan = nchan;
+  A.tilt_chan = tilt ? 2 : -1;
+  A.sd = P->front.d_sd.p;
+  A.W0 = d->m.win_w;
+  A.H0 = d->m.win_h;
+  A.nstages = (int)d->m.stage_ntrees.size();
+  A.stage_first = d->d_stage_first.p;
+  A.stage_ntrees = d->d_stage_ntrees.p;
+  A.group_first = d->d_group_first.p;
+  A.ngroups = d->n_groups;
+  A.dense_from = d->dense_from;
+  A.wave_below = d->wave_below;
+  A.stop_after = d->stop_after;
+  A.split_stumps = d->split_stumps;
+  A.early_skip = d->early_skip;
+  A.sq_compact = sq_compact;
+  A.stage_thr = d->d_stage_thr.p;
+  A.masks = d->d_masks[slot].p;
+  A.mask_frame_words = P->mask_frame_words;
+  A.cands = d->d_cands[slot].p;
+  A.cand_count = d->d_counts[slot].p;
+  A.cand_cap = d->cand_cap;
+  A.stamps = nullptr;
+  A.dbg_codes = debug ? d->d_dbg_codes.p : nullptr;
+  A.dbg_sums = debug ? d->d_dbg_sums.p : nullptr;
+  A.stumps1 = haar ? (const void*)d->d_haar1.p : (const void*)d->d_lbp1.p;
+  A.stumps2 = haar ? (const void*)d->d_haar2.p : (const void*)d->d_lbp2.p;
+  A.wstumps1 = d->d_haar1w.p ? (const void*)d->d_haar1w.p : A.stumps1;
+  A.wstumps2 = d->d_haar2w.p ? (const void*)d->d_haar2w.p : A.stumps2;
+  A.gstumps = haar ? (const void*)d->d_haar_g.p : (const void*)d->d_lbp_g.p;
+  A.lbp16_all = d->lbp16_all;
+  if (!haar && d->d_lbp16.p) A.wstumps2 = d->d_lbp16.p;  // LBP wave phase of kernels with 16-bit tiles
+  A.trees = d->m.max_nodes_per_tree > 1 ? 1 : 0;
+  A.nodes1 = haar ? (const void*)d->d_hnode1.p : (const void*)d->d_lnode1.p;
+  A.nodes2 = haar ? (const void*)d->d_hnode2.p : (const void*)d->d_lnode2.p;
+  A.tree_root = d->d_tree_root.p;
+  A.tree_leaf0 = d->d_tree_leaf0.p;
+  A.leaves = d->d_leaves.p;
+  return A;
+}
+
+// The cascade-kernel launches of a pass over nf frames, one after the other on `st`.
+static cc_status launch_eval(cc_detector* d, EvalArgs A, const EvalLaunch* launches, int n_launches, int nf, bool haar, hipStream_t st) {
+  for (int i = 0; i < n_launches; i++) {
+    const EvalLaunch& L = launches[i];
+    if (L.n_tiles == 0) continue;
+    A.tiles = L.tiles;
+    if (L.fn) {
+      void* params[] = {&A};
+      // (the pass's EV_EVAL pair spans all cascade-kernel launches; the STEP-1 module's launch is also timed on its own)
+      EvScope ev1(d, i == 1 ? EV_EVAL_STEP1 : -1, st);
+      CC_HIP(hipModuleLaunchKernel(L.fn, (unsigned)L.n_tiles, (unsigned)nf, 1, EVAL_THREADS, 1, 1, (unsigned)L.lds, st, params, nullptr));
+    } else if (haar)
+      hipLaunchKernelGGL(k_eval_haar, dim3(L.n_tiles, nf), dim3(EVAL_THREADS), L.lds, st, A);
+    else
+      hipLaunchKernelGGL(k_eval_lbp, dim3(L.n_tiles, nf), dim3(EVAL_THREADS), L.lds, st, A);
+    if (A.stamps) A.stamps += (size_t)L.n_tiles * (size_t)nf * STAMP_SLOTS;
+  }
+  return CC_OK;
+}
+
+// CCAMD_DEBUG_STAMPS=<path>: waits for the pass and writes its stamps, [n_tiles * nf][STAMP_SLOTS] u64 (overwritten per pass).
+static cc_status dump_stamps(cc_detector* d, const char* path, int nf) {
+  CC_HIP(hipStreamSynchronize(d->stream));
+  const int n_tiles_run = d->last_stamp_tiles;
+  std::vector<unsigned long long> h((size_t)n_tiles_run * (size_t)nf * STAMP_SLOTS);
+  CC_HIP(hipMemcpyAsync(h.data(), d->d_stamps.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream));
+  CC_HIP(hipStreamSynchronize(d->stream));
+  if (FILE* f = std::fopen(path, "wb")) {
+    const int hdr[4] = {n_tiles_run, nf, STAMP_SLOTS, 0};
+    std::fwrite(hdr, sizeof(int), 4, f);
+    std::fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
+    std::fclose(f);
+  }
+  return CC_OK;
+}
+
 // Device pipeline for up to max_batch frames already resident on the device. Leaves the filtered candidate list
 // (d_out[slot], d_counts[slot][1]) on the device; no synchronisation.
 static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes, int nf, size_t row_stride,
                                  size_t frame_stride, bool debug, int slot, bool single_stream = false) {
-  const FrontLayout& FL = P->front.L;
-  const int ns = (int)FL.sd.size();
+  const int ns = (int)P->front.L.sd.size();
   hipStream_t st = d->stream;
   hipStream_t fs = d->overlap_front && !single_stream ? d->front_stream : d->stream;  // pyramid + integrals
   const bool haar = d->m.feature_type == CC_FEATURE_HAAR;
@@ -595,22 +749,7 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
   if (ns == 0 || nf == 0) return CC_OK;
   // even window sizes: the variance rectangle's corners of step-2 scales sit on odd rows and odd columns only
   const int sq_compact = (haar && d->m.win_w % 2 == 0 && d->m.win_h % 2 == 0) ? 1 : 0;
-  CC_HIP(d->d_pyr.ensure(FL.pyr_frame_bytes * (size_t)d->pass_capacity));
-  CC_HIP(d->d_integ[slot].ensure(FL.int_frame_elems * (size_t)nchan * (size_t)d->pass_capacity));
-  CC_HIP(d->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)nchan * (size_t)d->pass_capacity, 4)));
-  if (tilt) {
-    CC_HIP(d->d_diag.ensure(FL.int_frame_elems * 2 * (size_t)d->pass_capacity));
-    CC_HIP(d->d_tseg.ensure(std::max<size_t>(FL.tseg_frame_elems * (size_t)d->pass_capacity, 1)));
-  }
-  CC_HIP(d->d_masks[slot].ensure(std::max<size_t>(P->mask_frame_words * (size_t)d->pass_capacity, 1)));
-  if (d->cand_cap == 0) d->cand_cap = 1 << 18;
-  CC_HIP(d->d_cands[slot].ensure((size_t)d->cand_cap));
-  CC_HIP(d->d_out[slot].ensure((size_t)d->cand_cap));
-  if (debug) {
-    CC_HIP(d->d_dbg_codes.ensure((size_t)std::max<long long>(P->windows, 1)));
-    CC_HIP(d->d_dbg_sums.ensure((size_t)std::max<long long>(P->windows, 1)));
-    CC_HIP(d->d_dbg_visited.ensure((size_t)std::max<long long>(P->windows, 1)));
-  }
+  if (cc_status ws = ensure_pass_workspace(d, P, slot, nchan, tilt, debug); ws != CC_OK) return ws;
   // this slot's integrals may still be read by the cascade kernel launched two passes ago
   if (fs != st && d->eval_pending[slot]) CC_HIP(hipStreamWaitEvent(fs, d->eval_done[slot], 0));
   FrontIO io;
@@ -639,60 +778,10 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
   }
   {
     EvScope ev(d, EV_EVAL, st);
-    EvalArgs A;
-    A.integ = d->d_integ[slot].p;
-    A.int_frame_elems = FL.int_frame_elems;
-    A.nchan = nchan;
-    A.tilt_chan = tilt ? 2 : -1;
-    A.sd = P->front.d_sd.p;
-    A.W0 = d->m.win_w;
-    A.H0 = d->m.win_h;
-    A.nstages = (int)d->m.stage_ntrees.size();
-    A.stage_first = d->d_stage_first.p;
-    A.stage_ntrees = d->d_stage_ntrees.p;
-    A.group_first = d->d_group_first.p;
-    A.ngroups = d->n_groups;
-    A.dense_from = d->dense_from;
-    A.wave_below = d->wave_below;
-    A.stop_after = d->stop_after;
-    A.split_stumps = d->split_stumps;
-    A.early_skip = d->early_skip;
-    A.sq_compact = sq_compact;
-    A.stage_thr = d->d_stage_thr.p;
-    A.masks = d->d_masks[slot].p;
-    A.mask_frame_words = P->mask_frame_words;
-    A.cands = d->d_cands[slot].p;
-    A.cand_count = d->d_counts[slot].p;
-    A.cand_cap = d->cand_cap;
-    A.stamps = nullptr;
-    // The launches of this pass: one ahead-of-time kernel over the plan's tiles, or the specialised kernel's module(s), each
-    // over its own tile list (its tile height; the tiles of one step when there is a module per step). The lists were built
-    // by ensure_spec_tiles before the pass (never inside a graph capture).
-    struct EvalLaunch {
-      hipFunction_t fn;
-      size_t lds;
-      int n_tiles;
-      const int4* tiles;
-    };
+    EvalArgs A = eval_args(d, P, slot, nchan, tilt, sq_compact, debug);
     EvalLaunch launches[2];
     int n_launches = 0;
-    const bool run_spec = d->spec_fn && d->m.max_nodes_per_tree <= 1;
-    if (run_spec) {
-      const int want[2][2] = {{d->spec_tile_y, d->spec_only_step}, {d->spec_fn1 ? d->spec_tile_y1 : 0, 1}};
-      for (int i = 0; i < 2; i++) {
-        if (want[i][0] == 0) continue;
-        EvalLaunch L{i == 0 ? d->spec_fn : d->spec_fn1, i == 0 ? d->lds_spec : d->lds_spec1, P->n_tiles, P->d_tiles.p};
-        if (!(want[i][0] == TILE_Y && want[i][1] == 0)) {
-          const auto it = P->other_tiles.find(tile_list_key(want[i][0], want[i][1]));
-          if (it == P->other_tiles.end() || !it->second)
-            return set_error(CC_ERR_HIP, "internal: no tile list for tiles of %d window rows (step %d)", want[i][0], want[i][1]);
-          L.n_tiles = it->second->n;
-          L.tiles = it->second->d.p;
-        }
-        launches[n_launches++] = L;
-      }
-    } else
-      launches[n_launches++] = EvalLaunch{nullptr, d->lds, P->n_tiles, P->d_tiles.p};
+    if (cc_status ls = pass_launches(d, P, false, launches, &n_launches); ls != CC_OK) return ls;
     size_t stamp_tiles = 0;
     for (int i = 0; i < n_launches; i++) stamp_tiles += (size_t)launches[i].n_tiles;
     if (std::getenv("CCAMD_DEBUG_STAMPS")) {  // timing experiments: per-block phase stamps of the cascade kernel (launch after launch)
@@ -700,36 +789,7 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
       CC_HIP(hipMemsetAsync(d->d_stamps.p, 0, stamp_tiles * (size_t)nf * STAMP_SLOTS * sizeof(unsigned long long), st));
       A.stamps = d->d_stamps.p;
     }
-    A.dbg_codes = debug ? d->d_dbg_codes.p : nullptr;
-    A.dbg_sums = debug ? d->d_dbg_sums.p : nullptr;
-    A.stumps1 = haar ? (const void*)d->d_haar1.p : (const void*)d->d_lbp1.p;
-    A.stumps2 = haar ? (const void*)d->d_haar2.p : (const void*)d->d_lbp2.p;
-    A.wstumps1 = d->d_haar1w.p ? (const void*)d->d_haar1w.p : A.stumps1;
-    A.wstumps2 = d->d_haar2w.p ? (const void*)d->d_haar2w.p : A.stumps2;
-    A.gstumps = haar ? (const void*)d->d_haar_g.p : (const void*)d->d_lbp_g.p;
-    A.lbp16_all = d->lbp16_all;
-    if (!haar && d->d_lbp16.p) A.wstumps2 = d->d_lbp16.p;  // LBP wave phase of kernels with 16-bit tiles
-    A.trees = d->m.max_nodes_per_tree > 1 ? 1 : 0;
-    A.nodes1 = haar ? (const void*)d->d_hnode1.p : (const void*)d->d_lnode1.p;
-    A.nodes2 = haar ? (const void*)d->d_hnode2.p : (const void*)d->d_lnode2.p;
-    A.tree_root = d->d_tree_root.p;
-    A.tree_leaf0 = d->d_tree_leaf0.p;
-    A.leaves = d->d_leaves.p;
-    for (int i = 0; i < n_launches; i++) {
-      const EvalLaunch& L = launches[i];
-      if (L.n_tiles == 0) continue;
-      A.tiles = L.tiles;
-      if (L.fn) {
-        void* params[] = {&A};
-        // (the pass's EV_EVAL pair spans all cascade-kernel launches; the STEP-1 module's launch is also timed on its own)
-        EvScope ev1(d, i == 1 ? EV_EVAL_STEP1 : -1, st);
-        CC_HIP(hipModuleLaunchKernel(L.fn, (unsigned)L.n_tiles, (unsigned)nf, 1, EVAL_THREADS, 1, 1, (unsigned)L.lds, st, params, nullptr));
-      } else if (haar)
-        hipLaunchKernelGGL(k_eval_haar, dim3(L.n_tiles, nf), dim3(EVAL_THREADS), L.lds, st, A);
-      else
-        hipLaunchKernelGGL(k_eval_lbp, dim3(L.n_tiles, nf), dim3(EVAL_THREADS), L.lds, st, A);
-      if (A.stamps) A.stamps += (size_t)L.n_tiles * (size_t)nf * STAMP_SLOTS;
-    }
+    if (cc_status es = launch_eval(d, A, launches, n_launches, nf, haar, st); es != CC_OK) return es;
     d->last_stamp_tiles = (int)stamp_tiles;
   }
   if (fs != st) {
@@ -745,19 +805,8 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
                          d->d_masks[slot].p, d->d_dbg_visited.p);
   }
   CC_HIP(hipGetLastError());
-  if (const char* path = std::getenv("CCAMD_DEBUG_STAMPS")) {  // dump [n_tiles * nf][STAMP_SLOTS] u64 (overwritten per pass)
-    CC_HIP(hipStreamSynchronize(st));
-    const int n_tiles_run = d->last_stamp_tiles;
-    std::vector<unsigned long long> h((size_t)n_tiles_run * (size_t)nf * STAMP_SLOTS);
-    CC_HIP(hipMemcpyAsync(h.data(), d->d_stamps.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream));
-    CC_HIP(hipStreamSynchronize(d->stream));
-    if (FILE* f = std::fopen(path, "wb")) {
-      const int hdr[4] = {n_tiles_run, nf, STAMP_SLOTS, 0};
-      std::fwrite(hdr, sizeof(int), 4, f);
-      std::fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-      std::fclose(f);
-    }
-  }
+  if (const char* path = std::getenv("CCAMD_DEBUG_STAMPS"))
+    if (cc_status ds = dump_stamps(d, path, nf); ds != CC_OK) return ds;
   d->tm.frames += nf;
   d->tm.grid_windows += P->windows * nf;
   d->tm.integral_elems += P->integral_elems * nf;
@@ -781,33 +830,6 @@ static cc_status check_frame_args(const cc_detector* d, const uint8_t* frames, i
   if (!(p->scale_factor > 1.0)) return set_error(CC_ERR_INVALID_ARG, "%s: scaleFactor must be > 1", who);
   return CC_OK;
 }
-
-// The specialised kernel may use another tile height than the ahead-of-time kernels: its tile list is built on first use,
-// before the pass is launched and never from inside a hipGraph capture. The copy goes through the detector's own stream and
-// is waited for there: a copy on the legacy stream (plain hipMemcpy) is refused while ANY thread of the process captures a
-// graph, and fails that thread's capture with it (two detectors on two host threads, one of them capturing its single-image pass).
-static cc_status ensure_spec_tiles(cc_detector* d, Plan* P) {
-  if (!d->spec_fn || d->m.max_nodes_per_tree > 1) return CC_OK;
-  const int want[2][2] = {{d->spec_tile_y, d->spec_only_step}, {d->spec_fn1 ? d->spec_tile_y1 : 0, 1}};
-  for (const auto& w : want) {
-    if (w[0] == 0 || (w[0] == TILE_Y && w[1] == 0)) continue;  // no such module / the plan's own list serves it
-    std::unique_ptr<Plan::TileList>& tl = P->other_tiles[tile_list_key(w[0], w[1])];
-    if (tl) continue;
-    std::unique_ptr<Plan::TileList> fresh(new Plan::TileList);
-    const std::vector<int4> tv = plan_tile_list(P->geom, w[0], w[1]);
-    fresh->n = (int)tv.size();
-    CC_HIP(fresh->d.ensure(std::max<size_t>(tv.size(), 1)));
-    if (!tv.empty()) {
-      CC_HIP(hipMemcpyAsync(fresh->d.p, tv.data(), tv.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
-      CC_HIP(hipStreamSynchronize(d->stream));  // tv ends here
-    }
-    tl = std::move(fresh);
-  }
-  return CC_OK;
-}
-
-static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes, int nf, size_t row_stride,
-                                 size_t frame_stride, bool debug, int slot, bool single_stream);
 
 // Fetches the results of the pending pass and hands them to its sink. On candidate-list overflow the lists grow and the
 // pass is redone synchronously. Growing frees the lists of BOTH slots; a pass is judged against the capacity it was
@@ -946,6 +968,203 @@ static cc_status stage_host_frames(cc_detector* d, const uint8_t* src, int nf, i
 
 static void spec_poll(cc_detector* d);  // installs a finished background specialisation
 
+// Retires the pending pass, if any, on behalf of the batch that delivers to `sink`: as its own when it is that batch's (an
+// error is the caller's), as a foreign one otherwise (an error is kept for the batch it belongs to).
+static cc_status retire_for(cc_detector* d, const std::shared_ptr<BatchSink>& sink) {
+  if (!d->pending.active) return CC_OK;
+  if (d->pending.sink == sink) return retire_pending(d);
+  retire_foreign(d);
+  return CC_OK;
+}
+
+// The streams, events and pinned counters of the pass loop, created by the first detection call.
+static cc_status ensure_pipeline_objects(cc_detector* d) {
+  if (d->copy_stream) return CC_OK;
+  CC_HIP(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
+  CC_HIP(hipEventCreateWithFlags(&d->pass_done[0], hipEventDisableTiming));
+  CC_HIP(hipEventCreateWithFlags(&d->pass_done[1], hipEventDisableTiming));
+  CC_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_counts), 4 * sizeof(int), hipHostMallocDefault));
+  {  // the pyramid / integral stream only fills what the cascade kernel leaves idle: lowest priority
+    int least = 0, greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+    CC_HIP(hipStreamCreateWithPriority(&d->front_stream, hipStreamNonBlocking, least));
+  }
+  for (hipEvent_t* e : {&d->front_done[0], &d->front_done[1], &d->eval_done[0], &d->eval_done[1], &d->batch_begin})
+    CC_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  d->overlap_front = std::getenv("CCAMD_NO_FRONT_OVERLAP") ? 0 : 1;
+  return CC_OK;
+}
+
+// Single host image: one pass on one stream, replayed from a hipGraph once the buffers are sized. Hands the candidates to
+// `sink` and sets `delivered`, or leaves it false when the candidate lists overflowed: the ordinary path then grows the
+// lists and redoes the pass.
+static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* frames, int width, int height, size_t row_stride, int fmt,
+                                        BatchSink& sink, bool* delivered) {
+  *delivered = false;
+  const size_t rs = (size_t)align_up(width, 4), fs = rs * (size_t)height;
+  const bool color = fmt != CC_PIX_GRAY8;
+  // colour: rows of width * bpp bytes (planar: 3 * height rows of width) at a pitch of their own
+  const int crows = pix_rows(fmt, height);
+  const size_t cw = (size_t)width * pix_bytes(fmt), cpitch = (size_t)align_up((int)cw, 4), cfs = cpitch * (size_t)crows;
+  uint8_t*& hbuf = color ? d->h_color_frame : d->h_frame;
+  size_t& hbytes = color ? d->h_color_frame_bytes : d->h_frame_bytes;
+  const size_t hneed = color ? cfs : fs;
+  if (hbytes < hneed) {
+    if (hbuf) (void)hipHostFree(hbuf);
+    hbuf = nullptr;
+    hbytes = 0;
+    CC_HIP(hipHostMalloc(reinterpret_cast<void**>(&hbuf), hneed, hipHostMallocDefault));
+    hbytes = hneed;
+  }
+  if (color)
+    for (int y = 0; y < crows; y++) std::memcpy(hbuf + (size_t)y * cpitch, frames + (size_t)y * row_stride, cw);
+  else
+    for (int y = 0; y < height; y++) std::memcpy(d->h_frame + (size_t)y * rs, frames + (size_t)y * row_stride, (size_t)width);
+  CC_HIP(d->d_frames.ensure(fs * (size_t)d->pass_capacity * 2));
+  if (color) {
+    if (d->d_color.n < cfs && d->d_color.p && d->front_stream) CC_HIP(hipStreamSynchronize(d->front_stream));  // batch conversions
+    CC_HIP(d->d_color.ensure(cfs));
+  }
+  auto body = [&]() -> cc_status {
+    if (color) {
+      CC_HIP(hipMemcpyAsync(d->d_color.p, d->h_color_frame, cfs, hipMemcpyHostToDevice, d->stream));
+      launch_to_gray(d->stream, fmt, d->d_color.p, cpitch, cfs, width, height, 1, d->d_frames.p, rs, fs);
+    } else
+      CC_HIP(hipMemcpyAsync(d->d_frames.p, d->h_frame, fs, hipMemcpyHostToDevice, d->stream));
+    cc_status s2 = run_device_pass(d, P, d->d_frames.p, 1, rs, fs, false, 0, true);
+    if (s2 != CC_OK) return s2;
+    CC_HIP(hipMemcpyAsync(d->h_counts, d->d_counts[0].p, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    return CC_OK;
+  };
+  auto key_now = [&]() {
+    return std::vector<const void*>{d->d_frames.p, hbuf, color ? d->d_color.p : nullptr, d->d_pyr.p, d->d_integ[0].p, d->d_hbuf.p, d->d_diag.p, d->d_tseg.p, d->d_masks[0].p, d->d_cands[0].p,
+                                    d->d_out[0].p, d->d_counts[0].p, d->h_counts, (const void*)d->spec[0].fn, (const void*)d->spec[1].fn, (const void*)d->stream,
+                                    (const void*)(size_t)d->cand_cap, (const void*)(size_t)d->wave_below, (const void*)(size_t)(d->stop_after + 16)};
+  };
+  if (d->eval_pending[0] || d->eval_pending[1]) {  // a batch call may still be using the buffers on the other stream
+    CC_HIP(hipStreamSynchronize(d->front_stream));
+    d->eval_pending[0] = d->eval_pending[1] = false;
+  }
+  bool launched = false;
+  d->last_call_graph = 0;
+  hipGraphExec_t& gexec = P->graph_exec[fmt];
+  if (gexec && P->graph_key[fmt] == key_now()) {
+    CC_HIP(hipGraphLaunch(gexec, d->stream));
+    launched = true;
+    d->last_call_graph = 1;
+  } else if (P->graph_warm[fmt]) {
+    if (gexec) (void)hipGraphExecDestroy(gexec);
+    gexec = nullptr;
+    hipGraph_t graph = nullptr;
+    // Relaxed mode: this thread's stream-ordered calls are captured, nobody's legacy-stream calls are policed (other
+    // host threads may be inside synchronous copies of their own handles; under the stricter modes HIP fails those
+    // calls and invalidates this capture). One capture at a time per process; if a capture does not come out, the
+    // detector simply stops using graphs.
+    static std::mutex capture_mu;
+    hipError_t ce = hipSuccess, ie = hipSuccess;
+    cc_status s2 = CC_OK;
+    {
+      std::lock_guard<std::mutex> capture_lock(capture_mu);
+      ce = std::getenv("CCAMD_DEBUG_FAIL_CAPTURE") ? hipErrorStreamCaptureUnsupported  // tests: the fallback path
+                                                   : hipStreamBeginCapture(d->stream, hipStreamCaptureModeRelaxed);
+      if (ce == hipSuccess) {
+        s2 = body();
+        ce = hipStreamEndCapture(d->stream, &graph);
+      }
+    }
+    if (ce == hipSuccess && s2 == CC_OK && graph) ie = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (ce != hipSuccess || s2 != CC_OK || ie != hipSuccess || !gexec) {
+      // said once per detector, on stderr: the call still succeeds, only the launch-bound single-image path gets slower
+      std::fprintf(stderr, "[ccamd] hipGraph capture of the single-image pass failed (begin/end: %s, body status %d, instantiate: %s): "
+                           "this detector uses ordinary launches from now on\n",
+                   hipGetErrorString(ce), (int)s2, hipGetErrorString(ie));
+      (void)hipGetLastError();
+      gexec = nullptr;
+      d->use_graph = 0;  // ordinary launches from now on (this call included)
+    } else {
+      P->graph_key[fmt] = key_now();
+      d->graph_captures++;
+      CC_HIP(hipGraphLaunch(gexec, d->stream));
+      launched = true;
+      d->last_call_graph = 1;
+    }
+  }
+  if (!launched) {
+    const cc_status stt = body();
+    if (stt != CC_OK) return stt;
+    P->graph_warm[fmt] = true;  // every buffer now has its size: the next call can be captured
+  }
+  CC_HIP(hipStreamSynchronize(d->stream));
+  const int raw = d->h_counts[0], kept = d->h_counts[1];
+  if (raw <= d->cand_cap) {
+    std::vector<CandOut> got((size_t)kept);
+    if (kept > 0) {
+      CC_HIP(hipMemcpyAsync(got.data(), d->d_out[0].p, (size_t)kept * sizeof(CandOut), hipMemcpyDeviceToHost, d->stream));
+      CC_HIP(hipStreamSynchronize(d->stream));
+    }
+    sink.consume(0, 1, got);
+    *delivered = true;
+  }
+  return CC_OK;
+}
+
+// Stages frames [pf0, pf0 + pnf) of the batch (host frames, or colour frames wherever they are) into the next staging slot,
+// on `front`; `where` receives the slot's gray frames. `sink`: the calling batch's, for a pending pass that must go first.
+// Host frames: THREE staging slots (device and pinned), handed out round-robin across passes and calls. The frames of
+// pass i + 1 are staged and their copy issued right after pass i is launched and BEFORE the pass before it is fetched
+// (a blocking wait), so the host copy and the H2D transfer of a pass run a whole pass ahead of the kernels that read
+// them. Two slots are not enough for that: the slot of pass i + 1 would be the one of pass i - 1, which is still
+// unfetched at that point and re-reads its frames if it has to be redone (candidate-list overflow). With three, the slot
+// that is overwritten belongs to pass i - 2, fetched when pass i - 1 was launched.
+// Colour frames take the same slots: k_to_gray writes the pass's gray frames there (from the caller's device buffer, or from
+// d_color, where stage_host_frames has put host frames), so a redone pass re-reads gray frames like any other. The rule holds
+// only while every pass uses the same slot pitch: the device slots are gray frames of the plan (a pending pass of another
+// plan is retired first), the pinned slots have one pitch for every format (stage_host_frames).
+static cc_status stage_pass(cc_detector* d, const std::shared_ptr<BatchSink>& sink, const uint8_t* frames, int on_device, int width, int height,
+                            size_t row_stride, size_t frame_stride, int fmt, hipStream_t front, int pf0, int pnf, const uint8_t** where) {
+  const size_t rs = (size_t)align_up(width, 4), fs = rs * (size_t)height;
+  const size_t need = fs * (size_t)d->pass_capacity * kStageSlots;
+  if (d->d_frames.n < need && d->pending.active) {
+    // Growing the staging area frees it, and the unfetched pass still names its frames there (round-3 advisor finding).
+    const cc_status st2 = retire_for(d, sink);
+    if (st2 != CC_OK) return st2;
+  }
+  if (d->d_frames.n < need) d->stage_slot = 0;
+  CC_HIP(d->d_frames.ensure(need));
+  const int sslot = d->stage_slot;
+  d->stage_slot = (d->stage_slot + 1) % kStageSlots;
+  uint8_t* stage = d->d_frames.p + (size_t)sslot * fs * (size_t)d->pass_capacity;
+  if (fmt == CC_PIX_GRAY8) {
+    const cc_status st2 = stage_host_frames(d, frames + (size_t)pf0 * frame_stride, pnf, width, height, row_stride, frame_stride, stage, rs,
+                                            fs, sslot, front);
+    if (st2 != CC_OK) return st2;
+    *where = stage;
+    return CC_OK;
+  }
+  const uint8_t* csrc = frames + (size_t)pf0 * frame_stride;
+  size_t crs = row_stride, cfs = frame_stride;
+  if (!on_device) {  // the colour bytes travel as they are, like gray frames, into d_color
+    const int crows = pix_rows(fmt, height);
+    const size_t cw = (size_t)width * pix_bytes(fmt);
+    crs = (size_t)align_up((int)cw, 4);
+    cfs = crs * (size_t)crows;
+    const size_t cneed = cfs * (size_t)d->pass_capacity;
+    if (d->d_color.n < cneed && d->d_color.p) CC_HIP(hipStreamSynchronize(front));  // the last k_to_gray may still read it
+    CC_HIP(d->d_color.ensure(cneed));
+    const cc_status st2 = stage_host_frames(d, csrc, pnf, (int)cw, crows, row_stride, frame_stride, d->d_color.p, crs, cfs, sslot, front);
+    if (st2 != CC_OK) return st2;
+    csrc = d->d_color.p;
+  }
+  {
+    EvScope ev(d, EV_RESIZE, front);  // the conversion's time counts as pyramid time (include/cascadeclassifier_amd.h)
+    launch_to_gray(front, fmt, csrc, crs, cfs, width, height, pnf, stage, rs, fs);
+  }
+  CC_HIP(hipGetLastError());
+  *where = stage;
+  return CC_OK;
+}
+
 // Runs the batch in passes. `consume` (optional) receives the filtered candidates of each pass (frame indices made
 // global) on the calling thread. With two or more frames the batch is cut into at least two passes and the host side
 // of pass i (copy-back + consume) overlaps the device side of pass i+1.
@@ -963,14 +1182,13 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     sink = std::make_shared<BatchSink>();
     sink->consume = consume_fn;
   }
-  auto consume = [&](int f0_, int nf_, std::vector<CandOut>& c) { sink->consume(f0_, nf_, c); };
   // A pass of an earlier (submitted) batch may still be pending. It can stay so -- and overlap this call's first pass --
   // only if this call runs ordinary passes on the same plan; everything else fetches it first.
+  const bool single_image_graph = n_frames == 1 && !on_device && want_results && !debug && !d->profiling && d->use_graph;
   if (d->pending.active) {
     bool same_plan = false;
     for (auto& pl : d->plans)
       if (pl.get() == d->pending.plan && pl->w == width && pl->h == height && same_params(pl->p, *p)) same_plan = true;
-    const bool single_image_graph = n_frames == 1 && !on_device && want_results && !debug && !d->profiling && d->use_graph;
     if (!same_plan || debug || !want_results || single_image_graph || n_frames < 1) retire_foreign(d);  // (a new plan may evict the pending pass's)
   }
   spec_poll(d);
@@ -979,20 +1197,8 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
   if (stt != CC_OK) return stt;
   stt = ensure_spec_tiles(d, P);
   if (stt != CC_OK) return stt;
-  if (!d->copy_stream) {
-    CC_HIP(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
-    CC_HIP(hipEventCreateWithFlags(&d->pass_done[0], hipEventDisableTiming));
-    CC_HIP(hipEventCreateWithFlags(&d->pass_done[1], hipEventDisableTiming));
-    CC_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_counts), 4 * sizeof(int), hipHostMallocDefault));
-    {  // the pyramid / integral stream only fills what the cascade kernel leaves idle: lowest priority
-      int least = 0, greatest = 0;
-      (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-      CC_HIP(hipStreamCreateWithPriority(&d->front_stream, hipStreamNonBlocking, least));
-    }
-    for (hipEvent_t* e : {&d->front_done[0], &d->front_done[1], &d->eval_done[0], &d->eval_done[1], &d->batch_begin})
-      CC_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    d->overlap_front = std::getenv("CCAMD_NO_FRONT_OVERLAP") ? 0 : 1;
-  }
+  stt = ensure_pipeline_objects(d);
+  if (stt != CC_OK) return stt;
   hipStream_t front = d->overlap_front ? d->front_stream : d->stream;
   // Frames produced by earlier work on a stream the CALLER gave us (cc_detector_set_stream) must be complete before the
   // pyramid reads them. On the detector's own stream there is only our own earlier work -- a pending pass of the batch
@@ -1001,203 +1207,15 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     CC_HIP(hipEventRecord(d->batch_begin, d->stream));
     CC_HIP(hipStreamWaitEvent(front, d->batch_begin, 0));
   }
-  if (n_frames == 1 && !on_device && want_results && !debug && !d->profiling && d->use_graph) {
-    // ---- single host image: one pass on one stream, replayed from a hipGraph once the buffers are sized ----
-    const size_t rs = (size_t)align_up(width, 4), fs = rs * (size_t)height;
-    const bool color = fmt != CC_PIX_GRAY8;
-    // colour: rows of width * bpp bytes (planar: 3 * height rows of width) at a pitch of their own
-    const int crows = pix_rows(fmt, height);
-    const size_t cw = (size_t)width * pix_bytes(fmt), cpitch = (size_t)align_up((int)cw, 4), cfs = cpitch * (size_t)crows;
-    uint8_t*& hbuf = color ? d->h_color_frame : d->h_frame;
-    size_t& hbytes = color ? d->h_color_frame_bytes : d->h_frame_bytes;
-    const size_t hneed = color ? cfs : fs;
-    if (hbytes < hneed) {
-      if (hbuf) (void)hipHostFree(hbuf);
-      hbuf = nullptr;
-      hbytes = 0;
-      CC_HIP(hipHostMalloc(reinterpret_cast<void**>(&hbuf), hneed, hipHostMallocDefault));
-      hbytes = hneed;
-    }
-    if (color)
-      for (int y = 0; y < crows; y++) std::memcpy(hbuf + (size_t)y * cpitch, frames + (size_t)y * row_stride, cw);
-    else
-      for (int y = 0; y < height; y++) std::memcpy(d->h_frame + (size_t)y * rs, frames + (size_t)y * row_stride, (size_t)width);
-    CC_HIP(d->d_frames.ensure(fs * (size_t)d->pass_capacity * 2));
-    if (color) {
-      if (d->d_color.n < cfs && d->d_color.p && d->front_stream) CC_HIP(hipStreamSynchronize(d->front_stream));  // batch conversions
-      CC_HIP(d->d_color.ensure(cfs));
-    }
-    auto body = [&]() -> cc_status {
-      if (color) {
-        CC_HIP(hipMemcpyAsync(d->d_color.p, d->h_color_frame, cfs, hipMemcpyHostToDevice, d->stream));
-        launch_to_gray(d->stream, fmt, d->d_color.p, cpitch, cfs, width, height, 1, d->d_frames.p, rs, fs);
-      } else
-        CC_HIP(hipMemcpyAsync(d->d_frames.p, d->h_frame, fs, hipMemcpyHostToDevice, d->stream));
-      cc_status s2 = run_device_pass(d, P, d->d_frames.p, 1, rs, fs, false, 0, true);
-      if (s2 != CC_OK) return s2;
-      CC_HIP(hipMemcpyAsync(d->h_counts, d->d_counts[0].p, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-      return CC_OK;
-    };
-    auto key_now = [&]() {
-      return std::vector<const void*>{d->d_frames.p, hbuf, color ? d->d_color.p : nullptr, d->d_pyr.p, d->d_integ[0].p, d->d_hbuf.p, d->d_diag.p, d->d_tseg.p, d->d_masks[0].p, d->d_cands[0].p,
-                                      d->d_out[0].p, d->d_counts[0].p, d->h_counts, (const void*)d->spec_fn, (const void*)d->spec_fn1, (const void*)d->stream,
-                                      (const void*)(size_t)d->cand_cap, (const void*)(size_t)d->wave_below, (const void*)(size_t)(d->stop_after + 16)};
-    };
-    if (d->eval_pending[0] || d->eval_pending[1]) {  // a batch call may still be using the buffers on the other stream
-      CC_HIP(hipStreamSynchronize(d->front_stream));
-      d->eval_pending[0] = d->eval_pending[1] = false;
-    }
-    bool launched = false;
-    d->last_call_graph = 0;
-    hipGraphExec_t& gexec = P->graph_exec[fmt];
-    if (gexec && P->graph_key[fmt] == key_now()) {
-      CC_HIP(hipGraphLaunch(gexec, d->stream));
-      launched = true;
-      d->last_call_graph = 1;
-    } else if (P->graph_warm[fmt]) {
-      if (gexec) (void)hipGraphExecDestroy(gexec);
-      gexec = nullptr;
-      hipGraph_t graph = nullptr;
-      // Relaxed mode: this thread's stream-ordered calls are captured, nobody's legacy-stream calls are policed (other
-      // host threads may be inside synchronous copies of their own handles; under the stricter modes HIP fails those
-      // calls and invalidates this capture). One capture at a time per process; if a capture does not come out, the
-      // detector simply stops using graphs.
-      static std::mutex capture_mu;
-      hipError_t ce = hipSuccess, ie = hipSuccess;
-      cc_status s2 = CC_OK;
-      {
-        std::lock_guard<std::mutex> capture_lock(capture_mu);
-        ce = std::getenv("CCAMD_DEBUG_FAIL_CAPTURE") ? hipErrorStreamCaptureUnsupported  // tests: the fallback path
-                                                     : hipStreamBeginCapture(d->stream, hipStreamCaptureModeRelaxed);
-        if (ce == hipSuccess) {
-          s2 = body();
-          ce = hipStreamEndCapture(d->stream, &graph);
-        }
-      }
-      if (ce == hipSuccess && s2 == CC_OK && graph) ie = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-      if (graph) (void)hipGraphDestroy(graph);
-      if (ce != hipSuccess || s2 != CC_OK || ie != hipSuccess || !gexec) {
-        // said once per detector, on stderr: the call still succeeds, only the launch-bound single-image path gets slower
-        std::fprintf(stderr, "[ccamd] hipGraph capture of the single-image pass failed (begin/end: %s, body status %d, instantiate: %s): "
-                             "this detector uses ordinary launches from now on\n",
-                     hipGetErrorString(ce), (int)s2, hipGetErrorString(ie));
-        (void)hipGetLastError();
-        gexec = nullptr;
-        d->use_graph = 0;  // ordinary launches from now on (this call included)
-      } else {
-        P->graph_key[fmt] = key_now();
-        d->graph_captures++;
-        CC_HIP(hipGraphLaunch(gexec, d->stream));
-        launched = true;
-        d->last_call_graph = 1;
-      }
-    }
-    if (!launched) {
-      stt = body();
-      if (stt != CC_OK) return stt;
-      P->graph_warm[fmt] = true;  // every buffer now has its size: the next call can be captured
-    }
-    CC_HIP(hipStreamSynchronize(d->stream));
-    const int raw = d->h_counts[0], kept = d->h_counts[1];
-    if (raw <= d->cand_cap) {
-      std::vector<CandOut> got((size_t)kept);
-      if (kept > 0) {
-        CC_HIP(hipMemcpyAsync(got.data(), d->d_out[0].p, (size_t)kept * sizeof(CandOut), hipMemcpyDeviceToHost, d->stream));
-        CC_HIP(hipStreamSynchronize(d->stream));
-      }
-      consume(0, 1, got);
-      return CC_OK;
-    }
-    // candidate list overflow: the ordinary path below grows the lists and redoes the pass
+  if (single_image_graph) {
+    bool delivered = false;
+    stt = run_single_image_graph(d, P, frames, width, height, row_stride, fmt, *sink, &delivered);
+    if (stt != CC_OK || delivered) return stt;
   }
-  // Pass sizes. With results wanted the batch is cut into a few passes so that the host side of pass i (copy-back +
-  // grouping) overlaps the device side of pass i+1 and the pyramid/integrals of pass i+1 overlap the cascade kernel of
-  // pass i. Nothing overlaps the LAST pass's host work, so it carries about half the frames of the others (32 frames ->
-  // 9, 9, 9, 5; a small first pass, to start the cascade kernel earlier, measured no better). A SUBMITTED batch has its last
-  // pass overlapped by the batch after it, so it is cut into two even passes only (bench step 17.51 ms against 17.86 / 18.25
-  // for 1 / 4 passes, profiles/r03_kernel_experiments.txt).
-  std::vector<int> sizes;
-  if (want_results && n_frames >= 2) {
-    const bool submitted = defer_last && !d->pipeline_passes_set;
-    const int passes = std::min(submitted ? 2 : d->pipeline_passes, n_frames);
-    int per = (n_frames + passes - 1) / passes;
-    if (passes >= 3 && !submitted) {
-      const int big = (2 * n_frames + 2 * passes - 2) / (2 * passes - 1);
-      if (big >= 2 && big * (passes - 1) < n_frames) per = big;
-    }
-    for (int f = 0; f < n_frames; f += per) sizes.push_back(std::min(per, n_frames - f));
-  } else {
-    for (int f = 0; f < n_frames; f += d->max_batch) sizes.push_back(std::min(d->max_batch, n_frames - f));
-  }
-  {  // normalise: sizes within max_batch, summing to n_frames (a batch of more than passes * max_batch frames is cut further)
-    std::vector<int> fixed;
-    int left = n_frames;
-    for (size_t i = 0; left > 0; i++) {
-      int v = i < sizes.size() ? sizes[i] : left;
-      v = std::max(1, std::min({v, d->max_batch, left}));
-      fixed.push_back(v);
-      left -= v;
-    }
-    sizes.swap(fixed);
-  }
+  const std::vector<int> sizes = pass_sizes(n_frames, d->max_batch, d->pipeline_passes, d->pipeline_passes_set != 0, want_results, defer_last);
   for (int v : sizes) d->pass_capacity = std::max(d->pass_capacity, v);  // the workspace only ever grows
-  // Host frames: THREE staging slots (device and pinned), handed out round-robin across passes and calls. The frames of
-  // pass i + 1 are staged and their copy issued right after pass i is launched and BEFORE the pass before it is fetched
-  // (a blocking wait), so the host copy and the H2D transfer of a pass run a whole pass ahead of the kernels that read
-  // them. Two slots are not enough for that: the slot of pass i + 1 would be the one of pass i - 1, which is still
-  // unfetched at that point and re-reads its frames if it has to be redone (candidate-list overflow). With three, the slot
-  // that is overwritten belongs to pass i - 2, fetched when pass i - 1 was launched.
-  // Colour frames take the same slots: k_to_gray writes the pass's gray frames there (from the caller's device buffer, or from
-  // d_color, where stage_host_frames has put host frames), so a redone pass re-reads gray frames like any other. The rule holds
-  // only while every pass uses the same slot pitch: the device slots are gray frames of the plan (a pending pass of another
-  // plan is retired first), the pinned slots have one pitch for every format (stage_host_frames).
   const bool staged = !on_device || fmt != CC_PIX_GRAY8;
   const uint8_t* prestaged = nullptr;
-  auto stage_pass = [&](int pf0, int pnf, const uint8_t** where) -> cc_status {
-    const size_t rs = (size_t)align_up(width, 4), fs = rs * (size_t)height;
-    const size_t need = fs * (size_t)d->pass_capacity * kStageSlots;
-    if (d->d_frames.n < need && d->pending.active) {
-      // Growing the staging area frees it, and the unfetched pass still names its frames there (round-3 advisor finding).
-      if (d->pending.sink == sink) {
-        const cc_status st2 = retire_pending(d);
-        if (st2 != CC_OK) return st2;
-      } else
-        retire_foreign(d);
-    }
-    if (d->d_frames.n < need) d->stage_slot = 0;
-    CC_HIP(d->d_frames.ensure(need));
-    const int sslot = d->stage_slot;
-    d->stage_slot = (d->stage_slot + 1) % kStageSlots;
-    uint8_t* stage = d->d_frames.p + (size_t)sslot * fs * (size_t)d->pass_capacity;
-    if (fmt == CC_PIX_GRAY8) {
-      const cc_status st2 = stage_host_frames(d, frames + (size_t)pf0 * frame_stride, pnf, width, height, row_stride, frame_stride, stage, rs,
-                                              fs, sslot, front);
-      if (st2 != CC_OK) return st2;
-      *where = stage;
-      return CC_OK;
-    }
-    const uint8_t* csrc = frames + (size_t)pf0 * frame_stride;
-    size_t crs = row_stride, cfs = frame_stride;
-    if (!on_device) {  // the colour bytes travel as they are, like gray frames, into d_color
-      const int crows = pix_rows(fmt, height);
-      const size_t cw = (size_t)width * pix_bytes(fmt);
-      crs = (size_t)align_up((int)cw, 4);
-      cfs = crs * (size_t)crows;
-      const size_t cneed = cfs * (size_t)d->pass_capacity;
-      if (d->d_color.n < cneed && d->d_color.p) CC_HIP(hipStreamSynchronize(front));  // the last k_to_gray may still read it
-      CC_HIP(d->d_color.ensure(cneed));
-      const cc_status st2 = stage_host_frames(d, csrc, pnf, (int)cw, crows, row_stride, frame_stride, d->d_color.p, crs, cfs, sslot, front);
-      if (st2 != CC_OK) return st2;
-      csrc = d->d_color.p;
-    }
-    {
-      EvScope ev(d, EV_RESIZE, front);  // the conversion's time counts as pyramid time (include/cascadeclassifier_amd.h)
-      launch_to_gray(front, fmt, csrc, crs, cfs, width, height, pnf, stage, rs, fs);
-    }
-    CC_HIP(hipGetLastError());
-    *where = stage;
-    return CC_OK;
-  };
   // spec_poll may have installed another kernel: a pending pass keeps the results it was launched for, nothing to redo.
   int f0 = 0;
   for (size_t pi = 0; pi < sizes.size(); f0 += sizes[pi], pi++) {
@@ -1217,7 +1235,7 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
       ps.rs = (size_t)align_up(width, 4);
       ps.fs = ps.rs * (size_t)height;
       if (!prestaged) {
-        stt = stage_pass(f0, sizes[pi], &prestaged);
+        stt = stage_pass(d, sink, frames, on_device, width, height, row_stride, frame_stride, fmt, front, f0, sizes[pi], &prestaged);
         if (stt != CC_OK) return stt;
       }
       ps.dptr = prestaged;
@@ -1236,7 +1254,8 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     ps.cap = d->cand_cap;
     ps.gen = d->list_gen;
     if (staged && pi + 1 < sizes.size() && want_results) {  // the next pass's frames travel while this pass runs
-      stt = stage_pass(f0 + sizes[pi], sizes[pi + 1], &prestaged);
+      stt = stage_pass(d, sink, frames, on_device, width, height, row_stride, frame_stride, fmt, front, f0 + sizes[pi], sizes[pi + 1],
+                       &prestaged);
       if (stt != CC_OK) return stt;
       th("next pass staged");
     }
@@ -1245,25 +1264,17 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
       CC_HIP(hipEventRecord(d->pass_done[slot], d->stream));
       // fetch the pass launched before this one -- of this batch or, for the first pass, of the batch submitted before --
       // while the device runs this one
-      if (d->pending.active) {
-        if (d->pending.sink == sink) {
-          stt = retire_pending(d);
-          if (stt != CC_OK) return stt;
-        } else
-          retire_foreign(d);
-      }
+      stt = retire_for(d, sink);
+      if (stt != CC_OK) return stt;
       th("previous retired");
       ps.active = true;
       d->pending = ps;
     }
     d->next_slot ^= 1;
   }
-  if (d->pending.active && !(defer_last && d->pending.sink == sink)) {
-    if (d->pending.sink == sink) {
-      stt = retire_pending(d);
-      if (stt != CC_OK) return stt;
-    } else
-      retire_foreign(d);
+  if (!(defer_last && d->pending.sink == sink)) {
+    stt = retire_for(d, sink);
+    if (stt != CC_OK) return stt;
   }
   // Profiling: the event pairs of this call are read once their kernels are done. A submitted batch must not wait for that
   // here (the synchronisation would undo the overlap with the next batch -- which is how the round-3 bench first measured
@@ -1310,84 +1321,16 @@ static void group_pass(int min_neighbors, int f0, int nf, std::vector<CandOut>& 
   }
 }
 
-// Device half: load the code object and make it the detector's cascade kernel. Owning thread only.
+// Switches the detector over to the compiled modules (spec_load is the device half). Owning thread only.
 static cc_status spec_install(cc_detector* d, const std::vector<SpecCode>& codes, int k, int tmode) {
-  if (codes.empty() || codes.size() > 2) return set_error(CC_ERR_HIP, "cc_detector_specialize: %zu modules", codes.size());
   retire_foreign(d);  // a pass still unfetched was launched with the old kernel (and its tile lists): fetch it before the switch
-  const bool haar_k = d->m.feature_type == CC_FEATURE_HAAR;
-  struct Loaded {
-    hipModule_t mod = nullptr;
-    hipFunction_t fn = nullptr;
-    size_t lds = 0;
-    int tile_y = TILE_Y, only_step = 0;
-  };
-  std::vector<Loaded> L;
-  auto unload_all = [&]() {
-    for (Loaded& x : L)
-      if (x.mod) (void)hipModuleUnload(x.mod);
-  };
-  for (const SpecCode& c : codes) {
-    Loaded x;
-    x.tile_y = c.tile_y;
-    x.only_step = c.only_step;
-    const char* entry = c.only_step == 1 ? "k_eval_spec_step1" : c.only_step == 2 ? "k_eval_spec_step2" : "k_eval_spec";
-    if (hipModuleLoadData(&x.mod, c.code.data()) != hipSuccess || hipModuleGetFunction(&x.fn, x.mod, entry) != hipSuccess) {
-      (void)hipGetLastError();
-      if (x.mod) (void)hipModuleUnload(x.mod);
-      unload_all();
-      return set_error(CC_ERR_HIP, "cc_detector_specialize: the compiled module does not load or has no entry point");
-    }
-    const int ty = c.tile_y;
-    const int step = c.only_step;  // tiles this module stages: of the step(s) it covers
-    x.lds = d->lds;
-    if (tmode == TILE_32) {
-      const TileGeom<1> G1(d->m.win_w, d->m.win_h, ty);
-      const TileGeom<2> G2(d->m.win_w, d->m.win_h, ty);
-      const int words = step == 1 ? G1.words() : step == 2 ? G2.words() : std::max(G1.words(), G2.words());
-      x.lds = eval_lds_bytes(words, d->m.has_tilted, haar_k, ty);
-    } else if (tmode == TILE_16) {  // STEP-1 tile in 32 bits, STEP-2 tile in 16 bits
-      const TileGeom<1> G1(d->m.win_w, d->m.win_h, ty);
-      const TileGeom16 G2(d->m.win_w, d->m.win_h, ty);
-      x.lds = eval_lds_bytes(std::max(G1.words(), G2.words()), false, haar_k, ty);
-    }
-    if (x.lds > 64 * 1024) {  // same opt-in as the ahead-of-time kernels (cc_detector_create)
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(x.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipModuleUnload(x.mod);
-        unload_all();
-        return set_error(CC_ERR_UNSUPPORTED, "cc_detector_specialize: %zu bytes of LDS per tile cannot be requested for a run-time module (%s)",
-                         x.lds, hipGetErrorString(e));
-      }
-    }
-    if (std::getenv("CCAMD_TRACE_HOST")) {  // what the specialised kernel's footprint allows per CU
-      int nb = 0;
-      if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, x.fn, EVAL_THREADS, x.lds) != hipSuccess) (void)hipGetLastError();
-      std::fprintf(stderr, "[ccamd host] specialised kernel: tile mode %d, tiles of step %d (0 = all), %d window rows, %zu bytes of LDS per block, %d resident blocks per CU\n",
-                   tmode, c.only_step, ty, x.lds, nb);
-    }
-    L.push_back(x);
-  }
-  CC_HIP(hipStreamSynchronize(d->stream));
-  if (d->spec_mod) (void)hipModuleUnload(d->spec_mod);
-  if (d->spec_mod1) (void)hipModuleUnload(d->spec_mod1);
-  d->spec_mod1 = nullptr;
-  d->spec_fn1 = nullptr;
-  // the module for all tiles or for the STEP-2 tiles is the primary one; a STEP-1 module, if any, the second
-  const Loaded* prim = &L[0];
-  const Loaded* sec = L.size() > 1 ? &L[1] : nullptr;
-  if (sec && prim->only_step == 1) std::swap(prim, sec);
-  d->spec_mod = prim->mod;
-  d->spec_fn = prim->fn;
-  d->lds_spec = prim->lds;
-  d->spec_tile_y = prim->tile_y;
-  d->spec_only_step = prim->only_step;
-  if (sec) {
-    d->spec_mod1 = sec->mod;
-    d->spec_fn1 = sec->fn;
-    d->lds_spec1 = sec->lds;
-    d->spec_tile_y1 = sec->tile_y;
-  }
+  CC_HIP(hipStreamSynchronize(d->stream));  // no launch of the old modules is in flight any more
+  SpecModule fresh[2];
+  int n_fresh = 0;
+  if (cc_status st = spec_load(d->m, codes, tmode, d->lds, fresh, &n_fresh); st != CC_OK) return st;  // the old kernel stays
+  d->unload_spec();
+  for (int i = 0; i < n_fresh; i++) d->spec[i] = fresh[i];
+  d->n_spec = n_fresh;
   d->spec_stages = k;
   return CC_OK;
 }
@@ -1500,6 +1443,70 @@ static unsigned long long detector_registry(int op, unsigned long long serial) {
   return live.count(serial) ? 1 : 0;
 }
 
+// The cascade's tree / stump records in the layouts the kernels read (one table per tile layout), built and uploaded on the
+// detector's stream. Every branch ends synchronised: its host vectors go out of scope.
+static cc_status upload_cascade_tables(cc_detector* d) {
+  const bool haar = d->m.feature_type == CC_FEATURE_HAAR;
+  const bool trees = d->m.max_nodes_per_tree > 1;
+  if (trees) {
+    std::vector<int> root(d->m.tree_first_node.begin(), d->m.tree_first_node.end()), leaf0(d->m.tree_first_leaf.begin(), d->m.tree_first_leaf.end());
+    CC_HIP(d->d_tree_root.upload(root, d->stream));
+    CC_HIP(d->d_tree_leaf0.upload(leaf0, d->stream));
+    CC_HIP(d->d_leaves.upload(d->m.leaves, d->stream));
+    if (haar) {
+      std::vector<HaarNodeDev> n1, n2;
+      build_haar_nodes<1>(d->m, n1);
+      build_haar_nodes<2>(d->m, n2);
+      CC_HIP(d->d_hnode1.upload(n1, d->stream));
+      CC_HIP(d->d_hnode2.upload(n2, d->stream));
+      CC_HIP(hipStreamSynchronize(d->stream));
+    } else {
+      std::vector<LbpNodeDev> n1, n2;
+      build_lbp_nodes<1>(d->m, n1);
+      build_lbp_nodes<2>(d->m, n2);
+      CC_HIP(d->d_lnode1.upload(n1, d->stream));
+      CC_HIP(d->d_lnode2.upload(n2, d->stream));
+      CC_HIP(hipStreamSynchronize(d->stream));
+    }
+  } else if (haar) {
+    std::vector<HaarStumpDev> s1, s2;
+    build_haar_stumps<1>(d->m, s1);
+    build_haar_stumps<2>(d->m, s2);
+    CC_HIP(d->d_haar1.upload(s1, d->stream));
+    CC_HIP(d->d_haar2.upload(s2, d->stream));
+    std::vector<HaarStumpDev> sg;
+    if (!d->m.has_tilted) build_haar_gstumps(d->m, sg);
+    CC_HIP(d->d_haar_g.upload(sg, d->stream));
+    CC_HIP(hipStreamSynchronize(d->stream));
+    if (d->wave_below > 0) {
+      const std::vector<HaarStumpDev> w1 = schedule_for_wave_phase(d->m, s1), w2 = schedule_for_wave_phase(d->m, s2);
+      CC_HIP(d->d_haar1w.upload(w1, d->stream));
+      CC_HIP(d->d_haar2w.upload(w2, d->stream));
+      CC_HIP(hipStreamSynchronize(d->stream));
+    }
+  } else {
+    std::vector<LbpStumpDev> s1, s2;
+    build_lbp_stumps<1>(d->m, s1);
+    build_lbp_stumps<2>(d->m, s2);
+    CC_HIP(d->d_lbp1.upload(s1, d->stream));
+    CC_HIP(d->d_lbp2.upload(s2, d->stream));
+    std::vector<LbpStumpDev> sg, s16;
+    build_lbp_gstumps(d->m, sg);
+    CC_HIP(d->d_lbp_g.upload(sg, d->stream));
+    d->lbp16_all = 1;
+    for (size_t i = 0; i < d->m.stump_feature.size(); i++) {
+      const int32_t* r = &d->m.lbp_rects[(size_t)d->m.stump_feature[i] * 4];
+      if (!fits16((long long)r[2] * r[3])) d->lbp16_all = 0;
+    }
+    if (d->lbp16_all) {
+      build_lbp_stumps16(d->m, s16);
+      CC_HIP(d->d_lbp16.upload(s16, d->stream));
+    }
+    CC_HIP(hipStreamSynchronize(d->stream));
+  }
+  return CC_OK;
+}
+
 cc_status cc_detector_create(const cc_cascade* c, int device, int max_batch, cc_detector** out) {
   if (!c || !out) return set_error(CC_ERR_INVALID_ARG, "cc_detector_create: null argument");
   *out = nullptr;
@@ -1560,108 +1567,22 @@ cc_status cc_detector_create(const cc_cascade* c, int device, int max_batch, cc_
     if (d->wave_below) d->wave_below = std::max(0, std::min(64, std::atoi(e)));  // the wave phase holds one window per lane
   CC_HIP(d->d_stage_thr.upload(d->m.stage_threshold, d->stream));
   {
-    // Stage groups (EvalArgs::group_first). Every stage boundary inside the cascade kernel costs the block a barrier, the
-    // class counts and a queue rebuild -- about as much as a pass over 25 stumps -- while what it buys is that the windows
-    // rejected by the stage stop occupying lanes. For short stages (the stock LBP cascade has 3-10 stumps per stage) the
-    // boundary costs more than it saves, so consecutive stages are put into one group while the group stays within
-    // `budget` stumps; a stage longer than the budget is a group of its own (the form every stage had before). Grouping
-    // never changes a result: a window's exit stage and stage sum are recorded where it fails, whatever the lanes around
-    // it do. Cascades with deeper trees keep one stage per group.
-    // Measured (round 3, stock LBP cascade, ms per 32 Full-HD frames alone on the device; tools/sweeps/r3_*.txt): grouping
-    // from stage 1 on is slower at every budget but 12 stumps (-3 %), because the lanes of windows that died inside a
-    // group keep executing; the gain is in the LATE stages, where a handful of windows per tile pay a barrier round per
-    // stage. Hence two knobs: groups start at stage `from`, and hold up to `budget` stumps.
+    // Stage groups and queue form (stage_groups, where the numbers behind the defaults are): LBP stump cascades group their
+    // short stages from stage 2 on, up to 14 stumps, and switch to the list queue there; everything else keeps one stage per
+    // group and the bank-class table.
     const bool lbp = !haar && !trees;
-    // LBP with its wave phase (which takes over below 24 windows), round 3 (tiles of 8 rows, bank-class table): groups of
-    // <= 20 stumps from stage 2 on 4.91-5.06, 12 from stage 1: 5.04-5.25, one stage per group 5.29, 30 from stage 2: 5.36.
-    // Round 4 (list queue from stage 2; specialised kernel on tiles of 20 rows): <= 14 stumps 3.70, <= 20 3.87, <= 30 4.17;
-    // at 8 rows 4.84 / 4.87 / 5.13.
     int budget = lbp ? 14 : 0;
     const int from = lbp ? 2 : 1;
     if (const char* e = std::getenv("CCAMD_GROUP_STUMPS")) budget = trees ? 0 : std::max(0, std::atoi(e));  // tuning
-    std::vector<int> gf;
-    const int nst = (int)d->m.stage_ntrees.size();
-    for (int s0 = 0; s0 < nst;) {
-      gf.push_back(s0);
-      const int cap = s0 < from ? 0 : budget;  // stage 0 is the dense phase: always alone
-      int s1 = s0 + 1, sum = d->m.stage_ntrees[(size_t)s0];
-      while (s1 < nst && sum + d->m.stage_ntrees[(size_t)s1] <= cap) sum += d->m.stage_ntrees[(size_t)s1++];
-      s0 = s1;
-    }
-    gf.push_back(nst);
-    if (gf.size() < 2) gf.push_back(nst);  // no stage at all: one empty group, the kernels read group_first[1]
-    d->n_groups = (int)gf.size() - 1;
-    // Queue form (EvalArgs::dense_from): LBP stump cascades switch from the bank-class table to a plain list at stage 2.
-    // There the tile is down to ~100 of its 512 windows: the table needs 6.2 rows for them (its fullest class) where a list
-    // needs 3.1, i.e. four wavefront passes over the group's 19 stumps instead of two, and the LBP kernel is bound by the
-    // vector ALU (73 % busy; LDS 52 %, profiles/r04_pmc_eval_lbp.json), not by the ~2.5-way bank conflicts the list costs.
-    // Haar cascades keep the table everywhere (LDS-bound; CCAMD_DENSE_FROM=<stage> to experiment).
     int dense_stage = lbp ? 2 : -1;
     if (const char* e = std::getenv("CCAMD_DENSE_FROM")) dense_stage = std::atoi(e);
-    d->dense_from = 0x7fffffff;
-    if (dense_stage >= 1)
-      for (int g = (int)gf.size() - 2; g >= 1; g--)
-        if (gf[(size_t)g] >= dense_stage) d->dense_from = g;
+    std::vector<int> gf;
+    stage_groups(d->m.stage_ntrees, from, budget, dense_stage, gf, d->dense_from);
+    d->n_groups = (int)gf.size() - 1;
     CC_HIP(d->d_group_first.upload(gf, d->stream));
     CC_HIP(hipStreamSynchronize(d->stream));
   }
-  if (trees) {
-    std::vector<int> root(d->m.tree_first_node.begin(), d->m.tree_first_node.end()), leaf0(d->m.tree_first_leaf.begin(), d->m.tree_first_leaf.end());
-    CC_HIP(d->d_tree_root.upload(root, d->stream));
-    CC_HIP(d->d_tree_leaf0.upload(leaf0, d->stream));
-    CC_HIP(d->d_leaves.upload(d->m.leaves, d->stream));
-    if (haar) {
-      std::vector<HaarNodeDev> n1, n2;
-      build_haar_nodes<1>(d->m, n1);
-      build_haar_nodes<2>(d->m, n2);
-      CC_HIP(d->d_hnode1.upload(n1, d->stream));
-      CC_HIP(d->d_hnode2.upload(n2, d->stream));
-      CC_HIP(hipStreamSynchronize(d->stream));
-    } else {
-      std::vector<LbpNodeDev> n1, n2;
-      build_lbp_nodes<1>(d->m, n1);
-      build_lbp_nodes<2>(d->m, n2);
-      CC_HIP(d->d_lnode1.upload(n1, d->stream));
-      CC_HIP(d->d_lnode2.upload(n2, d->stream));
-      CC_HIP(hipStreamSynchronize(d->stream));
-    }
-  } else if (haar) {
-    std::vector<HaarStumpDev> s1, s2;
-    build_haar_stumps<1>(d->m, s1);
-    build_haar_stumps<2>(d->m, s2);
-    CC_HIP(d->d_haar1.upload(s1, d->stream));
-    CC_HIP(d->d_haar2.upload(s2, d->stream));
-    std::vector<HaarStumpDev> sg;
-    if (!d->m.has_tilted) build_haar_gstumps(d->m, sg);
-    CC_HIP(d->d_haar_g.upload(sg, d->stream));
-    CC_HIP(hipStreamSynchronize(d->stream));
-    if (d->wave_below > 0) {
-      const std::vector<HaarStumpDev> w1 = schedule_for_wave_phase(d->m, s1), w2 = schedule_for_wave_phase(d->m, s2);
-      CC_HIP(d->d_haar1w.upload(w1, d->stream));
-      CC_HIP(d->d_haar2w.upload(w2, d->stream));
-      CC_HIP(hipStreamSynchronize(d->stream));
-    }
-    CC_HIP(hipStreamSynchronize(d->stream));
-  } else {
-    std::vector<LbpStumpDev> s1, s2;
-    build_lbp_stumps<1>(d->m, s1);
-    build_lbp_stumps<2>(d->m, s2);
-    CC_HIP(d->d_lbp1.upload(s1, d->stream));
-    CC_HIP(d->d_lbp2.upload(s2, d->stream));
-    std::vector<LbpStumpDev> sg, s16;
-    build_lbp_gstumps(d->m, sg);
-    CC_HIP(d->d_lbp_g.upload(sg, d->stream));
-    d->lbp16_all = 1;
-    for (size_t i = 0; i < d->m.stump_feature.size(); i++) {
-      const int32_t* r = &d->m.lbp_rects[(size_t)d->m.stump_feature[i] * 4];
-      if (!fits16((long long)r[2] * r[3])) d->lbp16_all = 0;
-    }
-    if (d->lbp16_all) {
-      build_lbp_stumps16(d->m, s16);
-      CC_HIP(d->d_lbp16.upload(s16, d->stream));
-    }
-    CC_HIP(hipStreamSynchronize(d->stream));
-  }
+  if (cc_status ts = upload_cascade_tables(d.get()); ts != CC_OK) return ts;
   // CCAMD_AUTO_SPECIALIZE=<stages>: build the specialised kernel in the background; detection starts on the table-driven
   // kernel and switches over when the module is ready (no change to the calling code)
   if (const char* e = std::getenv("CCAMD_AUTO_SPECIALIZE")) {
@@ -1700,11 +1621,7 @@ cc_status cc_detector_specialize(cc_detector* d, int n_stages) {
   d->spec_bg_code.clear();
   if (n_stages <= 0) {  // back to the table-driven kernel
     CC_HIP(hipStreamSynchronize(d->stream));
-    if (d->spec_mod) (void)hipModuleUnload(d->spec_mod);
-    if (d->spec_mod1) (void)hipModuleUnload(d->spec_mod1);
-    d->spec_mod = d->spec_mod1 = nullptr;
-    d->spec_fn = d->spec_fn1 = nullptr;
-    d->spec_stages = 0;
+    d->unload_spec();
     return CC_OK;
   }
   std::string arch;
@@ -2031,7 +1948,7 @@ cc_status cc_detect_debug_windows(cc_detector* d, const uint8_t* gray, int width
   if (P->windows > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_detect_debug_windows: %lld windows, capacity %lld", P->windows, (long long)cap);
   const size_t nw = (size_t)P->windows;
   if (nw) {
-    // through the detector's stream, not the legacy one: see ensure_spec_tiles
+    // through the detector's stream, not the legacy one: see plan_tiles
     if (codes) CC_HIP(hipMemcpyAsync(codes, d->d_dbg_codes.p, nw * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
     if (sums) CC_HIP(hipMemcpyAsync(sums, d->d_dbg_sums.p, nw * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     if (visited) CC_HIP(hipMemcpyAsync(visited, d->d_dbg_visited.p, nw, hipMemcpyDeviceToHost, d->stream));

@@ -205,4 +205,18 @@ struct SpecCode {
 // `arch`. No device calls: safe on a background thread.
 cc_status spec_build(const Cascade& m, int n_stages, const std::string& arch, std::vector<SpecCode>& codes, int& k_out, int& tmode_out);
 
+// One loaded module of the specialised kernel: its entry point, the dynamic LDS bytes a block of it requests, and the tiles
+// it runs over (window rows per tile; 0 = the tiles of all scales, 1 / 2 = of the STEP-1 / STEP-2 scales).
+struct SpecModule {
+  hipModule_t mod = nullptr;
+  hipFunction_t fn = nullptr;
+  size_t lds = 0;
+  int tile_y = TILE_Y;
+  int only_step = 0;
+};
+
+// Device half: the code objects of spec_build as loaded modules, out[0] the one for all tiles or the STEP-2 tiles, out[1]
+// the STEP-1 module if any. `base_lds`: the LDS request of the ahead-of-time kernels. Owning thread only.
+cc_status spec_load(const Cascade& m, const std::vector<SpecCode>& codes, int tmode, size_t base_lds, SpecModule out[2], int* n_out);
+
 }  // namespace ccamd

@@ -102,6 +102,81 @@ void linear_exact_taps(int src, int dst, AxisTaps& t) {
   }
 }
 
+// Pass sizes. With results wanted the batch is cut into a few passes so that the host side of pass i (copy-back +
+// grouping) overlaps the device side of pass i+1 and the pyramid/integrals of pass i+1 overlap the cascade kernel of
+// pass i. Nothing overlaps the LAST pass's host work, so with three or more passes it is the short one: every pass before
+// it carries ceil(2n / (2 passes - 1)) frames and the last what is left, half a pass or less (32 frames in 4 passes ->
+// 10, 10, 10, 2; a small first pass, to start the cascade kernel earlier, measured no better). A SUBMITTED batch has its last
+// pass overlapped by the batch after it, so it is cut into two even passes only (bench step 17.51 ms against 17.86 / 18.25
+// for 1 / 4 passes, profiles/r03_kernel_experiments.txt). Without results the passes are as large as max_batch allows.
+std::vector<int> pass_sizes(int n_frames, int max_batch, int pipeline_passes, bool pipeline_passes_set, bool want_results,
+                            bool defer_last) {
+  std::vector<int> sizes;
+  if (want_results && n_frames >= 2) {
+    const bool submitted = defer_last && !pipeline_passes_set;
+    const int passes = std::min(submitted ? 2 : pipeline_passes, n_frames);
+    int per = (n_frames + passes - 1) / passes;
+    if (passes >= 3 && !submitted) {
+      const int big = (2 * n_frames + 2 * passes - 2) / (2 * passes - 1);
+      if (big >= 2 && big * (passes - 1) < n_frames) per = big;
+    }
+    for (int f = 0; f < n_frames; f += per) sizes.push_back(std::min(per, n_frames - f));
+  } else {
+    for (int f = 0; f < n_frames; f += max_batch) sizes.push_back(std::min(max_batch, n_frames - f));
+  }
+  // normalise: sizes within max_batch, summing to n_frames (a pass larger than max_batch is cut down where it stands and
+  // the frames it loses make up further passes at the end: 64 frames at max_batch 16 -> 16, 16, 16, 7, 9)
+  std::vector<int> fixed;
+  int left = n_frames;
+  for (size_t i = 0; left > 0; i++) {
+    int v = i < sizes.size() ? sizes[i] : left;
+    v = std::max(1, std::min({v, max_batch, left}));
+    fixed.push_back(v);
+    left -= v;
+  }
+  return fixed;
+}
+
+// Stage groups (EvalArgs::group_first). Every stage boundary inside the cascade kernel costs the block a barrier, the
+// class counts and a queue rebuild -- about as much as a pass over 25 stumps -- while what it buys is that the windows
+// rejected by the stage stop occupying lanes. For short stages (the stock LBP cascade has 3-10 stumps per stage) the
+// boundary costs more than it saves, so consecutive stages are put into one group while the group stays within
+// `budget` stumps; a stage longer than the budget is a group of its own (the form every stage had before). Grouping
+// never changes a result: a window's exit stage and stage sum are recorded where it fails, whatever the lanes around
+// it do. Cascades with deeper trees keep one stage per group (budget 0).
+// Measured (round 3, stock LBP cascade, ms per 32 Full-HD frames alone on the device; tools/sweeps/r3_*.txt): grouping
+// from stage 1 on is slower at every budget but 12 stumps (-3 %), because the lanes of windows that died inside a
+// group keep executing; the gain is in the LATE stages, where a handful of windows per tile pay a barrier round per
+// stage. Hence two knobs: groups start at stage `from`, and hold up to `budget` stumps.
+// LBP with its wave phase (which takes over below 24 windows), round 3 (tiles of 8 rows, bank-class table): groups of
+// <= 20 stumps from stage 2 on 4.91-5.06, 12 from stage 1: 5.04-5.25, one stage per group 5.29, 30 from stage 2: 5.36.
+// Round 4 (list queue from stage 2; specialised kernel on tiles of 20 rows): <= 14 stumps 3.70, <= 20 3.87, <= 30 4.17;
+// at 8 rows 4.84 / 4.87 / 5.13.
+void stage_groups(const std::vector<int32_t>& stage_ntrees, int from, int budget, int dense_stage, std::vector<int>& group_first,
+                  int& dense_from) {
+  std::vector<int>& gf = group_first;
+  gf.clear();
+  const int nst = (int)stage_ntrees.size();
+  for (int s0 = 0; s0 < nst;) {
+    gf.push_back(s0);
+    const int cap = s0 < from ? 0 : budget;  // stage 0 is the dense phase: always alone
+    int s1 = s0 + 1, sum = stage_ntrees[(size_t)s0];
+    while (s1 < nst && sum + stage_ntrees[(size_t)s1] <= cap) sum += stage_ntrees[(size_t)s1++];
+    s0 = s1;
+  }
+  gf.push_back(nst);
+  if (gf.size() < 2) gf.push_back(nst);  // no stage at all: one empty group, the kernels read group_first[1]
+  // Queue form (EvalArgs::dense_from): LBP stump cascades switch from the bank-class table to a plain list at stage 2.
+  // There the tile is down to ~100 of its 512 windows: the table needs 6.2 rows for them (its fullest class) where a list
+  // needs 3.1, i.e. four wavefront passes over the group's 19 stumps instead of two, and the LBP kernel is bound by the
+  // vector ALU (73 % busy; LDS 52 %, profiles/r04_pmc_eval_lbp.json), not by the ~2.5-way bank conflicts the list costs.
+  // Haar cascades keep the table everywhere (LDS-bound; CCAMD_DENSE_FROM=<stage> to experiment).
+  dense_from = 0x7fffffff;
+  if (dense_stage >= 1)
+    for (int g = (int)gf.size() - 2; g >= 1; g--)
+      if (gf[(size_t)g] >= dense_stage) dense_from = g;
+}
+
 // cv::groupRectangles. Classes are the connected components of the SimilarRects graph, labelled in
 // order of first appearance, which is what cv::partition yields.
 void group_rectangles(std::vector<cc_rect>& rects, int group_threshold, double eps, std::vector<int>* levels,

@@ -106,6 +106,19 @@ void linear_exact_taps(int src, int dst, AxisTaps& t);
 void group_rectangles(std::vector<cc_rect>& rects, int group_threshold, double eps, std::vector<int>* levels = nullptr,
                       std::vector<double>* level_weights = nullptr);
 
+// ---- detector arithmetic that needs no device (cc_detect.hip; tests/cpp/test_detect_host.cpp) ---
+// How cc_detector's pass loop cuts a batch of n_frames into passes: sizes in [1, max_batch] that sum to n_frames.
+// `pipeline_passes_set`: the pass count was given (CCAMD_PIPELINE_PASSES), so a submitted batch (`defer_last`) keeps it.
+std::vector<int> pass_sizes(int n_frames, int max_batch, int pipeline_passes, bool pipeline_passes_set, bool want_results,
+                            bool defer_last);
+
+// Stage groups of the cascade kernel (EvalArgs::group_first, EvalArgs::dense_from): consecutive stages from stage `from`
+// on share a group while the group stays within `budget` stumps. group_first gets one entry per group plus the stage
+// count; dense_from the first group >= 1 that starts at stage `dense_stage` or later (0x7fffffff: none, also for
+// dense_stage < 1).
+void stage_groups(const std::vector<int32_t>& stage_ntrees, int from, int budget, int dense_stage, std::vector<int>& group_first,
+                  int& dense_from);
+
 // ---- catalogs (training side) -------------------------------------------------------------------
 void haar_catalog(int W, int H, int mode, std::vector<HaarFeature>& out);
 void lbp_catalog(int W, int H, std::vector<int32_t>& rects);

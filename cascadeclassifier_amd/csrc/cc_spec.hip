@@ -1,7 +1,8 @@
-// Run-time specialisation of the cascade kernel, host side only: generates straight-line source for a cascade's first
-// stages (spec_stage_source, spec_stage_source_lbp), splices it into the text of cc_eval_kernel.inc and compiles it with
-// hiprtc (loaded on demand), caching code objects in memory and on disk. spec_build is the entry point; loading a module
-// into a detector is cc_detect.hip's (spec_install). Depends on the cascade model only, never on a detector.
+// Run-time specialisation of the cascade kernel: generates straight-line source for a cascade's first stages
+// (spec_stage_source, spec_stage_source_lbp), splices it into the text of cc_eval_kernel.inc and compiles it with hiprtc
+// (loaded on demand), caching code objects in memory and on disk (spec_build, host side only), and loads the code objects
+// as modules (spec_load). Switching a detector over to them is cc_detect.hip's (spec_install). Depends on the cascade
+// model only, never on a detector.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -849,6 +850,60 @@ cc_status spec_build(const Cascade& m, int n_stages, const std::string& arch, st
     if (st != CC_OK) return st;
     codes.push_back(std::move(c));
   }
+  return CC_OK;
+}
+
+// Device half of the specialisation: loads the code objects of spec_build and sizes each module's LDS request from the
+// tiles it stages (`base_lds`: what the ahead-of-time kernels request). out[0] is the module for all tiles or for the STEP-2
+// tiles, out[1] the STEP-1 module if there is one. On failure nothing stays loaded.
+cc_status spec_load(const Cascade& m, const std::vector<SpecCode>& codes, int tmode, size_t base_lds, SpecModule out[2], int* n_out) {
+  if (codes.empty() || codes.size() > 2) return set_error(CC_ERR_HIP, "cc_detector_specialize: %zu modules", codes.size());
+  const bool haar_k = m.feature_type == CC_FEATURE_HAAR;
+  int n = 0;
+  auto fail = [&](SpecModule& x) {
+    (void)hipGetLastError();
+    if (x.mod) (void)hipModuleUnload(x.mod);
+    for (int i = 0; i < n; i++) (void)hipModuleUnload(out[i].mod);
+  };
+  for (const SpecCode& c : codes) {
+    SpecModule x;
+    x.tile_y = c.tile_y;
+    x.only_step = c.only_step;  // tiles this module stages: of the step(s) it covers
+    const char* entry = c.only_step == 1 ? "k_eval_spec_step1" : c.only_step == 2 ? "k_eval_spec_step2" : "k_eval_spec";
+    if (hipModuleLoadData(&x.mod, c.code.data()) != hipSuccess || hipModuleGetFunction(&x.fn, x.mod, entry) != hipSuccess) {
+      fail(x);
+      return set_error(CC_ERR_HIP, "cc_detector_specialize: the compiled module does not load or has no entry point");
+    }
+    const int ty = c.tile_y, step = c.only_step;
+    x.lds = base_lds;
+    if (tmode == TILE_32) {
+      const TileGeom<1> G1(m.win_w, m.win_h, ty);
+      const TileGeom<2> G2(m.win_w, m.win_h, ty);
+      const int words = step == 1 ? G1.words() : step == 2 ? G2.words() : std::max(G1.words(), G2.words());
+      x.lds = eval_lds_bytes(words, m.has_tilted, haar_k, ty);
+    } else if (tmode == TILE_16) {  // STEP-1 tile in 32 bits, STEP-2 tile in 16 bits
+      const TileGeom<1> G1(m.win_w, m.win_h, ty);
+      const TileGeom16 G2(m.win_w, m.win_h, ty);
+      x.lds = eval_lds_bytes(std::max(G1.words(), G2.words()), false, haar_k, ty);
+    }
+    if (x.lds > 64 * 1024) {  // same opt-in as the ahead-of-time kernels (cc_detector_create)
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(x.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds);
+      if (e != hipSuccess) {
+        fail(x);
+        return set_error(CC_ERR_UNSUPPORTED, "cc_detector_specialize: %zu bytes of LDS per tile cannot be requested for a run-time module (%s)",
+                         x.lds, hipGetErrorString(e));
+      }
+    }
+    if (std::getenv("CCAMD_TRACE_HOST")) {  // what the specialised kernel's footprint allows per CU
+      int nb = 0;
+      if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, x.fn, EVAL_THREADS, x.lds) != hipSuccess) (void)hipGetLastError();
+      std::fprintf(stderr, "[ccamd host] specialised kernel: tile mode %d, tiles of step %d (0 = all), %d window rows, %zu bytes of LDS per block, %d resident blocks per CU\n",
+                   tmode, c.only_step, ty, x.lds, nb);
+    }
+    out[n++] = x;
+  }
+  if (n == 2 && out[0].only_step == 1) std::swap(out[0], out[1]);
+  *n_out = n;
   return CC_OK;
 }
 

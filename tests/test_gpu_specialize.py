@@ -351,3 +351,39 @@ def test_tile_heights_and_modules_do_not_change_results(lbp_xml, haar_xml, env, 
         n = _same_as_oracle(p, o, img, 1.1)
         n += _same_as_oracle(p, o, img2, 1.25)
         assert n > 0
+
+
+@pytest.mark.parametrize("which,k,env", [
+    ("haar", 4, {"CCAMD_SPEC_TILE_Y1": "16", "CCAMD_SPEC_TILE_Y2": "12"}),     # two modules, two tile lists of their own
+    ("lbp", 20, {"CCAMD_SPEC_TWO_MODULES": "1", "CCAMD_SPEC_TILE_Y1": "12"}),  # LBP: a module per step, 20 / 12 rows
+])
+def test_captured_graph_follows_a_kernel_switch(lbp_xml, haar_xml, which, k, env, monkeypatch):
+    """The captured single-image graph across kernel switches: a graph records the kernel, its LDS request and the tile list
+    of every launch of the pass, so installing the specialised modules (each with a tile list of its own height) and going
+    back to the table-driven kernel must each end the old graph and capture a new one -- and every call, the ordinary first
+    one, the capturing one and the replays, must return the CPU reference's rectangles. One small frame with STEP-1 and
+    STEP-2 scales and several tiles per scale; minNeighbors 0, so that every candidate shows."""
+    for kk, v in env.items():
+        monkeypatch.setenv(kk, v)
+    monkeypatch.setenv("CCAMD_CACHE_DIR", "")
+    xml = haar_xml if which == "haar" else lbp_xml
+    img = frame_natural(200, 150, 43)
+    want = orc.detect_multiscale(orc.load_cascade_xml(xml), img, 1.1, 0, nthreads=8)
+    assert len(want) > 0
+    p = cc.CascadeClassifier(xml)
+
+    def three_calls():
+        for _ in range(3):
+            got = p.detectMultiScale(img, 1.1, 0)
+            assert got.shape == want.shape and (got == want).all()
+        assert p.graph_active()
+        return p.graph_captures()
+
+    c0 = three_calls()
+    assert c0 >= 1
+    assert p.specialize(k) == k
+    c1 = three_calls()
+    assert c1 > c0
+    assert p.specialize(0) == 0
+    c2 = three_calls()
+    assert c2 > c1

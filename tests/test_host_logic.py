@@ -239,3 +239,22 @@ def test_value_cache_policy_of_the_cpp_adaptor():
     assert os.path.exists(exe), "build first: make -C cascadeclassifier_amd/cpp (or __graft_entry__.build())"
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "test_cache_policy OK" in r.stdout, r.stdout + r.stderr
+
+
+def test_pass_sizes_and_stage_groups(repo_root, tmp_path):
+    """The detector's device-free arithmetic, cut out of the pass loop and of cc_detector_create: pass_sizes (every size in
+    [1, max_batch], summing to the batch, and the values the pass loop has always produced) and stage_groups (strictly
+    ascending groups within the stump budget, stage 0 alone, dense_from, the stock LBP cascade's literal grouping).
+    tests/cpp/test_detect_host.cpp, compiled with g++ against cc_host.cpp; no GPU."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "a host C++ compiler is needed"
+    csrc = os.path.join(repo_root, "cascadeclassifier_amd", "csrc")
+    exe = str(tmp_path / "test_detect_host")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-I" + os.path.join(repo_root, "include"), "-I" + csrc,
+                        os.path.join(repo_root, "tests", "cpp", "test_detect_host.cpp"), os.path.join(csrc, "cc_host.cpp"), "-o", exe],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "test_detect_host OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
