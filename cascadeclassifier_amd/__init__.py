@@ -1,5 +1,6 @@
 """MI355X-native cascade-classifier hot path (integral images + Haar/LBP window evaluation) behind the reference's
 own plugin surface. The compute lives in cascadeclassifier_amd/csrc (HIP, gfx950) behind include/cascadeclassifier_amd.h."""
 from ._lib import CascadeError, LIB_PATH  # noqa: F401
-from .detector import CascadeClassifier, frame_layout, group_rectangles, scale_plan, to_gray  # noqa: F401
+from .detector import (CascadeClassifier, frame_layout, group_rectangles, group_rectangles_device, scale_plan,  # noqa: F401
+                       to_gray)
 from .evaluator import CvFeatureEvaluator, CvFeatureParams, NegativeMiner  # noqa: F401

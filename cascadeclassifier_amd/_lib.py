@@ -58,7 +58,8 @@ class DetectorTimings(C.Structure):
     _fields_ = [("resize_ms", C.c_double), ("integral_ms", C.c_double), ("eval_ms", C.c_double), ("finalize_ms", C.c_double),
                 ("resize_launches", C.c_int64), ("integral_launches", C.c_int64), ("eval_launches", C.c_int64),
                 ("finalize_launches", C.c_int64), ("frames", C.c_int64), ("grid_windows", C.c_int64),
-                ("integral_elems", C.c_int64), ("eval_step1_ms", C.c_double)]
+                ("integral_elems", C.c_int64), ("eval_step1_ms", C.c_double),
+                ("group_ms", C.c_double), ("group_launches", C.c_int64)]
 
 
 class Split(C.Structure):
@@ -100,6 +101,8 @@ SIGNATURES = {
     "cc_detect_multiscale_fmt": (_i, [_vp, _vp, _i, _i, _sz, _i, C.POINTER(DetectParams), _vp, _i, C.POINTER(_i)]),
     "cc_detect_batch_fmt": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _vp, _i, _vp]),
     "cc_detect_batch_submit_fmt": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _pp]),
+    "cc_detect_batch_to_device": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _vp, _i, _vp,
+                                       C.POINTER(_i)]),
     "cc_detect_multiscale_levels_fmt": (_i, [_vp, _vp, _i, _i, _sz, _i, C.POINTER(DetectParams), _vp, _vp, _vp, _i,
                                              C.POINTER(_i)]),
     "cc_to_gray_u8": (_i, [_i, _vp, _i, _i, _i, _sz, _vp, _sz]),
@@ -116,12 +119,14 @@ SIGNATURES = {
     "cc_detector_graph_active": (_i, [_vp]),
     "cc_detector_graph_captures": (C.c_int64, [_vp]),
     "cc_detector_get_timings": (_i, [_vp, C.POINTER(DetectorTimings), _i]),
+    "cc_detector_candidate_capacity": (_i, [_vp]),
     "cc_integral_u8": (_i, [_i, _vp, _i, _i, _sz, _vp, _vp, _vp]),
     "cc_resize_linear_exact_u8": (_i, [_i, _vp, _i, _i, _sz, _vp, _i, _i, _sz]),
     "cc_debug_stream_dwords": (_i, [_i, _sz, _i, C.POINTER(C.c_uint32)]),
     "cc_debug_division_check": (_i, [_i, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cc_debug_vnf_check": (_i, [_i, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cc_group_rectangles": (_i, [_vp, _i, _i, _d, _vp, _i, C.POINTER(_i)]),
+    "cc_group_rectangles_device": (_i, [_i, _vp, _vp, _i, _i, _d, _vp, _i, _vp, C.POINTER(_i)]),
     "cc_eval_create": (_i, [_i, _i, _i, _i, _i, _i, _pp]),
     "cc_eval_destroy": (None, [_vp]),
     "cc_eval_num_features": (_i, [_vp]),

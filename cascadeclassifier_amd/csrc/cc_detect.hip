@@ -225,6 +225,11 @@ struct cc_detector {
   // Results of a pass are double-buffered so that the host can fetch and group pass i while the device runs pass i+1.
   DevBuf<CandOut> d_out[2];
   DevBuf<int> d_counts[2];  // [0] raw count, [1] filtered count
+  // cc_detect_batch_to_device: the workspace of the ordering and grouping kernels (cc_group.hip), sized for cand_cap
+  // candidates and pass_capacity frames, and two words on the device: [0] rectangles written so far in the batch, [1] set by
+  // a pass whose candidate list overflowed (GroupGuard::abort).
+  GroupBufs group;
+  DevBuf<int> d_group_state;
   int* h_counts = nullptr;  // pinned, 2 x 2 ints
   uint8_t* h_frame = nullptr;  // pinned staging copy of a single host image (graph path)
   size_t h_frame_bytes = 0;
@@ -558,7 +563,7 @@ static cc_status build_plan(cc_detector* d, int w, int h, const cc_detect_params
   return CC_OK;
 }
 
-enum { EV_RESIZE = 0, EV_INTEGRAL = 1, EV_EVAL = 2, EV_FILTER = 3, EV_EVAL_STEP1 = 4 };
+enum { EV_RESIZE = 0, EV_INTEGRAL = 1, EV_EVAL = 2, EV_FILTER = 3, EV_EVAL_STEP1 = 4, EV_GROUP = 5 };
 
 struct EvScope {  // records a pair of events around a group of launches when profiling is on
   cc_detector* d;
@@ -590,6 +595,7 @@ static void collect_events(cc_detector* d) {
         case EV_EVAL: d->tm.eval_ms += ms; d->tm.eval_launches++; break;
         case EV_EVAL_STEP1: d->tm.eval_step1_ms += ms; break;
         case EV_FILTER: d->tm.finalize_ms += ms; d->tm.finalize_launches++; break;
+        case EV_GROUP: d->tm.group_ms += ms; d->tm.group_launches++; break;
       }
     }
     (void)hipEventDestroy(e.a);
@@ -1662,6 +1668,8 @@ cc_status cc_detector_set_profiling(cc_detector* d, int enabled) {
   return CC_OK;
 }
 
+int cc_detector_candidate_capacity(const cc_detector* d) { return d ? d->cand_cap : -1; }
+
 cc_status cc_detector_get_timings(cc_detector* d, cc_detector_timings* t, int reset) {
   if (!d || !t) return set_error(CC_ERR_INVALID_ARG, "cc_detector_get_timings: null argument");
   if (!d->events.empty()) {  // event pairs of submitted batches: their kernels may still be running
@@ -1724,6 +1732,104 @@ cc_status cc_detect_batch_fmt(cc_detector* d, const uint8_t* frames, int on_devi
                  std::chrono::duration<double, std::milli>(t1 - t_start).count(), group_ms, n_cands);
   }
   if (total > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_detect_batch: %lld rectangles, capacity %d", total, cap);
+  return CC_OK;
+}
+
+// The device-output batch. The same passes as cc_detect_batch, each followed on the detector's stream by the ordering and
+// grouping kernels, which append to the caller's buffers; at most two passes are in flight (the slots of the results). Per
+// pass the host reads back the two counters of d_counts only (raw and filtered candidates; the raw one decides). A pass that overflowed its candidate list has written nothing, and
+// neither has the pass launched behind it (GroupGuard): the lists grow and the loop goes back to that pass.
+cc_status cc_detect_batch_to_device(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
+                                    size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p,
+                                    cc_rect* d_out, int cap, int32_t* d_offsets, int* n_total) {
+  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch_to_device", pixel_format, frame_stride);
+  if (st != CC_OK) return st;
+  if (!d_offsets || !n_total || (cap > 0 && !d_out) || cap < 0)
+    return set_error(CC_ERR_INVALID_ARG, "cc_detect_batch_to_device: bad output buffers");
+  st = ensure_device(d->device);
+  if (st != CC_OK) return st;
+  retire_foreign(d);  // a batch submitted earlier and not yet fetched
+  spec_poll(d);
+  Plan* P = nullptr;
+  st = build_plan(d, width, height, *p, &P);
+  if (st != CC_OK) return st;
+  st = ensure_spec_tiles(d, P);
+  if (st != CC_OK) return st;
+  st = ensure_pipeline_objects(d);
+  if (st != CC_OK) return st;
+  hipStream_t front = d->overlap_front ? d->front_stream : d->stream;
+  if (front != d->stream && d->stream != d->own_stream) {  // frames made by earlier work on the caller's stream (run_batch)
+    CC_HIP(hipEventRecord(d->batch_begin, d->stream));
+    CC_HIP(hipStreamWaitEvent(front, d->batch_begin, 0));
+  }
+  const std::vector<int> sizes = pass_sizes(n_frames, d->max_batch, d->pipeline_passes, d->pipeline_passes_set != 0, true, false);
+  for (int v : sizes) d->pass_capacity = std::max(d->pass_capacity, v);
+  CC_HIP(d->d_group_state.ensure(2));
+  CC_HIP(hipMemsetAsync(d->d_group_state.p, 0, 2 * sizeof(int), d->stream));
+  if (sizes.empty()) CC_HIP(hipMemsetAsync(d_offsets, 0, sizeof(int32_t), d->stream));
+  const bool staged = !on_device || pixel_format != CC_PIX_GRAY8;
+  std::vector<int> first((size_t)sizes.size() + 1, 0);  // first frame of each pass
+  for (size_t i = 0; i < sizes.size(); i++) first[i + 1] = first[i] + sizes[i];
+  int slot_of[2] = {0, 0}, cap_of[2] = {0, 0};  // of the passes in flight, by pass index & 1
+  size_t next = 0, done = 0;
+  while (done < sizes.size()) {
+    if (next < sizes.size() && next - done < 2) {
+      const int f0 = first[next], nf = sizes[next], slot = d->next_slot;
+      const uint8_t* dptr = frames + (size_t)f0 * frame_stride;
+      size_t rs = row_stride, fs = frame_stride;
+      if (staged) {  // at most one pass is unretired here, so the staging slot of the pass three back is free (stage_pass)
+        rs = (size_t)align_up(width, 4);
+        fs = rs * (size_t)height;
+        st = stage_pass(d, nullptr, frames, on_device, width, height, row_stride, frame_stride, pixel_format, front, f0, nf, &dptr);
+        if (st != CC_OK) return st;
+      }
+      st = run_device_pass(d, P, dptr, nf, rs, fs, false, slot);
+      if (st != CC_OK) return st;
+      // sized here, where cand_cap is known; allocates only while the detector's lists or passes are still growing
+      CC_HIP(d->group.ensure((size_t)std::max(d->cand_cap, 1), (size_t)d->pass_capacity, true));
+      const GroupGuard g{d->d_counts[slot].p, d->cand_cap, d->d_group_state.p + 1};
+      {
+        EvScope ev(d, EV_GROUP, d->stream);
+        launch_order_candidates(d->stream, g, d->d_out[slot].p, nf, d->group);
+        launch_group_frames(d->stream, g, d->group.ordered.p, d->group.seg.p, nf, p->min_neighbors, 0.2, d->group, d_out, cap, d_offsets + f0,
+                            d->d_group_state.p);
+      }
+      CC_HIP(hipGetLastError());
+      CC_HIP(hipMemcpyAsync(d->h_counts + 2 * slot, d->d_counts[slot].p, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+      CC_HIP(hipEventRecord(d->pass_done[slot], d->stream));
+      slot_of[next & 1] = slot;
+      cap_of[next & 1] = d->cand_cap;
+      d->next_slot ^= 1;
+      next++;
+      continue;
+    }
+    const int slot = slot_of[done & 1];
+    CC_HIP(hipEventSynchronize(d->pass_done[slot]));
+    const int raw = d->h_counts[2 * slot];
+    if (raw > cap_of[done & 1]) {  // retire_pending's grow-and-rerun: this pass and the one behind it wrote nothing
+      CC_HIP(hipStreamSynchronize(d->stream));
+      if (raw > d->cand_cap) {
+        d->cand_cap = raw + raw / 2;
+        for (int s2 = 0; s2 < 2; s2++) {
+          d->d_cands[s2].release();
+          d->d_out[s2].release();
+        }
+        d->list_gen++;
+      }
+      CC_HIP(hipMemsetAsync(d->d_group_state.p + 1, 0, sizeof(int), d->stream));
+      next = done;
+      continue;
+    }
+    done++;
+  }
+  int total = 0;
+  CC_HIP(copy_sync(&total, d->d_group_state.p, sizeof(int), hipMemcpyDeviceToHost, d->stream));
+  if (d->profiling) {
+    if (d->front_stream) CC_HIP(hipStreamSynchronize(d->front_stream));
+    collect_events(d);
+  }
+  *n_total = total;
+  if (total > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_detect_batch_to_device: %d rectangles, capacity %d", total, cap);
   return CC_OK;
 }
 

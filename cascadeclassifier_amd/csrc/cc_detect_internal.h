@@ -219,4 +219,31 @@ struct SpecModule {
 // the STEP-1 module if any. `base_lds`: the LDS request of the ahead-of-time kernels. Owning thread only.
 cc_status spec_load(const Cascade& m, const std::vector<SpecCode>& codes, int tmode, size_t base_lds, SpecModule out[2], int* n_out);
 
+// ---- ordering and grouping on the device (cc_group.hip) ----
+// What lets the kernels of a detector pass drop out: counts = the pass's {raw, filtered} candidate counts on the device, the
+// capacity its lists were launched with, and the detector's abort word (set by a pass that overflowed, for the passes behind
+// it). All null / 0 for rectangles that come from a caller (cc_group_rectangles_device).
+struct GroupGuard {
+  const int* counts = nullptr;
+  int cand_cap = 0;
+  int* abort = nullptr;
+};
+constexpr int GROUP_WS_INTS = 7;  // workspace ints per rectangle of k_group_frames
+// Device workspace of the two launch helpers below, owned by the caller; ensure() only grows it (the detector sizes it for
+// its candidate capacity and pass size, so a warm pass allocates nothing).
+struct GroupBufs {
+  DevBuf<cc_rect> ordered, grouped;  // a pass's rectangles in candidate order; each frame's result at its input offset
+  DevBuf<unsigned long long> keys;
+  DevBuf<int> src, seg, frame_cnt, out_count, ws;  // seg: frames + 1 segment offsets of `ordered`; ws: GROUP_WS_INTS per rectangle
+  hipError_t ensure(size_t rects, size_t frames, bool ordering);
+};
+// Only launches, on `st`. The filtered candidates of a pass of nf frames -> B.ordered in (frame, scale, gy, gx) order with
+// B.seg as its per-frame offsets.
+void launch_order_candidates(hipStream_t st, GroupGuard g, const CandOut* cands, int nf, GroupBufs& B);
+// cv::groupRectangles on each of nf frames (frame f: rects[offsets[f] .. offsets[f + 1])). The results go to `out` from
+// *total on, frame after frame, only what lies below cap being written; out_offsets[0 .. nf] receives their offsets and *total
+// moves on by their number.
+void launch_group_frames(hipStream_t st, GroupGuard g, const cc_rect* rects, const int* offsets, int nf, int group_threshold, double eps,
+                         GroupBufs& B, cc_rect* out, int cap, int32_t* out_offsets, int* total);
+
 }  // namespace ccamd

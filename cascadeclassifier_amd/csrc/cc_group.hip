@@ -1,0 +1,371 @@
+// Device side of what follows k_filter_candidates: the candidates of a pass put into OpenCV's single-threaded order
+// (frame, scale, gy, gx) and cv::groupRectangles per frame, so that a detector's result can stay in device memory
+// (cc_detect_batch_to_device), plus the building block cc_group_rectangles_device. The host twins are sort_candidates /
+// group_pass (cc_detect.hip) and group_rectangles (cc_host.cpp); every step below restates theirs in the same integer,
+// float and double operations, and nothing here depends on the order in which threads run ("Results that
+// stay on the device").
+//
+// Every kernel finds its element counts in device memory (the filtered-candidate count, the segment offsets): the host
+// launches fixed grids and never waits for a count before the next launch.
+#include <hip/hip_runtime.h>
+
+#include "cc_detect_internal.h"
+
+namespace ccamd {
+
+// A pass whose raw candidate list overflowed holds an arbitrary subset: its host redoes it with longer lists (the detector's
+// grow-and-rerun). Until then nothing of it, and nothing of a pass launched behind it, may reach the caller's buffers:
+// every kernel of such a pass returns at once, and the last one leaves `abort` set for the passes behind.
+__device__ __forceinline__ bool pass_dead(const GroupGuard g) { return (g.counts && g.counts[0] > g.cand_cap) || (g.abort && *g.abort); }
+
+// Workspace words are written with atomics by some steps and read by other threads after a barrier: reads go to the
+// coherent level (in LDS this is a plain ds_read), and ws_sync orders plain stores to the global workspace as well.
+__device__ __forceinline__ int ws_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void ws_sync() {
+  __threadfence();
+  __syncthreads();
+}
+
+// Exclusive scan of one value per thread over the block, continued from `carry` (the same in every thread; advanced by
+// the block's total). Every thread of the block must call it. s_wave: THREADS / 64 ints of LDS.
+template <int THREADS>
+__device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int& carry) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += t;
+  }
+  if (lane == 63) s_wave[wave] = inc;
+  __syncthreads();
+  int before = 0, total = 0;
+  for (int w = 0; w < THREADS / 64; w++) {
+    const int t = s_wave[w];
+    if (w < wave) before += t;
+    total += t;
+  }
+  __syncthreads();  // s_wave is free for the next call
+  const int pos = carry + before + inc - v;
+  carry += total;
+  return pos;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ordering. The key (frame, scale, gy, gx) is unique per candidate, so a candidate's place in its frame is the number of
+// the frame's keys below its own: a rank, the same whatever order the filter kernel's atomics left the list in.
+//   k_cand_count    candidates per frame
+//   k_cand_segments exclusive scan -> seg[nf + 1], cursors cleared
+//   k_cand_bucket   key + list index of every candidate into its frame's segment (any order inside it)
+//   k_cand_rank     rank inside the segment -> the rectangle at seg[f] + rank
+// ------------------------------------------------------------------------------------------------
+constexpr int ORDER_THREADS = 256;
+constexpr int RANK_CHUNKS = 8;  // blocks that share one frame's ranks
+
+__device__ __forceinline__ unsigned long long cand_key(const CandOut& c) {  // gx, gy <= 32768 (frame side limit), scale and frame < 2^16
+  return ((unsigned long long)(c.frame & 0xffff) << 48) | ((unsigned long long)(c.scale & 0xffff) << 32) |
+         ((unsigned long long)(c.gy & 0xffff) << 16) | (unsigned long long)(c.gx & 0xffff);
+}
+
+__global__ __launch_bounds__(ORDER_THREADS) void k_cand_count(GroupGuard g, const CandOut* __restrict__ cands, int nf,
+                                                              int* __restrict__ frame_cnt) {
+  if (pass_dead(g)) return;
+  const int n = min(g.counts[1], g.cand_cap);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int f = cands[i].frame;
+    if ((unsigned)f < (unsigned)nf) atomicAdd(frame_cnt + f, 1);
+  }
+}
+
+// One block. cnt[nf] -> seg[nf + 1]; cnt becomes the cursors of k_cand_bucket (zero).
+__global__ __launch_bounds__(ORDER_THREADS) void k_cand_segments(GroupGuard g, int nf, int* __restrict__ cnt, int* __restrict__ seg) {
+  __shared__ int s_wave[ORDER_THREADS / 64];
+  const bool dead = pass_dead(g);  // a dead pass: empty segments, so that whatever reads seg stays inside its buffers
+  int carry = 0;
+  for (int f0 = 0; f0 < nf; f0 += ORDER_THREADS) {
+    const int f = f0 + threadIdx.x;
+    const int v = (f < nf && !dead) ? cnt[f] : 0;
+    const int pos = block_excl_scan<ORDER_THREADS>(v, s_wave, carry);
+    if (f < nf) {
+      seg[f] = pos;
+      cnt[f] = 0;
+    }
+  }
+  if (threadIdx.x == 0) seg[nf] = carry;
+}
+
+__global__ __launch_bounds__(ORDER_THREADS) void k_cand_bucket(GroupGuard g, const CandOut* __restrict__ cands, int nf,
+                                                               const int* __restrict__ seg, int* __restrict__ cursor,
+                                                               unsigned long long* __restrict__ keys, int* __restrict__ src) {
+  if (pass_dead(g)) return;
+  const int n = min(g.counts[1], g.cand_cap);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const CandOut c = cands[i];
+    if ((unsigned)c.frame >= (unsigned)nf) continue;
+    const int at = seg[c.frame] + atomicAdd(cursor + c.frame, 1);  // < seg[frame + 1] <= n: k_cand_count counted the same list
+    keys[at] = cand_key(c);
+    src[at] = i;
+  }
+}
+
+// grid (nf, RANK_CHUNKS): the blocks of a frame take its candidates in turns of ORDER_THREADS and count, for each, the
+// frame's keys below it, a tile of keys at a time through LDS.
+__global__ __launch_bounds__(ORDER_THREADS) void k_cand_rank(GroupGuard g, const CandOut* __restrict__ cands, const int* __restrict__ seg,
+                                                             const unsigned long long* __restrict__ keys, const int* __restrict__ src,
+                                                             cc_rect* __restrict__ rects) {
+  if (pass_dead(g)) return;
+  __shared__ unsigned long long s_keys[ORDER_THREADS];
+  const int base = seg[blockIdx.x], n = seg[blockIdx.x + 1] - base;
+  for (int i0 = blockIdx.y * ORDER_THREADS; i0 < n; i0 += RANK_CHUNKS * ORDER_THREADS) {  // block-uniform
+    const int i = i0 + threadIdx.x;
+    const unsigned long long mine = i < n ? keys[base + i] : 0ull;
+    int rank = 0;
+    for (int t0 = 0; t0 < n; t0 += ORDER_THREADS) {
+      __syncthreads();
+      if (t0 + (int)threadIdx.x < n) s_keys[threadIdx.x] = keys[base + t0 + threadIdx.x];
+      __syncthreads();
+      const int tn = min(ORDER_THREADS, n - t0);
+      for (int k = 0; k < tn; k++) rank += s_keys[k] < mine ? 1 : 0;  // same address in every lane: a broadcast
+    }
+    if (i < n) {
+      const CandOut c = cands[src[base + i]];
+      rects[base + rank] = cc_rect{c.x, c.y, c.w, c.h};  // rank < n: the keys are distinct
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Grouping: one work-group per frame, group_rectangles (cc_host.cpp) step by step.
+//   classes   union-find over all similar pairs: a root only ever hooks itself (compare-and-swap) under a smaller index, so
+//             links never form a cycle, none is ever undone, and when all pairs are in, every component's one root is its
+//             smallest member -- whatever the order of the hooks. Class number = rank of that root among the roots =
+//             order of first appearance (cv::partition).
+//   averages  int32 sums by integer atomics (exact, order-free), s = 1.f / cnt correctly rounded, rint((float)sum * s)
+//   filters   cnt <= threshold; inside a bigger class
+//   output    survivors in class order, at the frame's INPUT offset of `grouped` (there are never more than went in);
+//             k_group_offsets / k_group_compact pack the frames behind one another
+// Workspace: GROUP_WS_INTS ints per rectangle -- parent, class of a root (later: nothing), and per class x y w h sums and the
+// count. In LDS up to GROUP_LDS_RECTS rectangles, else the frame's slice of the caller's global workspace.
+// ------------------------------------------------------------------------------------------------
+constexpr int GROUP_THREADS = 1024;
+constexpr int GROUP_LDS_RECTS = 2048;  // 7 x 2048 x 4 B = 56 KiB of the 64 KiB a block may declare
+
+__device__ __forceinline__ bool similar_rects(const cc_rect a, const cc_rect b, double eps) {
+  const double delta = eps * (min(a.width, b.width) + min(a.height, b.height)) * 0.5;
+  return abs(a.x - b.x) <= delta && abs(a.y - b.y) <= delta && abs(a.x + a.width - b.x - b.width) <= delta &&
+         abs(a.y + a.height - b.y - b.height) <= delta;
+}
+
+__device__ __forceinline__ int find_root(const int* parent, int i) {
+  for (int p; (p = ws_ld(parent + i)) != i;) i = p;
+  return i;
+}
+
+__device__ __forceinline__ void unite(int* parent, int i, int j) {
+  int a = find_root(parent, i), b = find_root(parent, j);
+  while (a != b) {
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicCAS(parent + a, a, b);  // a > b
+    if (old == a) break;
+    a = find_root(parent, old);  // a got a parent meanwhile: go on from there
+    b = find_root(parent, b);
+  }
+}
+
+__device__ __forceinline__ void group_frame(int* ws, int* s_wave, const cc_rect* __restrict__ rects, int n, int group_threshold,
+                                            double eps, cc_rect* __restrict__ out, int* __restrict__ out_count) {
+  int* parent = ws;
+  int* cls = ws + n;
+  int* sx = ws + 2 * (size_t)n;
+  int* sy = ws + 3 * (size_t)n;
+  int* sw = ws + 4 * (size_t)n;
+  int* sh = ws + 5 * (size_t)n;
+  int* cnt = ws + 6 * (size_t)n;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += GROUP_THREADS) parent[i] = i;
+  ws_sync();
+  for (int i = tid; i < n; i += GROUP_THREADS) {
+    const cc_rect a = rects[i];
+    for (int j = i + 1; j < n; j++)
+      if (similar_rects(a, rects[j], eps)) unite(parent, i, j);
+  }
+  ws_sync();
+  // every rectangle straight under its root (a reader meets the old parent or the root: both lead to the root)
+  for (int i = tid; i < n; i += GROUP_THREADS) {
+    const int r = find_root(parent, i);
+    if (r != i) __hip_atomic_store(parent + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  ws_sync();
+  int nclasses = 0;
+  for (int i0 = 0; i0 < n; i0 += GROUP_THREADS) {
+    const int i = i0 + tid;
+    const bool root = i < n && ws_ld(parent + i) == i;
+    const int c = block_excl_scan<GROUP_THREADS>(root ? 1 : 0, s_wave, nclasses);
+    if (root) cls[i] = c;
+  }
+  for (int c = tid; c < nclasses; c += GROUP_THREADS) sx[c] = sy[c] = sw[c] = sh[c] = cnt[c] = 0;
+  ws_sync();
+  for (int i = tid; i < n; i += GROUP_THREADS) {
+    const cc_rect r = rects[i];
+    const int c = ws_ld(cls + ws_ld(parent + i));
+    atomicAdd(sx + c, r.x);
+    atomicAdd(sy + c, r.y);
+    atomicAdd(sw + c, r.width);
+    atomicAdd(sh + c, r.height);
+    atomicAdd(cnt + c, 1);
+  }
+  ws_sync();
+  for (int c = tid; c < nclasses; c += GROUP_THREADS) {
+    const float s = __fdiv_rn(1.f, (float)ws_ld(cnt + c));
+    const int x = __float2int_rn((float)ws_ld(sx + c) * s), y = __float2int_rn((float)ws_ld(sy + c) * s);
+    const int w = __float2int_rn((float)ws_ld(sw + c) * s), h = __float2int_rn((float)ws_ld(sh + c) * s);
+    sx[c] = x;
+    sy[c] = y;
+    sw[c] = w;
+    sh[c] = h;
+  }
+  ws_sync();
+  int n_out = 0;
+  for (int c0 = 0; c0 < nclasses; c0 += GROUP_THREADS) {
+    const int c = c0 + tid;
+    bool keep = false;
+    cc_rect r1{0, 0, 0, 0};
+    if (c < nclasses) {
+      const int n1 = ws_ld(cnt + c);
+      r1 = cc_rect{ws_ld(sx + c), ws_ld(sy + c), ws_ld(sw + c), ws_ld(sh + c)};
+      keep = n1 > group_threshold;
+      for (int j = 0; keep && j < nclasses; j++) {
+        const int n2 = ws_ld(cnt + j);
+        if (j == c || n2 <= group_threshold) continue;
+        const cc_rect r2{ws_ld(sx + j), ws_ld(sy + j), ws_ld(sw + j), ws_ld(sh + j)};
+        const int dx = __double2int_rn(r2.width * eps), dy = __double2int_rn(r2.height * eps);
+        if (r1.x >= r2.x - dx && r1.y >= r2.y - dy && r1.x + r1.width <= r2.x + r2.width + dx &&
+            r1.y + r1.height <= r2.y + r2.height + dy && (n2 > max(3, n1) || n1 < 3))
+          keep = false;
+      }
+    }
+    const int at = block_excl_scan<GROUP_THREADS>(keep ? 1 : 0, s_wave, n_out);
+    if (keep) out[at] = r1;  // at < nclasses <= n
+  }
+  if (tid == 0) *out_count = n_out;
+}
+
+__global__ __launch_bounds__(GROUP_THREADS) void k_group_frames(GroupGuard g, const cc_rect* __restrict__ rects,
+                                                                const int* __restrict__ offsets, int group_threshold, double eps,
+                                                                int* __restrict__ ws, cc_rect* __restrict__ grouped,
+                                                                int* __restrict__ out_count) {
+  if (pass_dead(g)) return;
+  __shared__ int s_ws[GROUP_WS_INTS * GROUP_LDS_RECTS];
+  __shared__ int s_wave[GROUP_THREADS / 64];
+  const int f = blockIdx.x;
+  const int base = offsets[f], n = offsets[f + 1] - base;
+  if (group_threshold <= 0 || n <= 0) {  // the ordered candidates as they are
+    for (int i = threadIdx.x; i < n; i += GROUP_THREADS) grouped[base + i] = rects[base + i];
+    if (threadIdx.x == 0) out_count[f] = max(n, 0);
+    return;
+  }
+  if (n <= GROUP_LDS_RECTS)
+    group_frame(s_ws, s_wave, rects + base, n, group_threshold, eps, grouped + base, out_count + f);
+  else
+    group_frame(ws + (size_t)GROUP_WS_INTS * base, s_wave, rects + base, n, group_threshold, eps, grouped + base, out_count + f);
+}
+
+// One block. Frames f0 .. f0 + nf of the batch: out_offsets[f0 + i] = *total + (rectangles of the frames before i);
+// *total moves on and also lands in out_offsets[f0 + nf], so the offsets are complete after the batch's last pass.
+__global__ __launch_bounds__(ORDER_THREADS) void k_group_offsets(GroupGuard g, const int* __restrict__ out_count, int nf,
+                                                                 int32_t* __restrict__ out_offsets, int* __restrict__ total) {
+  __shared__ int s_wave[ORDER_THREADS / 64];
+  if (pass_dead(g)) {
+    if (threadIdx.x == 0 && g.abort) *g.abort = 1;
+    return;
+  }
+  int carry = *total;
+  __syncthreads();  // every thread has read the total before thread 0 moves it on
+  for (int f0 = 0; f0 < nf; f0 += ORDER_THREADS) {
+    const int f = f0 + threadIdx.x;
+    const int pos = block_excl_scan<ORDER_THREADS>(f < nf ? out_count[f] : 0, s_wave, carry);
+    if (f < nf) out_offsets[f] = pos;
+  }
+  if (threadIdx.x == 0) {
+    out_offsets[nf] = carry;
+    *total = carry;
+  }
+}
+
+// grid nf: frame f's rectangles from its input offset of `grouped` to its place in `out`, what fits below cap.
+__global__ __launch_bounds__(ORDER_THREADS) void k_group_compact(GroupGuard g, const cc_rect* __restrict__ grouped,
+                                                                 const int* __restrict__ offsets, const int32_t* __restrict__ out_offsets,
+                                                                 cc_rect* __restrict__ out, int cap) {
+  if (pass_dead(g)) return;
+  const int f = blockIdx.x;
+  const int from = offsets[f], to = out_offsets[f], n = out_offsets[f + 1] - to;
+  for (int i = threadIdx.x; i < n; i += ORDER_THREADS)
+    if (to + i < cap) out[to + i] = grouped[from + i];
+}
+
+hipError_t GroupBufs::ensure(size_t rects, size_t frames, bool ordering) {
+  rects = std::max<size_t>(rects, 1);
+  for (hipError_t e : {grouped.ensure(rects), ws.ensure(rects * GROUP_WS_INTS), out_count.ensure(std::max<size_t>(frames, 1)),
+                       ordering ? ordered.ensure(rects) : hipSuccess, ordering ? keys.ensure(rects) : hipSuccess,
+                       ordering ? src.ensure(rects) : hipSuccess, ordering ? seg.ensure(frames + 1) : hipSuccess,
+                       ordering ? frame_cnt.ensure(std::max<size_t>(frames, 1)) : hipSuccess})
+    if (e != hipSuccess) return e;
+  return hipSuccess;
+}
+
+void launch_order_candidates(hipStream_t st, const GroupGuard g, const CandOut* cands, int nf, GroupBufs& B) {
+  if (nf <= 0) return;
+  (void)hipMemsetAsync(B.frame_cnt.p, 0, (size_t)nf * sizeof(int), st);
+  hipLaunchKernelGGL(k_cand_count, dim3(64), dim3(ORDER_THREADS), 0, st, g, cands, nf, B.frame_cnt.p);
+  hipLaunchKernelGGL(k_cand_segments, dim3(1), dim3(ORDER_THREADS), 0, st, g, nf, B.frame_cnt.p, B.seg.p);
+  hipLaunchKernelGGL(k_cand_bucket, dim3(64), dim3(ORDER_THREADS), 0, st, g, cands, nf, B.seg.p, B.frame_cnt.p, B.keys.p, B.src.p);
+  hipLaunchKernelGGL(k_cand_rank, dim3(nf, RANK_CHUNKS), dim3(ORDER_THREADS), 0, st, g, cands, B.seg.p, B.keys.p, B.src.p, B.ordered.p);
+}
+
+void launch_group_frames(hipStream_t st, const GroupGuard g, const cc_rect* rects, const int* offsets, int nf, int group_threshold,
+                         double eps, GroupBufs& B, cc_rect* out, int cap, int32_t* out_offsets, int* total) {
+  if (nf > 0)
+    hipLaunchKernelGGL(k_group_frames, dim3(nf), dim3(GROUP_THREADS), 0, st, g, rects, offsets, group_threshold, eps, B.ws.p, B.grouped.p,
+                       B.out_count.p);
+  hipLaunchKernelGGL(k_group_offsets, dim3(1), dim3(ORDER_THREADS), 0, st, g, B.out_count.p, nf, out_offsets, total);
+  if (nf > 0)
+    hipLaunchKernelGGL(k_group_compact, dim3(nf), dim3(ORDER_THREADS), 0, st, g, B.grouped.p, offsets, out_offsets, out, cap);
+}
+
+}  // namespace ccamd
+
+using namespace ccamd;
+
+extern "C" cc_status cc_group_rectangles_device(int device, const cc_rect* rects, const int32_t* offsets, int n_frames,
+                                                int group_threshold, double eps, cc_rect* out, int cap, int32_t* out_offsets,
+                                                int* n_total) {
+  if (!offsets || !out_offsets || !n_total || n_frames < 0 || cap < 0 || (cap > 0 && !out))
+    return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: bad argument");
+  cc_status st = ensure_device(device);
+  if (st != CC_OK) return st;
+  OwnStream s;
+  CC_HIP(s.create());
+  // the offsets decide what the kernels index: look at them before anything is launched
+  std::vector<int32_t> h_off((size_t)n_frames + 1);
+  CC_HIP(copy_sync(h_off.data(), offsets, h_off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s.s));
+  if (h_off[0] < 0) return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: negative offset");
+  for (int f = 0; f < n_frames; f++)
+    if (h_off[(size_t)f + 1] < h_off[(size_t)f]) return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: offsets decrease at frame %d", f);
+  const size_t n_rects = (size_t)h_off[(size_t)n_frames];
+  if (n_rects > 0 && !rects) return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: null rectangles");
+  GroupBufs B;
+  DevBuf<int> total;
+  CC_HIP(B.ensure(n_rects, (size_t)n_frames, false));
+  CC_HIP(total.ensure(1));
+  CC_HIP(hipMemsetAsync(total.p, 0, sizeof(int), s.s));
+  launch_group_frames(s.s, GroupGuard{}, rects, offsets, n_frames, group_threshold, eps, B, out, cap, out_offsets, total.p);
+  CC_HIP(hipGetLastError());
+  int h_total = 0;
+  CC_HIP(copy_sync(&h_total, total.p, sizeof(int), hipMemcpyDeviceToHost, s.s));
+  *n_total = h_total;
+  if (h_total > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_group_rectangles_device: %d rectangles, capacity %d", h_total, cap);
+  return CC_OK;
+}

@@ -60,6 +60,30 @@ def group_rectangles(rects, group_threshold, eps=0.2) -> np.ndarray:
     return out[:n.value].copy()
 
 
+def _raise_with_count(status, needed):
+    """CascadeError of a failed call; CC_ERR_BUFFER_TOO_SMALL carries the count the buffer must hold as .needed."""
+    err = L.CascadeError(status, L.lib().cc_last_error().decode("utf-8", "replace"))
+    if status == L.CC_ERR_BUFFER_TOO_SMALL:
+        err.needed = int(needed)
+    raise err
+
+
+def group_rectangles_device(rects_ptr, offsets_ptr, n_frames, group_threshold, out_ptr, cap, out_offsets_ptr, eps=0.2,
+                            device=0) -> int:
+    """cv::groupRectangles on every frame of a batch, in device memory (cc_group_rectangles_device). All pointers are plain
+    integers (e.g. tensor.data_ptr()) into memory of `device`: rects int32 (n, 4), offsets int32 (n_frames + 1), out int32
+    (cap, 4), out_offsets int32 (n_frames + 1). Returns the number of rectangles over all frames; raises CascadeError with
+    CC_ERR_BUFFER_TOO_SMALL (.needed = that number) when it exceeds cap -- out_offsets are complete then, out holds the
+    first cap."""
+    n = C.c_int(0)
+    st = L.lib().cc_group_rectangles_device(int(device), C.c_void_p(rects_ptr or 0), C.c_void_p(offsets_ptr or 0), int(n_frames),
+                                            int(group_threshold), float(eps), C.c_void_p(out_ptr or 0), int(cap),
+                                            C.c_void_p(out_offsets_ptr or 0), C.byref(n))
+    if st != L.CC_OK:
+        _raise_with_count(st, n.value)
+    return n.value
+
+
 # pixel_format keywords -> CC_PIX_* (include/cascadeclassifier_amd.h). 3- and 4-channel arrays default to cv2's BGR / BGRA.
 PIXEL_FORMATS = {"gray": L.CC_PIX_GRAY8, "bgr": L.CC_PIX_BGR8, "bgra": L.CC_PIX_BGRA8, "rgb": L.CC_PIX_RGB8,
                  "rgba": L.CC_PIX_RGBA8, "rgb_planar": L.CC_PIX_RGB8_PLANAR}
@@ -271,6 +295,26 @@ class CascadeClassifier:
             L.check(st)
             return [out[offs[i]:offs[i + 1]].copy() for i in range(n)]
 
+    def detect_batch_to_device(self, frames, scaleFactor=1.1, minNeighbors=3, minSize=None, maxSize=None, *, out_ptr, cap,
+                               offsets_ptr, device_ptr=None, shape=None, row_stride=None, frame_stride=None,
+                               pixel_format=None) -> int:
+        """detect_batch whose result stays on the device (cc_detect_batch_to_device): out_ptr -> int32 (cap, 4) and
+        offsets_ptr -> int32 (n + 1) in memory of the detector's device, as plain integers (tensor.data_ptr()); frame i's
+        rectangles are out[offsets[i]:offsets[i + 1]], the same and in the same order as detect_batch returns. Frames as
+        detect_batch takes them. Returns the number of rectangles over all frames; raises CascadeError with
+        CC_ERR_BUFFER_TOO_SMALL (.needed = that number) when it exceeds cap -- the offsets are complete then, out holds
+        the first cap."""
+        p = _params(scaleFactor, minNeighbors, minSize, maxSize)
+        keep, ptr, on_dev, n, h, w, fmt, rs, fs = self._batch_frames(frames, device_ptr, shape, row_stride, frame_stride,
+                                                                       pixel_format)
+        total = C.c_int(0)
+        st = L.lib().cc_detect_batch_to_device(self._detector(), ptr, on_dev, n, w, h, rs, fs, fmt, C.byref(p),
+                                               C.c_void_p(out_ptr or 0), int(cap), C.c_void_p(offsets_ptr or 0), C.byref(total))
+        del keep  # host frames were staged inside the call
+        if st != L.CC_OK:
+            _raise_with_count(st, total.value)
+        return total.value
+
     def detect_batch_submit(self, frames, scaleFactor=1.1, minNeighbors=3, minSize=None, maxSize=None, device_ptr=None,
                             shape=None, row_stride=None, frame_stride=None, pixel_format=None):
         """First half of detect_batch (cc_detect_batch_submit): launches the batch and returns a ticket while its last pass
@@ -398,6 +442,11 @@ class CascadeClassifier:
         t = L.DetectorTimings()
         L.check(L.lib().cc_detector_get_timings(self._detector(), C.byref(t), 1 if reset else 0))
         return {n: getattr(t, n) for n, _ in t._fields_}
+
+    def candidate_capacity(self) -> int:
+        """Entries of the per-pass candidate lists: 0 before a first pass has sized them, larger after an overflowing pass
+        was redone (cc_detector_candidate_capacity)."""
+        return int(L.lib().cc_detector_candidate_capacity(self._detector()))
 
     # -- lifetime -------------------------------------------------------------------------------
     def _release(self):

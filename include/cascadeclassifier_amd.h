@@ -211,6 +211,23 @@ CC_API cc_status cc_detect_batch_submit_fmt(cc_detector* d, const uint8_t* frame
                                             int height, size_t row_stride, size_t frame_stride, int pixel_format,
                                             const cc_detect_params* p, cc_batch_ticket** ticket);
 
+/* cc_detect_batch_fmt whose out / offsets are DEVICE memory of the detector's device (cap rectangles, n_frames + 1 offsets),
+ * for callers whose next stage runs on the same card. No candidate is copied to the host and no host thread sorts or groups:
+ * each pass's candidates are ordered and grouped by kernels on the detector's stream (cc_group_rectangles_device below is
+ * the grouping on its own), frames of later passes append behind earlier ones, and per pass the host reads back only the pass's two
+ * counters (8 bytes: the raw candidate count, which triggers the grow-and-rerun of an overflowing candidate list, and the
+ * filtered count). Same rectangles, same order as
+ * cc_detect_batch_fmt. The call returns when out / offsets are complete on the detector's stream. *n_total (host) = rectangles
+ * over all frames; if it exceeds cap: CC_ERR_BUFFER_TOO_SMALL, offsets still complete, out holds the first cap. A batch
+ * submitted earlier and still unfetched is retired first. Work of the caller that still touches out / offsets on another
+ * stream must have finished before the call (the detector writes them on its own stream, or the one set with
+ * cc_detector_set_stream). There is no submit / collect pair, no outputRejectLevels variant and
+ * no single-image hipGraph for this entry point: one frame runs as an ordinary pass. */
+CC_API cc_status cc_detect_batch_to_device(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width,
+                                           int height, size_t row_stride, size_t frame_stride, int pixel_format,
+                                           const cc_detect_params* p, cc_rect* d_out, int cap, int32_t* d_offsets,
+                                           int* n_total);
+
 /* The outputRejectLevels overload of cv::CascadeClassifier::detectMultiScale (objects, rejectLevels, levelWeights,
  * ..., outputRejectLevels = true; OpenCV 4.6.0 objdetect, no call site in the reference: SURVEY.md 8f-4). Windows that
  * pass every stage are reported with level = number of stages and weight = the stage sum of the last stage; the
@@ -280,8 +297,16 @@ typedef struct cc_detector_timings {
    * one module per step (k_eval_spec_step2 over the tiles of STEP-2 scales, then k_eval_spec_step1): eval_step1_ms is the
    * part of eval_ms the STEP-1 module's launches took (0 when the pass is a single launch). */
   double eval_step1_ms;
+  /* cc_detect_batch_to_device only: the ordering and grouping kernels behind k_filter_candidates (cc_group.hip), one span per
+   * pass (group_launches counts passes, a pass redone after a candidate-list overflow twice). Not part of finalize_ms, which
+   * stays k_filter_candidates alone. */
+  double group_ms;
+  int64_t group_launches;
 } cc_detector_timings;
 CC_API cc_status cc_detector_set_profiling(cc_detector* d, int enabled);
+/* Entries of the detector's per-pass candidate lists: 0 until a first pass has sized them (262 144 then), larger after a pass
+ * overflowed them and was redone. -1 for a null detector. */
+CC_API int cc_detector_candidate_capacity(const cc_detector* d);
 CC_API cc_status cc_detector_get_timings(cc_detector* d, cc_detector_timings* t, int reset);
 /* Single-image calls (cc_detect_multiscale on a host image; the call shape of tools/detection/Cpp/main.cpp:45) replay
  * the whole device pass from one hipGraph once a first ordinary call has sized the buffers. Returns 1 if the LAST such
@@ -324,6 +349,15 @@ CC_API cc_status cc_debug_vnf_check(int device, uint64_t n_values, uint64_t seed
 /* Host-side (tiny, serial in the reference too): cv::groupRectangles(rects, group_threshold, eps). */
 CC_API cc_status cc_group_rectangles(const cc_rect* rects, int n, int group_threshold, double eps, cc_rect* out, int cap,
                                      int* n_out);
+/* The device twin of cc_group_rectangles, for many frames at once: rects / offsets / out / out_offsets are DEVICE memory of
+ * `device`; frame f's input is rects[offsets[f] .. offsets[f+1]) (n_frames + 1 non-decreasing offsets), its result
+ * out[out_offsets[f] .. out_offsets[f+1]). Same result, same order as cc_group_rectangles on each frame. *n_total (host) =
+ * rectangles over all frames; if it exceeds cap: CC_ERR_BUFFER_TOO_SMALL, out_offsets still complete, out holds the first
+ * cap. Blocking, on a stream of its own: work of the caller that still touches the buffers must have finished. Allocates its
+ * own workspace (the detector keeps one). */
+CC_API cc_status cc_group_rectangles_device(int device, const cc_rect* rects, const int32_t* offsets, int n_frames,
+                                            int group_threshold, double eps, cc_rect* out, int cap, int32_t* out_offsets,
+                                            int* n_total);
 
 /* ============================================================================================
  * 4. Training-side feature evaluator.
