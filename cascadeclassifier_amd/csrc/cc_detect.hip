@@ -159,6 +159,36 @@ struct BatchSink {
   }
 };
 
+// The frames of a call as the caller describes them: n_frames frames of pixel format `fmt` (CC_PIX_*), frame_stride bytes
+// apart, in host memory or (on_device) on the detector's card.
+struct FrameSet {
+  const uint8_t* frames;
+  int on_device, n_frames, width, height;
+  size_t row_stride, frame_stride;
+  int fmt;
+};
+inline FrameSet host_image(const uint8_t* img, int width, int height, size_t row_stride, int fmt = CC_PIX_GRAY8) {
+  return FrameSet{img, 0, 1, width, height, row_stride, row_stride * (size_t)pix_rows(fmt, height), fmt};
+}
+
+// Where the grouped rectangles of a device-output pass go (cc_detect_batch_to_device): the caller's device buffers, with
+// d_offsets already at the pass's first frame. d_offsets null: a host-output pass, whose candidates go to its sink.
+struct DeviceOutput {
+  cc_rect* d_out = nullptr;
+  int cap = 0;
+  int32_t* d_offsets = nullptr;
+  int min_neighbors = 0;
+  explicit operator bool() const { return d_offsets != nullptr; }
+};
+
+// How run_batch runs a batch. want_results false: launches only, nothing is read back (cc_detect_batch_device_only).
+// debug: the windows' exit codes and sums are kept (cc_detect_debug_windows). defer_last: the batch's last pass stays pending
+// when the call returns (cc_detect_batch_submit). dev: a device-output batch.
+struct BatchOptions {
+  bool want_results = true, debug = false, defer_last = false;
+  DeviceOutput dev;
+};
+
 }  // namespace ccamd
 
 using namespace ccamd;
@@ -249,7 +279,9 @@ struct cc_detector {
   int cand_cap = 0;
   // The pass launched last, not yet fetched (run_batch): inside a batch that is what lets the host side of pass i overlap
   // the device side of pass i + 1; across calls (cc_detect_batch_submit) it lets the first pass of the next batch overlap
-  // the last pass of this one. `sink` receives the pass's candidates when it is retired.
+  // the last pass of this one. `sink` receives the pass's candidates when it is retired. A device-output pass (`dev`) is a
+  // pass like any other whose launch is followed by the ordering and grouping kernels (enqueue_group): retiring it only
+  // looks at its raw count, and there is nothing to fetch unless it has to be redone (retire_pending).
   struct PendingPass {
     bool active = false;
     Plan* plan = nullptr;
@@ -259,7 +291,9 @@ struct cc_detector {
     int cap = 0;       // capacity of the candidate lists the pass was launched with
     unsigned gen = 0;  // generation of the candidate lists it wrote into
     bool debug = false;
+    ccamd::DeviceOutput dev;
     std::shared_ptr<ccamd::BatchSink> sink;
+    void drop() { active = false, sink.reset(); }  // nobody fetches it: its results are left where they are
   } pending;
   unsigned list_gen = 0;  // bumped whenever the candidate lists are released and regrown
   int next_slot = 0;      // result / integral slot the next pass uses (alternates, also across calls)
@@ -821,52 +855,86 @@ static cc_status run_device_pass(cc_detector* d, Plan* P, const uint8_t* dframes
 
 // Colour formats: row_stride counts bytes (width * bytes per pixel at least) and, with more than one frame, frame_stride must
 // hold a whole frame of the format. Gray frames are checked as they always were.
-static cc_status check_frame_args(const cc_detector* d, const uint8_t* frames, int n_frames, int width, int height,
-                                  size_t row_stride, const cc_detect_params* p, const char* who, int fmt = CC_PIX_GRAY8,
-                                  size_t frame_stride = 0) {
-  if (!d || !p || (!frames && n_frames > 0)) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
-  const int bpp = pix_bytes(fmt);
-  if (bpp == 0) return set_error(CC_ERR_INVALID_ARG, "%s: unknown pixel format %d", who, fmt);
-  if (n_frames < 0 || width < 1 || height < 1 || row_stride < (size_t)width * bpp)
-    return set_error(CC_ERR_INVALID_ARG, "%s: bad frame geometry (%dx%d, stride %zu, n %d)", who, width, height, row_stride, n_frames);
-  if (fmt != CC_PIX_GRAY8 && n_frames > 1 &&
-      frame_stride < (size_t)(pix_rows(fmt, height) - 1) * row_stride + (size_t)width * bpp)
-    return set_error(CC_ERR_INVALID_ARG, "%s: frame stride %zu shorter than one frame of pixel format %d", who, frame_stride, fmt);
-  if (width > 32768 || height > 32768) return set_error(CC_ERR_UNSUPPORTED, "%s: frames larger than 32768 px per side", who);
+static cc_status check_frame_args(const cc_detector* d, const FrameSet& F, const cc_detect_params* p, const char* who) {
+  if (!d || !p || (!F.frames && F.n_frames > 0)) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
+  const int bpp = pix_bytes(F.fmt);
+  if (bpp == 0) return set_error(CC_ERR_INVALID_ARG, "%s: unknown pixel format %d", who, F.fmt);
+  if (F.n_frames < 0 || F.width < 1 || F.height < 1 || F.row_stride < (size_t)F.width * bpp)
+    return set_error(CC_ERR_INVALID_ARG, "%s: bad frame geometry (%dx%d, stride %zu, n %d)", who, F.width, F.height, F.row_stride, F.n_frames);
+  if (F.fmt != CC_PIX_GRAY8 && F.n_frames > 1 &&
+      F.frame_stride < (size_t)(pix_rows(F.fmt, F.height) - 1) * F.row_stride + (size_t)F.width * bpp)
+    return set_error(CC_ERR_INVALID_ARG, "%s: frame stride %zu shorter than one frame of pixel format %d", who, F.frame_stride, F.fmt);
+  if (F.width > 32768 || F.height > 32768) return set_error(CC_ERR_UNSUPPORTED, "%s: frames larger than 32768 px per side", who);
   if (!(p->scale_factor > 1.0)) return set_error(CC_ERR_INVALID_ARG, "%s: scaleFactor must be > 1", who);
+  return CC_OK;
+}
+
+// The candidate lists of BOTH slots are freed (run_device_pass allocates them again, `raw` and half as many entries long),
+// so every pass launched before this belongs to an older generation of the lists.
+static void grow_candidate_lists(cc_detector* d, int raw) {
+  d->cand_cap = raw + raw / 2;
+  for (int s = 0; s < 2; s++) {
+    d->d_cands[s].release();
+    d->d_out[s].release();
+  }
+  d->list_gen++;
+}
+
+// A pass's two counters (raw and filtered candidates) travel to the pinned h_counts behind its kernels; pass_done[slot]
+// tells when they have arrived.
+static cc_status read_back_counts(cc_detector* d, int slot) {
+  CC_HIP(hipMemcpyAsync(d->h_counts + 2 * slot, d->d_counts[slot].p, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+  CC_HIP(hipEventRecord(d->pass_done[slot], d->stream));
+  return CC_OK;
+}
+
+// Device-output pass: behind the pass's kernels on the detector's stream, the ordering and grouping kernels append its
+// rectangles to the caller's buffers at the batch's running total (d_group_state[0]). They drop out when the pass's list
+// overflowed or a pass before it set the abort word (GroupGuard). Runs for a plan without scales too (run_device_pass has
+// zeroed the counters by then): that is what writes such a pass's offsets.
+static cc_status enqueue_group(cc_detector* d, const cc_detector::PendingPass& ps) {
+  // sized here, where cand_cap is known; allocates only while the detector's lists or passes are still growing
+  CC_HIP(d->group.ensure((size_t)std::max(d->cand_cap, 1), (size_t)d->pass_capacity, true));
+  const GroupGuard g{d->d_counts[ps.slot].p, d->cand_cap, d->d_group_state.p + 1};
+  {
+    EvScope ev(d, EV_GROUP, d->stream);
+    launch_order_candidates(d->stream, g, d->d_out[ps.slot].p, ps.nf, d->group);
+    launch_group_frames(d->stream, g, d->group.ordered.p, d->group.seg.p, ps.nf, ps.dev.min_neighbors, 0.2, d->group, ps.dev.d_out,
+                        ps.dev.cap, ps.dev.d_offsets, d->d_group_state.p);
+  }
+  CC_HIP(hipGetLastError());
   return CC_OK;
 }
 
 // Fetches the results of the pending pass and hands them to its sink. On candidate-list overflow the lists grow and the
 // pass is redone synchronously. Growing frees the lists of BOTH slots; a pass is judged against the capacity it was
 // launched with and against the generation of the lists it wrote into (stale generation => redone as well).
+// Device-output passes append at a running total, so unlike host-output passes they must be redone in batch order. One that
+// overflowed has written nothing and has set the abort word, so the pass launched behind it has written nothing either;
+// that pass is stale by then (an overflow always grows the lists: raw > ps.cap at the current generation means ps.cap ==
+// cand_cap), and run_batch retires it, and so redoes it from its frames, still in their staging slot, before it launches the
+// next pass. Here the redo clears the abort word first and runs the grouping kernels again behind the pass.
 static cc_status retire_pending(cc_detector* d) {
   if (!d->pending.active) return CC_OK;
   cc_detector::PendingPass ps = d->pending;
-  d->pending.active = false;
-  d->pending.sink.reset();
+  d->pending.drop();
   std::vector<CandOut> got;
   for (;;) {
     CC_HIP(hipEventSynchronize(d->pass_done[ps.slot]));
     const int raw = d->h_counts[2 * ps.slot], kept = d->h_counts[2 * ps.slot + 1];
     if (raw > ps.cap || ps.gen != d->list_gen) {
       CC_HIP(hipStreamSynchronize(d->stream));
-      if (raw > d->cand_cap) {
-        d->cand_cap = raw + raw / 2;
-        d->d_cands[0].release();
-        d->d_cands[1].release();
-        d->d_out[0].release();
-        d->d_out[1].release();
-        d->list_gen++;
-      }
+      if (raw > d->cand_cap) grow_candidate_lists(d, raw);
+      if (ps.dev) CC_HIP(hipMemsetAsync(d->d_group_state.p + 1, 0, sizeof(int), d->stream));
       cc_status st2 = run_device_pass(d, ps.plan, ps.dptr, ps.nf, ps.rs, ps.fs, ps.debug, ps.slot, false);
       if (st2 != CC_OK) return st2;
       ps.cap = d->cand_cap;
       ps.gen = d->list_gen;
-      CC_HIP(hipMemcpyAsync(d->h_counts + 2 * ps.slot, d->d_counts[ps.slot].p, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-      CC_HIP(hipEventRecord(d->pass_done[ps.slot], d->stream));
+      if (cc_status gs = ps.dev ? enqueue_group(d, ps) : CC_OK; gs != CC_OK) return gs;
+      if (cc_status cs = read_back_counts(d, ps.slot); cs != CC_OK) return cs;
       continue;
     }
+    if (ps.dev) return CC_OK;  // its rectangles are in the caller's buffers: nothing to fetch, nobody to hand them to
     got.resize((size_t)kept);
     if (kept > 0) {  // the copy stream is free to run while the main stream executes the next pass
       CC_HIP(hipMemcpyAsync(got.data(), d->d_out[ps.slot].p, (size_t)kept * sizeof(CandOut), hipMemcpyDeviceToHost, d->copy_stream));
@@ -1004,14 +1072,13 @@ static cc_status ensure_pipeline_objects(cc_detector* d) {
 // Single host image: one pass on one stream, replayed from a hipGraph once the buffers are sized. Hands the candidates to
 // `sink` and sets `delivered`, or leaves it false when the candidate lists overflowed: the ordinary path then grows the
 // lists and redoes the pass.
-static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* frames, int width, int height, size_t row_stride, int fmt,
-                                        BatchSink& sink, bool* delivered) {
+static cc_status run_single_image_graph(cc_detector* d, Plan* P, const FrameSet& F, BatchSink& sink, bool* delivered) {
   *delivered = false;
-  const size_t rs = (size_t)align_up(width, 4), fs = rs * (size_t)height;
-  const bool color = fmt != CC_PIX_GRAY8;
+  const size_t rs = (size_t)align_up(F.width, 4), fs = rs * (size_t)F.height;
+  const bool color = F.fmt != CC_PIX_GRAY8;
   // colour: rows of width * bpp bytes (planar: 3 * height rows of width) at a pitch of their own
-  const int crows = pix_rows(fmt, height);
-  const size_t cw = (size_t)width * pix_bytes(fmt), cpitch = (size_t)align_up((int)cw, 4), cfs = cpitch * (size_t)crows;
+  const int crows = pix_rows(F.fmt, F.height);
+  const size_t cw = (size_t)F.width * pix_bytes(F.fmt), cpitch = (size_t)align_up((int)cw, 4), cfs = cpitch * (size_t)crows;
   uint8_t*& hbuf = color ? d->h_color_frame : d->h_frame;
   size_t& hbytes = color ? d->h_color_frame_bytes : d->h_frame_bytes;
   const size_t hneed = color ? cfs : fs;
@@ -1023,9 +1090,9 @@ static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* 
     hbytes = hneed;
   }
   if (color)
-    for (int y = 0; y < crows; y++) std::memcpy(hbuf + (size_t)y * cpitch, frames + (size_t)y * row_stride, cw);
+    for (int y = 0; y < crows; y++) std::memcpy(hbuf + (size_t)y * cpitch, F.frames + (size_t)y * F.row_stride, cw);
   else
-    for (int y = 0; y < height; y++) std::memcpy(d->h_frame + (size_t)y * rs, frames + (size_t)y * row_stride, (size_t)width);
+    for (int y = 0; y < F.height; y++) std::memcpy(d->h_frame + (size_t)y * rs, F.frames + (size_t)y * F.row_stride, (size_t)F.width);
   CC_HIP(d->d_frames.ensure(fs * (size_t)d->pass_capacity * 2));
   if (color) {
     if (d->d_color.n < cfs && d->d_color.p && d->front_stream) CC_HIP(hipStreamSynchronize(d->front_stream));  // batch conversions
@@ -1034,7 +1101,7 @@ static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* 
   auto body = [&]() -> cc_status {
     if (color) {
       CC_HIP(hipMemcpyAsync(d->d_color.p, d->h_color_frame, cfs, hipMemcpyHostToDevice, d->stream));
-      launch_to_gray(d->stream, fmt, d->d_color.p, cpitch, cfs, width, height, 1, d->d_frames.p, rs, fs);
+      launch_to_gray(d->stream, F.fmt, d->d_color.p, cpitch, cfs, F.width, F.height, 1, d->d_frames.p, rs, fs);
     } else
       CC_HIP(hipMemcpyAsync(d->d_frames.p, d->h_frame, fs, hipMemcpyHostToDevice, d->stream));
     cc_status s2 = run_device_pass(d, P, d->d_frames.p, 1, rs, fs, false, 0, true);
@@ -1053,12 +1120,12 @@ static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* 
   }
   bool launched = false;
   d->last_call_graph = 0;
-  hipGraphExec_t& gexec = P->graph_exec[fmt];
-  if (gexec && P->graph_key[fmt] == key_now()) {
+  hipGraphExec_t& gexec = P->graph_exec[F.fmt];
+  if (gexec && P->graph_key[F.fmt] == key_now()) {
     CC_HIP(hipGraphLaunch(gexec, d->stream));
     launched = true;
     d->last_call_graph = 1;
-  } else if (P->graph_warm[fmt]) {
+  } else if (P->graph_warm[F.fmt]) {
     if (gexec) (void)hipGraphExecDestroy(gexec);
     gexec = nullptr;
     hipGraph_t graph = nullptr;
@@ -1089,7 +1156,7 @@ static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* 
       gexec = nullptr;
       d->use_graph = 0;  // ordinary launches from now on (this call included)
     } else {
-      P->graph_key[fmt] = key_now();
+      P->graph_key[F.fmt] = key_now();
       d->graph_captures++;
       CC_HIP(hipGraphLaunch(gexec, d->stream));
       launched = true;
@@ -1099,7 +1166,7 @@ static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* 
   if (!launched) {
     const cc_status stt = body();
     if (stt != CC_OK) return stt;
-    P->graph_warm[fmt] = true;  // every buffer now has its size: the next call can be captured
+    P->graph_warm[F.fmt] = true;  // every buffer now has its size: the next call can be captured
   }
   CC_HIP(hipStreamSynchronize(d->stream));
   const int raw = d->h_counts[0], kept = d->h_counts[1];
@@ -1109,7 +1176,7 @@ static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* 
       CC_HIP(hipMemcpyAsync(got.data(), d->d_out[0].p, (size_t)kept * sizeof(CandOut), hipMemcpyDeviceToHost, d->stream));
       CC_HIP(hipStreamSynchronize(d->stream));
     }
-    sink.consume(0, 1, got);
+    if (sink.consume) sink.consume(0, 1, got);
     *delivered = true;
   }
   return CC_OK;
@@ -1127,9 +1194,9 @@ static cc_status run_single_image_graph(cc_detector* d, Plan* P, const uint8_t* 
 // d_color, where stage_host_frames has put host frames), so a redone pass re-reads gray frames like any other. The rule holds
 // only while every pass uses the same slot pitch: the device slots are gray frames of the plan (a pending pass of another
 // plan is retired first), the pinned slots have one pitch for every format (stage_host_frames).
-static cc_status stage_pass(cc_detector* d, const std::shared_ptr<BatchSink>& sink, const uint8_t* frames, int on_device, int width, int height,
-                            size_t row_stride, size_t frame_stride, int fmt, hipStream_t front, int pf0, int pnf, const uint8_t** where) {
-  const size_t rs = (size_t)align_up(width, 4), fs = rs * (size_t)height;
+static cc_status stage_pass(cc_detector* d, const std::shared_ptr<BatchSink>& sink, const FrameSet& F, hipStream_t front, int pf0, int pnf,
+                            const uint8_t** where) {
+  const size_t rs = (size_t)align_up(F.width, 4), fs = rs * (size_t)F.height;
   const size_t need = fs * (size_t)d->pass_capacity * kStageSlots;
   if (d->d_frames.n < need && d->pending.active) {
     // Growing the staging area frees it, and the unfetched pass still names its frames there (round-3 advisor finding).
@@ -1141,70 +1208,64 @@ static cc_status stage_pass(cc_detector* d, const std::shared_ptr<BatchSink>& si
   const int sslot = d->stage_slot;
   d->stage_slot = (d->stage_slot + 1) % kStageSlots;
   uint8_t* stage = d->d_frames.p + (size_t)sslot * fs * (size_t)d->pass_capacity;
-  if (fmt == CC_PIX_GRAY8) {
-    const cc_status st2 = stage_host_frames(d, frames + (size_t)pf0 * frame_stride, pnf, width, height, row_stride, frame_stride, stage, rs,
+  if (F.fmt == CC_PIX_GRAY8) {
+    const cc_status st2 = stage_host_frames(d, F.frames + (size_t)pf0 * F.frame_stride, pnf, F.width, F.height, F.row_stride, F.frame_stride, stage, rs,
                                             fs, sslot, front);
     if (st2 != CC_OK) return st2;
     *where = stage;
     return CC_OK;
   }
-  const uint8_t* csrc = frames + (size_t)pf0 * frame_stride;
-  size_t crs = row_stride, cfs = frame_stride;
-  if (!on_device) {  // the colour bytes travel as they are, like gray frames, into d_color
-    const int crows = pix_rows(fmt, height);
-    const size_t cw = (size_t)width * pix_bytes(fmt);
+  const uint8_t* csrc = F.frames + (size_t)pf0 * F.frame_stride;
+  size_t crs = F.row_stride, cfs = F.frame_stride;
+  if (!F.on_device) {  // the colour bytes travel as they are, like gray frames, into d_color
+    const int crows = pix_rows(F.fmt, F.height);
+    const size_t cw = (size_t)F.width * pix_bytes(F.fmt);
     crs = (size_t)align_up((int)cw, 4);
     cfs = crs * (size_t)crows;
     const size_t cneed = cfs * (size_t)d->pass_capacity;
     if (d->d_color.n < cneed && d->d_color.p) CC_HIP(hipStreamSynchronize(front));  // the last k_to_gray may still read it
     CC_HIP(d->d_color.ensure(cneed));
-    const cc_status st2 = stage_host_frames(d, csrc, pnf, (int)cw, crows, row_stride, frame_stride, d->d_color.p, crs, cfs, sslot, front);
+    const cc_status st2 = stage_host_frames(d, csrc, pnf, (int)cw, crows, F.row_stride, F.frame_stride, d->d_color.p, crs, cfs, sslot, front);
     if (st2 != CC_OK) return st2;
     csrc = d->d_color.p;
   }
   {
     EvScope ev(d, EV_RESIZE, front);  // the conversion's time counts as pyramid time (include/cascadeclassifier_amd.h)
-    launch_to_gray(front, fmt, csrc, crs, cfs, width, height, pnf, stage, rs, fs);
+    launch_to_gray(front, F.fmt, csrc, crs, cfs, F.width, F.height, pnf, stage, rs, fs);
   }
   CC_HIP(hipGetLastError());
   *where = stage;
   return CC_OK;
 }
 
-// Runs the batch in passes. `consume` (optional) receives the filtered candidates of each pass (frame indices made
-// global) on the calling thread. With two or more frames the batch is cut into at least two passes and the host side
-// of pass i (copy-back + consume) overlaps the device side of pass i+1.
-// `defer_last`: the batch's last pass stays pending when the call returns (cc_detect_batch_submit); its candidates reach
+// The pass loop of run_batch: runs the batch in passes. `sink->consume` (optional) receives the filtered candidates of each
+// pass (frame indices made global) on the calling thread. With two or more frames the batch is cut into at least two passes
+// and the host side of pass i (copy-back + consume) overlaps the device side of pass i+1.
+// `opt.defer_last`: the batch's last pass stays pending when the call returns (cc_detect_batch_submit); its candidates reach
 // `consume` when the next call -- or cc_detect_batch_collect -- retires it.
-// `fmt` (CC_PIX_*): colour frames become gray frames in the staging slots (stage_pass) before the pass reads them.
-template <class Consume>
-static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
-                           size_t row_stride, size_t frame_stride, int fmt, const cc_detect_params* p, bool want_results, bool debug,
-                           Consume consume_fn, bool defer_last = false, std::shared_ptr<BatchSink> shared_sink = nullptr) {
+// `opt.dev`: a device-output batch. Its passes go through this same loop; each is followed by enqueue_group, and retiring
+// one delivers nothing (retire_pending, which also has the rule that keeps their output in order).
+// `F.fmt` (CC_PIX_*): colour frames become gray frames in the staging slots (stage_pass) before the pass reads them.
+static cc_status run_batch_passes(cc_detector* d, const FrameSet& F, const cc_detect_params* p, const std::shared_ptr<BatchSink>& sink,
+                                  const BatchOptions& opt) {
+  const bool want_results = opt.want_results, debug = opt.debug, defer_last = opt.defer_last, to_device = (bool)opt.dev;
+  const int n_frames = F.n_frames;
   cc_status stt = ensure_device(d->device);
   if (stt != CC_OK) return stt;
-  std::shared_ptr<BatchSink> sink = shared_sink;
-  if (!sink) {
-    sink = std::make_shared<BatchSink>();
-    sink->consume = consume_fn;
-  }
   // A pass of an earlier (submitted) batch may still be pending. It can stay so -- and overlap this call's first pass --
-  // only if this call runs ordinary passes on the same plan; everything else fetches it first.
-  const bool single_image_graph = n_frames == 1 && !on_device && want_results && !debug && !d->profiling && d->use_graph;
+  // only if this call runs ordinary host-output passes on the same plan; everything else fetches it first.
+  const bool single_image_graph = n_frames == 1 && !F.on_device && want_results && !debug && !to_device && !d->profiling && d->use_graph;
   if (d->pending.active) {
     bool same_plan = false;
     for (auto& pl : d->plans)
-      if (pl.get() == d->pending.plan && pl->w == width && pl->h == height && same_params(pl->p, *p)) same_plan = true;
-    if (!same_plan || debug || !want_results || single_image_graph || n_frames < 1) retire_foreign(d);  // (a new plan may evict the pending pass's)
+      if (pl.get() == d->pending.plan && pl->w == F.width && pl->h == F.height && same_params(pl->p, *p)) same_plan = true;
+    if (!same_plan || debug || !want_results || to_device || single_image_graph || n_frames < 1) retire_foreign(d);  // (a new plan may evict the pending pass's)
   }
   spec_poll(d);
   Plan* P = nullptr;
-  stt = build_plan(d, width, height, *p, &P);
-  if (stt != CC_OK) return stt;
-  stt = ensure_spec_tiles(d, P);
-  if (stt != CC_OK) return stt;
-  stt = ensure_pipeline_objects(d);
-  if (stt != CC_OK) return stt;
+  if (stt = build_plan(d, F.width, F.height, *p, &P); stt != CC_OK) return stt;
+  if (stt = ensure_spec_tiles(d, P); stt != CC_OK) return stt;
+  if (stt = ensure_pipeline_objects(d); stt != CC_OK) return stt;
   hipStream_t front = d->overlap_front ? d->front_stream : d->stream;
   // Frames produced by earlier work on a stream the CALLER gave us (cc_detector_set_stream) must be complete before the
   // pyramid reads them. On the detector's own stream there is only our own earlier work -- a pending pass of the batch
@@ -1215,12 +1276,17 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
   }
   if (single_image_graph) {
     bool delivered = false;
-    stt = run_single_image_graph(d, P, frames, width, height, row_stride, fmt, *sink, &delivered);
+    stt = run_single_image_graph(d, P, F, *sink, &delivered);
     if (stt != CC_OK || delivered) return stt;
   }
   const std::vector<int> sizes = pass_sizes(n_frames, d->max_batch, d->pipeline_passes, d->pipeline_passes_set != 0, want_results, defer_last);
   for (int v : sizes) d->pass_capacity = std::max(d->pass_capacity, v);  // the workspace only ever grows
-  const bool staged = !on_device || fmt != CC_PIX_GRAY8;
+  if (to_device) {  // the batch's running total and the abort word start at zero; a batch without frames has one offset
+    CC_HIP(d->d_group_state.ensure(2));
+    CC_HIP(hipMemsetAsync(d->d_group_state.p, 0, 2 * sizeof(int), d->stream));
+    if (sizes.empty()) CC_HIP(hipMemsetAsync(opt.dev.d_offsets, 0, sizeof(int32_t), d->stream));
+  }
+  const bool staged = !F.on_device || F.fmt != CC_PIX_GRAY8;
   const uint8_t* prestaged = nullptr;
   // spec_poll may have installed another kernel: a pending pass keeps the results it was launched for, nothing to redo.
   int f0 = 0;
@@ -1231,18 +1297,19 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     ps.f0 = f0;
     ps.nf = sizes[pi];
     ps.slot = slot;
-    ps.rs = row_stride;
-    ps.fs = frame_stride;
+    ps.rs = F.row_stride;
+    ps.fs = F.frame_stride;
     ps.debug = debug;
+    ps.dev = opt.dev;
+    if (to_device) ps.dev.d_offsets += f0;
     ps.sink = sink;
     if (!staged) {
-      ps.dptr = frames + (size_t)f0 * frame_stride;
+      ps.dptr = F.frames + (size_t)f0 * F.frame_stride;
     } else {
-      ps.rs = (size_t)align_up(width, 4);
-      ps.fs = ps.rs * (size_t)height;
+      ps.rs = (size_t)align_up(F.width, 4);
+      ps.fs = ps.rs * (size_t)F.height;
       if (!prestaged) {
-        stt = stage_pass(d, sink, frames, on_device, width, height, row_stride, frame_stride, fmt, front, f0, sizes[pi], &prestaged);
-        if (stt != CC_OK) return stt;
+        if (stt = stage_pass(d, sink, F, front, f0, sizes[pi], &prestaged); stt != CC_OK) return stt;
       }
       ps.dptr = prestaged;
       prestaged = nullptr;
@@ -1254,34 +1321,31 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
       if (trace_host)
         std::fprintf(stderr, "[ccamd host] pass %zu %-18s +%.3f ms\n", pi, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count());
     };
-    stt = run_device_pass(d, P, ps.dptr, ps.nf, ps.rs, ps.fs, debug, slot);
-    if (stt != CC_OK) return stt;
-    th("launched");
+    if (stt = run_device_pass(d, P, ps.dptr, ps.nf, ps.rs, ps.fs, debug, slot); stt != CC_OK) return stt;
     ps.cap = d->cand_cap;
     ps.gen = d->list_gen;
+    if (stt = to_device ? enqueue_group(d, ps) : CC_OK; stt != CC_OK) return stt;
+    th("launched");
     if (staged && pi + 1 < sizes.size() && want_results) {  // the next pass's frames travel while this pass runs
-      stt = stage_pass(d, sink, frames, on_device, width, height, row_stride, frame_stride, fmt, front, f0 + sizes[pi], sizes[pi + 1],
-                       &prestaged);
-      if (stt != CC_OK) return stt;
+      if (stt = stage_pass(d, sink, F, front, f0 + sizes[pi], sizes[pi + 1], &prestaged); stt != CC_OK) return stt;
       th("next pass staged");
     }
     if (want_results) {
-      CC_HIP(hipMemcpyAsync(d->h_counts + 2 * slot, d->d_counts[slot].p, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-      CC_HIP(hipEventRecord(d->pass_done[slot], d->stream));
+      if (stt = read_back_counts(d, slot); stt != CC_OK) return stt;
       // fetch the pass launched before this one -- of this batch or, for the first pass, of the batch submitted before --
       // while the device runs this one
-      stt = retire_for(d, sink);
-      if (stt != CC_OK) return stt;
+      if (stt = retire_for(d, sink); stt != CC_OK) return stt;
       th("previous retired");
       ps.active = true;
       d->pending = ps;
+      // device output: dead behind a pass that overflowed, so redone now, before the next pass is launched (retire_pending)
+      if (to_device && ps.gen != d->list_gen)
+        if (stt = retire_pending(d); stt != CC_OK) return stt;
     }
     d->next_slot ^= 1;
   }
-  if (!(defer_last && d->pending.sink == sink)) {
-    stt = retire_for(d, sink);
-    if (stt != CC_OK) return stt;
-  }
+  if (!(defer_last && d->pending.sink == sink))
+    if (stt = retire_for(d, sink); stt != CC_OK) return stt;
   // Profiling: the event pairs of this call are read once their kernels are done. A submitted batch must not wait for that
   // here (the synchronisation would undo the overlap with the next batch -- which is how the round-3 bench first measured
   // its own instrumentation instead of the pipeline): its events are read by cc_detector_get_timings or by the next
@@ -1292,6 +1356,15 @@ static cc_status run_batch(cc_detector* d, const uint8_t* frames, int on_device,
     collect_events(d);
   }
   return CC_OK;
+}
+
+// A batch that failed leaves none of its passes pending: a later call must not deliver to (or, for device output, redo a pass
+// into the buffers of) a call that has returned.
+static cc_status run_batch(cc_detector* d, const FrameSet& F, const cc_detect_params* p, const std::shared_ptr<BatchSink>& sink,
+                           const BatchOptions& opt = BatchOptions{}) {
+  const cc_status st = run_batch_passes(d, F, p, sink, opt);
+  if (st != CC_OK && d->pending.active && d->pending.sink == sink) d->pending.drop();
+  return st;
 }
 
 static void sort_candidates(std::vector<CandOut>& v) {
@@ -1325,6 +1398,31 @@ static void group_pass(int min_neighbors, int f0, int nf, std::vector<CandOut>& 
     for (int t = 0; t < nthr; t++) th.emplace_back(work, (int)((long long)nf * t / nthr), (int)((long long)nf * (t + 1) / nthr));
     for (auto& t : th) t.join();
   }
+}
+
+// The frames' rectangles one after the other into out (below cap) and their offsets into offsets; returns how many there are.
+static long long flatten_grouped(const std::vector<std::vector<cc_rect>>& grouped, cc_rect* out, int cap, int32_t* offsets) {
+  long long total = 0;
+  for (size_t f = 0; f < grouped.size(); f++) {
+    offsets[f] = (int32_t)total;
+    for (const cc_rect& r : grouped[f]) {
+      if (total < cap) out[total] = r;
+      total++;
+    }
+  }
+  offsets[grouped.size()] = (int32_t)total;
+  return total;
+}
+
+// One host image through run_batch: the candidates of all its passes in OpenCV's single-threaded order.
+static cc_status image_candidates(cc_detector* d, const FrameSet& F, const cc_detect_params* p, bool debug, std::vector<CandOut>& cands) {
+  auto sink = std::make_shared<BatchSink>();
+  sink->consume = [&cands](int, int, std::vector<CandOut>& c) { cands.insert(cands.end(), c.begin(), c.end()); };
+  BatchOptions opt;
+  opt.debug = debug;
+  const cc_status st = run_batch(d, F, p, sink, opt);
+  if (st == CC_OK) sort_candidates(cands);
+  return st;
 }
 
 // Switches the detector over to the compiled modules (spec_load is the device half). Owning thread only.
@@ -1605,8 +1703,7 @@ void cc_detector_destroy(cc_detector* d) {
   (void)hipSetDevice(d->device);
   if (d->pending.active) {  // a submitted batch nobody collected: let the device finish, drop the results
     (void)hipStreamSynchronize(d->stream);
-    d->pending.active = false;
-    d->pending.sink.reset();
+    d->pending.drop();
   }
   delete d;
 }
@@ -1686,10 +1783,12 @@ cc_status cc_detector_get_timings(cc_detector* d, cc_detector_timings* t, int re
 
 cc_status cc_detect_batch_device_only(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
                                       size_t row_stride, size_t frame_stride, const cc_detect_params* p) {
-  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch_device_only");
+  const FrameSet F{frames, on_device, n_frames, width, height, row_stride, frame_stride, CC_PIX_GRAY8};
+  cc_status st = check_frame_args(d, F, p, "cc_detect_batch_device_only");
   if (st != CC_OK) return st;
-  return run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, CC_PIX_GRAY8, p, false, false,
-                   [](int, int, std::vector<CandOut>&) {});
+  BatchOptions opt;
+  opt.want_results = false;
+  return run_batch(d, F, p, std::make_shared<BatchSink>(), opt);
 }
 
 cc_status cc_detect_batch(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
@@ -1701,7 +1800,8 @@ cc_status cc_detect_batch(cc_detector* d, const uint8_t* frames, int on_device, 
 cc_status cc_detect_batch_fmt(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
                               size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p, cc_rect* out,
                               int cap, int32_t* offsets) {
-  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch", pixel_format, frame_stride);
+  const FrameSet F{frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format};
+  cc_status st = check_frame_args(d, F, p, "cc_detect_batch");
   if (st != CC_OK) return st;
   if (!offsets || (cap > 0 && !out) || cap < 0) return set_error(CC_ERR_INVALID_ARG, "cc_detect_batch: bad output buffers");
   const auto t_start = std::chrono::steady_clock::now();
@@ -1709,23 +1809,16 @@ cc_status cc_detect_batch_fmt(cc_detector* d, const uint8_t* frames, int on_devi
   size_t n_cands = 0;
   std::vector<std::vector<cc_rect>> grouped((size_t)n_frames);
   const int min_neighbors = p->min_neighbors;
-  auto consume = [&](int f0, int nf, std::vector<CandOut>& cands) {
+  auto sink = std::make_shared<BatchSink>();
+  sink->consume = [&](int f0, int nf, std::vector<CandOut>& cands) {
     const auto t0 = std::chrono::steady_clock::now();
     n_cands += cands.size();
     group_pass(min_neighbors, f0, nf, cands, grouped);
     group_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   };
-  st = run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format, p, true, false, consume);
+  st = run_batch(d, F, p, sink);
   if (st != CC_OK) return st;
-  long long total = 0;
-  for (int f = 0; f < n_frames; f++) {
-    offsets[f] = (int32_t)total;
-    for (const cc_rect& r : grouped[(size_t)f]) {
-      if (total < cap) out[total] = r;
-      total++;
-    }
-  }
-  offsets[n_frames] = (int32_t)total;
+  const long long total = flatten_grouped(grouped, out, cap, offsets);
   if (std::getenv("CCAMD_TIMING")) {
     const auto t1 = std::chrono::steady_clock::now();
     std::fprintf(stderr, "[ccamd] detect_batch: total %.3f ms, of which sort+group on the host %.3f ms (overlapped), %zu candidates\n",
@@ -1735,99 +1828,23 @@ cc_status cc_detect_batch_fmt(cc_detector* d, const uint8_t* frames, int on_devi
   return CC_OK;
 }
 
-// The device-output batch. The same passes as cc_detect_batch, each followed on the detector's stream by the ordering and
-// grouping kernels, which append to the caller's buffers; at most two passes are in flight (the slots of the results). Per
-// pass the host reads back the two counters of d_counts only (raw and filtered candidates; the raw one decides). A pass that overflowed its candidate list has written nothing, and
-// neither has the pass launched behind it (GroupGuard): the lists grow and the loop goes back to that pass.
+// The device-output batch: the passes of cc_detect_batch through the same loop (run_batch), each followed on the detector's
+// stream by the ordering and grouping kernels, which append to the caller's buffers (enqueue_group). The host reads back the
+// batch's total at the end and nothing else of the results.
 cc_status cc_detect_batch_to_device(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
                                     size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p,
                                     cc_rect* d_out, int cap, int32_t* d_offsets, int* n_total) {
-  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch_to_device", pixel_format, frame_stride);
+  const FrameSet F{frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format};
+  cc_status st = check_frame_args(d, F, p, "cc_detect_batch_to_device");
   if (st != CC_OK) return st;
   if (!d_offsets || !n_total || (cap > 0 && !d_out) || cap < 0)
     return set_error(CC_ERR_INVALID_ARG, "cc_detect_batch_to_device: bad output buffers");
-  st = ensure_device(d->device);
+  BatchOptions opt;
+  opt.dev = DeviceOutput{d_out, cap, d_offsets, p->min_neighbors};
+  st = run_batch(d, F, p, std::make_shared<BatchSink>(), opt);
   if (st != CC_OK) return st;
-  retire_foreign(d);  // a batch submitted earlier and not yet fetched
-  spec_poll(d);
-  Plan* P = nullptr;
-  st = build_plan(d, width, height, *p, &P);
-  if (st != CC_OK) return st;
-  st = ensure_spec_tiles(d, P);
-  if (st != CC_OK) return st;
-  st = ensure_pipeline_objects(d);
-  if (st != CC_OK) return st;
-  hipStream_t front = d->overlap_front ? d->front_stream : d->stream;
-  if (front != d->stream && d->stream != d->own_stream) {  // frames made by earlier work on the caller's stream (run_batch)
-    CC_HIP(hipEventRecord(d->batch_begin, d->stream));
-    CC_HIP(hipStreamWaitEvent(front, d->batch_begin, 0));
-  }
-  const std::vector<int> sizes = pass_sizes(n_frames, d->max_batch, d->pipeline_passes, d->pipeline_passes_set != 0, true, false);
-  for (int v : sizes) d->pass_capacity = std::max(d->pass_capacity, v);
-  CC_HIP(d->d_group_state.ensure(2));
-  CC_HIP(hipMemsetAsync(d->d_group_state.p, 0, 2 * sizeof(int), d->stream));
-  if (sizes.empty()) CC_HIP(hipMemsetAsync(d_offsets, 0, sizeof(int32_t), d->stream));
-  const bool staged = !on_device || pixel_format != CC_PIX_GRAY8;
-  std::vector<int> first((size_t)sizes.size() + 1, 0);  // first frame of each pass
-  for (size_t i = 0; i < sizes.size(); i++) first[i + 1] = first[i] + sizes[i];
-  int slot_of[2] = {0, 0}, cap_of[2] = {0, 0};  // of the passes in flight, by pass index & 1
-  size_t next = 0, done = 0;
-  while (done < sizes.size()) {
-    if (next < sizes.size() && next - done < 2) {
-      const int f0 = first[next], nf = sizes[next], slot = d->next_slot;
-      const uint8_t* dptr = frames + (size_t)f0 * frame_stride;
-      size_t rs = row_stride, fs = frame_stride;
-      if (staged) {  // at most one pass is unretired here, so the staging slot of the pass three back is free (stage_pass)
-        rs = (size_t)align_up(width, 4);
-        fs = rs * (size_t)height;
-        st = stage_pass(d, nullptr, frames, on_device, width, height, row_stride, frame_stride, pixel_format, front, f0, nf, &dptr);
-        if (st != CC_OK) return st;
-      }
-      st = run_device_pass(d, P, dptr, nf, rs, fs, false, slot);
-      if (st != CC_OK) return st;
-      // sized here, where cand_cap is known; allocates only while the detector's lists or passes are still growing
-      CC_HIP(d->group.ensure((size_t)std::max(d->cand_cap, 1), (size_t)d->pass_capacity, true));
-      const GroupGuard g{d->d_counts[slot].p, d->cand_cap, d->d_group_state.p + 1};
-      {
-        EvScope ev(d, EV_GROUP, d->stream);
-        launch_order_candidates(d->stream, g, d->d_out[slot].p, nf, d->group);
-        launch_group_frames(d->stream, g, d->group.ordered.p, d->group.seg.p, nf, p->min_neighbors, 0.2, d->group, d_out, cap, d_offsets + f0,
-                            d->d_group_state.p);
-      }
-      CC_HIP(hipGetLastError());
-      CC_HIP(hipMemcpyAsync(d->h_counts + 2 * slot, d->d_counts[slot].p, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-      CC_HIP(hipEventRecord(d->pass_done[slot], d->stream));
-      slot_of[next & 1] = slot;
-      cap_of[next & 1] = d->cand_cap;
-      d->next_slot ^= 1;
-      next++;
-      continue;
-    }
-    const int slot = slot_of[done & 1];
-    CC_HIP(hipEventSynchronize(d->pass_done[slot]));
-    const int raw = d->h_counts[2 * slot];
-    if (raw > cap_of[done & 1]) {  // retire_pending's grow-and-rerun: this pass and the one behind it wrote nothing
-      CC_HIP(hipStreamSynchronize(d->stream));
-      if (raw > d->cand_cap) {
-        d->cand_cap = raw + raw / 2;
-        for (int s2 = 0; s2 < 2; s2++) {
-          d->d_cands[s2].release();
-          d->d_out[s2].release();
-        }
-        d->list_gen++;
-      }
-      CC_HIP(hipMemsetAsync(d->d_group_state.p + 1, 0, sizeof(int), d->stream));
-      next = done;
-      continue;
-    }
-    done++;
-  }
   int total = 0;
   CC_HIP(copy_sync(&total, d->d_group_state.p, sizeof(int), hipMemcpyDeviceToHost, d->stream));
-  if (d->profiling) {
-    if (d->front_stream) CC_HIP(hipStreamSynchronize(d->front_stream));
-    collect_events(d);
-  }
   *n_total = total;
   if (total > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_detect_batch_to_device: %d rectangles, capacity %d", total, cap);
   return CC_OK;
@@ -1836,7 +1853,6 @@ cc_status cc_detect_batch_to_device(cc_detector* d, const uint8_t* frames, int o
 struct cc_batch_ticket {
   cc_detector* owner = nullptr;
   unsigned long long owner_serial = 0;  // cc_detector::serial of the owner: an address can be reused by a later detector
-  int n_frames = 0;
   std::shared_ptr<BatchSink> sink;
   // Shared with the sink's consume function, NOT owned by the ticket alone: the detector may still hold the sink of a pass
   // it has not fetched when the ticket ends on an error path, and that pass's helper then writes here (round-3 advisor
@@ -1877,27 +1893,22 @@ cc_status cc_detect_batch_submit_fmt(cc_detector* d, const uint8_t* frames, int 
                                      cc_batch_ticket** ticket) {
   if (!ticket) return set_error(CC_ERR_INVALID_ARG, "cc_detect_batch_submit: null ticket pointer");
   *ticket = nullptr;
-  cc_status st = check_frame_args(d, frames, n_frames, width, height, row_stride, p, "cc_detect_batch_submit", pixel_format, frame_stride);
+  const FrameSet F{frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format};
+  cc_status st = check_frame_args(d, F, p, "cc_detect_batch_submit");
   if (st != CC_OK) return st;
   std::unique_ptr<cc_batch_ticket> t(new cc_batch_ticket);
   t->owner = d;
   t->owner_serial = d->serial;
-  t->n_frames = n_frames;
   t->grouped = std::make_shared<std::vector<std::vector<cc_rect>>>((size_t)n_frames);
   t->sink = std::make_shared<BatchSink>();
   std::shared_ptr<std::vector<std::vector<cc_rect>>> grouped = t->grouped;
   const int min_neighbors = p->min_neighbors;
   t->sink->consume = [grouped, min_neighbors](int f0, int nf, std::vector<CandOut>& cands) { group_pass(min_neighbors, f0, nf, cands, *grouped); };
   t->sink->async_consume = true;  // passes of a batch cover disjoint frames: their helpers never touch the same entry of `grouped`
-  st = run_batch(d, frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format, p, true, false,
-                 [](int, int, std::vector<CandOut>&) {}, /*defer_last=*/true, t->sink);
-  if (st != CC_OK) {
-    if (d->pending.active && d->pending.sink == t->sink) {  // the batch failed: its unfetched pass delivers to nobody
-      d->pending.active = false;
-      d->pending.sink.reset();
-    }
-    return st;
-  }
+  BatchOptions opt;
+  opt.defer_last = true;
+  st = run_batch(d, F, p, t->sink, opt);
+  if (st != CC_OK) return st;
   *ticket = t.release();
   return CC_OK;
 }
@@ -1926,16 +1937,7 @@ cc_status cc_detect_batch_collect(cc_detector* d, cc_batch_ticket* t, cc_rect* o
   if (t->sink->status != CC_OK) return set_error(t->sink->status, "cc_detect_batch_collect: %s", t->sink->error.c_str());
   st = wait_sink_jobs(*t->sink, "cc_detect_batch_collect");  // the helper threads that sort + group what the passes delivered
   if (st != CC_OK) return st;
-  const std::vector<std::vector<cc_rect>>& grouped = *t->grouped;
-  long long total = 0;
-  for (int f = 0; f < t->n_frames; f++) {
-    offsets[f] = (int32_t)total;
-    for (const cc_rect& r : grouped[(size_t)f]) {
-      if (total < cap) out[total] = r;
-      total++;
-    }
-  }
-  offsets[t->n_frames] = (int32_t)total;
+  const long long total = flatten_grouped(*t->grouped, out, cap, offsets);
   if (total > cap) {
     (void)own.release();  // the results stay in the ticket: collect again with room for offsets[n_frames] rectangles
     return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_detect_batch_collect: %lld rectangles, capacity %d", total, cap);
@@ -1954,8 +1956,7 @@ cc_status cc_detect_batch_discard(cc_detector* d, cc_batch_ticket* t) {
   if (d->pending.active && d->pending.sink == t->sink) {  // let its last pass finish and drop what it delivers
     cc_status st = ensure_device(d->device);
     if (st != CC_OK) {  // the pass cannot be fetched: cut it loose (its helper, if any, keeps `grouped` alive by itself)
-      d->pending.active = false;
-      d->pending.sink.reset();
+      d->pending.drop();
       return st;
     }
     (void)retire_pending(d);
@@ -1988,15 +1989,14 @@ cc_status cc_detect_multiscale_levels(cc_detector* d, const uint8_t* gray, int w
 cc_status cc_detect_multiscale_levels_fmt(cc_detector* d, const uint8_t* img, int width, int height, size_t row_stride,
                                           int pixel_format, const cc_detect_params* p, cc_rect* out, int32_t* reject_levels,
                                           double* level_weights, int cap, int* n) {
-  cc_status st = check_frame_args(d, img, 1, width, height, row_stride, p, "cc_detect_multiscale_levels", pixel_format);
+  const FrameSet F = host_image(img, width, height, row_stride, pixel_format);
+  cc_status st = check_frame_args(d, F, p, "cc_detect_multiscale_levels");
   if (st != CC_OK) return st;
   if (!n || cap < 0 || (cap > 0 && (!out || !reject_levels || !level_weights)))
     return set_error(CC_ERR_INVALID_ARG, "cc_detect_multiscale_levels: bad output buffers");
   std::vector<CandOut> cands;
-  st = run_batch(d, img, 0, 1, width, height, row_stride, row_stride * (size_t)pix_rows(pixel_format, height), pixel_format, p, true, false,
-                 [&](int, int, std::vector<CandOut>& c) { cands.insert(cands.end(), c.begin(), c.end()); });
+  st = image_candidates(d, F, p, false, cands);
   if (st != CC_OK) return st;
-  sort_candidates(cands);  // OpenCV's single-threaded order
   std::vector<cc_rect> rects;
   std::vector<int> levels;
   std::vector<double> weights;
@@ -2019,14 +2019,13 @@ cc_status cc_detect_multiscale_levels_fmt(cc_detector* d, const uint8_t* img, in
 
 cc_status cc_detect_raw(cc_detector* d, const uint8_t* gray, int width, int height, size_t row_stride, const cc_detect_params* p,
                         int32_t* cand, int cap, int* n) {
-  cc_status st = check_frame_args(d, gray, 1, width, height, row_stride, p, "cc_detect_raw");
+  const FrameSet F = host_image(gray, width, height, row_stride);
+  cc_status st = check_frame_args(d, F, p, "cc_detect_raw");
   if (st != CC_OK) return st;
   if (!n || (cap > 0 && !cand)) return set_error(CC_ERR_INVALID_ARG, "cc_detect_raw: bad output buffers");
   std::vector<CandOut> cands;
-  st = run_batch(d, gray, 0, 1, width, height, row_stride, row_stride * (size_t)height, CC_PIX_GRAY8, p, true, false,
-                 [&](int, int, std::vector<CandOut>& c) { cands.insert(cands.end(), c.begin(), c.end()); });
+  st = image_candidates(d, F, p, false, cands);
   if (st != CC_OK) return st;
-  sort_candidates(cands);
   *n = (int)cands.size();
   for (int i = 0; i < (int)cands.size() && i < cap; i++) {
     const CandOut& c = cands[i];
@@ -2040,12 +2039,12 @@ cc_status cc_detect_raw(cc_detector* d, const uint8_t* gray, int width, int heig
 cc_status cc_detect_debug_windows(cc_detector* d, const uint8_t* gray, int width, int height, size_t row_stride,
                                   const cc_detect_params* p, int32_t* codes, double* sums, uint8_t* visited, int64_t cap,
                                   int64_t* n_windows) {
-  cc_status st = check_frame_args(d, gray, 1, width, height, row_stride, p, "cc_detect_debug_windows");
+  const FrameSet F = host_image(gray, width, height, row_stride);
+  cc_status st = check_frame_args(d, F, p, "cc_detect_debug_windows");
   if (st != CC_OK) return st;
   if (!n_windows) return set_error(CC_ERR_INVALID_ARG, "cc_detect_debug_windows: null count pointer");
-  std::vector<CandOut> cands;
-  st = run_batch(d, gray, 0, 1, width, height, row_stride, row_stride * (size_t)height, CC_PIX_GRAY8, p, true, true,
-                 [&](int, int, std::vector<CandOut>& c) { cands.insert(cands.end(), c.begin(), c.end()); });
+  std::vector<CandOut> cands;  // not reported: the windows' codes and sums are
+  st = image_candidates(d, F, p, true, cands);
   if (st != CC_OK) return st;
   Plan* P = nullptr;
   st = build_plan(d, width, height, *p, &P);

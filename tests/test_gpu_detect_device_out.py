@@ -14,6 +14,7 @@ from tests.util import frame_natural
 pytestmark = pytest.mark.gpu
 
 W, H, N = 320, 240, 5
+ORDER = [1, 3, 0, 2, 4]  # a pass that fits (the flat frame), one that overflows 16 candidates, then frames with candidates
 
 
 def _paste(img, seed, ks):
@@ -41,13 +42,13 @@ def xml(request, haar_xml, lbp_xml):
 
 
 def test_inputs_cover_the_cases(frames, haar_xml, lbp_xml):
-    """On the CPU, with the oracle: a frame with two grouped rectangles at least, one with none, one with more than 16 raw
-    candidates (the regrow test's capacity)."""
+    """On the CPU, with the oracle: a frame with two grouped rectangles at least, frame 1 with no candidate at all, frame 3
+    with more than 16 (the regrow tests' capacity; the device's raw count is at least the oracle's filtered one)."""
     for path in (haar_xml, lbp_xml):
         o = orc.load_cascade_xml(path)
         grouped = [len(orc.detect_multiscale(o, f, 1.1, 2, nthreads=8)) for f in frames]
         raw = [len(orc.detect_raw(o, f, 1.1, nthreads=8).candidates) for f in frames]
-        assert max(grouped) >= 2 and grouped[1] == 0 and raw[1] == 0 and max(raw) > 16, (path, grouped, raw)
+        assert max(grouped) >= 2 and grouped[1] == 0 and raw[1] == 0 and raw[3] > 16 and max(raw) > 16, (path, grouped, raw)
 
 
 def _to_device(p, frames, mn, cap=4096, sf=1.1, **kw):
@@ -113,6 +114,39 @@ def test_regrow_of_the_candidate_lists(xml, frames, monkeypatch):
         _same(q.detect_batch(frames, 1.1, 2), want)
 
 
+def test_regrow_behind_a_pass_that_fitted(xml, frames, monkeypatch):
+    """Frames in ORDER. max_batch 1: five passes of one frame; pass 0 (flat) fits, pass 1 overflows, the pass launched behind
+    it is dropped on the device and redone before pass 3 is launched, with lists that its own count outgrows again.
+    max_batch 2: passes of 2, 2, 1, the first overflows and the second is dead behind it."""
+    perm = np.ascontiguousarray(frames[ORDER])
+    want = cc.CascadeClassifier(xml, max_batch=2).detect_batch(perm, 1.1, 2)
+    monkeypatch.setenv("CCAMD_CAND_CAP", "16")
+    for mb in (1, 2):
+        q = cc.CascadeClassifier(xml, max_batch=mb)
+        assert q.candidate_capacity() == 16
+        _same(_to_device(q, perm, 2, host=perm), want)
+        grown = q.candidate_capacity()
+        assert grown > 16
+        _same(_to_device(q, perm, 2, host=perm), want)
+        assert q.candidate_capacity() == grown
+        _same(q.detect_batch(perm, 1.1, 2), want)
+
+
+def test_frames_smaller_than_the_window(xml, frames):
+    """16x16 frames under a 24x24 window: the plan has no scale, the pass returns before it has a workspace and only the
+    grouping launches run. No rectangle, every offset 0, `out` untouched -- on a fresh detector and on a used one."""
+    import torch
+    small = np.ascontiguousarray(frames[:3, :16, :16])
+    used = cc.CascadeClassifier(xml, max_batch=2)
+    _to_device(used, frames, 2, host=frames)
+    for p in (cc.CascadeClassifier(xml, max_batch=2), used):
+        d_out = torch.full((8, 4), -7, dtype=torch.int32, device="cuda")
+        d_off = torch.full((len(small) + 1,), -7, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        total = p.detect_batch_to_device(small, 1.1, 2, out_ptr=d_out.data_ptr(), cap=8, offsets_ptr=d_off.data_ptr())
+        assert total == 0 and (d_off.cpu().numpy() == 0).all() and (d_out.cpu().numpy() == -7).all()
+
+
 def test_cap_too_small(xml, frames):
     import torch
     p = cc.CascadeClassifier(xml, max_batch=2)
@@ -129,6 +163,8 @@ def test_cap_too_small(xml, frames):
     out, off = d_out.cpu().numpy(), d_off.cpu().numpy()
     assert off.tolist() == np.concatenate([[0], np.cumsum([len(w) for w in want])]).tolist()
     assert (out[:cap] == np.concatenate(want)[:cap]).all() and (out[cap] == -7).all()
+    _same(p.detect_batch(frames, 1.1, 0), want)  # the failed call left no pass pending
+    _same(_to_device(p, frames, 0, host=frames), want)
     with pytest.raises(cc.CascadeError) as err:
         p.detect_batch_to_device(frames, 1.1, 0, out_ptr=d_out.data_ptr(), cap=-1, offsets_ptr=d_off.data_ptr())
     assert err.value.status == L.CC_ERR_INVALID_ARG
