@@ -182,10 +182,8 @@ def test_profiling_counters(lbp_xml):
 def test_candidate_list_overflow_in_a_multi_pass_batch(monkeypatch):
     """A weak cascade passes almost every window: the candidate lists overflow on the first pass of a batch while the next
     pass is already in flight with the old capacity. Both must be redone; every frame's rectangles equal the oracle's."""
-    from tests import cascade_factory as cf
-    cat = orc.haar_catalog(24, 24, 0)
-    feats = cat[[1234]].copy()
-    xml_text = cf.haar_xml(feats, [(np.float32(-1.0), [([(0, -1, 0, np.float32(0.0))], [1.0, 1.0])])], mode="BASIC")
+    from tests import group_cases as gc
+    xml_text = gc.weak_cascade_text()
     import tempfile
     with tempfile.NamedTemporaryFile("w", suffix=".xml", delete=False) as f:
         f.write(xml_text)

@@ -1,6 +1,10 @@
 """cc_detect_batch_to_device against cc_detect_batch on the same frames: the rectangles left in device memory, their order
 and the per-frame offsets must be exactly what the host path returns -- over several passes with a partial last one, host,
-device and colour frames, the grouping thresholds, the specialised kernel, the candidate-list regrow and a short buffer."""
+device and colour frames, the grouping thresholds, the specialised kernel, the candidate-list regrow and a short buffer.
+
+From test_many_candidates_in_a_frame on, with the one-stage cascade of tests/group_cases.py that passes almost every window:
+the order is held to the oracle's raw candidates sorted by (scale, gy, gx), frames of thousands of candidates, a pass of 300
+frames, and a caller's stream with no device-wide synchronisation."""
 import os
 
 import numpy as np
@@ -9,6 +13,7 @@ import pytest
 import cascadeclassifier_amd as cc
 from cascadeclassifier_amd import _lib as L
 from oracle import oracle as orc
+from tests import group_cases as gc
 from tests.util import frame_natural
 
 pytestmark = pytest.mark.gpu
@@ -200,3 +205,88 @@ def test_unknown_pixel_format_and_hog(frames, lbp_xml, tmp_path):
     with pytest.raises(cc.CascadeError) as err:
         c.detect_batch_to_device(frames, 1.1, 2, out_ptr=d_out.data_ptr(), cap=64, offsets_ptr=d_off.data_ptr())
     assert err.value.status == L.CC_ERR_UNSUPPORTED and "HOG" in str(err.value)
+
+
+# ------------------------------------------------------------------ ordering at scale, against the oracle
+def _same_as_oracle(got, which, mn):
+    want = [o[0] if mn == 0 else o[1] for o in gc.oracle_results(which)]
+    _same(got, want)
+
+
+@pytest.mark.parametrize("mn", [0, 2])
+def test_many_candidates_in_a_frame(mn, monkeypatch):
+    """Four 160x120 frames in one pass, 18 913, 2 997, 0 and 349 candidates (k_cand_rank takes 2048 per turn: ten turns, two,
+    none, one), default candidate capacity. minNeighbors 0: the oracle's raw candidates sorted by (scale index, gy, gx), an
+    order stated without the host path; 2: oracle.detect_multiscale. detect_batch must return the same.
+    max_batch 4 alone gives four passes of one frame (a batch is cut into up to four passes so that host and device work
+    overlap); with CCAMD_PIPELINE_PASSES=1 it is one pass of four, which the timings confirm."""
+    monkeypatch.setenv("CCAMD_PIPELINE_PASSES", "1")
+    path, _ = gc.weak_cascade()
+    frames = np.asarray(gc.many_candidate_frames())
+    p = cc.CascadeClassifier(path, max_batch=4)
+    p.set_profiling(True)
+    got = _to_device(p, frames, mn, cap=32768, host=frames)
+    t = p.timings(reset=True)
+    assert t["frames"] == 4 and t["eval_launches"] == 1  # one pass
+    assert p.candidate_capacity() == 262144  # the default, not regrown
+    _same_as_oracle(got, "many", mn)
+    _same(p.detect_batch(frames, 1.1, mn), got)
+
+
+def _one_call_timings(p, call):
+    p.timings(reset=True)
+    out = call()
+    return out, p.timings(reset=True)
+
+
+@pytest.mark.parametrize("mn", [0, 2])
+def test_a_pass_of_300_frames(mn, monkeypatch):
+    """300 frames of 40x40, a fifth of them flat: with max_batch 512 and CCAMD_PIPELINE_PASSES=1 both the device-output and
+    the host path run them as one pass (frames == 300, eval_launches == 1), so k_cand_segments and k_group_offsets take a
+    second turn and every front-end and cascade launch has 300 as its grid's y. Then max_batch 128: passes of 128, 128 and
+    44, where k_group_offsets goes on from a running total. Every result is held to the oracle, frame by frame."""
+    monkeypatch.setenv("CCAMD_PIPELINE_PASSES", "1")
+    path, _ = gc.weak_cascade()
+    frames = np.asarray(gc.many_small_frames())
+    cap = 156 * len(frames)
+    for mb, passes in ((512, 1), (128, 3)):
+        p = cc.CascadeClassifier(path, max_batch=mb)
+        p.set_profiling(True)
+        got, t = _one_call_timings(p, lambda: _to_device(p, frames, mn, cap=cap, host=frames))
+        assert t["frames"] == 300 and t["eval_launches"] == passes, t
+        _same_as_oracle(got, "small", mn)
+        host, t = _one_call_timings(p, lambda: p.detect_batch(frames, 1.1, mn))
+        assert t["frames"] == 300 and t["eval_launches"] == passes, t
+        _same_as_oracle(host, "small", mn)
+
+
+@pytest.mark.parametrize("colour", [False, True])
+def test_on_the_callers_stream(xml, frames, colour):
+    """The use the device output is for: frames uploaded, the detector run and its result consumed on one stream of the
+    caller's, with no device-wide synchronisation in between -- the detector must order itself behind the upload and the
+    consumer behind the detector through the stream alone."""
+    import torch
+    src = np.stack([frames, np.roll(frames, 3, 2), 255 - frames], -1) if colour else frames
+    p = cc.CascadeClassifier(xml, max_batch=2)
+    want = p.detect_batch(src, 1.1, 2)
+    cap = 4096
+    pinned = torch.from_numpy(np.ascontiguousarray(src)).pin_memory()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        t = torch.zeros(src.shape, dtype=torch.uint8, device="cuda")
+        busy = torch.ones((4096, 4096), device="cuda")
+        for _ in range(8):  # some milliseconds of work ahead of the upload: a detector that did not wait would read zeros
+            busy = (busy @ busy) * (1.0 / 4096)
+        t.copy_(pinned, non_blocking=True)
+        d_out = torch.full((cap + 1, 4), -7, dtype=torch.int32, device="cuda")
+        d_off = torch.full((len(src) + 1,), -7, dtype=torch.int32, device="cuda")
+        p.set_stream(s.cuda_stream)
+        total = p.detect_batch_to_device(None, 1.1, 2, out_ptr=d_out.data_ptr(), cap=cap, offsets_ptr=d_off.data_ptr(),
+                                         device_ptr=t.data_ptr(), shape=t.shape)
+        out_copy, off_copy = d_out.clone(), d_off.clone()  # the consumer
+    s.synchronize()
+    p.set_stream(None)
+    out, off = out_copy.cpu().numpy(), off_copy.cpu().numpy()
+    assert off[-1] == total and (out[cap:] == -7).all()
+    _same([out[off[i]:off[i + 1]] for i in range(len(src))], want)

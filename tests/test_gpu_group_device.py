@@ -1,12 +1,18 @@
 """cc_group_rectangles_device against cc_group_rectangles (the host restatement of cv::groupRectangles, itself held to
 the oracle): rectangles, their order and the per-frame offsets must be identical, on hand-made lists that aim at the
 device algorithm's joints -- closure of a class across wavefronts, class numbering, rounding of the averages, the two
-filters, the LDS / global workspace switch (2048 rectangles per frame), empty frames and a short output buffer."""
+filters, the LDS / global workspace switch (2048 rectangles per frame), empty frames and a short output buffer.
+
+The second half (from test_random_lists_over_the_eps_grid on) judges the device by the oracle's plain n^2 groupRectangles
+and by the host, on the inputs of tests/group_cases.py: an eps and threshold grid, calls of hundreds of frames, global
+workspace slices at non-zero bases, one class and chains of thousands, and the same call repeated."""
 import numpy as np
 import pytest
 
 import cascadeclassifier_amd as cc
 from cascadeclassifier_amd import _lib as L
+from oracle import oracle as orc
+from tests import group_cases as gc
 
 pytestmark = pytest.mark.gpu
 
@@ -154,3 +160,93 @@ def test_cap_one_short():
     assert status == L.CC_ERR_BUFFER_TOO_SMALL and needed == n
     assert oo.tolist() == [0, 6, 6, 9]
     assert (out[:n - 1] == np.concatenate(want)[:n - 1]).all()
+
+
+# ------------------------------------------------------------------ against the oracle, past one tile, block and LDS size
+def _check_oracle(frames, thr, eps=0.2):
+    """Device == oracle and device == host, frame by frame: rectangles, order, offsets. -> (oracle's results, raw bytes)"""
+    frames = [np.asarray(f, np.int32).reshape(-1, 4) for f in frames]
+    want = [orc.group_rectangles(f, thr, eps) for f in frames]
+    status, total, out, oo = _device_group(frames, thr, eps)
+    assert status is None
+    w_off = np.concatenate([[0], np.cumsum([len(w) for w in want])])
+    assert oo.tolist() == w_off.tolist() and total == w_off[-1]
+    for i, (f, w) in enumerate(zip(frames, want)):
+        got = out[oo[i]:oo[i + 1]]
+        assert got.shape == w.shape and (got == w).all(), ("oracle", i, thr, eps, got[:8], w[:8])
+        h = cc.group_rectangles(f, thr, eps)
+        assert got.shape == h.shape and (got == h).all(), ("host", i, thr, eps, got[:8], h[:8])
+    return want, out.tobytes() + oo.tobytes()
+
+
+@pytest.mark.parametrize("eps", gc.EPS_GRID)
+def test_random_lists_over_the_eps_grid(eps):
+    """100 random lists as the 100 frames of one call per (eps, threshold): negative coordinates, rectangles that are not
+    square, pairs exactly at delta, classes the inside filter removes (tests/test_group_cases_host.py holds the lists to that)."""
+    for thr in gc.THRESHOLDS:
+        _check_oracle(gc.random_lists(), thr, eps)
+
+
+def test_rounding_in_the_inside_filter():
+    names = list(gc.ROUNDING_CASES)
+    want, _ = _check_oracle([gc.rounding_rects(n) for n in names], gc.ROUNDING_THRESHOLD, gc.ROUNDING_EPS)
+    assert [len(w) for w in want] == [gc.ROUNDING_WANT[n] for n in names]
+
+
+def test_global_workspace_slices_away_from_base_zero():
+    """Frames of 2049, 5, 3000, 0, 2048 and 2500 rectangles: LDS and global-workspace frames take turns, and the slices of the
+    frames of 3000 and 2500 start at rectangle 2054 and 7102 of the workspace."""
+    loner = [[90000, 90000, 30, 30]]
+    frames = [np.concatenate([_clusters(256, 8, 11), loner]), _clusters(1, 5, 12), _clusters(250, 12, 13), np.zeros((0, 4), np.int32),
+              _clusters(256, 8, 14), _clusters(250, 10, 15)]
+    assert [len(f) for f in frames] == [2049, 5, 3000, 0, 2048, 2500]
+    want, _ = _check_oracle(frames, 3)
+    assert [len(w) for w in want] == [256, 1, 250, 0, 256, 250]
+
+
+@pytest.mark.parametrize("n_frames", [256, 257, 700])
+def test_more_frames_than_one_scan_turn(n_frames):
+    """k_group_offsets scans 256 frames per turn: one turn exactly, one frame into the second, and three turns."""
+    _check_oracle(gc.small_frames(n_frames, n_frames), 1)
+
+
+def test_700_frames_cap_one_short():
+    frames = gc.small_frames(700, 700)
+    want = [orc.group_rectangles(f, 1) for f in frames]
+    n = sum(len(w) for w in want)
+    status, needed, out, oo = _device_group(frames, 1, cap=n - 1)  # asserts that the guard row behind cap is untouched
+    assert status == L.CC_ERR_BUFFER_TOO_SMALL and needed == n
+    assert oo.tolist() == np.concatenate([[0], np.cumsum([len(w) for w in want])]).tolist()
+    assert (out[:n - 1] == np.concatenate(want)[:n - 1]).all()
+
+
+def _union_find_case(kind, n):
+    if kind == "one_class":
+        return gc.one_class(n), 1
+    if kind == "two_chains":
+        return gc.two_chains(n), 2
+    r = gc.chain(n)
+    if kind == "chain_reversed":
+        r = r[::-1].copy()
+    elif kind == "chain_shuffled":
+        r = r[np.random.default_rng(5).permutation(n)]
+    return r, 1
+
+
+@pytest.mark.parametrize("n", [2048, 3000])  # the workspace in LDS, and in global memory
+@pytest.mark.parametrize("kind", ["one_class", "chain_index", "chain_reversed", "chain_shuffled", "two_chains"])
+def test_union_find_contention_and_depth(kind, n):
+    """One class of n (every pair unites), a chain of n in three orders (each rectangle similar to its neighbours only), and
+    two chains that take turns in the list and must stay apart."""
+    r, classes = _union_find_case(kind, n)
+    want, _ = _check_oracle([r], 1)
+    assert len(want[0]) == classes
+
+
+def test_repeated_calls_are_byte_identical():
+    """The result does not depend on the order in which threads run: five calls each, output and offsets compared as bytes."""
+    for frames, thr, eps in [([_union_find_case("chain_shuffled", 3000)[0]], 1, 0.2), (gc.random_lists(), 2, 0.25)]:
+        first = _check_oracle(frames, thr, eps)[1]
+        for _ in range(4):
+            status, _, out, oo = _device_group(frames, thr, eps)
+            assert status is None and out.tobytes() + oo.tobytes() == first
