@@ -687,55 +687,40 @@ static int device_cus(int device) {
   return v;
 }
 
-extern "C" {
+// The LDS opt-in is per device and cheap: set on every launch that needs it.
+template <class Args>
+static cc_status launch(void (*kernel)(Args), unsigned blocks, unsigned threads, size_t lds, hipStream_t stream, const Args& args) {
+  if (lds > 64 * 1024) CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, stream, args);
+  CC_HIP(hipGetLastError());
+  return CC_OK;
+}
 
-cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n_samples) {
-  if (!e) return set_error(CC_ERR_INVALID_ARG, "cc_eval_presort: null evaluator");
-  if (n_samples < 1 || n_samples > e->max_samples)
-    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_presort: n_samples %d out of range (max_samples %d)", n_samples, e->max_samples);
-  if (fi_begin < 0 || fi_end > e->nfeat || fi_begin >= fi_end)
-    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_presort: features [%d, %d) out of range (%d)", fi_begin, fi_end, e->nfeat);
-  cc_status st = eval_device(e);
-  if (st != CC_OK) return st;
-  std::lock_guard<std::mutex> lk(e->mu);
-  st = flush_pending_images(e);
-  if (st != CC_OK) return st;
-  e->presort_n = 0;
-  const bool haar = e->type != CC_FEATURE_LBP;  // HOG variables are ordered: the Haar tables (launch_batch dispatches HOG)
-  const int F = fi_end - fi_begin, N = n_samples;
-  const void* feats = haar ? (const void*)e->d_haar.p : (const void*)e->d_lbp.p;
-  // variables per pass: whole groups of 64, at most 2^28 values per scratch array
-  int FB = (int)std::min<size_t>((size_t)F, std::max<size_t>(64, (((size_t)1 << 28) / (size_t)N) / 64 * 64));
-  const size_t groups = ((size_t)F + 63) / 64;
-  size_t free_b = 0, total_b = 0;
-  CC_HIP(hipMemGetInfo(&free_b, &total_b));
-  // LBP keeps the (code, sample)-sorted table of k_split_cat_sorted beside the codes while sample numbers fit 24 bits
-  const bool no_cat_table = std::getenv("CCAMD_SPLIT_CAT_STREAM") != nullptr;  // A/B: round-1 categorical search only
-  const bool cat_table = !haar && N < (1 << 24) && !no_cat_table;
-  const size_t resident = haar ? groups * 64 * (size_t)N * (4 + (N <= 65536 ? 2 : 4)) : (size_t)F * N + (cat_table ? groups * 64 * ((size_t)N + 3 + SPLIT_CAT_PAD_RANKS) * 4 : 0);
-  const size_t have = e->d_sorted_val.n * 4 + e->d_sorted_idx16.n * 2 + e->d_sorted_idx32.n * 4 + e->d_codes.n + e->d_cat_sorted.n * 4 + e->d_out.n * 4;
-  const size_t scratch = (size_t)FB * N * (haar || cat_table ? 16 : 4);
-  if (resident + scratch > free_b + have)
-    return set_error(CC_ERR_UNSUPPORTED, "cc_eval_presort: needs %.1f GB of device memory (%.1f GB free)",
-                     (double)(resident + scratch) / 1e9, (double)(free_b + have) / 1e9);
+// Stable sort of the rows of e->d_out (one variable per row of N values, at most FB rows) into keys_out / sorted. Owns
+// the scratch of both sorts; that of the device-wide segmented sort is built when a pass first needs it.
+struct RowSorter {
+  cc_evaluator* e;
+  int N, FB;
   DevBuf<float> keys_out;
-  DevBuf<int> iota, sorted, offsets;
+  DevBuf<int> sorted, iota, offsets;
   DevBuf<char> temp;
-  const size_t cap = (size_t)FB * N;
-  if (haar || cat_table) {
-    CC_HIP(e->d_out.ensure(cap));
-    CC_HIP(keys_out.ensure(cap));
-    CC_HIP(sorted.ensure(cap));
+  bool segmented_ready = false;
+
+  RowSorter(cc_evaluator* e_, int N_, int FB_) : e(e_), N(N_), FB(FB_) {}
+  cc_status init() {
+    CC_HIP(e->d_out.ensure((size_t)FB * N));
+    CC_HIP(keys_out.ensure((size_t)FB * N));
+    CC_HIP(sorted.ensure((size_t)FB * N));
+    return CC_OK;
   }
-  bool scratch_for_device_sort = false;
-  // stable sort of the nf rows of d_out (one variable per row) into keys_out / sorted
-  auto sort_rows = [&](int nf) -> cc_status {
+  cc_status sort(int nf) {
     if (N <= sort_rows_block_limit()) {  // a row fits one block: sorted in LDS, read once and written once
       // a part that refuses the ~100 KB LDS request (or the launch) takes the device-wide sort below instead of failing
       if (sort_rows_block(e->d_out.p, nf, N, keys_out.p, sorted.p, e->stream) == hipSuccess) return CC_OK;
       (void)hipGetLastError();
     }
-    if (!scratch_for_device_sort) {
+    if (!segmented_ready) {
+      const size_t cap = (size_t)FB * N;
       CC_HIP(iota.ensure(cap));
       CC_HIP(offsets.ensure((size_t)FB + 1));
       std::vector<int> off((size_t)FB + 1);
@@ -743,7 +728,7 @@ cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n
       CC_HIP(hipMemcpyAsync(offsets.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, e->stream));
       CC_HIP(hipStreamSynchronize(e->stream));  // `off` is pageable and about to go out of scope
       hipLaunchKernelGGL(k_iota_rows2, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, e->stream, iota.p, cap, N);
-      scratch_for_device_sort = true;
+      segmented_ready = true;
     }
     const size_t total = (size_t)nf * N;
     size_t temp_bytes = 0;
@@ -754,72 +739,396 @@ cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n
     CC_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(temp.p, temp_bytes, e->d_out.p, keys_out.p, iota.p, sorted.p, (int)total, nf, offsets.p,
                                                        offsets.p + 1, 0, 32, e->stream));
     return CC_OK;
-  };
-  if (!haar) {
-    CC_HIP(e->d_codes.ensure((size_t)F * N));
-    if (cat_table) {
-      // ranks padded to a multiple of 4 per group (the tail of a group's last quad is never summed: r >= n_pre); zeroed
-      // padding behind the last group for the read-ahead
-      const size_t used = groups * 64 * ((((size_t)N + 3) >> 2) << 2), pad = (size_t)SPLIT_CAT_PAD_RANKS * 64;
-      CC_HIP(e->d_cat_sorted.ensure(used + pad));
-      CC_HIP(hipMemsetAsync(e->d_cat_sorted.p, 0, (used + pad) * sizeof(uint32_t), e->stream));
-    }
-    e->cat_sorted_n = 0;
-    for (int f0 = 0; f0 < F; f0 += FB) {
-      const int f1 = std::min(F, f0 + FB), nf = f1 - f0;
-      const size_t total = (size_t)nf * N;
-      CC_HIP(e->d_out.ensure(total));
-      st = launch_batch(e, false, feats, fi_begin + f0, fi_begin + f1, nullptr, N, e->d_out.p, 1, 0);
-      if (st != CC_OK) return st;
-      hipLaunchKernelGGL(k_codes_u8, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, e->d_out.p,
-                         e->d_codes.p + (size_t)f0 * N, total);
-      if (cat_table) {
-        st = sort_rows(nf);
-        if (st != CC_OK) return st;
-        hipLaunchKernelGGL(k_interleave_cat, dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream, keys_out.p,
-                           sorted.p, nf, N, e->d_cat_sorted.p, (size_t)f0 / 64);
-      }
-    }
-    CC_HIP(hipGetLastError());
-    CC_HIP(hipStreamSynchronize(e->stream));
-    e->presort_n = N;
-    e->presort_f0 = fi_begin;
-    e->presort_f1 = fi_end;
-    e->cat_sorted_n = cat_table ? N : 0;
-    return CC_OK;
   }
-  const bool idx16 = N <= 65536;
-  {  // tables + SPLIT_TABLE_PAD_RANKS ranks of zeroed padding behind the last group (read-ahead of k_split_ord_lean)
-    const size_t used = groups * 64 * (size_t)N, pad = (size_t)SPLIT_TABLE_PAD_RANKS * 64;
-    CC_HIP(e->d_sorted_val.ensure(used + pad));
-    CC_HIP(hipMemsetAsync(e->d_sorted_val.p + used, 0, pad * sizeof(float), e->stream));
-    if (idx16) {
-      CC_HIP(e->d_sorted_idx16.ensure(used + pad));
-      CC_HIP(hipMemsetAsync(e->d_sorted_idx16.p + used, 0, pad * sizeof(uint16_t), e->stream));
-    } else {
-      CC_HIP(e->d_sorted_idx32.ensure(used + pad));
-      CC_HIP(hipMemsetAsync(e->d_sorted_idx32.p + used, 0, pad * sizeof(int32_t), e->stream));
-    }
+};
+
+// The resident tables plus one pass's scratch have to fit what is free plus what the evaluator already holds for them.
+static cc_status presort_memory_check(const cc_evaluator* e, bool haar, bool cat_table, int F, int N, int FB) {
+  const size_t groups = ((size_t)F + 63) / 64;
+  size_t free_b = 0, total_b = 0;
+  CC_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t resident = haar ? groups * 64 * (size_t)N * (4 + (N <= 65536 ? 2 : 4)) : (size_t)F * N + (cat_table ? groups * 64 * ((size_t)N + 3 + SPLIT_CAT_PAD_RANKS) * 4 : 0);
+  const size_t have = e->d_sorted_val.n * 4 + e->d_sorted_idx16.n * 2 + e->d_sorted_idx32.n * 4 + e->d_codes.n + e->d_cat_sorted.n * 4 + e->d_out.n * 4;
+  const size_t scratch = (size_t)FB * N * (haar || cat_table ? 16 : 4);
+  if (resident + scratch > free_b + have)
+    return set_error(CC_ERR_UNSUPPORTED, "cc_eval_presort: needs %.1f GB of device memory (%.1f GB free)",
+                     (double)(resident + scratch) / 1e9, (double)(free_b + have) / 1e9);
+  return CC_OK;
+}
+
+// Ordered variables (Haar, HOG): sorted values and sample numbers (TI: 16-bit while they fit), [group][rank][64].
+template <class TI>
+static cc_status presort_ordered(cc_evaluator* e, RowSorter& rows, const void* feats, int fi_begin, int F, DevBuf<TI>& d_sorted_idx) {
+  const int N = rows.N, FB = rows.FB;
+  // tables + SPLIT_TABLE_PAD_RANKS ranks of zeroed padding behind the last group (read-ahead of k_split_ord_lean)
+  const size_t used = ((size_t)F + 63) / 64 * 64 * (size_t)N, pad = (size_t)SPLIT_TABLE_PAD_RANKS * 64;
+  CC_HIP(e->d_sorted_val.ensure(used + pad));
+  CC_HIP(hipMemsetAsync(e->d_sorted_val.p + used, 0, pad * sizeof(float), e->stream));
+  CC_HIP(d_sorted_idx.ensure(used + pad));
+  CC_HIP(hipMemsetAsync(d_sorted_idx.p + used, 0, pad * sizeof(TI), e->stream));
+  for (int f0 = 0; f0 < F; f0 += FB) {
+    const int f1 = std::min(F, f0 + FB), nf = f1 - f0;
+    if (cc_status st = launch_batch(e, true, feats, fi_begin + f0, fi_begin + f1, nullptr, N, e->d_out.p, 1, 0); st != CC_OK) return st;
+    if (cc_status st = rows.sort(nf); st != CC_OK) return st;
+    hipLaunchKernelGGL((k_interleave<TI>), dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream, rows.keys_out.p,
+                       rows.sorted.p, nf, N, e->d_sorted_val.p, d_sorted_idx.p, (size_t)f0 / 64);
+    CC_HIP(hipGetLastError());
+  }
+  return CC_OK;
+}
+
+// Categorical variables (LBP): the codes [variable][sample] and, with cat_table, the (code, sample)-sorted table beside them.
+static cc_status presort_categorical(cc_evaluator* e, RowSorter& rows, const void* feats, int fi_begin, int F, bool cat_table) {
+  const int N = rows.N, FB = rows.FB;
+  CC_HIP(e->d_codes.ensure((size_t)F * N));
+  if (cat_table) {
+    // ranks padded to a multiple of 4 per group (the tail of a group's last quad is never summed: r >= n_pre); zeroed
+    // padding behind the last group for the read-ahead
+    const size_t used = ((size_t)F + 63) / 64 * 64 * ((((size_t)N + 3) >> 2) << 2), pad = (size_t)SPLIT_CAT_PAD_RANKS * 64;
+    CC_HIP(e->d_cat_sorted.ensure(used + pad));
+    CC_HIP(hipMemsetAsync(e->d_cat_sorted.p, 0, (used + pad) * sizeof(uint32_t), e->stream));
   }
   for (int f0 = 0; f0 < F; f0 += FB) {
     const int f1 = std::min(F, f0 + FB), nf = f1 - f0;
-    st = launch_batch(e, true, feats, fi_begin + f0, fi_begin + f1, nullptr, N, e->d_out.p, 1, 0);
-    if (st != CC_OK) return st;
-    st = sort_rows(nf);
-    if (st != CC_OK) return st;
-    const dim3 grid((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64));
-    if (idx16)
-      hipLaunchKernelGGL((k_interleave<uint16_t>), grid, dim3(256), 0, e->stream, keys_out.p, sorted.p, nf, N, e->d_sorted_val.p,
-                         e->d_sorted_idx16.p, (size_t)f0 / 64);
+    const size_t total = (size_t)nf * N;
+    CC_HIP(e->d_out.ensure(total));
+    if (cc_status st = launch_batch(e, false, feats, fi_begin + f0, fi_begin + f1, nullptr, N, e->d_out.p, 1, 0); st != CC_OK) return st;
+    hipLaunchKernelGGL(k_codes_u8, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, e->d_out.p,
+                       e->d_codes.p + (size_t)f0 * N, total);
+    if (!cat_table) continue;
+    if (cc_status st = rows.sort(nf); st != CC_OK) return st;
+    hipLaunchKernelGGL(k_interleave_cat, dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream, rows.keys_out.p,
+                       rows.sorted.p, nf, N, e->d_cat_sorted.p, (size_t)f0 / 64);
+  }
+  CC_HIP(hipGetLastError());
+  return CC_OK;
+}
+
+// One call, arguments checked: the node and what the three searches share.
+struct SplitQuery {
+  cc_evaluator* e;
+  const int32_t* sample_idx;  // NULL: samples 0 .. n-1
+  int n;
+  const double* weights;
+  const float* responses;
+  const int32_t* class_labels;
+  double node_value;
+  bool is_classifier, gini;
+  int N, F, var0;  // presorted samples and variables; per-variable outputs are indexed from presort's fi_begin = var0
+  cc_split* out;
+  double* per_var_quality;
+  int32_t* per_var_point;
+
+  int sample(int i) const { return sample_idx ? sample_idx[i] : i; }
+  // 8-byte entry: response * w (w = |entry|), or w with the class in the sign bit
+  double entry8(int i) const { return is_classifier ? (class_labels[i] ? -weights[i] : weights[i]) : responses[i] * weights[i]; }
+  SplitEntry entry16(int i) const { return SplitEntry{weights[i], is_classifier ? (double)class_labels[i] : responses[i] * weights[i]}; }
+};
+
+// The per-sample table of a node search: where it lives and how wide its entries are. The values are the kernels' TAB.
+enum TableForm : int { TABLE_GLOBAL16 = 0, TABLE_LDS16 = 1, TABLE_LDS8 = 2 };
+constexpr size_t SPLIT_LDS_CAP = 160 * 1024;
+// A table in LDS implies 16-bit sample numbers in the sorted tables: no kernel pairs int32_t with an LDS form.
+static_assert(SPLIT_LDS_CAP / 8 <= 65536, "an LDS table holds at most 65 536 samples");
+
+static size_t table_bytes(TableForm form, size_t entries) { return entries * (form == TABLE_LDS8 ? 8 : 16); }
+static size_t table_lds(TableForm form, int N) { return form == TABLE_GLOBAL16 ? 0 : table_bytes(form, (size_t)N); }
+
+// 8-byte entries need a class or a response of +-1, and whenever 16-byte entries would fit LDS so do 8-byte ones:
+// TABLE_LDS16 is what regression with other responses (LOGIT) gets, and nothing else does.
+static TableForm table_form(const SplitQuery& q) {
+  if (std::getenv("CCAMD_SPLIT_GLOBAL_TABLE")) return TABLE_GLOBAL16;
+  bool unit_responses = !q.is_classifier;
+  for (int i = 0; i < q.n && unit_responses; i++) unit_responses = q.responses[i] == 1.0f || q.responses[i] == -1.0f;
+  if ((q.is_classifier || unit_responses) && (size_t)q.N * 8 <= SPLIT_LDS_CAP) return TABLE_LDS8;
+  return (size_t)q.N * 16 <= SPLIT_LDS_CAP ? TABLE_LDS16 : TABLE_GLOBAL16;
+}
+
+// What a table holds for a stored sample that is not in the node. The ordered kernels test for it: w = -1, or the quiet
+// NaN whose high word k_split_ord_lean compares (0x7ff80000, low word 0). k_split_cat_sorted adds every entry up: +0.0.
+struct AbsentEntry {
+  double e8;
+  SplitEntry e16;
+};
+static const AbsentEntry ABSENT_ORDERED = {std::numeric_limits<double>::quiet_NaN(), {-1.0, 0.0}};
+static const AbsentEntry ABSENT_CATEGORICAL = {0.0, {0.0, 0.0}};
+
+// Builds the node's table in pin_in and sends it to d_split_tab. With `absent`: dense, one entry per stored sample and
+// `absent` for those outside the node. Without: the compact list of k_split_cat, the node's entries in node order
+// (16-byte: TABLE_GLOBAL16) and their stored-sample numbers, which go to d_split_idx.
+static cc_status upload_node_table(const SplitQuery& q, TableForm form, const AbsentEntry* absent) {
+  cc_evaluator* e = q.e;
+  const size_t m = absent ? (size_t)q.N : (size_t)q.n, bytes = table_bytes(form, m);
+  CC_HIP(e->pin_in.ensure(bytes + (absent ? 0 : m * 4)));
+  double* tab8 = static_cast<double*>(e->pin_in.p);
+  SplitEntry* tab16 = static_cast<SplitEntry*>(e->pin_in.p);
+  int32_t* idx_host = reinterpret_cast<int32_t*>(static_cast<char*>(e->pin_in.p) + bytes);
+  if (absent && form == TABLE_LDS8) std::fill_n(tab8, m, absent->e8);
+  if (absent && form != TABLE_LDS8) std::fill_n(tab16, m, absent->e16);
+  std::vector<uint8_t> seen((size_t)q.N, 0);
+  for (int i = 0; i < q.n; i++) {
+    const int g = q.sample(i), slot = absent ? g : i;
+    if (g < 0 || g >= q.N) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_find_best_split: sample index %d outside the %d presorted samples", g, q.N);
+    if (seen[(size_t)g]) return set_error(CC_ERR_INVALID_ARG, "cc_eval_find_best_split: sample %d occurs twice in the node", g);
+    seen[(size_t)g] = 1;
+    if (!absent) idx_host[i] = g;
+    if (form == TABLE_LDS8)
+      tab8[slot] = q.entry8(i);
     else
-      hipLaunchKernelGGL((k_interleave<int32_t>), grid, dim3(256), 0, e->stream, keys_out.p, sorted.p, nf, N, e->d_sorted_val.p,
-                         e->d_sorted_idx32.p, (size_t)f0 / 64);
-    CC_HIP(hipGetLastError());
+      tab16[slot] = q.entry16(i);
+  }
+  CC_HIP(e->d_split_tab.ensure(m * 2));
+  CC_HIP(hipMemcpyAsync(e->d_split_tab.p, e->pin_in.p, bytes, hipMemcpyHostToDevice, e->stream));
+  if (absent) return CC_OK;
+  CC_HIP(e->d_split_idx.ensure(m));
+  CC_HIP(hipMemcpyAsync(e->d_split_idx.p, idx_host, m * 4, hipMemcpyHostToDevice, e->stream));
+  return CC_OK;
+}
+
+// The kernels that can be launched, and no others: what is not named here is not in the code object. With the table in
+// global memory the index type follows N; with it in LDS the indices are 16-bit (SPLIT_LDS_CAP) and TABLE_LDS16 is
+// regression only (table_form). k_split_ord_lean for the regression / GINI searches (Gentle 6.77 against 7.01 ms, GINI
+// 8.91 against 9.31 at configs[4]); the MISCLASS search has no division and nothing to hoist: the round-1 kernel stays
+// (4.46 against 4.76 ms). A combination that cannot occur gets no kernel, and its launch fails.
+static void (*ordered_kernel(int mode, TableForm form, bool idx16))(SplitOrdArgs) {
+  if (form == TABLE_GLOBAL16 && !idx16) return mode == 0 ? k_split_ord<0, int32_t, 0> : mode == 1 ? k_split_ord<1, int32_t, 0> : k_split_ord<2, int32_t, 0>;
+  if (form == TABLE_GLOBAL16) return mode == 0 ? k_split_ord<0, uint16_t, 0> : mode == 1 ? k_split_ord<1, uint16_t, 0> : k_split_ord<2, uint16_t, 0>;
+  if (!idx16) return nullptr;
+  if (form == TABLE_LDS16) return mode == 0 ? k_split_ord<0, uint16_t, 1> : nullptr;
+  return mode == 0 ? k_split_ord_lean<0, uint16_t> : mode == 1 ? k_split_ord_lean<1, uint16_t> : k_split_ord<2, uint16_t, 2>;
+}
+static void (*categorical_sorted_kernel(bool is_classifier, TableForm form))(SplitCatArgs) {
+  if (form == TABLE_GLOBAL16) return is_classifier ? k_split_cat_sorted<true, 0> : k_split_cat_sorted<false, 0>;
+  if (form == TABLE_LDS16) return is_classifier ? nullptr : k_split_cat_sorted<false, 1>;
+  return is_classifier ? k_split_cat_sorted<true, 2> : k_split_cat_sorted<false, 2>;
+}
+
+// d_split_out of the ordered search and its pinned copy: best_val [fpad] doubles, then best_i, best_vl and best_vr,
+// [fpad] 4-byte values each.
+struct OrdResult {
+  double* best_val;
+  int* best_i;
+  float *best_vl, *best_vr;
+  OrdResult(void* base, size_t fpad)
+      : best_val(static_cast<double*>(base)), best_i(reinterpret_cast<int*>(best_val + fpad)), best_vl(reinterpret_cast<float*>(best_i + fpad)),
+        best_vr(best_vl + fpad) {}
+  static size_t bytes(size_t fpad) { return fpad * 20; }
+};
+
+// ev_a .. ev_b for cc_eval_last_kernel_ms; the stream has been synchronised
+static void note_kernel_ms(cc_evaluator* e) {
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, e->ev_a, e->ev_b) == hipSuccess) e->last_ms = ms;
+}
+
+// The winner, variable by variable as DTreeBestSplitFinder::operator() does (o_cvdtree.cpp:320-342): a variable reports
+// a split only if it beats the best quality so far (a float), and replaces it only if its own quality, rounded to
+// float, is larger. Fills the per-variable outputs and the winner's part of q.out; returns the winner, or -1 for no split.
+template <class Found, class Quality, class Point>
+static int pick_winner(const SplitQuery& q, Found found, Quality quality, Point point) {
+  float best_q = -1.f;
+  int winner = -1;
+  for (int f = 0; f < q.F; f++) {
+    if (q.per_var_quality) q.per_var_quality[f] = found(f) ? quality(f) : -1.0;
+    if (q.per_var_point) q.per_var_point[f] = point(f);
+    if (!found(f) || !((double)best_q < quality(f))) continue;
+    const float v = (float)quality(f);
+    if (best_q < v) {
+      best_q = v;
+      winner = f;
+    }
+  }
+  if (winner < 0 || !(best_q > 0)) return -1;  // o_cvdtree.cpp:351
+  q.out->found = 1;
+  q.out->var_idx = q.var0 + winner;
+  q.out->quality = best_q;
+  return winner;
+}
+
+static cc_status search_ordered(const SplitQuery& q) {
+  cc_evaluator* e = q.e;
+  const int N = q.N;
+  const bool idx16 = N <= 65536;
+  const int mode = !q.is_classifier ? 0 : (q.gini ? 1 : 2);
+  const TableForm form = table_form(q);
+  if (cc_status st = upload_node_table(q, form, &ABSENT_ORDERED); st != CC_OK) return st;
+  const size_t groups = ((size_t)q.F + 63) / 64, fpad = groups * 64;
+  CC_HIP(e->d_split_out.ensure(fpad * 3));  // OrdResult::bytes + slack
+  const OrdResult dev(e->d_split_out.p, fpad);
+  // in the struct's order: sv, si, tab, n_pre, n_vars, w_total0, w_total1, rsum0, best_val, best_i, best_vl, best_vr, n_groups, dbg_nogather
+  const SplitOrdArgs A{e->d_sorted_val.p, idx16 ? (const void*)e->d_sorted_idx16.p : (const void*)e->d_sorted_idx32.p,
+                       reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), N, q.F, q.weights[q.n], q.weights[q.n + 1], q.node_value * q.weights[q.n],
+                       dev.best_val, dev.best_i, dev.best_vl, dev.best_vr, (int)groups, std::getenv("CCAMD_DEBUG_SPLIT_NOGATHER") ? 1 : 0};
+  // wavefronts per block: with the table in LDS one block owns a CU, so spread the groups evenly over the CUs
+  // (162 336 variables = 2 537 groups -> 254 blocks of 10 wavefronts on 256 CUs); from global memory, one wavefront
+  // per block.
+  int wpb = 1;
+  if (form != TABLE_GLOBAL16) {
+    const int cus = device_cus(e->device);
+    wpb = (int)std::min<size_t>(16, std::max<size_t>(1, (groups + cus - 1) / cus));
+    if (form == TABLE_LDS8 && mode != 2) wpb = std::min(wpb, SPLIT_LEAN_WAVES);  // k_split_ord_lean
+  }
+  const unsigned blocks = (unsigned)((groups + wpb - 1) / wpb);
+  (void)hipEventRecord(e->ev_a, e->stream);
+  if (cc_status st = launch(ordered_kernel(mode, form, idx16), blocks, 64u * wpb, table_lds(form, N), e->stream, A); st != CC_OK) return st;
+  (void)hipEventRecord(e->ev_b, e->stream);
+  CC_HIP(e->pin_out.ensure(fpad * 24));
+  CC_HIP(hipMemcpyAsync(e->pin_out.p, e->d_split_out.p, OrdResult::bytes(fpad), hipMemcpyDeviceToHost, e->stream));
+  CC_HIP(hipStreamSynchronize(e->stream));
+  note_kernel_ms(e);
+  const OrdResult got(e->pin_out.p, fpad);
+  const int winner = pick_winner(q, [&](int f) { return got.best_i[f] >= 0; }, [&](int f) { return got.best_val[f]; }, [&](int f) { return got.best_i[f]; });
+  if (winner >= 0) {
+    q.out->ord_c = (got.best_vl[winner] + got.best_vr[winner]) * 0.5f;
+    q.out->split_point = got.best_i[winner];
+  }
+  return CC_OK;
+}
+
+// Per-category sums of a node that lists its samples in increasing order, from the (code, sample)-sorted table.
+static cc_status search_categorical_sorted(const SplitQuery& q, size_t hist_n) {
+  cc_evaluator* e = q.e;
+  const int N = q.N;
+  const TableForm form = table_form(q);
+  if (cc_status st = upload_node_table(q, form, &ABSENT_CATEGORICAL); st != CC_OK) return st;
+  (void)hipEventRecord(e->ev_a, e->stream);
+  CC_HIP(hipMemsetAsync(e->d_split_out.p, 0, hist_n * 8, e->stream));  // categories without a sample
+  const size_t groups = ((size_t)q.F + 63) / 64;
+  SplitCatArgs A;
+  A.packed = e->d_cat_sorted.p;
+  A.tab = reinterpret_cast<const SplitEntry*>(e->d_split_tab.p);
+  A.n_pre = N;
+  A.n_vars = q.F;
+  A.n_groups = (int)groups;
+  A.hist = e->d_split_out.p;
+  // One wavefront per (group, part); with the table in LDS a block owns a CU (<= 4 wavefronts of it): as many parts as
+  // give every CU a full block, no part shorter than 1 024 ranks. CCAMD_SPLIT_CAT_PARTS overrides (1 = round-4 first form).
+  const int cus = device_cus(e->device);
+  int parts = (int)std::max<size_t>(1, (size_t)cus * 4 / groups);
+  parts = std::max(1, std::min(parts, N / 1024));
+  if (const char* v = std::getenv("CCAMD_SPLIT_CAT_PARTS")) parts = std::max(1, std::min(64, std::atoi(v)));
+  const int chunk = SPLIT_CAT_DEPTH * SPLIT_CAT_UNROLL;
+  A.parts = parts;
+  A.part_len = ((N + parts - 1) / parts + chunk - 1) / chunk * chunk;
+  const size_t units = groups * (size_t)parts;
+  A.waves = form == TABLE_GLOBAL16 ? 4 : (int)std::min<size_t>(4, std::max<size_t>(1, (units + cus - 1) / cus));
+  const unsigned blocks = (unsigned)((units + A.waves - 1) / A.waves);
+  const cc_status st = launch(categorical_sorted_kernel(q.is_classifier, form), blocks, 256, table_lds(form, N), e->stream, A);
+  (void)hipEventRecord(e->ev_b, e->stream);
+  return st;
+}
+
+// The same sums for a node in any order: its samples streamed through k_split_cat.
+static cc_status search_categorical_stream(const SplitQuery& q) {
+  cc_evaluator* e = q.e;
+  if (cc_status st = upload_node_table(q, TABLE_GLOBAL16, nullptr); st != CC_OK) return st;
+  (void)hipEventRecord(e->ev_a, e->stream);
+  hipLaunchKernelGGL(q.is_classifier ? k_split_cat<true> : k_split_cat<false>, dim3((unsigned)q.F), dim3(256), 0, e->stream, e->d_codes.p, q.N,
+                     q.sample_idx ? e->d_split_idx.p : nullptr, reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), q.n, e->d_split_out.p);
+  (void)hipEventRecord(e->ev_b, e->stream);
+  CC_HIP(hipGetLastError());
+  return CC_OK;
+}
+
+// The 34.7 MB of sums (8 464 variables) come back in pieces; the host's part -- ordering each variable's categories and
+// scanning them (split_categories) -- starts on a piece as soon as it has landed, on up to 16 threads.
+static cc_status reduce_category_sums(const SplitQuery& q, size_t hist_n, std::vector<CatSplit>& res) {
+  cc_evaluator* e = q.e;
+  const int F = q.F;
+  CC_HIP(e->pin_out.ensure(hist_n * 8));
+  constexpr int kPieces = 8;
+  for (int c = 0; c < kPieces; c++)
+    if (!e->ev_piece[c]) CC_HIP(hipEventCreateWithFlags(&e->ev_piece[c], hipEventDisableTiming));
+  const int per_piece = (F + kPieces - 1) / kPieces;
+  double* hist = static_cast<double*>(e->pin_out.p);
+  for (int c = 0; c < kPieces; c++) {
+    const int f0 = std::min(F, c * per_piece), f1 = std::min(F, f0 + per_piece);
+    if (f1 > f0)
+      CC_HIP(hipMemcpyAsync(hist + (size_t)f0 * 512, e->d_split_out.p + (size_t)f0 * 512, (size_t)(f1 - f0) * 512 * 8, hipMemcpyDeviceToHost, e->stream));
+    CC_HIP(hipEventRecord(e->ev_piece[c], e->stream));
+  }
+  std::atomic<int> copy_failed{0};
+  const bool trace = std::getenv("CCAMD_TRACE_SPLIT") != nullptr;  // host-side timeline of the call's tail (stderr)
+  const auto t_enq = std::chrono::steady_clock::now();
+  double landed_ms[kPieces] = {};
+  {
+    const int nt = std::max(1, std::min<int>({(int)std::thread::hardware_concurrency(), 16, F / 64 + 1}));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; t++)
+      th.emplace_back([&, t]() {
+        for (int c = 0; c < kPieces; c++) {
+          if (hipEventSynchronize(e->ev_piece[c]) != hipSuccess) {
+            copy_failed = 1;
+            return;
+          }
+          if (trace && t == 0) landed_ms[c] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq).count();
+          const int f0 = std::min(F, c * per_piece), f1 = std::min(F, f0 + per_piece);
+          for (int f = f0 + t; f < f1; f += nt) split_categories(hist + (size_t)f * 512, 256, q.is_classifier, q.gini, res[(size_t)f]);
+        }
+      });
+    for (auto& x : th) x.join();
+  }
+  if (trace) {
+    std::fprintf(stderr, "[ccamd split] after the last enqueue: pieces landed (as seen by worker 0) at");
+    for (int c = 0; c < kPieces; c++) std::fprintf(stderr, " %.2f", landed_ms[c]);
+    std::fprintf(stderr, " ms; workers done at %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq).count());
   }
   CC_HIP(hipStreamSynchronize(e->stream));
+  if (copy_failed) return set_error(CC_ERR_HIP, "cc_eval_find_best_split: copying the category sums back failed");
+  note_kernel_ms(e);
+  return CC_OK;
+}
+
+static cc_status search_categorical(const SplitQuery& q) {
+  const size_t hist_n = (size_t)q.F * 256 * 2;
+  CC_HIP(q.e->d_split_out.ensure(hist_n));
+  bool ascending = true;  // the node lists its samples in increasing order: what k_split_cat_sorted's exactness needs
+  for (int i = 1; i < q.n && ascending && q.sample_idx; i++) ascending = q.sample_idx[i - 1] < q.sample_idx[i];
+  const bool stream_only = std::getenv("CCAMD_SPLIT_CAT_STREAM") != nullptr;  // read per call: tests compare the two paths
+  const bool sorted = ascending && q.e->cat_sorted_n == q.N && !stream_only;
+  if (cc_status st = sorted ? search_categorical_sorted(q, hist_n) : search_categorical_stream(q); st != CC_OK) return st;
+  std::vector<CatSplit> res((size_t)q.F);
+  if (cc_status st = reduce_category_sums(q, hist_n, res); st != CC_OK) return st;
+  const int winner = pick_winner(q, [&](int f) { return res[(size_t)f].found; }, [&](int f) { return res[(size_t)f].quality; },
+                                 [&](int f) { return res[(size_t)f].found ? res[(size_t)f].n_left - 1 : -1; });
+  if (winner >= 0) std::memcpy(q.out->subset, res[(size_t)winner].subset, sizeof(q.out->subset));
+  return CC_OK;
+}
+
+extern "C" {
+
+cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n_samples) {
+  if (!e) return set_error(CC_ERR_INVALID_ARG, "cc_eval_presort: null evaluator");
+  if (n_samples < 1 || n_samples > e->max_samples)
+    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_presort: n_samples %d out of range (max_samples %d)", n_samples, e->max_samples);
+  if (fi_begin < 0 || fi_end > e->nfeat || fi_begin >= fi_end)
+    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_presort: features [%d, %d) out of range (%d)", fi_begin, fi_end, e->nfeat);
+  if (cc_status st = eval_device(e); st != CC_OK) return st;
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (cc_status st = flush_pending_images(e); st != CC_OK) return st;
+  e->presort_n = 0;  // until the epilogue: a failure below leaves no tables to search
+  const bool haar = e->type != CC_FEATURE_LBP;  // HOG variables are ordered: the Haar tables (launch_batch dispatches HOG)
+  const int F = fi_end - fi_begin, N = n_samples;
+  const void* feats = haar ? (const void*)e->d_haar.p : (const void*)e->d_lbp.p;
+  // variables per pass: whole groups of 64, at most 2^28 values per scratch array
+  const int FB = (int)std::min<size_t>((size_t)F, std::max<size_t>(64, (((size_t)1 << 28) / (size_t)N) / 64 * 64));
+  // LBP keeps the (code, sample)-sorted table of k_split_cat_sorted beside the codes while sample numbers fit 24 bits
+  const bool no_cat_table = std::getenv("CCAMD_SPLIT_CAT_STREAM") != nullptr;  // A/B: round-1 categorical search only
+  const bool cat_table = !haar && N < (1 << 24) && !no_cat_table;
+  if (cc_status st = presort_memory_check(e, haar, cat_table, F, N, FB); st != CC_OK) return st;
+  RowSorter rows(e, N, FB);
+  if (haar || cat_table)
+    if (cc_status st = rows.init(); st != CC_OK) return st;
+  const cc_status st = !haar        ? presort_categorical(e, rows, feats, fi_begin, F, cat_table)
+                       : N <= 65536 ? presort_ordered(e, rows, feats, fi_begin, F, e->d_sorted_idx16)
+                                    : presort_ordered(e, rows, feats, fi_begin, F, e->d_sorted_idx32);
+  if (st != CC_OK) return st;
+  CC_HIP(hipStreamSynchronize(e->stream));
+  // epilogue: the tables are valid
   e->presort_n = N;
   e->presort_f0 = fi_begin;
   e->presort_f1 = fi_end;
+  e->cat_sorted_n = cat_table ? N : 0;
   return CC_OK;
 }
 
@@ -842,12 +1151,10 @@ cc_status cc_eval_find_best_split(cc_evaluator* e, const int32_t* sample_idx, in
   if (n < 0 || n > N) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_find_best_split: n %d exceeds the %d presorted samples", n, N);
   int criteria = split_criteria;
   if (criteria != 1 && criteria != 3) criteria = boost_type == 0 ? 3 : 1;  // o_cvboostree.cpp:188-190
-  const bool gini = criteria == 1;
-  cc_status st = eval_device(e);
-  if (st != CC_OK) return st;
+  if (cc_status st = eval_device(e); st != CC_OK) return st;
   std::memset(out, 0, sizeof(*out));
   out->quality = -1.f;
-  const int F = e->presort_f1 - e->presort_f0, var0 = e->presort_f0;  // per-variable outputs are indexed from presort's fi_begin
+  const int F = e->presort_f1 - e->presort_f0;
   if (per_var_quality)
     for (int f = 0; f < F; f++) per_var_quality[f] = -1.0;
   if (per_var_point)
@@ -859,333 +1166,9 @@ cc_status cc_eval_find_best_split(cc_evaluator* e, const int32_t* sample_idx, in
     if (!(weights[i] >= 0.0)) return set_error(CC_ERR_INVALID_ARG, "cc_eval_find_best_split: weight of sample %d is negative or NaN", i);
   }
   std::lock_guard<std::mutex> lk(e->mu);
-  const bool haar = e->type != CC_FEATURE_LBP;  // ordered variables (Haar, HOG)
-  PinnedBuf& pin_in = e->pin_in;
-  PinnedBuf& pin_out = e->pin_out;
-  if (haar) {
-    // per stored sample {w, t}; not in this node: w = -1 (16-B entries) or NaN (8-B entries)
-    const bool idx16 = N <= 65536;
-    const int mode = !is_classifier ? 0 : (gini ? 1 : 2);
-    bool unit_responses = !is_classifier;
-    if (!is_classifier)
-      for (int i = 0; i < n && unit_responses; i++) unit_responses = responses[i] == 1.0f || responses[i] == -1.0f;
-    const size_t lds_cap = 160 * 1024;
-    int tab_kind = 0;
-    if ((is_classifier || unit_responses) && (size_t)N * 8 <= lds_cap)
-      tab_kind = 2;
-    else if ((size_t)N * 16 <= lds_cap)
-      tab_kind = 1;
-    if (std::getenv("CCAMD_SPLIT_GLOBAL_TABLE")) tab_kind = 0;
-    const size_t entry_bytes = tab_kind == 2 ? 8 : 16;
-    CC_HIP(pin_in.ensure((size_t)N * entry_bytes));
-    std::vector<uint8_t> seen((size_t)N, 0);
-    SplitEntry* tab16 = static_cast<SplitEntry*>(pin_in.p);
-    double* tab8 = static_cast<double*>(pin_in.p);
-    for (int g = 0; g < N; g++) {
-      if (tab_kind == 2)
-        tab8[g] = std::numeric_limits<double>::quiet_NaN();
-      else
-        tab16[g] = SplitEntry{-1.0, 0.0};
-    }
-    for (int i = 0; i < n; i++) {
-      const int g = sample_idx ? sample_idx[i] : i;
-      if (g < 0 || g >= N) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_find_best_split: sample index %d outside the %d presorted samples", g, N);
-      if (seen[(size_t)g]) return set_error(CC_ERR_INVALID_ARG, "cc_eval_find_best_split: sample %d occurs twice in the node", g);
-      seen[(size_t)g] = 1;
-      const double w = weights[i];
-      if (tab_kind == 2)
-        tab8[g] = is_classifier ? (class_labels[i] ? -w : w) : responses[i] * w;
-      else {
-        tab16[g].w = w;
-        tab16[g].t = is_classifier ? (double)class_labels[i] : responses[i] * w;
-      }
-    }
-    const size_t groups = ((size_t)F + 63) / 64, fpad = groups * 64;
-    CC_HIP(e->d_split_tab.ensure((size_t)N * 2));
-    CC_HIP(e->d_split_out.ensure(fpad * 3));  // best_val (8 B) + best_i, vl, vr (4 B each) + slack
-    CC_HIP(hipMemcpyAsync(e->d_split_tab.p, pin_in.p, (size_t)N * entry_bytes, hipMemcpyHostToDevice, e->stream));
-    SplitOrdArgs A;
-    A.sv = e->d_sorted_val.p;
-    A.si = idx16 ? (const void*)e->d_sorted_idx16.p : (const void*)e->d_sorted_idx32.p;
-    A.tab = reinterpret_cast<const SplitEntry*>(e->d_split_tab.p);
-    A.n_pre = N;
-    A.n_vars = F;
-    A.n_groups = (int)groups;
-    A.w_total0 = weights[n];
-    A.w_total1 = weights[n + 1];
-    A.rsum0 = node_value * weights[n];
-    A.best_val = e->d_split_out.p;
-    A.best_i = reinterpret_cast<int*>(e->d_split_out.p + fpad);
-    A.best_vl = reinterpret_cast<float*>(A.best_i + fpad);
-    A.best_vr = A.best_vl + fpad;
-    A.dbg_nogather = std::getenv("CCAMD_DEBUG_SPLIT_NOGATHER") ? 1 : 0;
-    // wavefronts per block: with the table in LDS one block owns a CU, so spread the groups evenly over the CUs
-    // (162 336 variables = 2 537 groups -> 254 blocks of 10 wavefronts on 256 CUs); from global memory, one wavefront
-    // per block. k_split_ord_lean for the regression / GINI searches (Gentle 6.77 against 7.01 ms, GINI 8.91 against 9.31 at configs[4]);
-    // the MISCLASS search has no division and nothing to hoist: the round-1 kernel stays (4.46 against 4.76 ms).
-    int wpb = 1;
-    if (tab_kind != 0) {
-      const int cus = device_cus(e->device);
-      wpb = (int)std::min<size_t>(16, std::max<size_t>(1, (groups + cus - 1) / cus));
-      if (tab_kind == 2 && mode != 2) wpb = std::min(wpb, SPLIT_LEAN_WAVES);
-    }
-    const unsigned blocks = (unsigned)((groups + wpb - 1) / wpb);
-    const size_t lds = tab_kind == 0 ? 0 : (size_t)N * entry_bytes;
-    (void)hipEventRecord(e->ev_a, e->stream);
-    // TAB8 is the launch for the 8-byte table. The macros name k_split_ord_lean for modes 0 and 1 only and
-    // k_split_ord<M, TI, 2> for mode 2 only, so the code object holds no instantiation that is never launched.
-#define CC_LAUNCH_ORD3(M, TI, T)                                                                                              \
-  do {                                                                                                                        \
-    if (lds > 64 * 1024)                                                                                                      \
-      CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_split_ord<M, TI, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((k_split_ord<M, TI, T>), dim3(blocks), dim3(64 * wpb), lds, e->stream, A);                             \
-  } while (0)
-#define CC_LAUNCH_LEAN(M, TI)                                                                                                 \
-  do {                                                                                                                        \
-    if (lds > 64 * 1024)                                                                                                      \
-      CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_split_ord_lean<M, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((k_split_ord_lean<M, TI>), dim3(blocks), dim3(64 * wpb), lds, e->stream, A);                           \
-  } while (0)
-#define CC_LAUNCH_ORD3_TAB8(M, TI) CC_LAUNCH_ORD3(M, TI, 2)
-#define CC_LAUNCH_ORD2(M, TI, TAB8)    \
-  do {                                 \
-    if (tab_kind == 0)                 \
-      CC_LAUNCH_ORD3(M, TI, 0);        \
-    else if (tab_kind == 1)            \
-      CC_LAUNCH_ORD3(M, TI, 1);        \
-    else                               \
-      TAB8(M, TI);                     \
-  } while (0)
-#define CC_LAUNCH_ORD(M, TAB8)           \
-  do {                                   \
-    if (idx16)                           \
-      CC_LAUNCH_ORD2(M, uint16_t, TAB8); \
-    else                                 \
-      CC_LAUNCH_ORD2(M, int32_t, TAB8);  \
-  } while (0)
-    if (mode == 0)
-      CC_LAUNCH_ORD(0, CC_LAUNCH_LEAN);
-    else if (mode == 1)
-      CC_LAUNCH_ORD(1, CC_LAUNCH_LEAN);
-    else
-      CC_LAUNCH_ORD(2, CC_LAUNCH_ORD3_TAB8);
-#undef CC_LAUNCH_ORD
-#undef CC_LAUNCH_ORD3_TAB8
-#undef CC_LAUNCH_LEAN
-#undef CC_LAUNCH_ORD2
-#undef CC_LAUNCH_ORD3
-    (void)hipEventRecord(e->ev_b, e->stream);
-    CC_HIP(hipGetLastError());
-    CC_HIP(pin_out.ensure(fpad * 24));
-    CC_HIP(hipMemcpyAsync(pin_out.p, e->d_split_out.p, fpad * 20, hipMemcpyDeviceToHost, e->stream));
-    CC_HIP(hipStreamSynchronize(e->stream));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, e->ev_a, e->ev_b) == hipSuccess) e->last_ms = ms;
-    const double* bv = static_cast<const double*>(pin_out.p);
-    const int* bi = reinterpret_cast<const int*>(bv + fpad);
-    const float* vl = reinterpret_cast<const float*>(bi + fpad);
-    const float* vr = vl + fpad;
-    // the winner, variable by variable as DTreeBestSplitFinder::operator() does (o_cvdtree.cpp:320-342): a variable
-    // reports a split only if it beats the best quality so far (a float), and replaces it only if its own quality,
-    // rounded to float, is larger
-    float best_q = -1.f;
-    int winner = -1;
-    for (int f = 0; f < F; f++) {
-      if (per_var_quality) per_var_quality[f] = bi[f] >= 0 ? bv[f] : -1.0;
-      if (per_var_point) per_var_point[f] = bi[f];
-      if (bi[f] < 0 || !((double)best_q < bv[f])) continue;
-      const float q = (float)bv[f];
-      if (best_q < q) {
-        best_q = q;
-        winner = f;
-      }
-    }
-    if (winner >= 0 && best_q > 0) {  // o_cvdtree.cpp:351
-      out->found = 1;
-      out->var_idx = var0 + winner;
-      out->quality = best_q;
-      out->ord_c = (vl[winner] + vr[winner]) * 0.5f;
-      out->split_point = bi[winner];
-    }
-    return CC_OK;
-  }
-  // ---- categorical (LBP) ----
-  const size_t hist_n = (size_t)F * 256 * 2;
-  CC_HIP(e->d_split_out.ensure(hist_n));
-  bool ascending = true;  // the node lists its samples in increasing order: what k_split_cat_sorted's exactness needs
-  for (int i = 1; i < n && ascending && sample_idx; i++) ascending = sample_idx[i - 1] < sample_idx[i];
-  const bool stream_only = std::getenv("CCAMD_SPLIT_CAT_STREAM") != nullptr;  // read per call: tests compare the two paths
-  if (ascending && e->cat_sorted_n == N && !stream_only) {
-    bool unit_responses = !is_classifier;
-    if (!is_classifier)
-      for (int i = 0; i < n && unit_responses; i++) unit_responses = responses[i] == 1.0f || responses[i] == -1.0f;
-    const size_t lds_cap = 160 * 1024;
-    int tab_kind = 0;  // as for the ordered search: 2 = 8-byte entries in LDS, 1 = 16-byte entries in LDS, 0 = global memory
-    if ((is_classifier || unit_responses) && (size_t)N * 8 <= lds_cap)
-      tab_kind = 2;
-    else if ((size_t)N * 16 <= lds_cap)
-      tab_kind = 1;
-    if (std::getenv("CCAMD_SPLIT_GLOBAL_TABLE")) tab_kind = 0;
-    const size_t entry_bytes = tab_kind == 2 ? 8 : 16;
-    CC_HIP(pin_in.ensure((size_t)N * entry_bytes));
-    SplitEntry* tab16 = static_cast<SplitEntry*>(pin_in.p);
-    double* tab8 = static_cast<double*>(pin_in.p);
-    std::memset(pin_in.p, 0, (size_t)N * entry_bytes);  // not in the node: +0.0 / {0, 0}, adds nothing to any sum
-    for (int i = 0; i < n; i++) {  // strictly increasing: no sample twice
-      const int g = sample_idx ? sample_idx[i] : i;
-      if (g < 0 || g >= N) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_find_best_split: sample index %d outside the %d presorted samples", g, N);
-      const double w = weights[i];
-      if (tab_kind == 2)
-        tab8[g] = is_classifier ? (class_labels[i] ? -w : w) : responses[i] * w;
-      else {
-        tab16[g].w = w;
-        tab16[g].t = is_classifier ? (double)class_labels[i] : responses[i] * w;
-      }
-    }
-    CC_HIP(e->d_split_tab.ensure((size_t)N * 2));
-    CC_HIP(hipMemcpyAsync(e->d_split_tab.p, pin_in.p, (size_t)N * entry_bytes, hipMemcpyHostToDevice, e->stream));
-    (void)hipEventRecord(e->ev_a, e->stream);
-    CC_HIP(hipMemsetAsync(e->d_split_out.p, 0, hist_n * 8, e->stream));  // categories without a sample
-    const size_t groups = ((size_t)F + 63) / 64;
-    SplitCatArgs A;
-    A.packed = e->d_cat_sorted.p;
-    A.tab = reinterpret_cast<const SplitEntry*>(e->d_split_tab.p);
-    A.n_pre = N;
-    A.n_vars = F;
-    A.n_groups = (int)groups;
-    A.hist = e->d_split_out.p;
-    // One wavefront per (group, part); with the table in LDS a block owns a CU (<= 4 wavefronts of it): as many parts as
-    // give every CU a full block, no part shorter than 1 024 ranks. CCAMD_SPLIT_CAT_PARTS overrides (1 = round-4 first form).
-    const int cus = device_cus(e->device);
-    int parts = (int)std::max<size_t>(1, (size_t)cus * 4 / groups);
-    parts = std::max(1, std::min(parts, N / 1024));
-    if (const char* v = std::getenv("CCAMD_SPLIT_CAT_PARTS")) parts = std::max(1, std::min(64, std::atoi(v)));
-    const int chunk = SPLIT_CAT_DEPTH * SPLIT_CAT_UNROLL;
-    A.parts = parts;
-    A.part_len = ((N + parts - 1) / parts + chunk - 1) / chunk * chunk;
-    const size_t units = groups * (size_t)parts;
-    A.waves = tab_kind == 0 ? 4 : (int)std::min<size_t>(4, std::max<size_t>(1, (units + cus - 1) / cus));
-    const unsigned blocks = (unsigned)((units + A.waves - 1) / A.waves);
-    const size_t lds = tab_kind == 0 ? 0 : (size_t)N * entry_bytes;
-#define CC_LAUNCH_CAT(C, T)                                                                                                          \
-  do {                                                                                                                               \
-    if (lds > 64 * 1024)                                                                                                             \
-      CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_split_cat_sorted<C, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((k_split_cat_sorted<C, T>), dim3(blocks), dim3(256), lds, e->stream, A);                                      \
-  } while (0)
-    if (is_classifier) {
-      if (tab_kind == 2)
-        CC_LAUNCH_CAT(true, 2);
-      else if (tab_kind == 1)
-        CC_LAUNCH_CAT(true, 1);
-      else
-        CC_LAUNCH_CAT(true, 0);
-    } else {
-      if (tab_kind == 2)
-        CC_LAUNCH_CAT(false, 2);
-      else if (tab_kind == 1)
-        CC_LAUNCH_CAT(false, 1);
-      else
-        CC_LAUNCH_CAT(false, 0);
-    }
-#undef CC_LAUNCH_CAT
-    (void)hipEventRecord(e->ev_b, e->stream);
-    CC_HIP(hipGetLastError());
-  } else {
-    CC_HIP(pin_in.ensure((size_t)n * (sizeof(SplitEntry) + 4)));
-    SplitEntry* tab = static_cast<SplitEntry*>(pin_in.p);
-    int32_t* idx_host = reinterpret_cast<int32_t*>(tab + n);
-    {
-      std::vector<uint8_t> seen((size_t)N, 0);
-      for (int i = 0; i < n; i++) {
-        const int g = sample_idx ? sample_idx[i] : i;
-        if (g < 0 || g >= N) return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_find_best_split: sample index %d outside the %d presorted samples", g, N);
-        if (seen[(size_t)g]) return set_error(CC_ERR_INVALID_ARG, "cc_eval_find_best_split: sample %d occurs twice in the node", g);
-        seen[(size_t)g] = 1;
-        idx_host[i] = g;
-        tab[i].w = weights[i];
-        tab[i].t = is_classifier ? (double)class_labels[i] : responses[i] * weights[i];
-      }
-    }
-    CC_HIP(e->d_split_tab.ensure((size_t)n * 2));
-    CC_HIP(e->d_split_idx.ensure((size_t)n));
-    CC_HIP(hipMemcpyAsync(e->d_split_tab.p, tab, (size_t)n * sizeof(SplitEntry), hipMemcpyHostToDevice, e->stream));
-    CC_HIP(hipMemcpyAsync(e->d_split_idx.p, idx_host, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    (void)hipEventRecord(e->ev_a, e->stream);
-    if (is_classifier)
-      hipLaunchKernelGGL(k_split_cat<true>, dim3((unsigned)F), dim3(256), 0, e->stream, e->d_codes.p, N, sample_idx ? e->d_split_idx.p : nullptr,
-                         reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), n, e->d_split_out.p);
-    else
-      hipLaunchKernelGGL(k_split_cat<false>, dim3((unsigned)F), dim3(256), 0, e->stream, e->d_codes.p, N, sample_idx ? e->d_split_idx.p : nullptr,
-                         reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), n, e->d_split_out.p);
-    (void)hipEventRecord(e->ev_b, e->stream);
-    CC_HIP(hipGetLastError());
-  }
-  // The 34.7 MB of sums (8 464 variables) come back in pieces; the host's part -- ordering each variable's categories and
-  // scanning them (split_categories) -- starts on a piece as soon as it has landed, on up to 16 threads.
-  CC_HIP(pin_out.ensure(hist_n * 8));
-  constexpr int kPieces = 8;
-  for (int c = 0; c < kPieces; c++)
-    if (!e->ev_piece[c]) CC_HIP(hipEventCreateWithFlags(&e->ev_piece[c], hipEventDisableTiming));
-  const int per_piece = (F + kPieces - 1) / kPieces;
-  double* hist = static_cast<double*>(pin_out.p);
-  for (int c = 0; c < kPieces; c++) {
-    const int f0 = std::min(F, c * per_piece), f1 = std::min(F, f0 + per_piece);
-    if (f1 > f0)
-      CC_HIP(hipMemcpyAsync(hist + (size_t)f0 * 512, e->d_split_out.p + (size_t)f0 * 512, (size_t)(f1 - f0) * 512 * 8, hipMemcpyDeviceToHost, e->stream));
-    CC_HIP(hipEventRecord(e->ev_piece[c], e->stream));
-  }
-  std::vector<CatSplit> res((size_t)F);
-  std::atomic<int> copy_failed{0};
-  const bool trace = std::getenv("CCAMD_TRACE_SPLIT") != nullptr;  // host-side timeline of the call's tail (stderr)
-  const auto t_enq = std::chrono::steady_clock::now();
-  double landed_ms[kPieces] = {};
-  {
-    const int nt = std::max(1, std::min<int>({(int)std::thread::hardware_concurrency(), 16, F / 64 + 1}));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++)
-      th.emplace_back([&, t]() {
-        for (int c = 0; c < kPieces; c++) {
-          if (hipEventSynchronize(e->ev_piece[c]) != hipSuccess) {
-            copy_failed = 1;
-            return;
-          }
-          if (trace && t == 0) landed_ms[c] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq).count();
-          const int f0 = std::min(F, c * per_piece), f1 = std::min(F, f0 + per_piece);
-          for (int f = f0 + t; f < f1; f += nt) split_categories(hist + (size_t)f * 512, 256, is_classifier, gini, res[(size_t)f]);
-        }
-      });
-    for (auto& x : th) x.join();
-  }
-  if (trace) {
-    std::fprintf(stderr, "[ccamd split] after the last enqueue: pieces landed (as seen by worker 0) at");
-    for (int c = 0; c < kPieces; c++) std::fprintf(stderr, " %.2f", landed_ms[c]);
-    std::fprintf(stderr, " ms; workers done at %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq).count());
-  }
-  CC_HIP(hipStreamSynchronize(e->stream));
-  if (copy_failed) return set_error(CC_ERR_HIP, "cc_eval_find_best_split: copying the category sums back failed");
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, e->ev_a, e->ev_b) == hipSuccess) e->last_ms = ms;
-  float best_q = -1.f;
-  int winner = -1;
-  for (int f = 0; f < F; f++) {
-    const CatSplit& r = res[(size_t)f];
-    if (per_var_quality) per_var_quality[f] = r.found ? r.quality : -1.0;
-    if (per_var_point) per_var_point[f] = r.found ? r.n_left - 1 : -1;
-    if (!r.found || !((double)best_q < r.quality)) continue;
-    const float q = (float)r.quality;
-    if (best_q < q) {
-      best_q = q;
-      winner = f;
-    }
-  }
-  if (winner >= 0 && best_q > 0) {
-    out->found = 1;
-    out->var_idx = var0 + winner;
-    out->quality = best_q;
-    std::memcpy(out->subset, res[(size_t)winner].subset, sizeof(out->subset));
-  }
-  return CC_OK;
+  const SplitQuery q{e, sample_idx, n, weights, responses, class_labels, node_value, is_classifier, criteria == 1, N, F, e->presort_f0, out,
+                     per_var_quality, per_var_point};
+  return e->type != CC_FEATURE_LBP ? search_ordered(q) : search_categorical(q);  // ordered variables: Haar, HOG
 }
 
 }  // extern "C"
