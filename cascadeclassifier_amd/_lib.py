@@ -103,6 +103,9 @@ SIGNATURES = {
     "cc_detect_batch_submit_fmt": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _pp]),
     "cc_detect_batch_to_device": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _vp, _i, _vp,
                                        C.POINTER(_i)]),
+    "cc_detect_batch_levels_fmt": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _vp, _vp, _vp, _i, _vp]),
+    "cc_detect_batch_to_device_levels": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _sz, _i, C.POINTER(DetectParams), _vp, _vp, _vp, _i,
+                                              _vp, C.POINTER(_i)]),
     "cc_detect_multiscale_levels_fmt": (_i, [_vp, _vp, _i, _i, _sz, _i, C.POINTER(DetectParams), _vp, _vp, _vp, _i,
                                              C.POINTER(_i)]),
     "cc_to_gray_u8": (_i, [_i, _vp, _i, _i, _i, _sz, _vp, _sz]),
@@ -127,6 +130,8 @@ SIGNATURES = {
     "cc_debug_vnf_check": (_i, [_i, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cc_group_rectangles": (_i, [_vp, _i, _i, _d, _vp, _i, C.POINTER(_i)]),
     "cc_group_rectangles_device": (_i, [_i, _vp, _vp, _i, _i, _d, _vp, _i, _vp, C.POINTER(_i)]),
+    "cc_group_rectangles_levels": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "cc_group_rectangles_device_levels": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _i, _vp, C.POINTER(_i)]),
     "cc_eval_create": (_i, [_i, _i, _i, _i, _i, _i, _pp]),
     "cc_eval_destroy": (None, [_vp]),
     "cc_eval_num_features": (_i, [_vp]),

@@ -173,11 +173,15 @@ inline FrameSet host_image(const uint8_t* img, int width, int height, size_t row
 
 // Where the grouped rectangles of a device-output pass go (cc_detect_batch_to_device): the caller's device buffers, with
 // d_offsets already at the pass's first frame. d_offsets null: a host-output pass, whose candidates go to its sink.
+// d_weights set: with scores (cc_detect_batch_to_device_levels), d_levels / d_weights beside d_out, every level = `level`.
 struct DeviceOutput {
   cc_rect* d_out = nullptr;
   int cap = 0;
   int32_t* d_offsets = nullptr;
   int min_neighbors = 0;
+  int32_t* d_levels = nullptr;
+  double* d_weights = nullptr;
+  int level = 0;
   explicit operator bool() const { return d_offsets != nullptr; }
 };
 
@@ -894,13 +898,15 @@ static cc_status read_back_counts(cc_detector* d, int slot) {
 // zeroed the counters by then): that is what writes such a pass's offsets.
 static cc_status enqueue_group(cc_detector* d, const cc_detector::PendingPass& ps) {
   // sized here, where cand_cap is known; allocates only while the detector's lists or passes are still growing
-  CC_HIP(d->group.ensure((size_t)std::max(d->cand_cap, 1), (size_t)d->pass_capacity, true));
+  const bool scored = ps.dev.d_weights != nullptr;  // the scored buffers come with the detector's first scored pass
+  CC_HIP(d->group.ensure((size_t)std::max(d->cand_cap, 1), (size_t)d->pass_capacity, true, scored));
   const GroupGuard g{d->d_counts[ps.slot].p, d->cand_cap, d->d_group_state.p + 1};
+  const GroupScores sc{scored, nullptr, ps.dev.level, d->group.ordered_weights.p, ps.dev.d_levels, ps.dev.d_weights};
   {
     EvScope ev(d, EV_GROUP, d->stream);
-    launch_order_candidates(d->stream, g, d->d_out[ps.slot].p, ps.nf, d->group);
+    launch_order_candidates(d->stream, g, d->d_out[ps.slot].p, ps.nf, d->group, scored);
     launch_group_frames(d->stream, g, d->group.ordered.p, d->group.seg.p, ps.nf, ps.dev.min_neighbors, 0.2, d->group, ps.dev.d_out,
-                        ps.dev.cap, ps.dev.d_offsets, d->d_group_state.p);
+                        ps.dev.cap, ps.dev.d_offsets, d->d_group_state.p, sc);
   }
   CC_HIP(hipGetLastError());
   return CC_OK;
@@ -1376,9 +1382,17 @@ static void sort_candidates(std::vector<CandOut>& v) {
   });
 }
 
+// A frame's reject levels and level weights, beside its rectangles (cc_detect_batch_levels_fmt).
+struct FrameScores {
+  std::vector<int> levels;
+  std::vector<double> weights;
+};
+
 // Host side of one pass (called while the device already runs the next pass). Per frame: order the candidates (scale, y, x)
 // = OpenCV's single-threaded order, then group. Frames are independent, so they are spread over a few host threads.
-static void group_pass(int min_neighbors, int f0, int nf, std::vector<CandOut>& cands, std::vector<std::vector<cc_rect>>& grouped) {
+// scores: grouped as cc_detect_multiscale_levels_fmt groups, every candidate with `level` and its last stage's sum.
+static void group_pass(int min_neighbors, int f0, int nf, std::vector<CandOut>& cands, std::vector<std::vector<cc_rect>>& grouped,
+                       std::vector<FrameScores>* scores = nullptr, int level = 0) {
   std::vector<std::vector<CandOut>> per_frame((size_t)nf);
   for (const CandOut& c : cands) per_frame[(size_t)(c.frame - f0)].push_back(c);
   auto work = [&](int a0, int a1) {
@@ -1387,7 +1401,14 @@ static void group_pass(int min_neighbors, int f0, int nf, std::vector<CandOut>& 
       std::vector<cc_rect>& rects = grouped[(size_t)(f0 + f)];
       rects.reserve(per_frame[(size_t)f].size());
       for (const CandOut& c : per_frame[(size_t)f]) rects.push_back(cc_rect{c.x, c.y, c.w, c.h});
-      group_rectangles(rects, min_neighbors, 0.2);  // GROUP_EPS
+      if (scores) {
+        FrameScores& fs = (*scores)[(size_t)(f0 + f)];
+        fs.levels.assign(rects.size(), level);
+        fs.weights.reserve(rects.size());
+        for (const CandOut& c : per_frame[(size_t)f]) fs.weights.push_back(c.sum);
+        group_rectangles(rects, min_neighbors, 0.2, &fs.levels, &fs.weights);
+      } else
+        group_rectangles(rects, min_neighbors, 0.2);  // GROUP_EPS
     }
   };
   const int nthr = std::max(1, std::min({nf, (int)std::thread::hardware_concurrency(), 16}));
@@ -1828,19 +1849,51 @@ cc_status cc_detect_batch_fmt(cc_detector* d, const uint8_t* frames, int on_devi
   return CC_OK;
 }
 
+// cc_detect_batch_fmt with scores: the same passes, and a sink that groups with levels and weights.
+cc_status cc_detect_batch_levels_fmt(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
+                                     size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p, cc_rect* out,
+                                     int32_t* reject_levels, double* level_weights, int cap, int32_t* offsets) {
+  const FrameSet F{frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format};
+  cc_status st = check_frame_args(d, F, p, "cc_detect_batch_levels");
+  if (st != CC_OK) return st;
+  if (!offsets || cap < 0 || (cap > 0 && (!out || !reject_levels || !level_weights)))
+    return set_error(CC_ERR_INVALID_ARG, "cc_detect_batch_levels: bad output buffers");
+  std::vector<std::vector<cc_rect>> grouped((size_t)n_frames);
+  std::vector<FrameScores> scores((size_t)n_frames);
+  const int min_neighbors = p->min_neighbors, nstages = (int)d->m.stage_ntrees.size();
+  auto sink = std::make_shared<BatchSink>();
+  sink->consume = [&](int f0, int nf, std::vector<CandOut>& cands) { group_pass(min_neighbors, f0, nf, cands, grouped, &scores, nstages); };
+  st = run_batch(d, F, p, sink);
+  if (st != CC_OK) return st;
+  const long long total = flatten_grouped(grouped, out, cap, offsets);
+  long long at = 0;
+  for (const FrameScores& fs : scores)
+    for (size_t i = 0; i < fs.levels.size(); i++, at++)
+      if (at < cap) {
+        reject_levels[at] = fs.levels[i];
+        level_weights[at] = fs.weights[i];
+      }
+  if (total > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_detect_batch_levels: %lld rectangles, capacity %d", total, cap);
+  return CC_OK;
+}
+
 // The device-output batch: the passes of cc_detect_batch through the same loop (run_batch), each followed on the detector's
 // stream by the ordering and grouping kernels, which append to the caller's buffers (enqueue_group). The host reads back the
 // batch's total at the end and nothing else of the results.
-cc_status cc_detect_batch_to_device(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
-                                    size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p,
-                                    cc_rect* d_out, int cap, int32_t* d_offsets, int* n_total) {
-  const FrameSet F{frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format};
+// `scored`: cc_detect_batch_to_device_levels, whose passes run the scored kernels and write d_levels / d_weights as well.
+static cc_status detect_batch_to_device(cc_detector* d, const FrameSet& F, const cc_detect_params* p, cc_rect* d_out, bool scored,
+                                        int32_t* d_levels, double* d_weights, int cap, int32_t* d_offsets, int* n_total) {
   cc_status st = check_frame_args(d, F, p, "cc_detect_batch_to_device");
   if (st != CC_OK) return st;
-  if (!d_offsets || !n_total || (cap > 0 && !d_out) || cap < 0)
+  if (!d_offsets || !n_total || (cap > 0 && !d_out) || cap < 0 || (scored && (!d_levels || !d_weights)))
     return set_error(CC_ERR_INVALID_ARG, "cc_detect_batch_to_device: bad output buffers");
   BatchOptions opt;
   opt.dev = DeviceOutput{d_out, cap, d_offsets, p->min_neighbors};
+  if (scored) {
+    opt.dev.d_levels = d_levels;
+    opt.dev.d_weights = d_weights;
+    opt.dev.level = (int)d->m.stage_ntrees.size();
+  }
   st = run_batch(d, F, p, std::make_shared<BatchSink>(), opt);
   if (st != CC_OK) return st;
   int total = 0;
@@ -1848,6 +1901,21 @@ cc_status cc_detect_batch_to_device(cc_detector* d, const uint8_t* frames, int o
   *n_total = total;
   if (total > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_detect_batch_to_device: %d rectangles, capacity %d", total, cap);
   return CC_OK;
+}
+
+cc_status cc_detect_batch_to_device(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
+                                    size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p,
+                                    cc_rect* d_out, int cap, int32_t* d_offsets, int* n_total) {
+  const FrameSet F{frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format};
+  return detect_batch_to_device(d, F, p, d_out, false, nullptr, nullptr, cap, d_offsets, n_total);
+}
+
+cc_status cc_detect_batch_to_device_levels(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width, int height,
+                                           size_t row_stride, size_t frame_stride, int pixel_format, const cc_detect_params* p,
+                                           cc_rect* d_out, int32_t* d_levels, double* d_weights, int cap, int32_t* d_offsets,
+                                           int* n_total) {
+  const FrameSet F{frames, on_device, n_frames, width, height, row_stride, frame_stride, pixel_format};
+  return detect_batch_to_device(d, F, p, d_out, true, d_levels, d_weights, cap, d_offsets, n_total);
 }
 
 struct cc_batch_ticket {

@@ -228,22 +228,38 @@ struct GroupGuard {
   int cand_cap = 0;
   int* abort = nullptr;
 };
-constexpr int GROUP_WS_INTS = 7;  // workspace ints per rectangle of k_group_frames
+constexpr int GROUP_WS_INTS = 7;          // workspace ints per rectangle of k_group_frames
+constexpr int GROUP_WS_INTS_SCORED = 10;  // of k_group_frames_scored: + the class level and the class weight's 64-bit image
+// The scored form of both helpers (cv::groupRectangles with rejectLevels and levelWeights): a level and a weight per input
+// rectangle (levels null: const_level for all of them, the detector's case) and where the survivors' go, beside `out`.
+// Default: unscored.
+struct GroupScores {
+  bool scored = false;
+  const int32_t* levels = nullptr;
+  int const_level = 0;
+  const double* weights = nullptr;
+  int32_t* out_levels = nullptr;
+  double* out_weights = nullptr;
+  explicit operator bool() const { return scored; }
+};
 // Device workspace of the two launch helpers below, owned by the caller; ensure() only grows it (the detector sizes it for
-// its candidate capacity and pass size, so a warm pass allocates nothing).
+// its candidate capacity and pass size, so a warm pass allocates nothing). What only scored calls use -- the ordered weights,
+// the staged levels and weights, the wider ws -- is allocated by the first ensure(scored = true).
 struct GroupBufs {
   DevBuf<cc_rect> ordered, grouped;  // a pass's rectangles in candidate order; each frame's result at its input offset
   DevBuf<unsigned long long> keys;
-  DevBuf<int> src, seg, frame_cnt, out_count, ws;  // seg: frames + 1 segment offsets of `ordered`; ws: GROUP_WS_INTS per rectangle
-  hipError_t ensure(size_t rects, size_t frames, bool ordering);
+  DevBuf<int> src, seg, frame_cnt, out_count, ws;  // seg: frames + 1 segment offsets of `ordered`; ws: GROUP_WS_INTS(_SCORED) per rectangle
+  DevBuf<double> ordered_weights, grouped_weights;  // scored: beside ordered / grouped
+  DevBuf<int32_t> grouped_levels;
+  hipError_t ensure(size_t rects, size_t frames, bool ordering, bool scored = false);
 };
 // Only launches, on `st`. The filtered candidates of a pass of nf frames -> B.ordered in (frame, scale, gy, gx) order with
-// B.seg as its per-frame offsets.
-void launch_order_candidates(hipStream_t st, GroupGuard g, const CandOut* cands, int nf, GroupBufs& B);
+// B.seg as its per-frame offsets; scored: their stage sums -> B.ordered_weights in the same order.
+void launch_order_candidates(hipStream_t st, GroupGuard g, const CandOut* cands, int nf, GroupBufs& B, bool scored = false);
 // cv::groupRectangles on each of nf frames (frame f: rects[offsets[f] .. offsets[f + 1])). The results go to `out` from
 // *total on, frame after frame, only what lies below cap being written; out_offsets[0 .. nf] receives their offsets and *total
-// moves on by their number.
+// moves on by their number. sc: with levels and weights, B sized by ensure(scored = true).
 void launch_group_frames(hipStream_t st, GroupGuard g, const cc_rect* rects, const int* offsets, int nf, int group_threshold, double eps,
-                         GroupBufs& B, cc_rect* out, int cap, int32_t* out_offsets, int* total);
+                         GroupBufs& B, cc_rect* out, int cap, int32_t* out_offsets, int* total, const GroupScores& sc = GroupScores{});
 
 }  // namespace ccamd

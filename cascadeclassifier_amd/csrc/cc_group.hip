@@ -5,9 +5,16 @@
 // float and double operations, and nothing here depends on the order in which threads run ("Results that
 // stay on the device").
 //
+// The scored forms (k_cand_rank<true>, k_group_frames_scored, k_group_compact<true>) carry what cv::groupRectangles(rects,
+// rejectLevels, levelWeights, ...) carries: a level and a weight per rectangle, and per class the highest level and the largest
+// weight among the members at that level (group_rectangles with both vectors, cc_host.cpp). The unscored kernels are the
+// instantiations they were before.
+//
 // Every kernel finds its element counts in device memory (the filtered-candidate count, the segment offsets): the host
 // launches fixed grids and never waits for a count before the next launch.
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
 
 #include "cc_detect_internal.h"
 
@@ -21,6 +28,9 @@ __device__ __forceinline__ bool pass_dead(const GroupGuard g) { return (g.counts
 // Workspace words are written with atomics by some steps and read by other threads after a barrier: reads go to the
 // coherent level (in LDS this is a plain ds_read), and ws_sync orders plain stores to the global workspace as well.
 __device__ __forceinline__ int ws_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long ws_ld(const unsigned long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 __device__ __forceinline__ void ws_sync() {
   __threadfence();
   __syncthreads();
@@ -56,7 +66,7 @@ __device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int& carry) {
 //   k_cand_count    candidates per frame
 //   k_cand_segments exclusive scan -> seg[nf + 1], cursors cleared
 //   k_cand_bucket   key + list index of every candidate into its frame's segment (any order inside it)
-//   k_cand_rank     rank inside the segment -> the rectangle at seg[f] + rank
+//   k_cand_rank     rank inside the segment -> the rectangle at seg[f] + rank (SCORED: and the candidate's stage sum beside it)
 // ------------------------------------------------------------------------------------------------
 constexpr int ORDER_THREADS = 256;
 constexpr int RANK_CHUNKS = 8;  // blocks that share one frame's ranks
@@ -109,9 +119,10 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_cand_bucket(GroupGuard g, con
 
 // grid (nf, RANK_CHUNKS): the blocks of a frame take its candidates in turns of ORDER_THREADS and count, for each, the
 // frame's keys below it, a tile of keys at a time through LDS.
+template <bool SCORED>
 __global__ __launch_bounds__(ORDER_THREADS) void k_cand_rank(GroupGuard g, const CandOut* __restrict__ cands, const int* __restrict__ seg,
                                                              const unsigned long long* __restrict__ keys, const int* __restrict__ src,
-                                                             cc_rect* __restrict__ rects) {
+                                                             cc_rect* __restrict__ rects, double* __restrict__ sums) {
   if (pass_dead(g)) return;
   __shared__ unsigned long long s_keys[ORDER_THREADS];
   const int base = seg[blockIdx.x], n = seg[blockIdx.x + 1] - base;
@@ -129,6 +140,7 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_cand_rank(GroupGuard g, const
     if (i < n) {
       const CandOut c = cands[src[base + i]];
       rects[base + rank] = cc_rect{c.x, c.y, c.w, c.h};  // rank < n: the keys are distinct
+      if constexpr (SCORED) sums[base + rank] = c.sum;
     }
   }
 }
@@ -145,9 +157,39 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_cand_rank(GroupGuard g, const
 //             k_group_offsets / k_group_compact pack the frames behind one another
 // Workspace: GROUP_WS_INTS ints per rectangle -- parent, class of a root (later: nothing), and per class x y w h sums and the
 // count. In LDS up to GROUP_LDS_RECTS rectangles, else the frame's slice of the caller's global workspace.
+// Scored (group_rectangles with levels and weights, cc_host.cpp "outputRejectLevels variant"): per class also
+//   level     max(0, highest member level): an integer atomicMax from 0, beside the sums
+//   weight    the largest weight among the members at that level, from DBL_MIN when the level stayed 0: a 64-bit atomicMax
+//             over weight_key, an unsigned image of the double in which the integers order as the values do. Both maxima
+//             are the same whatever order the members arrive in. (+0.0 and -0.0 are equal values with different images: where
+//             they tie for a class's best, the host keeps the one it met first and the device +0.0. NaN has no place in
+//             the order on either side.)
+// and the workspace is GROUP_WS_INTS_SCORED ints per rectangle: the seven, the level, and the two halves of the weight's
+// image (8-byte aligned: it starts 8 n ints into a slice that starts at an even number of ints). In LDS up to
+// GROUP_LDS_RECTS_SCORED rectangles.
 // ------------------------------------------------------------------------------------------------
 constexpr int GROUP_THREADS = 1024;
 constexpr int GROUP_LDS_RECTS = 2048;  // 7 x 2048 x 4 B = 56 KiB of the 64 KiB a block may declare
+constexpr int GROUP_LDS_RECTS_SCORED = 1536;  // 10 x 1536 x 4 B = 60 KiB
+static_assert(GROUP_WS_INTS_SCORED % 2 == 0, "a frame's slice of the scored workspace starts 8-byte aligned");
+
+// What the scored grouping reads and writes beside the rectangles; levels null: every rectangle has const_level.
+struct ScoresIO {
+  const int32_t* levels;
+  int const_level;
+  const double* weights;
+  int32_t* out_levels;
+  double* out_weights;
+};
+
+// a < b as doubles (neither NaN, and not a zero against the other zero) <=> weight_key(a) < weight_key(b) as integers
+__device__ __forceinline__ unsigned long long weight_key(double w) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(w);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_weight(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
 
 __device__ __forceinline__ bool similar_rects(const cc_rect a, const cc_rect b, double eps) {
   const double delta = eps * (min(a.width, b.width) + min(a.height, b.height)) * 0.5;
@@ -175,8 +217,10 @@ __device__ __forceinline__ void unite(int* parent, int i, int j) {
   }
 }
 
+// sc: the frame's own levels / weights and where its survivors' go (SCORED only; offsets as for rects / out).
+template <bool SCORED>
 __device__ __forceinline__ void group_frame(int* ws, int* s_wave, const cc_rect* __restrict__ rects, int n, int group_threshold,
-                                            double eps, cc_rect* __restrict__ out, int* __restrict__ out_count) {
+                                            double eps, cc_rect* __restrict__ out, int* __restrict__ out_count, const ScoresIO sc) {
   int* parent = ws;
   int* cls = ws + n;
   int* sx = ws + 2 * (size_t)n;
@@ -184,6 +228,8 @@ __device__ __forceinline__ void group_frame(int* ws, int* s_wave, const cc_rect*
   int* sw = ws + 4 * (size_t)n;
   int* sh = ws + 5 * (size_t)n;
   int* cnt = ws + 6 * (size_t)n;
+  int* lvl = ws + 7 * (size_t)n;                                                                  // SCORED
+  unsigned long long* wkey = reinterpret_cast<unsigned long long*>(ws + 8 * (size_t)n);  // SCORED
   const int tid = threadIdx.x;
   for (int i = tid; i < n; i += GROUP_THREADS) parent[i] = i;
   ws_sync();
@@ -206,7 +252,13 @@ __device__ __forceinline__ void group_frame(int* ws, int* s_wave, const cc_rect*
     const int c = block_excl_scan<GROUP_THREADS>(root ? 1 : 0, s_wave, nclasses);
     if (root) cls[i] = c;
   }
-  for (int c = tid; c < nclasses; c += GROUP_THREADS) sx[c] = sy[c] = sw[c] = sh[c] = cnt[c] = 0;
+  for (int c = tid; c < nclasses; c += GROUP_THREADS) {
+    sx[c] = sy[c] = sw[c] = sh[c] = cnt[c] = 0;
+    if constexpr (SCORED) {
+      lvl[c] = 0;
+      wkey[c] = 0;  // below every weight's image
+    }
+  }
   ws_sync();
   for (int i = tid; i < n; i += GROUP_THREADS) {
     const cc_rect r = rects[i];
@@ -216,8 +268,14 @@ __device__ __forceinline__ void group_frame(int* ws, int* s_wave, const cc_rect*
     atomicAdd(sw + c, r.width);
     atomicAdd(sh + c, r.height);
     atomicAdd(cnt + c, 1);
+    if constexpr (SCORED) atomicMax(lvl + c, sc.levels ? sc.levels[i] : sc.const_level);
   }
   ws_sync();
+  if constexpr (SCORED)  // the class levels are final: the members at their class's level offer their weights
+    for (int i = tid; i < n; i += GROUP_THREADS) {
+      const int c = ws_ld(cls + ws_ld(parent + i));
+      if ((sc.levels ? sc.levels[i] : sc.const_level) == ws_ld(lvl + c)) atomicMax(wkey + c, weight_key(sc.weights[i]));
+    }
   for (int c = tid; c < nclasses; c += GROUP_THREADS) {
     const float s = __fdiv_rn(1.f, (float)ws_ld(cnt + c));
     const int x = __float2int_rn((float)ws_ld(sx + c) * s), y = __float2int_rn((float)ws_ld(sy + c) * s);
@@ -249,6 +307,13 @@ __device__ __forceinline__ void group_frame(int* ws, int* s_wave, const cc_rect*
     }
     const int at = block_excl_scan<GROUP_THREADS>(keep ? 1 : 0, s_wave, n_out);
     if (keep) out[at] = r1;  // at < nclasses <= n
+    if constexpr (SCORED)
+      if (keep) {
+        // a class of level 0 starts from DBL_MIN, one of a higher level has a member at that level (its image is not 0)
+        const int l = ws_ld(lvl + c);
+        sc.out_levels[at] = l;
+        sc.out_weights[at] = key_weight(max(ws_ld(wkey + c), l == 0 ? weight_key(DBL_MIN) : 0ull));
+      }
   }
   if (tid == 0) *out_count = n_out;
 }
@@ -268,9 +333,37 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_frames(GroupGuard g, co
     return;
   }
   if (n <= GROUP_LDS_RECTS)
-    group_frame(s_ws, s_wave, rects + base, n, group_threshold, eps, grouped + base, out_count + f);
+    group_frame<false>(s_ws, s_wave, rects + base, n, group_threshold, eps, grouped + base, out_count + f, ScoresIO{});
   else
-    group_frame(ws + (size_t)GROUP_WS_INTS * base, s_wave, rects + base, n, group_threshold, eps, grouped + base, out_count + f);
+    group_frame<false>(ws + (size_t)GROUP_WS_INTS * base, s_wave, rects + base, n, group_threshold, eps, grouped + base, out_count + f,
+                       ScoresIO{});
+}
+
+// k_group_frames with levels and weights: sc.levels / sc.weights lie beside rects, sc.out_levels / sc.out_weights beside grouped.
+__global__ __launch_bounds__(GROUP_THREADS) void k_group_frames_scored(GroupGuard g, const cc_rect* __restrict__ rects,
+                                                                       const int* __restrict__ offsets, int group_threshold, double eps,
+                                                                       int* __restrict__ ws, cc_rect* __restrict__ grouped,
+                                                                       int* __restrict__ out_count, const ScoresIO sc) {
+  if (pass_dead(g)) return;
+  __shared__ __attribute__((aligned(8))) int s_ws[GROUP_WS_INTS_SCORED * GROUP_LDS_RECTS_SCORED];
+  __shared__ int s_wave[GROUP_THREADS / 64];
+  const int f = blockIdx.x;
+  const int base = offsets[f], n = offsets[f + 1] - base;
+  if (group_threshold <= 0 || n <= 0) {  // the ordered candidates as they are, with their levels and weights
+    for (int i = threadIdx.x; i < n; i += GROUP_THREADS) {
+      grouped[base + i] = rects[base + i];
+      sc.out_levels[base + i] = sc.levels ? sc.levels[base + i] : sc.const_level;
+      sc.out_weights[base + i] = sc.weights[base + i];
+    }
+    if (threadIdx.x == 0) out_count[f] = max(n, 0);
+    return;
+  }
+  const ScoresIO fs{sc.levels ? sc.levels + base : nullptr, sc.const_level, sc.weights + base, sc.out_levels + base, sc.out_weights + base};
+  if (n <= GROUP_LDS_RECTS_SCORED)
+    group_frame<true>(s_ws, s_wave, rects + base, n, group_threshold, eps, grouped + base, out_count + f, fs);
+  else
+    group_frame<true>(ws + (size_t)GROUP_WS_INTS_SCORED * base, s_wave, rects + base, n, group_threshold, eps, grouped + base,
+                      out_count + f, fs);
 }
 
 // One block. Frames f0 .. f0 + nf of the batch: out_offsets[f0 + i] = *total + (rectangles of the frames before i);
@@ -295,53 +388,77 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_group_offsets(GroupGuard g, c
   }
 }
 
-// grid nf: frame f's rectangles from its input offset of `grouped` to its place in `out`, what fits below cap.
+// grid nf: frame f's rectangles from its input offset of `grouped` to its place in `out`, what fits below cap. SCORED: their
+// levels and weights move with them (sc.levels / sc.weights beside grouped, sc.out_levels / sc.out_weights beside out).
+template <bool SCORED>
 __global__ __launch_bounds__(ORDER_THREADS) void k_group_compact(GroupGuard g, const cc_rect* __restrict__ grouped,
                                                                  const int* __restrict__ offsets, const int32_t* __restrict__ out_offsets,
-                                                                 cc_rect* __restrict__ out, int cap) {
+                                                                 cc_rect* __restrict__ out, int cap, const ScoresIO sc) {
   if (pass_dead(g)) return;
   const int f = blockIdx.x;
   const int from = offsets[f], to = out_offsets[f], n = out_offsets[f + 1] - to;
   for (int i = threadIdx.x; i < n; i += ORDER_THREADS)
-    if (to + i < cap) out[to + i] = grouped[from + i];
+    if (to + i < cap) {
+      out[to + i] = grouped[from + i];
+      if constexpr (SCORED) {
+        sc.out_levels[to + i] = sc.levels[from + i];
+        sc.out_weights[to + i] = sc.weights[from + i];
+      }
+    }
 }
 
-hipError_t GroupBufs::ensure(size_t rects, size_t frames, bool ordering) {
+hipError_t GroupBufs::ensure(size_t rects, size_t frames, bool ordering, bool scored) {
   rects = std::max<size_t>(rects, 1);
-  for (hipError_t e : {grouped.ensure(rects), ws.ensure(rects * GROUP_WS_INTS), out_count.ensure(std::max<size_t>(frames, 1)),
+  for (hipError_t e : {grouped.ensure(rects), ws.ensure(rects * (scored ? GROUP_WS_INTS_SCORED : GROUP_WS_INTS)),
+                       out_count.ensure(std::max<size_t>(frames, 1)),
                        ordering ? ordered.ensure(rects) : hipSuccess, ordering ? keys.ensure(rects) : hipSuccess,
                        ordering ? src.ensure(rects) : hipSuccess, ordering ? seg.ensure(frames + 1) : hipSuccess,
-                       ordering ? frame_cnt.ensure(std::max<size_t>(frames, 1)) : hipSuccess})
+                       ordering ? frame_cnt.ensure(std::max<size_t>(frames, 1)) : hipSuccess,
+                       scored ? grouped_levels.ensure(rects) : hipSuccess, scored ? grouped_weights.ensure(rects) : hipSuccess,
+                       scored && ordering ? ordered_weights.ensure(rects) : hipSuccess})
     if (e != hipSuccess) return e;
   return hipSuccess;
 }
 
-void launch_order_candidates(hipStream_t st, const GroupGuard g, const CandOut* cands, int nf, GroupBufs& B) {
+void launch_order_candidates(hipStream_t st, const GroupGuard g, const CandOut* cands, int nf, GroupBufs& B, bool scored) {
   if (nf <= 0) return;
   (void)hipMemsetAsync(B.frame_cnt.p, 0, (size_t)nf * sizeof(int), st);
   hipLaunchKernelGGL(k_cand_count, dim3(64), dim3(ORDER_THREADS), 0, st, g, cands, nf, B.frame_cnt.p);
   hipLaunchKernelGGL(k_cand_segments, dim3(1), dim3(ORDER_THREADS), 0, st, g, nf, B.frame_cnt.p, B.seg.p);
   hipLaunchKernelGGL(k_cand_bucket, dim3(64), dim3(ORDER_THREADS), 0, st, g, cands, nf, B.seg.p, B.frame_cnt.p, B.keys.p, B.src.p);
-  hipLaunchKernelGGL(k_cand_rank, dim3(nf, RANK_CHUNKS), dim3(ORDER_THREADS), 0, st, g, cands, B.seg.p, B.keys.p, B.src.p, B.ordered.p);
+  if (scored)
+    hipLaunchKernelGGL(k_cand_rank<true>, dim3(nf, RANK_CHUNKS), dim3(ORDER_THREADS), 0, st, g, cands, B.seg.p, B.keys.p, B.src.p,
+                       B.ordered.p, B.ordered_weights.p);
+  else
+    hipLaunchKernelGGL(k_cand_rank<false>, dim3(nf, RANK_CHUNKS), dim3(ORDER_THREADS), 0, st, g, cands, B.seg.p, B.keys.p, B.src.p,
+                       B.ordered.p, (double*)nullptr);
 }
 
 void launch_group_frames(hipStream_t st, const GroupGuard g, const cc_rect* rects, const int* offsets, int nf, int group_threshold,
-                         double eps, GroupBufs& B, cc_rect* out, int cap, int32_t* out_offsets, int* total) {
-  if (nf > 0)
+                         double eps, GroupBufs& B, cc_rect* out, int cap, int32_t* out_offsets, int* total, const GroupScores& sc) {
+  // scored: the frames' levels and weights are staged beside B.grouped and packed beside `out`
+  const ScoresIO frames_io{sc.levels, sc.const_level, sc.weights, B.grouped_levels.p, B.grouped_weights.p};
+  const ScoresIO compact_io{B.grouped_levels.p, 0, B.grouped_weights.p, sc.out_levels, sc.out_weights};
+  if (nf > 0 && sc)
+    hipLaunchKernelGGL(k_group_frames_scored, dim3(nf), dim3(GROUP_THREADS), 0, st, g, rects, offsets, group_threshold, eps, B.ws.p,
+                       B.grouped.p, B.out_count.p, frames_io);
+  else if (nf > 0)
     hipLaunchKernelGGL(k_group_frames, dim3(nf), dim3(GROUP_THREADS), 0, st, g, rects, offsets, group_threshold, eps, B.ws.p, B.grouped.p,
                        B.out_count.p);
   hipLaunchKernelGGL(k_group_offsets, dim3(1), dim3(ORDER_THREADS), 0, st, g, B.out_count.p, nf, out_offsets, total);
-  if (nf > 0)
-    hipLaunchKernelGGL(k_group_compact, dim3(nf), dim3(ORDER_THREADS), 0, st, g, B.grouped.p, offsets, out_offsets, out, cap);
+  if (nf > 0 && sc)
+    hipLaunchKernelGGL(k_group_compact<true>, dim3(nf), dim3(ORDER_THREADS), 0, st, g, B.grouped.p, offsets, out_offsets, out, cap, compact_io);
+  else if (nf > 0)
+    hipLaunchKernelGGL(k_group_compact<false>, dim3(nf), dim3(ORDER_THREADS), 0, st, g, B.grouped.p, offsets, out_offsets, out, cap, ScoresIO{});
 }
 
 }  // namespace ccamd
 
 using namespace ccamd;
 
-extern "C" cc_status cc_group_rectangles_device(int device, const cc_rect* rects, const int32_t* offsets, int n_frames,
-                                                int group_threshold, double eps, cc_rect* out, int cap, int32_t* out_offsets,
-                                                int* n_total) {
+// Both entry points below; sc empty: the unscored call.
+static cc_status group_rectangles_device(int device, const cc_rect* rects, const int32_t* offsets, int n_frames, int group_threshold,
+                                         double eps, cc_rect* out, int cap, int32_t* out_offsets, int* n_total, const GroupScores& sc) {
   if (!offsets || !out_offsets || !n_total || n_frames < 0 || cap < 0 || (cap > 0 && !out))
     return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: bad argument");
   cc_status st = ensure_device(device);
@@ -356,16 +473,33 @@ extern "C" cc_status cc_group_rectangles_device(int device, const cc_rect* rects
     if (h_off[(size_t)f + 1] < h_off[(size_t)f]) return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: offsets decrease at frame %d", f);
   const size_t n_rects = (size_t)h_off[(size_t)n_frames];
   if (n_rects > 0 && !rects) return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: null rectangles");
+  if (n_rects > 0 && sc && (!sc.levels || !sc.weights))
+    return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: null levels or weights");
   GroupBufs B;
   DevBuf<int> total;
-  CC_HIP(B.ensure(n_rects, (size_t)n_frames, false));
+  CC_HIP(B.ensure(n_rects, (size_t)n_frames, false, (bool)sc));
   CC_HIP(total.ensure(1));
   CC_HIP(hipMemsetAsync(total.p, 0, sizeof(int), s.s));
-  launch_group_frames(s.s, GroupGuard{}, rects, offsets, n_frames, group_threshold, eps, B, out, cap, out_offsets, total.p);
+  launch_group_frames(s.s, GroupGuard{}, rects, offsets, n_frames, group_threshold, eps, B, out, cap, out_offsets, total.p, sc);
   CC_HIP(hipGetLastError());
   int h_total = 0;
   CC_HIP(copy_sync(&h_total, total.p, sizeof(int), hipMemcpyDeviceToHost, s.s));
   *n_total = h_total;
   if (h_total > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_group_rectangles_device: %d rectangles, capacity %d", h_total, cap);
   return CC_OK;
+}
+
+extern "C" cc_status cc_group_rectangles_device(int device, const cc_rect* rects, const int32_t* offsets, int n_frames,
+                                                int group_threshold, double eps, cc_rect* out, int cap, int32_t* out_offsets,
+                                                int* n_total) {
+  return group_rectangles_device(device, rects, offsets, n_frames, group_threshold, eps, out, cap, out_offsets, n_total, GroupScores{});
+}
+
+extern "C" cc_status cc_group_rectangles_device_levels(int device, const cc_rect* rects, const int32_t* levels, const double* weights,
+                                                       const int32_t* offsets, int n_frames, int group_threshold, double eps,
+                                                       cc_rect* out, int32_t* out_levels, double* out_weights, int cap,
+                                                       int32_t* out_offsets, int* n_total) {
+  if (cap > 0 && (!out_levels || !out_weights)) return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_device: bad argument");
+  return group_rectangles_device(device, rects, offsets, n_frames, group_threshold, eps, out, cap, out_offsets, n_total,
+                                 GroupScores{true, levels, 0, weights, out_levels, out_weights});
 }

@@ -482,4 +482,22 @@ cc_status cc_group_rectangles(const cc_rect* rects, int n, int group_threshold, 
   return CC_OK;
 }
 
+cc_status cc_group_rectangles_levels(const cc_rect* rects, const int32_t* levels, const double* weights, int n, int group_threshold,
+                                     double eps, cc_rect* out, int32_t* out_levels, double* out_weights, int cap, int* n_out) {
+  if ((n > 0 && (!rects || !levels || !weights)) || !n_out || n < 0)
+    return set_error(CC_ERR_INVALID_ARG, "cc_group_rectangles_levels: bad argument");
+  std::vector<cc_rect> v(rects, rects + n);
+  std::vector<int> l(levels, levels + n);
+  std::vector<double> w(weights, weights + n);
+  group_rectangles(v, group_threshold, eps, &l, &w);
+  *n_out = (int)v.size();
+  for (int i = 0; i < (int)v.size() && i < cap && out && out_levels && out_weights; i++) {
+    out[i] = v[(size_t)i];
+    out_levels[i] = l[(size_t)i];
+    out_weights[i] = w[(size_t)i];
+  }
+  if ((int)v.size() > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_group_rectangles_levels: %zu rects, capacity %d", v.size(), cap);
+  return CC_OK;
+}
+
 }  // extern "C"

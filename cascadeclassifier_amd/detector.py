@@ -52,12 +52,31 @@ def scale_plan(win_w, win_h, width, height, scale_factor=1.1, min_size=None, max
     return np.frombuffer(bytes(buf), dt, n.value).copy()
 
 
-def group_rectangles(rects, group_threshold, eps=0.2) -> np.ndarray:
+def _all_or_none(what, *args):
+    """True when every one of `args` is given, False when none is; anything in between is a ValueError."""
+    given = [a is not None for a in args]
+    if any(given) and not all(given):
+        raise ValueError(f"{what} go together: give all of them or none")
+    return all(given)
+
+
+def group_rectangles(rects, group_threshold, eps=0.2, levels=None, weights=None):
+    """cv::groupRectangles on the host. With levels (n,) int32 and weights (n,) float64 -- both or neither -- the
+    rejectLevels / levelWeights form (cc_group_rectangles_levels), which returns (rects, levels, weights)."""
     rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
     out = np.zeros((max(len(rects), 1), 4), np.int32)
     n = C.c_int(0)
-    L.check(L.lib().cc_group_rectangles(_vp(rects), len(rects), int(group_threshold), float(eps), _vp(out), len(out), C.byref(n)))
-    return out[:n.value].copy()
+    if not _all_or_none("levels and weights", levels, weights):
+        L.check(L.lib().cc_group_rectangles(_vp(rects), len(rects), int(group_threshold), float(eps), _vp(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+    levels = np.ascontiguousarray(levels, np.int32).reshape(-1)
+    weights = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    if len(levels) != len(rects) or len(weights) != len(rects):
+        raise ValueError("levels and weights need one entry per rectangle")
+    out_l, out_w = np.zeros(len(out), np.int32), np.zeros(len(out), np.float64)
+    L.check(L.lib().cc_group_rectangles_levels(_vp(rects), _vp(levels), _vp(weights), len(rects), int(group_threshold), float(eps),
+                                               _vp(out), _vp(out_l), _vp(out_w), len(out), C.byref(n)))
+    return out[:n.value].copy(), out_l[:n.value].copy(), out_w[:n.value].copy()
 
 
 def _raise_with_count(status, needed):
@@ -69,13 +88,23 @@ def _raise_with_count(status, needed):
 
 
 def group_rectangles_device(rects_ptr, offsets_ptr, n_frames, group_threshold, out_ptr, cap, out_offsets_ptr, eps=0.2,
-                            device=0) -> int:
+                            device=0, levels_ptr=None, weights_ptr=None, out_levels_ptr=None, out_weights_ptr=None) -> int:
     """cv::groupRectangles on every frame of a batch, in device memory (cc_group_rectangles_device). All pointers are plain
     integers (e.g. tensor.data_ptr()) into memory of `device`: rects int32 (n, 4), offsets int32 (n_frames + 1), out int32
     (cap, 4), out_offsets int32 (n_frames + 1). Returns the number of rectangles over all frames; raises CascadeError with
     CC_ERR_BUFFER_TOO_SMALL (.needed = that number) when it exceeds cap -- out_offsets are complete then, out holds the
-    first cap."""
+    first cap. levels_ptr -> int32 (n), weights_ptr -> float64 (n), out_levels_ptr -> int32 (cap), out_weights_ptr -> float64
+    (cap), all four or none: the grouping with levels and weights (cc_group_rectangles_device_levels)."""
     n = C.c_int(0)
+    if _all_or_none("levels_ptr, weights_ptr, out_levels_ptr and out_weights_ptr", levels_ptr, weights_ptr, out_levels_ptr, out_weights_ptr):
+        st = L.lib().cc_group_rectangles_device_levels(int(device), C.c_void_p(rects_ptr or 0), C.c_void_p(levels_ptr or 0),
+                                                       C.c_void_p(weights_ptr or 0), C.c_void_p(offsets_ptr or 0), int(n_frames),
+                                                       int(group_threshold), float(eps), C.c_void_p(out_ptr or 0),
+                                                       C.c_void_p(out_levels_ptr or 0), C.c_void_p(out_weights_ptr or 0), int(cap),
+                                                       C.c_void_p(out_offsets_ptr or 0), C.byref(n))
+        if st != L.CC_OK:
+            _raise_with_count(st, n.value)
+        return n.value
     st = L.lib().cc_group_rectangles_device(int(device), C.c_void_p(rects_ptr or 0), C.c_void_p(offsets_ptr or 0), int(n_frames),
                                             int(group_threshold), float(eps), C.c_void_p(out_ptr or 0), int(cap),
                                             C.c_void_p(out_offsets_ptr or 0), C.byref(n))
@@ -295,21 +324,52 @@ class CascadeClassifier:
             L.check(st)
             return [out[offs[i]:offs[i + 1]].copy() for i in range(n)]
 
+    def detect_batch3(self, frames, scaleFactor=1.1, minNeighbors=3, minSize=None, maxSize=None, device_ptr=None,
+                      shape=None, row_stride=None, frame_stride=None, pixel_format=None):
+        """detect_batch with scores, as detectMultiScale3 is detectMultiScale with scores (cc_detect_batch_levels_fmt): a list
+        of (rects (k_i, 4) int32, rejectLevels (k_i,) int32, levelWeights (k_i,) float64), one per frame. Frames as
+        detect_batch takes them."""
+        p = _params(scaleFactor, minNeighbors, minSize, maxSize)
+        frames, ptr, on_dev, n, h, w, fmt, rs, fs = self._batch_frames(frames, device_ptr, shape, row_stride, frame_stride,
+                                                                         pixel_format)
+        cap = max(256 * n, 1024)
+        while True:
+            out = np.zeros((cap, 4), np.int32)
+            levels = np.zeros(cap, np.int32)
+            weights = np.zeros(cap, np.float64)
+            offs = np.zeros(n + 1, np.int32)
+            st = L.lib().cc_detect_batch_levels_fmt(self._detector(), ptr, on_dev, n, w, h, rs, fs, fmt, C.byref(p), _vp(out),
+                                                    _vp(levels), _vp(weights), cap, _vp(offs))
+            if st == L.CC_ERR_BUFFER_TOO_SMALL:
+                cap = int(offs[n])
+                continue
+            L.check(st)
+            return [(out[offs[i]:offs[i + 1]].copy(), levels[offs[i]:offs[i + 1]].copy(), weights[offs[i]:offs[i + 1]].copy())
+                    for i in range(n)]
+
     def detect_batch_to_device(self, frames, scaleFactor=1.1, minNeighbors=3, minSize=None, maxSize=None, *, out_ptr, cap,
                                offsets_ptr, device_ptr=None, shape=None, row_stride=None, frame_stride=None,
-                               pixel_format=None) -> int:
+                               pixel_format=None, levels_ptr=None, weights_ptr=None) -> int:
         """detect_batch whose result stays on the device (cc_detect_batch_to_device): out_ptr -> int32 (cap, 4) and
         offsets_ptr -> int32 (n + 1) in memory of the detector's device, as plain integers (tensor.data_ptr()); frame i's
         rectangles are out[offsets[i]:offsets[i + 1]], the same and in the same order as detect_batch returns. Frames as
         detect_batch takes them. Returns the number of rectangles over all frames; raises CascadeError with
         CC_ERR_BUFFER_TOO_SMALL (.needed = that number) when it exceeds cap -- the offsets are complete then, out holds
-        the first cap."""
+        the first cap. levels_ptr -> int32 (cap) and weights_ptr -> float64 (cap), both or neither: the scores of
+        detect_batch3 beside the rectangles (cc_detect_batch_to_device_levels)."""
+        scored = _all_or_none("levels_ptr and weights_ptr", levels_ptr, weights_ptr)
         p = _params(scaleFactor, minNeighbors, minSize, maxSize)
         keep, ptr, on_dev, n, h, w, fmt, rs, fs = self._batch_frames(frames, device_ptr, shape, row_stride, frame_stride,
                                                                        pixel_format)
         total = C.c_int(0)
-        st = L.lib().cc_detect_batch_to_device(self._detector(), ptr, on_dev, n, w, h, rs, fs, fmt, C.byref(p),
-                                               C.c_void_p(out_ptr or 0), int(cap), C.c_void_p(offsets_ptr or 0), C.byref(total))
+        if scored:
+            st = L.lib().cc_detect_batch_to_device_levels(self._detector(), ptr, on_dev, n, w, h, rs, fs, fmt, C.byref(p),
+                                                          C.c_void_p(out_ptr or 0), C.c_void_p(levels_ptr or 0),
+                                                          C.c_void_p(weights_ptr or 0), int(cap), C.c_void_p(offsets_ptr or 0),
+                                                          C.byref(total))
+        else:
+            st = L.lib().cc_detect_batch_to_device(self._detector(), ptr, on_dev, n, w, h, rs, fs, fmt, C.byref(p),
+                                                   C.c_void_p(out_ptr or 0), int(cap), C.c_void_p(offsets_ptr or 0), C.byref(total))
         del keep  # host frames were staged inside the call
         if st != L.CC_OK:
             _raise_with_count(st, total.value)

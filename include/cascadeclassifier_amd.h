@@ -221,8 +221,8 @@ CC_API cc_status cc_detect_batch_submit_fmt(cc_detector* d, const uint8_t* frame
  * over all frames; if it exceeds cap: CC_ERR_BUFFER_TOO_SMALL, offsets still complete, out holds the first cap. A batch
  * submitted earlier and still unfetched is retired first. Work of the caller that still touches out / offsets on another
  * stream must have finished before the call (the detector writes them on its own stream, or the one set with
- * cc_detector_set_stream). There is no submit / collect pair, no outputRejectLevels variant and
- * no single-image hipGraph for this entry point: one frame runs as an ordinary pass. */
+ * cc_detector_set_stream). The outputRejectLevels variant is cc_detect_batch_to_device_levels below. Out of scope for both:
+ * a submit / collect pair and a single-image hipGraph (one frame runs as an ordinary pass). */
 CC_API cc_status cc_detect_batch_to_device(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width,
                                            int height, size_t row_stride, size_t frame_stride, int pixel_format,
                                            const cc_detect_params* p, cc_rect* d_out, int cap, int32_t* d_offsets,
@@ -241,6 +241,28 @@ CC_API cc_status cc_detect_multiscale_levels_fmt(cc_detector* d, const uint8_t* 
                                                  size_t row_stride, int pixel_format, const cc_detect_params* p,
                                                  cc_rect* out, int32_t* reject_levels, double* level_weights, int cap,
                                                  int* n);
+
+/* cc_detect_batch_fmt with the scores of cc_detect_multiscale_levels_fmt: the same passes, each grouped on the host with
+ * levels and weights. reject_levels / level_weights hold cap entries like out; frame f's entries are [offsets[f],
+ * offsets[f+1]) of all three arrays, and they are what cc_detect_multiscale_levels_fmt returns for that frame. On
+ * CC_ERR_BUFFER_TOO_SMALL the offsets are complete and the three arrays hold their first cap entries. There is no scored
+ * submit / collect pair. No reference counterpart (one image per call, tools/detection/Cpp/main.cpp:42-45). */
+CC_API cc_status cc_detect_batch_levels_fmt(cc_detector* d, const uint8_t* frames, int on_device, int n_frames, int width,
+                                            int height, size_t row_stride, size_t frame_stride, int pixel_format,
+                                            const cc_detect_params* p, cc_rect* out, int32_t* reject_levels,
+                                            double* level_weights, int cap, int32_t* offsets);
+
+/* cc_detect_batch_to_device with scores: d_levels / d_weights are DEVICE memory of cap entries beside d_out (both required).
+ * Same rectangles and offsets as cc_detect_batch_to_device; level = number of stages; weight = the largest last-stage sum
+ * among the group's members (cc_group_rectangles_device_levels is this grouping on its own), or with min_neighbors <= 0
+ * each candidate's own sum, in (scale, gy, gx) order: what cc_detect_batch_levels_fmt returns. Passes append at the running
+ * total, and a pass redone after its candidate list overflowed carries its scores. A detector allocates the scored
+ * workspace with its first scored call. Out of scope as for the unscored call: submit / collect, a single-image hipGraph. */
+CC_API cc_status cc_detect_batch_to_device_levels(cc_detector* d, const uint8_t* frames, int on_device, int n_frames,
+                                                  int width, int height, size_t row_stride, size_t frame_stride,
+                                                  int pixel_format, const cc_detect_params* p, cc_rect* d_out,
+                                                  int32_t* d_levels, double* d_weights, int cap, int32_t* d_offsets,
+                                                  int* n_total);
 
 /* Ungrouped candidates of one frame, as int32[7] = {scale_idx, gx, gy, x, y, w, h}, sorted (scale, gy, gx). */
 CC_API cc_status cc_detect_raw(cc_detector* d, const uint8_t* gray, int width, int height, size_t row_stride,
@@ -358,6 +380,24 @@ CC_API cc_status cc_group_rectangles(const cc_rect* rects, int n, int group_thre
 CC_API cc_status cc_group_rectangles_device(int device, const cc_rect* rects, const int32_t* offsets, int n_frames,
                                             int group_threshold, double eps, cc_rect* out, int cap, int32_t* out_offsets,
                                             int* n_total);
+/* Host-side cv::groupRectangles(rects, rejectLevels, levelWeights, group_threshold, eps), the grouping of detectMultiScale's
+ * outputRejectLevels overload (OpenCV 4.6.0 objdetect, no call site in the reference: SURVEY.md 8f-4): a kept class has
+ * level max(0, highest member level) and the largest weight among its members at that level, counted from DBL_MIN when no
+ * member's level exceeded 0. levels / weights: n entries; out / out_levels / out_weights: cap entries. group_threshold <= 0
+ * copies all three through. */
+CC_API cc_status cc_group_rectangles_levels(const cc_rect* rects, const int32_t* levels, const double* weights, int n,
+                                            int group_threshold, double eps, cc_rect* out, int32_t* out_levels,
+                                            double* out_weights, int cap, int* n_out);
+/* The device twin of cc_group_rectangles_levels, as cc_group_rectangles_device is of cc_group_rectangles: levels / weights lie
+ * beside rects, out_levels / out_weights beside out, all in DEVICE memory. Same result, same order as
+ * cc_group_rectangles_levels on each frame; on CC_ERR_BUFFER_TOO_SMALL out_offsets are complete and all three outputs hold
+ * their first cap entries. Argument checks as for the unscored call. Weights are compared by value: where the best
+ * weights of a class are +0.0 and -0.0, either may come out (the host keeps the first it meets, the device +0.0). NaN
+ * weights are outside the contract. */
+CC_API cc_status cc_group_rectangles_device_levels(int device, const cc_rect* rects, const int32_t* levels,
+                                                   const double* weights, const int32_t* offsets, int n_frames,
+                                                   int group_threshold, double eps, cc_rect* out, int32_t* out_levels,
+                                                   double* out_weights, int cap, int32_t* out_offsets, int* n_total);
 
 /* ============================================================================================
  * 4. Training-side feature evaluator.

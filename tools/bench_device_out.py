@@ -6,8 +6,11 @@ stock-profile Haar cascade, scaleFactor 1.1, minNeighbors 3, 7 stages specialise
   host_pipelined    detect_batch_submit / _collect, step i + 1 submitted before step i is collected (bench.py's headline form)
   host_sync         one detect_batch per step
   device_out        one detect_batch_to_device per step (the entry point has no submit / collect pair)
+  device_out_scores the same with levels_ptr / weights_ptr: the scored ordering and grouping kernels. Its time against
+                    device_out's in the same run is what the scores cost.
 The legs alternate round by round in one process; a round times `--chunk` steps of one leg and the median over rounds is
-reported. The rectangles of the legs must be identical. Prints one JSON line (--out also writes it to a file)."""
+reported. The rectangles of the legs must be identical, and the scored leg's levels the number of stages. Prints one JSON
+line (--out also writes it to a file)."""
 import argparse
 import json
 import os
@@ -50,6 +53,9 @@ def main():
     cap = 256 * B
     d_out = torch.zeros((cap, 4), dtype=torch.int32, device="cuda")
     d_off = torch.zeros(B + 1, dtype=torch.int32, device="cuda")
+    s_out, s_off = torch.zeros_like(d_out), torch.zeros_like(d_off)  # the scored leg's own outputs
+    s_lv = torch.zeros(cap, dtype=torch.int32, device="cuda")
+    s_wt = torch.zeros(cap, dtype=torch.float64, device="cuda")
     src = dict(device_ptr=frames.data_ptr(), shape=(B, H, W))
     torch.cuda.synchronize()  # the buffers are filled on torch's stream, the detector writes them on its own
 
@@ -72,7 +78,13 @@ def main():
             clf.detect_batch_to_device(None, sf, mn, out_ptr=d_out.data_ptr(), cap=cap, offsets_ptr=d_off.data_ptr(), **src)
         return None  # read back after the timing, below
 
-    legs = {"host_pipelined": host_pipelined, "host_sync": host_sync, "device_out": device_out}
+    def device_out_scores(k):
+        for _ in range(k):
+            clf.detect_batch_to_device(None, sf, mn, out_ptr=s_out.data_ptr(), cap=cap, offsets_ptr=s_off.data_ptr(),
+                                       levels_ptr=s_lv.data_ptr(), weights_ptr=s_wt.data_ptr(), **src)
+        return None
+
+    legs = {"host_pipelined": host_pipelined, "host_sync": host_sync, "device_out": device_out, "device_out_scores": device_out_scores}
     last, per = {}, {}
     for name, fn in legs.items():
         last[name] = fn(2)  # warm-up: plan, workspaces, candidate lists
@@ -86,6 +98,9 @@ def main():
     dev = [rects[off[i]:off[i + 1]] for i in range(B)]
     identical = all(len(r) == B and all(x.shape == y.shape and (x == y).all() for x, y in zip(r, dev))
                     for r in (last["host_pipelined"], last["host_sync"]))
+    n = int(off[B])
+    identical = identical and (s_off.cpu().numpy() == off).all() and (s_out.cpu().numpy()[:n] == rects[:n]).all()
+    identical = identical and (s_lv.cpu().numpy()[:n] == clf.info()["n_stages"]).all() and bool(np.isfinite(s_wt.cpu().numpy()[:n]).all())
     out = {"metric": "ms_per_step", "frames_per_step": B, "width": W, "height": H, "specialized_stages": spec,
            "rounds": args.rounds, "steps_per_round": args.chunk, "rectangles_identical": bool(identical),
            "rectangles_per_step": int(off[B])}
