@@ -355,30 +355,6 @@ cc_status ensure_device(int device) {
   return CC_OK;
 }
 
-bool stage_sums_order_independent(const Cascade& m, double headroom) {
-  for (size_t s = 0; s < m.stage_ntrees.size(); s++) {
-    int emin = INT32_MAX;
-    double mag = 0;
-    for (int i = 0; i < m.stage_ntrees[s]; i++) {
-      const size_t k = (size_t)m.stage_first[s] + i;
-      const float l = m.stump_left[k], r = m.stump_right[k];
-      if (!std::isfinite(l) || !std::isfinite(r)) return false;
-      mag += std::max(std::fabs((double)l), std::fabs((double)r));
-      for (float v : {l, r})
-        if (v != 0.0f) {
-          int e;
-          std::frexp(v, &e);
-          emin = std::min(emin, e);
-        }
-    }
-    if (emin == INT32_MAX) continue;
-    // v = f * 2^e with f in [0.5, 1) and a 24-bit significand: v is a multiple of 2^(e-24); subnormals only get coarser
-    const double q = std::ldexp(1.0, emin - 24);
-    if (mag * headroom / q >= 9007199254740992.0) return false;
-  }
-  return true;
-}
-
 // Wave phase: lane l of step k evaluates stump (64 k + l) of the stage, so the 32 lanes of a half-wavefront read 32
 // unrelated LDS words per corner slot (~3.8-way bank conflicts in file order). The stage sums are order-independent
 // when this phase is used, so the stumps of a stage may be dealt to the lanes in any order, and the two '+' and the

@@ -113,10 +113,14 @@ cc_status refuse_hog(const Cascade& m, const char* who);
 cc_status ensure_device(int device);
 
 // True when, for every stage, any partial sum of leaf values is exactly representable in double: all leaves are
-// integer multiples of q = 2^(emin-23) (emin = smallest exponent among the stage's nonzero leaves) and the sum of the
+// integer multiples of q = 2^(emin-24) (emin = smallest frexp exponent among the stage's nonzero leaves) and the sum of the
 // larger leaf magnitudes divided by q stays below 2^53. Then the double accumulation never rounds, so its result
 // does not depend on the order of the additions.
 bool stage_sums_order_independent(const Cascade& m, double headroom = 1.0);
+// Stage s alone, for int32 vote sums: true when its leaves are all multiples of q = 2^(emin-24) and the sum of the larger
+// leaf magnitudes divided by q stays below 2^31 - 1; q is set then. False for a stage without a nonzero leaf. The caller
+// has established finite leaves (stage_sums_order_independent). Both are defined in cc_host.cpp.
+bool stage_quantum(const Cascade& m, int s, double& q);
 
 // ---- stump tables of the cascade kernels (detector and specialiser) ----
 // `at(y, x)` maps a corner inside the window to what the record stores: an LDS offset of one of the tile layouts, or

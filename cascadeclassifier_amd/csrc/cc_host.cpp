@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <numeric>
 
@@ -175,6 +176,54 @@ void stage_groups(const std::vector<int32_t>& stage_ntrees, int from, int budget
   if (dense_stage >= 1)
     for (int g = (int)gf.size() - 2; g >= 1; g--)
       if (gf[(size_t)g] >= dense_stage) dense_from = g;
+}
+
+// Range proofs over a cascade's leaf values that decide, at load time, which arithmetic a kernel may use for the stage
+// sums (declared in cc_detect_internal.h; tests/cpp/test_detect_host.cpp sits on their bounds).
+bool stage_sums_order_independent(const Cascade& m, double headroom) {
+  for (size_t s = 0; s < m.stage_ntrees.size(); s++) {
+    int emin = INT32_MAX;
+    double mag = 0;
+    for (int i = 0; i < m.stage_ntrees[s]; i++) {
+      const size_t k = (size_t)m.stage_first[s] + i;
+      const float l = m.stump_left[k], r = m.stump_right[k];
+      if (!std::isfinite(l) || !std::isfinite(r)) return false;
+      mag += std::max(std::fabs((double)l), std::fabs((double)r));
+      for (float v : {l, r})
+        if (v != 0.0f) {
+          int e;
+          std::frexp(v, &e);
+          emin = std::min(emin, e);
+        }
+    }
+    if (emin == INT32_MAX) continue;
+    // v = f * 2^e with f in [0.5, 1) and a 24-bit significand: v is a multiple of 2^(e-24); subnormals only get coarser
+    const double q = std::ldexp(1.0, emin - 24);
+    if (mag * headroom / q >= 9007199254740992.0) return false;
+  }
+  return true;
+}
+
+// Fixed-point votes of a generated stage (cc_spec.hip): true when the stage's leaves are all multiples of q = 2^k and the
+// sum of their larger magnitudes stays below (2^31 - 1) q, so that the stage sum of ANY subset of votes is an int32
+// multiple of q. A stage without a nonzero leaf has no quantum.
+bool stage_quantum(const Cascade& m, int s, double& q) {
+  int emin = INT32_MAX;
+  double mag = 0;
+  for (int i = 0; i < m.stage_ntrees[(size_t)s]; i++) {
+    const size_t k = (size_t)m.stage_first[(size_t)s] + i;
+    const float l = m.stump_left[k], r = m.stump_right[k];
+    mag += std::max(std::fabs((double)l), std::fabs((double)r));
+    for (float v : {l, r})
+      if (v != 0.0f) {
+        int e;
+        std::frexp(v, &e);
+        emin = std::min(emin, e);
+      }
+  }
+  if (emin == INT32_MAX) return false;
+  q = std::ldexp(1.0, emin - 24);  // every leaf is a multiple of q (see stage_sums_order_independent)
+  return mag / q < 2147483647.0;
 }
 
 // cv::groupRectangles. Classes are the connected components of the SimilarRects graph, labelled in

@@ -182,24 +182,6 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
   // 32-bit integers (one select + one add per stump instead of two selects and a double add; intermediate wrap-around
   // is harmless modulo 2^32) and converted once, exactly, at the end: (double)(int)acc * q is the same real number the
   // double accumulation produces, so every comparison and reported sum is bit-identical.
-  auto stage_quantum = [&](int s, double& q) {
-    int emin = INT32_MAX;
-    double mag = 0;
-    for (int i = 0; i < m.stage_ntrees[(size_t)s]; i++) {
-      const size_t k = (size_t)m.stage_first[(size_t)s] + i;
-      const float l = m.stump_left[k], r = m.stump_right[k];
-      mag += std::max(std::fabs((double)l), std::fabs((double)r));
-      for (float v : {l, r})
-        if (v != 0.0f) {
-          int e;
-          std::frexp(v, &e);
-          emin = std::min(emin, e);
-        }
-    }
-    if (emin == INT32_MAX) return false;
-    q = std::ldexp(1.0, emin - 24);  // every leaf is a multiple of q (see stage_sums_order_independent)
-    return mag / q < 2147483647.0;
-  };
   std::function<std::string(const HaarStumpDev&, const std::string&, double, SpecStump&)> vote_text;
   // `reuse`: words the stump evaluated just before this one holds in variables (tile offset -> name): a corner both stumps
   // read is not loaded again. `vars_out` receives this stump's own map for the next one.
@@ -437,7 +419,7 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
       o += buf;
       std::vector<SpecStump> st;
       double q = 0.;
-      const bool fixed = delta_form && stage_quantum(s, q);
+      const bool fixed = delta_form && stage_quantum(m, s, q);
       if (fixed && share_corners) {
         const int nt = m.stage_ntrees[(size_t)s];
         const std::vector<int> order = sharing_order(s, step);
@@ -477,7 +459,7 @@ static std::string spec_stage_source(const Cascade& m, int n_stages, int tmode) 
     {
       std::vector<SpecStump> st;
       double q = 0.;
-      const bool fixed = delta_form && stage_quantum(0, q);
+      const bool fixed = delta_form && stage_quantum(m, 0, q);
       for (int i = 0; i < m.stage_ntrees[0]; i++) {
         const HaarStumpDev& d = t[step - 1][(size_t)m.stage_first[0] + i];
         SpecStump a = stump(d, m.stage_first[0] + i, i, "a", fixed ? q : 0., h16), b2 = stump(d, m.stage_first[0] + i, i, "b", fixed ? q : 0., h16);

@@ -1,11 +1,22 @@
 // The detector's device-free arithmetic (cc_internal.h, defined in cc_host.cpp): how a batch is cut into passes
-// (pass_sizes) and how a cascade's stages are put into groups (stage_groups). Compiled with g++ against cc_host.cpp and run
-// by tests/test_host_logic.py; no GPU, no HIP.
+// (pass_sizes), how a cascade's stages are put into groups (stage_groups), and the two range proofs over a cascade's leaves
+// that decide which arithmetic a kernel may use for the stage sums (stage_sums_order_independent, stage_quantum), on the
+// leaf sets of tests/cascade_edges.py that sit on their bounds. Compiled with g++ against cc_host.cpp and run by
+// tests/test_host_logic.py; no GPU, no HIP.
+#include <cmath>
 #include <cstdio>
 #include <initializer_list>
+#include <limits>
+#include <utility>
 #include <vector>
 
 #include "cc_internal.h"
+
+namespace ccamd {
+// as in cc_detect_internal.h, which needs the HIP headers
+bool stage_sums_order_independent(const Cascade& m, double headroom);
+bool stage_quantum(const Cascade& m, int s, double& q);
+}  // namespace ccamd
 
 using namespace ccamd;
 
@@ -135,10 +146,108 @@ static void test_stage_groups() {
   CHECK(dense_from == 2, "stock LBP cascade: dense_from %d", dense_from);
 }
 
+// A stump cascade of the given stages, each a list of (left, right) leaves.
+using Leaves = std::vector<std::pair<float, float>>;
+static Cascade cascade_of(const std::vector<Leaves>& stages) {
+  Cascade m;
+  m.max_nodes_per_tree = 1;
+  for (const Leaves& st : stages) {
+    m.stage_first.push_back((int32_t)m.stump_left.size());
+    m.stage_ntrees.push_back((int32_t)st.size());
+    for (const auto& lr : st) {
+      m.stump_left.push_back(lr.first);
+      m.stump_right.push_back(lr.second);
+    }
+  }
+  return m;
+}
+
+static Leaves repeat(int n, float l, float r) { return Leaves((size_t)n, {l, r}); }
+static Leaves operator+(Leaves a, const Leaves& b) {
+  a.insert(a.end(), b.begin(), b.end());
+  return a;
+}
+
+static void test_order_independence_bound() {
+  const float odd = 1.f + std::ldexp(1.f, -23);  // exponent 1: q = 2^-23, so the bound 2^53 q is 2^30 and a quarter of it 2^28
+  const Leaves ordinary = {{0.5f, -0.25f}, {-0.75f, 0.125f}};
+  struct Row {
+    const char* what;
+    Leaves critical;
+    bool with1, with4;
+  };
+  const float x27 = std::ldexp(1.f, 27), x28 = std::ldexp(1.f, 28), x29 = std::ldexp(1.f, 29);
+  const Row rows[] = {
+      {"sum max / q = 2^51 - 2^43 + 2^23 + 1", {{x27 - std::ldexp(1.f, 19), 0.f}, {-1.f, x27 - std::ldexp(1.f, 19)}, {odd, -1.f}}, true, true},
+      {"2^51 exactly", {{x27, -x27}, {x27 - 8.f, 1.f}, {odd, -1.f}, {2.f - std::ldexp(1.f, -23), 0.f}, {5.f, -1.f}}, true, false},
+      {"2^51 - 1", {{x27, -x27}, {x27 - 8.f, 1.f}, {odd, -1.f}, {2.f - std::ldexp(1.f, -22), 0.f}, {5.f, -1.f}}, true, true},
+      {"2^52 + ...", {{x28, -x28}, {-x28, x28}, {odd, -odd}}, true, false},
+      {"2^53 - 1", {{x29, x29}, {-(x29 - 32.f), 0.f}, {odd, -1.f}, {2.f - std::ldexp(1.f, -22), 0.f}, {29.f, -1.f}}, true, false},
+      {"2^53 exactly", {{x29, x29}, {-(x29 - 32.f), 0.f}, {odd, -1.f}, {2.f - std::ldexp(1.f, -23), 0.f}, {29.f, -1.f}}, false, false},
+      {"witness at the bound: 2^54 + ...", {{-x29, x29}, {1.5f, -1.5f}, {-odd, odd}, {-2.f * x29, 2.f * x29}, {x29, -x29}, {2.f * x29, 0.f}}, false, false},
+      {"2^40 beside multiples of 2^-15", {{std::ldexp(1.f, 40), 0.f}, {40 * std::ldexp(1.f, -15), 22 * std::ldexp(1.f, -15)}}, false, false},
+      {"a subnormal leaf: q = 2^-149, 1.0 is 2^149 q", {{std::ldexp(1.f, -149), 1.f}}, false, false},
+      {"subnormal leaves alone", {{std::ldexp(1.f, -149), -std::ldexp(1.f, -140)}, {std::ldexp(3.f, -149), 0.f}}, true, true},
+      {"a zero leaf does not lower q", {{0.f, x27 - 8.f}, {x27 - 8.f, -0.f}, {odd, 0.f}}, true, true},
+      {"an all-zero stage", {{0.f, -0.f}, {0.f, 0.f}}, true, true},
+      {"an empty stage", {}, true, true},
+      {"+inf", {{std::numeric_limits<float>::infinity(), 1.f}}, false, false},
+      {"-inf", {{1.f, -std::numeric_limits<float>::infinity()}}, false, false},
+      {"NaN", {{std::numeric_limits<float>::quiet_NaN(), 1.f}}, false, false},
+      {"largest floats: FLT_MAX / 2^104 < 2^24", {{std::numeric_limits<float>::max(), -std::numeric_limits<float>::max()}}, true, true},
+  };
+  for (const Row& r : rows)
+    for (int where = 0; where < 3; where++) {  // the critical stage first, in the middle, last
+      std::vector<Leaves> st = {ordinary, ordinary};
+      st.insert(st.begin() + where, r.critical);
+      const Cascade m = cascade_of(st);
+      CHECK(stage_sums_order_independent(m, 1.0) == r.with1, "%s (stage %d), headroom 1", r.what, where);
+      CHECK(stage_sums_order_independent(m, 4.0) == r.with4, "%s (stage %d), headroom 4", r.what, where);
+    }
+}
+
+static void test_stage_quantum_bound() {
+  const float below1 = 1.f - std::ldexp(1.f, -24), below2 = 1.f - std::ldexp(1.f, -23);  // exponent 0: q = 2^-24
+  struct Row {
+    const char* what;
+    Leaves stage;
+    bool ok;
+    double q;
+  };
+  const Row rows[] = {
+      {"2^31 - 2", repeat(127, 1.f, -1.f) + Leaves{{below2, -below2}}, true, std::ldexp(1.0, -24)},
+      {"2^31 - 2, the larger leaf on the right", repeat(127, 0.5f, -1.f) + Leaves{{0.f, below2}}, true, std::ldexp(1.0, -24)},
+      {"2^31 - 1", repeat(127, 1.f, -1.f) + Leaves{{below1, -below1}}, false, 0.},
+      {"2^31", repeat(128, -1.f, 1.f) + Leaves{{0.5f, 0.f}, {0.f, -0.5f}}, false, 0.},
+      {"2^31 + 2^24 - 1", repeat(128, 1.f, -1.f) + Leaves{{below1, -below1}}, false, 0.},
+      {"one leaf: 2^24 - 1 quanta", {{below1, 0.f}}, true, std::ldexp(1.0, -24)},
+      {"powers of two: q follows the smallest leaf", {{4.f, -2.f}, {0.f, 0.25f}}, true, std::ldexp(1.0, -25)},
+      {"a subnormal leaf beside 1.0", {{std::ldexp(1.f, -149), 1.f}}, false, 0.},
+      {"subnormal leaves alone", {{std::ldexp(1.f, -149), std::ldexp(5.f, -149)}}, true, std::ldexp(1.0, -172)},
+      {"an all-zero stage has no quantum", {{0.f, -0.f}, {0.f, 0.f}}, false, 0.},
+      {"an empty stage", {}, false, 0.},
+  };
+  for (const Row& r : rows) {
+    const Cascade m = cascade_of({{{0.5f, -0.5f}}, r.stage, {{3.f, 1.f}}});
+    double q = -1.;
+    const bool ok = stage_quantum(m, 1, q);
+    CHECK(ok == r.ok, "%s: got %d", r.what, (int)ok);
+    if (ok && r.ok) {
+      CHECK(q == r.q, "%s: q %a, expected %a", r.what, q, r.q);
+      for (const auto& lr : r.stage)  // every leaf is an integer number of quanta, and they fit int32 together
+        for (float v : {lr.first, lr.second}) CHECK((double)v / q == std::nearbyint((double)v / q), "%s: leaf %a is no multiple of q", r.what, (double)v);
+    }
+    double q0 = -1., q2 = -1.;
+    CHECK(stage_quantum(m, 0, q0) && q0 == std::ldexp(1.0, -24) && stage_quantum(m, 2, q2) && q2 == std::ldexp(1.0, -23), "%s: the neighbours", r.what);
+  }
+}
+
 int main() {
   test_pass_sizes_properties();
   test_pass_sizes_values();
   test_stage_groups();
+  test_order_independence_bound();
+  test_stage_quantum_bound();
   if (g_failures) {
     std::printf("test_detect_host: %d check(s) failed\n", g_failures);
     return 1;

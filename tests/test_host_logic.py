@@ -244,7 +244,9 @@ def test_value_cache_policy_of_the_cpp_adaptor():
 def test_pass_sizes_and_stage_groups(repo_root, tmp_path):
     """The detector's device-free arithmetic, cut out of the pass loop and of cc_detector_create: pass_sizes (every size in
     [1, max_batch], summing to the batch, and the values the pass loop has always produced) and stage_groups (strictly
-    ascending groups within the stump budget, stage 0 alone, dense_from, the stock LBP cascade's literal grouping).
+    ascending groups within the stump budget, stage 0 alone, dense_from, the stock LBP cascade's literal grouping), and the
+    two leaf predicates stage_sums_order_independent and stage_quantum on leaf sets at 2^51, 2^53 and 2^31 - 1 quanta,
+    with subnormal, zero, infinite and NaN leaves.
     tests/cpp/test_detect_host.cpp, compiled with g++ against cc_host.cpp; no GPU."""
     import shutil
     import subprocess
