@@ -13,19 +13,11 @@ import cascadeclassifier_amd as cc
 from cascadeclassifier_amd import detector as det
 from oracle import oracle as orc
 from tests import cascade_factory as cf
+from tests.front_cases import integral_witness as _cumsum_u32
 from tests.test_gpu_negmine import _truncated
 from tests.util import frame_natural, frame_uniform
 
 pytestmark = pytest.mark.gpu
-
-
-def _cumsum_u32(img, square):
-    v = img.astype(np.uint64)
-    if square:
-        v = v * v
-    out = np.zeros((img.shape[0] + 1, img.shape[1] + 1), np.uint64)
-    out[1:, 1:] = v.cumsum(0).cumsum(1)  # < 2^64 for any image here; reduced modulo 2^32 below
-    return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
 
 def _check_integral(img):

@@ -117,3 +117,123 @@ def test_negative_miner_argument_checks(haar_xml):
         m.run(frame_uniform(64, 64, 1), ox=50, oy=0)  # offset leaves no room for the window (nextImg would skip it)
     with pytest.raises(cc.CascadeError):
         m.run(frame_uniform(20, 64, 1))
+
+
+# ---- batches that do not fit one staging piece -------------------------------------------------------------------
+# mine_images stages a batch in pieces of at least 8 MiB and launches every kernel once per piece at the piece's first
+# image: source, pyramid, integrals, band sums, diagonal sums, segment totals and pass flags are all offset by it. The
+# batches above are one piece each; these are two, and the first piece is staged by several threads.
+# The library does not report how it cut a batch, so _pieces is a copy by hand of mine_images' arithmetic (8 MiB per piece,
+# at most 4 staging threads, one per 2 MiB): its assertions guard this copy. Whoever changes those constants in
+# cc_negmine.hip changes them here, and the image counts below with them, or these batches silently become one piece.
+STAGING_PIECE_BYTES = 8 << 20
+
+
+def _pieces(w, h, k):
+    """(images per piece, pieces, staging threads of the first piece) as mine_images derives them."""
+    src_bytes = (w + 3) // 4 * 4 * h
+    per = max(1, STAGING_PIECE_BYTES // src_bytes)
+    n = min(per, k)
+    return per, (k + per - 1) // per, min(4, n, max(1, (n * src_bytes) >> 21))
+
+
+def _check_multi_piece_batch(path, imgs, expect_threads):
+    o = orc.load_cascade_xml(path)
+    c = cc.CascadeClassifier(path)
+    assert not c.empty(), getattr(c, "load_error", "")
+    m = cc.NegativeMiner(c)
+    h, w = imgs[0].shape
+    k = len(imgs)
+    per, n_pieces, threads = _pieces(w, h, k)
+    assert n_pieces >= 2 and threads == expect_threads, (per, n_pieces, threads)
+    wins = m.plan(w, h)["n_windows"]
+    single = [m.run(im, max_keep=wins) for im in imgs]
+    # a stale offset would hand an image the flags of a neighbour, or of the image at the same place of the other piece
+    for a in range(k - 1):
+        assert (single[a][0] != single[a + 1][0]).any(), a
+    for a in range(per, k):
+        assert (single[a][0] != single[a - per][0]).any(), a
+    passed = [int(f.sum()) for f, _, _ in single]
+    first, second = sum(passed[:per]), sum(passed[per:])
+    assert first > 0 and second >= 2
+    keep = first + (second + 1) // 2  # the kept windows start in piece one and end inside piece two
+    flags, pix, idx = m.run_batch(imgs, max_keep=keep)
+    assert flags.shape == (k, wins)
+    for a, (f1, _, _) in enumerate(single):
+        assert (flags[a] == f1).all(), f"image {a}: {(flags[a] != f1).sum()} windows differ"
+    want_idx = np.concatenate([i1 + a * wins for a, (_, _, i1) in enumerate(single)])[:keep]
+    want_pix = np.concatenate([p1 for _, p1, _ in single])[:keep]
+    assert len(idx) == keep and idx[0] < per * wins <= idx[-1]
+    assert (idx == want_idx).all() and (pix == want_pix).all()
+    for a in sorted({0, per - 1, per, k - 1}):
+        want_f, want_p, _ = orc.negmine_image(o, imgs[a], 0, 0, max_keep=wins)
+        assert (flags[a] == want_f).all(), a
+        assert (single[a][1] == want_p).all(), a
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["haar3", "haar_tilted"])
+def test_batch_of_two_pieces_staged_by_four_threads(tmp_path, haar_xml, kind):
+    """9 images of 1024x1024: 1 MiB each, pieces of 8 and 1, the first staged by 4 threads with whole-image copies (the
+    width is a multiple of 4). haar3 runs the wave kernel; the tilted cascade also offsets the diagonal sums and the
+    segment totals."""
+    if kind == "haar3":
+        path = _truncated(haar_xml, 3, str(tmp_path))
+    else:
+        calib = frame_natural(320, 240, 3)
+        wins = np.stack([calib[y:y + 24, x:x + 24] for y in range(0, 200, 9) for x in range(0, 280, 11)])
+        path = os.path.join(str(tmp_path), "tilted.xml")
+        open(path, "w").write(cf.tilted_stump_cascade(wins))
+    assert _pieces(1024, 1024, 9)[:2] == (8, 2)
+    _check_multi_piece_batch(path, [frame_natural(1024, 1024, 500 + a) for a in range(9)], 4)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["lbp4", "haar_trees"])
+def test_batch_of_256_images_in_two_pieces_staged_row_by_row(tmp_path, lbp_xml, kind):
+    """256 images (the most a call takes) of 190x176: the pitch is 192, so rows are copied one by one; 248 images fit a
+    piece, which 3 threads stage, and 8 are left for the second. The tree cascade runs the thread-per-window kernel."""
+    if kind == "lbp4":
+        path = _truncated(lbp_xml, 4, str(tmp_path))
+    else:
+        calib = frame_natural(320, 240, 3)
+        wins = np.stack([calib[y:y + 24, x:x + 24] for y in range(0, 200, 9) for x in range(0, 280, 11)])
+        path = os.path.join(str(tmp_path), "trees.xml")
+        open(path, "w").write(cf.haar_tree_cascade(wins))
+    assert _pieces(190, 176, 256)[:2] == (248, 2)
+    _check_multi_piece_batch(path, [frame_natural(190, 176, 600 + a) for a in range(256)], 3)
+
+
+@pytest.mark.gpu
+def test_batch_refusals_leave_the_miner_usable(tmp_path, haar_xml):
+    """Through the C ABI: more than 256 images and a flag buffer one entry short are refused, the latter still reports the
+    windows per image, and the next valid call returns the bits it returned before."""
+    import ctypes as C
+    from cascadeclassifier_amd import _lib as L
+    m = cc.NegativeMiner(cc.CascadeClassifier(_truncated(haar_xml, 3, str(tmp_path))))
+    w, h, k = 100, 75, 3
+    imgs = [frame_natural(w, h, 700 + a) for a in range(k)]
+    before = m.run_batch(imgs, max_keep=50)
+    wins = before[0].shape[1]
+    assert before[0].sum() > 0
+
+    def call(images, cap):
+        ptrs = (C.c_void_p * len(images))(*[im.ctypes.data for im in images])
+        flags = np.zeros(max(wins * len(images), 1), np.uint8)
+        pix, idx = np.zeros((50, 24, 24), np.uint8), np.zeros(50, np.int64)
+        nw, nk = C.c_int64(-1), C.c_int(0)
+        st = L.lib().cc_negminer_run_batch(m._m, ptrs, len(images), w, h, w, 0, 0, flags.ctypes.data_as(C.c_void_p), cap, C.byref(nw),
+                                           pix.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), 50, C.byref(nk))
+        return st, nw.value
+
+    def same_as_before():
+        again = m.run_batch(imgs, max_keep=50)
+        assert all((a == b).all() for a, b in zip(again, before))
+
+    assert call([imgs[a % k] for a in range(257)], wins * 257)[0] == L.CC_ERR_INVALID_ARG
+    same_as_before()
+    assert call([imgs[a % k] for a in range(256)], wins * 256)[0] == L.CC_OK
+    same_as_before()
+    assert call(imgs, wins * k - 1) == (L.CC_ERR_BUFFER_TOO_SMALL, wins)
+    same_as_before()
+    assert call(imgs, wins * k)[0] == L.CC_OK
