@@ -154,6 +154,7 @@ SIGNATURES = {
     "cc_debug_hog_bins": (_i, [_i, C.POINTER(C.c_int32), _vp, _vp]),
     "cc_eval_predict_cascade": (_i, [_vp, _vp, _vp, _i, _vp]),
     "cc_eval_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
+    "cc_debug_eval_tile_samples": (_i, [_vp]),
     "cc_eval_presort": (_i, [_vp, _i]),
     "cc_eval_presort_range": (_i, [_vp, _i, _i, _i]),
     "cc_eval_find_best_split": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _d, _i, _i, C.POINTER(Split), _vp, _vp]),

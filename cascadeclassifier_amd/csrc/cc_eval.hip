@@ -816,6 +816,10 @@ cc_status cc_eval_create(int feature_type, int haar_mode, int win_w, int win_h, 
     CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eval_batch_wide<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(per_sample * S)));
     CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eval_batch_wide<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(per_sample * S)));
   }
+  // k_set_images keeps the row prefix sums of one sample, H * (W + 1) words, in dynamic LDS: past 64 KB (128x128 LBP asks
+  // for 66 048 bytes) the attribute is raised as for the batch kernels above (a runtime that enforces it refuses the launch)
+  if (const size_t set_lds = (size_t)win_h * (win_w + 1) * 4; set_lds > 64 * 1024)
+    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_set_images), hipFuncAttributeMaxDynamicSharedMemorySize, (int)set_lds));
   CC_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   CC_HIP(hipEventCreate(&e->ev_a));
   CC_HIP(hipEventCreate(&e->ev_b));
@@ -857,6 +861,7 @@ int cc_eval_num_features(const cc_evaluator* e) {
   if (!e) return 0;
   return e->type == CC_FEATURE_HOG ? (int)(e->hog_blocks.size() / 4) : e->nfeat;  // HOG: blocks (HOGfeatures.cpp:105)
 }
+int cc_debug_eval_tile_samples(const cc_evaluator* e) { return e && e->type != CC_FEATURE_HOG ? e->S : 0; }
 int cc_eval_max_cat_count(const cc_evaluator* e) { return e && e->type == CC_FEATURE_LBP ? 256 : 0; }
 int cc_eval_feature_size(const cc_evaluator* e) { return e ? (e->type == CC_FEATURE_HOG ? 36 : 1) : 0; }  // N_BINS * N_CELLS
 const float* cc_eval_labels(const cc_evaluator* e) { return e ? e->cls.data() : nullptr; }

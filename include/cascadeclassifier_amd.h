@@ -505,6 +505,9 @@ CC_API cc_status cc_debug_hog_bins(int device, int32_t* n, uint8_t* bin, float* 
 CC_API cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const int32_t* sample_idx, int n_samples,
                                          uint8_t* out);
 CC_API cc_status cc_eval_last_kernel_ms(cc_evaluator* e, double* ms);
+/* Test instrumentation: samples per LDS tile of the bulk kernel that cc_eval_create picked from the window (64 = the wide
+ * kernel, 32 .. 1 = the narrow one); 0 for a HOG or NULL evaluator. */
+CC_API int cc_debug_eval_tile_samples(const cc_evaluator* e);
 
 /* ============================================================================================
  * 5. Batched negative mining over a background image.
