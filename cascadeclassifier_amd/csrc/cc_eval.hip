@@ -890,6 +890,7 @@ cc_status cc_eval_set_images(cc_evaluator* e, const uint8_t* imgs, int n, int fi
   std::lock_guard<std::mutex> lk(e->mu);
   st = flush_pending_images(e);  // images set earlier, one at a time, must not land on top of these
   if (st != CC_OK) return st;
+  e->generation++;
   if (e->mirror_idx >= first_idx && e->mirror_idx < first_idx + n) e->mirror_idx = -1;
   const size_t bytes = (size_t)n * e->W * e->H;
   CC_HIP(e->d_imgs.ensure(bytes));
@@ -924,6 +925,7 @@ cc_status cc_eval_set_image(cc_evaluator* e, const uint8_t* img, size_t row_stri
   const size_t px = (size_t)e->W * e->H;
   constexpr int kMaxQueued = 4096;
   std::lock_guard<std::mutex> lk(e->mu);
+  e->generation++;
   if ((int)e->pend_idx.size() >= kMaxQueued && (e->pend_slot.empty() || e->pend_slot[(size_t)idx] < 0)) {
     cc_status st = eval_device(e);
     if (st == CC_OK) st = flush_pending_images(e);

@@ -35,8 +35,7 @@ cc_status launch_batch(cc_evaluator* e, bool haar, const void* feats, int fb, in
 // Every entry point that reads stored samples on the device calls it first. Caller holds e->mu.
 cc_status flush_pending_images(cc_evaluator* e);
 
-// HOG (cc_hog.hip). Catalog blocks as (x, y, cell w, cell h); variables are block * 36 + cell * 9 + bin.
-void hog_catalog(int W, int H, std::vector<int32_t>& blocks);
+// HOG (cc_hog.hip). Catalog blocks as (x, y, cell w, cell h) (hog_catalog, cc_internal.h); variables are block * 36 + cell * 9 + bin.
 // Builds the catalog, sets nfeat to the variable count and allocates the planes. Called by cc_eval_create.
 cc_status hog_init(cc_evaluator* e);
 // setImage of n images already on the device (e->stream), samples [first_idx, first_idx + n). Caller holds e->mu.
@@ -50,6 +49,39 @@ cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, i
 // Host mirror: the ten planes of one window ([cols][10], the device layout) and one variable's value on them.
 void hog_host_planes(const cc_evaluator* e, const uint8_t* px, std::vector<float>& planes);
 float hog_host_value(const cc_evaluator* e, const float* planes, int vi);
+
+
+// ---- the split search (cc_split.hip) as the booster (cc_boost.hip) enters it ---------------------
+// per stored sample: weight and (regression) response * weight or (classification) class; w < 0 marks "not in the node"
+struct SplitEntry {
+  double w, t;
+};
+// The per-sample table of a node search: where it lives and how wide its entries are. The values are the kernels' TAB.
+enum TableForm : int { TABLE_GLOBAL16 = 0, TABLE_LDS16 = 1, TABLE_LDS8 = 2 };
+// What a table holds for a stored sample that is not in the node (the values: cc_split.hip).
+struct AbsentEntry {
+  double e8;
+  SplitEntry e16;
+};
+extern const AbsentEntry ABSENT_ORDERED, ABSENT_CATEGORICAL;
+// d_split_out of the ordered search and its pinned copy: best_val [fpad] doubles, then best_i, best_vl and best_vr,
+// [fpad] 4-byte values each.
+struct OrdResult {
+  double* best_val;
+  int* best_i;
+  float *best_vl, *best_vr;
+  OrdResult(void* base, size_t fpad)
+      : best_val(static_cast<double*>(base)), best_i(reinterpret_cast<int*>(best_val + fpad)), best_vl(reinterpret_cast<float*>(best_i + fpad)),
+        best_vr(best_vl + fpad) {}
+  static size_t bytes(size_t fpad) { return fpad * 20; }
+};
+// The form cc_eval_find_best_split picks for class labels or responses of +-1 over N presorted samples.
+TableForm split_table_form_unit(int N);
+// Both search the presorted variables over a node table that is already in e->d_split_tab. Caller holds e->mu.
+// Ordered: mode 0 regression, 1 GINI, 2 MISCLASS; the per-variable results stay in e->d_split_out (OrdResult).
+cc_status split_launch_ordered(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0);
+// Categorical: node = stored samples in increasing order; the winner as cc_eval_find_best_split reports it.
+cc_status split_categorical_from_table(cc_evaluator* e, bool is_classifier, bool gini, TableForm form, cc_split* out);
 
 }  // namespace ccamd
 
@@ -91,6 +123,7 @@ struct cc_evaluator {
   DevBuf<uint8_t> d_codes;  // LBP: [feature][sample] codes
   int cat_sorted_n = 0;          // samples per variable in d_cat_sorted (0: not built)
   DevBuf<uint32_t> d_cat_sorted;  // LBP: (sample << 8 | code) in (code, sample) order, [group][rank][64] (cc_split.hip)
+  uint64_t generation = 0;  // bumped by every presort and setImage(s): what a cc_boost was created against
   int presort_n = 0;      // samples covered by the tables (0 = none)
   int presort_f0 = 0, presort_f1 = 0;  // variables covered by the tables
   DevBuf<double> d_split_tab, d_split_out;

@@ -185,18 +185,7 @@ __global__ void k_hog_bins(uint8_t* __restrict__ bin, float* __restrict__ mag) {
 // ------------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------------
-// HOGfeatures.cpp:67-106: cell size t = 8, 16, ... while t <= W / 2; per t three block shapes (2t x 2t, 2t x 4t, 4t x 2t
-// in pixels; cells t x t, t x 2t, 2t x t), each placed with step 4, x outer and y inner.
-void hog_catalog(int W, int H, std::vector<int32_t>& blocks) {
-  blocks.clear();
-  for (int t = 8; t <= W / 2; t += 8) {
-    const int cell[3][2] = {{t, t}, {t, 2 * t}, {2 * t, t}};
-    for (const auto& c : cell)
-      for (int x = 0; x <= W - 2 * c[0]; x += 4)
-        for (int y = 0; y <= H - 2 * c[1]; y += 4) blocks.insert(blocks.end(), {x, y, c[0], c[1]});
-  }
-}
-
+// hog_catalog: cc_host.cpp, beside the Haar and LBP catalogs (cc_cascade_from_stumps needs it without a device).
 static size_t hog_set_lds(int W, int H, int P) { return (size_t)W * H * 4 + (size_t)P * H * (W + 1) * 4 + (size_t)W * H; }
 
 cc_status hog_init(cc_evaluator* e) {

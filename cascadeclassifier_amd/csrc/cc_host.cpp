@@ -385,6 +385,18 @@ void lbp_catalog(int W, int H, std::vector<int32_t>& rects) {
           }
 }
 
+// HOG catalog (HOGfeatures.cpp:67-106): cell size t = 8, 16, ... while t <= W / 2; per t three block shapes (2t x 2t,
+// 2t x 4t, 4t x 2t in pixels; cells t x t, t x 2t, 2t x t), each placed with step 4, x outer and y inner.
+void hog_catalog(int W, int H, std::vector<int32_t>& blocks) {
+  blocks.clear();
+  for (int t = 8; t <= W / 2; t += 8) {
+    const int cell[3][2] = {{t, t}, {t, 2 * t}, {2 * t, t}};
+    for (const auto& c : cell)
+      for (int x = 0; x <= W - 2 * c[0]; x += 4)
+        for (int y = 0; y <= H - 2 * c[1]; y += 4) blocks.insert(blocks.end(), {x, y, c[0], c[1]});
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Categorical split: category ordering + scan (o_cvboostree.cpp:289-357 classification, :466-515 regression).
 // The accumulation over samples happened on the device; this is the O(n_cat log n_cat) remainder. std::sort with a

@@ -122,6 +122,7 @@ void stage_groups(const std::vector<int32_t>& stage_ntrees, int from, int budget
 // ---- catalogs (training side) -------------------------------------------------------------------
 void haar_catalog(int W, int H, int mode, std::vector<HaarFeature>& out);
 void lbp_catalog(int W, int H, std::vector<int32_t>& rects);
+void hog_catalog(int W, int H, std::vector<int32_t>& blocks);  // (x, y, cell w, cell h) per block
 
 // ---- split search, categorical variables: the part after the per-category accumulation (host) ------
 // hist: n_cat pairs, regression {sum of response*w, sum of w}, classification {w of class 0, w of class 1}, each

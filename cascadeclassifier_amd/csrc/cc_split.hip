@@ -29,11 +29,6 @@
 
 namespace ccamd {
 
-// per stored sample: weight and (regression) response * weight or (classification) class; w < 0 marks "not in the node"
-struct SplitEntry {
-  double w, t;
-};
-
 // ------------------------------------------------------------------------------------------------
 // [rows][n] row-major (one sorted variable per row) -> [group][rank][64]
 // ------------------------------------------------------------------------------------------------
@@ -825,8 +820,6 @@ struct SplitQuery {
   SplitEntry entry16(int i) const { return SplitEntry{weights[i], is_classifier ? (double)class_labels[i] : responses[i] * weights[i]}; }
 };
 
-// The per-sample table of a node search: where it lives and how wide its entries are. The values are the kernels' TAB.
-enum TableForm : int { TABLE_GLOBAL16 = 0, TABLE_LDS16 = 1, TABLE_LDS8 = 2 };
 constexpr size_t SPLIT_LDS_CAP = 160 * 1024;
 // A table in LDS implies 16-bit sample numbers in the sorted tables: no kernel pairs int32_t with an LDS form.
 static_assert(SPLIT_LDS_CAP / 8 <= 65536, "an LDS table holds at most 65 536 samples");
@@ -836,22 +829,24 @@ static size_t table_lds(TableForm form, int N) { return form == TABLE_GLOBAL16 ?
 
 // 8-byte entries need a class or a response of +-1, and whenever 16-byte entries would fit LDS so do 8-byte ones:
 // TABLE_LDS16 is what regression with other responses (LOGIT) gets, and nothing else does.
-static TableForm table_form(const SplitQuery& q) {
+static TableForm table_form(int N, bool unit_entries) {
   if (std::getenv("CCAMD_SPLIT_GLOBAL_TABLE")) return TABLE_GLOBAL16;
+  if (unit_entries && (size_t)N * 8 <= SPLIT_LDS_CAP) return TABLE_LDS8;
+  return (size_t)N * 16 <= SPLIT_LDS_CAP ? TABLE_LDS16 : TABLE_GLOBAL16;
+}
+static TableForm table_form(const SplitQuery& q) {
   bool unit_responses = !q.is_classifier;
   for (int i = 0; i < q.n && unit_responses; i++) unit_responses = q.responses[i] == 1.0f || q.responses[i] == -1.0f;
-  if ((q.is_classifier || unit_responses) && (size_t)q.N * 8 <= SPLIT_LDS_CAP) return TABLE_LDS8;
-  return (size_t)q.N * 16 <= SPLIT_LDS_CAP ? TABLE_LDS16 : TABLE_GLOBAL16;
+  return table_form(q.N, q.is_classifier || unit_responses);
+}
+namespace ccamd {
+TableForm split_table_form_unit(int N) { return table_form(N, true); }
 }
 
 // What a table holds for a stored sample that is not in the node. The ordered kernels test for it: w = -1, or the quiet
 // NaN whose high word k_split_ord_lean compares (0x7ff80000, low word 0). k_split_cat_sorted adds every entry up: +0.0.
-struct AbsentEntry {
-  double e8;
-  SplitEntry e16;
-};
-static const AbsentEntry ABSENT_ORDERED = {std::numeric_limits<double>::quiet_NaN(), {-1.0, 0.0}};
-static const AbsentEntry ABSENT_CATEGORICAL = {0.0, {0.0, 0.0}};
+const AbsentEntry ccamd::ABSENT_ORDERED = {std::numeric_limits<double>::quiet_NaN(), {-1.0, 0.0}};
+const AbsentEntry ccamd::ABSENT_CATEGORICAL = {0.0, {0.0, 0.0}};
 
 // Builds the node's table in pin_in and sends it to d_split_tab. With `absent`: dense, one entry per stored sample and
 // `absent` for those outside the node. Without: the compact list of k_split_cat, the node's entries in node order
@@ -903,18 +898,6 @@ static void (*categorical_sorted_kernel(bool is_classifier, TableForm form))(Spl
   return is_classifier ? k_split_cat_sorted<true, 2> : k_split_cat_sorted<false, 2>;
 }
 
-// d_split_out of the ordered search and its pinned copy: best_val [fpad] doubles, then best_i, best_vl and best_vr,
-// [fpad] 4-byte values each.
-struct OrdResult {
-  double* best_val;
-  int* best_i;
-  float *best_vl, *best_vr;
-  OrdResult(void* base, size_t fpad)
-      : best_val(static_cast<double*>(base)), best_i(reinterpret_cast<int*>(best_val + fpad)), best_vl(reinterpret_cast<float*>(best_i + fpad)),
-        best_vr(best_vl + fpad) {}
-  static size_t bytes(size_t fpad) { return fpad * 20; }
-};
-
 // ev_a .. ev_b for cc_eval_last_kernel_ms; the stream has been synchronised
 static void note_kernel_ms(cc_evaluator* e) {
   float ms = 0;
@@ -945,19 +928,18 @@ static int pick_winner(const SplitQuery& q, Found found, Quality quality, Point 
   return winner;
 }
 
-static cc_status search_ordered(const SplitQuery& q) {
-  cc_evaluator* e = q.e;
-  const int N = q.N;
+// The ordered search of the presorted variables over the node table in d_split_tab (`form`; built by upload_node_table
+// or, on the device, by the booster): the per-variable results stay in d_split_out as OrdResult lays them out, between
+// ev_a and ev_b on the evaluator's stream.
+cc_status ccamd::split_launch_ordered(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0) {
+  const int N = e->presort_n, F = e->presort_f1 - e->presort_f0;
   const bool idx16 = N <= 65536;
-  const int mode = !q.is_classifier ? 0 : (q.gini ? 1 : 2);
-  const TableForm form = table_form(q);
-  if (cc_status st = upload_node_table(q, form, &ABSENT_ORDERED); st != CC_OK) return st;
-  const size_t groups = ((size_t)q.F + 63) / 64, fpad = groups * 64;
+  const size_t groups = ((size_t)F + 63) / 64, fpad = groups * 64;
   CC_HIP(e->d_split_out.ensure(fpad * 3));  // OrdResult::bytes + slack
   const OrdResult dev(e->d_split_out.p, fpad);
   // in the struct's order: sv, si, tab, n_pre, n_vars, w_total0, w_total1, rsum0, best_val, best_i, best_vl, best_vr, n_groups, dbg_nogather
   const SplitOrdArgs A{e->d_sorted_val.p, idx16 ? (const void*)e->d_sorted_idx16.p : (const void*)e->d_sorted_idx32.p,
-                       reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), N, q.F, q.weights[q.n], q.weights[q.n + 1], q.node_value * q.weights[q.n],
+                       reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), N, F, w_total0, w_total1, rsum0,
                        dev.best_val, dev.best_i, dev.best_vl, dev.best_vr, (int)groups, std::getenv("CCAMD_DEBUG_SPLIT_NOGATHER") ? 1 : 0};
   // wavefronts per block: with the table in LDS one block owns a CU, so spread the groups evenly over the CUs
   // (162 336 variables = 2 537 groups -> 254 blocks of 10 wavefronts on 256 CUs); from global memory, one wavefront
@@ -972,6 +954,16 @@ static cc_status search_ordered(const SplitQuery& q) {
   (void)hipEventRecord(e->ev_a, e->stream);
   if (cc_status st = launch(ordered_kernel(mode, form, idx16), blocks, 64u * wpb, table_lds(form, N), e->stream, A); st != CC_OK) return st;
   (void)hipEventRecord(e->ev_b, e->stream);
+  return CC_OK;
+}
+
+static cc_status search_ordered(const SplitQuery& q) {
+  cc_evaluator* e = q.e;
+  const int mode = !q.is_classifier ? 0 : (q.gini ? 1 : 2);
+  const TableForm form = table_form(q);
+  if (cc_status st = upload_node_table(q, form, &ABSENT_ORDERED); st != CC_OK) return st;
+  if (cc_status st = split_launch_ordered(e, mode, form, q.weights[q.n], q.weights[q.n + 1], q.node_value * q.weights[q.n]); st != CC_OK) return st;
+  const size_t fpad = ((size_t)q.F + 63) / 64 * 64;
   CC_HIP(e->pin_out.ensure(fpad * 24));
   CC_HIP(hipMemcpyAsync(e->pin_out.p, e->d_split_out.p, OrdResult::bytes(fpad), hipMemcpyDeviceToHost, e->stream));
   CC_HIP(hipStreamSynchronize(e->stream));
@@ -986,11 +978,9 @@ static cc_status search_ordered(const SplitQuery& q) {
 }
 
 // Per-category sums of a node that lists its samples in increasing order, from the (code, sample)-sorted table.
-static cc_status search_categorical_sorted(const SplitQuery& q, size_t hist_n) {
+static cc_status search_categorical_sorted(const SplitQuery& q, size_t hist_n, TableForm form) {
   cc_evaluator* e = q.e;
   const int N = q.N;
-  const TableForm form = table_form(q);
-  if (cc_status st = upload_node_table(q, form, &ABSENT_CATEGORICAL); st != CC_OK) return st;
   (void)hipEventRecord(e->ev_a, e->stream);
   CC_HIP(hipMemsetAsync(e->d_split_out.p, 0, hist_n * 8, e->stream));  // categories without a sample
   const size_t groups = ((size_t)q.F + 63) / 64;
@@ -1079,6 +1069,7 @@ static cc_status reduce_category_sums(const SplitQuery& q, size_t hist_n, std::v
   return CC_OK;
 }
 
+static cc_status finish_categorical(const SplitQuery& q, size_t hist_n);
 static cc_status search_categorical(const SplitQuery& q) {
   const size_t hist_n = (size_t)q.F * 256 * 2;
   CC_HIP(q.e->d_split_out.ensure(hist_n));
@@ -1086,7 +1077,32 @@ static cc_status search_categorical(const SplitQuery& q) {
   for (int i = 1; i < q.n && ascending && q.sample_idx; i++) ascending = q.sample_idx[i - 1] < q.sample_idx[i];
   const bool stream_only = std::getenv("CCAMD_SPLIT_CAT_STREAM") != nullptr;  // read per call: tests compare the two paths
   const bool sorted = ascending && q.e->cat_sorted_n == q.N && !stream_only;
-  if (cc_status st = sorted ? search_categorical_sorted(q, hist_n) : search_categorical_stream(q); st != CC_OK) return st;
+  if (sorted) {
+    const TableForm form = table_form(q);
+    if (cc_status st = upload_node_table(q, form, &ABSENT_CATEGORICAL); st != CC_OK) return st;
+    if (cc_status st = search_categorical_sorted(q, hist_n, form); st != CC_OK) return st;
+  } else if (cc_status st = search_categorical_stream(q); st != CC_OK)
+    return st;
+  return finish_categorical(q, hist_n);
+}
+
+// The categorical search over the node table the booster built in d_split_tab (`form`, absent samples as
+// ABSENT_CATEGORICAL, node = stored samples in increasing order): the sorted-table kernel, then the host's category
+// ordering exactly as cc_eval_find_best_split does it.
+cc_status ccamd::split_categorical_from_table(cc_evaluator* e, bool is_classifier, bool gini, TableForm form, cc_split* out) {
+  if (e->cat_sorted_n != e->presort_n)
+    return set_error(CC_ERR_UNSUPPORTED, "cc_boost: the categorical search needs the (code, sample)-sorted table of cc_eval_presort");
+  std::memset(out, 0, sizeof(*out));
+  out->quality = -1.f;
+  const int F = e->presort_f1 - e->presort_f0;
+  const SplitQuery q{e, nullptr, e->presort_n, nullptr, nullptr, nullptr, 0.0, is_classifier, gini, e->presort_n, F, e->presort_f0, out, nullptr, nullptr};
+  const size_t hist_n = (size_t)F * 256 * 2;
+  CC_HIP(e->d_split_out.ensure(hist_n));
+  if (cc_status st = search_categorical_sorted(q, hist_n, form); st != CC_OK) return st;
+  return finish_categorical(q, hist_n);
+}
+
+static cc_status finish_categorical(const SplitQuery& q, size_t hist_n) {
   std::vector<CatSplit> res((size_t)q.F);
   if (cc_status st = reduce_category_sums(q, hist_n, res); st != CC_OK) return st;
   const int winner = pick_winner(q, [&](int f) { return res[(size_t)f].found; }, [&](int f) { return res[(size_t)f].quality; },
@@ -1107,6 +1123,7 @@ cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n
   std::lock_guard<std::mutex> lk(e->mu);
   if (cc_status st = flush_pending_images(e); st != CC_OK) return st;
   e->presort_n = 0;  // until the epilogue: a failure below leaves no tables to search
+  e->generation++;   // a booster created over the earlier tables refuses its next round
   const bool haar = e->type != CC_FEATURE_LBP;  // HOG variables are ordered: the Haar tables (launch_batch dispatches HOG)
   const int F = fi_end - fi_begin, N = n_samples;
   const void* feats = haar ? (const void*)e->d_haar.p : (const void*)e->d_lbp.p;

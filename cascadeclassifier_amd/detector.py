@@ -222,6 +222,28 @@ class CascadeClassifier:
             return False
         return True
 
+    @classmethod
+    def from_stumps(cls, feature_type, win, stages, haar_mode=L.CC_HAAR_BASIC, device: int = 0, max_batch: int = 1):
+        """The cascade CvCascadeClassifier::save would write for trained stumps: `stages` is a list of
+        (stage_threshold, [weak dicts]) with the dicts CascadeBoost.train_stage returns (var_idx, ord_c or subset,
+        left_value, right_value; records with trained == False are skipped) and the threshold of the stage's last record.
+        Leaves and thresholds are cast to float here, as the writer does; the used variables are renumbered in catalog
+        order."""
+        weaks = [[w for w in ws if w.get("trained", True)] for _, ws in stages]
+        n_weak = np.array([len(ws) for ws in weaks], np.int32)
+        flat = [w for ws in weaks for w in ws]
+        thr = np.array([np.float32(t) for t, _ in stages], np.float32)
+        var = np.array([w["var_idx"] for w in flat], np.int32)
+        lbp = feature_type == L.CC_FEATURE_LBP
+        ord_c = None if lbp else np.array([np.float32(w["ord_c"]) for w in flat], np.float32)
+        subsets = np.array([np.asarray(w["subset"], np.int64).astype(np.int32) for w in flat], np.int32).reshape(-1) if lbp else None
+        left = np.array([np.float32(w["left_value"]) for w in flat], np.float32)
+        right = np.array([np.float32(w["right_value"]) for w in flat], np.float32)
+        self = cls(None, device, max_batch)
+        L.check(L.lib().cc_cascade_from_stumps(int(feature_type), int(haar_mode), int(win[0]), int(win[1]), len(n_weak), _vp(n_weak),
+                                               len(var), _vp(thr), _vp(var), _vp(ord_c), _vp(subsets), _vp(left), _vp(right), C.byref(self._c)))
+        return self
+
     def empty(self) -> bool:
         return not self._c
 

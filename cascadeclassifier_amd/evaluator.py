@@ -225,6 +225,79 @@ class CvFeatureEvaluator:
             pass
 
 
+def _weak_dict(w: L.Weak) -> dict:
+    return {"trained": bool(w.trained), "stop": w.stop, "n_active": w.n_active, "var_idx": w.var_idx, "split_point": w.split_point,
+            "quality": np.float32(w.quality), "ord_c": np.float32(w.ord_c), "subset": np.array(w.subset[:], np.int32),
+            "left_value": w.left_value, "right_value": w.right_value, "stage_threshold": np.float32(w.stage_threshold),
+            "hit_rate": np.float32(w.hit_rate), "false_alarm": np.float32(w.false_alarm)}
+
+
+class CascadeBoost:
+    """One stage of CvCascadeBoost::train (boost.cpp:409-459) with stumps, on the device: weights, subsample mask, weak
+    responses and stage sums stay there; the split of every round is the evaluator's presorted search. The evaluator
+    must have been presorted over exactly n_samples; presorting or setting images again invalidates the booster."""
+
+    STOP_GO_ON, STOP_FALSE_ALARM, STOP_MAX_WEAK, STOP_NO_ACTIVE, STOP_NOT_TRAINED = 0, 1, 2, 3, 4
+    ROUND_PARTS = ("node_table_root", "split_search", "winner", "apply_split", "leaves", "update_weights", "trim", "stage_status")
+
+    def __init__(self, evaluator: CvFeatureEvaluator, n_samples: int, boost_type=BOOST_GENTLE, split_criteria=SPLIT_DEFAULT,
+                 weight_trim_rate=0.95, min_hit_rate=0.995, max_false_alarm=0.5, max_weak_count=100):
+        self._b = C.c_void_p()
+        self._evaluator = evaluator  # keep the evaluator alive
+        self.n_samples = int(n_samples)
+        self.max_weak_count = int(max_weak_count)
+        p = L.BoostParams(int(boost_type), int(split_criteria), float(weight_trim_rate), float(min_hit_rate), float(max_false_alarm),
+                          int(max_weak_count))
+        L.check(L.lib().cc_boost_create(evaluator._e, self.n_samples, C.byref(p), C.byref(self._b)))
+
+    def round(self) -> dict:
+        """One weak classifier: the record of cc_boost_round as a dict."""
+        w = L.Weak()
+        L.check(L.lib().cc_boost_round(self._b, C.byref(w)))
+        return _weak_dict(w)
+
+    def train_stage(self) -> list:
+        """Rounds until one says stop; the records of all of them (the last one carries the stage threshold)."""
+        cap = self.max_weak_count + 1
+        arr = (L.Weak * cap)()
+        k = C.c_int(0)
+        L.check(L.lib().cc_boost_train_stage(self._b, arr, cap, C.byref(k)))
+        return [_weak_dict(arr[i]) for i in range(k.value)]
+
+    def state(self) -> dict:
+        n = self.n_samples
+        w, we, ss = (np.empty(n, np.float64) for _ in range(3))
+        m = np.empty(n, np.uint8)
+        L.check(L.lib().cc_boost_get_state(self._b, _vp(w), _vp(we), _vp(m), _vp(ss)))
+        return {"weights": w, "weak_eval": we, "mask": m, "stage_sum": ss}
+
+    def last_round_ms(self) -> dict:
+        """Device time of the last round's kernels, by part."""
+        ms = np.zeros(len(self.ROUND_PARTS), np.float64)
+        k = C.c_int(0)
+        L.check(L.lib().cc_boost_last_round_ms(self._b, _vp(ms), len(ms), C.byref(k)))
+        return dict(zip(self.ROUND_PARTS, ms.tolist()))
+
+    def _release(self):
+        if getattr(self, "_b", None):
+            L.lib().cc_boost_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+
+def device_exp(x, device=0) -> np.ndarray:
+    """The device's exp(double) (cc_debug_exp64): what update_weights applies to the weak responses."""
+    a = np.ascontiguousarray(x, np.float64)
+    out = np.empty(a.shape, np.float64)
+    L.check(L.lib().cc_debug_exp64(int(device), _vp(a), a.size, _vp(out)))
+    return out
+
+
 class NegativeMiner:
     """Batched form of the negative branch of CvCascadeClassifier::fillPassedSamples (cascadeclassifier.cpp:329-357):
     one call runs the reader's whole window stream of one background image (imagestorage.cpp:57-126) through the

@@ -599,6 +599,60 @@ CC_API cc_status cc_eval_find_best_split(cc_evaluator* e, const int32_t* sample_
                                          int32_t* per_var_point);
 
 /* ============================================================================================
+ * 6b. Boosting a stage: one stage of stumps (maxDepth 1, the trainer's default) trained on the device.
+ *    Replaces the loop of CvCascadeBoost::train (traincascade/lib/src/boost.cpp:409-459) with
+ *    CvCascadeBoost::update_weights (:160-407) and isErrDesired (:479-518), CvBoost::trim_weights (o_cvboost.cpp:101-139),
+ *    CvBoostTree::calc_node_value (o_cvboostree.cpp:657-732), calc_node_dir (:87-149) and CvCascadeBoostTree::predict
+ *    (o_cvcascadeboosttree.cpp:16-39) for trees of one split. The split of every round is section 6's search.
+ *
+ *    cc_boost_create needs cc_eval_presort(_range) over exactly n_samples; the classes are the evaluator's labels
+ *    (getCls == 1.0f positive, 0.0f negative); with a presorted variable range the booster searches that range. Weights
+ *    start at 1./n with every sample active (boost.cpp:190-265). A later presort or setImage(s) on the evaluator makes
+ *    the next cc_boost_round fail with CC_ERR_INVALID_ARG. Weights, subsample mask, weak_eval and the running stage sums
+ *    stay on the device; a round returns one fixed-size record. Every sum the reference forms in a loop is formed in
+ *    the reference's order by one lane, so a round is reproducible bit for bit. The scalar log / exp of REAL's leaves and
+ *    DISCRETE's C are libm's on the host, as in the reference; the n exponentials of update_weights (the reference:
+ *    cvExp) are the device's exp(double), which cc_debug_exp64 exposes.
+ * ============================================================================================ */
+typedef struct cc_boost cc_boost;
+typedef struct cc_boost_params {
+  int32_t boost_type;       /* DISCRETE 0, REAL 1, GENTLE 3; LOGIT 2 -> CC_ERR_UNSUPPORTED (its responses change every round) */
+  int32_t split_criteria;   /* as cc_eval_find_best_split */
+  double weight_trim_rate;  /* 0.95; <= 0 or >= 1 disables trimming (o_cvboost.cpp:109) */
+  float min_hit_rate, max_false_alarm; /* 0.995f, 0.5f */
+  int32_t max_weak_count;   /* 100 */
+} cc_boost_params;
+typedef struct cc_weak { /* one round's fixed-size record */
+  int32_t trained;       /* 0: the tree could not be trained (boost.cpp:436-440), nothing was added */
+  int32_t stop;          /* 0 go on; 1 false alarm reached; 2 max_weak_count; 3 no active sample left (boost.cpp:444); 4 not trained */
+  int32_t n_active, var_idx, split_point; /* n_active: samples the tree was trained on */
+  float quality, ord_c;
+  int32_t subset[8];
+  double left_value, right_value; /* node->value of the leaves; after tree->scale(C) for DISCRETE */
+  float stage_threshold, hit_rate, false_alarm; /* isErrDesired, boost.cpp:479-518; unchanged when stop == 3 or 4 */
+} cc_weak;
+CC_API cc_status cc_boost_create(cc_evaluator* e, int n_samples, const cc_boost_params* p, cc_boost** out);
+CC_API void cc_boost_destroy(cc_boost* b);
+CC_API cc_status cc_boost_round(cc_boost* b, cc_weak* out);
+/* rounds until stop != 0, at most cap of them */
+CC_API cc_status cc_boost_train_stage(cc_boost* b, cc_weak* out, int cap, int* n_weak);
+/* parity instrumentation: any pointer may be NULL; n_samples values each */
+CC_API cc_status cc_boost_get_state(cc_boost* b, double* weights, double* weak_eval, uint8_t* mask, double* stage_sum);
+/* device time of the last round's parts in ms: node table + root value, split search, winner, apply the split, leaves,
+ * weight update + stage sums, trimming, stage status (8 values) */
+CC_API cc_status cc_boost_last_round_ms(cc_boost* b, double* ms, int cap, int* n_parts);
+/* the device's exp(double), for the witness of update_weights */
+CC_API cc_status cc_debug_exp64(int device, const double* x, int n, double* out);
+/* Host only, no device needed: the model CvCascadeClassifier::save would write for these stumps
+ * (cascadeclassifier.cpp:439-456): the used variables only, renumbered in catalog order (markUsedFeaturesInMap,
+ * boost.cpp:566-573; the catalogs are section 4's), stage thresholds and leaves as given. var_idx are catalog indices
+ * (HOG: variable indices), one entry per weak classifier in stage order, n_weak_total of them (what n_weak must add up to); ord_c is read for HAAR / HOG, subsets (8 words
+ * per weak classifier) for LBP. Callers pass (float)value for the leaves and stage_threshold as isErrDesired left it. */
+CC_API cc_status cc_cascade_from_stumps(int feature_type, int haar_mode, int win_w, int win_h, int n_stages, const int32_t* n_weak,
+                                        int n_weak_total, const float* stage_threshold, const int32_t* var_idx, const float* ord_c,
+                                        const int32_t* subsets, const float* left, const float* right, cc_cascade** out);
+
+/* ============================================================================================
  * 7. Multi-GPU: the gather of detections (BASELINE configs[3]).
  *    Detection shards by frame, one process per GPU, and needs no data-path collective: rank r runs cc_detect_batch on
  *    frames [lo, hi) = cc_shard_range(n_frames, r, world). The only exchange is this gather of the per-frame rectangle

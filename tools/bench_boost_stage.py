@@ -4,8 +4,11 @@ maxDepth 1) on 10 000 + 10 000 samples of 24x24 with the full Haar BASIC catalog
 data-parallel step on the device: batched setImage, presort of all variables (once), then per weak learner the node
 split search and one feature row for the sample directions. The boosting bookkeeping between those calls (node values,
 w *= exp(-y f), renormalisation; boost.cpp:378-398, o_cvboostree.cpp:657-732) is the reference's serial host code,
-restated here in numpy with sequential double sums. Prints one JSON line.
-usage: bench_boost_stage.py [rounds=16] [n_samples=20000] [easy|hard] [HAAR|LBP]
+restated here in numpy with sequential double sums: that loop is the BASELINE. The same rounds then run through
+CascadeBoost (cc_boost.hip), where the bookkeeping is on the device too: once without trimming (the baseline's
+arithmetic; the chosen variables must agree) and once with the trainer's weight_trim_rate 0.95, with the device time of
+every kernel of a round beside the split search's. Prints one JSON line.
+usage: bench_boost_stage.py [rounds=20] [n_samples=20000] [easy|hard] [HAAR|LBP]
   easy = SURVEY config 5 as specified (template + N(0,15^2) vs uniform noise: one stump separates it);
   hard = positives template + N(0,40^2), negatives a half-and-half blend with a second template + N(0,40^2)."""
 import json
@@ -25,10 +28,35 @@ def seq_sum(a):
     return float(np.cumsum(a, dtype=np.float64)[-1]) if len(a) else 0.0
 
 
+def device_rounds(cc, e, N, rounds, trim):
+    """`rounds` rounds of CascadeBoost: wall time per round and per stage, device time of each part of a round."""
+    t0 = time.perf_counter()
+    b = cc.CascadeBoost(e, N, weight_trim_rate=trim, max_weak_count=rounds + 1, max_false_alarm=1e-6)
+    t_create = time.perf_counter() - t0
+    parts = {k: 0.0 for k in cc.CascadeBoost.ROUND_PARTS}
+    wall, chosen, active = [], [], []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        rec = b.round()
+        wall.append(time.perf_counter() - t0)
+        if not rec["trained"]:
+            break
+        for k, v in b.last_round_ms().items():
+            parts[k] += v
+        chosen.append(int(rec["var_idx"]))
+        active.append(int(rec["n_active"]))
+    k = max(len(chosen), 1)
+    return {"weight_trim_rate": trim, "rounds_trained": len(chosen), "create_ms": round(t_create * 1e3, 3),
+            "per_round_ms_wall": round(float(np.mean(wall)) * 1e3, 3), "per_round_ms_wall_min": round(float(np.min(wall)) * 1e3, 3),
+            "stage_ms_wall": round(float(np.sum(wall)) * 1e3, 3),
+            "per_round_kernel_ms": {name: round(v / k, 4) for name, v in parts.items()},
+            "active_samples_per_round": active, "chosen_variables": chosen}
+
+
 def main():
     import cascadeclassifier_amd as cc
     from cascadeclassifier_amd import evaluator as ev
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 20000
     imgs, labels = samples(n=N // 2)
     hard = len(sys.argv) > 3 and sys.argv[3] == "hard"
@@ -99,7 +127,14 @@ def main():
            "per_weak_learner_ms": {"split_search_wall": round(t_split / rounds * 1e3, 3), "split_search_kernel": round(float(np.mean(kernel_ms)), 3),
                                    "feature_row": round(t_row / rounds * 1e3, 3), "host_bookkeeping_numpy": round(t_host / rounds * 1e3, 3)},
            "stage_total_s": round(t_set + t_presort + t_split + t_row + t_host, 3),
+           "baseline_per_round_ms": round((t_split + t_row + t_host) / rounds * 1e3, 3),
+           "baseline_stage_ms": round((t_split + t_row + t_host) * 1e3, 3),
            "chosen_variables": chosen, "training_error_after_each_round": [round(x, 4) for x in errs]}
+    dev = device_rounds(cc, e, N, rounds, 1.0)  # no trimming: the baseline's arithmetic
+    k = dev["rounds_trained"]
+    dev["same_variables_as_baseline"] = dev["chosen_variables"] == chosen[:k] and k == rounds
+    out["device_booster"] = dev
+    out["device_booster_trim_0.95"] = device_rounds(cc, e, N, rounds, 0.95)
     print(json.dumps(out))
 
 

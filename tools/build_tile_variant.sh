@@ -10,5 +10,5 @@ flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 /opt/rocm/bin/hipcc $flags -c cc_detect.hip -o build/cc_detect_${ty}_${th}.o
 /opt/rocm/bin/hipcc $flags -c cc_spec.hip -o build/cc_spec_${ty}_${th}.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o ../lib/libcascadeclassifier_amd_${ty}_${th}.so build/cc_xml.o build/cc_cascade.o build/cc_host.o \
-  build/cc_front.o build/cc_negmine.o build/cc_eval.o build/cc_split.o build/cc_hog.o build/cc_comm.o build/cc_detect_${ty}_${th}.o build/cc_spec_${ty}_${th}.o -ldl
+  build/cc_front.o build/cc_negmine.o build/cc_eval.o build/cc_split.o build/cc_boost.o build/cc_hog.o build/cc_comm.o build/cc_detect_${ty}_${th}.o build/cc_spec_${ty}_${th}.o -ldl
 echo built ../lib/libcascadeclassifier_amd_${ty}_${th}.so
