@@ -154,6 +154,13 @@ __device__ __forceinline__ double dpp_f64(double v) {
   const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, ROW_MASK, 0xF, false);
   return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
+// The double that lane `src` (wave-uniform) holds, returned wave-uniform: two 32-bit readlanes.
+__device__ __forceinline__ double readlane_f64(double v, int src) {
+  const unsigned long long u = __double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)u, src);
+  const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
+  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
 __device__ __forceinline__ double wave_sum_f64(double v) {
   v += dpp_f64<0xB1, 0xF>(v);   // quad_perm [1,0,3,2]
   v += dpp_f64<0x4E, 0xF>(v);   // quad_perm [2,3,0,1]
@@ -161,10 +168,11 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   v += dpp_f64<0x140, 0xF>(v);  // row_mirror: every lane now holds the total of its row of 16
   v += dpp_f64<0x142, 0xA>(v);  // row_bcast15 into rows 1 and 3 (masked rows add 0)
   v += dpp_f64<0x143, 0xC>(v);  // row_bcast31 into rows 2 and 3: lane 63 holds the wave total
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)u, 63);
-  const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 63);
-  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+  return readlane_f64(v, 63);
+}
+// Number of set bits of the ballot `mask` below the calling lane: its rank among the lanes that voted.
+__device__ __forceinline__ int lane_rank(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
 }
 
 #endif  // CC_EVAL_COMMON_H

@@ -40,6 +40,10 @@ __device__ __forceinline__ T load_record(const T CC_CONST* p) {
 //                      lanes split the stage's stumps and reduce their votes. Only used when the stage sums of the
 //                      cascade are provably order-independent (exact in double, checked on the host at load time),
 //                      so the reduction is bit-identical to the sequential CPU accumulation.
+// In the code: struct EvalTile holds what a block knows about its tile and the rules the phases share (deliver, enqueue,
+// stage0_outcome, mask_column, never_visited, stage_sum, table_sum, deal_windows); its members stage_phase, dense_phase /
+// dense_phase_rolled, thread_phase (+ split_stage) and wave_phase_haar / wave_phase_lbp are the phases, eval_tile is their
+// sequence with the early exits between them, and eval_block picks the tile layout for the three kernels.
 // ------------------------------------------------------------------------------------------------
 // Stages the tile of the integral into LDS: one wavefront per tile row, lanes = groups of 4 consecutive entries
 // (16-byte global loads; tile origins are multiples of 64 entries and row pitches multiples of 4, so they are aligned,
@@ -320,57 +324,229 @@ struct cc_select<false, A, B> {
   using type = B;
 };
 
+// What the thread phase hands to a wave phase: the group it stopped in front of and that group's queue.
+struct QueueState {
+  int qg = 1;  // current group = index of its queue table / counters
+  int st = 1;  // first stage of the current group
+  int n = 0, rows = 0, my_rows = 0;  // queued windows, rows of the table, rows that hold a window in this lane's column
+};
+// A wavefront's share of the queued windows in a wave phase: lane k < cnt holds the id of its k-th window.
+struct WaveShare {
+  int cnt, my_id;
+  unsigned long long alive;  // bit k = the k-th window is still in the cascade
+};
+
+// One tile of one scale: what every phase of a block needs (all of it block- or lane-constant), the small rules the
+// phases share, and the phases themselves. Everything is inlined into the kernel: eval_tile below is the whole sequence.
 template <int STEP, bool HAAR, bool TREES>
-__device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const int4 T, const ScaleDev& S) {
+struct EvalTile {
   using Stump = typename cc_select<HAAR, HaarStumpDev, LbpStumpDev>::type;
   using Node = typename cc_select<HAAR, HaarNodeDev, LbpNodeDev>::type;
-  const Node* __restrict__ nodes = reinterpret_cast<const Node*>(STEP == 2 ? A.nodes2 : A.nodes1);
+  // 16-bit tile layout: run-time specialised builds the host compiled with CC_SPEC_TILE16, STEP-2 tiles only
+#ifdef CC_SPEC_TILE16
+  static constexpr bool G16 = STEP == 2 && !TREES;
+#else
+  static constexpr bool G16 = false;
+#endif
+  using Geom = typename cc_select<G16, TileGeom16, TileGeom<STEP>>::type;
+
+  const EvalArgs& A;
+  int32_t* const lds;
+  const int4 T;
+  const ScaleDev& S;
 #ifdef CC_SPEC_W0  // run-time specialised build: the window size is a compile-time constant, and with it the tile geometry
-  constexpr int W0 = CC_SPEC_W0, H0 = CC_SPEC_H0;
+  static constexpr int W0 = CC_SPEC_W0, H0 = CC_SPEC_H0;
 #else
   const int W0 = A.W0, H0 = A.H0;
 #endif
-  // 16-bit tile layout: run-time specialised builds the host compiled with CC_SPEC_TILE16, STEP-2 tiles only
-#ifdef CC_SPEC_TILE16
-  constexpr bool G16 = STEP == 2 && !TREES;
-#else
-  constexpr bool G16 = false;
-#endif
-  using Geom = typename cc_select<G16, TileGeom16, TileGeom<STEP>>::type;
-  const Geom G(W0, H0);
-  double* s_part = reinterpret_cast<double*>(lds + tile_words_padded(G.words()) * ((HAAR && A.tilt_chan >= 0) ? 2 : 1));
-  float* s_vnf = reinterpret_cast<float*>(s_part + PART_DOUBLES);                      // [TILE_Y][VNF_PITCH], see vnf_slot (Haar only)
-  unsigned short* s_q = reinterpret_cast<unsigned short*>(s_vnf + (HAAR ? TILE_Y * VNF_PITCH : 0));  // 2 tables [QUEUE_ROWS][32 classes]
-  int* s_cnt = reinterpret_cast<int*>(s_q + 2 * TILE_WINDOWS);                         // [stage % 3][class] = queued windows
+  const Geom G{W0, H0};
+  double* const s_part = reinterpret_cast<double*>(lds + tile_words_padded(G.words()) * ((HAAR && A.tilt_chan >= 0) ? 2 : 1));
+  float* const s_vnf = reinterpret_cast<float*>(s_part + PART_DOUBLES);  // [TILE_Y][VNF_PITCH], see vnf_slot (Haar only)
+  unsigned short* const s_q = reinterpret_cast<unsigned short*>(s_vnf + (HAAR ? TILE_Y * VNF_PITCH : 0));  // 2 tables [QUEUE_ROWS][32 classes]
+  int* const s_cnt = reinterpret_cast<int*>(s_q + 2 * TILE_WINDOWS);  // [stage % 3][class] = queued windows
   const int frame = blockIdx.y;
-  const int32_t* sum = A.integ + ((size_t)frame * A.nchan + 0) * A.int_frame_elems + S.int_ofs;
+  const int32_t* const sum = A.integ + ((size_t)frame * A.nchan + 0) * A.int_frame_elems + S.int_ofs;
   // the wave index is the same in all 64 lanes; say so, or every loop bounded by it is compiled as divergent
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int half = lane >> 5, cls = lane & 31;  // thread and wave phases: half-wavefront and queue column of the lane
   const int gx0 = T.y * TILE_X, gy0 = T.z * TILE_Y;
+  const int skew = (STEP * G.row_stride) & 31;  // see win_class
+  const Node* const nodes = reinterpret_cast<const Node*>(STEP == 2 ? A.nodes2 : A.nodes1);
   // table-driven stages: tile-offset records for the 32-bit tile of this layout; window-coordinate records (gstumps) when
   // the tile holds 16-bit entries and the corners come from global memory (GlobalReader)
-  const Stump CC_CONST* stumps = as_const_table(reinterpret_cast<const Stump*>(G16 ? A.gstumps : STEP == 2 ? A.stumps2 : A.stumps1));
-  const int CC_CONST* stage_first = as_const_table(A.stage_first);
-  const int CC_CONST* stage_ntrees = as_const_table(A.stage_ntrees);
-  const float CC_CONST* stage_thr = as_const_table(A.stage_thr);
+  const Stump CC_CONST* const stumps = as_const_table(reinterpret_cast<const Stump*>(G16 ? A.gstumps : STEP == 2 ? A.stumps2 : A.stumps1));
+  const int CC_CONST* const stage_first = as_const_table(A.stage_first);
+  const int CC_CONST* const stage_ntrees = as_const_table(A.stage_ntrees);
+  const float CC_CONST* const stage_thr = as_const_table(A.stage_thr);
+  const int CC_CONST* const group_first = as_const_table(A.group_first);
   const bool dbg = A.dbg_codes != nullptr && frame == 0;
-  auto stamp = [&](int slot) {  // wavefront 0 only; the buffer is read by nothing but the experiment's host code
+
+  __device__ __forceinline__ EvalTile(const EvalArgs& A_, int32_t* lds_, const int4 T_, const ScaleDev& S_) : A(A_), lds(lds_), T(T_), S(S_) {}
+
+  // ---- the rules the phases share ---------------------------------------------------------------------------------
+  __device__ __forceinline__ void stamp(int slot) const {  // wavefront 0 only; the buffer is read by nothing but the experiment's host code
     if (A.stamps && threadIdx.x == 0)
       A.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * STAMP_SLOTS + slot] = __builtin_amdgcn_s_memtime();
-  };
-  stamp(0);
+  }
+  __device__ __forceinline__ int window_base(int id) const { return ((id >> 6) * STEP) * G.row_stride + (id & 63); }
+  // where the table-driven stump records of window `id` find their corners (see LdsReader / GlobalReader)
+  __device__ __forceinline__ auto table_reader(int id) const {
+    if constexpr (G16)
+      return GlobalReader{sum, (unsigned)((gy0 + (id >> 6)) * STEP) * (unsigned)S.pitchI + (unsigned)((gx0 + (id & 63)) * STEP), S.pitchI};
+    else
+      return LdsReader{lds + window_base(id)};
+  }
+  __device__ __forceinline__ void report(int id, int code, double last) const {  // parity instrumentation
+    const size_t o = (size_t)S.win_ofs + (size_t)(gy0 + (id >> 6)) * S.nx + (gx0 + (id & 63));
+    A.dbg_codes[o] = code;
+    if (A.dbg_sums) A.dbg_sums[o] = last;
+  }
+  __device__ __forceinline__ void emit_candidate(int id, double last_sum) const {
+    const int slot = atomicAdd(A.cand_count, 1);
+    if (slot < A.cand_cap) A.cands[slot] = CandRaw{frame, T.x, gx0 + (id & 63), gy0 + (id >> 6), last_sum};
+  }
+  // Bank class of a window: its tile base mod 32 (every corner read of a stage adds the same constant for all windows).
+  __device__ __forceinline__ int win_class(int id) const { return ((id & 63) + skew * (id >> 6)) & 31; }
+  // s_vnf is laid out so that a window's entry sits on the bank of its class as well
+  __device__ __forceinline__ int vnf_slot(int id) const { return (id >> 6) * (TILE_X + skew) + (id & 63); }
+  // Appends the calling lanes with `pass` to the queue table of stage `st`: next free row of the window's class column.
+  // The 32 lanes of a half-wavefront always hold windows of 32 different classes here (dense phase: 32 consecutive
+  // columns of one row; thread phase: by construction of the table), so the atomics never meet on one counter.
+  __device__ __forceinline__ void enqueue(bool pass, int id, int g) const {  // g = stage group whose queue receives the window
+    if (g >= A.dense_from) {  // block-uniform. Every call site runs with all 64 lanes of the wavefront active.
+      const unsigned long long m = __ballot(pass);
+      int first = 0;
+      if (lane == 0 && m) first = atomicAdd(&s_cnt[(g % 3) * 32], __builtin_popcountll(m));
+      first = __builtin_amdgcn_readfirstlane(first);
+      if (pass) s_q[(g & 1) * TILE_WINDOWS + first + lane_rank(m)] = (unsigned short)id;
+    } else if (pass) {
+      const int c = win_class(id);
+      const int row = atomicAdd(&s_cnt[(g % 3) * 32 + c], 1);
+      s_q[(g & 1) * TILE_WINDOWS + row * 32 + c] = (unsigned short)id;
+    }
+  }
+  // A window that passed the last stage of its group: a candidate when that was the cascade's last group, otherwise it
+  // queues for the next group. Called with all 64 lanes active (enqueue). The queue is marked as the straight path: without
+  // the hint the compiler lays the candidate branch in front of it in the thread phase (table-driven kernels 0.4 % slower).
+  __device__ __forceinline__ void deliver(bool pass, int id, double last_sum, bool last_group, int next_group) const {
+    if (__builtin_expect(last_group, false)) {
+      if (pass) {
+        emit_candidate(id, last_sum);
+        if (dbg) report(id, 1, last_sum);
+      }
+    } else
+      enqueue(pass, id, next_group);
+  }
+  // Stage-0 skip rule, applied early: the scan loop never visits a window whose run of consecutive stage-0
+  // rejections immediately to its left has odd length (k_filter_candidates), so such a window can stop here instead
+  // of walking the later stages for nothing. The run is read off the row's ballot mask `m`; when it reaches the left edge
+  // of this tile its length is only known for the first tile of a row, otherwise the window is kept (the final
+  // filter decides). The parity instrumentation evaluates every window, so it is skipped there.
+  __device__ __forceinline__ bool never_visited(unsigned long long m) const {
+    bool never = false;
+    if (!dbg && A.early_skip) {
+      const unsigned long long lower = (1ull << lane) - 1ull;
+      const unsigned long long zeros_below = ~m & lower;  // lower lanes that were NOT rejected at stage 0
+      int run;
+      bool known;
+      if (zeros_below) {
+        run = lane - 1 - (63 - __clzll((long long)zeros_below));
+        known = true;
+      } else {
+        run = lane;
+        known = T.y == 0;
+      }
+      if (known && (run & 1)) never = true;
+    }
+    return never;
+  }
+  // Stage-0 outcome of the wavefront's window row `ly` (lane = column): writes the row's rejection mask word and returns
+  // whether the lane's window goes on. mask_col = mask_column(), worked out once per phase by the caller: formed here, the
+  // compiler reloads the kernel arguments behind it, with a wait, for every row.
+  __device__ __forceinline__ unsigned long long* mask_column() const {
+    return A.masks + (size_t)frame * A.mask_frame_words + S.mask_ofs + T.y;
+  }
+  __device__ __forceinline__ bool stage0_outcome(int ly, bool alive, double acc, double thr, unsigned long long* mask_col) const {
+    const int gy = gy0 + ly;
+    bool pass = alive && !(acc < thr);
+    const bool rej0 = alive && !pass;
+    const unsigned long long m = __ballot(rej0);
+    if (lane == 0 && gy < S.ny) mask_col[(size_t)gy * S.nxw] = m;
+    if (dbg && rej0) report(ly * 64 + lane, 0, acc);
+    if (never_visited(m)) pass = false;  // (every lane works it out: no branch on `pass`)
+    return pass;
+  }
+  // Sum of one whole stage for one window, in stump order (the CPU's order). `want` only saves work for lanes whose
+  // result is not used (tree walks); every lane addresses a window inside the tile either way.
+  __device__ __forceinline__ double stage_sum(int s, int id, const int32_t* b, float vnf, bool want) const {
+    double acc = 0.;
+    const int first = stage_first[s], nt = stage_ntrees[s];
+    if constexpr (TREES) {
+      for (int j = 0; j < nt; j++) {
+        const int root = as_const_table(A.tree_root)[first + j], leaf0 = as_const_table(A.tree_leaf0)[first + j];
+        if (want) acc += tree_vote(b, nodes, root, leaf0, A.leaves, vnf);
+      }
+    } else {
+#ifdef CC_SPEC_STAGES
+      if (s < CC_SPEC_STAGES) return spec_stage<STEP>(s, 0, SPEC_PARTS, b, vnf);
+#endif
+      acc = table_sum(table_reader(id), first, nt, 0, 1, vnf);
+    }
+    return acc;
+  }
+  // Stumps lo, lo + step, ... of the `nt` >= 1 table-driven stumps from `first` on, for one window. Haar: software pipeline,
+  // the next stump record is fetched (scalar loads) while this one is evaluated.
+  template <class R>
+  __device__ __forceinline__ double table_sum(const R& rd, int first, int nt, int lo, int step, float vnf) const {
+    double acc = 0.;
+    if constexpr (HAAR) {
+      if (lo == 0 || lo < nt) {  // lo == 0 (a whole stage, a constant after inlining): the first load needs no test, nt >= 1
+        Stump cur = load_record(stumps + first + lo);
+        for (int j = lo; j < nt; j += step) {
+          const Stump nxt = load_record(stumps + first + min(j + step, nt - 1));
+          acc += stump_vote(rd, cur, vnf);
+          cur = nxt;
+        }
+      }
+    } else {
+      for (int j = lo; j < nt; j += step) acc += stump_vote(rd, stumps + first + j, vnf);
+    }
+    return acc;
+  }
+  // Deals the queued windows of group h.qg to the wavefronts (both wave phases). Windows are numbered in table order (a
+  // ballot per pair of rows) and dealt round-robin: wavefront w takes numbers w, w + EVAL_WAVES, ... and keeps its k-th
+  // window's id in lane k. Every wavefront numbers the whole table itself and writes only its own share to a private list
+  // (s_part is free here: its last readers finished before the barrier at the top of this stage); the host keeps
+  // wave_below <= 64, so a share fits the 64 lanes.
+  __device__ __forceinline__ WaveShare deal_windows(const QueueState& h) const {
+    const unsigned short* q = s_q + (h.qg & 1) * TILE_WINDOWS;
+    unsigned short* my_list = reinterpret_cast<unsigned short*>(s_part) + wave * 64;
+    int numbered = 0;
+    for (int r0 = 0; r0 < h.rows; r0 += 2) {
+      const int row = r0 + half;
+      const bool valid = row < h.my_rows;
+      const int id = valid ? q[row * 32 + cls] : 0;
+      const unsigned long long mask = __ballot(valid);
+      const int number = numbered + lane_rank(mask);
+      if (valid && number % EVAL_WAVES == wave) my_list[number / EVAL_WAVES] = (unsigned short)id;
+      numbered += __builtin_popcountll(mask);
+    }
+    const int cnt = (numbered - wave + EVAL_WAVES - 1) / EVAL_WAVES;
+    return WaveShare{cnt, lane < cnt ? my_list[lane] : 0, cnt >= 64 ? ~0ull : ((1ull << cnt) - 1ull)};
+  }
 
+  // ---- staging: the squared-sum corners of the variance test and the tile(s) of the integral --------------------------
   // The squared-sum integral is needed at 4 corners per window only: read them from global memory, and issue those
   // loads before the tile is staged so that their latency hides under the staging (they are combined afterwards).
-  unsigned sq_raw[WIN_PER_THREAD][4];
+  __device__ __forceinline__ void stage_phase(unsigned (&valsq_pre)[WIN_PER_THREAD]) const {
+    unsigned sq_raw[WIN_PER_THREAD][4];
 #pragma unroll
-  for (int k = 0; k < WIN_PER_THREAD; k++) {
-    sq_raw[k][0] = sq_raw[k][1] = sq_raw[k][2] = sq_raw[k][3] = 0;
-    if (HAAR) {
-      // windows outside the grid read the last grid window's corners (unconditional loads: a branch here would make the
-      // compiler wait for the data on the spot); they are never alive
-      const int gx = min(gx0 + lane, S.nx - 1), gy = min(gy0 + wave * WIN_PER_THREAD + k, S.ny - 1);
-      {
+    for (int k = 0; k < WIN_PER_THREAD; k++) {
+      sq_raw[k][0] = sq_raw[k][1] = sq_raw[k][2] = sq_raw[k][3] = 0;
+      if (HAAR) {
+        // windows outside the grid read the last grid window's corners (unconditional loads: a branch here would make the
+        // compiler wait for the data on the spot); they are never alive
+        const int gx = min(gx0 + lane, S.nx - 1), gy = min(gy0 + wave * WIN_PER_THREAD + k, S.ny - 1);
         const unsigned* sq = reinterpret_cast<const unsigned*>(A.integ + ((size_t)frame * A.nchan + 1) * A.int_frame_elems + S.int_ofs);
         const int nrx = W0 - 2, nry = H0 - 2;
         size_t q0;
@@ -388,109 +564,37 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
         sq_raw[k][3] = sq[q0 + (size_t)nry * S.pitchI + dx];
       }
     }
-  }
 #ifdef CC_PRIO_STAGE  // tuning (hiprtc -D): issue priority of a block's wavefronts while they stage their tile
-  __builtin_amdgcn_s_setprio(CC_PRIO_STAGE);
+    __builtin_amdgcn_s_setprio(CC_PRIO_STAGE);
 #endif
-  stage_tile<STEP>(lds, G, sum, S, gx0 * STEP, gy0 * STEP);
-  if (HAAR && A.tilt_chan >= 0)  // second tile right behind the first: tilted stumps simply carry offsets shifted by it (never with 16-bit tiles)
-    stage_tile<STEP>(lds + tile_words_padded(G.words()), G,
-                     A.integ + ((size_t)frame * A.nchan + A.tilt_chan) * A.int_frame_elems + S.int_ofs, S, gx0 * STEP, gy0 * STEP);
-  if (threadIdx.x < 3 * 32) s_cnt[threadIdx.x] = 0;
-  unsigned valsq_pre[WIN_PER_THREAD];
+    stage_tile<STEP>(lds, G, sum, S, gx0 * STEP, gy0 * STEP);
+    if (HAAR && A.tilt_chan >= 0)  // second tile right behind the first: tilted stumps simply carry offsets shifted by it (never with 16-bit tiles)
+      stage_tile<STEP>(lds + tile_words_padded(G.words()), G,
+                       A.integ + ((size_t)frame * A.nchan + A.tilt_chan) * A.int_frame_elems + S.int_ofs, S, gx0 * STEP, gy0 * STEP);
+    if (threadIdx.x < 3 * 32) s_cnt[threadIdx.x] = 0;
 #pragma unroll
-  for (int k = 0; k < WIN_PER_THREAD; k++) valsq_pre[k] = sq_raw[k][0] - sq_raw[k][1] - sq_raw[k][2] + sq_raw[k][3];
-  __syncthreads();
+    for (int k = 0; k < WIN_PER_THREAD; k++) valsq_pre[k] = sq_raw[k][0] - sq_raw[k][1] - sq_raw[k][2] + sq_raw[k][3];
+    __syncthreads();
 #ifdef CC_PRIO_STAGE
-  __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 #endif
-  stamp(1);
+  }
 
-  if (A.stop_after == -2) return;  // timing experiments: tile staging only
-  auto window_base = [&](int id) { return ((id >> 6) * STEP) * G.row_stride + (id & 63); };
-  // where the table-driven stump records of window `id` find their corners (see LdsReader / GlobalReader)
-  auto table_reader = [&](int id) {
-    if constexpr (G16)
-      return GlobalReader{sum, (unsigned)((gy0 + (id >> 6)) * STEP) * (unsigned)S.pitchI + (unsigned)((gx0 + (id & 63)) * STEP), S.pitchI};
-    else
-      return LdsReader{lds + window_base(id)};
-  };
-  auto report = [&](int id, int code, double last) {  // parity instrumentation
-    const size_t o = (size_t)S.win_ofs + (size_t)(gy0 + (id >> 6)) * S.nx + (gx0 + (id & 63));
-    A.dbg_codes[o] = code;
-    if (A.dbg_sums) A.dbg_sums[o] = last;
-  };
-  auto emit_candidate = [&](int id, double last_sum) {
-    const int slot = atomicAdd(A.cand_count, 1);
-    if (slot < A.cand_cap) A.cands[slot] = CandRaw{frame, T.x, gx0 + (id & 63), gy0 + (id >> 6), last_sum};
-  };
-  // Bank class of a window: its tile base mod 32 (every corner read of a stage adds the same constant for all windows).
-  const int skew = (STEP * G.row_stride) & 31;
-  auto win_class = [&](int id) { return ((id & 63) + skew * (id >> 6)) & 31; };
-  // s_vnf is laid out so that a window's entry sits on the bank of its class as well
-  auto vnf_slot = [&](int id) { return (id >> 6) * (TILE_X + skew) + (id & 63); };
-  // Appends the calling lanes with `pass` to the queue table of stage `st`: next free row of the window's class column.
-  // The 32 lanes of a half-wavefront always hold windows of 32 different classes here (dense phase: 32 consecutive
-  // columns of one row; thread phase: by construction of the table), so the atomics never meet on one counter.
-  auto enqueue = [&](bool pass, int id, int g) {  // g = stage group whose queue receives the window
-    if (g >= A.dense_from) {  // block-uniform. Every call site runs with all 64 lanes of the wavefront active.
-      const unsigned long long m = __ballot(pass);
-      int first = 0;
-      if (lane == 0 && m) first = atomicAdd(&s_cnt[(g % 3) * 32], __builtin_popcountll(m));
-      first = __builtin_amdgcn_readfirstlane(first);
-      if (pass) s_q[(g & 1) * TILE_WINDOWS + first + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0))] = (unsigned short)id;
-    } else if (pass) {
-      const int c = win_class(id);
-      const int row = atomicAdd(&s_cnt[(g % 3) * 32 + c], 1);
-      s_q[(g & 1) * TILE_WINDOWS + row * 32 + c] = (unsigned short)id;
-    }
-  };
-
-  const int CC_CONST* group_first = as_const_table(A.group_first);
-  // Sum of one whole stage for one window, in stump order (the CPU's order). `want` only saves work for lanes whose
-  // result is not used (tree walks); every lane addresses a window inside the tile either way.
-  auto stage_sum = [&](int s, int id, const int32_t* b, float vnf, bool want) -> double {
-    double acc = 0.;
-    const int first = stage_first[s], nt = stage_ntrees[s];
-    if constexpr (TREES) {
-      for (int j = 0; j < nt; j++) {
-        const int root = as_const_table(A.tree_root)[first + j], leaf0 = as_const_table(A.tree_leaf0)[first + j];
-        if (want) acc += tree_vote(b, nodes, root, leaf0, A.leaves, vnf);
-      }
-    } else {
-#ifdef CC_SPEC_STAGES
-      if (s < CC_SPEC_STAGES) return spec_stage<STEP>(s, 0, SPEC_PARTS, b, vnf);
-#endif
-      const auto rd = table_reader(id);
-      if constexpr (HAAR) {
-        Stump cur = load_record(stumps + first);
-        for (int j = 0; j < nt; j++) {
-          const Stump nxt = load_record(stumps + first + min(j + 1, nt - 1));
-          acc += stump_vote(rd, cur, vnf);
-          cur = nxt;
-        }
-      } else {
-        for (int j = 0; j < nt; j++) acc += stump_vote(rd, stumps + first + j, vnf);
-      }
-    }
-    return acc;
-  };
-
-  // ---------------- phase D: variance test + stage 0, WIN_PER_THREAD window rows per thread -------------------
+  // ---- phase D: variance test + stage 0, WIN_PER_THREAD window rows per thread ----------------------------------------
   // LBP stump kernels with more than two rows per thread (the 20-row tiles of the specialised LBP kernel: five) take the
   // rows one after the other in a rolled loop: there is no variance test to batch, and five unrolled copies of stage 0
   // kept 25 VGPRs in scratch (1.07 GB of spill stores per 32-frame launch in the counters). Same operations per window.
-  if constexpr (!HAAR && !TREES && WIN_PER_THREAD > 2) {
+  static constexpr bool kRolledDense = !HAAR && !TREES && WIN_PER_THREAD > 2;
+  __device__ __forceinline__ void dense_phase_rolled() const {
     const int gx = gx0 + lane;
     const double thr0 = (double)stage_thr[0];
-    const int nt0 = stage_ntrees[0];
+    unsigned long long* const mask_col = mask_column();
+    [[maybe_unused]] const int nt0 = stage_ntrees[0];
 #pragma unroll 1
     for (int k = 0; k < WIN_PER_THREAD; k++) {
       const int ly = wave * WIN_PER_THREAD + k;
-      const int gy = gy0 + ly;
-      const int id = ly * 64 + lane;
       const int32_t* b = lds + (ly * STEP) * G.row_stride + lane;
-      const bool alive = gx < S.nx && gy < S.ny;
+      const bool alive = gx < S.nx && gy0 + ly < S.ny;
       double acc = 0.;
       if (__any(alive)) {
 #ifdef CC_SPEC_STAGES
@@ -499,35 +603,11 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
         for (int i = 0; i < nt0; i++) acc += stump_vote(LdsReader{b}, stumps + i, 1.f);
 #endif
       }
-      (void)nt0;
-      bool pass = alive && !(acc < thr0);
-      const bool rej0 = alive && !pass;
-      const unsigned long long m = __ballot(rej0);
-      if (lane == 0 && gy < S.ny) A.masks[(size_t)frame * A.mask_frame_words + S.mask_ofs + (size_t)gy * S.nxw + T.y] = m;
-      if (dbg && rej0) report(id, 0, acc);
-      if (!dbg && A.early_skip) {  // the stage-0 skip rule, applied early (see the general path below)
-        const unsigned long long lower = (1ull << lane) - 1ull;
-        const unsigned long long zeros_below = ~m & lower;
-        int run;
-        bool known;
-        if (zeros_below) {
-          run = lane - 1 - (63 - __clzll((long long)zeros_below));
-          known = true;
-        } else {
-          run = lane;
-          known = T.y == 0;
-        }
-        if (known && (run & 1)) pass = false;
-      }
-      if (A.nstages == 1) {
-        if (pass) {
-          emit_candidate(id, acc);
-          if (dbg) report(id, 1, acc);
-        }
-      } else
-        enqueue(pass, id, 1);
+      deliver(stage0_outcome(ly, alive, acc, thr0, mask_col), ly * 64 + lane, acc, A.nstages == 1, 1);
     }
-  } else {
+  }
+  // Returns false when the block ends here (stop_after == -3).
+  __device__ __forceinline__ bool dense_phase(const unsigned (&valsq_pre)[WIN_PER_THREAD]) const {
     int base[WIN_PER_THREAD];
     float vnf[WIN_PER_THREAD];
     bool alive[WIN_PER_THREAD];
@@ -570,7 +650,7 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
 #pragma unroll
       for (int k = 0; k < WIN_PER_THREAD; k++) sink += alive[k] ? vnf[k] : 0.f;
       if (HAAR && sink == 12345.f) s_vnf[0] = sink;
-      return;
+      return false;
     }
     bool any_mine = false;
     double acc[WIN_PER_THREAD];
@@ -580,7 +660,7 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
       acc[k] = 0.;
     }
     if (__any(any_mine)) {
-      const int nt = stage_ntrees[0];
+      [[maybe_unused]] const int nt = stage_ntrees[0];
       if constexpr (TREES) {
         for (int i = 0; i < nt; i++) {
           const int root = as_const_table(A.tree_root)[i], leaf0 = as_const_table(A.tree_leaf0)[i];
@@ -588,26 +668,8 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
           for (int k = 0; k < WIN_PER_THREAD; k++)
             if (alive[k]) acc[k] += tree_vote(lds + base[k], nodes, root, leaf0, A.leaves, vnf[k]);
         }
-      } else if constexpr (HAAR) {
-#ifdef CC_SPEC_STAGES
-        if constexpr (WIN_PER_THREAD == 2) {
-          spec_stage0_x2<STEP>(lds + base[0], lds + base[1], vnf[0], vnf[1], acc[0], acc[1]);
-        } else {
-#pragma unroll
-          for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] = spec_stage<STEP>(0, 0, SPEC_PARTS, lds + base[k], vnf[k]);
-        }
-#else
-        // software pipeline: the next stump record is fetched (scalar loads) while this one is evaluated
-        Stump cur = load_record(stumps);
-        for (int i = 0; i < nt; i++) {
-          const Stump nxt = load_record(stumps + min(i + 1, nt - 1));
-#pragma unroll
-          for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] += stump_vote(LdsReader{lds + base[k]}, cur, vnf[k]);
-          cur = nxt;
-        }
-#endif
       } else {
-#ifdef CC_SPEC_STAGES
+#ifdef CC_SPEC_STAGES  // the generated stage 0: the two rows of a thread together where the tile gives it two
         if constexpr (WIN_PER_THREAD == 2) {
           spec_stage0_x2<STEP>(lds + base[0], lds + base[1], vnf[0], vnf[1], acc[0], acc[1]);
         } else {
@@ -615,116 +677,85 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
           for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] = spec_stage<STEP>(0, 0, SPEC_PARTS, lds + base[k], vnf[k]);
         }
 #else
-        for (int i = 0; i < nt; i++) {
+        if constexpr (HAAR) {
+          // software pipeline: the next stump record is fetched (scalar loads) while this one is evaluated
+          Stump cur = load_record(stumps);
+          for (int i = 0; i < nt; i++) {
+            const Stump nxt = load_record(stumps + min(i + 1, nt - 1));
 #pragma unroll
-          for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] += stump_vote(LdsReader{lds + base[k]}, stumps + i, vnf[k]);
+            for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] += stump_vote(LdsReader{lds + base[k]}, cur, vnf[k]);
+            cur = nxt;
+          }
+        } else {
+          for (int i = 0; i < nt; i++) {
+#pragma unroll
+            for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] += stump_vote(LdsReader{lds + base[k]}, stumps + i, vnf[k]);
+          }
         }
 #endif
       }
     }
     const double thr = (double)stage_thr[0];
+    unsigned long long* const mask_col = mask_column();
     bool pass_k[WIN_PER_THREAD];
 #pragma unroll
-    for (int k = 0; k < WIN_PER_THREAD; k++) {
-      const int ly = wave * WIN_PER_THREAD + k;
-      const int gy = gy0 + ly;
-      const int id = ly * 64 + lane;
-      bool pass = alive[k] && !(acc[k] < thr);
-      const bool rej0 = alive[k] && !pass;
-      const unsigned long long m = __ballot(rej0);
-      if (lane == 0 && gy < S.ny) A.masks[(size_t)frame * A.mask_frame_words + S.mask_ofs + (size_t)gy * S.nxw + T.y] = m;
-      if (dbg && rej0) report(id, 0, acc[k]);
-      // Stage-0 skip rule, applied early: the scan loop never visits a window whose run of consecutive stage-0
-      // rejections immediately to its left has odd length (k_filter_candidates), so such a window can stop here instead
-      // of walking the later stages for nothing. The run is read off the row's ballot mask; when it reaches the left edge
-      // of this tile its length is only known for the first tile of a row, otherwise the window is kept (the final
-      // filter decides). The parity instrumentation evaluates every window, so it is skipped there.
-      if (!dbg && A.early_skip) {
-        const unsigned long long lower = (1ull << lane) - 1ull;
-        const unsigned long long zeros_below = ~m & lower;  // lower lanes that were NOT rejected at stage 0
-        int run;
-        bool known;
-        if (zeros_below) {
-          run = lane - 1 - (63 - __clzll((long long)zeros_below));
-          known = true;
-        } else {
-          run = lane;
-          known = T.y == 0;
-        }
-        if (known && (run & 1)) pass = false;
-      }
-      pass_k[k] = pass;
-    }
+    for (int k = 0; k < WIN_PER_THREAD; k++) pass_k[k] = stage0_outcome(wave * WIN_PER_THREAD + k, alive[k], acc[k], thr, mask_col);
+    const bool last_group = A.nstages == 1;
 #pragma unroll
     for (int k = 0; k < WIN_PER_THREAD; k++) {
       const int id = (wave * WIN_PER_THREAD + k) * 64 + lane;
-      const bool pass = pass_k[k];
-      if (A.nstages == 1) {
-        if (pass) {
-          emit_candidate(id, acc[k]);
-          if (dbg) report(id, 1, acc[k]);
-        }
-      } else {
-        if (HAAR && pass) s_vnf[vnf_slot(id)] = vnf[k];  // LBP blocks have no s_vnf area (eval_lds_bytes)
-        enqueue(pass, id, 1);
-      }
+      if (HAAR && pass_k[k] && !last_group) s_vnf[vnf_slot(id)] = vnf[k];  // LBP blocks have no s_vnf area (eval_lds_bytes)
+      deliver(pass_k[k], id, acc[k], last_group, 1);
     }
+    return true;
   }
 
-  stamp(2);
-#ifdef CC_PRIO_LATE  // tuning (hiprtc -D): issue priority once the dense phase is done
-  __builtin_amdgcn_s_setprio(CC_PRIO_LATE);
-#endif
-  // ---------------- phase T: one thread per queued window, stage by stage -------------------------------------
+  // ---- phase T: one thread per queued window, stage by stage -----------------------------------------------------------
   // Half-wavefront h of wavefront g takes queue row 2g + h; its lane l the window of class l in that row (if the class
   // has that many). With few rows queued and order-independent (exact) stage sums, the block's wavefronts also SPLIT
   // THE STUMPS of the stage (slices j = slice, slice+ns, ...): the partial sums meet in LDS and slice 0 finishes the
   // window. This keeps all wavefronts busy through the long late stages instead of leaving one wave to walk them.
-  const int half = lane >> 5, cls = lane & 31;
-  int st = 1;          // first stage of the current group
-  int qg = 1;          // current group = index of its queue table / counters
-  int n = 0, rows = 0, my_rows = 0;
-  for (; qg < A.ngroups; qg++) {
-    st = group_first[qg];
-    const int st_end = group_first[qg + 1];
-    if (A.stop_after >= 0 && st > A.stop_after) return;
-    __syncthreads();  // queue of group qg complete; previous readers of the buffers it overwrites are done
-    // (the counts are clamped to what the tables can hold: a count that some bug corrupted must not become a loop bound
-    // of 2^30 trips on a device where waves that never finish take the node down)
-    if (qg >= A.dense_from) {  // plain list: entry i sits in row i / 32, column i % 32
-      n = min(s_cnt[(qg % 3) * 32], TILE_WINDOWS);
-      rows = (n + 31) >> 5;
-      my_rows = max(0, (n - cls + 31) >> 5);  // rows that hold an entry in this lane's column
-    } else {
-      my_rows = min(s_cnt[(qg % 3) * 32 + cls], QUEUE_ROWS);  // windows queued in this lane's class
-      rows = wave_max_u32(my_rows);                            // both halves hold the same 32 counts
-      n = wave_sum_u32(my_rows) >> 1;
-    }
-    if (threadIdx.x < 32) s_cnt[((qg + 2) % 3) * 32 + threadIdx.x] = 0;  // counters of group qg+2 (last read in group qg-1)
-    if (st + 2 < STAMP_SLOTS - 1) stamp(st + 2);  // the previous group (and the barrier behind it) done
-    if (n == 0 || n < A.wave_below) break;
-    const unsigned short* q = s_q + (qg & 1) * TILE_WINDOWS;
-    const bool last_group = st_end >= A.nstages;
-    const int groups = (rows + 1) >> 1;  // wavefronts needed to give every queue row a half-wavefront
-    const int first = stage_first[st], nt = stage_ntrees[st];
-    const double thr = (double)stage_thr[st];
-    // Whole rounds of EVAL_WAVES row groups run one group per wavefront; the groups left over (all of them when there are
-    // fewer groups than wavefronts) are split by stumps over the wavefronts, so that no wavefront walks a whole extra
-    // pass alone while the others wait at the barrier. Only a group that is ONE stage can be split that way (the sum of
-    // a stage must be known before the next one starts).
-    const bool may_split = A.split_stumps && st_end - st == 1;
-    const int g_split = may_split ? groups - groups % EVAL_WAVES : groups;  // first row group of the split part
-    const int rem = groups - g_split;
-    int ns = 1;                          // stump slices of the split part
-    if (rem > 0)
-      while (ns * 2 * rem <= EVAL_WAVES) ns *= 2;  // largest power of two with ns * rem <= wavefronts
-    {
+  // Returns false when the block ends here (stop_after); otherwise h says where the phase stopped.
+  __device__ __forceinline__ bool thread_phase(QueueState& h) const {
+    for (; h.qg < A.ngroups; h.qg++) {
+      const int qg = h.qg;
+      const int st = h.st = group_first[qg];
+      const int st_end = group_first[qg + 1];
+      if (A.stop_after >= 0 && st > A.stop_after) return false;
+      __syncthreads();  // queue of group qg complete; previous readers of the buffers it overwrites are done
+      // (the counts are clamped to what the tables can hold: a count that some bug corrupted must not become a loop bound
+      // of 2^30 trips on a device where waves that never finish take the node down)
+      if (qg >= A.dense_from) {  // plain list: entry i sits in row i / 32, column i % 32
+        h.n = min(s_cnt[(qg % 3) * 32], TILE_WINDOWS);
+        h.rows = (h.n + 31) >> 5;
+        h.my_rows = max(0, (h.n - cls + 31) >> 5);  // rows that hold an entry in this lane's column
+      } else {
+        h.my_rows = min(s_cnt[(qg % 3) * 32 + cls], QUEUE_ROWS);  // windows queued in this lane's class
+        h.rows = wave_max_u32(h.my_rows);                            // both halves hold the same 32 counts
+        h.n = wave_sum_u32(h.my_rows) >> 1;
+      }
+      if (threadIdx.x < 32) s_cnt[((qg + 2) % 3) * 32 + threadIdx.x] = 0;  // counters of group qg+2 (last read in group qg-1)
+      if (st + 2 < STAMP_SLOTS - 1) stamp(st + 2);  // the previous group (and the barrier behind it) done
+      if (h.n == 0 || h.n < A.wave_below) break;
+      const unsigned short* q = s_q + (qg & 1) * TILE_WINDOWS;
+      const bool last_group = st_end >= A.nstages;
+      const int groups = (h.rows + 1) >> 1;  // wavefronts needed to give every queue row a half-wavefront
+      // Whole rounds of EVAL_WAVES row groups run one group per wavefront; the groups left over (all of them when there are
+      // fewer groups than wavefronts) are split by stumps over the wavefronts, so that no wavefront walks a whole extra
+      // pass alone while the others wait at the barrier. Only a group that is ONE stage can be split that way (the sum of
+      // a stage must be known before the next one starts).
+      const bool may_split = A.split_stumps && st_end - st == 1;
+      const int g_split = may_split ? groups - groups % EVAL_WAVES : groups;  // first row group of the split part
+      const int rem = groups - g_split;
+      int ns = 1;                          // stump slices of the split part
+      if (rem > 0)
+        while (ns * 2 * rem <= EVAL_WAVES) ns *= 2;  // largest power of two with ns * rem <= wavefronts
       // each lane walks the group's stages with its window; no barrier and no re-queueing between them, a window that
       // fails records its exit and only stops counting
       const int g_end = ns == 1 ? groups : g_split;
       for (int g = wave; g < g_end; g += EVAL_WAVES) {  // wave-uniform trip count
         const int row = g * 2 + half;
-        const bool valid = row < my_rows;
+        const bool valid = row < h.my_rows;
         // a lane without a window evaluates the (in-tile) window `cls` of its own class, so it stays off the others' banks
         const int id = valid ? q[row * 32 + cls] : cls;
         const int32_t* b = lds + window_base(id);
@@ -739,99 +770,53 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
           if (alive) acc = a;
           alive = pass;
         }
-        if (last_group) {
-          if (alive) {
-            emit_candidate(id, acc);
-            if (dbg) report(id, 1, acc);
-          }
-        } else
-          enqueue(alive, id, qg + 1);
+        deliver(alive, id, acc, last_group, qg + 1);
       }
+      if (ns > 1) split_stage(h, q, last_group, g_split, rem, ns);
     }
-    auto finish = [&](bool valid, int id, double acc) {
-      const bool pass = valid && !(acc < thr);
-      if (dbg && valid && !pass) report(id, -st, acc);
-      if (last_group) {
-        if (pass) {
-          emit_candidate(id, acc);
-          if (dbg) report(id, 1, acc);
-        }
-      } else
-        enqueue(pass, id, qg + 1);
-    };
-    if (ns > 1) {
-      const int slice = wave % ns, grp = wave / ns;  // EVAL_WAVES / ns groups >= `rem`
-      const int row = (g_split + grp) * 2 + half;
-      const int i = grp * 64 + lane;
-      const bool valid = row < my_rows;
-      const int id = valid ? q[min(row, QUEUE_ROWS - 1) * 32 + cls] : cls;  // (QUEUE_ROWS is not a power of two for every tile height)
-      double acc = 0.;
-      if (grp < rem) {
-        [[maybe_unused]] const int32_t* b = lds + window_base(id);
-        const float vnf = HAAR ? s_vnf[vnf_slot(id)] : 1.f;
-        [[maybe_unused]] const auto rd = table_reader(id);
-        if constexpr (HAAR) {
-#ifdef CC_SPEC_STAGES
-          if (!TREES && st < CC_SPEC_STAGES) {
-            acc = spec_stage<STEP>(st, slice * (SPEC_PARTS / ns), (slice + 1) * (SPEC_PARTS / ns), b, vnf);
-          } else
-#endif
-          if (slice < nt) {
-            Stump cur = load_record(stumps + first + slice);
-            for (int j = slice; j < nt; j += ns) {
-              const Stump nxt = load_record(stumps + first + min(j + ns, nt - 1));
-              acc += stump_vote(rd, cur, vnf);
-              cur = nxt;
-            }
-          }
-        } else {
-#ifdef CC_SPEC_STAGES
-          if (!TREES && st < CC_SPEC_STAGES)
-            acc = spec_stage<STEP>(st, slice * (SPEC_PARTS / ns), (slice + 1) * (SPEC_PARTS / ns), b, vnf);
-          else
-#endif
-            for (int j = slice; j < nt; j += ns) acc += stump_vote(rd, stumps + first + j, vnf);
-        }
-        if (slice) s_part[(slice - 1) * (EVAL_THREADS / ns) + i] = acc;  // <= (EVAL_WAVES - 1) * 64 entries for every ns
-      }
-      __syncthreads();  // partial sums visible
-      if (grp < rem && slice == 0) {
-        for (int k = 1; k < ns; k++) acc += s_part[(k - 1) * (EVAL_THREADS / ns) + i];
-        finish(valid, id, acc);
-      }
-    }
+    return true;
   }
-  if (qg >= A.ngroups || n == 0) {
-    stamp(STAMP_SLOTS - 1);
-    return;
+  // The stump-split part of a one-stage group: row groups g_split .. g_split + rem - 1, each cut into ns stump slices.
+  __device__ __forceinline__ void split_stage(const QueueState& h, const unsigned short* q, bool last_group, int g_split, int rem, int ns) const {
+    const int st = h.st;
+    const int first = stage_first[st], nt = stage_ntrees[st];
+    const int slice = wave % ns, grp = wave / ns;  // EVAL_WAVES / ns groups >= `rem`
+    const int row = (g_split + grp) * 2 + half;
+    const int i = grp * 64 + lane;
+    const bool valid = row < h.my_rows;
+    const int id = valid ? q[min(row, QUEUE_ROWS - 1) * 32 + cls] : cls;  // (QUEUE_ROWS is not a power of two for every tile height)
+    double acc = 0.;
+    if (grp < rem) {
+      [[maybe_unused]] const int32_t* b = lds + window_base(id);
+      const float vnf = HAAR ? s_vnf[vnf_slot(id)] : 1.f;
+#ifdef CC_SPEC_STAGES
+      if (!TREES && st < CC_SPEC_STAGES)
+        acc = spec_stage<STEP>(st, slice * (SPEC_PARTS / ns), (slice + 1) * (SPEC_PARTS / ns), b, vnf);
+      else
+#endif
+        acc = table_sum(table_reader(id), first, nt, slice, ns, vnf);
+      if (slice) s_part[(slice - 1) * (EVAL_THREADS / ns) + i] = acc;  // <= (EVAL_WAVES - 1) * 64 entries for every ns
+    }
+    __syncthreads();  // partial sums visible
+    if (grp < rem && slice == 0) {
+      for (int k = 1; k < ns; k++) acc += s_part[(k - 1) * (EVAL_THREADS / ns) + i];
+      const bool pass = valid && !(acc < (double)stage_thr[st]);
+      if (dbg && valid && !pass) report(id, -st, acc);
+      deliver(pass, id, acc, last_group, h.qg + 1);
+    }
   }
 
-  // ---------------- phase W: one wavefront per window, lanes split the stumps ---------------------------------
-  // A wavefront takes the valid slots wave, wave + EVAL_WAVES, ... of the queue table (row-major; a slot beyond its
-  // class's count is empty) and walks its windows STAGE BY STAGE: lane j fetches stump j's record once per stage (a
-  // per-lane 64-byte global load, the slow part) and keeps it in registers while the wavefront's windows are evaluated
-  // against it one after the other. Lane k carries the stage sum of the wavefront's k-th window.
-  if constexpr (HAAR && !TREES) {
-    const unsigned short* q = s_q + (qg & 1) * TILE_WINDOWS;
+  // ---- phase W: one wavefront per window, lanes split the stumps -------------------------------------------------------
+  // A wavefront takes its share of the queued windows (deal_windows) and walks them STAGE BY STAGE: lane j fetches stump
+  // j's record once per stage (a per-lane 64-byte global load, the slow part) and keeps it in registers while the
+  // wavefront's windows are evaluated against it one after the other. Lane k carries the stage sum of the wavefront's
+  // k-th window.
+  __device__ __forceinline__ void wave_phase_haar(const QueueState& h) const {
+    const int st = h.st;
     const Stump* wstumps = reinterpret_cast<const Stump*>(G16 ? A.gstumps : STEP == 2 ? A.wstumps2 : A.wstumps1);
-    // Windows are numbered in table order (a ballot per pair of rows) and dealt round-robin: wavefront w takes numbers
-    // w, w + EVAL_WAVES, ... and keeps its k-th window's id in lane k. Every wavefront numbers the whole table itself and
-    // writes only its own share to a private list (s_part is free here: its last readers finished before the barrier at
-    // the top of this stage); the host keeps wave_below <= 64, so a share fits the 64 lanes.
-    unsigned short* my_list = reinterpret_cast<unsigned short*>(s_part) + wave * 64;
-    int numbered = 0;
-    for (int r0 = 0; r0 < rows; r0 += 2) {
-      const int row = r0 + half;
-      const bool valid = row < my_rows;
-      const int id = valid ? q[row * 32 + cls] : 0;
-      const unsigned long long mask = __ballot(valid);
-      const int number = numbered + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-      if (valid && number % EVAL_WAVES == wave) my_list[number / EVAL_WAVES] = (unsigned short)id;
-      numbered += __builtin_popcountll(mask);
-    }
-    const int cnt = (numbered - wave + EVAL_WAVES - 1) / EVAL_WAVES;
-    const int my_id = lane < cnt ? my_list[lane] : 0;
-    unsigned long long alive = cnt >= 64 ? ~0ull : ((1ull << cnt) - 1ull);
+    const WaveShare w = deal_windows(h);
+    const int cnt = w.cnt, my_id = w.my_id;
+    unsigned long long alive = w.alive;
     const bool w_stamps = st + 2 < 30;  // stamp slots 30.. are free then: 30 = windows collected, 31 + i = i-th wave-phase stage done
     if (w_stamps) stamp(30);
     double tot = 0., last = 0.;
@@ -868,7 +853,7 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
       if (dbg && (accepted || !((alive >> lane) & 1ull))) report(my_id, accepted ? 1 : -rej, last);
     }
   }
-  // ---------------- phase W for LBP stump cascades: one wavefront per window, lanes = the stumps of SEVERAL stages ----
+  // ---- phase W for LBP stump cascades: one wavefront per window, lanes = the stumps of SEVERAL stages -------------------
   // LBP stages are short (3-10 stumps in the stock cascade) and a stump is a long dependent chain (16 corner reads, nine
   // cell sums, eight comparisons, the subset bit), so once a tile is down to a few windows every further stage costs a
   // barrier round plus its stumps' latencies one after the other -- 40 % of a block's life for a handful of windows
@@ -877,31 +862,19 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
   // wavefront's windows), the votes go to a small LDS scratch, and the first lanes add up one stage each IN STUMP ORDER --
   // the CPU's order, so no exactness condition is needed -- and test it; the first failing stage is the window's result.
   // Stages behind a failing one were evaluated for nothing, which costs no time: they ran in the same pass.
-  if constexpr (!HAAR && !TREES && EVAL_WAVES >= 4) {
-    const unsigned short* q = s_q + (qg & 1) * TILE_WINDOWS;
-    unsigned short* my_list = reinterpret_cast<unsigned short*>(s_part) + wave * 64;   // as in the Haar wave phase
-    float* votes = reinterpret_cast<float*>(reinterpret_cast<char*>(s_part) + EVAL_WAVES * 128) + wave * 64;  // behind the lists
-    int numbered = 0;
-    for (int r0 = 0; r0 < rows; r0 += 2) {
-      const int row = r0 + half;
-      const bool valid = row < my_rows;
-      const int id = valid ? q[row * 32 + cls] : 0;
-      const unsigned long long mask = __ballot(valid);
-      const int number = numbered + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-      if (valid && number % EVAL_WAVES == wave) my_list[number / EVAL_WAVES] = (unsigned short)id;
-      numbered += __builtin_popcountll(mask);
-    }
-    const int cnt = (numbered - wave + EVAL_WAVES - 1) / EVAL_WAVES;
-    const int my_id = lane < cnt ? my_list[lane] : 0;
-    unsigned long long alive = cnt >= 64 ? ~0ull : ((1ull << cnt) - 1ull);
-    if (st + 2 < 30) stamp(30);
+  __device__ __forceinline__ void wave_phase_lbp(const QueueState& h) const {
+    float* votes = reinterpret_cast<float*>(reinterpret_cast<char*>(s_part) + EVAL_WAVES * 128) + wave * 64;  // behind the lists of deal_windows
+    const WaveShare w = deal_windows(h);
+    const int cnt = w.cnt, my_id = w.my_id;
+    unsigned long long alive = w.alive;
+    if (h.st + 2 < 30) stamp(30);
     // records: tile offsets of the layout this tile uses; with 16-bit tiles only when EVERY cell of the cascade fits 16 bits
     // (lbp16_all), otherwise window coordinates and the corners come from global memory
     const bool use16 = G16 && A.lbp16_all;
     const Stump* tab = reinterpret_cast<const Stump*>(G16 ? (use16 ? A.wstumps2 : A.gstumps) : STEP == 2 ? A.stumps2 : A.stumps1);
     double last = 0.;  // lane k: stage sum its window ended with
     int code = 1;      // lane k: result code of its window (1 = passed every stage so far)
-    int s2 = st;
+    int s2 = h.st;
     while (s2 < A.nstages && alive) {
       if (A.stop_after >= 0 && s2 > A.stop_after) break;
       const int first = stage_first[s2];
@@ -928,10 +901,9 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
         for (int i = 0; i < my_nt; i++) acc += (double)votes[my_f0 + i];  // same wavefront: LDS operations stay in order
         const unsigned long long failed = __ballot(lane < n_st && acc < my_thr);
         const int t = failed ? __builtin_ctzll(failed) : n_st - 1;  // first failing stage of the chunk, else its last stage
-        const unsigned long long au = __double_as_longlong(acc);
-        const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)au, t), hi = __builtin_amdgcn_readlane((int)(unsigned)(au >> 32), t);
+        const double ended = readlane_f64(acc, t);
         if (lane == k) {
-          last = __longlong_as_double(((unsigned long long)hi << 32) | lo);
+          last = ended;
           if (failed) code = -(s2 + t);
         }
         if (failed) alive &= ~(1ull << k);
@@ -944,40 +916,67 @@ __device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const
       if (dbg && (accepted || code != 1)) report(my_id, code, last);
     }
   }
-  stamp(STAMP_SLOTS - 1);
+};
+
+template <int STEP, bool HAAR, bool TREES>
+__device__ __forceinline__ void eval_tile(const EvalArgs& A, int32_t* lds, const int4 T, const ScaleDev& S) {
+  using Tile = EvalTile<STEP, HAAR, TREES>;
+  const Tile t(A, lds, T, S);
+  t.stamp(0);
+  unsigned valsq_pre[WIN_PER_THREAD];
+  t.stage_phase(valsq_pre);
+  t.stamp(1);
+  if (A.stop_after == -2) return;  // timing experiments: tile staging only
+  if constexpr (Tile::kRolledDense)
+    t.dense_phase_rolled();
+  else if (!t.dense_phase(valsq_pre))
+    return;
+  t.stamp(2);
+#ifdef CC_PRIO_LATE  // tuning (hiprtc -D): issue priority once the dense phase is done
+  __builtin_amdgcn_s_setprio(CC_PRIO_LATE);
+#endif
+  QueueState h;
+  if (!t.thread_phase(h)) return;
+  if (h.qg < A.ngroups && h.n != 0) {  // windows left for a wave phase (stump cascades; wave_below is 0 for the others)
+    if constexpr (HAAR && !TREES) t.wave_phase_haar(h);
+    if constexpr (!HAAR && !TREES && EVAL_WAVES >= 4) t.wave_phase_lbp(h);
+  }
+  t.stamp(STAMP_SLOTS - 1);
+}
+
+// Block entry: the block's tile and scale records, and the (block-uniform) choice of the tile layout by the scale's step.
+// ONLY_STEP 1 / 2: only that layout is compiled in. ALLOW_TREES: cascades with trees deeper than stumps (rare; thread-
+// per-window phases only) are served too.
+template <bool HAAR, int ONLY_STEP, bool ALLOW_TREES>
+__device__ __forceinline__ void eval_block(const EvalArgs& A) {
+  extern __shared__ __attribute__((aligned(16))) int32_t lds[];
+  const int4 T = load_record(as_const_table(A.tiles) + blockIdx.x);
+  const ScaleDev S = load_record(as_const_table(A.sd) + T.x);
+  constexpr bool kDo1 = ONLY_STEP != 2, kDo2 = ONLY_STEP != 1;
+  if constexpr (ALLOW_TREES) {
+    if (A.trees) {
+      if (S.ystep == 2)
+        eval_tile<2, HAAR, true>(A, lds, T, S);
+      else
+        eval_tile<1, HAAR, true>(A, lds, T, S);
+      return;
+    }
+  }
+  if (kDo2 && (!kDo1 || S.ystep == 2))
+    eval_tile<2, HAAR, false>(A, lds, T, S);
+  else if (kDo1)
+    eval_tile<1, HAAR, false>(A, lds, T, S);
 }
 
 #ifndef CC_SPEC_STAGES
 // One launch covers every scale: the tile's scale decides (block-uniformly) which layout it uses.
 // keep the register budget of the LDS-bound occupancy (CC_EVAL_MIN_WAVES_PER_EU wavefronts per SIMD)
 __global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(CC_EVAL_MIN_WAVES_PER_EU, 8))) void k_eval_haar(EvalArgs A) {
-  extern __shared__ __attribute__((aligned(16))) int32_t lds[];
-  const int4 T = load_record(as_const_table(A.tiles) + blockIdx.x);
-  const ScaleDev S = load_record(as_const_table(A.sd) + T.x);
-  if (A.trees) {  // rare: cascades with trees deeper than stumps (thread-per-window phases only)
-    if (S.ystep == 2)
-      eval_tile<2, true, true>(A, lds, T, S);
-    else
-      eval_tile<1, true, true>(A, lds, T, S);
-  } else if (S.ystep == 2)
-    eval_tile<2, true, false>(A, lds, T, S);
-  else
-    eval_tile<1, true, false>(A, lds, T, S);
+  eval_block<true, 0, true>(A);
 }
 
 __global__ __launch_bounds__(EVAL_THREADS) void k_eval_lbp(EvalArgs A) {
-  extern __shared__ __attribute__((aligned(16))) int32_t lds[];
-  const int4 T = load_record(as_const_table(A.tiles) + blockIdx.x);
-  const ScaleDev S = load_record(as_const_table(A.sd) + T.x);
-  if (A.trees) {
-    if (S.ystep == 2)
-      eval_tile<2, false, true>(A, lds, T, S);
-    else
-      eval_tile<1, false, true>(A, lds, T, S);
-  } else if (S.ystep == 2)
-    eval_tile<2, false, false>(A, lds, T, S);
-  else
-    eval_tile<1, false, false>(A, lds, T, S);
+  eval_block<false, 0, true>(A);
 }
 #endif
 
@@ -997,21 +996,12 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_eval_lbp(EvalArgs A) {
 #else
 #define CC_SPEC_ENTRY k_eval_spec
 #endif
-extern "C" __global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(CC_EVAL_MIN_WAVES_PER_EU, 8))) void CC_SPEC_ENTRY(EvalArgs A) {
-  extern __shared__ __attribute__((aligned(16))) int32_t lds[];
-  const int4 T = load_record(as_const_table(A.tiles) + blockIdx.x);
-  const ScaleDev S = load_record(as_const_table(A.sd) + T.x);
-  constexpr bool kDo1 = CC_ONLY_STEP != 2, kDo2 = CC_ONLY_STEP != 1;
 #ifdef CC_SPEC_LBP
-  if (kDo2 && (!kDo1 || S.ystep == 2))
-    eval_tile<2, false, false>(A, lds, T, S);
-  else if (kDo1)
-    eval_tile<1, false, false>(A, lds, T, S);
+constexpr bool kSpecHaar = false;
 #else
-  if (kDo2 && (!kDo1 || S.ystep == 2))
-    eval_tile<2, true, false>(A, lds, T, S);
-  else if (kDo1)
-    eval_tile<1, true, false>(A, lds, T, S);
+constexpr bool kSpecHaar = true;
 #endif
+extern "C" __global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(CC_EVAL_MIN_WAVES_PER_EU, 8))) void CC_SPEC_ENTRY(EvalArgs A) {
+  eval_block<kSpecHaar, CC_ONLY_STEP, false>(A);
 }
 #endif

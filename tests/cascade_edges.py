@@ -707,6 +707,28 @@ def _f_stage_ties():
     return haar_cascade(stages, 262, critical=5, pool_kinds="balanced", max_side=10, wins=windows_of(tie_frame(400, 300, 80), 24, 24))
 
 
+# ---- g. a single stage -----------------------------------------------------------------------------------------------
+# Cascades of ONE stage: the dense phase of the cascade kernel emits the candidates itself, nothing is ever queued. One per
+# feature kind and weak-classifier form, from the factories of tests/cascade_factory.py; the Haar ones are calibrated on
+# the 24 x 24 windows of the frame they run on. name -> (kind, stump cascade, factory)
+ONE_STAGE = {
+    "g_one_stage_lbp_stump": ("lbp", True, lambda cal: cf.lbp_stump_cascade(24, 24, seed=41, stage_sizes=(3,))),
+    "g_one_stage_lbp_tree": ("lbp", False, lambda cal: cf.lbp_tree_cascade(seed=31, stage_sizes=(3,))),
+    "g_one_stage_haar_tree": ("haar", False, lambda cal: cf.haar_tree_cascade(cal, seed=21, stage_sizes=(4,))),
+    "g_one_stage_tilted_stump": ("haar", True, lambda cal: cf.tilted_stump_cascade(cal, seed=11, stage_sizes=(6,))),
+}
+
+
+def one_stage_frame():
+    """200 x 120 at scale factor 1.25: 11 439 grid windows, scales of both steps, a partial tile in each direction."""
+    return frame_natural(200, 120, 5), 1.25
+
+
+def _g_cascade(name):
+    kind, _, make = ONE_STAGE[name]
+    return Built(make(windows_of(one_stage_frame()[0], 24, 24)), kind, 24, 24, 0, 1)
+
+
 # ------------------------------------------------------------------ the table
 A_NAMES = ["a_below_quarter", "a_between", "a_at_bound", "a_far_above"]
 B_NAMES = ["b_below", "b_at", "b_above"]
@@ -716,6 +738,7 @@ E_HAAR_NAMES = ["e_63_stages", "e_sizes_small", "e_sizes_large"]
 E_LBP_NAMES = list(LBP_SIZES)
 F_NAMES = ["f_node_ties", "f_node_ties_plain", "f_stage_ties", "f_lbp_ties"]
 NAMES = A_NAMES + B_NAMES + C_NAMES + D_NAMES + E_HAAR_NAMES + E_LBP_NAMES + F_NAMES
+G_NAMES = list(ONE_STAGE)  # one frame each, tests of their own: not part of NAMES
 REFUSED = "e_64_stages"  # built like e_63_stages; the detector refuses it
 
 
@@ -748,12 +771,16 @@ def built(name):
         return _f_stage_ties()
     if name == "f_lbp_ties":
         return lbp_cascade(24, 24, (4, 6, 8, 10, 12, 9), 181, step=0.125, tie_thresholds=True)
+    if name in ONE_STAGE:
+        return _g_cascade(name)
     raise KeyError(name)
 
 
 @functools.lru_cache(maxsize=None)
 def frames(name):
-    """(frame, scale factor) pairs of a cascade: at most 400 x 300, two scale factors."""
+    """(frame, scale factor) pairs of a cascade: at most 400 x 300, two scale factors (one-stage cascades: one frame)."""
+    if name in ONE_STAGE:
+        return [one_stage_frame()]
     b = built(name)
     W, H = b.W, b.H
     if name == "c_int_edge":

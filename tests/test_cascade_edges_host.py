@@ -248,6 +248,27 @@ def test_tiles_on_both_sides_of_the_wave_phase_limit(refs, name):
             assert ((t >= 1) & (t <= 23)).any() and (t > 24).any(), (name, s, sorted(t.tolist()))
 
 
+# (accepted, rejected at stage 0, candidates) the oracle finds on the one-stage inputs. The LBP rows are the figures of the
+# issue that asked for these cases; its Haar rows (7967 / 3472 / 7009 and 5793 / 5646 / 4571) came from calibration windows it
+# does not specify and that no regular grid over the frame reproduces: the Haar cascades here are calibrated on
+# ce.windows_of(frame, 24, 24), and these are their counts.
+ONE_STAGE_COUNTS = {"g_one_stage_lbp_stump": (6225, 5214, 4362), "g_one_stage_lbp_tree": (4668, 6771, 3149),
+                    "g_one_stage_haar_tree": (7735, 3704, 6753), "g_one_stage_tilted_stump": (6317, 5122, 5061)}
+
+
+@pytest.mark.parametrize("name", ce.G_NAMES)
+def test_one_stage_inputs(refs, name):
+    """One stage, 11 439 grid windows: the oracle alone finds accepted windows, windows rejected at stage 0, and fewer
+    candidates than accepted windows, so the stage-0 skip rule bites."""
+    o, (ref,) = refs(name)
+    assert o.nstages == 1 and ref.n_grid_windows == 11439 and len(ce.frames(name)) == 1
+    got = (int((ref.codes == 1).sum()), int((ref.codes == 0).sum()), len(ref.candidates))
+    assert got == ONE_STAGE_COUNTS[name], (name, got)
+    accepted, rejected, candidates = got
+    assert accepted > 0 and rejected > 0 and 0 < candidates < accepted
+    assert accepted + rejected + int((ref.codes == -1).sum()) == 11439  # -1: no variance (Haar)
+
+
 def _stage_ties(o, img, sf):
     """Windows whose stage sum equals the effective stage threshold exactly, per stage: the cascade cut after stage k accepts
     them with that sum."""

@@ -84,6 +84,17 @@ def test_table_driven_detector(refs, name):
     _same_as_oracle(_classifier(name), name, refs)
 
 
+@pytest.mark.parametrize("name", ce.G_NAMES)
+def test_single_stage_cascades(refs, name):
+    """One stage: the dense phase emits the candidates itself. Table-driven kernel, and for the stump cascades the
+    specialised one (LBP: the rolled dense loop of the module with 20-row tiles)."""
+    p = _classifier(name)
+    _same_as_oracle(p, name, refs, frames=(0,))
+    if ce.ONE_STAGE[name][1]:
+        assert p.specialize(1) == 1 and p.specialized_stages() == 1
+        _same_as_oracle(p, name, refs, frames=(0,))
+
+
 SWITCHED = ["a_below_quarter", "a_between", "a_at_bound", "e_sizes_small", "e_sizes_large"]
 
 
