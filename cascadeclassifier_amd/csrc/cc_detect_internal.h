@@ -1,6 +1,7 @@
-// Declarations shared by the detection-side translation units: cc_detect.hip (the detector), cc_front.hip (pyramid and
-// integral images), cc_negmine.hip (negative mining for training) and cc_spec.hip (the run-time specialiser). Only what
-// crosses those files lives here; everything else stays static in the file that uses it.
+// Declarations shared by the detection-side translation units: the detector (cc_detector.h and its four files), cc_front.hip
+// (pyramid and integral images), cc_negmine.hip (negative mining for training), cc_spec.hip (the run-time specialiser) and
+// cc_group.hip (ordering and grouping on the device). What only the detector's own files share is in cc_detector.h;
+// everything else stays static in the file that uses it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -105,7 +106,7 @@ inline int pix_rows(int fmt, int height) { return fmt == CC_PIX_RGB8_PLANAR ? 3 
 void launch_to_gray(hipStream_t st, int fmt, const uint8_t* src, size_t row_stride, size_t frame_stride, int w, int h, int nf,
                     uint8_t* dst, size_t dst_stride, size_t dst_frame_stride);
 
-// ---- checks shared by the entry points (cc_detect.hip) ----
+// ---- checks shared by the entry points (defined in cc_detect_api.hip) ----
 // Detection and its run-time specialisation are Haar / LBP only: nothing in the reference defines detection with a HOG
 // cascade. Every detector entry point calls this before the model reaches a kernel or a table builder (the LBP branches
 // would read lbp_rects, which a HOG model leaves empty).
@@ -126,34 +127,45 @@ bool stage_quantum(const Cascade& m, int s, double& q);
 // `at(y, x)` maps a corner inside the window to what the record stores: an LDS offset of one of the tile layouts, or
 // (y << 16 | x) for the records whose corners are read from global memory (GlobalReader). tilt_shift: distance of the
 // tilted tile behind the sum tile.
+// The two record kinds (stump, tree node) share their corner fields; the builders add thr / left / right.
+template <class R, class At>
+void fill_haar_corners(const Cascade& m, int fi, R& d, At at, int tilt_shift) {  // ofs, w, nrect of feature fi
+  d.nrect = 2;
+  for (int j = 0; j < 3; j++) {
+    const int32_t* r = &m.haar_rects[(size_t)fi * 12 + j * 4];
+    const float wt = m.haar_weights[(size_t)fi * 3 + j];
+    d.w[j] = wt;
+    // rects after the first zero weight contribute w*0 upstream (offsets stay 0): keep corner offsets equal
+    const bool used = j < 2 || wt != 0.0f;
+    if (j == 2 && wt != 0.0f) d.nrect = 3;
+    const int x = used ? r[0] : 0, y = used ? r[1] : 0, rw = used ? r[2] : 0, rh = used ? r[3] : 0;
+    if (!m.haar_tilted[fi]) {
+      d.ofs[j][0] = at(y, x);
+      d.ofs[j][1] = at(y, x + rw);
+      d.ofs[j][2] = at(y + rh, x);
+      d.ofs[j][3] = at(y + rh, x + rw);
+    } else {  // corners of the 45-degree rectangle (CV_TILTED_OFFSETS), read from the tilted tile behind the sum tile
+      d.ofs[j][0] = tilt_shift + at(y, x);
+      d.ofs[j][1] = tilt_shift + at(y + rh, x - rh);
+      d.ofs[j][2] = tilt_shift + at(y + rw, x + rw);
+      d.ofs[j][3] = tilt_shift + at(y + rw + rh, x + rw - rh);
+    }
+  }
+}
+template <class R, class At>
+void fill_lbp_cells(const Cascade& m, int fi, size_t i, R& d, At at) {  // ofs of feature fi, subset of stump / node i
+  const int32_t* r = &m.lbp_rects[(size_t)fi * 4];
+  for (int rr = 0; rr < 4; rr++)
+    for (int cc = 0; cc < 4; cc++) d.ofs[4 * rr + cc] = at(r[1] + rr * r[3], r[0] + cc * r[2]);
+  for (int j = 0; j < 8; j++) d.subset[j] = m.node_subset[i * 8 + j];
+}
 template <class At>
 void build_haar_stumps_at(const Cascade& m, std::vector<HaarStumpDev>& out, At at, int tilt_shift) {
   out.resize(m.stump_feature.size());
   for (size_t i = 0; i < out.size(); i++) {
     HaarStumpDev& d = out[i];
     std::memset(&d, 0, sizeof(d));
-    const int fi = m.stump_feature[i];
-    d.nrect = 2;
-    for (int j = 0; j < 3; j++) {
-      const int32_t* r = &m.haar_rects[(size_t)fi * 12 + j * 4];
-      const float wt = m.haar_weights[(size_t)fi * 3 + j];
-      d.w[j] = wt;
-      // rects after the first zero weight contribute w*0 upstream (offsets stay 0): keep corner offsets equal
-      const bool used = j < 2 || wt != 0.0f;
-      if (j == 2 && wt != 0.0f) d.nrect = 3;
-      const int x = used ? r[0] : 0, y = used ? r[1] : 0, rw = used ? r[2] : 0, rh = used ? r[3] : 0;
-      if (!m.haar_tilted[fi]) {
-        d.ofs[j][0] = at(y, x);
-        d.ofs[j][1] = at(y, x + rw);
-        d.ofs[j][2] = at(y + rh, x);
-        d.ofs[j][3] = at(y + rh, x + rw);
-      } else {  // corners of the 45-degree rectangle (CV_TILTED_OFFSETS), read from the tilted tile behind the sum tile
-        d.ofs[j][0] = tilt_shift + at(y, x);
-        d.ofs[j][1] = tilt_shift + at(y + rh, x - rh);
-        d.ofs[j][2] = tilt_shift + at(y + rw, x + rw);
-        d.ofs[j][3] = tilt_shift + at(y + rw + rh, x + rw - rh);
-      }
-    }
+    fill_haar_corners(m, m.stump_feature[i], d, at, tilt_shift);
     d.thr = m.stump_threshold[i];
     d.left = m.stump_left[i];
     d.right = m.stump_right[i];
@@ -171,12 +183,9 @@ void build_lbp_stumps_at(const Cascade& m, std::vector<LbpStumpDev>& out, At at)
   for (size_t i = 0; i < out.size(); i++) {
     LbpStumpDev& d = out[i];
     std::memset(&d, 0, sizeof(d));
-    const int32_t* r = &m.lbp_rects[(size_t)m.stump_feature[i] * 4];
-    for (int rr = 0; rr < 4; rr++)
-      for (int cc = 0; cc < 4; cc++) d.ofs[4 * rr + cc] = at(r[1] + rr * r[3], r[0] + cc * r[2]);
+    fill_lbp_cells(m, m.stump_feature[i], i, d, at);
     d.left = m.stump_left[i];
     d.right = m.stump_right[i];
-    for (int j = 0; j < 8; j++) d.subset[j] = m.node_subset[i * 8 + j];
   }
 }
 template <int STEP>

@@ -1,7 +1,7 @@
 // Device side of what follows k_filter_candidates: the candidates of a pass put into OpenCV's single-threaded order
 // (frame, scale, gy, gx) and cv::groupRectangles per frame, so that a detector's result can stay in device memory
 // (cc_detect_batch_to_device), plus the building block cc_group_rectangles_device. The host twins are sort_candidates /
-// group_pass (cc_detect.hip) and group_rectangles (cc_host.cpp); every step below restates theirs in the same integer,
+// group_pass (cc_detect_api.hip) and group_rectangles (cc_host.cpp); every step below restates theirs in the same integer,
 // float and double operations, and nothing here depends on the order in which threads run ("Results that
 // stay on the device").
 //

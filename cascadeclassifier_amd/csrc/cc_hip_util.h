@@ -25,11 +25,23 @@ inline hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyK
   const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
   return e != hipSuccess ? e : hipStreamSynchronize(st);
 }
-struct OwnStream {  // for entry points that have no handle to borrow a stream from
+struct OwnStream {  // for entry points that have no handle to borrow a stream from, and the detector's own streams
   hipStream_t s = nullptr;
   hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  hipError_t create(int priority) { return hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority); }
   ~OwnStream() {
     if (s) (void)hipStreamDestroy(s);
+  }
+};
+struct OwnEvent {  // move-only: a vector of them may grow
+  hipEvent_t e = nullptr;
+  OwnEvent() = default;
+  OwnEvent(OwnEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
+  OwnEvent& operator=(OwnEvent&& o) noexcept { return std::swap(e, o.e), *this; }  // o's destructor ends what this one held
+  hipError_t create() { return hipEventCreate(&e); }
+  hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&e, flags); }
+  ~OwnEvent() {
+    if (e) (void)hipEventDestroy(e);
   }
 };
 

@@ -1,4 +1,4 @@
-// HOG device code shared by the evaluator's setImage (cc_hog.hip) and the negative miner's HOG kernel (cc_detect.hip):
+// HOG device code shared by the evaluator's setImage (cc_hog.hip) and the negative miner's HOG kernel (cc_negmine.hip):
 // the per-pixel gradient and bin, the two sequential float passes that turn them into the ten integral planes, and one
 // variable's value. Both kernels call these functions, so a mined window's planes and values equal setImage's of that
 // window by construction. Every translation unit that includes this is compiled with -ffp-contract=off.

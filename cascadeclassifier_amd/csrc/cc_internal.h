@@ -106,7 +106,7 @@ void linear_exact_taps(int src, int dst, AxisTaps& t);
 void group_rectangles(std::vector<cc_rect>& rects, int group_threshold, double eps, std::vector<int>* levels = nullptr,
                       std::vector<double>* level_weights = nullptr);
 
-// ---- detector arithmetic that needs no device (cc_detect.hip; tests/cpp/test_detect_host.cpp) ---
+// ---- detector arithmetic that needs no device (cc_pass.hip, cc_tables.hip; tests/cpp/test_detect_host.cpp) ---
 // How cc_detector's pass loop cuts a batch of n_frames into passes: sizes in [1, max_batch] that sum to n_frames.
 // `pipeline_passes_set`: the pass count was given (CCAMD_PIPELINE_PASSES), so a submitted batch (`defer_last`) keeps it.
 std::vector<int> pass_sizes(int n_frames, int max_batch, int pipeline_passes, bool pipeline_passes_set, bool want_results,

@@ -1,7 +1,7 @@
 // Run-time specialisation of the cascade kernel: generates straight-line source for a cascade's first stages
 // (spec_stage_source, spec_stage_source_lbp), splices it into the text of cc_eval_kernel.inc and compiles it with hiprtc
 // (loaded on demand), caching code objects in memory and on disk (spec_build, host side only), and loads the code objects
-// as modules (spec_load). Switching a detector over to them is cc_detect.hip's (spec_install). Depends on the cascade
+// as modules (spec_load). Switching a detector over to them is cc_detect_api.hip's (spec_install). Depends on the cascade
 // model only, never on a detector.
 #include <hip/hip_runtime.h>
 

@@ -9,7 +9,7 @@ from oracle import oracle as orc
 from tests import cascade_factory as cf
 from tests.util import frame_natural
 
-# (W, H): why this window is here (cc_detect.hip / cc_eval_common.h / cc_spec.hip select code by it)
+# (W, H): why this window is here (cc_tables.hip / cc_pass.hip / cc_eval_common.h / cc_spec.hip select code by it)
 WINDOWS = [
     (20, 20),    # the stock frontal-face size: even / even, smaller than 24x24
     (19, 23),    # odd / odd: no compact squared-sum integral at step 2
