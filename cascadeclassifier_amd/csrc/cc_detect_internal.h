@@ -111,7 +111,6 @@ void launch_to_gray(hipStream_t st, int fmt, const uint8_t* src, size_t row_stri
 // cascade. Every detector entry point calls this before the model reaches a kernel or a table builder (the LBP branches
 // would read lbp_rects, which a HOG model leaves empty).
 cc_status refuse_hog(const Cascade& m, const char* who);
-cc_status ensure_device(int device);
 
 // True when, for every stage, any partial sum of leaf values is exactly representable in double: all leaves are
 // integer multiples of q = 2^(emin-24) (emin = smallest frexp exponent among the stage's nonzero leaves) and the sum of the

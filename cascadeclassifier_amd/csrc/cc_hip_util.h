@@ -18,6 +18,10 @@
 
 namespace ccamd {
 
+// Makes `device` the calling thread's device, or says why it cannot be (no device at all, index out of range). Every entry
+// point that touches the device starts with it. Defined in cc_detect_api.hip.
+cc_status ensure_device(int device);
+
 // A blocking copy that stays off the legacy stream. Plain hipMemcpy / hipMemset are refused while ANY thread of the process
 // captures a hipGraph (the detector's single-image path captures one per scale plan) and fail that thread's capture with them;
 // stream-ordered copies on a non-blocking stream are not.

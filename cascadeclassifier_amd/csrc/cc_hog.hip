@@ -16,8 +16,8 @@
 #include <memory>
 #include <mutex>
 
-#include "cc_eval_internal.h"
 #include "cc_hog_device.h"
+#include "cc_train_device.h"
 
 namespace ccamd {
 
@@ -123,10 +123,8 @@ __global__ void k_hog_eval_list(const float* __restrict__ planes, const int32_t*
   out[i] = hog_var_value(planes, sw, blocks + 4 * (vi / 36), vi % 36);
 }
 
-// CvCascadeClassifier::predict on stored samples (boost.cpp:461-477, o_cvcascadeboosttree.cpp:16-39): one thread per
-// sample walks the stages on the sample's planes; a variable's value is operator()'s (hog_var_value), an ordered split
-// goes left on `<=`, the stage sum is a double over float leaves in tree order, a stage fails iff sum < its stored
-// threshold (which already has CV_THRESHOLD_EPS subtracted). Stumps are one-node trees.
+// CvCascadeClassifier::predict on stored samples: one thread per sample walks the stages (walk_stages, cc_train_device.h)
+// on the sample's planes; a variable's value is operator()'s (hog_var_value), an ordered split goes left on `<=`.
 struct HogNodeDev {
   int32_t blk[4];  // x, y, cell w, cell h of the block
   int32_t comp;
@@ -138,13 +136,9 @@ struct HogPredictArgs {
   const float* planes;
   int sw, cols;
   const int32_t* sample_idx;  // optional
-  int n_samples, nstages;
-  const int* stage_ntrees;
-  const float* stage_thr;
-  const int* tree_root;
-  const int* tree_leaf0;
+  int n_samples;
+  WalkTables walk;
   const HogNodeDev* nodes;
-  const float* leaves;
   uint8_t* out;
 };
 
@@ -153,23 +147,10 @@ __global__ __launch_bounds__(64) void k_hog_predict(HogPredictArgs A) {
   if (s >= A.n_samples) return;
   const int si = A.sample_idx ? A.sample_idx[s] : s;
   const float* planes = A.planes + (size_t)si * A.cols * 10;
-  int t = 0;
-  uint8_t pass = 1;
-  for (int st = 0; st < A.nstages && pass; st++) {
-    double acc = 0;
-    const int nt = A.stage_ntrees[st];
-    for (int i = 0; i < nt; i++, t++) {
-      const int root = A.tree_root[t];
-      int idx = 0;
-      do {
-        const HogNodeDev& n = A.nodes[root + idx];
-        idx = hog_var_value(planes, A.sw, n.blk, n.comp) <= n.thr ? n.left : n.right;
-      } while (idx > 0);
-      acc += (double)A.leaves[A.tree_leaf0[t] - idx];
-    }
-    if (acc < (double)A.stage_thr[st]) pass = 0;
-  }
-  A.out[s] = pass;
+  A.out[s] = walk_stages(A.walk, [&](int i) {
+    const HogNodeDev& n = A.nodes[i];
+    return hog_var_value(planes, A.sw, n.blk, n.comp) <= n.thr ? n.left : n.right;
+  });
 }
 
 // Bin and magnitude of every (dx, dy) in [-255, 255]^2, pair (dx, dy) at (dy + 255) * 511 + dx + 255.
@@ -263,23 +244,11 @@ cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, i
     n.left = m.node_left[i];
     n.right = m.node_right[i];
   }
-  const std::vector<int> ntrees(m.stage_ntrees.begin(), m.stage_ntrees.end());
-  const std::vector<int> root(m.tree_first_node.begin(), m.tree_first_node.end()), leaf0(m.tree_first_leaf.begin(), m.tree_first_leaf.end());
+  // declared after `nodes`: on an early return these go first, and hipFree waits for the queued copies that read it and m
+  WalkTablesDev walk;
   DevBuf<HogNodeDev> d_nodes;
-  DevBuf<int> d_ntrees, d_root, d_leaf0;
-  DevBuf<float> d_sthr, d_leaves;
-  CC_HIP(d_nodes.ensure(nodes.size()));
-  CC_HIP(copy_sync(d_nodes.p, nodes.data(), nodes.size() * sizeof(HogNodeDev), hipMemcpyHostToDevice, e->stream));
-  CC_HIP(d_ntrees.ensure(ntrees.size()));
-  CC_HIP(copy_sync(d_ntrees.p, ntrees.data(), ntrees.size() * 4, hipMemcpyHostToDevice, e->stream));
-  CC_HIP(d_sthr.ensure(ntrees.size()));
-  CC_HIP(copy_sync(d_sthr.p, m.stage_threshold.data(), ntrees.size() * 4, hipMemcpyHostToDevice, e->stream));
-  CC_HIP(d_root.ensure(root.size()));
-  CC_HIP(copy_sync(d_root.p, root.data(), root.size() * 4, hipMemcpyHostToDevice, e->stream));
-  CC_HIP(d_leaf0.ensure(leaf0.size()));
-  CC_HIP(copy_sync(d_leaf0.p, leaf0.data(), leaf0.size() * 4, hipMemcpyHostToDevice, e->stream));
-  CC_HIP(d_leaves.ensure(m.leaves.size()));
-  CC_HIP(copy_sync(d_leaves.p, m.leaves.data(), m.leaves.size() * 4, hipMemcpyHostToDevice, e->stream));
+  CC_HIP(walk.upload(m, e->stream));
+  CC_HIP(d_nodes.upload(nodes, e->stream));
   CC_HIP(e->d_pred.ensure((size_t)ns));
   HogPredictArgs A;
   A.planes = e->d_hog.p;
@@ -287,18 +256,13 @@ cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, i
   A.cols = e->cols;
   A.sample_idx = d_idx;
   A.n_samples = ns;
-  A.nstages = (int)ntrees.size();
-  A.stage_ntrees = d_ntrees.p;
-  A.stage_thr = d_sthr.p;
-  A.tree_root = d_root.p;
-  A.tree_leaf0 = d_leaf0.p;
+  A.walk = walk.tables();
   A.nodes = d_nodes.p;
-  A.leaves = d_leaves.p;
   A.out = e->d_pred.p;
   hipLaunchKernelGGL(k_hog_predict, dim3((ns + 63) / 64), dim3(64), 0, e->stream, A);
   CC_HIP(hipGetLastError());
   CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)ns, hipMemcpyDeviceToHost, e->stream));
-  CC_HIP(hipStreamSynchronize(e->stream));  // the tables above are freed on return
+  CC_HIP(hipStreamSynchronize(e->stream));  // the tables and `nodes` above are freed on return
   return CC_OK;
 }
 
@@ -373,11 +337,7 @@ cc_status cc_eval_get_hog_sample(cc_evaluator* e, int idx, float* hist, float* n
 
 cc_status cc_debug_hog_bins(int device, int32_t* n, uint8_t* bin, float* mag) {
   if (!n || !bin || !mag) return set_error(CC_ERR_INVALID_ARG, "cc_debug_hog_bins: null output");
-  int nd = 0;
-  hipError_t err = hipGetDeviceCount(&nd);
-  if (err != hipSuccess || nd <= 0) return set_error(CC_ERR_NO_DEVICE, "no usable HIP device; this library has no CPU fallback");
-  if (device < 0 || device >= nd) return set_error(CC_ERR_INVALID_ARG, "device %d out of range (devices: %d)", device, nd);
-  CC_HIP(hipSetDevice(device));
+  if (cc_status st = ensure_device(device); st != CC_OK) return st;
   constexpr int N = 511 * 511;
   DevBuf<uint8_t> d_bin;
   DevBuf<float> d_mag;

@@ -13,6 +13,7 @@
 
 #include "cc_detect_internal.h"
 #include "cc_hog_device.h"
+#include "cc_train_device.h"
 
 namespace ccamd {
 
@@ -44,14 +45,8 @@ struct MineArgs {
   int n_levels;
   long long n_windows;
   int W0, H0, ox, oy, sx, sy;
-  int nstages;
-  const int* stage_first;
-  const int* stage_ntrees;
-  const float* stage_thr;
+  WalkTables walk;
   const MineNode* nodes;
-  const int* tree_root;
-  const int* tree_leaf0;
-  const float* leaves;
   uint8_t* pass;   // [image][n_windows]
   int nchan;       // channels per image in integ: image f starts at integ + f * nchan * chan_elems (blockIdx.y = image)
 };
@@ -79,77 +74,71 @@ __device__ __forceinline__ float mine_norm_factor(const int32_t* sum, const unsi
   return (float)sqrt((double)(area * (double)vq - (double)vs * (double)vs));
 }
 
-// Node n's decision for the window at `base` of a level with integral pitch P. Haar: value = calc / normfactor, `<=` goes left;
-// LBP: the 3x3-cell code is in the node's subset.
+// What the window kernels know of their window: its level's integrals and their pitch, its base in them, its norm factor.
+struct MineWindow {
+  const int32_t *sum, *til;
+  size_t base;
+  int P;
+  float nf;
+};
+
+// The child node n chooses for window w. Haar: value = calc / normfactor, `<=` goes left; LBP: a code in the node's subset
+// goes left. The offsets come from the node's geometry and the level's pitch.
 template <bool HAAR>
-__device__ __forceinline__ bool mine_go_left(const MineNode* n, const int32_t* sum, const int32_t* til, size_t base, int P, float nf) {
+__device__ __forceinline__ int mine_child(const MineNode& n, const MineWindow& w) {
+  const int P = w.P;
   if (HAAR) {
-    const int32_t* b = (n->tilted ? til : sum) + base;
-    float ret = 0.f;
+    const int32_t* b = (n.tilted ? w.til : w.sum) + w.base;
+    HaarFeatDev F;
+    F.tilted = n.tilted;
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-      if (j == 2 && n->w[2] == 0.0f) break;
-      const int rx = n->r[j][0], ry = n->r[j][1], rw = n->r[j][2], rh = n->r[j][3];
-      int p0, p1, p2, p3;
-      if (!n->tilted) {  // CV_SUM_OFFSETS
-        p0 = rx + P * ry;
-        p1 = rx + rw + P * ry;
-        p2 = rx + P * (ry + rh);
-        p3 = rx + rw + P * (ry + rh);
+      const int rx = n.r[j][0], ry = n.r[j][1], rw = n.r[j][2], rh = n.r[j][3];
+      F.w[j] = n.w[j];
+      if (!n.tilted) {  // CV_SUM_OFFSETS
+        F.p[j][0] = rx + P * ry;
+        F.p[j][1] = rx + rw + P * ry;
+        F.p[j][2] = rx + P * (ry + rh);
+        F.p[j][3] = rx + rw + P * (ry + rh);
       } else {  // CV_TILTED_OFFSETS
-        p0 = rx + P * ry;
-        p1 = rx - rh + P * (ry + rh);
-        p2 = rx + rw + P * (ry + rw);
-        p3 = rx + rw - rh + P * (ry + rw + rh);
+        F.p[j][0] = rx + P * ry;
+        F.p[j][1] = rx - rh + P * (ry + rh);
+        F.p[j][2] = rx + rw + P * (ry + rw);
+        F.p[j][3] = rx + rw - rh + P * (ry + rw + rh);
       }
-      const float term = n->w[j] * (float)(b[p0] - b[p1] - b[p2] + b[p3]);
-      ret = j == 0 ? term : ret + term;
     }
-    const float val = nf == 0.0f ? 0.0f : ret / nf;
-    return val <= n->thr;
+    return haar_value(haar_sum(F, [&](int o) { return b[o]; }), w.nf) <= n.thr ? n.left : n.right;
   }
-  const int32_t* b = sum + base;
-  int p[16];
+  const int32_t* b = w.sum + w.base;
+  LbpFeatDev F;
 #pragma unroll
   for (int rr = 0; rr < 4; rr++)
 #pragma unroll
-    for (int cc = 0; cc < 4; cc++) p[4 * rr + cc] = b[(n->r[0][0] + cc * n->r[0][2]) + P * (n->r[0][1] + rr * n->r[0][3])];
-  const int c = p[5] - p[6] - p[9] + p[10];
-  const int code = (p[0] - p[1] - p[4] + p[5] >= c ? 128 : 0) | (p[1] - p[2] - p[5] + p[6] >= c ? 64 : 0) |
-                   (p[2] - p[3] - p[6] + p[7] >= c ? 32 : 0) | (p[6] - p[7] - p[10] + p[11] >= c ? 16 : 0) |
-                   (p[10] - p[11] - p[14] + p[15] >= c ? 8 : 0) | (p[9] - p[10] - p[13] + p[14] >= c ? 4 : 0) |
-                   (p[8] - p[9] - p[12] + p[13] >= c ? 2 : 0) | (p[4] - p[5] - p[8] + p[9] >= c ? 1 : 0);
-  return (n->subset[code >> 5] & (1 << (code & 31))) != 0;
+    for (int cc = 0; cc < 4; cc++) F.p[4 * rr + cc] = (n.r[0][0] + cc * n.r[0][2]) + P * (n.r[0][1] + rr * n.r[0][3]);
+  const int code = lbp_code_at(F, [&](int o) { return b[o]; });
+  return (n.subset[code >> 5] & (1 << (code & 31))) != 0 ? n.left : n.right;
+}
+
+template <bool HAAR>
+__device__ __forceinline__ MineWindow mine_window_integrals(const MineArgs& A, long long i, int image) {
+  int x, y;
+  const MineLevel L = mine_window(A.levels, A.n_levels, i, A.ox, A.oy, A.sx, A.sy, x, y);
+  const int32_t* integ = A.integ + (size_t)image * A.nchan * A.chan_elems;
+  MineWindow w;
+  w.sum = integ + L.int_ofs;
+  w.til = integ + 2 * A.chan_elems + L.int_ofs;
+  w.P = L.pitchI;
+  w.base = (size_t)y * w.P + x;
+  w.nf = HAAR ? mine_norm_factor(w.sum, reinterpret_cast<const unsigned*>(integ + A.chan_elems + L.int_ofs), w.base, w.P, A.W0, A.H0) : 1.f;
+  return w;
 }
 
 template <bool HAAR>
 __global__ __launch_bounds__(256) void k_negmine_windows(MineArgs A) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= A.n_windows) return;
-  int x, y;
-  const MineLevel L = mine_window(A.levels, A.n_levels, i, A.ox, A.oy, A.sx, A.sy, x, y);
-  const int32_t* integ = A.integ + (size_t)blockIdx.y * A.nchan * A.chan_elems;
-  const int32_t* sum = integ + L.int_ofs;
-  const int32_t* til = integ + 2 * A.chan_elems + L.int_ofs;
-  const int P = L.pitchI;
-  const size_t base = (size_t)y * P + x;
-  const float nf = HAAR ? mine_norm_factor(sum, reinterpret_cast<const unsigned*>(integ + A.chan_elems + L.int_ofs), base, P, A.W0, A.H0) : 1.f;
-  uint8_t pass = 1;
-  for (int st = 0; st < A.nstages && pass; st++) {
-    double acc = 0;
-    const int first = A.stage_first[st], nt = A.stage_ntrees[st];
-    for (int t = first; t < first + nt; t++) {
-      int idx = 0;
-      const int root = A.tree_root[t];
-      do {
-        const MineNode* n = A.nodes + root + idx;
-        idx = mine_go_left<HAAR>(n, sum, til, base, P, nf) ? n->left : n->right;
-      } while (idx > 0);
-      acc += (double)A.leaves[A.tree_leaf0[t] - idx];
-    }
-    if (acc < (double)A.stage_thr[st]) pass = 0;
-  }
-  A.pass[(size_t)blockIdx.y * A.n_windows + i] = pass;
+  const MineWindow w = mine_window_integrals<HAAR>(A, i, blockIdx.y);
+  A.pass[(size_t)blockIdx.y * A.n_windows + i] = walk_stages(A.walk, [&](int n) { return mine_child<HAAR>(A.nodes[n], w); });
 }
 
 // Same stream, one WAVEFRONT per window: the 64 lanes take the stumps of a stage (stump t = first + lane, + 64, ...), their
@@ -162,28 +151,8 @@ __global__ __launch_bounds__(256) void k_negmine_wave(MineArgs A) {
   const int lane = threadIdx.x & 63;
   const long long i = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (i >= A.n_windows) return;  // wave-uniform
-  int x, y;
-  const MineLevel L = mine_window(A.levels, A.n_levels, i, A.ox, A.oy, A.sx, A.sy, x, y);
-  const int32_t* integ = A.integ + (size_t)blockIdx.y * A.nchan * A.chan_elems;
-  const int32_t* sum = integ + L.int_ofs;
-  const int32_t* til = integ + 2 * A.chan_elems + L.int_ofs;
-  const int P = L.pitchI;
-  const size_t base = (size_t)y * P + x;
-  const float nf = HAAR ? mine_norm_factor(sum, reinterpret_cast<const unsigned*>(integ + A.chan_elems + L.int_ofs), base, P, A.W0, A.H0) : 1.f;
-  uint8_t pass = 1;
-  for (int st = 0; st < A.nstages; st++) {
-    const int first = A.stage_first[st], nt = A.stage_ntrees[st];
-    double part = 0;
-    for (int t = first + lane; t < first + nt; t += 64) {
-      const MineNode* n = A.nodes + A.tree_root[t];
-      const bool go_left = mine_go_left<HAAR>(n, sum, til, base, P, nf);
-      part += (double)A.leaves[A.tree_leaf0[t] - (go_left ? n->left : n->right)];
-    }
-    if (wave_sum_f64(part) < (double)A.stage_thr[st]) {
-      pass = 0;
-      break;
-    }
-  }
+  const MineWindow w = mine_window_integrals<HAAR>(A, i, blockIdx.y);
+  const bool pass = walk_stages_wave(A.walk, lane, [&](int n) { return mine_child<HAAR>(A.nodes[n], w); });
   if (lane == 0) A.pass[(size_t)blockIdx.y * A.n_windows + i] = pass;
 }
 
@@ -222,14 +191,8 @@ struct HogMineArgs {
   int n_levels;
   long long n_windows;
   int W0, H0, ox, oy, sx, sy;
-  int nstages;
-  const int* stage_first;
-  const int* stage_ntrees;
-  const float* stage_thr;
+  WalkTables walk;
   const HogMineNode* nodes;
-  const int* tree_root;
-  const int* tree_leaf0;
-  const float* leaves;
   uint8_t* pass;  // [image][n_windows]
   int wave;       // 1: stumps of a stage across the lanes of wavefront 0 (order-independent sums); 0: one lane walks
 };
@@ -264,36 +227,15 @@ __global__ __launch_bounds__(HOG_MINE_THREADS) void k_negmine_hog(HogMineArgs A)
   __syncthreads();
   if (threadIdx.x >= 64) return;  // wavefront 0 walks the stages
   const int lane = threadIdx.x;
-  uint8_t pass = 1;
-  if (A.wave) {
-    for (int st = 0; st < A.nstages; st++) {
-      const int first = A.stage_first[st], nt = A.stage_ntrees[st];
-      double part = 0;
-      for (int t = first + lane; t < first + nt; t += 64) {
-        const HogMineNode& n = A.nodes[A.tree_root[t]];
-        part += (double)A.leaves[A.tree_leaf0[t] - (hog_mine_value(planes, n) <= n.thr ? n.left : n.right)];
-      }
-      if (wave_sum_f64(part) < (double)A.stage_thr[st]) {
-        pass = 0;
-        break;
-      }
-    }
-  } else if (lane == 0) {
-    for (int st = 0; st < A.nstages && pass; st++) {
-      double acc = 0;
-      const int first = A.stage_first[st], nt = A.stage_ntrees[st];
-      for (int t = first; t < first + nt; t++) {
-        const int root = A.tree_root[t];
-        int idx = 0;
-        do {
-          const HogMineNode& n = A.nodes[root + idx];
-          idx = hog_mine_value(planes, n) <= n.thr ? n.left : n.right;
-        } while (idx > 0);
-        acc += (double)A.leaves[A.tree_leaf0[t] - idx];
-      }
-      if (acc < (double)A.stage_thr[st]) pass = 0;
-    }
-  }
+  auto child = [&](int k) {
+    const HogMineNode& n = A.nodes[k];
+    return hog_mine_value(planes, n) <= n.thr ? n.left : n.right;
+  };
+  bool pass = true;
+  if (A.wave)
+    pass = walk_stages_wave(A.walk, lane, child);
+  else if (lane == 0)
+    pass = walk_stages(A.walk, child);
   if (lane == 0) A.pass[(size_t)blockIdx.y * A.n_windows + i] = pass;
 }
 
@@ -306,12 +248,11 @@ using namespace ccamd;
 struct cc_negminer {
   Cascade m;
   int device = 0;
-  hipStream_t stream = nullptr;
+  OwnStream stream;
+  WalkTablesDev walk;
   DevBuf<MineNode> d_nodes;
   DevBuf<HogMineNode> d_hog_nodes;  // HOG cascades (k_negmine_hog)
   size_t hog_lds = 0;               // k_negmine_hog's dynamic LDS per workgroup
-  DevBuf<int> d_stage_first, d_stage_ntrees, d_tree_root, d_tree_leaf0;
-  DevBuf<float> d_stage_thr, d_leaves;
   // per-image workspace
   DevBuf<uint8_t> d_src, d_pyr, d_pass, d_pix;
   DevBuf<int32_t> d_integ, d_hbuf, d_diag, d_tseg;
@@ -326,13 +267,8 @@ struct cc_negminer {
   } plan;
   PinnedBuf h_src;   // the images of a call, tight rows of align4(width)
   PinnedBuf h_pass;  // pass flags on their way back
-  hipStream_t copy_stream = nullptr;      // the images' way to the device, piece by piece, under the kernels of the piece before
-  std::vector<hipEvent_t> piece_landed;   // one per piece of a call (grown on demand)
-  ~cc_negminer() {
-    for (hipEvent_t e : piece_landed) (void)hipEventDestroy(e);
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  OwnStream copy_stream;               // the images' way to the device, piece by piece, under the kernels of the piece before
+  std::vector<OwnEvent> piece_landed;  // one per piece of a call (grown on demand)
 };
 
 extern "C" {
@@ -391,8 +327,8 @@ cc_status cc_negminer_create(const cc_cascade* c, int device, cc_negminer** out)
   std::unique_ptr<cc_negminer> m(new cc_negminer());
   m->m = c->m;
   m->device = device;
-  CC_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-  CC_HIP(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
+  CC_HIP(m->stream.create());
+  CC_HIP(m->copy_stream.create());
   const Cascade& M = m->m;
   const bool haar = M.feature_type == CC_FEATURE_HAAR, hog = M.feature_type == CC_FEATURE_HOG;
   if (!haar && !hog && M.feature_type != CC_FEATURE_LBP)
@@ -425,7 +361,8 @@ cc_status cc_negminer_create(const cc_cascade* c, int device, cc_negminer** out)
       n.left = M.node_left[i];
       n.right = M.node_right[i];
     }
-    CC_HIP(m->d_hog_nodes.upload(hn, m->stream));
+    CC_HIP(m->d_hog_nodes.upload(hn, m->stream.s));
+    CC_HIP(hipStreamSynchronize(m->stream.s));  // `hn` ends here
   }
   std::vector<MineNode> nodes(hog ? 0 : M.node_feature.size());
   for (size_t i = 0; i < nodes.size(); i++) {
@@ -450,16 +387,9 @@ cc_status cc_negminer_create(const cc_cascade* c, int device, cc_negminer** out)
     n.left = M.node_left[i];
     n.right = M.node_right[i];
   }
-  std::vector<int> sfirst(M.stage_first.begin(), M.stage_first.end()), sn(M.stage_ntrees.begin(), M.stage_ntrees.end());
-  std::vector<int> root(M.tree_first_node.begin(), M.tree_first_node.end()), leaf0(M.tree_first_leaf.begin(), M.tree_first_leaf.end());
-  CC_HIP(m->d_nodes.upload(nodes, m->stream));
-  CC_HIP(m->d_stage_first.upload(sfirst, m->stream));
-  CC_HIP(m->d_stage_ntrees.upload(sn, m->stream));
-  CC_HIP(m->d_stage_thr.upload(M.stage_threshold, m->stream));  // already threshold - 1e-5f (CV_THRESHOLD_EPS)
-  CC_HIP(m->d_tree_root.upload(root, m->stream));
-  CC_HIP(m->d_tree_leaf0.upload(leaf0, m->stream));
-  CC_HIP(m->d_leaves.upload(M.leaves, m->stream));
-  CC_HIP(hipStreamSynchronize(m->stream));
+  CC_HIP(m->d_nodes.upload(nodes, m->stream.s));
+  CC_HIP(m->walk.upload(M, m->stream.s));
+  CC_HIP(hipStreamSynchronize(m->stream.s));
   *out = m.release();
   return CC_OK;
 }
@@ -524,8 +454,8 @@ static cc_status mine_plan(cc_negminer* m, int width, int height, int ox, int oy
     L.pad = 0;
     wins += (long long)g[i].nx * g[i].ny;
   }
-  CC_HIP(m->d_levels.upload(lv, m->stream));
-  CC_HIP(m->front.upload(m->stream));  // synchronises: `lv` ends here
+  CC_HIP(m->d_levels.upload(lv, m->stream.s));
+  CC_HIP(m->front.upload(m->stream.s));  // synchronises: `lv` ends here
   P.wins = wins;
   P.ox = ox;
   P.oy = oy;
@@ -534,202 +464,266 @@ static cc_status mine_plan(cc_negminer* m, int width, int height, int ox, int oy
   return CC_OK;
 }
 
+// One call of mine_images: the arguments its parts share, and what mine_begin derives from them and the plan.
+struct MineCall {
+  cc_negminer* m;
+  const uint8_t* const* images;
+  int K, width, height;
+  size_t row_stride;
+  int ox, oy;
+  const char* who;
+  bool haar, tilt, hog, wave_mode;
+  int nchan, sx, sy;
+  long long wins;
+  size_t chan_elems, spitch, src_bytes;
+};
+
+// Checks and plan. *n_windows is set as soon as the plan is known, also when the capacity is too small.
+static cc_status mine_begin(MineCall& C, uint8_t* pass, int64_t cap, int64_t* n_windows, uint8_t* pixels, int64_t* keep_index, int max_keep,
+                            int* n_keep) {
+  cc_negminer* m = C.m;
+  const char* who = C.who;
+  cc_status st = mine_check(m, C.width, C.height, C.ox, C.oy, who);
+  if (st != CC_OK) return st;
+  if (!C.images || C.K < 1 || !pass || !n_windows || C.row_stride < (size_t)C.width) return set_error(CC_ERR_INVALID_ARG, "%s: bad argument", who);
+  for (int k = 0; k < C.K; k++)
+    if (!C.images[k]) return set_error(CC_ERR_INVALID_ARG, "%s: image %d is null", who, k);
+  if (pixels && (!keep_index || !n_keep || max_keep < 0)) return set_error(CC_ERR_INVALID_ARG, "%s: bad keep buffers", who);
+  st = ensure_device(m->device);
+  if (st != CC_OK) return st;
+  st = mine_plan(m, C.width, C.height, C.ox, C.oy, who);
+  if (st != CC_OK) return st;
+  const Cascade& M = m->m;
+  C.haar = M.feature_type == CC_FEATURE_HAAR;
+  C.tilt = C.haar && M.has_tilted;
+  C.hog = M.feature_type == CC_FEATURE_HOG;
+  C.wins = m->plan.wins;
+  *n_windows = C.wins;
+  if (C.wins * C.K > cap)
+    return set_error(CC_ERR_BUFFER_TOO_SMALL, "%s: %lld windows (%d images), capacity %lld", who, C.wins * C.K, C.K, (long long)cap);
+  C.nchan = C.haar ? (C.tilt ? 3 : 2) : 1;
+  C.chan_elems = m->front.L.int_frame_elems;
+  C.spitch = (size_t)align_up(C.width, 4);
+  C.src_bytes = C.spitch * (size_t)C.height;
+  C.sx = (int)(0.5F * M.win_w);
+  C.sy = (int)(0.5F * M.win_h);
+  // one wavefront per window where the parallel stage sum is exact (stumps, order-independent sums); else one thread per window
+  C.wave_mode = M.max_nodes_per_tree == 1 && stage_sums_order_independent(M);
+  return CC_OK;
+}
+
+// The per-call workspace, sized for all K images.
+static cc_status mine_workspace(const MineCall& C) {
+  cc_negminer* m = C.m;
+  const FrontLayout& FL = m->front.L;
+  const size_t K = (size_t)C.K;
+  CC_HIP(m->d_src.ensure(C.src_bytes * K));
+  CC_HIP(m->d_pyr.ensure(FL.pyr_frame_bytes * K));
+  if (!C.hog) {  // HOG windows build their planes from the levels' pixels: no integral images
+    CC_HIP(m->d_integ.ensure(C.chan_elems * (size_t)C.nchan * K));
+    CC_HIP(m->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)C.nchan * K, 4)));
+  }
+  CC_HIP(m->d_pass.ensure((size_t)std::max<long long>(C.wins * C.K, 1)));
+  CC_HIP(m->h_src.ensure(C.src_bytes * K));
+  CC_HIP(m->h_pass.ensure((size_t)std::max<long long>(C.wins * C.K, 1)));
+  if (C.tilt) {
+    CC_HIP(m->d_diag.ensure(C.chan_elems * 2 * K));
+    CC_HIP(m->d_tseg.ensure(std::max<size_t>(FL.tseg_frame_elems * K, 1)));
+  }
+  return CC_OK;
+}
+
+// Every kernel over the images [k0, k0 + n): the front-end kernels and the window kernels take the image as blockIdx.y.
+static void mine_launch_images(const MineCall& C, int k0, int n) {
+  cc_negminer* m = C.m;
+  const FrontLayout& FL = m->front.L;
+  const Cascade& M = m->m;
+  hipStream_t s = m->stream.s;
+  const long long wins = C.wins;
+  FrontIO io;
+  io.src = m->d_src.p + (size_t)k0 * C.src_bytes;
+  io.row_stride = C.spitch;
+  io.frame_stride = C.src_bytes;
+  io.pyr = m->d_pyr.p + (size_t)k0 * FL.pyr_frame_bytes;
+  if (!C.hog) {
+    io.integ = m->d_integ.p + (size_t)k0 * C.nchan * C.chan_elems;
+    io.hbuf = m->d_hbuf.p + (size_t)k0 * C.nchan * FL.h_frame_elems;
+  }
+  if (C.tilt) {
+    io.diag = m->d_diag.p + (size_t)k0 * 2 * C.chan_elems;
+    io.tseg = m->d_tseg.p + (size_t)k0 * FL.tseg_frame_elems;
+  }
+  io.nchan = C.nchan;
+  io.sq = C.haar;
+  launch_front(s, m->front, io, n, C.hog ? FRONT_RESIZE : FRONT_RESIZE | FRONT_INTEGRALS);
+  if (wins == 0) return;
+  if (C.hog) {
+    HogMineArgs H;
+    H.pyr = io.pyr;
+    H.pyr_image_bytes = FL.pyr_frame_bytes;
+    H.levels = m->d_levels.p;
+    H.n_levels = (int)FL.sd.size();
+    H.n_windows = wins;
+    H.W0 = M.win_w;
+    H.H0 = M.win_h;
+    H.ox = C.ox;
+    H.oy = C.oy;
+    H.sx = C.sx;
+    H.sy = C.sy;
+    H.walk = m->walk.tables();
+    H.nodes = m->d_hog_nodes.p;
+    H.pass = m->d_pass.p + (size_t)k0 * (size_t)wins;
+    H.wave = C.wave_mode ? 1 : 0;
+    hipLaunchKernelGGL(k_negmine_hog, dim3((unsigned)wins, n), dim3(HOG_MINE_THREADS), m->hog_lds, s, H);
+    return;
+  }
+  MineArgs B;
+  B.integ = io.integ;
+  B.chan_elems = C.chan_elems;
+  B.nchan = C.nchan;
+  B.levels = m->d_levels.p;
+  B.n_levels = (int)FL.sd.size();
+  B.n_windows = wins;
+  B.W0 = M.win_w;
+  B.H0 = M.win_h;
+  B.ox = C.ox;
+  B.oy = C.oy;
+  B.sx = C.sx;
+  B.sy = C.sy;
+  B.walk = m->walk.tables();
+  B.nodes = m->d_nodes.p;
+  B.pass = m->d_pass.p + (size_t)k0 * (size_t)wins;
+  if (C.wave_mode) {
+    const unsigned nb = (unsigned)((wins + 3) / 4);
+    if (C.haar)
+      hipLaunchKernelGGL(k_negmine_wave<true>, dim3(nb, n), dim3(256), 0, s, B);
+    else
+      hipLaunchKernelGGL(k_negmine_wave<false>, dim3(nb, n), dim3(256), 0, s, B);
+  } else {
+    const unsigned nb = (unsigned)((wins + 255) / 256);
+    if (C.haar)
+      hipLaunchKernelGGL(k_negmine_windows<true>, dim3(nb, n), dim3(256), 0, s, B);
+    else
+      hipLaunchKernelGGL(k_negmine_windows<false>, dim3(nb, n), dim3(256), 0, s, B);
+  }
+}
+
+// Pageable rows -> pinned, tight rows, then asynchronous transfers on the copy stream: the images travel in pieces of >= 8 MB;
+// a piece's copy is issued as soon as it is staged (it runs under the staging of the next piece) and its kernels are queued
+// behind it on the compute stream (they run under the next piece's copy). A Full-HD background is 2 MB for 13 584 windows:
+// the image's way to the device is most of what a call costs. Large pieces are staged by up to 4 threads.
+static cc_status mine_pieces(const MineCall& C) {
+  cc_negminer* m = C.m;
+  const char* who = C.who;
+  const uint8_t* const* images = C.images;
+  const int K = C.K, width = C.width, height = C.height;
+  const size_t row_stride = C.row_stride, spitch = C.spitch, src_bytes = C.src_bytes;
+  hipStream_t s = m->stream.s;
+  uint8_t* const h_src = static_cast<uint8_t*>(m->h_src.p);
+  auto stage = [&](int ka, int kb) {
+    for (int k = ka; k < kb; k++) {
+      uint8_t* dst = h_src + (size_t)k * src_bytes;
+      if (row_stride == spitch)
+        std::memcpy(dst, images[k], (size_t)(height - 1) * spitch + (size_t)width);
+      else
+        for (int y = 0; y < height; y++) std::memcpy(dst + (size_t)y * spitch, images[k] + (size_t)y * row_stride, (size_t)width);
+    }
+  };
+  const int per_piece = (int)std::max<size_t>(1, ((size_t)8 << 20) / std::max<size_t>(src_bytes, 1));
+  const size_t n_pieces = ((size_t)K + per_piece - 1) / per_piece;
+  while (m->piece_landed.size() < n_pieces) {
+    OwnEvent ev;
+    CC_HIP(ev.create(hipEventDisableTiming));
+    m->piece_landed.push_back(std::move(ev));
+  }
+  size_t piece = 0;
+  for (int k0 = 0; k0 < K; k0 += per_piece, piece++) {
+    const int k1 = std::min(K, k0 + per_piece), n = k1 - k0;
+    const int nt = std::min({4, n, (int)std::max<size_t>(1, ((size_t)n * src_bytes) >> 21)});
+    if (nt <= 1) {
+      stage(k0, k1);
+    } else {
+      std::vector<std::future<void>> jobs;
+      try {
+        for (int t = 1; t < nt; t++) jobs.push_back(std::async(std::launch::async, stage, k0 + (int)((long long)n * t / nt), k0 + (int)((long long)n * (t + 1) / nt)));
+        stage(k0, k0 + n / nt);
+        for (auto& j : jobs) j.get();
+      } catch (const std::exception& e) {
+        for (auto& j : jobs)
+          if (j.valid()) j.wait();
+        (void)hipStreamSynchronize(m->copy_stream.s);
+        (void)hipStreamSynchronize(s);
+        return set_error(CC_ERR_HIP, "%s: staging the images: %s", who, e.what());
+      }
+    }
+    CC_HIP(hipMemcpyAsync(m->d_src.p + (size_t)k0 * src_bytes, h_src + (size_t)k0 * src_bytes, (size_t)n * src_bytes, hipMemcpyHostToDevice,
+                          m->copy_stream.s));
+    CC_HIP(hipEventRecord(m->piece_landed[piece].e, m->copy_stream.s));
+    CC_HIP(hipStreamWaitEvent(s, m->piece_landed[piece].e, 0));
+    mine_launch_images(C, k0, n);
+  }
+  CC_HIP(hipGetLastError());
+  return CC_OK;
+}
+
+// The flags of all K images back to `pass`; the compute stream is idle afterwards.
+static cc_status mine_fetch_flags(const MineCall& C, uint8_t* pass) {
+  cc_negminer* m = C.m;
+  hipStream_t s = m->stream.s;
+  const long long wins = C.wins;
+  const int K = C.K;
+  if (wins > 0) CC_HIP(hipMemcpyAsync(m->h_pass.p, m->d_pass.p, (size_t)(wins * K), hipMemcpyDeviceToHost, s));
+  CC_HIP(hipStreamSynchronize(s));
+  if (wins > 0) std::memcpy(pass, m->h_pass.p, (size_t)(wins * K));
+  return CC_OK;
+}
+
+// The pixels of the first max_keep windows that passed, out of the ladders still on the device.
+static cc_status mine_gather_kept(const MineCall& C, const uint8_t* pass, uint8_t* pixels, int64_t* keep_index, int max_keep, int* n_keep) {
+  cc_negminer* m = C.m;
+  hipStream_t s = m->stream.s;
+  const FrontLayout& FL = m->front.L;
+  const int W0 = m->m.win_w, H0 = m->m.win_h, nl = (int)FL.sd.size(), K = C.K;
+  const long long wins = C.wins;
+  std::vector<long long> keep;
+  for (long long i = 0; i < wins * K && (int)keep.size() < max_keep; i++)
+    if (pass[i]) keep.push_back(i);
+  *n_keep = (int)keep.size();
+  if (!keep.empty()) {
+    const size_t wsz = (size_t)W0 * H0;
+    CC_HIP(m->d_keep.upload(keep, s));
+    CC_HIP(m->d_pix.ensure(keep.size() * wsz));
+    hipLaunchKernelGGL(k_negmine_gather, dim3((unsigned)keep.size()), dim3(64), 0, s, m->d_pyr.p, FL.pyr_frame_bytes, wins, m->d_levels.p, nl,
+                       m->d_keep.p, W0, H0, C.ox, C.oy, C.sx, C.sy, m->d_pix.p);
+    CC_HIP(hipGetLastError());
+    CC_HIP(hipMemcpyAsync(pixels, m->d_pix.p, keep.size() * wsz, hipMemcpyDeviceToHost, s));
+    CC_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < keep.size(); i++) keep_index[i] = keep[i];
+  }
+  return CC_OK;
+}
+
 // n_images images of one size, consumed with one offset: ONE copy to the device, one launch of every kernel over all of
 // them (the front-end kernels and the window kernels take the image as blockIdx.y, like the detector's frames), one copy back.
 static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n_images, int width, int height, size_t row_stride, int ox,
                              int oy, uint8_t* pass, int64_t cap, int64_t* n_windows, uint8_t* pixels, int64_t* keep_index, int max_keep,
                              int* n_keep, const char* who) {
-  cc_status st = mine_check(m, width, height, ox, oy, who);
-  if (st != CC_OK) return st;
-  if (!images || n_images < 1 || !pass || !n_windows || row_stride < (size_t)width) return set_error(CC_ERR_INVALID_ARG, "%s: bad argument", who);
-  for (int k = 0; k < n_images; k++)
-    if (!images[k]) return set_error(CC_ERR_INVALID_ARG, "%s: image %d is null", who, k);
-  if (pixels && (!keep_index || !n_keep || max_keep < 0)) return set_error(CC_ERR_INVALID_ARG, "%s: bad keep buffers", who);
-  st = ensure_device(m->device);
-  if (st != CC_OK) return st;
-  st = mine_plan(m, width, height, ox, oy, who);
-  if (st != CC_OK) return st;
-  const cc_negminer::Plan& P = m->plan;
-  const FrontLayout& FL = m->front.L;
-  const Cascade& M = m->m;
-  const int W0 = M.win_w, H0 = M.win_h, nl = (int)FL.sd.size(), K = n_images;
-  const bool haar = M.feature_type == CC_FEATURE_HAAR, tilt = haar && M.has_tilted, hog = M.feature_type == CC_FEATURE_HOG;
-  const long long wins = P.wins;
-  *n_windows = wins;
-  if (wins * K > cap) return set_error(CC_ERR_BUFFER_TOO_SMALL, "%s: %lld windows (%d images), capacity %lld", who, wins * K, K, (long long)cap);
-  hipStream_t s = m->stream;
-  const int nchan = haar ? (tilt ? 3 : 2) : 1;
-  const size_t chan_elems = FL.int_frame_elems, spitch = (size_t)align_up(width, 4), src_bytes = spitch * (size_t)height;
-  CC_HIP(m->d_src.ensure(src_bytes * K));
-  CC_HIP(m->d_pyr.ensure(FL.pyr_frame_bytes * K));
-  if (!hog) {  // HOG windows build their planes from the levels' pixels: no integral images
-    CC_HIP(m->d_integ.ensure(chan_elems * (size_t)nchan * K));
-    CC_HIP(m->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)nchan * K, 4)));
-  }
-  CC_HIP(m->d_pass.ensure((size_t)std::max<long long>(wins * K, 1)));
-  CC_HIP(m->h_src.ensure(src_bytes * K));
-  CC_HIP(m->h_pass.ensure((size_t)std::max<long long>(wins * K, 1)));
-  uint8_t* const h_src = static_cast<uint8_t*>(m->h_src.p);
-  MineArgs A;
-  A.integ = m->d_integ.p;
-  A.chan_elems = chan_elems;
-  A.nchan = nchan;
-  A.levels = m->d_levels.p;
-  A.n_levels = nl;
-  A.n_windows = wins;
-  A.W0 = W0;
-  A.H0 = H0;
-  A.ox = ox;
-  A.oy = oy;
-  A.sx = (int)(0.5F * W0);
-  A.sy = (int)(0.5F * H0);
-  A.nstages = (int)M.stage_ntrees.size();
-  A.stage_first = m->d_stage_first.p;
-  A.stage_ntrees = m->d_stage_ntrees.p;
-  A.stage_thr = m->d_stage_thr.p;
-  A.nodes = m->d_nodes.p;
-  A.tree_root = m->d_tree_root.p;
-  A.tree_leaf0 = m->d_tree_leaf0.p;
-  A.leaves = m->d_leaves.p;
-  A.pass = m->d_pass.p;
-  if (tilt) {
-    CC_HIP(m->d_diag.ensure(chan_elems * 2 * K));
-    CC_HIP(m->d_tseg.ensure(std::max<size_t>(FL.tseg_frame_elems * K, 1)));
-  }
-  // one wavefront per window where the parallel stage sum is exact (stumps, order-independent sums); else one thread per window
-  const bool wave_mode = M.max_nodes_per_tree == 1 && stage_sums_order_independent(M);
-  // Every kernel over the images [k0, k0 + n): the front-end kernels and the window kernels take the image as blockIdx.y.
-  auto launch_images = [&](int k0, int n) {
-    FrontIO io;
-    io.src = m->d_src.p + (size_t)k0 * src_bytes;
-    io.row_stride = spitch;
-    io.frame_stride = src_bytes;
-    io.pyr = m->d_pyr.p + (size_t)k0 * FL.pyr_frame_bytes;
-    if (!hog) {
-      io.integ = m->d_integ.p + (size_t)k0 * nchan * chan_elems;
-      io.hbuf = m->d_hbuf.p + (size_t)k0 * nchan * FL.h_frame_elems;
-    }
-    if (tilt) {
-      io.diag = m->d_diag.p + (size_t)k0 * 2 * chan_elems;
-      io.tseg = m->d_tseg.p + (size_t)k0 * FL.tseg_frame_elems;
-    }
-    io.nchan = nchan;
-    io.sq = haar;
-    launch_front(s, m->front, io, n, hog ? FRONT_RESIZE : FRONT_RESIZE | FRONT_INTEGRALS);
-    if (wins == 0) return;
-    if (hog) {
-      HogMineArgs H;
-      H.pyr = io.pyr;
-      H.pyr_image_bytes = FL.pyr_frame_bytes;
-      H.levels = A.levels;
-      H.n_levels = A.n_levels;
-      H.n_windows = wins;
-      H.W0 = W0;
-      H.H0 = H0;
-      H.ox = ox;
-      H.oy = oy;
-      H.sx = A.sx;
-      H.sy = A.sy;
-      H.nstages = A.nstages;
-      H.stage_first = A.stage_first;
-      H.stage_ntrees = A.stage_ntrees;
-      H.stage_thr = A.stage_thr;
-      H.nodes = m->d_hog_nodes.p;
-      H.tree_root = A.tree_root;
-      H.tree_leaf0 = A.tree_leaf0;
-      H.leaves = A.leaves;
-      H.pass = m->d_pass.p + (size_t)k0 * (size_t)wins;
-      H.wave = wave_mode ? 1 : 0;
-      hipLaunchKernelGGL(k_negmine_hog, dim3((unsigned)wins, n), dim3(HOG_MINE_THREADS), m->hog_lds, s, H);
-      return;
-    }
-    MineArgs B = A;
-    B.integ = io.integ;
-    B.pass = m->d_pass.p + (size_t)k0 * (size_t)wins;
-    if (wave_mode) {
-      const unsigned nb = (unsigned)((wins + 3) / 4);
-      if (haar)
-        hipLaunchKernelGGL(k_negmine_wave<true>, dim3(nb, n), dim3(256), 0, s, B);
-      else
-        hipLaunchKernelGGL(k_negmine_wave<false>, dim3(nb, n), dim3(256), 0, s, B);
-    } else {
-      const unsigned nb = (unsigned)((wins + 255) / 256);
-      if (haar)
-        hipLaunchKernelGGL(k_negmine_windows<true>, dim3(nb, n), dim3(256), 0, s, B);
-      else
-        hipLaunchKernelGGL(k_negmine_windows<false>, dim3(nb, n), dim3(256), 0, s, B);
-    }
-  };
-  // Pageable rows -> pinned, tight rows, then asynchronous transfers on the copy stream: the images travel in pieces of >= 8 MB;
-  // a piece's copy is issued as soon as it is staged (it runs under the staging of the next piece) and its kernels are queued
-  // behind it on the compute stream (they run under the next piece's copy). A Full-HD background is 2 MB for 13 584 windows:
-  // the image's way to the device is most of what a call costs. Large pieces are staged by up to 4 threads.
-  {
-    auto stage = [&](int ka, int kb) {
-      for (int k = ka; k < kb; k++) {
-        uint8_t* dst = h_src + (size_t)k * src_bytes;
-        if (row_stride == spitch)
-          std::memcpy(dst, images[k], (size_t)(height - 1) * spitch + (size_t)width);
-        else
-          for (int y = 0; y < height; y++) std::memcpy(dst + (size_t)y * spitch, images[k] + (size_t)y * row_stride, (size_t)width);
-      }
-    };
-    const int per_piece = (int)std::max<size_t>(1, ((size_t)8 << 20) / std::max<size_t>(src_bytes, 1));
-    const size_t n_pieces = ((size_t)K + per_piece - 1) / per_piece;
-    while (m->piece_landed.size() < n_pieces) {
-      hipEvent_t ev = nullptr;
-      CC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      m->piece_landed.push_back(ev);
-    }
-    size_t piece = 0;
-    for (int k0 = 0; k0 < K; k0 += per_piece, piece++) {
-      const int k1 = std::min(K, k0 + per_piece), n = k1 - k0;
-      const int nt = std::min({4, n, (int)std::max<size_t>(1, ((size_t)n * src_bytes) >> 21)});
-      if (nt <= 1) {
-        stage(k0, k1);
-      } else {
-        std::vector<std::future<void>> jobs;
-        try {
-          for (int t = 1; t < nt; t++) jobs.push_back(std::async(std::launch::async, stage, k0 + (int)((long long)n * t / nt), k0 + (int)((long long)n * (t + 1) / nt)));
-          stage(k0, k0 + n / nt);
-          for (auto& j : jobs) j.get();
-        } catch (const std::exception& e) {
-          for (auto& j : jobs)
-            if (j.valid()) j.wait();
-          (void)hipStreamSynchronize(m->copy_stream);
-          (void)hipStreamSynchronize(s);
-          return set_error(CC_ERR_HIP, "%s: staging the images: %s", who, e.what());
-        }
-      }
-      CC_HIP(hipMemcpyAsync(m->d_src.p + (size_t)k0 * src_bytes, h_src + (size_t)k0 * src_bytes, (size_t)n * src_bytes, hipMemcpyHostToDevice,
-                            m->copy_stream));
-      CC_HIP(hipEventRecord(m->piece_landed[piece], m->copy_stream));
-      CC_HIP(hipStreamWaitEvent(s, m->piece_landed[piece], 0));
-      launch_images(k0, n);
-    }
-  }
-  CC_HIP(hipGetLastError());
-  if (wins > 0) CC_HIP(hipMemcpyAsync(m->h_pass.p, m->d_pass.p, (size_t)(wins * K), hipMemcpyDeviceToHost, s));
-  CC_HIP(hipStreamSynchronize(s));
-  if (wins > 0) std::memcpy(pass, m->h_pass.p, (size_t)(wins * K));
-  if (pixels) {
-    std::vector<long long> keep;
-    for (long long i = 0; i < wins * K && (int)keep.size() < max_keep; i++)
-      if (pass[i]) keep.push_back(i);
-    *n_keep = (int)keep.size();
-    if (!keep.empty()) {
-      const size_t wsz = (size_t)W0 * H0;
-      CC_HIP(m->d_keep.upload(keep, s));
-      CC_HIP(m->d_pix.ensure(keep.size() * wsz));
-      hipLaunchKernelGGL(k_negmine_gather, dim3((unsigned)keep.size()), dim3(64), 0, s, m->d_pyr.p, FL.pyr_frame_bytes, wins, m->d_levels.p, nl,
-                         m->d_keep.p, W0, H0, ox, oy, A.sx, A.sy, m->d_pix.p);
-      CC_HIP(hipGetLastError());
-      CC_HIP(hipMemcpyAsync(pixels, m->d_pix.p, keep.size() * wsz, hipMemcpyDeviceToHost, s));
-      CC_HIP(hipStreamSynchronize(s));
-      for (size_t i = 0; i < keep.size(); i++) keep_index[i] = keep[i];
-    }
-  }
-  return CC_OK;
+  MineCall C{};
+  C.m = m;
+  C.images = images;
+  C.K = n_images;
+  C.width = width;
+  C.height = height;
+  C.row_stride = row_stride;
+  C.ox = ox;
+  C.oy = oy;
+  C.who = who;
+  cc_status st = mine_begin(C, pass, cap, n_windows, pixels, keep_index, max_keep, n_keep);
+  if (st == CC_OK) st = mine_workspace(C);
+  if (st == CC_OK) st = mine_pieces(C);
+  if (st == CC_OK) st = mine_fetch_flags(C, pass);
+  if (st == CC_OK && pixels) st = mine_gather_kept(C, pass, pixels, keep_index, max_keep, n_keep);
+  return st;
 }
 
 cc_status cc_negminer_run(cc_negminer* m, const uint8_t* gray, int width, int height, size_t row_stride, int ox, int oy, uint8_t* pass,

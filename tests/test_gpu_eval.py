@@ -189,24 +189,62 @@ def test_haar_basic_on_barcode_samples(repo_root):  # 75x32 window: 2 790 554 fe
         assert (g.view(np.uint32) == o.view(np.uint32)).all()
 
 
-@pytest.mark.parametrize("which", ["haar", "lbp"])
-def test_training_side_cascade_predict(haar_xml, lbp_xml, which):
-    """CvCascadeClassifier::predict over stored samples (negative-mining inner loop, cascadeclassifier.cpp:297-357)."""
-    xml = haar_xml if which == "haar" else lbp_xml
+def _template_samples(xml):
+    """40 noisy copies of the face template, 160 of _samples, the template itself."""
     tm = np.load(os.path.join(os.path.dirname(xml), "face_template_24x24.npy"))
     rng = np.random.default_rng(5)
     near = np.clip(tm[None].astype(np.float64) + rng.normal(0, 6, (40, 24, 24)), 0, 255).astype(np.uint8)
-    imgs = np.concatenate([near, _samples(160, 6), tm[None]])
+    return np.concatenate([near, _samples(160, 6), tm[None]])
+
+
+@pytest.mark.parametrize("which", ["haar", "lbp", "haar_tilted_stumps"])
+def test_training_side_cascade_predict(tmp_path, haar_xml, lbp_xml, which):
+    """CvCascadeClassifier::predict over stored samples (negative-mining inner loop, cascadeclassifier.cpp:297-357).
+    haar_tilted_stumps: stumps on tilted features, which the bundled cascades do not have."""
+    tilted = which == "haar_tilted_stumps"
+    if tilted:
+        from tests import cascade_factory as cf
+        from tests.util import frame_natural
+        img = frame_natural(320, 240, 3)
+        wins = np.stack([img[y:y + 24, x:x + 24] for y in range(0, 200, 9) for x in range(0, 280, 11)])
+        xml = os.path.join(str(tmp_path), "c.xml")
+        open(xml, "w").write(cf.tilted_stump_cascade(wins))
+        imgs = wins[:300]
+    else:
+        xml = haar_xml if which == "haar" else lbp_xml
+        imgs = _template_samples(xml)
     c = cc.CascadeClassifier(xml)
     o = orc.load_cascade_xml(xml)
-    e = _mk(ev.HAAR if which == "haar" else ev.LBP, ev.BASIC, len(imgs))
+    e = _mk(ev.LBP if which == "lbp" else ev.HAAR, ev.ALL if tilted else ev.BASIC, len(imgs))
     e.setImages(imgs)
     got = e.predict_cascade(c)
-    s, t, nf = orc.set_images(imgs, want_norm=(which == "haar"))
+    s, t, nf = orc.set_images(imgs, want_tilted=tilted, want_norm=(which != "lbp"))
     want = np.array([orc.train_predict(o, s, t, nf, i, 24, 24) for i in range(len(imgs))], np.uint8)
     assert (got == want).all()
     if which == "haar":
-        assert got[-1] == 1 and 0 < got.sum() < len(imgs)
+        assert got[-1] == 1
+    if which != "lbp":
+        assert 0 < got.sum() < len(imgs)
+
+
+@pytest.mark.parametrize("which", ["haar", "lbp"])
+def test_training_side_predict_through_a_gather(haar_xml, lbp_xml, which):
+    """predict_cascade(sample_idx = k entries of a permutation) is the full result at those entries: one sample, a last
+    block that is not full, and more than one block."""
+    xml = haar_xml if which == "haar" else lbp_xml
+    imgs = _template_samples(xml)
+    c = cc.CascadeClassifier(xml)
+    e = _mk(ev.HAAR if which == "haar" else ev.LBP, ev.BASIC, len(imgs))
+    e.setImages(imgs)
+    full = e.predict_cascade(c)
+    perm = np.random.default_rng(8).permutation(len(imgs)).astype(np.int32)
+    assert (perm != np.arange(len(imgs))).any()
+    for k in (1, 63, 70, 200):
+        assert k < len(imgs)
+        got = e.predict_cascade(c, sample_idx=perm[:k])
+        assert got.shape == (k,) and (got == full[perm[:k]]).all(), k
+    if which == "haar":
+        assert 0 < full[perm[:70]].sum() < 70  # the gathered results are not all alike
 
 
 @pytest.mark.parametrize("which", ["haar", "haar_tilted", "lbp"])

@@ -2,7 +2,6 @@
 (NegReader::get + setImage + CvCascadeClassifier::predict; imagestorage.cpp:57-126, cascadeclassifier.cpp:329-357):
 identical pass flags for every window of the reader's stream, identical pixels for the accepted windows."""
 import os
-import xml.etree.ElementTree as ET
 
 import numpy as np
 import pytest
@@ -11,18 +10,7 @@ import cascadeclassifier_amd as cc
 from oracle import oracle as orc
 from tests import cascade_factory as cf
 from tests.util import frame_natural, frame_uniform
-
-
-def _truncated(path, n, tmp):
-    tree = ET.parse(path)
-    casc = list(tree.getroot())[0]
-    stages = casc.find("stages")
-    for s in [s for s in stages if s.tag == "_"][n:]:
-        stages.remove(s)
-    casc.find("stageNum").text = str(n)
-    out = os.path.join(tmp, f"trunc{n}.xml")
-    tree.write(out)
-    return out
+from tests.util import truncated_cascade as _truncated
 
 
 def _reference_negative():  # test_integration.cpp:59-64
@@ -40,9 +28,20 @@ def test_plan_matches_reader_stream_length(haar_xml):
         assert m.plan(w, h, ox, oy)["n_windows"] == len(flags)
 
 
+def test_haar9_takes_the_wave_walk(tmp_path, haar_xml):
+    """CPU only. The bundled Haar cascade cut to 9 stages is a stump cascade whose stage sums are exact in any order (the
+    miner's condition for one wavefront per window), and its last stages hold more than 64 stumps, so lanes of the wave
+    walk take a second stump; haar3 and haar6 stop short of that."""
+    from tests import cascade_edges as ce
+    sizes = {n: [sl.stop - sl.start for sl in ce.stage_slices(orc.load_cascade_xml(_truncated(haar_xml, n, str(tmp_path))))] for n in (6, 9)}
+    assert max(sizes[6]) <= 64 < max(sizes[9]) and len(sizes[9]) == 9
+    assert ce.order_independent(orc.load_cascade_xml(_truncated(haar_xml, 9, str(tmp_path))), 1)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["haar3", "haar6", "lbp4", "lbp_full", "haar_tilted", "haar_trees", "lbp_trees"])
+@pytest.mark.parametrize("kind", ["haar3", "haar6", "haar9", "lbp4", "lbp_full", "haar_tilted", "haar_trees", "lbp_trees"])
 def test_negative_mining_matches_reader_loop(tmp_path, haar_xml, lbp_xml, kind):
+    """haar9: stages of more than 64 stumps, the second round of lanes of the wave walk (test_haar9_takes_the_wave_walk)."""
     tmp = str(tmp_path)
     calib = frame_natural(320, 240, 3)
     wins = np.stack([calib[y:y + 24, x:x + 24] for y in range(0, 200, 9) for x in range(0, 280, 11)])
@@ -72,6 +71,28 @@ def test_negative_mining_matches_reader_loop(tmp_path, haar_xml, lbp_xml, kind):
         total_pass += int(want_f.sum())
     if kind not in ("lbp_full",):
         assert total_pass > 0
+
+
+@pytest.mark.gpu
+def test_haar9_through_training_side_predict(tmp_path, haar_xml):
+    """The cascade that takes the miner's wave walk, through the evaluator's serial walk on stored samples: both walks are
+    held to the oracle on the same cascade."""
+    from cascadeclassifier_amd import evaluator as ev
+    path = _truncated(haar_xml, 9, str(tmp_path))
+    tm = np.load(os.path.join(os.path.dirname(haar_xml), "face_template_24x24.npy"))
+    rng = np.random.default_rng(5)
+    near = np.clip(tm[None].astype(np.float64) + rng.normal(0, 6, (60, 24, 24)), 0, 255).astype(np.uint8)
+    calib = frame_natural(320, 240, 3)
+    wins = np.stack([calib[y:y + 24, x:x + 24] for y in range(0, 200, 9) for x in range(0, 280, 11)])
+    imgs = np.concatenate([near, wins[:240]])
+    e = cc.CvFeatureEvaluator.create(ev.HAAR)
+    e.init(cc.CvFeatureParams(ev.HAAR, ev.BASIC), len(imgs), (24, 24))
+    e.setImages(imgs)
+    got = e.predict_cascade(cc.CascadeClassifier(path))
+    o = orc.load_cascade_xml(path)
+    s, t, nf = orc.set_images(imgs)
+    want = np.array([orc.train_predict(o, s, t, nf, i, 24, 24) for i in range(len(imgs))], np.uint8)
+    assert (got == want).all() and 0 < want.sum() < len(imgs)
 
 
 @pytest.mark.gpu

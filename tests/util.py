@@ -16,6 +16,21 @@ def read_vec(path, w=75, h=32):
     return out
 
 
+def truncated_cascade(path, n, tmp):
+    """Writes the cascade XML at `path` cut to its first n stages into directory `tmp`; returns the new file's path."""
+    import os
+    import xml.etree.ElementTree as ET
+    tree = ET.parse(path)
+    casc = list(tree.getroot())[0]
+    stages = casc.find("stages")
+    for s in [s for s in stages if s.tag == "_"][n:]:
+        stages.remove(s)
+    casc.find("stageNum").text = str(n)
+    out = os.path.join(tmp, f"trunc{n}.xml")
+    tree.write(out)
+    return out
+
+
 def frame_uniform(w, h, seed):
     """Distribution (i): i.i.d. uniform [0,255]."""
     return np.random.default_rng(seed).integers(0, 256, (h, w), dtype=np.uint8)
