@@ -158,6 +158,8 @@ static EvalArgs eval_args(const cc_detector* d, const Plan* P, int slot, int nch
   A.stumps2 = haar ? (const void*)d->d_haar2.p : (const void*)d->d_lbp2.p;
   A.wstumps1 = d->d_haar1w.p ? (const void*)d->d_haar1w.p : A.stumps1;
   A.wstumps2 = d->d_haar2w.p ? (const void*)d->d_haar2w.p : A.stumps2;
+  A.wave_q = d->d_wave_q.p;
+  A.wave_thr_q = d->d_wave_thr_q.p;
   A.gstumps = haar ? (const void*)d->d_haar_g.p : (const void*)d->d_lbp_g.p;
   A.lbp16_all = d->lbp16_all;
   if (!haar && d->d_lbp16.p) A.wstumps2 = d->d_lbp16.p;  // LBP wave phase of kernels with 16-bit tiles

@@ -132,6 +132,12 @@ struct cc_detector {
   int split_stumps = 0;
   DevBuf<HaarStumpDev> d_haar1, d_haar2;
   DevBuf<HaarStumpDev> d_haar1w, d_haar2w;  // the same stumps dealt to lanes for the wave phase (bank-aware order)
+  // Integer form of the wave phase's stage sums (wave_int_tables; CCAMD_WAVE_INT=0: no stage has one). The leaf words of
+  // d_haar1w / d_haar2w hold int32 multiples of the quantum in the stages where wave_int.q is not 0.
+  int wave_int_enabled = 1;
+  WaveIntTables wave_int;
+  DevBuf<double> d_wave_q;
+  DevBuf<int> d_wave_thr_q;
   DevBuf<HaarStumpDev> d_haar_g;            // corners as window coordinates (GlobalReader; kernels with 16-bit tiles)
   DevBuf<LbpStumpDev> d_lbp_g, d_lbp16;      // LBP: window coordinates (GlobalReader) / 16-bit STEP-2 tile offsets (LBP wave phase)
   int lbp16_all = 0;                        // every LBP cell of the cascade sums below 2^16

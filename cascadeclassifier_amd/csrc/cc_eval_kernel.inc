@@ -125,7 +125,12 @@ struct EvalArgs {
   const void* stumps2;
   const void* wstumps1;  // Haar wave phase: per-stage reordered copies (NULL = use stumps1/2)
   const void* wstumps2;
-  const void* gstumps;   // the stump table with corners as (y << 16 | x) inside the window (GlobalReader; 16-bit tiles)
+  // Haar wave phase, per stage: wave_q[s] != 0 = the stage has an integer form. Its records in wstumps1/2 then carry the
+  // leaves as int32 multiples of the quantum wave_q[s] (a power of two) in their leaf words, every stage sum is such a
+  // multiple too (stage_quantum on the host), and `sum >= stage_thr[s]` is `multiple >= wave_thr_q[s]`. 0 = float leaves, sums in double.
+  const double* wave_q;
+  const int* wave_thr_q;
+  const void* gstumps;  // the stump table with corners as (y << 16 | x) inside the window (GlobalReader; 16-bit tiles)
   int lbp16_all;         // LBP: every cell of the cascade sums below 2^16 and wstumps2 holds 16-bit-tile offsets (LBP wave phase)
   int trees;            // cascade has trees deeper than stumps: node tables below, no stump tables
   const void* nodes1;
@@ -165,7 +170,7 @@ struct GlobalReader {
   __device__ __forceinline__ int operator()(int p) const { return g[org + (unsigned)((p >> 16) * pitch + (p & 0xffff))]; }
 };
 template <class R>
-__device__ __forceinline__ double stump_vote(const R& rd, const HaarStumpDev& sp, float vnf) {
+__device__ __forceinline__ bool stump_goes_left(const R& rd, const HaarStumpDev& sp, float vnf) {
   const int r0 = rd(sp.ofs[0][0]) - rd(sp.ofs[0][1]) - rd(sp.ofs[0][2]) + rd(sp.ofs[0][3]);
   const int r1 = rd(sp.ofs[1][0]) - rd(sp.ofs[1][1]) - rd(sp.ofs[1][2]) + rd(sp.ofs[1][3]);
   float v = sp.w[0] * (float)r0 + sp.w[1] * (float)r1;
@@ -174,7 +179,21 @@ __device__ __forceinline__ double stump_vote(const R& rd, const HaarStumpDev& sp
     v += sp.w[2] * (float)r2;
   }
   v *= vnf;
-  return (double)(v < sp.thr ? sp.left : sp.right);
+  return v < sp.thr;
+}
+template <class R>
+__device__ __forceinline__ double stump_vote(const R& rd, const HaarStumpDev& sp, float vnf) {
+  return (double)(stump_goes_left(rd, sp, vnf) ? sp.left : sp.right);
+}
+// The vote as the accumulator type of a wave-phase stage takes it. double: the leaf value. int: the record is one of the
+// wave phase's own copies whose stage has an integer form, and its leaf words hold the leaves in units of the stage's
+// quantum as int32 (EvalArgs::wave_q); they are picked as words, no float operation ever sees them.
+template <class Acc, class R>
+__device__ __forceinline__ Acc stump_vote_as(const R& rd, const HaarStumpDev& sp, float vnf) {
+  if constexpr (sizeof(Acc) == sizeof(int))
+    return stump_goes_left(rd, sp, vnf) ? __float_as_int(sp.left) : __float_as_int(sp.right);
+  else
+    return stump_vote(rd, sp, vnf);
 }
 template <class R>
 __device__ __forceinline__ double stump_vote(const R& rd, const HaarStumpDev CC_CONST* spp, float vnf) {
@@ -279,6 +298,11 @@ __device__ __forceinline__ int wave_sum_u32(int v) {
   v += dpp_i32<0x143, 0xC>(v);
   return __builtin_amdgcn_readlane(v, 63);
 }
+// The sum of a wave-phase stage's votes over the 64 lanes, by accumulator type. The int ladder is as good for signed
+// terms (two's complement; the host guarantees no partial sum leaves int32): each step is ONE add that carries the DPP
+// modifier, where a step of the double ladder is two DPP moves and a double add.
+__device__ __forceinline__ int wave_total(int v) { return wave_sum_u32(v); }
+__device__ __forceinline__ double wave_total(double v) { return wave_sum_f64(v); }
 
 // (float)(1.0 / sqrt(nf)) -- setWindow's varianceNormFactor (SURVEY.md A.4) -- for nf > 0 (an integer-valued double: area *
 // valsqsum - valsum^2), bit for bit, without the two correctly rounded double operations (~35 instructions: the dense
@@ -379,6 +403,8 @@ struct EvalTile {
   const int CC_CONST* const stage_ntrees = as_const_table(A.stage_ntrees);
   const float CC_CONST* const stage_thr = as_const_table(A.stage_thr);
   const int CC_CONST* const group_first = as_const_table(A.group_first);
+  const double CC_CONST* const wave_q = as_const_table(A.wave_q);
+  const int CC_CONST* const wave_thr_q = as_const_table(A.wave_thr_q);
   const bool dbg = A.dbg_codes != nullptr && frame == 0;
 
   __device__ __forceinline__ EvalTile(const EvalArgs& A_, int32_t* lds_, const int4 T_, const ScaleDev& S_) : A(A_), lds(lds_), T(T_), S(S_) {}
@@ -811,6 +837,31 @@ struct EvalTile {
   // j's record once per stage (a per-lane 64-byte global load, the slow part) and keeps it in registers while the
   // wavefront's windows are evaluated against it one after the other. Lane k carries the stage sum of the wavefront's
   // k-th window.
+  // A stage's sum is formed in one of two arithmetic forms, chosen per stage (wave-uniform) by the host's table wave_q: in
+  // int32 multiples of the stage's quantum where the host has proved that every subset sum of the stage's votes is one
+  // (stage_quantum) -- an integer vote is a select between two record words, and the 64 votes meet in six DPP adds -- and
+  // in double otherwise. Either is the exact real sum of the votes, so (double)multiple * quantum IS the double sum.
+  // wave_stage returns lane k's window's sum in the accumulator's units. The votes are reduced once per chunk of 64 stumps:
+  // keeping a share's partial sums in registers over the chunks (one reduction per window and stage, the windows walked by an
+  // unrolled loop) was measured slower, profiles/EXPERIMENTS.md 3.19.
+  template <class Acc>
+  __device__ __forceinline__ Acc wave_stage(const Stump* wstumps, int s2, unsigned long long alive, int my_id) const {
+    const int first = stage_first[s2], nt = stage_ntrees[s2];
+    Acc tot = 0;
+    for (int c = 0; c < nt; c += 64) {
+      const int j = c + lane;
+      const Stump rec = wstumps[first + min(j, nt - 1)];
+      for (unsigned long long m = alive; m; m &= m - 1ull) {
+        const int k = __builtin_ctzll(m);
+        const int id = __builtin_amdgcn_readlane(my_id, k);
+        const float vnf = s_vnf[vnf_slot(id)];
+        const Acc part = j < nt ? stump_vote_as<Acc>(table_reader(id), rec, vnf) : Acc(0);
+        const Acc total = wave_total(part);
+        if (lane == k) tot += total;
+      }
+    }
+    return tot;
+  }
   __device__ __forceinline__ void wave_phase_haar(const QueueState& h) const {
     const int st = h.st;
     const Stump* wstumps = reinterpret_cast<const Stump*>(G16 ? A.gstumps : STEP == 2 ? A.wstumps2 : A.wstumps1);
@@ -819,31 +870,28 @@ struct EvalTile {
     unsigned long long alive = w.alive;
     const bool w_stamps = st + 2 < 30;  // stamp slots 30.. are free then: 30 = windows collected, 31 + i = i-th wave-phase stage done
     if (w_stamps) stamp(30);
-    double tot = 0., last = 0.;
+    double last = 0.;
     int rej = 0;
     int s2 = st;
     for (; s2 < A.nstages && alive; s2++) {
       if (A.stop_after >= 0 && s2 > A.stop_after) break;
-      const int first = stage_first[s2], nt = stage_ntrees[s2];
-      for (int c = 0; c < nt; c += 64) {
-        const int j = c + lane;
-        const Stump rec = wstumps[first + min(j, nt - 1)];
-        for (unsigned long long m = alive; m; m &= m - 1ull) {
-          const int k = __builtin_ctzll(m);
-          const int id = __builtin_amdgcn_readlane(my_id, k);
-          const float vnf = s_vnf[vnf_slot(id)];
-          const double part = j < nt ? stump_vote(table_reader(id), rec, vnf) : 0.;
-          const double total = wave_sum_f64(part);
-          if (lane == k) tot += total;
-        }
+      const double q = G16 ? 0. : wave_q[s2];  // (kernels with 16-bit tiles read gstumps here, which other phases read too: float leaves)
+      double tot;
+      bool at_least_thr;
+      if (q != 0.) {
+        const int n = wave_stage<int>(wstumps, s2, alive, my_id);
+        tot = (double)n * q;
+        at_least_thr = n >= wave_thr_q[s2];
+      } else {
+        tot = wave_stage<double>(wstumps, s2, alive, my_id);
+        at_least_thr = !(tot < (double)stage_thr[s2]);
       }
       const bool mine = (alive >> lane) & 1ull;
-      const bool pass = mine && !(tot < (double)stage_thr[s2]);
+      const bool pass = mine && at_least_thr;
       if (mine) {
         last = tot;
         if (!pass) rej = s2;
       }
-      tot = 0.;
       alive = __ballot(pass);
       if (w_stamps && s2 - st < 8) stamp(31 + s2 - st);
     }

@@ -226,6 +226,33 @@ bool stage_quantum(const Cascade& m, int s, double& q) {
   return mag / q < 2147483647.0;
 }
 
+// Integer form of the Haar wave phase's stage sums (WaveIntTables, cc_detect_internal.h). With x = threshold / q (exact: q
+// is a power of two), an integer n has n * q >= threshold exactly when n >= ceil(x). A reachable n has |n| <= 2^31 - 2
+// (stage_quantum), so a threshold beyond either end saturates to the int32 limit that always passes / never does.
+WaveIntTables wave_int_tables(const Cascade& m, bool enabled) {
+  const size_t ns = m.stage_ntrees.size();
+  WaveIntTables t;
+  t.q.assign(ns, 0.0);
+  t.thr_q.assign(ns, 0);
+  t.left_q.assign(m.stump_left.size(), 0);
+  t.right_q.assign(m.stump_left.size(), 0);
+  if (!enabled || m.feature_type != CC_FEATURE_HAAR || m.max_nodes_per_tree != 1 || !stage_sums_order_independent(m, 1.0)) return t;
+  for (size_t s = 0; s < ns; s++) {
+    double q;
+    const double thr = (double)m.stage_threshold[s];
+    if (std::isnan(thr) || !stage_quantum(m, (int)s, q)) continue;  // (a NaN threshold passes every sum: left to the double form)
+    const double x = std::ceil(thr / q);
+    t.q[s] = q;
+    t.thr_q[s] = x >= 2147483647.0 ? INT32_MAX : x <= -2147483648.0 ? INT32_MIN : (int32_t)x;
+    for (int i = 0; i < m.stage_ntrees[s]; i++) {
+      const size_t k = (size_t)m.stage_first[s] + i;
+      t.left_q[k] = (int32_t)((double)m.stump_left[k] / q);  // exact, and below 2^31 - 1 in magnitude (stage_quantum)
+      t.right_q[k] = (int32_t)((double)m.stump_right[k] / q);
+    }
+  }
+  return t;
+}
+
 // cv::groupRectangles. Classes are the connected components of the SimilarRects graph, labelled in
 // order of first appearance, which is what cv::partition yields.
 void group_rectangles(std::vector<cc_rect>& rects, int group_threshold, double eps, std::vector<int>* levels,

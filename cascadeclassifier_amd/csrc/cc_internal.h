@@ -119,6 +119,18 @@ std::vector<int> pass_sizes(int n_frames, int max_batch, int pipeline_passes, bo
 void stage_groups(const std::vector<int32_t>& stage_ntrees, int from, int budget, int dense_stage, std::vector<int>& group_first,
                   int& dense_from);
 
+// Integer form of the stage sums in the Haar wave phase (cc_eval_kernel.inc: wave_phase_haar), per stage of a Haar stump
+// cascade whose stage sums are order-independent: where stage_quantum holds (and the threshold is a number), q[s] is the
+// stage's quantum, left_q / right_q its leaves in units of q[s] (exact), and thr_q[s] the smallest int32 n with
+// n * q[s] >= stage_threshold[s], saturated; the stage sum n * q[s] of any window passes exactly when n >= thr_q[s].
+// Elsewhere q[s] = 0 and the stage has no integer form (also everywhere when !enabled, or for any other cascade).
+struct WaveIntTables {
+  std::vector<double> q;
+  std::vector<int32_t> thr_q;
+  std::vector<int32_t> left_q, right_q;  // per stump, in the cascade's stump order
+};
+WaveIntTables wave_int_tables(const Cascade& m, bool enabled);
+
 // ---- catalogs (training side) -------------------------------------------------------------------
 void haar_catalog(int W, int H, int mode, std::vector<HaarFeature>& out);
 void lbp_catalog(int W, int H, std::vector<int32_t>& rects);

@@ -75,6 +75,24 @@ static std::vector<HaarStumpDev> schedule_for_wave_phase(const Cascade& m, const
   return out;
 }
 
+// The wave phase's copy of the stump table, stages with an integer form (WaveIntTables): the two leaf words of a record carry
+// the leaves as int32 multiples of the stage's quantum. The copy is read by the wave phase only; `pad` is the stump's index.
+static void put_integer_leaves(const Cascade& m, const WaveIntTables& t, std::vector<HaarStumpDev>& w) {
+  for (size_t s = 0; s < m.stage_ntrees.size(); s++) {
+    if (t.q[s] == 0.0) continue;
+    for (int i = 0; i < m.stage_ntrees[s]; i++) {
+      HaarStumpDev& r = w[(size_t)m.stage_first[s] + i];
+      static_assert(sizeof(r.left) == sizeof(int32_t), "leaf words");
+      std::memcpy(&r.left, &t.left_q[(size_t)r.pad], sizeof(int32_t));
+      std::memcpy(&r.right, &t.right_q[(size_t)r.pad], sizeof(int32_t));
+    }
+  }
+}
+static bool wave_int_wanted() {
+  const char* e = std::getenv("CCAMD_WAVE_INT");
+  return !e || std::atoi(e) != 0;
+}
+
 // Tree nodes: the corners of the stump records (fill_haar_corners / fill_lbp_cells), children instead of leaf values.
 template <int STEP>
 static void build_haar_nodes(const Cascade& m, std::vector<HaarNodeDev>& out) {
@@ -134,6 +152,9 @@ void configure_detector(cc_detector* d) {
   if (const char* e = std::getenv("CCAMD_CAND_CAP")) d->cand_cap = std::max(16, std::atoi(e));  // initial candidate-list capacity (tests: forces the overflow path)
   if (const char* e = std::getenv("CCAMD_WAVE_BELOW"))  // tuning knob; only honoured where the wave phase is valid at all
     if (d->wave_below) d->wave_below = std::max(0, std::min(64, std::atoi(e)));  // the wave phase holds one window per lane
+  // Haar wave phase: int32 vote sums in the stages that have a quantum. CCAMD_WAVE_INT=0: double sums in every stage (A/B runs, tests).
+  d->wave_int_enabled = wave_int_wanted();
+  d->wave_int = wave_int_tables(d->m, d->wave_int_enabled && haar && d->wave_below > 0);
   // Stage groups and queue form (stage_groups, where the numbers behind the defaults are): LBP stump cascades group their
   // short stages from stage 2 on, up to 14 stumps, and switch to the list queue there; everything else keeps one stage per
   // group and the bank-class table.
@@ -189,9 +210,13 @@ cc_status upload_cascade_tables(cc_detector* d) {
     CC_HIP(d->d_haar_g.upload(sg, d->stream));
     CC_HIP(hipStreamSynchronize(d->stream));
     if (d->wave_below > 0) {
-      const std::vector<HaarStumpDev> w1 = schedule_for_wave_phase(d->m, s1), w2 = schedule_for_wave_phase(d->m, s2);
+      std::vector<HaarStumpDev> w1 = schedule_for_wave_phase(d->m, s1), w2 = schedule_for_wave_phase(d->m, s2);
+      put_integer_leaves(d->m, d->wave_int, w1);
+      put_integer_leaves(d->m, d->wave_int, w2);
       CC_HIP(d->d_haar1w.upload(w1, d->stream));
       CC_HIP(d->d_haar2w.upload(w2, d->stream));
+      CC_HIP(d->d_wave_q.upload(d->wave_int.q, d->stream));
+      CC_HIP(d->d_wave_thr_q.upload(d->wave_int.thr_q, d->stream));
       CC_HIP(hipStreamSynchronize(d->stream));
     }
   } else {
@@ -218,3 +243,13 @@ cc_status upload_cascade_tables(cc_detector* d) {
 }
 
 }  // namespace ccamd
+
+extern "C" cc_status cc_debug_wave_int_tables(const cc_cascade* c, double* q, int32_t* thr_q, int32_t* left_q, int32_t* right_q) {
+  if (!c) return set_error(CC_ERR_INVALID_ARG, "cc_debug_wave_int_tables: null cascade");
+  const WaveIntTables t = wave_int_tables(c->m, wave_int_wanted());
+  if (q) std::copy(t.q.begin(), t.q.end(), q);
+  if (thr_q) std::copy(t.thr_q.begin(), t.thr_q.end(), thr_q);
+  if (left_q) std::copy(t.left_q.begin(), t.left_q.end(), left_q);
+  if (right_q) std::copy(t.right_q.begin(), t.right_q.end(), right_q);
+  return CC_OK;
+}

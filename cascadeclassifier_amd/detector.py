@@ -283,6 +283,15 @@ class CascadeClassifier:
             rects, weights, tilted = _view(r, C.c_int32, nf * 4).reshape(nf, 4), None, None
         return CascadeModel(inf, sf, sn, sthr, *stump, rects, weights, tilted)
 
+    def wave_int_tables(self):
+        """(q, thr_q, left_q, right_q) of cc_debug_wave_int_tables: per stage the quantum of the wave phase's integer vote
+        sums (0 = that stage sums in double) and the integer stage threshold, per stump the leaves in quanta. Host only."""
+        inf = self.info()
+        q, thr_q = np.zeros(inf["n_stages"], np.float64), np.zeros(inf["n_stages"], np.int32)
+        left_q, right_q = np.zeros(inf["n_weak"], np.int32), np.zeros(inf["n_weak"], np.int32)
+        L.check(L.lib().cc_debug_wave_int_tables(self._c, _vp(q), _vp(thr_q), _vp(left_q), _vp(right_q)))
+        return q, thr_q, left_q, right_q
+
     # -- detector -------------------------------------------------------------------------------
     def _detector(self):
         if not self._c:

@@ -368,6 +368,14 @@ CC_API cc_status cc_debug_division_check(int device, uint64_t n_pairs, uint64_t 
  * as the kernels form them) for which the refined-rsqrt path differs from (float)(1.0 / sqrt(nf)), the CPU's two correctly
  * rounded operations (cv::CascadeClassifier setWindow). Must report 0. */
 CC_API cc_status cc_debug_vnf_check(int device, uint64_t n_values, uint64_t seed, uint64_t* mismatches);
+/* Host only, no device: the tables behind the integer form of the Haar cascade kernel's wave phase, as a detector created
+ * from `c` now (CCAMD_WAVE_INT is read) builds them. Per stage: q[s] = the quantum 2^k of the stage's leaves, 0 where the
+ * stage sums stay in double (no int32 range proof, a NaN threshold, not a Haar stump cascade with order-independent sums,
+ * CCAMD_WAVE_INT=0); thr_q[s] = the smallest int32 n with n * q[s] >= the stage threshold as cc_cascade_stages reports it,
+ * saturated to the int32 limits. Per weak classifier, in cc_cascade_stumps order: left_q / right_q = the leaves in units of
+ * their stage's quantum. Entries of stages without the form are 0. q / thr_q hold n_stages entries, left_q / right_q n_weak;
+ * any may be NULL. */
+CC_API cc_status cc_debug_wave_int_tables(const cc_cascade* c, double* q, int32_t* thr_q, int32_t* left_q, int32_t* right_q);
 /* Host-side (tiny, serial in the reference too): cv::groupRectangles(rects, group_threshold, eps). */
 CC_API cc_status cc_group_rectangles(const cc_rect* rects, int n, int group_threshold, double eps, cc_rect* out, int cap,
                                      int* n_out);
