@@ -4,3 +4,4 @@ from ._lib import CascadeError, LIB_PATH  # noqa: F401
 from .detector import (CascadeClassifier, frame_layout, group_rectangles, group_rectangles_device, scale_plan,  # noqa: F401
                        to_gray)
 from .evaluator import CascadeBoost, CvFeatureEvaluator, CvFeatureParams, NegativeMiner, device_exp  # noqa: F401
+from .trainer import BackgroundReader, train_cascade  # noqa: F401

@@ -192,7 +192,15 @@ SIGNATURES = {
     "cc_negminer_plan": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(_i), C.POINTER(C.c_int64)]),
     "cc_negminer_run": (_i, [_vp, _vp, _i, _i, _sz, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64), _vp, _vp, _i, C.POINTER(_i)]),
     "cc_negminer_run_batch": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64), _vp, _vp, _i, C.POINTER(_i)]),
+    "cc_negminer_create_empty": (_i, [_i, _i, _i, _i, _pp]),
+    "cc_negminer_fill": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _i, _i, C.c_int64, _i, _i, C.c_int64, C.c_int64, _d,
+                              C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(_i), _vp]),
+    "cc_eval_fill_passed": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_uint8, C.POINTER(_i), C.POINTER(C.c_int64)]),
+    "cc_debug_fill_select": (_i, [_i, _vp, C.c_int64, C.c_int64, _i, C.c_int64, C.c_int64, _d, C.POINTER(_i), C.POINTER(C.c_int64),
+                                  C.POINTER(_i), _vp]),
+    "cc_debug_fill_scan_tile": (_i, []),
 }
+CC_FILL_FILLED, CC_FILL_RATIO, CC_FILL_EXHAUSTED = 0, 1, 2
 
 _lib = None
 

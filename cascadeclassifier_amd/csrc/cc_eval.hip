@@ -777,20 +777,44 @@ cc_status cc_eval_set_images(cc_evaluator* e, const uint8_t* imgs, int n, int fi
   const size_t bytes = (size_t)n * e->W * e->H;
   CC_HIP(e->d_imgs.ensure(bytes));
   CC_HIP(hipMemcpyAsync(e->d_imgs.p, imgs, bytes, hipMemcpyHostToDevice, e->stream));
-  if (e->type == CC_FEATURE_HOG) {
-    st = hog_launch_set_images(e, e->d_imgs.p, n, first_idx);
-    if (st != CC_OK) return st;
-  } else {
-    const size_t lds = (size_t)e->H * (e->W + 1) * 4;
-    hipLaunchKernelGGL(k_set_images, dim3(n), dim3(64), lds, e->stream, e->d_imgs.p, e->W, e->H, first_idx, e->d_sum.p,
-                       e->use_tilted ? e->d_tilted.p : nullptr, e->d_nf.p, e->type == CC_FEATURE_HAAR ? 1 : 0);
-  }
-  CC_HIP(hipGetLastError());
+  st = launch_set_images(e, e->d_imgs.p, n, first_idx);
+  if (st != CC_OK) return st;
   CC_HIP(hipStreamSynchronize(e->stream));
   if (labels)
     for (int i = 0; i < n; i++) e->cls[(size_t)first_idx + i] = (float)labels[i];
   return CC_OK;
 }
+
+}  // extern "C"
+
+namespace ccamd {
+
+cc_status launch_set_images(cc_evaluator* e, const uint8_t* d_imgs, int n, int first_idx) {
+  if (e->type == CC_FEATURE_HOG) return hog_launch_set_images(e, d_imgs, n, first_idx);
+  const size_t lds = (size_t)e->H * (e->W + 1) * 4;
+  hipLaunchKernelGGL(k_set_images, dim3(n), dim3(64), lds, e->stream, d_imgs, e->W, e->H, first_idx, e->d_sum.p,
+                     e->use_tilted ? e->d_tilted.p : nullptr, e->d_nf.p, e->type == CC_FEATURE_HAAR ? 1 : 0);
+  CC_HIP(hipGetLastError());
+  return CC_OK;
+}
+
+cc_status eval_set_images_device(cc_evaluator* e, const uint8_t* d_imgs, int n, int first_idx, float label) {
+  if (n == 0) return CC_OK;
+  std::lock_guard<std::mutex> lk(e->mu);
+  cc_status st = flush_pending_images(e);
+  if (st != CC_OK) return st;
+  e->generation++;
+  if (e->mirror_idx >= first_idx && e->mirror_idx < first_idx + n) e->mirror_idx = -1;
+  st = launch_set_images(e, d_imgs, n, first_idx);
+  if (st != CC_OK) return st;
+  CC_HIP(hipStreamSynchronize(e->stream));
+  for (int i = 0; i < n; i++) e->cls[(size_t)first_idx + i] = label;
+  return CC_OK;
+}
+
+}  // namespace ccamd
+
+extern "C" {
 
 // setImage for ONE window (haarfeatures.cpp:100-114, lbpfeatures.cpp:22-28) -- the call the trainer's negative-mining loop
 // makes for every candidate window (cascadeclassifier.cpp:340-347), 10^5..10^6 times per late stage, each followed by a
@@ -1162,7 +1186,7 @@ static cc_status predict_haar_stumps(cc_evaluator* e, const Cascade& m, const in
                            d_ntrees.p, d_sthr.p, dh.p, d_thr.p, d_left.p, d_right.p, e->d_pred.p};
   hipLaunchKernelGGL(k_predict_haar_stumps, dim3((n_samples + 63) / 64), dim3(64), 0, e->stream, A);
   CC_HIP(hipGetLastError());
-  CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)n_samples, hipMemcpyDeviceToHost, e->stream));
+  if (out) CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)n_samples, hipMemcpyDeviceToHost, e->stream));
   CC_HIP(hipStreamSynchronize(e->stream));
   return CC_OK;
 }
@@ -1170,12 +1194,10 @@ static cc_status predict_haar_stumps(cc_evaluator* e, const Cascade& m, const in
 cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const int32_t* sample_idx, int n_samples, uint8_t* out) {
   if (!e || !c || !out) return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: null argument");
   const Cascade& m = c->m;
-  if (m.feature_type != e->type || m.win_w != e->W || m.win_h != e->H)
-    return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: cascade (%s %dx%d) does not match the evaluator (%s %dx%d)",
-                     feature_type_name(m.feature_type), m.win_w, m.win_h, feature_type_name(e->type), e->W, e->H);
-  if (m.has_tilted && !e->use_tilted) return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: cascade has tilted features but the evaluator keeps no tilted integrals");
+  cc_status st = predict_check(e, m, "cc_eval_predict_cascade");
+  if (st != CC_OK) return st;
   if (n_samples < 0) return set_error(CC_ERR_INVALID_ARG, "cc_eval_predict_cascade: negative sample count");
-  cc_status st = eval_device(e);
+  st = eval_device(e);
   if (st != CC_OK) return st;
   if (n_samples == 0) return CC_OK;
   std::lock_guard<std::mutex> lk(e->mu);
@@ -1183,6 +1205,23 @@ cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const in
   const int32_t* d_idx = nullptr;
   st = upload_indices(e, sample_idx, n_samples, &d_idx);
   if (st != CC_OK) return st;
+  return predict_stored(e, m, d_idx, n_samples, out);
+}
+
+}  // extern "C"
+
+namespace ccamd {
+
+cc_status predict_check(const cc_evaluator* e, const Cascade& m, const char* who) {
+  if (m.feature_type != e->type || m.win_w != e->W || m.win_h != e->H)
+    return set_error(CC_ERR_INVALID_ARG, "%s: cascade (%s %dx%d) does not match the evaluator (%s %dx%d)", who,
+                     feature_type_name(m.feature_type), m.win_w, m.win_h, feature_type_name(e->type), e->W, e->H);
+  if (m.has_tilted && !e->use_tilted)
+    return set_error(CC_ERR_INVALID_ARG, "%s: cascade has tilted features but the evaluator keeps no tilted integrals", who);
+  return CC_OK;
+}
+
+cc_status predict_stored(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, int n_samples, uint8_t* out) {
   if (e->type == CC_FEATURE_HOG) return hog_predict(e, m, d_idx, n_samples, out);
   if (e->type != CC_FEATURE_HAAR && e->type != CC_FEATURE_LBP)
     return set_error(CC_ERR_UNSUPPORTED, "cc_eval_predict_cascade: feature type %d", e->type);
@@ -1213,10 +1252,14 @@ cc_status cc_eval_predict_cascade(cc_evaluator* e, const cc_cascade* c, const in
   else
     hipLaunchKernelGGL(k_predict<false>, dim3((n_samples + 63) / 64), dim3(64), 0, e->stream, A);
   CC_HIP(hipGetLastError());
-  CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)n_samples, hipMemcpyDeviceToHost, e->stream));
+  if (out) CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)n_samples, hipMemcpyDeviceToHost, e->stream));
   CC_HIP(hipStreamSynchronize(e->stream));  // the tables above are freed on return
   return CC_OK;
 }
+
+}  // namespace ccamd
+
+extern "C" {
 
 cc_status cc_eval_last_kernel_ms(cc_evaluator* e, double* ms) {
   if (!e || !ms) return set_error(CC_ERR_INVALID_ARG, "cc_eval_last_kernel_ms: null argument");

@@ -35,6 +35,40 @@ cc_status launch_batch(cc_evaluator* e, bool haar, const void* feats, int fb, in
 // Every entry point that reads stored samples on the device calls it first. Caller holds e->mu.
 cc_status flush_pending_images(cc_evaluator* e);
 
+// setImage of n windows whose pixels are already on the device (W * H bytes each, readable from e->stream) into the rows
+// [first_idx, first_idx + n) of the evaluator's sample tables: the launch cc_eval_set_images makes. Caller holds e->mu.
+cc_status launch_set_images(cc_evaluator* e, const uint8_t* d_imgs, int n, int first_idx);
+// cc_eval_set_images for device-resident pixels, every sample with one label: pending queue first, generation, host
+// mirror, launch, synchronise, labels. Takes e->mu. The range has been checked by the caller.
+cc_status eval_set_images_device(cc_evaluator* e, const uint8_t* d_imgs, int n, int first_idx, float label);
+// Whether cascade m can be predicted on e's samples (type, window, tilted integrals); `who` names the entry point.
+cc_status predict_check(const cc_evaluator* e, const Cascade& m, const char* who);
+// CvCascadeClassifier::predict of m on ns stored samples (d_idx: device indices or NULL for 0..ns-1): the flags stay in
+// e->d_pred and, if out is set, also go to host out. Synchronises e->stream. Caller holds e->mu, predict_check passed.
+cc_status predict_stored(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, int ns, uint8_t* out);
+
+// ---- filling a stage's training set (cc_fill.hip) -----------------------------------------------
+// The loop of fillPassedSamples (cascadeclassifier.cpp:329-357) over pass flags that are on the device: where it stops,
+// why, and which positions it keeps. FillWork is the caller's workspace; d_keep[0 .. n_filled) holds the kept positions.
+struct FillRecord {
+  unsigned long long stop;  // position * 4 + reason of the first position at which the loop stops
+  int n_filled, pad;
+};
+struct FillWork {
+  DevBuf<long long> d_block;  // per block of the scan: flags set in it, then the count before it
+  DevBuf<long long> d_keep;
+  DevBuf<FillRecord> d_rec;
+  PinnedBuf h_rec;
+};
+struct FillResult {
+  int n_filled = 0, stop = 0;
+  long long n_consumed = 0;
+};
+// Queues the selection over flags [start, n) behind what `st` holds and waits for its record. got_before, consumed_before
+// and ratio as cc_negminer_fill takes them.
+cc_status fill_select(FillWork& w, const uint8_t* d_flags, long long n, long long start, int want, long long got_before,
+                      long long consumed_before, double ratio, hipStream_t st, FillResult* out);
+
 // HOG (cc_hog.hip). Catalog blocks as (x, y, cell w, cell h) (hog_catalog, cc_internal.h); variables are block * 36 + cell * 9 + bin.
 // Builds the catalog, sets nfeat to the variable count and allocates the planes. Called by cc_eval_create.
 cc_status hog_init(cc_evaluator* e);
@@ -44,7 +78,7 @@ cc_status hog_launch_set_images(cc_evaluator* e, const uint8_t* d_imgs, int n, i
 cc_status hog_launch_batch(cc_evaluator* e, int vb, int ve, const int32_t* d_idx, int ns, float* d_out, size_t out_pitch);
 cc_status hog_launch_list(cc_evaluator* e, const int32_t* d_list, int n, int si, float* d_out);
 // CvCascadeClassifier::predict of HOG cascade m (type and window checked by the caller) on ns stored samples (d_idx:
-// device indices or NULL for 0..ns-1) into host out; synchronous. Caller holds e->mu.
+// device indices or NULL for 0..ns-1) into e->d_pred and, if set, host out; synchronous. Caller holds e->mu.
 cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, int ns, uint8_t* out);
 // Host mirror: the ten planes of one window ([cols][10], the device layout) and one variable's value on them.
 void hog_host_planes(const cc_evaluator* e, const uint8_t* px, std::vector<float>& planes);
@@ -151,6 +185,11 @@ struct cc_evaluator {
   DevBuf<float> d_hog;
   int hog_planes_per_pass = 0;
   std::vector<float> mirror_hog;
+  // cc_eval_fill_passed (cc_fill.hip): a chunk of candidates is set into these scratch rows, predicted there and the kept
+  // rows copied to their slots; guarded by mu
+  DevBuf<int32_t> fill_sum, fill_tilted;
+  DevBuf<float> fill_nf, fill_hog;
+  ccamd::FillWork fill;
   ~cc_evaluator() {
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);

@@ -261,7 +261,7 @@ cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, i
   A.out = e->d_pred.p;
   hipLaunchKernelGGL(k_hog_predict, dim3((ns + 63) / 64), dim3(64), 0, e->stream, A);
   CC_HIP(hipGetLastError());
-  CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)ns, hipMemcpyDeviceToHost, e->stream));
+  if (out) CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)ns, hipMemcpyDeviceToHost, e->stream));
   CC_HIP(hipStreamSynchronize(e->stream));  // the tables and `nodes` above are freed on return
   return CC_OK;
 }

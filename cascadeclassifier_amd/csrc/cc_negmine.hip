@@ -247,6 +247,7 @@ using namespace ccamd;
 
 struct cc_negminer {
   Cascade m;
+  bool empty = false;  // no trained stage (cc_negminer_create_empty): every window passes, no window kernel runs
   int device = 0;
   OwnStream stream;
   WalkTablesDev walk;
@@ -269,6 +270,7 @@ struct cc_negminer {
   PinnedBuf h_pass;  // pass flags on their way back
   OwnStream copy_stream;               // the images' way to the device, piece by piece, under the kernels of the piece before
   std::vector<OwnEvent> piece_landed;  // one per piece of a call (grown on demand)
+  FillWork fill;                       // cc_negminer_fill's selection
 };
 
 extern "C" {
@@ -318,6 +320,27 @@ cc_status mine_check(const cc_negminer* m, int width, int height, int ox, int oy
 }
 
 }  // namespace
+
+cc_status cc_negminer_create_empty(int feature_type, int win_w, int win_h, int device, cc_negminer** out) {
+  if (!out) return set_error(CC_ERR_INVALID_ARG, "cc_negminer_create_empty: null argument");
+  *out = nullptr;
+  if (feature_type != CC_FEATURE_HAAR && feature_type != CC_FEATURE_LBP && feature_type != CC_FEATURE_HOG)
+    return set_error(CC_ERR_UNSUPPORTED, "cc_negminer_create_empty: feature type %d", feature_type);
+  if (win_w < 2 || win_h < 2 || win_w > 4096 || win_h > 4096)  // half a window is the stream's step: at least one pixel
+    return set_error(CC_ERR_INVALID_ARG, "cc_negminer_create_empty: window %dx%d", win_w, win_h);
+  cc_status st = ensure_device(device);
+  if (st != CC_OK) return st;
+  std::unique_ptr<cc_negminer> m(new cc_negminer());
+  m->m.feature_type = feature_type;
+  m->m.win_w = win_w;
+  m->m.win_h = win_h;
+  m->empty = true;
+  m->device = device;
+  CC_HIP(m->stream.create());
+  CC_HIP(m->copy_stream.create());
+  *out = m.release();
+  return CC_OK;
+}
 
 cc_status cc_negminer_create(const cc_cascade* c, int device, cc_negminer** out) {
   if (!c || !out) return set_error(CC_ERR_INVALID_ARG, "cc_negminer_create: null argument");
@@ -472,7 +495,9 @@ struct MineCall {
   size_t row_stride;
   int ox, oy;
   const char* who;
+  bool to_host;  // the flags go back to the caller (cc_negminer_run*); cc_negminer_fill keeps them on the device
   bool haar, tilt, hog, wave_mode;
+  bool pixels_only;  // the window kernels read pixels (HOG) or nothing (no stages): no integral images
   int nchan, sx, sy;
   long long wins;
   size_t chan_elems, spitch, src_bytes;
@@ -485,7 +510,8 @@ static cc_status mine_begin(MineCall& C, uint8_t* pass, int64_t cap, int64_t* n_
   const char* who = C.who;
   cc_status st = mine_check(m, C.width, C.height, C.ox, C.oy, who);
   if (st != CC_OK) return st;
-  if (!C.images || C.K < 1 || !pass || !n_windows || C.row_stride < (size_t)C.width) return set_error(CC_ERR_INVALID_ARG, "%s: bad argument", who);
+  if (!C.images || C.K < 1 || (C.to_host && !pass) || !n_windows || C.row_stride < (size_t)C.width)
+    return set_error(CC_ERR_INVALID_ARG, "%s: bad argument", who);
   for (int k = 0; k < C.K; k++)
     if (!C.images[k]) return set_error(CC_ERR_INVALID_ARG, "%s: image %d is null", who, k);
   if (pixels && (!keep_index || !n_keep || max_keep < 0)) return set_error(CC_ERR_INVALID_ARG, "%s: bad keep buffers", who);
@@ -497,9 +523,10 @@ static cc_status mine_begin(MineCall& C, uint8_t* pass, int64_t cap, int64_t* n_
   C.haar = M.feature_type == CC_FEATURE_HAAR;
   C.tilt = C.haar && M.has_tilted;
   C.hog = M.feature_type == CC_FEATURE_HOG;
+  C.pixels_only = C.hog || m->empty;
   C.wins = m->plan.wins;
   *n_windows = C.wins;
-  if (C.wins * C.K > cap)
+  if (C.to_host && C.wins * C.K > cap)
     return set_error(CC_ERR_BUFFER_TOO_SMALL, "%s: %lld windows (%d images), capacity %lld", who, C.wins * C.K, C.K, (long long)cap);
   C.nchan = C.haar ? (C.tilt ? 3 : 2) : 1;
   C.chan_elems = m->front.L.int_frame_elems;
@@ -508,7 +535,7 @@ static cc_status mine_begin(MineCall& C, uint8_t* pass, int64_t cap, int64_t* n_
   C.sx = (int)(0.5F * M.win_w);
   C.sy = (int)(0.5F * M.win_h);
   // one wavefront per window where the parallel stage sum is exact (stumps, order-independent sums); else one thread per window
-  C.wave_mode = M.max_nodes_per_tree == 1 && stage_sums_order_independent(M);
+  C.wave_mode = !m->empty && M.max_nodes_per_tree == 1 && stage_sums_order_independent(M);
   return CC_OK;
 }
 
@@ -519,13 +546,13 @@ static cc_status mine_workspace(const MineCall& C) {
   const size_t K = (size_t)C.K;
   CC_HIP(m->d_src.ensure(C.src_bytes * K));
   CC_HIP(m->d_pyr.ensure(FL.pyr_frame_bytes * K));
-  if (!C.hog) {  // HOG windows build their planes from the levels' pixels: no integral images
+  if (!C.pixels_only) {  // HOG windows build their planes from the levels' pixels: no integral images
     CC_HIP(m->d_integ.ensure(C.chan_elems * (size_t)C.nchan * K));
     CC_HIP(m->d_hbuf.ensure(std::max<size_t>(FL.h_frame_elems * (size_t)C.nchan * K, 4)));
   }
   CC_HIP(m->d_pass.ensure((size_t)std::max<long long>(C.wins * C.K, 1)));
   CC_HIP(m->h_src.ensure(C.src_bytes * K));
-  CC_HIP(m->h_pass.ensure((size_t)std::max<long long>(C.wins * C.K, 1)));
+  if (C.to_host) CC_HIP(m->h_pass.ensure((size_t)std::max<long long>(C.wins * C.K, 1)));
   if (C.tilt) {
     CC_HIP(m->d_diag.ensure(C.chan_elems * 2 * K));
     CC_HIP(m->d_tseg.ensure(std::max<size_t>(FL.tseg_frame_elems * K, 1)));
@@ -545,7 +572,7 @@ static void mine_launch_images(const MineCall& C, int k0, int n) {
   io.row_stride = C.spitch;
   io.frame_stride = C.src_bytes;
   io.pyr = m->d_pyr.p + (size_t)k0 * FL.pyr_frame_bytes;
-  if (!C.hog) {
+  if (!C.pixels_only) {
     io.integ = m->d_integ.p + (size_t)k0 * C.nchan * C.chan_elems;
     io.hbuf = m->d_hbuf.p + (size_t)k0 * C.nchan * FL.h_frame_elems;
   }
@@ -555,8 +582,12 @@ static void mine_launch_images(const MineCall& C, int k0, int n) {
   }
   io.nchan = C.nchan;
   io.sq = C.haar;
-  launch_front(s, m->front, io, n, C.hog ? FRONT_RESIZE : FRONT_RESIZE | FRONT_INTEGRALS);
+  launch_front(s, m->front, io, n, C.pixels_only ? FRONT_RESIZE : FRONT_RESIZE | FRONT_INTEGRALS);
   if (wins == 0) return;
+  if (m->empty) {
+    (void)hipMemsetAsync(m->d_pass.p + (size_t)k0 * (size_t)wins, 1, (size_t)n * (size_t)wins, s);
+    return;
+  }
   if (C.hog) {
     HogMineArgs H;
     H.pyr = io.pyr;
@@ -718,6 +749,7 @@ static cc_status mine_images(cc_negminer* m, const uint8_t* const* images, int n
   C.ox = ox;
   C.oy = oy;
   C.who = who;
+  C.to_host = true;
   cc_status st = mine_begin(C, pass, cap, n_windows, pixels, keep_index, max_keep, n_keep);
   if (st == CC_OK) st = mine_workspace(C);
   if (st == CC_OK) st = mine_pieces(C);
@@ -739,6 +771,64 @@ cc_status cc_negminer_run_batch(cc_negminer* m, const uint8_t* const* images, in
   if (n_images > 256) return set_error(CC_ERR_INVALID_ARG, "cc_negminer_run_batch: at most 256 images per call (%d given)", n_images);
   return mine_images(m, images, n_images, width, height, row_stride, ox, oy, pass, cap, n_windows, pixels, keep_index, max_keep, n_keep,
                      "cc_negminer_run_batch");
+}
+
+// fillPassedSamples' negative branch over the stream of the images (section 6c): the window kernels as in mine_images, then
+// the selection on the flags where they are (cc_fill.hip), the kept windows' pixels out of the ladders, and the evaluator's
+// setImage on them. What crosses to the host is the selection's record and, on request, the kept positions.
+cc_status cc_negminer_fill(cc_negminer* m, cc_evaluator* e, const uint8_t* const* images, int n_images, int width, int height,
+                           size_t row_stride, int ox, int oy, int64_t start, int first_idx, int want, int64_t got_before,
+                           int64_t consumed_before, double min_acceptance_ratio, int* n_filled, int64_t* n_consumed, int* stop,
+                           int64_t* keep_index) {
+  const char* who = "cc_negminer_fill";
+  if (!m || !e || !n_filled || !n_consumed || !stop) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
+  if (e->device != m->device || e->type != m->m.feature_type || e->W != m->m.win_w || e->H != m->m.win_h)
+    return set_error(CC_ERR_INVALID_ARG, "%s: miner (device %d, feature type %d, %dx%d) and evaluator (device %d, feature type %d, %dx%d) differ",
+                     who, m->device, m->m.feature_type, m->m.win_w, m->m.win_h, e->device, e->type, e->W, e->H);
+  if (n_images < 1 || n_images > 256) return set_error(CC_ERR_INVALID_ARG, "%s: 1 to 256 images per call (%d given)", who, n_images);
+  if (first_idx < 0 || want < 0 || (long long)first_idx + want > e->max_samples)
+    return set_error(CC_ERR_OUT_OF_RANGE, "%s: samples [%d, %lld) exceed max_samples %d", who, first_idx, (long long)first_idx + want,
+                     e->max_samples);
+  if (got_before < 0 || consumed_before < 0) return set_error(CC_ERR_INVALID_ARG, "%s: negative counts", who);
+  MineCall C{};
+  C.m = m;
+  C.images = images;
+  C.K = n_images;
+  C.width = width;
+  C.height = height;
+  C.row_stride = row_stride;
+  C.ox = ox;
+  C.oy = oy;
+  C.who = who;
+  C.to_host = false;
+  int64_t wins = 0;
+  cc_status st = mine_begin(C, nullptr, 0, &wins, nullptr, nullptr, 0, nullptr);
+  if (st != CC_OK) return st;
+  const long long total = C.wins * C.K;
+  if (start < 0 || start > total) return set_error(CC_ERR_INVALID_ARG, "%s: start %lld outside the stream [0, %lld]", who, (long long)start, total);
+  st = mine_workspace(C);
+  if (st == CC_OK) st = mine_pieces(C);
+  if (st != CC_OK) return st;
+  hipStream_t s = m->stream.s;
+  FillResult R;
+  st = fill_select(m->fill, m->d_pass.p, total, start, want, got_before, consumed_before, min_acceptance_ratio, s, &R);
+  if (st != CC_OK) return st;
+  if (R.n_filled > 0) {
+    const FrontLayout& FL = m->front.L;
+    const int W0 = m->m.win_w, H0 = m->m.win_h;
+    CC_HIP(m->d_pix.ensure((size_t)R.n_filled * W0 * H0));
+    hipLaunchKernelGGL(k_negmine_gather, dim3((unsigned)R.n_filled), dim3(64), 0, s, m->d_pyr.p, FL.pyr_frame_bytes, C.wins, m->d_levels.p,
+                       (int)FL.sd.size(), m->fill.d_keep.p, W0, H0, C.ox, C.oy, C.sx, C.sy, m->d_pix.p);
+    CC_HIP(hipGetLastError());
+    if (keep_index) CC_HIP(hipMemcpyAsync(keep_index, m->fill.d_keep.p, (size_t)R.n_filled * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    CC_HIP(hipStreamSynchronize(s));  // the evaluator's stream reads d_pix
+    st = eval_set_images_device(e, m->d_pix.p, R.n_filled, first_idx, 0.f);
+    if (st != CC_OK) return st;
+  }
+  *n_filled = R.n_filled;
+  *n_consumed = R.n_consumed;
+  *stop = R.stop;
+  return CC_OK;
 }
 
 }  // extern "C"

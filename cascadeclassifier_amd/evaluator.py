@@ -129,6 +129,17 @@ class CvFeatureEvaluator:
         L.check(L.lib().cc_eval_predict_cascade(self._e, cascade._c, _vp(idx), ns, _vp(out)))
         return out
 
+    def fill_passed(self, cascade, imgs, first_idx, want, label=1):
+        """fillPassedSamples for packed candidates (the positives, cascadeclassifier.cpp:312): the candidates that pass
+        `cascade` (None: all) fill slots first_idx .. in order, at most `want`. Returns (n_filled, n_consumed)."""
+        imgs = np.ascontiguousarray(imgs, np.uint8)
+        if imgs.ndim != 3 or imgs.shape[1:] != (self.winSize[1], self.winSize[0]):
+            raise L.CascadeError(L.CC_ERR_INVALID_ARG, "fill_passed: images do not match winSize")
+        nf, nc = C.c_int(0), C.c_int64(0)
+        L.check(L.lib().cc_eval_fill_passed(self._e, None if cascade is None else cascade._c, _vp(imgs), imgs.shape[0], int(first_idx),
+                                            int(want), int(label), C.byref(nf), C.byref(nc)))
+        return nf.value, nc.value
+
     # ---- best-split search of a boosted-tree node (CvDTree::find_best_split, o_cvdtree.cpp:313-357)
     def presort(self, n_samples=None, fi_begin=0, fi_end=None):
         """Evaluate features [fi_begin, fi_end) (default: all) on stored samples [0, n_samples) and keep the sorted
@@ -309,6 +320,39 @@ class NegativeMiner:
         L.check(L.lib().cc_negminer_create(cascade._c, device, C.byref(self._m)))
         inf = cascade.info()
         self.win = (inf["win_w"], inf["win_h"])
+
+    @classmethod
+    def empty(cls, feature_type, win, device=0):
+        """A miner with no trained stage (stage 0 of training): every window of the stream passes."""
+        self = cls.__new__(cls)
+        self._m = C.c_void_p()
+        self._cascade = None
+        L.check(L.lib().cc_negminer_create_empty(int(feature_type), int(win[0]), int(win[1]), device, C.byref(self._m)))
+        self.win = (int(win[0]), int(win[1]))
+        return self
+
+    def fill(self, evaluator, imgs, first_idx, want, *, start=0, got=0, consumed=0, min_acceptance_ratio=0.0, ox=0, oy=0,
+             want_keep_index=False):
+        """cc_negminer_fill: the negative branch of fillPassedSamples over the window stream of `imgs` (one size, one offset),
+        from stream position `start`, straight into the evaluator's slots first_idx ..; `got` / `consumed` are the stage's
+        counts so far. Returns a dict: n_filled, n_consumed, stop (CC_FILL_*), and keep_index if asked for."""
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        if not imgs:
+            raise ValueError("fill: no image")
+        h, w = imgs[0].shape
+        if any(im.shape != (h, w) for im in imgs):
+            raise ValueError("fill: images of one size only")
+        k = len(imgs)
+        ptrs = (C.c_void_p * k)(*[im.ctypes.data for im in imgs])
+        keep = np.zeros(max(int(want), 1), np.int64) if want_keep_index else None
+        nf, nc, stop = C.c_int(0), C.c_int64(0), C.c_int(0)
+        L.check(L.lib().cc_negminer_fill(self._m, evaluator._e, ptrs, k, w, h, w, int(ox), int(oy), int(start), int(first_idx), int(want),
+                                         int(got), int(consumed), float(min_acceptance_ratio), C.byref(nf), C.byref(nc), C.byref(stop),
+                                         _vp(keep)))
+        out = {"n_filled": nf.value, "n_consumed": nc.value, "stop": stop.value}
+        if want_keep_index:
+            out["keep_index"] = keep[:nf.value].copy()
+        return out
 
     def plan(self, width, height, ox=0, oy=0):
         lw, lh, nx, ny = (np.zeros(64, np.int32) for _ in range(4))

@@ -661,6 +661,60 @@ CC_API cc_status cc_cascade_from_stumps(int feature_type, int haar_mode, int win
                                         const int32_t* subsets, const float* left, const float* right, cc_cascade** out);
 
 /* ============================================================================================
+ * 6c. Filling a stage's training set.
+ *    Replaces CvCascadeClassifier::fillPassedSamples (traincascade/lib/src/cascadeclassifier.cpp:329-357) as
+ *    updateTrainingSet (:308-327) calls it: the candidates (windows of the background stream, imagestorage.cpp:90-126, or
+ *    the positives) are taken in order, setImage + predict decides each, and the ones that pass fill consecutive sample
+ *    slots of the evaluator. Section 5's calls hand every pass flag to the host, which then sends the kept pixels back
+ *    through cc_eval_set_images; here the flags, the choice and the kept pixels stay on the device and one small record
+ *    comes back.
+ *
+ *    The loop, with `flags` the pass flag of every stream position (image 0 first, n_images * wins positions):
+ *        got = consumed = 0; j = start
+ *        loop: if got == want: stop = CC_FILL_FILLED; break                               (:333, the slots are full)
+ *              c = consumed_before + consumed; g = got_before + got
+ *              if c != 0 and (double)(g + 1) / (double)c <= min_acceptance_ratio: stop = CC_FILL_RATIO; break       (:337)
+ *              if j == n_images * wins: stop = CC_FILL_EXHAUSTED; break                   (:342, no further window here)
+ *              consumed += 1
+ *              if flags[j]: window j -> slot first_idx + got, label 0; keep_index[got] = j; got += 1          (:346-352)
+ *              j += 1
+ *    On the device: a count of the flags before every position (per block of cc_debug_fill_scan_tile() positions, then a scan
+ *    of the block totals), the first position at which one of the three conditions holds (IEEE double division), the
+ *    positions kept before it by rank, their pixels gathered out of the ladders, and the evaluator's own setImage code on
+ *    those pixels: a filled slot holds bit for bit what cc_eval_set_images stores for the window's pixels. got_before /
+ *    consumed_before carry a stage's counts over the calls that fill it; `start` resumes inside image 0's stream.
+ *    The evaluator: labels of the filled slots become 0, images queued by cc_eval_set_image are sent first, a host mirror of
+ *    an overwritten slot is dropped, boosters and presorted tables made before the call are stale (as after
+ *    cc_eval_set_images); slots outside [first_idx, first_idx + *n_filled) keep their contents. A call that fills nothing
+ *    leaves the evaluator alone.
+ *    Refused, with nothing changed: evaluator and miner of different device, feature type or window, n_images outside
+ *    [1, 256], start outside [0, n_images * wins] (CC_ERR_INVALID_ARG); first_idx < 0, want < 0 or first_idx + want >
+ *    max_samples (CC_ERR_OUT_OF_RANGE); offsets as cc_negminer_run_batch.
+ * ============================================================================================ */
+enum { CC_FILL_FILLED = 0, CC_FILL_RATIO = 1, CC_FILL_EXHAUSTED = 2 };
+/* A miner with no trained stages, for stage 0 of training: every window passes. (cc_cascade_from_stumps refuses a cascade
+ * without stages.) */
+CC_API cc_status cc_negminer_create_empty(int feature_type, int win_w, int win_h, int device, cc_negminer** out);
+/* n_images (<= 256) images of one size with one offset, as cc_negminer_run_batch takes them. keep_index (NULL, or `want`
+ * entries): the stream positions of the filled slots. */
+CC_API cc_status cc_negminer_fill(cc_negminer* m, cc_evaluator* e, const uint8_t* const* images, int n_images, int width, int height,
+                                  size_t row_stride, int ox, int oy, int64_t start, int first_idx, int want, int64_t got_before,
+                                  int64_t consumed_before, double min_acceptance_ratio, int* n_filled, int64_t* n_consumed, int* stop,
+                                  int64_t* keep_index);
+/* The positive branch (fillPassedSamples(0, numPos, true, 0, consumed)): the candidates are n_imgs packed windows
+ * (win_w * win_h bytes each) in order, the ratio is 0 and never stops the loop. The ones that pass `stages` (NULL: all) fill
+ * slots first_idx .. in order with `label`; *n_consumed = index of the last one taken + 1, or n_imgs when they run out
+ * before `want` are found. Candidates are set into scratch rows a chunk at a time, predicted there by the kernels of
+ * cc_eval_predict_cascade, and the kept rows copied to their slots. */
+CC_API cc_status cc_eval_fill_passed(cc_evaluator* e, const cc_cascade* stages, const uint8_t* imgs, int n_imgs, int first_idx,
+                                     int want, uint8_t label, int* n_filled, int64_t* n_consumed);
+/* Test instrumentation: the selection alone (count, first stop, keep list) over n host flags. */
+CC_API cc_status cc_debug_fill_select(int device, const uint8_t* flags, int64_t n, int64_t start, int want, int64_t got_before,
+                                      int64_t consumed_before, double ratio, int* n_filled, int64_t* n_consumed, int* stop,
+                                      int64_t* keep_index);
+CC_API int cc_debug_fill_scan_tile(void); /* positions per block of the scan */
+
+/* ============================================================================================
  * 7. Multi-GPU: the gather of detections (BASELINE configs[3]).
  *    Detection shards by frame, one process per GPU, and needs no data-path collective: rank r runs cc_detect_batch on
  *    frames [lo, hi) = cc_shard_range(n_frames, r, world). The only exchange is this gather of the per-frame rectangle
