@@ -79,6 +79,12 @@ class Weak(C.Structure):
                 ("hit_rate", C.c_float), ("false_alarm", C.c_float)]
 
 
+class TreeNode(C.Structure):
+    _fields_ = [("left", C.c_int32), ("right", C.c_int32), ("depth", C.c_int32), ("n_samples", C.c_int32), ("var_idx", C.c_int32),
+                ("split_point", C.c_int32), ("quality", C.c_float), ("ord_c", C.c_float), ("subset", C.c_int32 * 8),
+                ("value", C.c_double)]
+
+
 class HaarFeatureC(C.Structure):
     _fields_ = [("tilted", C.c_int32), ("r", (C.c_int32 * 4) * 3), ("w", C.c_float * 3)]
 
@@ -172,13 +178,16 @@ SIGNATURES = {
     "cc_eval_presort_range": (_i, [_vp, _i, _i, _i]),
     "cc_eval_find_best_split": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _d, _i, _i, C.POINTER(Split), _vp, _vp]),
     "cc_boost_create": (_i, [_vp, _i, C.POINTER(BoostParams), _pp]),
+    "cc_boost_create_depth": (_i, [_vp, _i, C.POINTER(BoostParams), _i, _pp]),
     "cc_boost_destroy": (None, [_vp]),
     "cc_boost_round": (_i, [_vp, C.POINTER(Weak)]),
     "cc_boost_train_stage": (_i, [_vp, C.POINTER(Weak), _i, C.POINTER(_i)]),
+    "cc_boost_last_tree": (_i, [_vp, C.POINTER(TreeNode), _i, _vp, _i, C.POINTER(_i)]),
     "cc_boost_get_state": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cc_boost_last_round_ms": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "cc_debug_exp64": (_i, [_i, _vp, _i, _vp]),
     "cc_cascade_from_stumps": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _pp]),
+    "cc_cascade_from_trees": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, C.POINTER(TreeNode), _vp, _pp]),
     "cc_shard_range": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "cc_comm_unique_id": (_i, [_vp]),
     "cc_comm_create": (_i, [_i, _i, _i, _vp, _pp]),

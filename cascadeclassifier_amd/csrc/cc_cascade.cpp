@@ -319,6 +319,133 @@ cc_status write_text_file(const char* path, const std::string& text) {
   if (!f) return set_error(CC_ERR_IO, "write to '%s' failed", path);
   return CC_OK;
 }
+
+// The model CvCascadeClassifier::save would write (cascadeclassifier.cpp:421-456) for trees given node by node in the
+// writer's order: what cc_cascade_from_stumps and cc_cascade_from_trees share, after the checks they share.
+cc_status check_shape(const char* who, int feature_type, int haar_mode, int win_w, int win_h, int n_stages, const int32_t* n_weak, int n_weak_total,
+                      size_t* total_out) {
+  if (feature_type != CC_FEATURE_HAAR && feature_type != CC_FEATURE_LBP && feature_type != CC_FEATURE_HOG)
+    return set_error(CC_ERR_INVALID_ARG, "%s: unknown feature type %d", who, feature_type);
+  if (feature_type == CC_FEATURE_HAAR && (haar_mode < 0 || haar_mode > 2)) return set_error(CC_ERR_INVALID_ARG, "%s: unknown Haar mode %d", who, haar_mode);
+  if (win_w < 3 || win_h < 3 || win_w > 4096 || win_h > 4096) return set_error(CC_ERR_INVALID_ARG, "%s: window %dx%d", who, win_w, win_h);
+  if (n_stages < 1) return set_error(CC_ERR_INVALID_ARG, "%s: no stages", who);
+  size_t total = 0;
+  for (int s = 0; s < n_stages; s++) {
+    if (n_weak[s] < 1) return set_error(CC_ERR_INVALID_ARG, "%s: stage %d has %d weak classifiers", who, s, n_weak[s]);
+    total += (size_t)n_weak[s];
+  }
+  if (n_weak_total < 0 || total != (size_t)n_weak_total)
+    return set_error(CC_ERR_INVALID_ARG, "%s: n_weak adds up to %zu weak classifiers, %d were given", who, total, n_weak_total);
+  *total_out = total;
+  return CC_OK;
+}
+
+// Arguments that passed check_shape. n_nodes == nullptr: one node per tree.
+cc_status cascade_from_nodes(const char* who, int feature_type, int haar_mode, int win_w, int win_h, int n_stages, const int32_t* n_weak, size_t total,
+                             const float* stage_threshold, const int32_t* n_nodes, int n_nodes_total, const cc_tree_node* nodes, const float* leaves,
+                             cc_cascade** out) {
+  const bool lbp = feature_type == CC_FEATURE_LBP;
+  size_t total_nodes = 0;
+  for (size_t t = 0; t < total; t++) {
+    const int nn = n_nodes ? n_nodes[t] : 1;
+    if (nn < 1) return set_error(CC_ERR_INVALID_ARG, "%s: weak classifier %zu has %d nodes", who, t, nn);
+    total_nodes += (size_t)nn;
+  }
+  if (n_nodes_total < 0 || total_nodes != (size_t)n_nodes_total)
+    return set_error(CC_ERR_INVALID_ARG, "%s: n_nodes adds up to %zu nodes, %d were given", who, total_nodes, n_nodes_total);
+  std::vector<HaarFeature> haar;
+  std::vector<int32_t> cat;  // LBP rects [n][4] or HOG blocks [n][4]
+  int n_vars = 0;
+  if (feature_type == CC_FEATURE_HAAR) {
+    haar_catalog(win_w, win_h, haar_mode, haar);
+    n_vars = (int)haar.size();
+  } else if (lbp) {
+    lbp_catalog(win_w, win_h, cat);
+    n_vars = (int)(cat.size() / 4);
+  } else {
+    hog_catalog(win_w, win_h, cat);
+    n_vars = (int)(cat.size() / 4) * 36;
+  }
+  // markUsedFeaturesInMap (boost.cpp:566-573) over every node (markFeaturesInMap, o_cvcascadeboosttree.cpp:349-359) + the
+  // numbering of CvCascadeClassifier::save (cascadeclassifier.cpp:421-437): used variables in catalog order
+  std::vector<int32_t> map((size_t)n_vars, -1);
+  {
+    size_t k = 0;
+    for (size_t t = 0; t < total; t++) {
+      const int nn = n_nodes ? n_nodes[t] : 1;
+      for (int j = 0; j < nn; j++, k++) {
+        const cc_tree_node& nd = nodes[k];
+        if (nd.var_idx < 0 || nd.var_idx >= n_vars)
+          return set_error(CC_ERR_OUT_OF_RANGE, "%s: variable %d of weak classifier %zu outside the catalog (%d)", who, nd.var_idx, t, n_vars);
+        // what the XML reader asks of child references (cascade_from_xml): inside the tree, and an internal child behind its parent
+        if (nd.left >= nn || nd.right >= nn || nd.left < -nn || nd.right < -nn)
+          return set_error(CC_ERR_OUT_OF_RANGE, "%s: child index of node %d of weak classifier %zu out of range", who, j, t);
+        if ((nd.left > 0 && nd.left <= j) || (nd.right > 0 && nd.right <= j))
+          return set_error(CC_ERR_OUT_OF_RANGE, "%s: child index of node %d of weak classifier %zu does not increase (cycle)", who, j, t);
+        map[(size_t)nd.var_idx] = 0;
+      }
+    }
+  }
+  std::unique_ptr<cc_cascade> c(new cc_cascade());
+  Cascade& m = c->m;
+  m.feature_type = feature_type;
+  m.win_w = win_w;
+  m.win_h = win_h;
+  m.max_cat_count = lbp ? 256 : 0;
+  m.subset_size = lbp ? 8 : 0;
+  m.max_nodes_per_tree = 0;
+  int next = 0;
+  for (int v = 0; v < n_vars; v++) {
+    if (map[(size_t)v] < 0) continue;
+    map[(size_t)v] = next++;
+    if (feature_type == CC_FEATURE_HAAR) {
+      const HaarFeature& f = haar[(size_t)v];
+      for (int j = 0; j < 3; j++) {
+        for (int k = 0; k < 4; k++) m.haar_rects.push_back(f.r[j][k]);
+        m.haar_weights.push_back(f.w[j]);
+      }
+      m.haar_tilted.push_back(f.tilted != 0);
+      m.has_tilted = m.has_tilted || f.tilted != 0;
+    } else if (lbp) {
+      for (int k = 0; k < 4; k++) m.lbp_rects.push_back(cat[(size_t)v * 4 + k]);
+    } else {
+      for (int k = 0; k < 4; k++) m.hog_feats.push_back(cat[(size_t)(v / 36) * 4 + k]);
+      m.hog_feats.push_back(v % 36);
+    }
+  }
+  size_t t = 0, k = 0;
+  for (int s = 0; s < n_stages; s++) {
+    m.stage_first.push_back((int32_t)t);
+    m.stage_ntrees.push_back(n_weak[s]);
+    m.stage_threshold.push_back(stage_threshold[s] - 1e-5f);  // THRESHOLD_EPS, as the reader stores it
+    for (int i = 0; i < n_weak[s]; i++, t++) {
+      const int nn = n_nodes ? n_nodes[t] : 1;
+      m.tree_first_node.push_back((int32_t)k);
+      m.tree_nnodes.push_back(nn);
+      m.tree_first_leaf.push_back((int32_t)(k + t));
+      for (int j = 0; j < nn + 1; j++) m.leaves.push_back(leaves[k + t + (size_t)j]);
+      for (int j = 0; j < nn; j++, k++) {
+        const cc_tree_node& nd = nodes[k];
+        m.node_left.push_back(nd.left);
+        m.node_right.push_back(nd.right);
+        m.node_feature.push_back(map[(size_t)nd.var_idx]);
+        m.node_threshold.push_back(lbp ? 0.f : nd.ord_c);
+        if (lbp)
+          for (int w = 0; w < 8; w++) m.node_subset.push_back(nd.subset[w]);
+      }
+      m.max_nodes_per_tree = std::max(m.max_nodes_per_tree, nn);
+    }
+  }
+  if (m.max_nodes_per_tree == 1)  // the stump view, as the reader builds it
+    for (size_t i = 0; i < total; i++) {
+      m.stump_feature.push_back(m.node_feature[i]);
+      m.stump_threshold.push_back(m.node_threshold[i]);
+      m.stump_left.push_back(m.leaves[2 * i]);
+      m.stump_right.push_back(m.leaves[2 * i + 1]);
+    }
+  *out = c.release();
+  return CC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -523,95 +650,41 @@ cc_status cc_vec_write(const char* path, const uint8_t* pixels, int count, int w
 cc_status cc_cascade_from_stumps(int feature_type, int haar_mode, int win_w, int win_h, int n_stages, const int32_t* n_weak,
                                  int n_weak_total, const float* stage_threshold, const int32_t* var_idx, const float* ord_c, const int32_t* subsets,
                                  const float* left, const float* right, cc_cascade** out) {
-  if (!out) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: null argument");
+  const char* who = "cc_cascade_from_stumps";
+  if (!out) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
   *out = nullptr;
-  if (!n_weak || !stage_threshold || !var_idx || !left || !right) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: null argument");
-  if (feature_type != CC_FEATURE_HAAR && feature_type != CC_FEATURE_LBP && feature_type != CC_FEATURE_HOG)
-    return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: unknown feature type %d", feature_type);
-  const bool lbp = feature_type == CC_FEATURE_LBP;
-  if (lbp ? !subsets : !ord_c) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: %s", lbp ? "subsets required for LBP" : "ord_c required for HAAR / HOG");
-  if (feature_type == CC_FEATURE_HAAR && (haar_mode < 0 || haar_mode > 2)) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: unknown Haar mode %d", haar_mode);
-  if (win_w < 3 || win_h < 3 || win_w > 4096 || win_h > 4096) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: window %dx%d", win_w, win_h);
-  if (n_stages < 1) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: no stages");
+  if (!n_weak || !stage_threshold || !var_idx || !left || !right) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
   size_t total = 0;
-  for (int s = 0; s < n_stages; s++) {
-    if (n_weak[s] < 1) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: stage %d has %d weak classifiers", s, n_weak[s]);
-    total += (size_t)n_weak[s];
-  }
-  if (n_weak_total < 0 || total != (size_t)n_weak_total)
-    return set_error(CC_ERR_INVALID_ARG, "cc_cascade_from_stumps: n_weak adds up to %zu weak classifiers, %d were given", total, n_weak_total);
-  std::vector<HaarFeature> haar;
-  std::vector<int32_t> cat;  // LBP rects [n][4] or HOG blocks [n][4]
-  int n_vars = 0;
-  if (feature_type == CC_FEATURE_HAAR) {
-    haar_catalog(win_w, win_h, haar_mode, haar);
-    n_vars = (int)haar.size();
-  } else if (lbp) {
-    lbp_catalog(win_w, win_h, cat);
-    n_vars = (int)(cat.size() / 4);
-  } else {
-    hog_catalog(win_w, win_h, cat);
-    n_vars = (int)(cat.size() / 4) * 36;
-  }
-  // markUsedFeaturesInMap + the numbering of CvCascadeClassifier::save (cascadeclassifier.cpp:421-437): used variables in catalog order
-  std::vector<int32_t> map((size_t)n_vars, -1);
+  if (cc_status st = check_shape(who, feature_type, haar_mode, win_w, win_h, n_stages, n_weak, n_weak_total, &total); st != CC_OK) return st;
+  const bool lbp = feature_type == CC_FEATURE_LBP;
+  if (lbp ? !subsets : !ord_c) return set_error(CC_ERR_INVALID_ARG, "%s: %s", who, lbp ? "subsets required for LBP" : "ord_c required for HAAR / HOG");
+  // a stump is the tree of one node with the writer's child references 0 / -1 (o_cvcascadeboosttree.cpp:60-77)
+  std::vector<cc_tree_node> nodes(total);
+  std::vector<float> leaves(2 * total);
   for (size_t t = 0; t < total; t++) {
-    if (var_idx[t] < 0 || var_idx[t] >= n_vars)
-      return set_error(CC_ERR_OUT_OF_RANGE, "cc_cascade_from_stumps: variable %d of weak classifier %zu outside the catalog (%d)", var_idx[t], t, n_vars);
-    map[(size_t)var_idx[t]] = 0;
+    cc_tree_node& nd = nodes[t];
+    std::memset(&nd, 0, sizeof(nd));
+    nd.right = -1;
+    nd.var_idx = var_idx[t];
+    if (ord_c) nd.ord_c = ord_c[t];
+    if (subsets) std::memcpy(nd.subset, subsets + t * 8, sizeof(nd.subset));
+    leaves[2 * t] = left[t];
+    leaves[2 * t + 1] = right[t];
   }
-  std::unique_ptr<cc_cascade> c(new cc_cascade());
-  Cascade& m = c->m;
-  m.feature_type = feature_type;
-  m.win_w = win_w;
-  m.win_h = win_h;
-  m.max_cat_count = lbp ? 256 : 0;
-  m.subset_size = lbp ? 8 : 0;
-  m.max_nodes_per_tree = 1;
-  int next = 0;
-  for (int v = 0; v < n_vars; v++) {
-    if (map[(size_t)v] < 0) continue;
-    map[(size_t)v] = next++;
-    if (feature_type == CC_FEATURE_HAAR) {
-      const HaarFeature& f = haar[(size_t)v];
-      for (int j = 0; j < 3; j++) {
-        for (int k = 0; k < 4; k++) m.haar_rects.push_back(f.r[j][k]);
-        m.haar_weights.push_back(f.w[j]);
-      }
-      m.haar_tilted.push_back(f.tilted != 0);
-      m.has_tilted = m.has_tilted || f.tilted != 0;
-    } else if (lbp) {
-      for (int k = 0; k < 4; k++) m.lbp_rects.push_back(cat[(size_t)v * 4 + k]);
-    } else {
-      for (int k = 0; k < 4; k++) m.hog_feats.push_back(cat[(size_t)(v / 36) * 4 + k]);
-      m.hog_feats.push_back(v % 36);
-    }
-  }
-  size_t t = 0;
-  for (int s = 0; s < n_stages; s++) {
-    m.stage_first.push_back((int32_t)t);
-    m.stage_ntrees.push_back(n_weak[s]);
-    m.stage_threshold.push_back(stage_threshold[s] - 1e-5f);  // THRESHOLD_EPS, as the reader stores it
-    for (int i = 0; i < n_weak[s]; i++, t++) {
-      m.tree_first_node.push_back((int32_t)t);
-      m.tree_nnodes.push_back(1);
-      m.tree_first_leaf.push_back((int32_t)(2 * t));
-      m.node_left.push_back(0);  // the writer's child references of a stump (o_cvcascadeboosttree.cpp:60-77)
-      m.node_right.push_back(-1);
-      m.node_feature.push_back(map[(size_t)var_idx[t]]);
-      m.node_threshold.push_back(lbp ? 0.f : ord_c[t]);
-      if (lbp)
-        for (int j = 0; j < 8; j++) m.node_subset.push_back(subsets[t * 8 + j]);
-      m.leaves.push_back(left[t]);
-      m.leaves.push_back(right[t]);
-      m.stump_feature.push_back(map[(size_t)var_idx[t]]);
-      m.stump_threshold.push_back(lbp ? 0.f : ord_c[t]);
-      m.stump_left.push_back(left[t]);
-      m.stump_right.push_back(right[t]);
-    }
-  }
-  *out = c.release();
-  return CC_OK;
+  return cascade_from_nodes(who, feature_type, haar_mode, win_w, win_h, n_stages, n_weak, total, stage_threshold, nullptr, n_weak_total, nodes.data(),
+                            leaves.data(), out);
+}
+
+cc_status cc_cascade_from_trees(int feature_type, int haar_mode, int win_w, int win_h, int n_stages, const int32_t* n_weak, int n_weak_total,
+                                const float* stage_threshold, const int32_t* n_nodes, int n_nodes_total, const cc_tree_node* nodes, const float* leaves,
+                                cc_cascade** out) {
+  const char* who = "cc_cascade_from_trees";
+  if (!out) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
+  *out = nullptr;
+  if (!n_weak || !stage_threshold || !n_nodes || !nodes || !leaves) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
+  size_t total = 0;
+  if (cc_status st = check_shape(who, feature_type, haar_mode, win_w, win_h, n_stages, n_weak, n_weak_total, &total); st != CC_OK) return st;
+  return cascade_from_nodes(who, feature_type, haar_mode, win_w, win_h, n_stages, n_weak, total, stage_threshold, n_nodes, n_nodes_total, nodes, leaves, out);
 }
 
 cc_status cc_cascade_info_get(const cc_cascade* c, cc_cascade_info* info) {

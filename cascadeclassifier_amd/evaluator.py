@@ -244,31 +244,57 @@ def _weak_dict(w: L.Weak) -> dict:
 
 
 class CascadeBoost:
-    """One stage of CvCascadeBoost::train (boost.cpp:409-459) with stumps, on the device: weights, subsample mask, weak
-    responses and stage sums stay there; the split of every round is the evaluator's presorted search. The evaluator
-    must have been presorted over exactly n_samples; presorting or setting images again invalidates the booster."""
+    """One stage of CvCascadeBoost::train (boost.cpp:409-459) on the device, with weak trees of at most max_depth levels
+    of splits (1: stumps): weights, subsample mask, weak responses and stage sums stay there; the split of every node is
+    the evaluator's presorted search. The evaluator must have been presorted over exactly n_samples; presorting or setting
+    images again invalidates the booster. With max_depth > 1 a trained record also carries the tree in the writer's order
+    (CvCascadeBoostTree::write): "nodes", a list of dicts (left, right, depth, n_samples, var_idx, split_point, quality,
+    ord_c, subset, value), and "leaves", len(nodes) + 1 values."""
 
     STOP_GO_ON, STOP_FALSE_ALARM, STOP_MAX_WEAK, STOP_NO_ACTIVE, STOP_NOT_TRAINED = 0, 1, 2, 3, 4
     ROUND_PARTS = ("node_table_root", "split_search", "winner", "apply_split", "leaves", "update_weights", "trim", "stage_status")
 
     def __init__(self, evaluator: CvFeatureEvaluator, n_samples: int, boost_type=BOOST_GENTLE, split_criteria=SPLIT_DEFAULT,
-                 weight_trim_rate=0.95, min_hit_rate=0.995, max_false_alarm=0.5, max_weak_count=100):
+                 weight_trim_rate=0.95, min_hit_rate=0.995, max_false_alarm=0.5, max_weak_count=100, max_depth=1):
         self._b = C.c_void_p()
         self._evaluator = evaluator  # keep the evaluator alive
         self.n_samples = int(n_samples)
         self.max_weak_count = int(max_weak_count)
+        self.max_depth = int(max_depth)
         p = L.BoostParams(int(boost_type), int(split_criteria), float(weight_trim_rate), float(min_hit_rate), float(max_false_alarm),
                           int(max_weak_count))
-        L.check(L.lib().cc_boost_create(evaluator._e, self.n_samples, C.byref(p), C.byref(self._b)))
+        L.check(L.lib().cc_boost_create_depth(evaluator._e, self.n_samples, C.byref(p), self.max_depth, C.byref(self._b)))
+
+    def last_tree(self):
+        """(nodes, leaves) of the last trained round's tree (cc_boost_last_tree)."""
+        k = C.c_int(0)
+        st = L.lib().cc_boost_last_tree(self._b, None, 0, None, 0, C.byref(k))
+        if st != L.CC_ERR_BUFFER_TOO_SMALL:
+            L.check(st)
+        nodes = (L.TreeNode * k.value)()
+        leaves = np.empty(k.value + 1, np.float64)
+        L.check(L.lib().cc_boost_last_tree(self._b, nodes, k.value, _vp(leaves), len(leaves), C.byref(k)))
+        names = [n for n, _ in L.TreeNode._fields_ if n != "subset"]
+        return [dict({n: getattr(nd, n) for n in names}, subset=np.array(list(nd.subset), np.int32)) for nd in nodes], leaves
 
     def round(self) -> dict:
         """One weak classifier: the record of cc_boost_round as a dict."""
         w = L.Weak()
         L.check(L.lib().cc_boost_round(self._b, C.byref(w)))
-        return _weak_dict(w)
+        rec = _weak_dict(w)
+        if self.max_depth > 1 and rec["trained"]:
+            rec["nodes"], rec["leaves"] = self.last_tree()
+        return rec
 
     def train_stage(self) -> list:
         """Rounds until one says stop; the records of all of them (the last one carries the stage threshold)."""
+        if self.max_depth > 1:  # a round's tree has to be fetched before the next round replaces it
+            recs = []
+            while len(recs) <= self.max_weak_count:
+                recs.append(self.round())
+                if recs[-1]["stop"] != 0:
+                    break
+            return recs
         cap = self.max_weak_count + 1
         arr = (L.Weak * cap)()
         k = C.c_int(0)

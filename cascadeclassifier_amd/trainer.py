@@ -130,22 +130,22 @@ class BackgroundReader:
 
 def train_cascade(positives, backgrounds, num_pos, num_neg, num_stages, *, feature_type=HAAR, win=(24, 24), haar_mode=BASIC,
                   boost_type=BOOST_GENTLE, min_hit_rate=0.995, max_false_alarm=0.5, weight_trim_rate=0.95, max_weak_count=100,
-                  acceptance_ratio_break_value=-1.0, device=0, max_batch=256, on_stage=None):
-    """CvCascadeClassifier::train for stages of stumps (cascadeclassifier.cpp:203-284). positives: [n][win_h][win_w]
+                  acceptance_ratio_break_value=-1.0, device=0, max_batch=256, on_stage=None, max_depth=1):
+    """CvCascadeClassifier::train (cascadeclassifier.cpp:203-284) for stages of weak trees with at most max_depth levels of
+    splits (the reference's -maxDepth; 1: stumps). positives: [n][win_h][win_w]
     uint8, taken from the first one again for every stage; backgrounds: 2-D uint8 images, read as NegReader reads its list.
     Returns (cascade or None, stage records, end reason); a record holds pos_count, pos_consumed, neg_count, neg_consumed,
     acceptance_ratio and, for a trained stage, weak (the records of CascadeBoost.train_stage). on_stage(i, record, cascade)
     is called after every trained stage. Raises ValueError when the positives run out before num_pos of them pass."""
     positives = np.ascontiguousarray(positives, np.uint8)
     win = (int(win[0]), int(win[1]))
-    if num_pos < 1 or num_neg < 0 or max_batch < 1:
-        raise ValueError("train_cascade: num_pos >= 1, num_neg >= 0, max_batch >= 1")
+    if num_pos < 1 or num_neg < 0 or max_batch < 1 or max_depth < 1:
+        raise ValueError("train_cascade: num_pos >= 1, num_neg >= 0, max_batch >= 1, max_depth >= 1")
     reader = BackgroundReader(backgrounds, win)
     e = CvFeatureEvaluator.create(feature_type, device)
     e.init(CvFeatureParams(feature_type, haar_mode), num_pos + num_neg, win)
     miner = NegativeMiner.empty(feature_type, win, device)
-    # stumps: max_depth == 1 (cascadeclassifier.cpp:209-210)
-    required_leaf_fa_rate = math.pow(float(np.float32(max_false_alarm)), float(num_stages))
+    required_leaf_fa_rate = math.pow(float(np.float32(max_false_alarm)), float(num_stages)) / float(max_depth)  # cascadeclassifier.cpp:209-210
     cascade, stages, records = None, [], []
     end = END_NUM_STAGES
     for i in range(num_stages):
@@ -181,13 +181,14 @@ def train_cascade(positives, backgrounds, num_pos, num_neg, num_stages, *, featu
         n = pos_count + neg_count
         e.presort(n)
         weak = CascadeBoost(e, n, boost_type=boost_type, weight_trim_rate=weight_trim_rate, min_hit_rate=min_hit_rate,
-                            max_false_alarm=max_false_alarm, max_weak_count=max_weak_count).train_stage()
+                            max_false_alarm=max_false_alarm, max_weak_count=max_weak_count, max_depth=max_depth).train_stage()
         if not any(w["trained"] for w in weak):
             end = END_STAGE_NOT_TRAINED
             break
         record["weak"] = weak
         stages.append((weak[-1]["stage_threshold"], weak))
-        cascade = CascadeClassifier.from_stumps(feature_type, win, stages, haar_mode=haar_mode, device=device)
+        build = CascadeClassifier.from_trees if max_depth > 1 else CascadeClassifier.from_stumps
+        cascade = build(feature_type, win, stages, haar_mode=haar_mode, device=device)
         miner = NegativeMiner(cascade, device)
         if on_stage is not None:
             on_stage(i, record, cascade)

@@ -607,11 +607,21 @@ CC_API cc_status cc_eval_find_best_split(cc_evaluator* e, const int32_t* sample_
                                          int32_t* per_var_point);
 
 /* ============================================================================================
- * 6b. Boosting a stage: one stage of stumps (maxDepth 1, the trainer's default) trained on the device.
+ * 6b. Boosting a stage: one stage of weak trees trained on the device; cc_boost_create grows stumps (maxDepth 1, the
+ *    trainer's default), cc_boost_create_depth trees of up to max_depth levels of splits.
  *    Replaces the loop of CvCascadeBoost::train (traincascade/lib/src/boost.cpp:409-459) with
  *    CvCascadeBoost::update_weights (:160-407) and isErrDesired (:479-518), CvBoost::trim_weights (o_cvboost.cpp:101-139),
- *    CvBoostTree::calc_node_value (o_cvboostree.cpp:657-732), calc_node_dir (:87-149) and CvCascadeBoostTree::predict
- *    (o_cvcascadeboosttree.cpp:16-39) for trees of one split. The split of every round is section 6's search.
+ *    CvDTree::try_split_node (o_cvdtree.cpp:122-187), CvBoostTree::calc_node_value (o_cvboostree.cpp:657-732),
+ *    calc_node_dir (:87-149) and CvCascadeBoostTree::predict (o_cvcascadeboosttree.cpp:16-39). The split of every node
+ *    is section 6's search, one launch per node.
+ *
+ *    A node stays a leaf when it holds at most 10 samples (min_sample_count), stands at depth max_depth, holds one class
+ *    only (DISCRETE / REAL), has sqrt(node_risk) / n < 0.01f (GENTLE; regression_accuracy) or finds no split with
+ *    quality > 0. No pruning, no surrogates, no cross-validation folds: what the reference's cascade trainer runs with
+ *    (o_cvdtreeparams.cpp:7-13). A child's samples keep increasing sample order (o_cvcascadeboosttree.cpp:300-338), so its
+ *    sums are formed in that order. Samples of the subsample reach their leaf by direction (rank in the node's sorted
+ *    order <= split_point, ties in increasing sample order; categorical: the subset bit); the samples outside it and the
+ *    stage sums of all samples by the predict walk (value <= ord_c / subset bit at every level).
  *
  *    cc_boost_create needs cc_eval_presort(_range) over exactly n_samples; the classes are the evaluator's labels
  *    (getCls == 1.0f positive, 0.0f negative); with a presorted variable range the booster searches that range. Weights
@@ -639,15 +649,34 @@ typedef struct cc_weak { /* one round's fixed-size record */
   double left_value, right_value; /* node->value of the leaves; after tree->scale(C) for DISCRETE */
   float stage_threshold, hit_rate, false_alarm; /* isErrDesired, boost.cpp:479-518; unchanged when stop == 3 or 4 */
 } cc_weak;
+/* one internal node of a round's tree, in the order CvCascadeBoostTree::write lists them (o_cvcascadeboosttree.cpp:41-93):
+ * breadth-first from the root */
+typedef struct cc_tree_node {
+  int32_t left, right;          /* > 0: internal node index inside this tree; <= 0: leaf -value */
+  int32_t depth, n_samples;     /* node->depth, node->sample_count */
+  int32_t var_idx, split_point; /* as cc_weak */
+  float quality, ord_c;
+  int32_t subset[8];
+  double value;                 /* node->value; DISCRETE: after tree->scale(C) */
+} cc_tree_node;
+/* cc_boost_create(e, n, p, out) is cc_boost_create_depth(e, n, p, 1, out). max_depth < 1: CC_ERR_INVALID_ARG; values above
+ * 25 are clamped to 25 (o_cvdtreetraindata.cpp:105). */
 CC_API cc_status cc_boost_create(cc_evaluator* e, int n_samples, const cc_boost_params* p, cc_boost** out);
+CC_API cc_status cc_boost_create_depth(cc_evaluator* e, int n_samples, const cc_boost_params* p, int max_depth, cc_boost** out);
 CC_API void cc_boost_destroy(cc_boost* b);
+/* The record describes the tree's root: its split, and in left_value / right_value the node->value of its two children,
+ * whether or not they split (for a stump: the leaves). */
 CC_API cc_status cc_boost_round(cc_boost* b, cc_weak* out);
+/* The tree of the last trained round: n_nodes internal nodes and n_nodes + 1 leaf values in the writer's order; changes
+ * nothing. CC_ERR_BUFFER_TOO_SMALL (a cap too small, or a NULL buffer) still sets *n_nodes; CC_ERR_INVALID_ARG before
+ * any round has trained a tree. */
+CC_API cc_status cc_boost_last_tree(cc_boost* b, cc_tree_node* nodes, int node_cap, double* leaves, int leaf_cap, int* n_nodes);
 /* rounds until stop != 0, at most cap of them */
 CC_API cc_status cc_boost_train_stage(cc_boost* b, cc_weak* out, int cap, int* n_weak);
 /* parity instrumentation: any pointer may be NULL; n_samples values each */
 CC_API cc_status cc_boost_get_state(cc_boost* b, double* weights, double* weak_eval, uint8_t* mask, double* stage_sum);
-/* device time of the last round's parts in ms: node table + root value, split search, winner, apply the split, leaves,
- * weight update + stage sums, trimming, stage status (8 values) */
+/* device time of the last round's parts in ms: node tables + root value, split search, winner, apply the split, children's
+ * values, weight update + stage sums, trimming, stage status (8 values); the first five summed over the tree's nodes */
 CC_API cc_status cc_boost_last_round_ms(cc_boost* b, double* ms, int cap, int* n_parts);
 /* the device's exp(double), for the witness of update_weights */
 CC_API cc_status cc_debug_exp64(int device, const double* x, int n, double* out);
@@ -659,6 +688,15 @@ CC_API cc_status cc_debug_exp64(int device, const double* x, int n, double* out)
 CC_API cc_status cc_cascade_from_stumps(int feature_type, int haar_mode, int win_w, int win_h, int n_stages, const int32_t* n_weak,
                                         int n_weak_total, const float* stage_threshold, const int32_t* var_idx, const float* ord_c,
                                         const int32_t* subsets, const float* left, const float* right, cc_cascade** out);
+/* The same for trees (CvCascadeBoostTree::write, o_cvcascadeboosttree.cpp:41-93): tree t has n_nodes[t] >= 1 internal
+ * nodes, as cc_boost_last_tree returns them (left, right, var_idx and ord_c or subset are read), and n_nodes[t] + 1 leaves;
+ * nodes and leaves of all trees follow each other in stage order, n_nodes_total and n_nodes_total + n_weak_total of them.
+ * The used variables of ALL nodes are renumbered in catalog order (markFeaturesInMap, :349-359). Child references the XML
+ * reader refuses (out of range, not larger than the node's own index) are refused here: CC_ERR_OUT_OF_RANGE. When every
+ * tree has one node the model equals cc_cascade_from_stumps' model, stump view included. */
+CC_API cc_status cc_cascade_from_trees(int feature_type, int haar_mode, int win_w, int win_h, int n_stages, const int32_t* n_weak,
+                                       int n_weak_total, const float* stage_threshold, const int32_t* n_nodes, int n_nodes_total,
+                                       const cc_tree_node* nodes, const float* leaves, cc_cascade** out);
 
 /* ============================================================================================
  * 6c. Filling a stage's training set.

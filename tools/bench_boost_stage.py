@@ -7,8 +7,10 @@ w *= exp(-y f), renormalisation; boost.cpp:378-398, o_cvboostree.cpp:657-732) is
 restated here in numpy with sequential double sums: that loop is the BASELINE. The same rounds then run through
 CascadeBoost (cc_boost.hip), where the bookkeeping is on the device too: once without trimming (the baseline's
 arithmetic; the chosen variables must agree) and once with the trainer's weight_trim_rate 0.95, with the device time of
-every kernel of a round beside the split search's. Prints one JSON line.
-usage: bench_boost_stage.py [rounds=20] [n_samples=20000] [easy|hard] [HAAR|LBP]
+every kernel of a round beside the split search's. With max_depth > 1 the device booster grows trees of that depth (the
+numpy baseline stays a stump stage, so the chosen variables are compared at depth 1 only) and the time per round is also
+given per searched node. Prints one JSON line.
+usage: bench_boost_stage.py [rounds=20] [n_samples=20000] [easy|hard] [HAAR|LBP] [max_depth=1]
   easy = SURVEY config 5 as specified (template + N(0,15^2) vs uniform noise: one stump separates it);
   hard = positives template + N(0,40^2), negatives a half-and-half blend with a second template + N(0,40^2)."""
 import json
@@ -28,13 +30,14 @@ def seq_sum(a):
     return float(np.cumsum(a, dtype=np.float64)[-1]) if len(a) else 0.0
 
 
-def device_rounds(cc, e, N, rounds, trim):
-    """`rounds` rounds of CascadeBoost: wall time per round and per stage, device time of each part of a round."""
+def device_rounds(cc, e, N, rounds, trim, max_depth=1):
+    """`rounds` rounds of CascadeBoost: wall time per round and per stage, device time of each part of a round. A round's
+    wall time includes fetching its tree when max_depth > 1."""
     t0 = time.perf_counter()
-    b = cc.CascadeBoost(e, N, weight_trim_rate=trim, max_weak_count=rounds + 1, max_false_alarm=1e-6)
+    b = cc.CascadeBoost(e, N, weight_trim_rate=trim, max_weak_count=rounds + 1, max_false_alarm=1e-6, max_depth=max_depth)
     t_create = time.perf_counter() - t0
     parts = {k: 0.0 for k in cc.CascadeBoost.ROUND_PARTS}
-    wall, chosen, active = [], [], []
+    wall, chosen, active, nodes = [], [], [], []
     for _ in range(rounds):
         t0 = time.perf_counter()
         rec = b.round()
@@ -45,10 +48,12 @@ def device_rounds(cc, e, N, rounds, trim):
             parts[k] += v
         chosen.append(int(rec["var_idx"]))
         active.append(int(rec["n_active"]))
+        nodes.append(len(rec["nodes"]) if "nodes" in rec else 1)
     k = max(len(chosen), 1)
-    return {"weight_trim_rate": trim, "rounds_trained": len(chosen), "create_ms": round(t_create * 1e3, 3),
+    return {"weight_trim_rate": trim, "max_depth": max_depth, "rounds_trained": len(chosen), "create_ms": round(t_create * 1e3, 3),
             "per_round_ms_wall": round(float(np.mean(wall)) * 1e3, 3), "per_round_ms_wall_min": round(float(np.min(wall)) * 1e3, 3),
-            "stage_ms_wall": round(float(np.sum(wall)) * 1e3, 3),
+            "stage_ms_wall": round(float(np.sum(wall)) * 1e3, 3), "internal_nodes_per_round": nodes,
+            "per_internal_node_ms_wall": round(float(np.sum(wall[:len(nodes)])) / max(sum(nodes), 1) * 1e3, 3),
             "per_round_kernel_ms": {name: round(v / k, 4) for name, v in parts.items()},
             "active_samples_per_round": active, "chosen_variables": chosen}
 
@@ -61,6 +66,7 @@ def main():
     imgs, labels = samples(n=N // 2)
     hard = len(sys.argv) > 3 and sys.argv[3] == "hard"
     lbp = len(sys.argv) > 4 and sys.argv[4] == "LBP"  # the same stage over the 8 464 categorical LBP variables
+    depth = int(sys.argv[5]) if len(sys.argv) > 5 else 1
     ftype = ev.LBP if lbp else ev.HAAR
     if hard:
         rng = np.random.default_rng(7)
@@ -130,11 +136,12 @@ def main():
            "baseline_per_round_ms": round((t_split + t_row + t_host) / rounds * 1e3, 3),
            "baseline_stage_ms": round((t_split + t_row + t_host) * 1e3, 3),
            "chosen_variables": chosen, "training_error_after_each_round": [round(x, 4) for x in errs]}
-    dev = device_rounds(cc, e, N, rounds, 1.0)  # no trimming: the baseline's arithmetic
+    dev = device_rounds(cc, e, N, rounds, 1.0, depth)  # no trimming: the baseline's arithmetic
     k = dev["rounds_trained"]
-    dev["same_variables_as_baseline"] = dev["chosen_variables"] == chosen[:k] and k == rounds
+    if depth == 1:
+        dev["same_variables_as_baseline"] = dev["chosen_variables"] == chosen[:k] and k == rounds
     out["device_booster"] = dev
-    out["device_booster_trim_0.95"] = device_rounds(cc, e, N, rounds, 0.95)
+    out["device_booster_trim_0.95"] = device_rounds(cc, e, N, rounds, 0.95, depth)
     print(json.dumps(out))
 
 
