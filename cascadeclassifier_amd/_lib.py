@@ -89,6 +89,25 @@ class HaarFeatureC(C.Structure):
     _fields_ = [("tilted", C.c_int32), ("r", (C.c_int32 * 4) * 3), ("w", C.c_float * 3)]
 
 
+class SampleParams(C.Structure):
+    _fields_ = [("bgcolor", C.c_int32), ("bgthreshold", C.c_int32), ("invert", C.c_int32), ("maxintensitydev", C.c_int32),
+                ("maxxangle", C.c_double), ("maxyangle", C.c_double), ("maxzangle", C.c_double), ("inscribe", C.c_int32),
+                ("reserved", C.c_int32), ("maxshift", C.c_double), ("maxscale", C.c_double)]
+
+
+class SampleRecord(C.Structure):
+    _fields_ = [("quad", C.c_double * 8), ("coeffs", C.c_double * 9), ("inverse", C.c_int32), ("forecolordev", C.c_int32),
+                ("roi_x", C.c_int32), ("roi_y", C.c_int32), ("roi_w", C.c_int32), ("roi_h", C.c_int32),
+                ("bg_image", C.c_int32), ("bg_w", C.c_int32), ("bg_h", C.c_int32), ("bg_x", C.c_int32), ("bg_y", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class SampleBgReader(C.Structure):
+    _fields_ = [("sizes", C.c_void_p), ("n_images", C.c_int32)] + \
+               [(n, C.c_int32) for n in ("have", "round", "last", "off_x", "off_y", "pt_x", "pt_y", "cur_w", "cur_h")] + \
+               [("scale", C.c_float)]
+
+
 # every symbol include/cascadeclassifier_amd.h declares: name -> (restype, argtypes)
 _vp, _i, _sz, _d = C.c_void_p, C.c_int, C.c_size_t, C.c_double
 _pp = C.POINTER(C.c_void_p)
@@ -208,8 +227,15 @@ SIGNATURES = {
     "cc_debug_fill_select": (_i, [_i, _vp, C.c_int64, C.c_int64, _i, C.c_int64, C.c_int64, _d, C.POINTER(_i), C.POINTER(C.c_int64),
                                   C.POINTER(_i), _vp]),
     "cc_debug_fill_scan_tile": (_i, []),
+    "cc_warp_perspective_u8": (_i, [_i, _vp, _i, _i, _sz, _vp, _i, _i, _sz, _vp]),
+    "cc_sample_plan": (_i, [_i, _i, _i, _i, C.POINTER(SampleParams), C.POINTER(C.c_uint64), C.POINTER(SampleBgReader), _i, _vp, _vp]),
+    "cc_sampler_create": (_i, [_i, _vp, _i, _i, _sz, _i, _i, _pp]),
+    "cc_sampler_destroy": (None, [_vp]),
+    "cc_sampler_set_backgrounds": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "cc_sampler_render": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
 }
 CC_FILL_FILLED, CC_FILL_RATIO, CC_FILL_EXHAUSTED = 0, 1, 2
+CC_SAMPLE_RANDOM_INVERT = 0x7FFFFFFF
 
 _lib = None
 

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "cc_detect_internal.h"
+#include "cc_resize_arith.h"
 
 namespace ccamd {
 
@@ -93,10 +94,10 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ fram
       const unsigned b_lo = __builtin_amdgcn_perm(v.d[1], v.d[0], sel1), b_hi = __builtin_amdgcn_perm(v.d[3], v.d[2], sel1);
       const unsigned t0 = (a_lo & low0) | (a_hi & ~low0), t1 = (b_lo & low1) | (b_hi & ~low1);
 #pragma unroll
-      for (int k = 0; k < 4; k++) h[k] = wx0[k] * ((t0 >> (8 * k)) & 255u) + wx1[k] * ((t1 >> (8 * k)) & 255u);
+      for (int k = 0; k < 4; k++) h[k] = resize_lerp_h(wx0[k], wx1[k], (t0 >> (8 * k)) & 255u, (t1 >> (8 * k)) & 255u);
     } else {
 #pragma unroll
-      for (int k = 0; k < 4; k++) h[k] = wx0[k] * r[x0[k]] + wx1[k] * r[x1[k]];
+      for (int k = 0; k < 4; k++) h[k] = resize_lerp_h(wx0[k], wx1[k], r[x0[k]], r[x1[k]]);
     }
   };
   unsigned hc[4] = {0, 0, 0, 0};
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ fram
     unsigned packed = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      const unsigned v = (xw * 4 + k < S.w) ? (h0[k] * wy0 + h1[k] * wy1 + (1u << 15)) >> 16 : 0u;
+      const unsigned v = (xw * 4 + k < S.w) ? resize_lerp_v(wy0, wy1, h0[k], h1[k]) : 0u;
       packed |= v << (8 * k);
       cs[k] += v;
       cq[k] += v * v;

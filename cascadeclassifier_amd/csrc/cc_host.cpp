@@ -9,6 +9,7 @@
 #include <numeric>
 
 #include "cc_internal.h"
+#include "cc_resize_arith.h"
 
 namespace ccamd {
 
@@ -88,19 +89,7 @@ void scale_plan(int W0, int H0, int imgw, int imgh, const cc_detect_params& p, s
 void linear_exact_taps(int src, int dst, AxisTaps& t) {
   t.ofs.resize(dst);
   t.w1.resize(dst);
-  const double inv_scale = (double)dst / (double)src;
-  const double scale = 1.0 / inv_scale;
-  for (int d = 0; d < dst; d++) {
-    const double f = scale * ((double)d + 0.5) - 0.5;
-    const int i = (int)std::floor(f);
-    if (i >= 0 && src > 1 && i < src - 1) {
-      t.ofs[d] = i;
-      t.w1[d] = (uint16_t)rnd_d((f - (double)i) * 256.0);
-    } else {  // outside [0, src-1): replicate the border pixel
-      t.ofs[d] = (i >= 0 && src > 1) ? src - 1 : 0;
-      t.w1[d] = 0;
-    }
-  }
+  for (int d = 0; d < dst; d++) linear_exact_tap(src, dst, d, t.ofs[d], t.w1[d]);
 }
 
 // Pass sizes. With results wanted the batch is cut into a few passes so that the host side of pass i (copy-back +

@@ -350,6 +350,13 @@ CC_API cc_status cc_integral_u8(int device, const uint8_t* img, int width, int h
                                 int32_t* sqsum, int32_t* tilted);
 CC_API cc_status cc_resize_linear_exact_u8(int device, const uint8_t* src, int sw, int sh, size_t sstride, uint8_t* dst,
                                            int dw, int dh, size_t dstride);
+/* cvWarpPerspective of the sample tool (tools/createsamples/utility.cpp:225-417) on one HOST image: the source is mapped
+ * into the quadrangle quad[4][2] (x, y per vertex, in order) of the caller-initialised dst; pixels outside the quadrangle's
+ * row spans keep their value. Coefficients and spans come from the host arithmetic of cc_sample_plan (section 8), the pixels
+ * from the device function the sample renderer uses. A nonconvex or degenerate quadrangle is CC_ERR_INVALID_ARG (the
+ * reference throws, :274-276), checked before the device is. Sides 1..16384. */
+CC_API cc_status cc_warp_perspective_u8(int device, const uint8_t* src, int sw, int sh, size_t sstride, uint8_t* dst, int dw,
+                                        int dh, size_t dstride, const double* quad);
 /* The detector's colour conversion (CC_PIX_*, section 2) on one HOST image: dst receives height rows of width gray bytes,
  * dst_stride apart. The device copy of src keeps its byte offset modulo 16 and its row stride, so that odd base addresses
  * and strides reach the kernel as they are. CC_PIX_GRAY8 is copied unchanged (its three weights sum to 2^14). */
@@ -783,6 +790,76 @@ CC_API int cc_comm_world(const cc_comm* c);
 CC_API cc_status cc_gather_detections(cc_comm* c, const cc_rect* rects, const int32_t* offsets, int n_frames, cc_rect* out,
                                       int cap_rects, int32_t* offsets_out, int cap_frames, int* n_frames_all, int* n_rects_all);
 CC_API cc_status cc_gather_fetch(const cc_comm* c, cc_rect* out, int cap_rects, int32_t* offsets_out, int cap_frames);
+
+/* ============================================================================================
+ * 8. Sample synthesis: the positives of the trainer from one object image.
+ *    Replaces cvCreateTrainingSamples (tools/createsamples/utility.cpp:952-1027) and what it calls:
+ *    icvStartSampleDistortion (:516-578) -> cc_sampler_create; icvRandomQuad (:419-466), cvGetPerspectiveTransform
+ *    (:180-223), the scanline walk of cvWarpPerspective (:255-416), the rectangle arithmetic of icvPlaceDistortedSample
+ *    (:615-648) and the background reader (:765-886) -> cc_sample_plan (host, serial: every random draw);
+ *    the warp's pixels (:351-387), GaussianBlur, the two resizes and the blend (:650-671) -> cc_sampler_render (device).
+ *    The random numbers are cv::RNG's (seed 12345 in the tool, createsamples.cpp:88,158): with the tool's image and
+ *    options the samples are the tool's, byte for byte.
+ * ============================================================================================ */
+#define CC_SAMPLE_RANDOM_INVERT 0x7FFFFFFF /* CV_RANDOM_INVERT */
+typedef struct cc_sample_params {
+  int32_t bgcolor, bgthreshold;
+  int32_t invert; /* 0, 1 or CC_SAMPLE_RANDOM_INVERT */
+  int32_t maxintensitydev;
+  double maxxangle, maxyangle, maxzangle;
+  int32_t inscribe; /* cvCreateTrainingSamples passes 0, 0.0, 0.0 for these three (:1000-1002) */
+  int32_t reserved;
+  double maxshift, maxscale;
+} cc_sample_params;
+
+/* One sample, as planned on the host. */
+typedef struct cc_sample_record {
+  double quad[8];   /* x, y of the four vertices on the canvas */
+  double coeffs[9]; /* canvas -> source, row-major 3x3, coeffs[8] = 1 */
+  int32_t inverse, forecolordev;
+  int32_t roi_x, roi_y, roi_w, roi_h; /* source rectangle of the resize, clipped to the canvas */
+  int32_t bg_image, bg_w, bg_h, bg_x, bg_y; /* background window: image (-1: none), the size it is scaled to, origin */
+  int32_t reserved;
+} cc_sample_record;
+
+/* The tool's background reader (CvBackgroundData + CvBackgroundReader) between calls of cc_sample_plan. The caller sets
+ * n_images and sizes (width, height per image) and zeroes the rest before the first call. */
+typedef struct cc_sample_bg_reader {
+  const int32_t* sizes;
+  int32_t n_images;
+  int32_t have, round, last, off_x, off_y, pt_x, pt_y, cur_w, cur_h;
+  float scale;
+} cc_sample_bg_reader;
+
+/* Host only, no device. Makes every random draw and all sequential arithmetic of n samples of an out_w x out_h window from
+ * a src_w x src_h object image. Per sample, in the tool's order: the background window (when bg != NULL; a new image is
+ * picked with uniform(0, RAND_MAX) % n_images), uniform(0, 2) for `inverse` when invert is random, icvRandomQuad, xshift,
+ * yshift, randscale, forecolordev. *rng_state is cv::RNG's state (seed, or 0xffffffff for seed 0) and is carried on: two
+ * calls of 37 and 63 samples give what one call of 100 gives. records: n entries. spans (may be NULL): per sample and row
+ * of the canvas (src_h + 2 * (src_h / 2) rows of src_w + 2 * (src_w / 2) pixels) ix_min, ix_max of the scanline walk,
+ * 0, -1 for a row it does not visit. A nonconvex or degenerate quadrangle, a singular system or a rectangle that misses
+ * the canvas is CC_ERR_INVALID_ARG; *rng_state and *bg are then as before the call. Sides: source 2..8192, window 1..4096. */
+CC_API cc_status cc_sample_plan(int src_w, int src_h, int out_w, int out_h, const cc_sample_params* params, uint64_t* rng_state,
+                                cc_sample_bg_reader* bg, int n, cc_sample_record* records, int32_t* spans);
+
+typedef struct cc_sampler cc_sampler;
+/* icvStartSampleDistortion on the device: the mask (0 within bgthreshold of bgcolor, else 255), and the image with its
+ * background pixels replaced by the 3x3 minimum / maximum where that differs from bgcolor by more than the threshold
+ * (differences taken modulo 256, as the reference's uchar casts do). Both stay in device memory. Sides 2..8192. */
+CC_API cc_status cc_sampler_create(int device, const uint8_t* img, int w, int h, size_t stride, int bgcolor, int bgthreshold,
+                                   cc_sampler** out);
+CC_API void cc_sampler_destroy(cc_sampler* s);
+/* The images behind the records' bg_image (the tool's -bg list), kept in device memory; replaces an earlier set. */
+CC_API cc_status cc_sampler_set_backgrounds(cc_sampler* s, const uint8_t* const* images, const int32_t* widths,
+                                            const int32_t* heights, int n_images);
+/* Renders n planned samples into out (n * out_h * out_w bytes, host). records / spans as cc_sample_plan filled them for
+ * this sampler's image size and this window. backgrounds: n windows of out_h * out_w bytes (host), or NULL: each sample is
+ * then blended onto its record's window of the cc_sampler_set_backgrounds images (scaled by the exact resize, cropped on
+ * the device), or onto bgcolor when bg_image is -1. One grid per batch of samples; the batch is sized from free device
+ * memory, at most 32768 samples and, when max_batch > 0, at most max_batch. Records whose rectangle or window leaves its
+ * image are CC_ERR_INVALID_ARG. */
+CC_API cc_status cc_sampler_render(cc_sampler* s, const cc_sample_record* records, const int32_t* spans, int n, int out_w,
+                                   int out_h, const uint8_t* backgrounds, int max_batch, uint8_t* out);
 
 #ifdef __cplusplus
 }
