@@ -512,7 +512,7 @@ static_assert(sizeof(NodeRec) <= 64 &&sizeof(SplitRec) <= 128 && sizeof(TailRec)
 static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
   cc_evaluator* e = b->e;
   const int n = b->n;
-  hipStream_t st = e->stream;
+  hipStream_t st = e->stream.s;
   if (b->generation != e->generation || e->presort_n != n)
     return set_error(CC_ERR_INVALID_ARG, "cc_boost_round: the evaluator's samples or presorted tables changed after cc_boost_create; create a new booster");
   std::memset(out, 0, sizeof(*out));
@@ -642,7 +642,7 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
     std::memcpy(&sr, pin, sizeof(sr));
     {
       float ms = 0;
-      if (hipEventElapsedTime(&ms, e->ev_a, e->ev_b) == hipSuccess) e->last_ms = ms;
+      if (hipEventElapsedTime(&ms, e->ev_a.e, e->ev_b.e) == hipSuccess) e->last_ms = ms;
       b->last_ms[1] += e->last_ms;
     }
     if (!b->categorical) {
@@ -820,7 +820,7 @@ cc_status cc_boost_create_depth(cc_evaluator* e, int n_samples, const cc_boost_p
   }
   b->n_pos = (int)pos.size();
   b->n_neg = n - b->n_pos;
-  hipStream_t st = e->stream;
+  hipStream_t st = e->stream.s;
   CC_HIP(b->w.ensure((size_t)n));
   CC_HIP(b->weak_eval.ensure((size_t)n));
   CC_HIP(b->stage_sum.ensure((size_t)n));
@@ -878,7 +878,7 @@ cc_status cc_boost_get_state(cc_boost* b, double* weights, double* weak_eval, ui
   if (!b) return set_error(CC_ERR_INVALID_ARG, "cc_boost_get_state: null booster");
   if (cc_status st = eval_device(b->e); st != CC_OK) return st;
   std::lock_guard<std::mutex> lk(b->e->mu);
-  hipStream_t st = b->e->stream;
+  hipStream_t st = b->e->stream.s;
   const size_t n = (size_t)b->n;
   if (weights) CC_HIP(hipMemcpyAsync(weights, b->w.p, n * 8, hipMemcpyDeviceToHost, st));
   if (weak_eval) CC_HIP(hipMemcpyAsync(weak_eval, b->weak_eval.p, n * 8, hipMemcpyDeviceToHost, st));

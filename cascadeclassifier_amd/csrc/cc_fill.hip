@@ -177,24 +177,6 @@ cc_status fill_select(FillWork& w, const uint8_t* d_flags, long long n, long lon
 
 namespace {
 
-// e's sample tables <-> its scratch rows, for the set-image and predict code, which know only e's tables. Under e->mu.
-struct ScratchRows {
-  cc_evaluator* e;
-  explicit ScratchRows(cc_evaluator* ev) : e(ev) { swap(); }
-  ~ScratchRows() { swap(); }
-  template <class B>
-  static void swap_buf(B& a, B& b) {
-    std::swap(a.p, b.p);
-    std::swap(a.n, b.n);
-  }
-  void swap() {
-    swap_buf(e->d_sum, e->fill_sum);
-    swap_buf(e->d_tilted, e->fill_tilted);
-    swap_buf(e->d_nf, e->fill_nf);
-    swap_buf(e->d_hog, e->fill_hog);
-  }
-};
-
 constexpr int FILL_CHUNK = 2048;  // candidates set, predicted and selected per step of cc_eval_fill_passed
 
 }  // namespace
@@ -250,12 +232,13 @@ cc_status cc_eval_fill_passed(cc_evaluator* e, const cc_cascade* stages, const u
   const bool hog = e->type == CC_FEATURE_HOG, haar = e->type == CC_FEATURE_HAAR;
   const size_t px = (size_t)e->W * e->H, cols = (size_t)e->cols;
   const int chunk = std::min(n_imgs, FILL_CHUNK);
+  SampleTables& rows = e->fill_rows;  // rows 0 .. chunk: the candidates are set and predicted here
   if (hog)
-    CC_HIP(e->fill_hog.ensure((size_t)chunk * cols * 10));
+    CC_HIP(rows.hog.ensure((size_t)chunk * cols * 10));
   else {
-    CC_HIP(e->fill_sum.ensure((size_t)chunk * cols));
-    if (e->use_tilted) CC_HIP(e->fill_tilted.ensure((size_t)chunk * cols));
-    if (haar) CC_HIP(e->fill_nf.ensure((size_t)chunk));
+    CC_HIP(rows.sum.ensure((size_t)chunk * cols));
+    if (e->use_tilted) CC_HIP(rows.tilted.ensure((size_t)chunk * cols));
+    if (haar) CC_HIP(rows.nf.ensure((size_t)chunk));
   }
   CC_HIP(e->d_imgs.ensure((size_t)chunk * px));
   CC_HIP(e->d_pred.ensure((size_t)chunk));
@@ -263,16 +246,13 @@ cc_status cc_eval_fill_passed(cc_evaluator* e, const cc_cascade* stages, const u
   long long consumed = 0;
   for (int c0 = 0; c0 < n_imgs && got < want; c0 += chunk) {
     const int n = std::min(chunk, n_imgs - c0);
-    CC_HIP(hipMemcpyAsync(e->d_imgs.p, imgs + (size_t)c0 * px, (size_t)n * px, hipMemcpyHostToDevice, e->stream));
-    {
-      ScratchRows scratch(e);  // rows 0 .. n of the scratch tables
-      st = launch_set_images(e, e->d_imgs.p, n, 0);
-      if (st == CC_OK && stages) st = predict_stored(e, stages->m, nullptr, n, nullptr);
-    }
+    CC_HIP(hipMemcpyAsync(e->d_imgs.p, imgs + (size_t)c0 * px, (size_t)n * px, hipMemcpyHostToDevice, e->stream.s));
+    st = launch_set_images(e, rows, e->d_imgs.p, n, 0);
+    if (st == CC_OK && stages) st = predict_stored(e, rows, stages->m, nullptr, n, nullptr);
     if (st != CC_OK) return st;
-    if (!stages) CC_HIP(hipMemsetAsync(e->d_pred.p, 1, (size_t)n, e->stream));
+    if (!stages) CC_HIP(hipMemsetAsync(e->d_pred.p, 1, (size_t)n, e->stream.s));
     FillResult r;
-    st = fill_select(e->fill, e->d_pred.p, n, 0, want - got, 0, 0, 0.0, e->stream, &r);
+    st = fill_select(e->fill, e->d_pred.p, n, 0, want - got, 0, 0, 0.0, e->stream.s, &r);
     if (st != CC_OK) return st;
     if (r.n_filled > 0) {
       e->generation++;
@@ -281,23 +261,23 @@ cc_status cc_eval_fill_passed(cc_evaluator* e, const cc_cascade* stages, const u
       A.first_slot = first_idx + got;
       A.cols = (int)cols;
       if (hog) {
-        A.hog_src = e->fill_hog.p;
-        A.hog_dst = e->d_hog.p;
+        A.hog_src = rows.hog.p;
+        A.hog_dst = e->samples.hog.p;
       } else {
-        A.sum_src = e->fill_sum.p;
-        A.sum_dst = e->d_sum.p;
+        A.sum_src = rows.sum.p;
+        A.sum_dst = e->samples.sum.p;
         if (e->use_tilted) {
-          A.tilted_src = e->fill_tilted.p;
-          A.tilted_dst = e->d_tilted.p;
+          A.tilted_src = rows.tilted.p;
+          A.tilted_dst = e->samples.tilted.p;
         }
         if (haar) {
-          A.nf_src = e->fill_nf.p;
-          A.nf_dst = e->d_nf.p;
+          A.nf_src = rows.nf.p;
+          A.nf_dst = e->samples.nf.p;
         }
       }
-      hipLaunchKernelGGL(k_fill_copy_rows, dim3(r.n_filled), dim3(256), 0, e->stream, A);
+      hipLaunchKernelGGL(k_fill_copy_rows, dim3(r.n_filled), dim3(256), 0, e->stream.s, A);
       CC_HIP(hipGetLastError());
-      CC_HIP(hipStreamSynchronize(e->stream));  // the scratch rows are rewritten by the next chunk
+      CC_HIP(hipStreamSynchronize(e->stream.s));  // the scratch rows are rewritten by the next chunk
       for (int i = 0; i < r.n_filled; i++) e->cls[(size_t)first_idx + got + i] = (float)label;
       if (e->mirror_idx >= first_idx + got && e->mirror_idx < first_idx + got + r.n_filled) e->mirror_idx = -1;
     }

@@ -184,25 +184,25 @@ cc_status hog_init(cc_evaluator* e) {
   const size_t lds = hog_set_lds(e->W, e->H, e->hog_planes_per_pass);
   if (lds > 64 * 1024)
     CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hog_set_images), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  CC_HIP(e->d_hog.ensure((size_t)e->max_samples * e->cols * 10));
-  CC_HIP(hipMemsetAsync(e->d_hog.p, 0, (size_t)e->max_samples * e->cols * 10 * 4, e->stream));
+  CC_HIP(e->samples.hog.ensure((size_t)e->max_samples * e->cols * 10));
+  CC_HIP(hipMemsetAsync(e->samples.hog.p, 0, (size_t)e->max_samples * e->cols * 10 * 4, e->stream.s));
   CC_HIP(e->d_hog_blocks.ensure(std::max<size_t>(e->hog_blocks.size(), 4)));
   if (!e->hog_blocks.empty())
-    CC_HIP(copy_sync(e->d_hog_blocks.p, e->hog_blocks.data(), e->hog_blocks.size() * 4, hipMemcpyHostToDevice, e->stream));
+    CC_HIP(copy_sync(e->d_hog_blocks.p, e->hog_blocks.data(), e->hog_blocks.size() * 4, hipMemcpyHostToDevice, e->stream.s));
   return CC_OK;
 }
 
-cc_status hog_launch_set_images(cc_evaluator* e, const uint8_t* d_imgs, int n, int first_idx) {
+cc_status hog_launch_set_images(cc_evaluator* e, const SampleTables& t, const uint8_t* d_imgs, int n, int first_idx) {
   const size_t lds = hog_set_lds(e->W, e->H, e->hog_planes_per_pass);
-  hipLaunchKernelGGL(k_hog_set_images, dim3(n), dim3(HOG_SET_THREADS), lds, e->stream, d_imgs, e->W, e->H, first_idx,
-                     e->hog_planes_per_pass, e->d_hog.p);
+  hipLaunchKernelGGL(k_hog_set_images, dim3(n), dim3(HOG_SET_THREADS), lds, e->stream.s, d_imgs, e->W, e->H, first_idx,
+                     e->hog_planes_per_pass, t.hog.p);
   CC_HIP(hipGetLastError());
   return CC_OK;
 }
 
 cc_status hog_launch_batch(cc_evaluator* e, int vb, int ve, const int32_t* d_idx, int ns, float* d_out, size_t out_pitch) {
   HogBatchArgs A;
-  A.planes = e->d_hog.p;
+  A.planes = e->samples.hog.p;
   A.blocks = e->d_hog_blocks.p;
   A.sample_idx = d_idx;
   A.n_samples = ns;
@@ -219,21 +219,21 @@ cc_status hog_launch_batch(cc_evaluator* e, int vb, int ve, const int32_t* d_idx
   int chunks = std::max(1, std::min((nblk + 3) / 4, (256 * 8 + tiles - 1) / std::max(tiles, 1)));
   A.blks_per_chunk = (nblk + chunks - 1) / chunks;
   chunks = (nblk + A.blks_per_chunk - 1) / A.blks_per_chunk;
-  (void)hipEventRecord(e->ev_a, e->stream);
-  hipLaunchKernelGGL(k_hog_eval_batch, dim3(tiles, chunks), dim3(HOG_EVAL_THREADS), 0, e->stream, A);
-  (void)hipEventRecord(e->ev_b, e->stream);
+  (void)hipEventRecord(e->ev_a.e, e->stream.s);
+  hipLaunchKernelGGL(k_hog_eval_batch, dim3(tiles, chunks), dim3(HOG_EVAL_THREADS), 0, e->stream.s, A);
+  (void)hipEventRecord(e->ev_b.e, e->stream.s);
   CC_HIP(hipGetLastError());
   return CC_OK;
 }
 
 cc_status hog_launch_list(cc_evaluator* e, const int32_t* d_list, int n, int si, float* d_out) {
-  hipLaunchKernelGGL(k_hog_eval_list, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->d_hog.p + (size_t)si * e->cols * 10,
+  hipLaunchKernelGGL(k_hog_eval_list, dim3((n + 255) / 256), dim3(256), 0, e->stream.s, e->samples.hog.p + (size_t)si * e->cols * 10,
                      e->d_hog_blocks.p, e->W + 1, d_list, n, d_out);
   CC_HIP(hipGetLastError());
   return CC_OK;
 }
 
-cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, int ns, uint8_t* out) {
+cc_status hog_predict(cc_evaluator* e, const SampleTables& t, const Cascade& m, const int32_t* d_idx, int ns, uint8_t* out) {
   std::vector<HogNodeDev> nodes(m.node_feature.size());
   for (size_t i = 0; i < nodes.size(); i++) {
     const int32_t* f = &m.hog_feats[(size_t)m.node_feature[i] * 5];  // validated inside the window at load
@@ -247,11 +247,11 @@ cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, i
   // declared after `nodes`: on an early return these go first, and hipFree waits for the queued copies that read it and m
   WalkTablesDev walk;
   DevBuf<HogNodeDev> d_nodes;
-  CC_HIP(walk.upload(m, e->stream));
-  CC_HIP(d_nodes.upload(nodes, e->stream));
+  CC_HIP(walk.upload(m, e->stream.s));
+  CC_HIP(d_nodes.upload(nodes, e->stream.s));
   CC_HIP(e->d_pred.ensure((size_t)ns));
   HogPredictArgs A;
-  A.planes = e->d_hog.p;
+  A.planes = t.hog.p;
   A.sw = e->W + 1;
   A.cols = e->cols;
   A.sample_idx = d_idx;
@@ -259,10 +259,10 @@ cc_status hog_predict(cc_evaluator* e, const Cascade& m, const int32_t* d_idx, i
   A.walk = walk.tables();
   A.nodes = d_nodes.p;
   A.out = e->d_pred.p;
-  hipLaunchKernelGGL(k_hog_predict, dim3((ns + 63) / 64), dim3(64), 0, e->stream, A);
+  hipLaunchKernelGGL(k_hog_predict, dim3((ns + 63) / 64), dim3(64), 0, e->stream.s, A);
   CC_HIP(hipGetLastError());
-  if (out) CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)ns, hipMemcpyDeviceToHost, e->stream));
-  CC_HIP(hipStreamSynchronize(e->stream));  // the tables and `nodes` above are freed on return
+  if (out) CC_HIP(hipMemcpyAsync(out, e->d_pred.p, (size_t)ns, hipMemcpyDeviceToHost, e->stream.s));
+  CC_HIP(hipStreamSynchronize(e->stream.s));  // the tables and `nodes` above are freed on return
   return CC_OK;
 }
 
@@ -326,7 +326,7 @@ cc_status cc_eval_get_hog_sample(cc_evaluator* e, int idx, float* hist, float* n
   st = flush_pending_images(e);  // the device's copy is what this call reports, also for a sample set a moment ago
   if (st != CC_OK) return st;
   std::vector<float> v((size_t)e->cols * 10);
-  CC_HIP(copy_sync(v.data(), e->d_hog.p + (size_t)idx * e->cols * 10, v.size() * 4, hipMemcpyDeviceToHost, e->stream));
+  CC_HIP(copy_sync(v.data(), e->samples.hog.p + (size_t)idx * e->cols * 10, v.size() * 4, hipMemcpyDeviceToHost, e->stream.s));
   for (int p = 0; p < e->cols; p++) {
     if (hist)
       for (int b = 0; b < 9; b++) hist[(size_t)b * e->cols + p] = v[(size_t)p * 10 + b];

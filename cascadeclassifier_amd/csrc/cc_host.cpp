@@ -1,6 +1,6 @@
 // Host-side pieces of the hot path that are tiny and serial in the reference too: error plumbing, the scale
 // pyramid geometry, the tap tables of the fixed-point bilinear resize, rectangle grouping and the feature catalogs.
-// Everything that scales with pixels / windows / samples runs in the HIP kernels (cc_detect.hip, cc_front.hip, cc_group.hip, cc_eval.hip).
+// Everything that scales with pixels / windows / samples runs in the HIP kernels (cc_detect.hip, cc_front.hip, cc_group.hip, cc_eval_*.hip).
 #include <algorithm>
 #include <cfloat>
 #include <cmath>

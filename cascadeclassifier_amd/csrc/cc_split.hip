@@ -711,7 +711,7 @@ struct RowSorter {
   cc_status sort(int nf) {
     if (N <= sort_rows_block_limit()) {  // a row fits one block: sorted in LDS, read once and written once
       // a part that refuses the ~100 KB LDS request (or the launch) takes the device-wide sort below instead of failing
-      if (sort_rows_block(e->d_out.p, nf, N, keys_out.p, sorted.p, e->stream) == hipSuccess) return CC_OK;
+      if (sort_rows_block(e->d_out.p, nf, N, keys_out.p, sorted.p, e->stream.s) == hipSuccess) return CC_OK;
       (void)hipGetLastError();
     }
     if (!segmented_ready) {
@@ -720,19 +720,19 @@ struct RowSorter {
       CC_HIP(offsets.ensure((size_t)FB + 1));
       std::vector<int> off((size_t)FB + 1);
       for (int i = 0; i <= FB; i++) off[(size_t)i] = (int)((size_t)i * N);
-      CC_HIP(hipMemcpyAsync(offsets.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, e->stream));
-      CC_HIP(hipStreamSynchronize(e->stream));  // `off` is pageable and about to go out of scope
-      hipLaunchKernelGGL(k_iota_rows2, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, e->stream, iota.p, cap, N);
+      CC_HIP(hipMemcpyAsync(offsets.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, e->stream.s));
+      CC_HIP(hipStreamSynchronize(e->stream.s));  // `off` is pageable and about to go out of scope
+      hipLaunchKernelGGL(k_iota_rows2, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, e->stream.s, iota.p, cap, N);
       segmented_ready = true;
     }
     const size_t total = (size_t)nf * N;
     size_t temp_bytes = 0;
     CC_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, temp_bytes, e->d_out.p, keys_out.p, iota.p, sorted.p, (int)total, nf, offsets.p,
-                                                       offsets.p + 1, 0, 32, e->stream));
+                                                       offsets.p + 1, 0, 32, e->stream.s));
     CC_HIP(temp.ensure(std::max<size_t>(temp_bytes, 1)));
     // stable: equal values keep increasing sample order
     CC_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(temp.p, temp_bytes, e->d_out.p, keys_out.p, iota.p, sorted.p, (int)total, nf, offsets.p,
-                                                       offsets.p + 1, 0, 32, e->stream));
+                                                       offsets.p + 1, 0, 32, e->stream.s));
     return CC_OK;
   }
 };
@@ -758,14 +758,14 @@ static cc_status presort_ordered(cc_evaluator* e, RowSorter& rows, const void* f
   // tables + SPLIT_TABLE_PAD_RANKS ranks of zeroed padding behind the last group (read-ahead of k_split_ord_lean)
   const size_t used = ((size_t)F + 63) / 64 * 64 * (size_t)N, pad = (size_t)SPLIT_TABLE_PAD_RANKS * 64;
   CC_HIP(e->d_sorted_val.ensure(used + pad));
-  CC_HIP(hipMemsetAsync(e->d_sorted_val.p + used, 0, pad * sizeof(float), e->stream));
+  CC_HIP(hipMemsetAsync(e->d_sorted_val.p + used, 0, pad * sizeof(float), e->stream.s));
   CC_HIP(d_sorted_idx.ensure(used + pad));
-  CC_HIP(hipMemsetAsync(d_sorted_idx.p + used, 0, pad * sizeof(TI), e->stream));
+  CC_HIP(hipMemsetAsync(d_sorted_idx.p + used, 0, pad * sizeof(TI), e->stream.s));
   for (int f0 = 0; f0 < F; f0 += FB) {
     const int f1 = std::min(F, f0 + FB), nf = f1 - f0;
     if (cc_status st = launch_batch(e, true, feats, fi_begin + f0, fi_begin + f1, nullptr, N, e->d_out.p, 1, 0); st != CC_OK) return st;
     if (cc_status st = rows.sort(nf); st != CC_OK) return st;
-    hipLaunchKernelGGL((k_interleave<TI>), dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream, rows.keys_out.p,
+    hipLaunchKernelGGL((k_interleave<TI>), dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream.s, rows.keys_out.p,
                        rows.sorted.p, nf, N, e->d_sorted_val.p, d_sorted_idx.p, (size_t)f0 / 64);
     CC_HIP(hipGetLastError());
   }
@@ -781,18 +781,18 @@ static cc_status presort_categorical(cc_evaluator* e, RowSorter& rows, const voi
     // padding behind the last group for the read-ahead
     const size_t used = ((size_t)F + 63) / 64 * 64 * ((((size_t)N + 3) >> 2) << 2), pad = (size_t)SPLIT_CAT_PAD_RANKS * 64;
     CC_HIP(e->d_cat_sorted.ensure(used + pad));
-    CC_HIP(hipMemsetAsync(e->d_cat_sorted.p, 0, (used + pad) * sizeof(uint32_t), e->stream));
+    CC_HIP(hipMemsetAsync(e->d_cat_sorted.p, 0, (used + pad) * sizeof(uint32_t), e->stream.s));
   }
   for (int f0 = 0; f0 < F; f0 += FB) {
     const int f1 = std::min(F, f0 + FB), nf = f1 - f0;
     const size_t total = (size_t)nf * N;
     CC_HIP(e->d_out.ensure(total));
     if (cc_status st = launch_batch(e, false, feats, fi_begin + f0, fi_begin + f1, nullptr, N, e->d_out.p, 1, 0); st != CC_OK) return st;
-    hipLaunchKernelGGL(k_codes_u8, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, e->d_out.p,
+    hipLaunchKernelGGL(k_codes_u8, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream.s, e->d_out.p,
                        e->d_codes.p + (size_t)f0 * N, total);
     if (!cat_table) continue;
     if (cc_status st = rows.sort(nf); st != CC_OK) return st;
-    hipLaunchKernelGGL(k_interleave_cat, dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream, rows.keys_out.p,
+    hipLaunchKernelGGL(k_interleave_cat, dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream.s, rows.keys_out.p,
                        rows.sorted.p, nf, N, e->d_cat_sorted.p, (size_t)f0 / 64);
   }
   CC_HIP(hipGetLastError());
@@ -873,10 +873,10 @@ static cc_status upload_node_table(const SplitQuery& q, TableForm form, const Ab
       tab16[slot] = q.entry16(i);
   }
   CC_HIP(e->d_split_tab.ensure(m * 2));
-  CC_HIP(hipMemcpyAsync(e->d_split_tab.p, e->pin_in.p, bytes, hipMemcpyHostToDevice, e->stream));
+  CC_HIP(hipMemcpyAsync(e->d_split_tab.p, e->pin_in.p, bytes, hipMemcpyHostToDevice, e->stream.s));
   if (absent) return CC_OK;
   CC_HIP(e->d_split_idx.ensure(m));
-  CC_HIP(hipMemcpyAsync(e->d_split_idx.p, idx_host, m * 4, hipMemcpyHostToDevice, e->stream));
+  CC_HIP(hipMemcpyAsync(e->d_split_idx.p, idx_host, m * 4, hipMemcpyHostToDevice, e->stream.s));
   return CC_OK;
 }
 
@@ -901,7 +901,7 @@ static void (*categorical_sorted_kernel(bool is_classifier, TableForm form))(Spl
 // ev_a .. ev_b for cc_eval_last_kernel_ms; the stream has been synchronised
 static void note_kernel_ms(cc_evaluator* e) {
   float ms = 0;
-  if (hipEventElapsedTime(&ms, e->ev_a, e->ev_b) == hipSuccess) e->last_ms = ms;
+  if (hipEventElapsedTime(&ms, e->ev_a.e, e->ev_b.e) == hipSuccess) e->last_ms = ms;
 }
 
 // The winner, variable by variable as DTreeBestSplitFinder::operator() does (o_cvdtree.cpp:320-342): a variable reports
@@ -951,9 +951,9 @@ cc_status ccamd::split_launch_ordered(cc_evaluator* e, int mode, TableForm form,
     if (form == TABLE_LDS8 && mode != 2) wpb = std::min(wpb, SPLIT_LEAN_WAVES);  // k_split_ord_lean
   }
   const unsigned blocks = (unsigned)((groups + wpb - 1) / wpb);
-  (void)hipEventRecord(e->ev_a, e->stream);
-  if (cc_status st = launch(ordered_kernel(mode, form, idx16), blocks, 64u * wpb, table_lds(form, N), e->stream, A); st != CC_OK) return st;
-  (void)hipEventRecord(e->ev_b, e->stream);
+  (void)hipEventRecord(e->ev_a.e, e->stream.s);
+  if (cc_status st = launch(ordered_kernel(mode, form, idx16), blocks, 64u * wpb, table_lds(form, N), e->stream.s, A); st != CC_OK) return st;
+  (void)hipEventRecord(e->ev_b.e, e->stream.s);
   return CC_OK;
 }
 
@@ -965,8 +965,8 @@ static cc_status search_ordered(const SplitQuery& q) {
   if (cc_status st = split_launch_ordered(e, mode, form, q.weights[q.n], q.weights[q.n + 1], q.node_value * q.weights[q.n]); st != CC_OK) return st;
   const size_t fpad = ((size_t)q.F + 63) / 64 * 64;
   CC_HIP(e->pin_out.ensure(fpad * 24));
-  CC_HIP(hipMemcpyAsync(e->pin_out.p, e->d_split_out.p, OrdResult::bytes(fpad), hipMemcpyDeviceToHost, e->stream));
-  CC_HIP(hipStreamSynchronize(e->stream));
+  CC_HIP(hipMemcpyAsync(e->pin_out.p, e->d_split_out.p, OrdResult::bytes(fpad), hipMemcpyDeviceToHost, e->stream.s));
+  CC_HIP(hipStreamSynchronize(e->stream.s));
   note_kernel_ms(e);
   const OrdResult got(e->pin_out.p, fpad);
   const int winner = pick_winner(q, [&](int f) { return got.best_i[f] >= 0; }, [&](int f) { return got.best_val[f]; }, [&](int f) { return got.best_i[f]; });
@@ -981,8 +981,8 @@ static cc_status search_ordered(const SplitQuery& q) {
 static cc_status search_categorical_sorted(const SplitQuery& q, size_t hist_n, TableForm form) {
   cc_evaluator* e = q.e;
   const int N = q.N;
-  (void)hipEventRecord(e->ev_a, e->stream);
-  CC_HIP(hipMemsetAsync(e->d_split_out.p, 0, hist_n * 8, e->stream));  // categories without a sample
+  (void)hipEventRecord(e->ev_a.e, e->stream.s);
+  CC_HIP(hipMemsetAsync(e->d_split_out.p, 0, hist_n * 8, e->stream.s));  // categories without a sample
   const size_t groups = ((size_t)q.F + 63) / 64;
   SplitCatArgs A;
   A.packed = e->d_cat_sorted.p;
@@ -1003,8 +1003,8 @@ static cc_status search_categorical_sorted(const SplitQuery& q, size_t hist_n, T
   const size_t units = groups * (size_t)parts;
   A.waves = form == TABLE_GLOBAL16 ? 4 : (int)std::min<size_t>(4, std::max<size_t>(1, (units + cus - 1) / cus));
   const unsigned blocks = (unsigned)((units + A.waves - 1) / A.waves);
-  const cc_status st = launch(categorical_sorted_kernel(q.is_classifier, form), blocks, 256, table_lds(form, N), e->stream, A);
-  (void)hipEventRecord(e->ev_b, e->stream);
+  const cc_status st = launch(categorical_sorted_kernel(q.is_classifier, form), blocks, 256, table_lds(form, N), e->stream.s, A);
+  (void)hipEventRecord(e->ev_b.e, e->stream.s);
   return st;
 }
 
@@ -1012,10 +1012,10 @@ static cc_status search_categorical_sorted(const SplitQuery& q, size_t hist_n, T
 static cc_status search_categorical_stream(const SplitQuery& q) {
   cc_evaluator* e = q.e;
   if (cc_status st = upload_node_table(q, TABLE_GLOBAL16, nullptr); st != CC_OK) return st;
-  (void)hipEventRecord(e->ev_a, e->stream);
-  hipLaunchKernelGGL(q.is_classifier ? k_split_cat<true> : k_split_cat<false>, dim3((unsigned)q.F), dim3(256), 0, e->stream, e->d_codes.p, q.N,
+  (void)hipEventRecord(e->ev_a.e, e->stream.s);
+  hipLaunchKernelGGL(q.is_classifier ? k_split_cat<true> : k_split_cat<false>, dim3((unsigned)q.F), dim3(256), 0, e->stream.s, e->d_codes.p, q.N,
                      q.sample_idx ? e->d_split_idx.p : nullptr, reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), q.n, e->d_split_out.p);
-  (void)hipEventRecord(e->ev_b, e->stream);
+  (void)hipEventRecord(e->ev_b.e, e->stream.s);
   CC_HIP(hipGetLastError());
   return CC_OK;
 }
@@ -1028,14 +1028,14 @@ static cc_status reduce_category_sums(const SplitQuery& q, size_t hist_n, std::v
   CC_HIP(e->pin_out.ensure(hist_n * 8));
   constexpr int kPieces = 8;
   for (int c = 0; c < kPieces; c++)
-    if (!e->ev_piece[c]) CC_HIP(hipEventCreateWithFlags(&e->ev_piece[c], hipEventDisableTiming));
+    if (!e->ev_piece[c].e) CC_HIP(e->ev_piece[c].create(hipEventDisableTiming));
   const int per_piece = (F + kPieces - 1) / kPieces;
   double* hist = static_cast<double*>(e->pin_out.p);
   for (int c = 0; c < kPieces; c++) {
     const int f0 = std::min(F, c * per_piece), f1 = std::min(F, f0 + per_piece);
     if (f1 > f0)
-      CC_HIP(hipMemcpyAsync(hist + (size_t)f0 * 512, e->d_split_out.p + (size_t)f0 * 512, (size_t)(f1 - f0) * 512 * 8, hipMemcpyDeviceToHost, e->stream));
-    CC_HIP(hipEventRecord(e->ev_piece[c], e->stream));
+      CC_HIP(hipMemcpyAsync(hist + (size_t)f0 * 512, e->d_split_out.p + (size_t)f0 * 512, (size_t)(f1 - f0) * 512 * 8, hipMemcpyDeviceToHost, e->stream.s));
+    CC_HIP(hipEventRecord(e->ev_piece[c].e, e->stream.s));
   }
   std::atomic<int> copy_failed{0};
   const bool trace = std::getenv("CCAMD_TRACE_SPLIT") != nullptr;  // host-side timeline of the call's tail (stderr)
@@ -1047,7 +1047,7 @@ static cc_status reduce_category_sums(const SplitQuery& q, size_t hist_n, std::v
     for (int t = 0; t < nt; t++)
       th.emplace_back([&, t]() {
         for (int c = 0; c < kPieces; c++) {
-          if (hipEventSynchronize(e->ev_piece[c]) != hipSuccess) {
+          if (hipEventSynchronize(e->ev_piece[c].e) != hipSuccess) {
             copy_failed = 1;
             return;
           }
@@ -1063,7 +1063,7 @@ static cc_status reduce_category_sums(const SplitQuery& q, size_t hist_n, std::v
     for (int c = 0; c < kPieces; c++) std::fprintf(stderr, " %.2f", landed_ms[c]);
     std::fprintf(stderr, " ms; workers done at %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq).count());
   }
-  CC_HIP(hipStreamSynchronize(e->stream));
+  CC_HIP(hipStreamSynchronize(e->stream.s));
   if (copy_failed) return set_error(CC_ERR_HIP, "cc_eval_find_best_split: copying the category sums back failed");
   note_kernel_ms(e);
   return CC_OK;
@@ -1140,7 +1140,7 @@ cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n
                        : N <= 65536 ? presort_ordered(e, rows, feats, fi_begin, F, e->d_sorted_idx16)
                                     : presort_ordered(e, rows, feats, fi_begin, F, e->d_sorted_idx32);
   if (st != CC_OK) return st;
-  CC_HIP(hipStreamSynchronize(e->stream));
+  CC_HIP(hipStreamSynchronize(e->stream.s));
   // epilogue: the tables are valid
   e->presort_n = N;
   e->presort_f0 = fi_begin;

@@ -1,7 +1,8 @@
-// Training-side code shared by cc_eval.hip (bulk operator(), predict), cc_negmine.hip (negative mining) and cc_hog.hip
-// (HOG predict): the trainer's feature arithmetic and the walk over the stages of a trained cascade, each written once,
-// and the host code that lays their tables out. Bit-exact against the reference: every translation unit that includes this
-// is built with -ffp-contract=off. Not part of cc_eval_common.h, whose text goes to hiprtc and into the specialiser's cache key.
+// Training-side code shared by cc_eval_calc.hip (bulk operator()), cc_eval_predict.hip (predict), cc_eval_store.hip (host
+// mirror), cc_negmine.hip (negative mining) and cc_hog.hip (HOG predict): the trainer's feature arithmetic and the walk over
+// the stages of a trained cascade, each written once, and the host code that lays their tables out. Bit-exact against the
+// reference: every translation unit that includes this is built with -ffp-contract=off. Not part of cc_eval_common.h, whose
+// text goes to hiprtc and into the specialiser's cache key.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,7 +45,7 @@ __host__ __device__ __forceinline__ float haar_sum(const HaarFeatDev& F, At at) 
   if (F.w[2] != 0.0f) ret += F.w[2] * (float)(at(F.p[2][0]) - at(F.p[2][1]) - at(F.p[2][2]) + at(F.p[2][3]));
   return ret;
 }
-// operator() (haarfeatures.h:108-112). The batch kernels divide by their hoisted div_by_refined instead (cc_eval.hip).
+// operator() (haarfeatures.h:108-112). The batch kernels divide by their hoisted div_by_refined instead (cc_eval_calc.hip).
 __host__ __device__ __forceinline__ float haar_value(float ret, float nf) { return nf == 0.0f ? 0.0f : ret / nf; }
 
 // ------------------------------------------------------------------------------------------------

@@ -418,6 +418,40 @@ def test_host_mirror_of_the_last_set_window_equals_the_device(ftype, mode):
     assert (e.get_sample(2)[0] == s[1]).all()
 
 
+@pytest.mark.parametrize("ftype,mode,win", [(ev.HAAR, ev.ALL, (24, 24)), (ev.LBP, 0, (24, 24)), (ev.HOG, 0, (16, 16))])
+def test_queued_windows_in_runs_and_gaps(ftype, mode, win):
+    """Windows queued by cc_eval_set_image reach the device sorted by sample index, one launch per run of consecutive
+    indices: slots 5, 2, 3, 9, 4, 2 (another image), 10 make a run of four (2-5), a run of two (9-10) and a replacement
+    inside the queue. No read in between; then every slot holds, bit for bit, what setImages of the final images stores,
+    and the nine slots never set are still zero. HOG at 16x16, the smallest window test_gpu_hog.py stores images at."""
+    rng = np.random.default_rng(29)
+    order = (5, 2, 3, 9, 4, 2, 10)
+    imgs = rng.integers(0, 256, (len(order), win[1], win[0]), dtype=np.uint8)
+    final = np.zeros((16, win[1], win[0]), np.uint8)
+    e, ref = _mk(ftype, mode, 16, win), _mk(ftype, mode, 16, win)
+    for k, idx in enumerate(order):
+        e.setImage(imgs[k], 1, idx)
+        final[idx] = imgs[k]  # the later image for slot 2 replaces the earlier one
+    set_slots = sorted(set(order))
+    for lo, hi in ((2, 6), (9, 11)):  # the reference holds the same images, loaded in bulk
+        ref.setImages(final[lo:hi], first_idx=lo)
+
+    def bits(x):
+        return np.ascontiguousarray(x).view(np.uint32) if x.dtype == np.float32 else x
+
+    for idx in range(16):
+        got = [np.asarray(a) for a in e.get_sample(idx) if a is not None]
+        want = [np.asarray(a) for a in ref.get_sample(idx) if a is not None]
+        assert len(got) == len(want) == {ev.HAAR: 3, ev.LBP: 1, ev.HOG: 2}[ftype]
+        for g, w in zip(got, want):
+            g, w = g.astype(np.float32) if g.dtype == np.float64 else g, w.astype(np.float32) if w.dtype == np.float64 else w
+            assert (bits(g) == bits(w)).all(), idx
+            if idx not in set_slots:
+                assert not bits(g).any(), idx
+            else:
+                assert bits(g).any(), idx
+
+
 def test_bulk_values_into_pitched_device_memory():
     """cc_eval_calc_batch_device: rows `pitch` floats apart in device memory; the padding is left untouched."""
     import torch

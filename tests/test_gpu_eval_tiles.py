@@ -1,4 +1,4 @@
-"""The training evaluator (cc_eval.hip) at every tile size cc_eval_create can pick and at its window limits, against the
+"""The training evaluator (cc_eval_*.hip) at every tile size cc_eval_create can pick and at its window limits, against the
 oracle with tolerance 0 on uint32 views. The cases, their expected tile and the inputs come from tests/eval_tiles.py;
 tests/test_eval_tiles_host.py checks the table and shows the oracle exact at these shapes. cc_debug_eval_tile_samples
 proves that a case ran on the kernel configuration it names."""
