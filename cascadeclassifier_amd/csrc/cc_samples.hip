@@ -282,6 +282,10 @@ __device__ __forceinline__ unsigned warp_sample(const uint8_t* __restrict__ src,
   return (unsigned)(int)(i0 + (i1 - i0) * w.dy) & 255u;
 }
 
+// The byte a canvas or a window without a background is filled with: Mat = Scalar saturates (utility.cpp:607, :992), so
+// a bgcolor of 300 fills with 255 and -5 with 0. The mask test and de / dd below take the int as it is (:536-537, :555-556).
+__host__ __device__ __forceinline__ unsigned sample_fill(int bgcolor) { return bgcolor < 0 ? 0u : bgcolor > 255 ? 255u : (unsigned)bgcolor; }
+
 // icvStartSampleDistortion (utility.cpp:533-565), one thread per pixel: mask, 3x3 minimum / maximum over the pixels inside
 // the image (cv::erode / cv::dilate leave the outside out), border extension with the reference's (uchar) wrap-around.
 __global__ __launch_bounds__(256) void k_sampler_prepare(const uint8_t* __restrict__ img, int w, int h, size_t stride, int bgcolor,
@@ -330,6 +334,7 @@ __global__ __launch_bounds__(256) void k_sample_render(const uint8_t* __restrict
   const cc_sample_record& R = recs[s];
   const int cw = sw + 2 * (sw / 2), ch = sh + 2 * (sh / 2);
   const int2* sp = spans + (size_t)s * ch;
+  const unsigned fill = sample_fill(bgcolor);
   int32_t x0, y0;
   uint16_t wx1, wy1;
   linear_exact_tap(R.roi_w, out_w, ox, x0, wx1);
@@ -344,7 +349,7 @@ __global__ __launch_bounds__(256) void k_sample_render(const uint8_t* __restrict
       const int x = reflect101(R.roi_x + x0 - 1 + i, cw);
       const bool inside = x >= span.x && x <= span.y;
       const bool centre = (i == 1 || i == 2) && (j == 1 || j == 2);
-      unsigned m = 0, v = (unsigned)bgcolor & 255u;
+      unsigned m = 0, v = fill;
       if (inside) {
         const WarpCoord w = warp_coord(R.coeffs, x, y, sw, sh);
         m = warp_sample(mask, sw, sh, sw, w);
@@ -372,7 +377,7 @@ __global__ __launch_bounds__(256) void k_sample_render(const uint8_t* __restrict
   const unsigned alpha = resize_lerp_v(wy0, wy1, resize_lerp_h(wx0, wx1, bl[0][0], bl[0][1]), resize_lerp_h(wx0, wx1, bl[1][0], bl[1][1]));
   // blend (utility.cpp:660-671)
   const size_t o = (size_t)s * out_w * out_h + p;
-  const int bg = backgrounds ? backgrounds[o] : bgcolor & 255;
+  const int bg = backgrounds ? backgrounds[o] : (int)fill;
   int t = min(max(R.forecolordev + (int)img, 0), 255);
   if (R.inverse) t ^= 0xFF;
   out[o] = (uint8_t)((t * (int)alpha + (255 - (int)alpha) * bg) / 255);
@@ -598,7 +603,7 @@ cc_status cc_sampler_render(cc_sampler* s, const cc_sample_record* records, cons
         const cc_sample_record& R = records[first + i];
         uint8_t* slot = s->bgwin.p + i * area;
         if (R.bg_image == -1) {
-          CC_HIP(hipMemsetAsync(slot, s->bgcolor & 255, area, q));
+          CC_HIP(hipMemsetAsync(slot, (int)sample_fill(s->bgcolor), area, q));
           continue;
         }
         if (R.bg_image != cur_i || R.bg_w != cur_w || R.bg_h != cur_h) {

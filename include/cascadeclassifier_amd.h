@@ -476,7 +476,9 @@ CC_API cc_status cc_eval_calc_batch(cc_evaluator* e, int fi_begin, int fi_end, c
 /* The same into DEVICE memory with a row pitch: d_out[(fi - fi_begin) * pitch + s], pitch in elements (0 = n_samples).
  * For consumers that stay on the device (presort, split search, a trainer holding valCache in HBM): the pitch lets rows
  * start on any alignment the consumer likes; measured in round 3, the store rate of the bulk evaluator does not depend
- * on it (profiles/r03_training_kernels.txt). */
+ * on it (profiles/r03_training_kernels.txt). The kernel runs on the evaluator's own non-blocking stream and the call
+ * returns when it is done: work of the caller's that writes d_out on another stream (a fill, say) must have finished
+ * before the call, or it can land on top of the values. */
 CC_API cc_status cc_eval_calc_batch_device(cc_evaluator* e, int fi_begin, int fi_end, const int32_t* sample_idx, int n_samples,
                                            float* d_out, size_t pitch);
 /* cc_eval_calc_batch plus, per feature, the argsort of the samples by value: the "sorted index" half of
@@ -855,7 +857,8 @@ CC_API cc_status cc_sampler_set_backgrounds(cc_sampler* s, const uint8_t* const*
 /* Renders n planned samples into out (n * out_h * out_w bytes, host). records / spans as cc_sample_plan filled them for
  * this sampler's image size and this window. backgrounds: n windows of out_h * out_w bytes (host), or NULL: each sample is
  * then blended onto its record's window of the cc_sampler_set_backgrounds images (scaled by the exact resize, cropped on
- * the device), or onto bgcolor when bg_image is -1. One grid per batch of samples; the batch is sized from free device
+ * the device), or onto bgcolor when bg_image is -1 (bgcolor saturated to 0..255 there and where the warp leaves the
+ * canvas unwritten, as the reference's Mat = Scalar does; the mask and the border extension use the int). One grid per batch of samples; the batch is sized from free device
  * memory, at most 32768 samples and, when max_batch > 0, at most max_batch. Records whose rectangle or window leaves its
  * image are CC_ERR_INVALID_ARG. */
 CC_API cc_status cc_sampler_render(cc_sampler* s, const cc_sample_record* records, const int32_t* spans, int n, int out_w,

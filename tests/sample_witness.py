@@ -380,6 +380,12 @@ def plan(src_w, src_h, out_w, out_h, p, rng, n, bg=None):
     return recs
 
 
+def fill_byte(bgcolor):
+    """The byte `Mat = Scalar(bgcolor)` stores (utility.cpp:607, :992): saturated, 300 -> 255 and -5 -> 0. The mask test and
+    de / dd of start_distortion use the int itself."""
+    return min(max(int(bgcolor), 0), 255)
+
+
 def _blend(img, alpha, bg, forecolordev, inverse):
     t = np.clip(forecolordev + img.astype(np.int64), 0, 255)
     if inverse:
@@ -391,7 +397,7 @@ def _blend(img, alpha, bg, forecolordev, inverse):
 def render_dense(src, mask, bgcolor, rec, out_w, out_h, bg=None):
     h, w = src.shape
     cw, ch = w + 2 * (w // 2), h + 2 * (h // 2)
-    img = np.full((ch, cw), bgcolor, np.uint8)
+    img = np.full((ch, cw), fill_byte(bgcolor), np.uint8)
     mimg = np.zeros((ch, cw), np.uint8)
     for s, d in ((src, img), (mask, mimg)):
         for y in range(ch):
@@ -401,7 +407,7 @@ def render_dense(src, mask, bgcolor, rec, out_w, out_h, bg=None):
                 d[y, a:b + 1] = warp_at(s, rec["coeffs"], X, np.full_like(X, y))
     mimg = gaussian3(mimg)
     x, y, rw, rh = rec["roi"]
-    bgw = np.full((out_h, out_w), bgcolor, np.uint8) if bg is None else bg
+    bgw = np.full((out_h, out_w), fill_byte(bgcolor), np.uint8) if bg is None else bg
     return _blend(resize_linear_exact(img[y:y + rh, x:x + rw], out_w, out_h),
                   resize_linear_exact(mimg[y:y + rh, x:x + rw], out_w, out_h), bgw, rec["forecolordev"], rec["inverse"])
 
@@ -418,7 +424,7 @@ def render_sparse(src, mask, bgcolor, rec, out_w, out_h, bg=None):
         return np.where(inside, warp_at(s, c, X, Y), np.uint8(fill))
 
     def fetch_img(rows, cols):
-        return canvas(src, bgcolor, rows + y0, cols + x0)
+        return canvas(src, fill_byte(bgcolor), rows + y0, cols + x0)
 
     def fetch_mask(rows, cols):
         rows, cols = rows + y0, cols + x0
@@ -428,7 +434,7 @@ def render_sparse(src, mask, bgcolor, rec, out_w, out_h, bg=None):
                 acc += wy * wx * canvas(mask, 0, _reflect(rows + dy, ch), _reflect(cols + dx, cw)).astype(np.int64)
         return (acc + 8) >> 4
 
-    bgw = np.full((out_h, out_w), bgcolor, np.uint8) if bg is None else bg
+    bgw = np.full((out_h, out_w), fill_byte(bgcolor), np.uint8) if bg is None else bg
     return _blend(_resize_from(fetch_img, rw, rh, out_w, out_h), _resize_from(fetch_mask, rw, rh, out_w, out_h), bgw,
                   rec["forecolordev"], rec["inverse"])
 

@@ -464,6 +464,7 @@ def test_bulk_values_into_pitched_device_memory():
     for pitch in (0, 100, 128, 133):
         p = pitch or 100
         out = torch.full((300, p), -7.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # the fill runs on torch's stream, the evaluator on its own: unordered, the fill can land last
         e.calc_batch_device(1000, 1300, out.data_ptr(), n_samples=100, pitch=pitch)
         got = out.cpu().numpy()
         assert (got[:, :100].view(np.uint32) == want.view(np.uint32)).all()

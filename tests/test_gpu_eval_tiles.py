@@ -154,6 +154,7 @@ def test_bulk_values_into_pitched_device_memory(rig):
     pitch = n + 37
     for a, b in case.ranges():
         out = torch.full((b - a, pitch), -7.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # the fill runs on torch's stream, the evaluator on its own: unordered, the fill can land last
         e.calc_batch_device(a, b, out.data_ptr(), n_samples=n, pitch=pitch)
         got = out.cpu().numpy()
         bad = _bits(got[:, :n]) != _bits(ref.vals[(a, b)][:, :n])

@@ -167,6 +167,7 @@ def test_gather_ranges_pitched_list_scalar(ev32):
     assert (_u(r) == _u(full[40:41, idx[:5]])).all()
     pitch = n + 37
     d = torch.full((1000 - 17, pitch), -7.0, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()  # the fill runs on torch's stream, the evaluator on its own: unordered, the fill can land last
     e.calc_batch_device(17, 1000, d.data_ptr(), pitch=pitch)
     torch.cuda.synchronize()
     dd = d.cpu().numpy()

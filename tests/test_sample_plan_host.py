@@ -1,5 +1,6 @@
 """cc_sample_plan (host, no device) against the numpy witness, bit for bit: doubles are compared as uint64."""
 import ctypes as C
+import re
 
 import numpy as np
 import pytest
@@ -7,7 +8,7 @@ import pytest
 from cascadeclassifier_amd import _lib as L
 from cascadeclassifier_amd import samples as S
 from tests import sample_witness as W
-from tests.sample_cases import BARCODE, CASES, bg_images
+from tests.sample_cases import BARCODE, BG_LIST_SIZES, CASES, EDGE_CASES, bg_images
 
 
 def _bits(values):
@@ -47,6 +48,59 @@ def test_plan_matches_witness(name):
         assert (want[0]["spans"][sh // 2 + 1:sh // 2 + sh - 1] == [sw // 2, sw // 2 + sw]).all()
     if name == "randinv":
         assert {r["inverse"] for r in want} == {0, 1}
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_CASES))
+def test_plan_matches_witness_at_edges(name):
+    sw, sh, ow, oh, kw, n, seed = EDGE_CASES[name]
+    _run(sw, sh, ow, oh, kw, n, seed=seed)
+
+
+@pytest.mark.parametrize("seed", [2 ** 32, 2 ** 63 + 5])
+def test_plan_seeds_past_32_bits(seed):
+    assert S.CvRNG(seed).state == seed  # neither is folded to its low half
+    _run(40, 24, 24, 24, dict(invert=W.RANDOM_INVERT), 10, seed=seed)
+
+
+def _witness_planned_before_refusal(sw, sh, ow, oh, kw, seed, limit):
+    """How many samples the witness plans before it refuses one as nonconvex, and those samples."""
+    rng, recs = W.RNG(seed), []
+    for _ in range(limit):
+        try:
+            recs += W.plan(sw, sh, ow, oh, W.Params(**kw), rng, 1)
+        except ValueError as e:
+            assert "nonconvex" in str(e)
+            return recs
+    raise AssertionError("the witness refused nothing")
+
+
+@pytest.mark.parametrize("sw,sh,seed,count", [(2, 9, 12345, 3), (2, 9, 2, 107), (2, 40, 12345, 0)])
+def test_plan_refuses_the_sample_the_witness_refuses(sw, sh, seed, count):
+    kw = dict(maxxangle=1.5, maxyangle=1.5)
+    want = _witness_planned_before_refusal(sw, sh, 8, 8, kw, seed, 200)
+    assert len(want) == count
+    with pytest.raises(L.CascadeError) as e:
+        S.plan(sw, sh, (8, 8), S.SampleParams(**kw), S.CvRNG(seed), 200)
+    assert e.value.status == L.CC_ERR_INVALID_ARG and "nonconvex" in str(e.value)
+    assert int(re.search(r"sample (\d+):", str(e.value)).group(1)) == count
+    recs, spans = S.plan(sw, sh, (8, 8), S.SampleParams(**kw), S.CvRNG(seed), count)  # exactly as many as are valid
+    _compare(recs, spans, want, count)
+
+
+def test_background_list_with_fit_skip_and_ladder():
+    """Images exactly the window's size, as wide but taller, too narrow (skipped) and with a four-step scale ladder."""
+    n = 80
+    kw = dict(invert=W.RANDOM_INVERT)
+    rng_w, rng = W.RNG(), S.CvRNG()
+    want = W.plan(40, 24, 24, 24, W.Params(**kw), rng_w, n, W.BgReader(BG_LIST_SIZES, 24, 24))
+    recs, spans = S.plan(40, 24, (24, 24), S.SampleParams(**kw), rng, n, bg_sizes=BG_LIST_SIZES)
+    _compare(recs, spans, want, n)
+    assert rng.state == rng_w.state
+    bgs = [r["bg"] for r in want]
+    assert {b[0] for b in bgs} == {0, 1, 2, 4}  # image 3 is 23 wide: never used
+    assert sorted({b[1:3] for b in bgs if b[0] == 2}) == [(51, 24), (72, 33), (102, 48), (145, 67)]
+    assert {b[1:] for b in bgs if b[0] == 0} == {(24, 24, 0, 0)}  # scale 1, one window, next image
+    assert {b[1] for b in bgs if b[0] == 1} == {24} and len({b[4] for b in bgs if b[0] == 1}) > 1  # steps down only
 
 
 def test_plan_barcode_parameters():
