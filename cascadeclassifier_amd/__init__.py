@@ -4,5 +4,6 @@ from ._lib import CascadeError, LIB_PATH  # noqa: F401
 from .detector import (CascadeClassifier, frame_layout, group_rectangles, group_rectangles_device, scale_plan,  # noqa: F401
                        to_gray)
 from .evaluator import CascadeBoost, CvFeatureEvaluator, CvFeatureParams, NegativeMiner, device_exp  # noqa: F401
-from .samples import CvRNG, SampleParams, Sampler, create_training_samples, warp_perspective  # noqa: F401
+from .samples import (CvRNG, SampleParams, Sampler, create_test_samples, create_training_samples, read_info,  # noqa: F401
+                      warp_perspective, write_info)
 from .trainer import BackgroundReader, train_cascade  # noqa: F401

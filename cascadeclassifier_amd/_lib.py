@@ -102,6 +102,10 @@ class SampleRecord(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class TestsetItem(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("iteration", "bg_image", "x", "y", "width", "height")]
+
+
 class SampleBgReader(C.Structure):
     _fields_ = [("sizes", C.c_void_p), ("n_images", C.c_int32)] + \
                [(n, C.c_int32) for n in ("have", "round", "last", "off_x", "off_y", "pt_x", "pt_y", "cur_w", "cur_h")] + \
@@ -233,6 +237,9 @@ SIGNATURES = {
     "cc_sampler_destroy": (None, [_vp]),
     "cc_sampler_set_backgrounds": (_i, [_vp, _vp, _vp, _vp, _i]),
     "cc_sampler_render": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "cc_testset_plan": (_i, [_i, _i, _i, _i, C.POINTER(SampleParams), C.POINTER(C.c_uint64), C.POINTER(SampleBgReader),
+                             C.POINTER(_d), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    "cc_sampler_render_testset": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz]),
 }
 CC_FILL_FILLED, CC_FILL_RATIO, CC_FILL_EXHAUSTED = 0, 1, 2
 CC_SAMPLE_RANDOM_INVERT = 0x7FFFFFFF

@@ -5,6 +5,8 @@
 //           background reader. Serial in the reference too, a few hundred flops per sample.
 //   device  k_sampler_prepare (mask, border extension), k_sample_render (warp, blur, resize and blend of a batch of samples,
 //           one thread per output pixel), k_warp_dense (the warp alone, cc_warp_perspective_u8).
+// The tool's test mode (cvCreateTestSamples: one sample blended into a random rectangle of each background image) adds
+// cc_testset_plan on the host and k_testset_render on the device; placement and pixel arithmetic are shared with the above.
 // The reference warps image and mask into a (w + 2 (w/2)) x (h + 2 (h/2)) canvas, blurs the mask canvas and resizes a
 // rectangle of both to the window. INTER_LINEAR_EXACT reads a 2x2 neighbourhood per output pixel whatever the ratio, so of
 // the canvas only 4 image pixels and the 4x4 mask pixels under the blur of those 4 are ever read: the kernel evaluates
@@ -39,6 +41,11 @@ struct CvRng {  // cv::RNG: multiply-with-carry
     const unsigned t = next();
     const double d = (double)(((uint64_t)t << 32) | next()) * 5.4210108624275221700372640043497e-20;
     return d * (b - a) + a;
+  }
+  // the float overload: ONE draw, (float)next() scaled by 2^-32 in float, every operation rounded to float
+  float uniform(float a, float b) {
+    const float f = (float)next() * 2.3283064365386962890625e-10f;
+    return f * (b - a) + a;
   }
 };
 
@@ -247,6 +254,51 @@ static bool sample_sizes_ok(int src_w, int src_h, int out_w, int out_h) {
          out_h >= 1 && out_w <= SAMPLE_WIN_MAX && out_h <= SAMPLE_WIN_MAX;
 }
 
+// icvPlaceDistortedSample without its pixels (utility.cpp:596-605, :615-648, :658), for a background of out_w x out_h: the
+// quad, its coefficients and row spans, the source rectangle, forecolordev. Shared by the training mode (cc_sample_plan)
+// and the test mode (cc_testset_plan). R keeps its bg_* fields. Returns why the sample is refused, or nullptr.
+static const char* place_sample(int src_w, int src_h, int out_w, int out_h, const cc_sample_params& P, CvRng& rng, int inverse,
+                                cc_sample_record& R, int32_t* spans) {
+  const int dx = src_w / 2, dy = src_h / 2, cw = src_w + 2 * dx, ch = src_h + 2 * dy;
+  double quad[4][2];
+  random_quad(rng, src_w, src_h, P.maxxangle, P.maxyangle, P.maxzangle, quad);
+  for (int i = 0; i < 4; i++) quad[i][0] += (double)dx, quad[i][1] += (double)dy;
+  memcpy(R.quad, quad, sizeof(quad));
+  if (!perspective_coeffs(src_w, src_h, quad, R.coeffs)) return "singular system";
+  if (!row_spans(quad, cw, ch, spans)) return "Quadrangle is nonconvex or degenerated.";
+  // icvPlaceDistortedSample (utility.cpp:615-648): doubles up to the random scale, then float
+  int cx = dx, cy = dy, cwid = src_w, chei = src_h;
+  if (P.inscribe) {
+    cx = (int)std::min(quad[0][0], quad[3][0]);
+    cy = (int)std::min(quad[0][1], quad[1][1]);
+    cwid = (int)(std::max(quad[1][0], quad[2][0]) + 0.5F) - cx;
+    chei = (int)(std::max(quad[2][1], quad[3][1]) + 0.5F) - cy;
+  }
+  const double xshift = rng.uniform(0., P.maxshift);
+  const double yshift = rng.uniform(0., P.maxshift);
+  cx -= (int)(xshift * cwid);
+  cy -= (int)(yshift * chei);
+  cwid = (int)((1.0 + P.maxshift) * cwid);
+  chei = (int)((1.0 + P.maxshift) * chei);
+  const double randscale = rng.uniform(0., P.maxscale);
+  cx -= (int)(0.5 * randscale * cwid);
+  cy -= (int)(0.5 * randscale * chei);
+  cwid = (int)((1.0 + randscale) * cwid);
+  chei = (int)((1.0 + randscale) * chei);
+  const float scale = std::max(((float)cwid) / out_w, ((float)chei) / out_h);
+  const int rx = (int)(-0.5F * (scale * out_w - cwid) + cx);
+  const int ry = (int)(-0.5F * (scale * out_h - chei) + cy);
+  const int rw = (int)(scale * out_w), rh = (int)(scale * out_h);
+  // roi & Rect(0, 0, canvas)
+  const int x0 = std::max(rx, 0), y0 = std::max(ry, 0);
+  const int x1 = (int)std::min<int64_t>((int64_t)rx + rw, cw), y1 = (int)std::min<int64_t>((int64_t)ry + rh, ch);
+  if (x1 <= x0 || y1 <= y0) return "its source rectangle misses the canvas";
+  R.roi_x = x0, R.roi_y = y0, R.roi_w = x1 - x0, R.roi_h = y1 - y0;
+  R.inverse = inverse;
+  R.forecolordev = rng.uniform(-P.maxintensitydev, P.maxintensitydev);
+  return nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Device
 // ------------------------------------------------------------------------------------------------
@@ -319,22 +371,16 @@ __device__ __forceinline__ int reflect101(int i, int n) {
   return min(max(i, 0), n - 1);
 }
 
-// A batch of samples: block = 256 output pixels of one sample (blockIdx.y), thread = one output pixel.
+// One output pixel (ox, oy) of a sample placed into an out_w x out_h window whose pixel there is bg: the one pixel
+// arithmetic of both render kernels. sp: the sample's row spans.
 // The pixel's resize taps (x0, x0 + 1) x (y0, y0 + 1) in the sample's rectangle give the canvas patch of columns
 // rx + x0 - 1 .. rx + x0 + 2 and as many rows: the inner 2x2 are the image taps, the 3x3 around each of them the support of
 // the blurred mask taps (1-2-1 both ways, (S + 8) >> 4). A tap the resize clamps to the border (x1 == x0) has weight 0, so
 // the patch column it gets does not matter. Each patch pixel costs one coordinate evaluation, shared by image and mask.
-__global__ __launch_bounds__(256) void k_sample_render(const uint8_t* __restrict__ src, const uint8_t* __restrict__ mask, int sw, int sh,
-                                                       int bgcolor, const cc_sample_record* __restrict__ recs,
-                                                       const int2* __restrict__ spans, int out_w, int out_h,
-                                                       const uint8_t* __restrict__ backgrounds, uint8_t* __restrict__ out) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= out_w * out_h) return;
-  const int s = blockIdx.y, oy = p / out_w, ox = p - oy * out_w;
-  const cc_sample_record& R = recs[s];
+__device__ __forceinline__ uint8_t sample_pixel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ mask, int sw, int sh,
+                                                unsigned fill, const cc_sample_record& R, const int2* __restrict__ sp, int out_w,
+                                                int out_h, int ox, int oy, int bg) {
   const int cw = sw + 2 * (sw / 2), ch = sh + 2 * (sh / 2);
-  const int2* sp = spans + (size_t)s * ch;
-  const unsigned fill = sample_fill(bgcolor);
   int32_t x0, y0;
   uint16_t wx1, wy1;
   linear_exact_tap(R.roi_w, out_w, ox, x0, wx1);
@@ -376,11 +422,49 @@ __global__ __launch_bounds__(256) void k_sample_render(const uint8_t* __restrict
   const unsigned img = resize_lerp_v(wy0, wy1, resize_lerp_h(wx0, wx1, iv[0][0], iv[0][1]), resize_lerp_h(wx0, wx1, iv[1][0], iv[1][1]));
   const unsigned alpha = resize_lerp_v(wy0, wy1, resize_lerp_h(wx0, wx1, bl[0][0], bl[0][1]), resize_lerp_h(wx0, wx1, bl[1][0], bl[1][1]));
   // blend (utility.cpp:660-671)
-  const size_t o = (size_t)s * out_w * out_h + p;
-  const int bg = backgrounds ? backgrounds[o] : (int)fill;
   int t = min(max(R.forecolordev + (int)img, 0), 255);
   if (R.inverse) t ^= 0xFF;
-  out[o] = (uint8_t)((t * (int)alpha + (255 - (int)alpha) * bg) / 255);
+  return (uint8_t)((t * (int)alpha + (255 - (int)alpha) * bg) / 255);
+}
+
+// A batch of samples of one window size: block = 256 output pixels of one sample (blockIdx.y), thread = one output pixel.
+__global__ __launch_bounds__(256) void k_sample_render(const uint8_t* __restrict__ src, const uint8_t* __restrict__ mask, int sw, int sh,
+                                                       int bgcolor, const cc_sample_record* __restrict__ recs,
+                                                       const int2* __restrict__ spans, int out_w, int out_h,
+                                                       const uint8_t* __restrict__ backgrounds, uint8_t* __restrict__ out) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= out_w * out_h) return;
+  const int s = blockIdx.y, oy = p / out_w, ox = p - oy * out_w;
+  const int ch = sh + 2 * (sh / 2);
+  const unsigned fill = sample_fill(bgcolor);
+  const size_t o = (size_t)s * out_w * out_h + p;
+  const int bg = backgrounds ? backgrounds[o] : (int)fill;
+  out[o] = sample_pixel(src, mask, sw, sh, fill, recs[s], spans + (size_t)s * ch, out_w, out_h, ox, oy, bg);
+}
+
+// One test image's rectangle in a batch (cc_sampler_render_testset): where its image copy starts in the batch's output,
+// that copy's row pitch in bytes, and the rectangle the sample is blended into.
+struct TestsetSlot {
+  size_t offset;
+  int32_t pitch, x, y, w, h, pad;
+};
+
+// A batch of test images whose rectangles differ in size: block = one 256-pixel tile of one rectangle, tiles[blockIdx.x] =
+// (sample, first pixel of the tile in the rectangle's row-major order); thread = one rectangle pixel, which it reads from
+// the image copy and writes back blended (nobody else touches that byte). The grid has exactly as many blocks as tiles.
+__global__ __launch_bounds__(256) void k_testset_render(const uint8_t* __restrict__ src, const uint8_t* __restrict__ mask, int sw, int sh,
+                                                        int bgcolor, const cc_sample_record* __restrict__ recs,
+                                                        const int2* __restrict__ spans, const TestsetSlot* __restrict__ slots,
+                                                        const int2* __restrict__ tiles, uint8_t* out) {
+  const int2 tile = tiles[blockIdx.x];
+  const int s = tile.x;
+  const TestsetSlot L = slots[s];
+  const int p = tile.y + threadIdx.x;
+  if (p >= L.w * L.h) return;
+  const int oy = p / L.w, ox = p - oy * L.w;
+  const int ch = sh + 2 * (sh / 2);
+  uint8_t* px = out + L.offset + (size_t)(L.y + oy) * L.pitch + (L.x + ox);
+  *px = sample_pixel(src, mask, sw, sh, sample_fill(bgcolor), recs[s], spans + (size_t)s * ch, L.w, L.h, ox, oy, (int)*px);
 }
 
 // The warp alone into an existing image: thread = one destination pixel, written only inside its row's span.
@@ -411,6 +495,8 @@ struct cc_sampler {
   DevBuf<cc_sample_record> recs;
   DevBuf<int2> spans;
   DevBuf<uint8_t> bgwin, out, scaled;
+  DevBuf<TestsetSlot> slots;  // test mode
+  DevBuf<int2> tiles;
 };
 
 // One background image at the size a record names, through the pyramid's exact resize (k_resize); the result has
@@ -439,8 +525,7 @@ cc_status cc_sample_plan(int src_w, int src_h, int out_w, int out_h, const cc_sa
     return set_error(CC_ERR_INVALID_ARG, "cc_sample_plan: bad argument (source sides %d..%d, window sides 1..%d)", SAMPLE_SRC_MIN,
                      SAMPLE_SRC_MAX, SAMPLE_WIN_MAX);
   if (bg && (!bg->sizes || bg->n_images < 1)) return set_error(CC_ERR_INVALID_ARG, "cc_sample_plan: background reader without images");
-  const cc_sample_params& P = *params;
-  const int dx = src_w / 2, dy = src_h / 2, cw = src_w + 2 * dx, ch = src_h + 2 * dy;
+  const int ch = src_h + 2 * (src_h / 2);
   CvRng rng{*rng_state};
   cc_sample_bg_reader reader;
   if (bg) reader = *bg;
@@ -451,48 +536,65 @@ cc_status cc_sample_plan(int src_w, int src_h, int out_w, int out_h, const cc_sa
     R.bg_image = -1;
     if (bg && !bg_take(reader, rng, out_w, out_h, R))
       return set_error(CC_ERR_INVALID_ARG, "cc_sample_plan: no background image holds a %d x %d window", out_w, out_h);
-    int inverse = P.invert;
-    if (P.invert == CC_SAMPLE_RANDOM_INVERT) inverse = rng.uniform(0, 2);
-    double quad[4][2];
-    random_quad(rng, src_w, src_h, P.maxxangle, P.maxyangle, P.maxzangle, quad);
-    for (int i = 0; i < 4; i++) quad[i][0] += (double)dx, quad[i][1] += (double)dy;
-    memcpy(R.quad, quad, sizeof(quad));
-    if (!perspective_coeffs(src_w, src_h, quad, R.coeffs)) return set_error(CC_ERR_INVALID_ARG, "cc_sample_plan: sample %d: singular system", s);
-    if (!row_spans(quad, cw, ch, spans ? spans + 2 * (size_t)s * ch : own_spans.data()))
-      return set_error(CC_ERR_INVALID_ARG, "cc_sample_plan: sample %d: Quadrangle is nonconvex or degenerated.", s);
-    // icvPlaceDistortedSample (utility.cpp:615-648): doubles up to the random scale, then float
-    int cx = dx, cy = dy, cwid = src_w, chei = src_h;
-    if (P.inscribe) {
-      cx = (int)std::min(quad[0][0], quad[3][0]);
-      cy = (int)std::min(quad[0][1], quad[1][1]);
-      cwid = (int)(std::max(quad[1][0], quad[2][0]) + 0.5F) - cx;
-      chei = (int)(std::max(quad[2][1], quad[3][1]) + 0.5F) - cy;
-    }
-    const double xshift = rng.uniform(0., P.maxshift);
-    const double yshift = rng.uniform(0., P.maxshift);
-    cx -= (int)(xshift * cwid);
-    cy -= (int)(yshift * chei);
-    cwid = (int)((1.0 + P.maxshift) * cwid);
-    chei = (int)((1.0 + P.maxshift) * chei);
-    const double randscale = rng.uniform(0., P.maxscale);
-    cx -= (int)(0.5 * randscale * cwid);
-    cy -= (int)(0.5 * randscale * chei);
-    cwid = (int)((1.0 + randscale) * cwid);
-    chei = (int)((1.0 + randscale) * chei);
-    const float scale = std::max(((float)cwid) / out_w, ((float)chei) / out_h);
-    const int rx = (int)(-0.5F * (scale * out_w - cwid) + cx);
-    const int ry = (int)(-0.5F * (scale * out_h - chei) + cy);
-    const int rw = (int)(scale * out_w), rh = (int)(scale * out_h);
-    // roi & Rect(0, 0, canvas)
-    const int x0 = std::max(rx, 0), y0 = std::max(ry, 0);
-    const int x1 = (int)std::min<int64_t>((int64_t)rx + rw, cw), y1 = (int)std::min<int64_t>((int64_t)ry + rh, ch);
-    if (x1 <= x0 || y1 <= y0) return set_error(CC_ERR_INVALID_ARG, "cc_sample_plan: sample %d: its source rectangle misses the canvas", s);
-    R.roi_x = x0, R.roi_y = y0, R.roi_w = x1 - x0, R.roi_h = y1 - y0;
-    R.inverse = inverse;
-    R.forecolordev = rng.uniform(-P.maxintensitydev, P.maxintensitydev);
+    int inverse = params->invert;
+    if (params->invert == CC_SAMPLE_RANDOM_INVERT) inverse = rng.uniform(0, 2);
+    const char* why = place_sample(src_w, src_h, out_w, out_h, *params, rng, inverse, R, spans ? spans + 2 * (size_t)s * ch : own_spans.data());
+    if (why) return set_error(CC_ERR_INVALID_ARG, "cc_sample_plan: sample %d: %s", s, why);
   }
   *rng_state = rng.state;
   if (bg) *bg = reader;
+  return CC_OK;
+}
+
+cc_status cc_testset_plan(int src_w, int src_h, int win_w, int win_h, const cc_sample_params* params, uint64_t* rng_state,
+                          cc_sample_bg_reader* bg, double* maxscale, int32_t* iterations_done, int num, int32_t* n_emitted,
+                          cc_testset_item* items, cc_sample_record* records, int32_t* spans) {
+  if (!params || !rng_state || !bg || !maxscale || !iterations_done || !n_emitted || num < 0 || *iterations_done < 0 ||
+      (num && (!items || !records)) || !sample_sizes_ok(src_w, src_h, win_w, win_h))
+    return set_error(CC_ERR_INVALID_ARG, "cc_testset_plan: bad argument (source sides %d..%d, window sides 1..%d)", SAMPLE_SRC_MIN,
+                     SAMPLE_SRC_MAX, SAMPLE_WIN_MAX);
+  if (!bg->sizes || bg->n_images < 1) return set_error(CC_ERR_INVALID_ARG, "cc_testset_plan: background reader without images");
+  cc_sample_params P = *params;  // icvPlaceDistortedSample(..., 1, 0.0, 0.0, &data) (utility.cpp:1099-1101)
+  P.inscribe = 1, P.maxshift = 0.0, P.maxscale = 0.0;
+  const int ch = src_h + 2 * (src_h / 2);
+  CvRng rng{*rng_state};
+  cc_sample_bg_reader reader = *bg;
+  double ms = *maxscale;
+  const int first = *iterations_done;
+  const int last = (int)std::min<int64_t>((int64_t)first + num, reader.n_images);  // count = MIN(count, cvbgdata->count)
+  std::vector<int32_t> own_spans(spans ? 0 : 2 * (size_t)ch);
+  int n = 0;
+  for (int i = first; i < last; i++) {
+    if (!bg_next_image(reader, rng, 10, 10))  // icvInitBackgroundReaders(bgfilename, Size(10, 10)) (:1055)
+      return set_error(CC_ERR_INVALID_ARG, "cc_testset_plan: iteration %d: no background image has both sides of 10 or more", i + 1);
+    const int cols = reader.sizes[2 * reader.last], rows = reader.sizes[2 * reader.last + 1];
+    if (ms < 0.0) ms = std::min(0.7F * cols / win_w, 0.7F * rows / win_h);  // float, assigned once (:1082-1085)
+    if (ms < 1.0F) continue;
+    const float scale = rng.uniform(1.0F, (float)ms);
+    const float fw = scale * win_w, fh = scale * win_h;
+    if (!(fw >= 1.0F && fw < SAMPLE_WIN_MAX + 1.0F && fh >= 1.0F && fh < SAMPLE_WIN_MAX + 1.0F))
+      return set_error(CC_ERR_INVALID_ARG, "cc_testset_plan: iteration %d: rectangle sides outside 1..%d", i + 1, SAMPLE_WIN_MAX);
+    const int width = (int)fw, height = (int)fh;
+    const int x = (int)(rng.uniform(0.1, 0.8) * (cols - width));
+    const int y = (int)(rng.uniform(0.1, 0.8) * (rows - height));
+    if (x < 0 || y < 0 || width > cols - x || height > rows - y)  // the reference's src(Rect(x, y, width, height)) asserts
+      return set_error(CC_ERR_INVALID_ARG, "cc_testset_plan: iteration %d: rectangle %d x %d at (%d, %d) leaves its %d x %d image", i + 1,
+                       width, height, x, y, cols, rows);
+    int inverse = P.invert;
+    if (P.invert == CC_SAMPLE_RANDOM_INVERT) inverse = rng.uniform(0, 2);
+    cc_sample_record& R = records[n];
+    memset(&R, 0, sizeof(R));
+    R.bg_image = -1;  // the record's own background fields belong to the training mode's reader
+    const char* why = place_sample(src_w, src_h, width, height, P, rng, inverse, R, spans ? spans + 2 * (size_t)n * ch : own_spans.data());
+    if (why) return set_error(CC_ERR_INVALID_ARG, "cc_testset_plan: iteration %d: %s", i + 1, why);
+    items[n] = cc_testset_item{i + 1, reader.last, x, y, width, height};
+    n++;
+  }
+  *rng_state = rng.state;
+  *bg = reader;
+  *maxscale = ms;
+  *iterations_done = std::max(first, last);
+  *n_emitted = n;
   return CC_OK;
 }
 
@@ -619,6 +721,97 @@ cc_status cc_sampler_render(cc_sampler* s, const cc_sample_record* records, cons
                        s->h, s->bgcolor, s->recs.p, s->spans.p, out_w, out_h, with_bg ? s->bgwin.p : nullptr, s->out.p);
     CC_HIP(hipGetLastError());
     CC_HIP(copy_sync(out + first * area, s->out.p, nb * area, hipMemcpyDeviceToHost, q));
+  }
+  return CC_OK;
+}
+
+cc_status cc_sampler_render_testset(cc_sampler* s, const cc_testset_item* items, const cc_sample_record* records, const int32_t* spans,
+                                    int n, int max_batch, uint8_t* const* out_host, void* out_device, size_t frame_stride) {
+  if (!s || n < 0 || (n && (!items || !records || !spans || (!out_host && !out_device))))
+    return set_error(CC_ERR_INVALID_ARG, "cc_sampler_render_testset: bad argument");
+  const int cw = s->w + 2 * (s->w / 2), ch = s->h + 2 * (s->h / 2);
+  for (int i = 0; i < n; i++) {
+    const cc_testset_item& I = items[i];
+    const cc_sample_record& R = records[i];
+    if (I.bg_image < 0 || (size_t)I.bg_image >= s->bgs.size())
+      return set_error(CC_ERR_INVALID_ARG, "cc_sampler_render_testset: item %d: background image %d of %zu", i, I.bg_image, s->bgs.size());
+    const cc_sampler::BgImage& b = s->bgs[I.bg_image];
+    // the kernel writes rows y .. y + height - 1, columns x .. x + width - 1 of the image's copy: all of them must be inside
+    if (I.width < 1 || I.height < 1 || I.width > SAMPLE_WIN_MAX || I.height > SAMPLE_WIN_MAX || I.x < 0 || I.y < 0 || I.x > b.w - I.width ||
+        I.y > b.h - I.height)
+      return set_error(CC_ERR_INVALID_ARG, "cc_sampler_render_testset: item %d: rectangle outside its %d x %d image (sides 1..%d)", i, b.w,
+                       b.h, SAMPLE_WIN_MAX);
+    if (R.roi_x < 0 || R.roi_y < 0 || R.roi_w < 1 || R.roi_h < 1 || R.roi_x > cw - R.roi_w || R.roi_y > ch - R.roi_h)
+      return set_error(CC_ERR_INVALID_ARG, "cc_sampler_render_testset: record %d: rectangle outside the %d x %d canvas", i, cw, ch);
+    if (out_host && !out_host[i]) return set_error(CC_ERR_INVALID_ARG, "cc_sampler_render_testset: item %d: output pointer is NULL", i);
+    if (out_device) {
+      const cc_sampler::BgImage& b0 = s->bgs[items[0].bg_image];
+      if (b.w != b0.w || b.h != b0.h)
+        return set_error(CC_ERR_INVALID_ARG, "cc_sampler_render_testset: a device output needs backgrounds of one size (item %d: %d x %d, item 0: %d x %d)",
+                         i, b.w, b.h, b0.w, b0.h);
+    }
+  }
+  if (out_device && n) {
+    const cc_sampler::BgImage& b0 = s->bgs[items[0].bg_image];
+    if (frame_stride == 0) frame_stride = (size_t)b0.w * b0.h;
+    if (frame_stride < (size_t)b0.w * b0.h) return set_error(CC_ERR_INVALID_ARG, "cc_sampler_render_testset: frame_stride below rows * cols");
+  }
+  cc_status st = ensure_device(s->device);
+  if (st != CC_OK) return st;
+  if (n == 0) return CC_OK;
+  // Batch: items are added while what the batch allocates (record, spans, slot, tiles and, without a device output, the image
+  // copy) stays within a quarter of the free memory, at most 32768 items and 2^24 tiles (a rectangle has at most 65536), and
+  // at most max_batch when the caller gives one. One item always goes.
+  size_t free_b = 0, total_b = 0;
+  CC_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = free_b / 4, max_tiles = (size_t)1 << 24;
+  hipStream_t q = s->st.s;
+  std::vector<TestsetSlot> slots;
+  std::vector<int2> tiles;
+  for (size_t first = 0; first < (size_t)n;) {
+    slots.clear();
+    tiles.clear();
+    size_t bytes = 0, image_bytes = 0;
+    while (first + slots.size() < (size_t)n) {
+      const size_t i = first + slots.size();
+      const cc_testset_item& I = items[i];
+      const cc_sampler::BgImage& b = s->bgs[I.bg_image];
+      const size_t area = (size_t)b.w * b.h, nt = ((size_t)I.width * I.height + 255) / 256;
+      const size_t need = sizeof(cc_sample_record) + (size_t)ch * sizeof(int2) + sizeof(TestsetSlot) + nt * sizeof(int2) + (out_device ? 0 : area);
+      if (!slots.empty() && (bytes + need > budget || tiles.size() + nt > max_tiles || slots.size() >= 32768 ||
+                             (max_batch > 0 && slots.size() >= (size_t)max_batch)))
+        break;
+      TestsetSlot L;
+      L.offset = out_device ? i * frame_stride : image_bytes;
+      L.pitch = b.w, L.x = I.x, L.y = I.y, L.w = I.width, L.h = I.height, L.pad = 0;
+      for (size_t t = 0; t < nt; t++) tiles.push_back(make_int2((int)slots.size(), (int)(t * 256)));
+      slots.push_back(L);
+      bytes += need;
+      image_bytes += area;
+    }
+    const size_t nb = slots.size();
+    CC_HIP(s->recs.ensure(nb));
+    CC_HIP(s->spans.ensure(nb * ch));
+    if (!out_device) CC_HIP(s->out.ensure(image_bytes));
+    uint8_t* base = out_device ? (uint8_t*)out_device : s->out.p;
+    CC_HIP(hipMemcpyAsync(s->recs.p, records + first, nb * sizeof(cc_sample_record), hipMemcpyHostToDevice, q));
+    CC_HIP(hipMemcpyAsync(s->spans.p, spans + 2 * first * ch, nb * ch * sizeof(int2), hipMemcpyHostToDevice, q));
+    CC_HIP(s->slots.upload(slots, q));
+    CC_HIP(s->tiles.upload(tiles, q));
+    for (size_t i = 0; i < nb; i++) {  // a fresh copy per item: two items of one image do not see each other
+      const cc_sampler::BgImage& b = s->bgs[items[first + i].bg_image];
+      CC_HIP(hipMemcpy2DAsync(base + slots[i].offset, b.w, b.px.p, b.pitch, b.w, b.h, hipMemcpyDeviceToDevice, q));
+    }
+    hipLaunchKernelGGL(k_testset_render, dim3((unsigned)tiles.size()), dim3(256), 0, q, s->src.p, s->mask.p, s->w, s->h, s->bgcolor,
+                       s->recs.p, s->spans.p, s->slots.p, s->tiles.p, base);
+    CC_HIP(hipGetLastError());
+    if (out_host)
+      for (size_t i = 0; i < nb; i++) {
+        const cc_sampler::BgImage& b = s->bgs[items[first + i].bg_image];
+        CC_HIP(hipMemcpyAsync(out_host[first + i], base + slots[i].offset, (size_t)b.w * b.h, hipMemcpyDeviceToHost, q));
+      }
+    CC_HIP(hipStreamSynchronize(q));  // slots and tiles are host memory of this frame, the device buffers are reused
+    first += nb;
   }
   return CC_OK;
 }

@@ -5,6 +5,11 @@
     python -m cascadeclassifier_amd.samples -img object.pgm -vec out.vec -num 1000 -w 24 -h 24
 
 takes the tool's options with the tool's defaults. Images are read as binary .pgm or .npy (no image decoder here).
+
+The tool's test mode (cvCreateTestSamples: one distorted copy pasted into a random rectangle of each background, with the
+ground truth in an info file) is cc_testset_plan + cc_sampler_render_testset, create_test_samples here and
+
+    python -m cascadeclassifier_amd.samples -img object.pgm -bg bg.txt -info out/info.dat [-maxscale 4]
 """
 from __future__ import annotations
 
@@ -72,8 +77,40 @@ def plan(src_w: int, src_h: int, win, params: SampleParams, rng: CvRNG, n: int, 
     return recs, spans
 
 
+class TestsetState:
+    """What cvCreateTestSamples carries from one iteration to the next, between calls of plan_testset: the background
+    reader, the sticky maxscale (negative: taken from the first image drawn) and the iterations made so far."""
+    __test__ = False  # not a test class, whatever the name starts with
+
+    def __init__(self, bg_sizes, maxscale: float = -1.0):
+        self.reader = _BgReader(bg_sizes)
+        self.maxscale = float(maxscale)
+        self.iterations = 0
+
+
+def plan_testset(src_w: int, src_h: int, win, params: SampleParams, rng: CvRNG, num: int, state: TestsetState):
+    """Host only: up to num more iterations of cvCreateTestSamples' loop (cc_testset_plan). (items, records, spans) of the
+    emitted samples: items is a list of (iteration, bg_index, x, y, width, height), records a ctypes array of
+    cc_sample_record, spans (n, canvas rows, 2) int32. rng and state are carried on."""
+    win_w, win_h = win
+    cap = max(min(num, len(state.reader.sizes)), 1)  # the loop runs MIN(num, images) times in all
+    items = (L.TestsetItem * cap)()
+    recs = (L.SampleRecord * cap)()
+    ch = src_h + 2 * (src_h // 2)
+    spans = np.zeros((cap, ch, 2), np.int32)
+    rs, ms, done, n = C.c_uint64(rng.state), C.c_double(state.maxscale), C.c_int32(state.iterations), C.c_int32(0)
+    p = params._c()
+    L.check(L.lib().cc_testset_plan(src_w, src_h, win_w, win_h, C.byref(p), C.byref(rs), C.byref(state.reader.c), C.byref(ms),
+                                    C.byref(done), num, C.byref(n), C.cast(items, C.c_void_p),
+                                    C.cast(recs, C.c_void_p), _vp(spans)))
+    rng.state, state.maxscale, state.iterations = rs.value, ms.value, done.value
+    out = [(it.iteration, it.bg_image, it.x, it.y, it.width, it.height) for it in items[:n.value]]
+    return out, recs, spans[:n.value]
+
+
 class Sampler:
-    """One object image on the device (icvStartSampleDistortion): generate() turns it into training samples."""
+    """One object image on the device (icvStartSampleDistortion): generate() turns it into training samples,
+    generate_testset() into detection test images."""
 
     def __init__(self, image, bgcolor: int = 0, bgthreshold: int = 80, device: int = 0):
         image = np.ascontiguousarray(image, np.uint8)
@@ -84,6 +121,8 @@ class Sampler:
         self._s = C.c_void_p()
         self._reader = None
         self._reader_win = None
+        self._bg_sizes = None
+        self._testset = None
         L.check(L.lib().cc_sampler_create(device, _vp(image), self.w, self.h, self.w, bgcolor, bgthreshold, C.byref(self._s)))
 
     def close(self):
@@ -108,6 +147,8 @@ class Sampler:
         L.check(L.lib().cc_sampler_set_backgrounds(self._s, C.cast(ptrs, C.c_void_p), _vp(ws), _vp(hs), len(imgs)))
         self._reader = _BgReader(np.stack([ws, hs], axis=1)) if imgs else None
         self._reader_win = None
+        self._bg_sizes = np.stack([ws, hs], axis=1) if imgs else None
+        self._testset = None
 
     def plan(self, n: int, win, params: SampleParams, rng: CvRNG):
         if self._reader is not None:
@@ -136,6 +177,47 @@ class Sampler:
                                           _vp(bg) if bg is not None else None, max_batch, _vp(out)))
         return out
 
+    def restart_testset(self):
+        """Forget the test mode's reader and iteration count: the next generate_testset starts the tool's loop again."""
+        self._testset = None
+
+    def generate_testset(self, num: int, win, params: SampleParams, rng: CvRNG, maxscale: float = -1.0, max_batch: int = 0,
+                         device_out=None, frame_stride: int = 0):
+        """Up to num more iterations of cvCreateTestSamples over the set_backgrounds images (MIN(num, images) in all; the
+        reader and the iteration count stay in the Sampler until set_backgrounds or restart_testset, so calls of a and b
+        equal one of a + b). Returns (samples, maxscale): samples is a list of (image, (x, y, w, h), iteration, bg_index),
+        the image a fresh copy of background bg_index with the object in the rectangle; maxscale is the value to pass to
+        the next call (a negative one is replaced by the first image's and then kept).
+        device_out: a device pointer that receives the images as an (n, rows, cols) stack, frame_stride bytes apart (0:
+        rows * cols), with room for MIN(num, images) frames; every image must then have one size, and the list's images
+        are None (nothing comes back to the host)."""
+        if getattr(self, "_bg_sizes", None) is None:
+            raise ValueError("generate_testset: set_backgrounds first")
+        self._check(params)
+        st = self._testset
+        if st is None:
+            st = self._testset = TestsetState(self._bg_sizes)
+        before = (rng.state, st.maxscale, st.iterations, bytes(st.reader.c))
+        st.maxscale = float(maxscale)
+        try:
+            return self._generate_testset(num, win, params, rng, st, max_batch, device_out, frame_stride)
+        except Exception:  # a refused call leaves the stream of draws where it was
+            rng.state, st.maxscale, st.iterations = before[:3]
+            C.memmove(C.byref(st.reader.c), before[3], len(before[3]))
+            raise
+
+    def _generate_testset(self, num, win, params, rng, st, max_batch, device_out, frame_stride):
+        items, recs, spans = plan_testset(self.w, self.h, win, params, rng, num, st)
+        n = len(items)
+        its = (L.TestsetItem * max(n, 1))(*[L.TestsetItem(*it) for it in items])
+        images, ptrs = [None] * n, None
+        if device_out is None:
+            images = [np.empty((int(self._bg_sizes[b][1]), int(self._bg_sizes[b][0])), np.uint8) for _, b, *_ in items]
+            ptrs = C.cast((C.c_void_p * max(n, 1))(*[i.ctypes.data for i in images]), C.c_void_p)
+        L.check(L.lib().cc_sampler_render_testset(self._s, C.cast(its, C.c_void_p), C.cast(recs, C.c_void_p), _vp(spans), n, max_batch,
+                                                  ptrs, C.c_void_p(device_out) if device_out is not None else None, frame_stride))
+        return [(images[k], tuple(items[k][2:6]), items[k][0], items[k][1]) for k in range(n)], st.maxscale
+
 
 def create_training_samples(vec_path: str, image, num: int = 1000, w: int = 24, h: int = 24, *, bgcolor=0, bgthreshold=80,
                             invert=0, maxintensitydev=40, maxxangle=1.1, maxyangle=1.1, maxzangle=0.5, backgrounds=None,
@@ -152,6 +234,63 @@ def create_training_samples(vec_path: str, image, num: int = 1000, w: int = 24, 
         s.close()
     vec_write(vec_path, out, w, h)
     return out
+
+
+def write_gray(path: str, image) -> None:
+    """A gray image as a binary .pgm (P5, 8 bit)."""
+    image = np.ascontiguousarray(image, np.uint8)
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (image.shape[1], image.shape[0]))
+        f.write(image.tobytes())
+
+
+def write_info(path: str, entries) -> None:
+    """The tool's info file (a detection test set's ground truth, or the -info input): per line an image name, a count and
+    count rectangles x y w h. entries: (name, rectangles) pairs."""
+    with open(path, "w") as f:
+        for name, rects in entries:
+            rects = [tuple(int(v) for v in r) for r in rects]
+            f.write(" ".join([name, str(len(rects))] + ["%d %d %d %d" % r for r in rects]) + "\n")
+
+
+def read_info(path: str):
+    """The entries of an info file as a list of (name, (count, 4) int32 array); names are as written, relative to the file."""
+    entries = []
+    for line_no, line in enumerate(open(path), 1):
+        tok = line.split()
+        if not tok:
+            continue
+        if len(tok) < 2 or not tok[1].isdigit() or len(tok) != 2 + 4 * int(tok[1]):
+            raise ValueError(f"{path}:{line_no}: expected 'name count' and count times 'x y w h'")
+        entries.append((tok[0], np.array(tok[2:], np.int32).reshape(-1, 4)))
+    return entries
+
+
+def create_test_samples(info_path: str, image, backgrounds, num: int = 1000, w: int = 24, h: int = 24, *, maxscale=-1.0, bgcolor=0,
+                        bgthreshold=80, invert=0, maxintensitydev=40, maxxangle=1.1, maxyangle=1.1, maxzangle=0.5, rngseed=12345,
+                        device=0):
+    """cvCreateTestSamples: MIN(num, len(backgrounds)) times one distorted copy of `image` is pasted into a random rectangle
+    of a randomly drawn background (scale 1..maxscale of the w x h window; maxscale < 0: 0.7 of the first image drawn).
+    Each image is written next to info_path as "%04d_%04d_%04d_%04d_%04d.pgm" % (iteration, x, y, width, height) (the tool
+    writes .jpg, and cuts the name short) with the line "<name> 1 x y width height" in info_path. Returns (images, rects):
+    a list of (rows, cols) uint8 arrays and an (n, 4) int32 array."""
+    s = Sampler(image, bgcolor, bgthreshold, device)
+    try:
+        s.set_backgrounds(backgrounds)
+        p = SampleParams(bgcolor, bgthreshold, invert, maxintensitydev, maxxangle, maxyangle, maxzangle)
+        samples, _ = s.generate_testset(num, (w, h), p, CvRNG(rngseed), maxscale)
+    finally:
+        s.close()
+    base = os.path.dirname(info_path)
+    if base:
+        os.makedirs(base, exist_ok=True)
+    entries = []
+    for img, rect, iteration, _ in samples:
+        name = "%04d_%04d_%04d_%04d_%04d.pgm" % ((iteration,) + rect)
+        write_gray(os.path.join(base, name), img)
+        entries.append((name, [rect]))
+    write_info(info_path, entries)
+    return [smp[0] for smp in samples], np.array([smp[1] for smp in samples], np.int32).reshape(-1, 4)
 
 
 def warp_perspective(src, dst, quad, device: int = 0) -> np.ndarray:
@@ -198,13 +337,18 @@ def read_background_list(path: str):
     return [read_gray(os.path.join(base, n)) for n in names]
 
 
-def main(argv=None) -> int:
+def parse_args(argv=None):
+    """(mode, options) of a command line: the mode is chosen as createsamples.cpp:184-198 does -- "training" (-img and
+    -vec: a .vec of distorted copies) before "test" (-img, -bg and -info: test images and their info file)."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m cascadeclassifier_amd.samples", add_help=False,
-                                 description="createsamples: a .vec of distorted copies of one image")
+                                 description="createsamples: a .vec of distorted copies of one image (-img -vec), or test "
+                                             "images with one copy pasted into each background (-img -bg -info)")
     ap.add_argument("--help", action="help")
     ap.add_argument("-img", required=True)
-    ap.add_argument("-vec", required=True)
+    ap.add_argument("-vec")
+    ap.add_argument("-info")
+    ap.add_argument("-maxscale", type=float, default=-1.0)
     ap.add_argument("-bg")
     ap.add_argument("-num", type=int, default=1000)
     ap.add_argument("-bgcolor", type=int, default=0)
@@ -219,7 +363,22 @@ def main(argv=None) -> int:
     ap.add_argument("-h", type=int, default=24)
     ap.add_argument("-rngseed", type=int, default=12345)
     a = ap.parse_args(argv)
+    if a.vec:
+        return "training", a
+    if a.bg and a.info:
+        return "test", a
+    ap.error("nothing to do: give -vec (training samples), or -bg and -info (test images)")
+
+
+def main(argv=None) -> int:
+    mode, a = parse_args(argv)
     invert = RANDOM_INVERT if a.randinv else 1 if a.inv else 0
+    if mode == "test":
+        images, _ = create_test_samples(a.info, read_gray(a.img), read_background_list(a.bg), a.num, a.w, a.h, maxscale=a.maxscale,
+                                        bgcolor=a.bgcolor, bgthreshold=a.bgthresh, invert=invert, maxintensitydev=a.maxidev,
+                                        maxxangle=a.maxxangle, maxyangle=a.maxyangle, maxzangle=a.maxzangle, rngseed=a.rngseed)
+        print(f"{a.info}: {len(images)} test images")
+        return 0
     out = create_training_samples(a.vec, read_gray(a.img), a.num, a.w, a.h, bgcolor=a.bgcolor, bgthreshold=a.bgthresh, invert=invert,
                                   maxintensitydev=a.maxidev, maxxangle=a.maxxangle, maxyangle=a.maxyangle, maxzangle=a.maxzangle,
                                   backgrounds=read_background_list(a.bg) if a.bg else None, rngseed=a.rngseed)

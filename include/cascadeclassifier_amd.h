@@ -864,6 +864,51 @@ CC_API cc_status cc_sampler_set_backgrounds(cc_sampler* s, const uint8_t* const*
 CC_API cc_status cc_sampler_render(cc_sampler* s, const cc_sample_record* records, const int32_t* spans, int n, int out_w,
                                    int out_h, const uint8_t* backgrounds, int max_batch, uint8_t* out);
 
+/* Test mode of the tool: detection test sets. Replaces cvCreateTestSamples (tools/createsamples/utility.cpp:1031-1123; chosen
+ * in createsamples.cpp:193-198 by -img, -bg and -info without -vec): the loop's draws and its rectangle (:1078-1098) ->
+ * cc_testset_plan (host, serial), icvPlaceDistortedSample into src(Rect(x, y, width, height)) (:1099-1101, :580-672) ->
+ * cc_sampler_render_testset (device). Writing the images and info.dat (:1103-1111) is host file IO (samples.py). */
+typedef struct cc_testset_item {
+  int32_t iteration;           /* the tool's i + 1, the first field of the file name (:1103) */
+  int32_t bg_image;            /* index into the background list */
+  int32_t x, y, width, height; /* the object's rectangle in that image: the ground truth of the info line (:1107) */
+} cc_testset_item;
+
+/* Host only, no device. Makes every random draw of up to `num` more iterations of the tool's loop for a win_w x win_h
+ * window, in the tool's order. The loop runs MIN(num, bg->n_images) times in all (:1078): *iterations_done (0 before the
+ * first call) is carried on, and this call makes MIN(num, n_images - *iterations_done) iterations, so that calls of a and b
+ * equal one call of a + b. Per iteration: the background image (icvGetNextFromBackgroundData with the reader's window of
+ * 10 x 10, :1055, :765-831: uniform(0, RAND_MAX) % n_images, an image with a side under 10 is drawn again, n_images
+ * rejections in a row fail); a negative *maxscale becomes MIN(0.7F * cols / win_w, 0.7F * rows / win_h) of THIS image in
+ * float and keeps that value from then on (:1082-1085; the tool's default is -1); *maxscale < 1 skips the iteration with
+ * its background draw spent (:1087); scale = uniform(1.0F, (float)maxscale), cv::RNG's float overload: one next(),
+ * (float)next() * 2.3283064365386962890625e-10f * (b - a) + a in float; width = (int)(scale * win_w), height likewise;
+ * x = (int)(uniform(0.1, 0.8) * (cols - width)), y likewise (double); uniform(0, 2) when invert is random; then the
+ * placement's plan exactly as cc_sample_plan makes it for a window of width x height with inscribe = 1, maxshift = 0,
+ * maxscale = 0 and no background reader (these three fields of *params are ignored here).
+ * items / records: room for `num` entries; spans (may be NULL): room for `num` samples' row spans, as cc_sample_plan lays
+ * them out. *n_emitted entries are filled. A rectangle that leaves its image (x < 0, y < 0, x + width > cols,
+ * y + height > rows; the reference's src(Rect) asserts), a width or height outside 1..4096, no image with both sides of 10
+ * or more, and everything cc_sample_plan refuses are CC_ERR_INVALID_ARG naming the iteration; *rng_state, *bg, *maxscale and
+ * *iterations_done are then as before the call. bg: as for cc_sample_plan, zeroed before the first call, kept apart from
+ * a training-mode reader. */
+CC_API cc_status cc_testset_plan(int src_w, int src_h, int win_w, int win_h, const cc_sample_params* params, uint64_t* rng_state,
+                                 cc_sample_bg_reader* bg, double* maxscale, int32_t* iterations_done, int num, int32_t* n_emitted,
+                                 cc_testset_item* items, cc_sample_record* records, int32_t* spans);
+
+/* Renders n planned test images: for each item a fresh copy of its cc_sampler_set_backgrounds image with the sample blended
+ * into Rect(x, y, width, height), the pixel arithmetic being cc_sampler_render's. One grid per batch covers rectangles of
+ * different sizes (a table of 256-pixel tiles); the image copies are device to device. out_host (may be NULL): n pointers,
+ * item i's image as rows * cols bytes of its background. out_device (may be NULL): device memory that receives the
+ * (n, rows, cols) stack, frame i at out_device + i * frame_stride bytes (0: rows * cols); every item's background must then
+ * have one size, and frame_stride at least rows * cols. At least one of the two when n > 0. Batches are sized from free
+ * device memory over the image bytes, and hold at most max_batch items when max_batch > 0. An item whose image index or
+ * rectangle is outside its bounds, a side outside 1..4096, and a record whose source rectangle leaves the canvas are
+ * CC_ERR_INVALID_ARG. */
+CC_API cc_status cc_sampler_render_testset(cc_sampler* s, const cc_testset_item* items, const cc_sample_record* records,
+                                           const int32_t* spans, int n, int max_batch, uint8_t* const* out_host, void* out_device,
+                                           size_t frame_stride);
+
 #ifdef __cplusplus
 }
 #endif
