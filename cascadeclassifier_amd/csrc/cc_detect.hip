@@ -183,6 +183,7 @@ cc_status launch_eval(cc_detector* d, const Plan* P, int slot, int nchan, bool t
     const EvalLaunch& L = launches[i];
     if (L.n_tiles == 0) continue;
     A.tiles = L.tiles;
+    A.wave_below = L.wave_below >= 0 ? L.wave_below : d->wave_below;
     if (L.fn) {
       void* params[] = {&A};
       // (the pass's EV_EVAL pair spans all cascade-kernel launches; the STEP-1 module's launch is also timed on its own)

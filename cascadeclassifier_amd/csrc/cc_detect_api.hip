@@ -109,7 +109,10 @@ static cc_status spec_install(cc_detector* d, const std::vector<SpecCode>& codes
   int n_fresh = 0;
   if (cc_status st = spec_load(d->m, codes, tmode, d->lds, fresh, &n_fresh); st != CC_OK) return st;  // the old kernel stays
   d->unload_spec();
-  for (int i = 0; i < n_fresh; i++) d->spec[i] = fresh[i];
+  for (int i = 0; i < n_fresh; i++) {
+    d->spec[i] = fresh[i];
+    d->spec[i].wave_below = spec_wave_below(d->wave_below, fresh[i].only_step, fresh[i].tile_y);
+  }
   d->n_spec = n_fresh;
   d->spec_stages = k;
   return CC_OK;

@@ -225,7 +225,12 @@ struct SpecModule {
   size_t lds = 0;
   int tile_y = TILE_Y;
   int only_step = 0;
+  int wave_below = -1;  // >= 0: the module's own EvalArgs::wave_below (spec_install); -1: the detector's
 };
+
+// EvalArgs::wave_below of the launches of a module over the tiles of step `only_step` at `tile_y` window rows, given the
+// detector's value; -1 = the detector's value.
+int spec_wave_below(int detector_value, int only_step, int tile_y);
 
 // Device half: the code objects of spec_build as loaded modules, out[0] the one for all tiles or the STEP-2 tiles, out[1]
 // the STEP-1 module if any. `base_lds`: the LDS request of the ahead-of-time kernels. Owning thread only.

@@ -265,6 +265,7 @@ struct EvalLaunch {
   size_t lds;
   int n_tiles;
   const int4* tiles;
+  int wave_below = -1;  // >= 0: this launch's EvalArgs::wave_below; -1: the detector's
 };
 // The cascade-kernel launches of a pass over nf frames in `slot`, one after the other on `st`. stamps: null, or where the
 // blocks' phase stamps go (CCAMD_DEBUG_STAMPS), eval_stamp_slots() words per block, launch after launch.

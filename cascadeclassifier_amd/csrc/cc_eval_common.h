@@ -139,9 +139,29 @@ __host__ __device__ inline int tile_words_padded(int tile_words) { return (tile_
 // LDS bytes per block: integral tile(s) + partial sums + vnf (Haar only: LBP has no norm factor) + 2 queue tables of
 // u16[QUEUE_ROWS][32] + 3 x 32 class counters. tile_y: window rows per tile of the build in question (the run-time
 // specialised kernel may be compiled with another CC_TILE_Y than this translation unit).
-__host__ __device__ inline size_t eval_lds_bytes(int tile_words, bool tilted, bool haar = true, int tile_y = TILE_Y) {
+//
+// lean = the layout of the run-time specialised Haar module of STEP-1 tiles (CC_LEAN_LDS; no tilted tile), whose tall
+// tiles must not pay for side tables: integral tile + vnf [tile_y][TILE_X], every row rotated instead of padded (vnf_slot)
+// + the 2 queue tables + the counters. The tables grow towards each other from the two ends of their area -- row r of
+// table 0 is the area's r-th row of 32 entries, row r of table 1 its r-th row from the end -- and what the other layout
+// keeps in s_part lives in the part of that area that is dead at the time: the stump-split phase's partial sums in the gap
+// between the tables (lean_split_gap_bytes), the wave phases' window lists in the table that no longer receives windows.
+__host__ __device__ inline size_t eval_lds_bytes(int tile_words, bool tilted, bool haar = true, int tile_y = TILE_Y, bool lean = false) {
+  if (lean) return (size_t)tile_words_padded(tile_words) * 4 + tile_y * TILE_X * 4 + 2 * (tile_y * TILE_X) * 2 + 3 * 32 * 4;
   return (size_t)tile_words_padded(tile_words) * 4 * (tilted ? 2 : 1) + PART_DOUBLES * 8 + (haar ? tile_y * VNF_PITCH * 4 : 0) +
          2 * (tile_y * TILE_X) * 2 + 3 * 32 * 4;
+}
+// Lean layout: bytes between the two queue tables while neither holds more than `rows` rows. A group's windows keep their
+// bank class, so the table it fills never has more rows than the table it reads.
+__host__ __device__ inline int lean_split_gap_bytes(int tile_y, int rows) { return 2 * (tile_y * TILE_X) * 2 - 2 * rows * 32 * 2; }
+// Bytes of partial sums a stage cut into `ns` stump slices exchanges: slices 1 .. ns-1, one double per thread of a slice.
+__host__ __device__ inline int split_part_bytes(int ns) { return (ns - 1) * (EVAL_THREADS / ns) * 8; }
+// LDS of a CU (gfx950: 160 KiB) and the blocks of one kernel that fit it by their LDS request alone (a CU holds 32
+// wavefronts: 8 blocks of 256 threads).
+constexpr int CU_LDS_BYTES = 160 * 1024;
+__host__ __device__ inline int lds_blocks_per_cu(size_t lds_bytes) {
+  const int n = (int)((size_t)CU_LDS_BYTES / (lds_bytes ? lds_bytes : 1)), cap = 32 / EVAL_WAVES;
+  return n > cap ? cap : n;
 }
 
 // Sum of `v` over the 64 lanes, returned wave-uniform (in scalar registers). Cross-lane moves are DPP modifiers

@@ -384,9 +384,17 @@ struct EvalTile {
   const int W0 = A.W0, H0 = A.H0;
 #endif
   const Geom G{W0, H0};
-  double* const s_part = reinterpret_cast<double*>(lds + tile_words_padded(G.words()) * ((HAAR && A.tilt_chan >= 0) ? 2 : 1));
-  float* const s_vnf = reinterpret_cast<float*>(s_part + PART_DOUBLES);  // [TILE_Y][VNF_PITCH], see vnf_slot (Haar only)
-  unsigned short* const s_q = reinterpret_cast<unsigned short*>(s_vnf + (HAAR ? TILE_Y * VNF_PITCH : 0));  // 2 tables [QUEUE_ROWS][32 classes]
+  // lean LDS layout (eval_lds_bytes): the run-time specialised Haar module of STEP-1 tiles, compiled with CC_LEAN_LDS
+#ifdef CC_LEAN_LDS
+  static constexpr bool kLean = HAAR && !TREES && STEP == 1;
+#else
+  static constexpr bool kLean = false;
+#endif
+  // (lean: no s_part area, see split_parts / wave_lists)
+  double* const s_part = kLean ? nullptr : reinterpret_cast<double*>(lds + tile_words_padded(G.words()) * ((HAAR && A.tilt_chan >= 0) ? 2 : 1));
+  // [TILE_Y][VNF_PITCH], lean [TILE_Y][TILE_X], see vnf_slot (Haar only)
+  float* const s_vnf = kLean ? reinterpret_cast<float*>(lds + tile_words_padded(G.words())) : reinterpret_cast<float*>(s_part + PART_DOUBLES);
+  unsigned short* const s_q = reinterpret_cast<unsigned short*>(s_vnf + (HAAR ? TILE_Y * (kLean ? TILE_X : VNF_PITCH) : 0));  // 2 tables [QUEUE_ROWS][32 classes]
   int* const s_cnt = reinterpret_cast<int*>(s_q + 2 * TILE_WINDOWS);  // [stage % 3][class] = queued windows
   const int frame = blockIdx.y;
   const int32_t* const sum = A.integ + ((size_t)frame * A.nchan + 0) * A.int_frame_elems + S.int_ofs;
@@ -433,8 +441,46 @@ struct EvalTile {
   }
   // Bank class of a window: its tile base mod 32 (every corner read of a stage adds the same constant for all windows).
   __device__ __forceinline__ int win_class(int id) const { return ((id & 63) + skew * (id >> 6)) & 31; }
-  // s_vnf is laid out so that a window's entry sits on the bank of its class as well
-  __device__ __forceinline__ int vnf_slot(int id) const { return (id >> 6) * (TILE_X + skew) + (id & 63); }
+  // s_vnf is laid out so that a window's entry sits on the bank of its class as well (up to the area's own bank offset,
+  // the same for all windows): rows of pitch TILE_X + skew; lean layout: rows of pitch TILE_X, row r rotated by r * skew
+  // columns -- slot = 64 r + ((x + r skew) mod 64), whose bank is (x + r skew) mod 32 = win_class, and the rotation maps a
+  // row's 64 columns onto its 64 slots one to one.
+  __device__ __forceinline__ int vnf_slot(int id) const {
+    if constexpr (kLean)
+      return (id & ~63) | (((id & 63) + skew * (id >> 6)) & 63);
+    else
+      return (id >> 6) * (TILE_X + skew) + (id & 63);
+  }
+  // Index into s_q of entry (row, c) of the queue table of group g. Lean layout: table 1 runs backwards from the end of the
+  // area. queued: the entry itself, for a reader that holds `q` = where group g's table starts in the other layout.
+  __device__ __forceinline__ int q_index(int g, int row, int c) const {
+    if constexpr (kLean)
+      return (g & 1) ? (2 * QUEUE_ROWS - 1 - row) * 32 + c : row * 32 + c;
+    else
+      return (g & 1) * TILE_WINDOWS + row * 32 + c;
+  }
+  __device__ __forceinline__ int queued(const unsigned short* q, int g, int row, int c) const {
+    if constexpr (kLean)
+      return s_q[q_index(g, row, c)];
+    else
+      return q[row * 32 + c];
+  }
+  // Lean layout, stump-split phase: the partial sums sit behind row `rows` of table 0, in the gap between the two tables
+  // (neither holds more than `rows` rows in this group; the caller has checked lean_split_gap_bytes).
+  __device__ __forceinline__ double* split_parts(int rows) const {
+    if constexpr (kLean)
+      return reinterpret_cast<double*>(s_q + rows * 32);
+    else
+      return s_part;
+  }
+  // Wave phases: a list of 64 window ids per wavefront. Lean layout: in the far end of the table that group h.qg does not
+  // read -- a wave phase queues nothing, so that table is dead, and a table (TILE_WINDOWS >= 256 entries) holds the lists.
+  __device__ __forceinline__ unsigned short* wave_lists(int qg) const {
+    if constexpr (kLean)
+      return s_q + ((qg & 1) ? 0 : 2 * TILE_WINDOWS - EVAL_WAVES * 64);
+    else
+      return reinterpret_cast<unsigned short*>(s_part);
+  }
   // Appends the calling lanes with `pass` to the queue table of stage `st`: next free row of the window's class column.
   // The 32 lanes of a half-wavefront always hold windows of 32 different classes here (dense phase: 32 consecutive
   // columns of one row; thread phase: by construction of the table), so the atomics never meet on one counter.
@@ -444,11 +490,18 @@ struct EvalTile {
       int first = 0;
       if (lane == 0 && m) first = atomicAdd(&s_cnt[(g % 3) * 32], __builtin_popcountll(m));
       first = __builtin_amdgcn_readfirstlane(first);
-      if (pass) s_q[(g & 1) * TILE_WINDOWS + first + lane_rank(m)] = (unsigned short)id;
+      if constexpr (kLean) {
+        const int i = first + lane_rank(m);
+        if (pass) s_q[q_index(g, i >> 5, i & 31)] = (unsigned short)id;
+      } else if (pass)
+        s_q[(g & 1) * TILE_WINDOWS + first + lane_rank(m)] = (unsigned short)id;
     } else if (pass) {
       const int c = win_class(id);
       const int row = atomicAdd(&s_cnt[(g % 3) * 32 + c], 1);
-      s_q[(g & 1) * TILE_WINDOWS + row * 32 + c] = (unsigned short)id;
+      if constexpr (kLean)
+        s_q[q_index(g, row, c)] = (unsigned short)id;
+      else
+        s_q[(g & 1) * TILE_WINDOWS + row * 32 + c] = (unsigned short)id;
     }
   }
   // A window that passed the last stage of its group: a candidate when that was the cascade's last group, otherwise it
@@ -542,16 +595,17 @@ struct EvalTile {
   // Deals the queued windows of group h.qg to the wavefronts (both wave phases). Windows are numbered in table order (a
   // ballot per pair of rows) and dealt round-robin: wavefront w takes numbers w, w + EVAL_WAVES, ... and keeps its k-th
   // window's id in lane k. Every wavefront numbers the whole table itself and writes only its own share to a private list
-  // (s_part is free here: its last readers finished before the barrier at the top of this stage); the host keeps
-  // wave_below <= 64, so a share fits the 64 lanes.
+  // (wave_lists: s_part is free here, its last readers finished before the barrier at the top of this stage; lean layout:
+  // the other queue table, whose last readers finished before the same barrier); the host keeps wave_below <= 64, so a
+  // share fits the 64 lanes.
   __device__ __forceinline__ WaveShare deal_windows(const QueueState& h) const {
     const unsigned short* q = s_q + (h.qg & 1) * TILE_WINDOWS;
-    unsigned short* my_list = reinterpret_cast<unsigned short*>(s_part) + wave * 64;
+    unsigned short* my_list = wave_lists(h.qg) + wave * 64;
     int numbered = 0;
     for (int r0 = 0; r0 < h.rows; r0 += 2) {
       const int row = r0 + half;
       const bool valid = row < h.my_rows;
-      const int id = valid ? q[row * 32 + cls] : 0;
+      const int id = valid ? queued(q, h.qg, row, cls) : 0;
       const unsigned long long mask = __ballot(valid);
       const int number = numbered + lane_rank(mask);
       if (valid && number % EVAL_WAVES == wave) my_list[number / EVAL_WAVES] = (unsigned short)id;
@@ -776,6 +830,8 @@ struct EvalTile {
       int ns = 1;                          // stump slices of the split part
       if (rem > 0)
         while (ns * 2 * rem <= EVAL_WAVES) ns *= 2;  // largest power of two with ns * rem <= wavefronts
+      if constexpr (kLean)  // the partial sums travel between the queue tables (split_parts): as many slices as fit there
+        while (ns > 1 && split_part_bytes(ns) > lean_split_gap_bytes(TILE_Y, h.rows)) ns >>= 1;
       // each lane walks the group's stages with its window; no barrier and no re-queueing between them, a window that
       // fails records its exit and only stops counting
       const int g_end = ns == 1 ? groups : g_split;
@@ -783,7 +839,7 @@ struct EvalTile {
         const int row = g * 2 + half;
         const bool valid = row < h.my_rows;
         // a lane without a window evaluates the (in-tile) window `cls` of its own class, so it stays off the others' banks
-        const int id = valid ? q[row * 32 + cls] : cls;
+        const int id = valid ? queued(q, qg, row, cls) : cls;
         const int32_t* b = lds + window_base(id);
         const float vnf = HAAR ? s_vnf[vnf_slot(id)] : 1.f;
         bool alive = valid;
@@ -810,7 +866,7 @@ struct EvalTile {
     const int row = (g_split + grp) * 2 + half;
     const int i = grp * 64 + lane;
     const bool valid = row < h.my_rows;
-    const int id = valid ? q[min(row, QUEUE_ROWS - 1) * 32 + cls] : cls;  // (QUEUE_ROWS is not a power of two for every tile height)
+    const int id = valid ? queued(q, h.qg, min(row, QUEUE_ROWS - 1), cls) : cls;  // (QUEUE_ROWS is not a power of two for every tile height)
     double acc = 0.;
     if (grp < rem) {
       [[maybe_unused]] const int32_t* b = lds + window_base(id);
@@ -821,11 +877,11 @@ struct EvalTile {
       else
 #endif
         acc = table_sum(table_reader(id), first, nt, slice, ns, vnf);
-      if (slice) s_part[(slice - 1) * (EVAL_THREADS / ns) + i] = acc;  // <= (EVAL_WAVES - 1) * 64 entries for every ns
+      if (slice) split_parts(h.rows)[(slice - 1) * (EVAL_THREADS / ns) + i] = acc;  // <= (EVAL_WAVES - 1) * 64 entries for every ns
     }
     __syncthreads();  // partial sums visible
     if (grp < rem && slice == 0) {
-      for (int k = 1; k < ns; k++) acc += s_part[(k - 1) * (EVAL_THREADS / ns) + i];
+      for (int k = 1; k < ns; k++) acc += split_parts(h.rows)[(k - 1) * (EVAL_THREADS / ns) + i];
       const bool pass = valid && !(acc < (double)stage_thr[st]);
       if (dbg && valid && !pass) report(id, -st, acc);
       deliver(pass, id, acc, last_group, h.qg + 1);

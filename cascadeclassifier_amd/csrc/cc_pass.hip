@@ -148,7 +148,7 @@ static cc_status pass_launches(cc_detector* d, Plan* P, bool create_lists, EvalL
     const SpecModule& M = run_spec ? d->spec[i] : aot;
     const Plan::TileList* tl = nullptr;
     if (cc_status st = plan_tiles(d, P, M.tile_y, M.only_step, create_lists, &tl); st != CC_OK) return st;
-    out[i] = EvalLaunch{M.fn, M.lds, tl->n, tl->d.p};
+    out[i] = EvalLaunch{M.fn, M.lds, tl->n, tl->d.p, M.wave_below};
   }
   *n_out = n;
   return CC_OK;

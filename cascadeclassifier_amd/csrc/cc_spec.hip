@@ -635,17 +635,54 @@ static const char kSpecPrelude[] =
 //   block to fill their wavefronts with; at 26 KB per block six blocks fit a CU (6 wavefronts per SIMD: 80 VGPRs).
 //   Stock LBP cascade, ms per 32 Full-HD frames alone (round-4 run, script not kept): 8 rows 4.90, 12 rows 4.25, 16 rows 3.96, 20 rows 3.78,
 //   24 rows 3.85, 32 rows 4.12 (each at its best register budget).
-// * Haar kernels with 32-bit tiles: TWO modules, one per step -- 12 rows for the STEP-1 tiles, 8 for the STEP-2 tiles. A
-//   STEP-1 tile is a third of a STEP-2 tile (12.7 KB against 24 KB), but one launch requests the larger of the two for every
-//   block; in a launch of their own the STEP-1 tiles run at 6 blocks per CU. ms per 32 Full-HD frames alone, one run
-//   (round-4 run, script not kept): one module at 8 rows 8.35; two modules at 8 / 8 rows 7.82, 12 / 8 rows 7.32, 12 / 12 rows 7.49,
-//   16 / 12 rows 7.77, 12 / 16 rows 8.11 (STEP-1 / STEP-2; a 32-bit STEP-2 tile of 12 rows leaves 4 blocks per CU).
+// * Haar kernels with 32-bit tiles: TWO modules, one per step -- 20 rows for the STEP-1 tiles, 8 for the STEP-2 tiles. A
+//   STEP-1 tile is a third of a STEP-2 tile (12.7 KB against 24 KB at 12 rows), but one launch requests the larger of the two
+//   for every block. ms per 32 Full-HD frames alone, one run (round-4 run, script not kept): one module at 8 rows 8.35; two
+//   modules at 8 / 8 rows 7.82, 12 / 8 rows 7.32, 12 / 12 rows 7.49, 16 / 12 rows 7.77, 12 / 16 rows 8.11 (STEP-1 / STEP-2; a
+//   32-bit STEP-2 tile of 12 rows leaves 4 blocks per CU). The STEP-1 module has the lean LDS layout (eval_lds_bytes), a
+//   register budget for the blocks its own request allows, and a wave_below of its own (spec_wave_below); for a 24x24 window
+//   12 / 16 / 20 / 24 rows are 19.2 / 22.7 / 26.1 / 29.6 KB per block = 8 / 7 / 6 / 5 blocks per CU, and its launch takes
+//   2.61 / 2.97 / 2.45 / 2.77 ms per 32 frames (2.78 / 2.99 / 2.65 / 3.09 with the padded layout at 7 / 6 / 5 / 4 blocks;
+//   profiles/EXPERIMENTS.md 3.22). Larger windows: spec_step1_rows.
 // * everything else (Haar with 16-bit tiles): one module at the library's 8 rows.
 // CCAMD_SPEC_TILE_Y sets every module's rows, CCAMD_SPEC_TILE_Y1 / _Y2 the STEP-1 / STEP-2 module's, CCAMD_SPEC_ONE_MODULE=1
 // forces a single module (tuning).
 struct SpecModulePlan {
   int only_step, tile_y;
 };
+// The Haar module of STEP-1 tiles takes the lean LDS layout (eval_lds_bytes; compiled with CC_LEAN_LDS): it is the one
+// module whose tiles grow tall. (Tilted cascades never get a module per step.)
+static bool spec_lean_lds(const Cascade& m, int tmode, int only_step) {
+  return only_step == 1 && tmode == TILE_32 && m.feature_type == CC_FEATURE_HAAR && !m.has_tilted;
+}
+// LDS request of one block of the STEP-1 Haar module at `tile_y` window rows.
+static size_t spec_step1_lds(const Cascade& m, int tile_y) {
+  return eval_lds_bytes(TileGeom<1>(m.win_w, m.win_h, tile_y).words(), false, true, tile_y, true);
+}
+// Window rows of the STEP-1 Haar module's tiles: `want`, or for windows whose tile is too large for that, the tallest
+// height below it (a multiple of the block's wavefronts) that still lets kSpecStep1MinBlocks blocks share a CU -- below that
+// the late stages of one block are no longer hidden by the others. Never less than the library's TILE_Y: a window that large
+// (128x40, 96x96) fits fewer blocks at any height.
+constexpr int kSpecStep1Rows = 20;
+constexpr int kSpecStep1MinBlocks = 4;
+static int spec_step1_rows(const Cascade& m, int want) {
+  int ty = want;
+  while (ty - EVAL_WAVES >= TILE_Y && lds_blocks_per_cu(spec_step1_lds(m, ty)) < kSpecStep1MinBlocks) ty -= EVAL_WAVES;
+  return ty;
+}
+// EvalArgs::wave_below of one module. The detector's value (configure_detector: 24) was tuned on tiles of 8 window rows. The
+// module of STEP-1 tiles pools 768 and more windows per block, and its blocks reach the wave phase with more windows each:
+// kStep1WaveBelow for tiles of 12 rows and more (measured at 12 and 20 rows: 16 +4.9 / +3.2 %, 24 0, 32 -1.2 / -1.8 %, 40 and
+// 56 at 20 rows -0.4 / -0.5 %; profiles/EXPERIMENTS.md 3.22). -1 = the detector's value: every other module, a wave phase
+// that is off, and under CCAMD_WAVE_BELOW (which then holds for all modules). CCAMD_WAVE_BELOW1: the STEP-1 module's value (tuning).
+constexpr int kStep1WaveBelow = 32;
+int spec_wave_below(int detector_value, int only_step, int tile_y) {
+  if (only_step != 1 || detector_value <= 0) return -1;
+  if (const char* e = std::getenv("CCAMD_WAVE_BELOW1")) return std::max(0, std::min(64, std::atoi(e)));
+  if (std::getenv("CCAMD_WAVE_BELOW") || tile_y < 12) return -1;
+  return std::max(detector_value, kStep1WaveBelow);
+}
+
 static std::vector<SpecModulePlan> spec_modules(const Cascade& m, int tmode) {
   auto valid = [&](int ty) { return ty >= EVAL_WAVES && ty <= 32 && ty % EVAL_WAVES == 0; };
   auto env_rows = [&](const char* name, int dflt) {
@@ -662,10 +699,12 @@ static std::vector<SpecModulePlan> spec_modules(const Cascade& m, int tmode) {
   const int all = env_rows("CCAMD_SPEC_TILE_Y", lbp16 ? 20 : TILE_Y);
   const bool two = (haar32 || std::getenv("CCAMD_SPEC_TWO_MODULES")) && !std::getenv("CCAMD_SPEC_ONE_MODULE");
   if (!two) return {{0, all}};
-  return {{2, env_rows("CCAMD_SPEC_TILE_Y2", all)}, {1, env_rows("CCAMD_SPEC_TILE_Y1", (haar32 && !rows_given) ? 12 : all)}};
+  return {{2, env_rows("CCAMD_SPEC_TILE_Y2", all)}, {1, env_rows("CCAMD_SPEC_TILE_Y1", (haar32 && !rows_given) ? spec_step1_rows(m, kSpecStep1Rows) : all)}};
 }
 
-static cc_status compile_specialised(const std::string& src, const std::string& arch, int n_stages, bool lbp, int tmode, int tile_y, int only_step, int win_w, int win_h, std::vector<char>& code) {
+// lean_blocks: 0, or this is the module with the lean LDS layout and its LDS request lets that many blocks share a CU.
+static cc_status compile_specialised(const std::string& src, const std::string& arch, int n_stages, bool lbp, int tmode, int tile_y, int only_step, int win_w, int win_h,
+                                     int lean_blocks, std::vector<char>& code) {
   const bool tile16 = tmode == TILE_16;
   static std::mutex mu;
   static std::map<std::string, std::vector<char>> cache;
@@ -674,13 +713,20 @@ static cc_status compile_specialised(const std::string& src, const std::string& 
   // same code generation rules as the ahead-of-time build (Makefile): no FMA contraction, no fast-math
   // register budget = the occupancy the LDS footprint allows: 5 blocks per CU with the 32-bit tile, 7-8 with the 16-bit one
   // (16-bit tiles of >= 20 rows: 26 KB per block = 6 blocks per CU)
-  const std::string o_w = "-DCC_EVAL_MIN_WAVES_PER_EU=" + std::to_string(tile16 ? (tile_y >= 20 ? 6 : 7) : CC_EVAL_MIN_WAVES_PER_EU);
+  // (lean module: what its own request allows, a block being one wavefront per SIMD; CCAMD_SPEC_WAVES1 overrides, tuning)
+  int min_waves = tile16 ? (tile_y >= 20 ? 6 : 7) : CC_EVAL_MIN_WAVES_PER_EU;
+  if (lean_blocks > 0) {
+    min_waves = std::max(1, std::min(8, lean_blocks * EVAL_WAVES / 4));
+    if (const char* e = std::getenv("CCAMD_SPEC_WAVES1")) min_waves = std::max(1, std::min(8, std::atoi(e)));
+  }
+  const std::string o_w = "-DCC_EVAL_MIN_WAVES_PER_EU=" + std::to_string(min_waves);
   const std::string o_step = "-DCC_ONLY_STEP=" + std::to_string(only_step);
   const std::string o_w0 = "-DCC_SPEC_W0=" + std::to_string(win_w), o_h0 = "-DCC_SPEC_H0=" + std::to_string(win_h);  // tile geometry folds to constants
   std::vector<const char*> optv = {o_arch.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", o_k.c_str(), o_ty.c_str(), o_th.c_str(), o_w.c_str(), o_w0.c_str(), o_h0.c_str()};
   if (only_step) optv.push_back(o_step.c_str());
   if (lbp) optv.push_back("-DCC_SPEC_LBP");
   if (tile16) optv.push_back("-DCC_SPEC_TILE16");
+  if (lean_blocks > 0) optv.push_back("-DCC_LEAN_LDS");
   const char* const* opts = optv.data();
   const int n_opts = (int)optv.size();
   std::string key;  // everything the code object depends on: compiler version, options, then the source
@@ -828,7 +874,8 @@ cc_status spec_build(const Cascade& m, int n_stages, const std::string& arch, st
     SpecCode c;
     c.only_step = mp.only_step;
     c.tile_y = mp.tile_y;
-    const cc_status st = compile_specialised(src, arch, k, m.feature_type == CC_FEATURE_LBP, tmode, mp.tile_y, mp.only_step, m.win_w, m.win_h, c.code);
+    const int lean_blocks = spec_lean_lds(m, tmode, mp.only_step) ? std::max(1, lds_blocks_per_cu(spec_step1_lds(m, mp.tile_y))) : 0;
+    const cc_status st = compile_specialised(src, arch, k, m.feature_type == CC_FEATURE_LBP, tmode, mp.tile_y, mp.only_step, m.win_w, m.win_h, lean_blocks, c.code);
     if (st != CC_OK) return st;
     codes.push_back(std::move(c));
   }
@@ -862,7 +909,7 @@ cc_status spec_load(const Cascade& m, const std::vector<SpecCode>& codes, int tm
       const TileGeom<1> G1(m.win_w, m.win_h, ty);
       const TileGeom<2> G2(m.win_w, m.win_h, ty);
       const int words = step == 1 ? G1.words() : step == 2 ? G2.words() : std::max(G1.words(), G2.words());
-      x.lds = eval_lds_bytes(words, m.has_tilted, haar_k, ty);
+      x.lds = spec_lean_lds(m, tmode, step) ? spec_step1_lds(m, ty) : eval_lds_bytes(words, m.has_tilted, haar_k, ty);
     } else if (tmode == TILE_16) {  // STEP-1 tile in 32 bits, STEP-2 tile in 16 bits
       const TileGeom<1> G1(m.win_w, m.win_h, ty);
       const TileGeom16 G2(m.win_w, m.win_h, ty);
@@ -894,6 +941,25 @@ cc_status spec_load(const Cascade& m, const std::vector<SpecCode>& codes, int tm
 using namespace ccamd;
 
 extern "C" {
+
+cc_status cc_debug_spec_step1_plan(const cc_cascade* c, int rows_wanted, int wave_below_detector, int* rows, size_t* lds_bytes, int* blocks_per_cu,
+                                   int* wave_below) {
+  if (!c) return set_error(CC_ERR_INVALID_ARG, "cc_debug_spec_step1_plan: null cascade");
+  if (cc_status hs = refuse_hog(c->m, "cc_debug_spec_step1_plan"); hs != CC_OK) return hs;
+  if (c->m.max_nodes_per_tree > 1 || !spec_lean_lds(c->m, TILE_32, 1))
+    return set_error(CC_ERR_UNSUPPORTED, "cc_debug_spec_step1_plan: upright Haar stump cascades only");
+  const int ty = rows_wanted > 0 ? rows_wanted : spec_step1_rows(c->m, kSpecStep1Rows);
+  if (ty < EVAL_WAVES || ty > 32 || ty % EVAL_WAVES) return set_error(CC_ERR_INVALID_ARG, "cc_debug_spec_step1_plan: %d window rows per tile", ty);
+  const size_t lds = spec_step1_lds(c->m, ty);
+  if (rows) *rows = ty;
+  if (lds_bytes) *lds_bytes = lds;
+  if (blocks_per_cu) *blocks_per_cu = lds_blocks_per_cu(lds);
+  if (wave_below) {
+    const int w = spec_wave_below(wave_below_detector, 1, ty);
+    *wave_below = w >= 0 ? w : wave_below_detector;
+  }
+  return CC_OK;
+}
 
 cc_status cc_cascade_compile_specialized(const cc_cascade* c, int n_stages, const char* arch, size_t* code_bytes) {
   if (!c || !arch || !code_bytes) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_compile_specialized: null argument");

@@ -383,6 +383,16 @@ CC_API cc_status cc_debug_vnf_check(int device, uint64_t n_values, uint64_t seed
  * their stage's quantum. Entries of stages without the form are 0. q / thr_q hold n_stages entries, left_q / right_q n_weak;
  * any may be NULL. */
 CC_API cc_status cc_debug_wave_int_tables(const cc_cascade* c, double* q, int32_t* thr_q, int32_t* left_q, int32_t* right_q);
+/* Host only, no device: what the run-time specialised kernel's module of STEP-1 tiles would be built with for the Haar stump
+ * cascade `c` (32-bit tiles, a module per step). rows_wanted > 0: tiles of that many window rows, as CCAMD_SPEC_TILE_Y1
+ * would ask for; <= 0: the library's choice, i.e. its default height or, for a window too large for that, the tallest
+ * height below it at which four blocks still share a CU (8 rows where none does). Out: *rows = window rows per tile, *lds_bytes = the dynamic LDS
+ * request of one block (eval_lds_bytes, lean layout), *blocks_per_cu = blocks that request lets share the 160 KiB of a CU
+ * (at most 8) = the wavefronts per SIMD the module's register budget is compiled for, *wave_below = EvalArgs::wave_below of the
+ * module's launches given the detector-wide value `wave_below_detector` (24 for such a cascade). Any may be NULL.
+ * CC_ERR_UNSUPPORTED for cascades that do not get such a module (LBP, HOG, trees, tilted features). */
+CC_API cc_status cc_debug_spec_step1_plan(const cc_cascade* c, int rows_wanted, int wave_below_detector, int* rows, size_t* lds_bytes,
+                                          int* blocks_per_cu, int* wave_below);
 /* Host-side (tiny, serial in the reference too): cv::groupRectangles(rects, group_threshold, eps). */
 CC_API cc_status cc_group_rectangles(const cc_rect* rects, int n, int group_threshold, double eps, cc_rect* out, int cap,
                                      int* n_out);
