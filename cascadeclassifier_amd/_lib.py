@@ -195,6 +195,7 @@ SIGNATURES = {
     "cc_eval_hog_feature_geometry": (_i, [_vp, _i, _vp]),
     "cc_eval_get_hog_sample": (_i, [_vp, _i, _vp, _vp]),
     "cc_debug_hog_bins": (_i, [_i, C.POINTER(C.c_int32), _vp, _vp]),
+    "cc_debug_hog_lds": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "cc_eval_predict_cascade": (_i, [_vp, _vp, _vp, _i, _vp]),
     "cc_eval_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
     "cc_debug_eval_tile_samples": (_i, [_vp]),

@@ -199,7 +199,8 @@ struct cc_evaluator {
   // variables (blocks * 36). mirror_hog is the host mirror of the last window, read and written under mu.
   std::vector<int32_t> hog_blocks;
   ccamd::DevBuf<int32_t> d_hog_blocks;
-  int hog_planes_per_pass = 0;
+  int hog_planes_per_pass = 0;  // k_hog_set_images' plan (hog_lds_plan, cc_hog_device.h), fixed by hog_init:
+  size_t hog_set_lds = 0;       // planes per LDS pass and the dynamic LDS per workgroup that goes with them
   std::vector<float> mirror_hog;
   // ---- fill (cc_fill.hip) ----
   // cc_eval_fill_passed sets a chunk of candidates into these scratch rows, predicts them there and copies the kept rows

@@ -167,23 +167,17 @@ __global__ void k_hog_bins(uint8_t* __restrict__ bin, float* __restrict__ mag) {
 // Host side
 // ------------------------------------------------------------------------------------------------
 // hog_catalog: cc_host.cpp, beside the Haar and LBP catalogs (cc_cascade_from_stumps needs it without a device).
-static size_t hog_set_lds(int W, int H, int P) { return (size_t)W * H * 4 + (size_t)P * H * (W + 1) * 4 + (size_t)W * H; }
+static LdsOptIn g_set_images_lds;  // k_hog_set_images' opt-in, shared by every HOG evaluator
 
 cc_status hog_init(cc_evaluator* e) {
   hog_catalog(e->W, e->H, e->hog_blocks);
   e->nfeat = (int)(e->hog_blocks.size() / 4) * 36;  // the trainer's variable space (o_cvcascadeboosttraindata.cpp:246-247)
-  // planes per LDS pass: all ten within 64 KB where they fit, else as many as 160 KB (one block per CU) holds
-  for (size_t budget : {(size_t)64 * 1024, (size_t)160 * 1024}) {
-    int P = 10;
-    while (P > 0 && hog_set_lds(e->W, e->H, P) > budget) P--;
-    e->hog_planes_per_pass = P;
-    if (P > 0) break;
-  }
+  const HogLdsPlan plan = hog_lds_plan(e->W, e->H);
+  e->hog_planes_per_pass = plan.planes_per_pass;
+  e->hog_set_lds = plan.set_bytes;
   if (e->hog_planes_per_pass == 0)
     return set_error(CC_ERR_UNSUPPORTED, "cc_eval_create: HOG window %dx%d too large for the setImage kernel's LDS", e->W, e->H);
-  const size_t lds = hog_set_lds(e->W, e->H, e->hog_planes_per_pass);
-  if (lds > 64 * 1024)
-    CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hog_set_images), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  CC_HIP(g_set_images_lds.raise(reinterpret_cast<const void*>(&k_hog_set_images), e->device, plan.set_bytes));
   CC_HIP(e->samples.hog.ensure((size_t)e->max_samples * e->cols * 10));
   CC_HIP(hipMemsetAsync(e->samples.hog.p, 0, (size_t)e->max_samples * e->cols * 10 * 4, e->stream.s));
   CC_HIP(e->d_hog_blocks.ensure(std::max<size_t>(e->hog_blocks.size(), 4)));
@@ -193,8 +187,7 @@ cc_status hog_init(cc_evaluator* e) {
 }
 
 cc_status hog_launch_set_images(cc_evaluator* e, const SampleTables& t, const uint8_t* d_imgs, int n, int first_idx) {
-  const size_t lds = hog_set_lds(e->W, e->H, e->hog_planes_per_pass);
-  hipLaunchKernelGGL(k_hog_set_images, dim3(n), dim3(HOG_SET_THREADS), lds, e->stream.s, d_imgs, e->W, e->H, first_idx,
+  hipLaunchKernelGGL(k_hog_set_images, dim3(n), dim3(HOG_SET_THREADS), e->hog_set_lds, e->stream.s, d_imgs, e->W, e->H, first_idx,
                      e->hog_planes_per_pass, t.hog.p);
   CC_HIP(hipGetLastError());
   return CC_OK;
@@ -332,6 +325,16 @@ cc_status cc_eval_get_hog_sample(cc_evaluator* e, int idx, float* hist, float* n
       for (int b = 0; b < 9; b++) hist[(size_t)b * e->cols + p] = v[(size_t)p * 10 + b];
     if (norm) norm[p] = v[(size_t)p * 10 + 9];
   }
+  return CC_OK;
+}
+
+cc_status cc_debug_hog_lds(int win_w, int win_h, int* planes_per_pass, int* set_budget_kib, int64_t* set_bytes, int64_t* mine_bytes) {
+  if (win_w < 1 || win_h < 1 || win_w > 4096 || win_h > 4096) return set_error(CC_ERR_INVALID_ARG, "cc_debug_hog_lds: window %dx%d", win_w, win_h);
+  const HogLdsPlan p = hog_lds_plan(win_w, win_h);
+  if (planes_per_pass) *planes_per_pass = p.planes_per_pass;
+  if (set_budget_kib) *set_budget_kib = p.set_budget_kib;
+  if (set_bytes) *set_bytes = (int64_t)p.set_bytes;
+  if (mine_bytes) *mine_bytes = (int64_t)p.mine_bytes;
   return CC_OK;
 }
 

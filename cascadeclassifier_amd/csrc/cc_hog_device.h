@@ -5,10 +5,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <mutex>
 
 namespace ccamd {
 
@@ -62,6 +64,58 @@ __host__ __device__ inline float hog_var_value(const float* planes, int sw, cons
   const float nf = ((at(x, y, 9) - at(x + 2 * cw, y, 9)) - at(x, y + 2 * ch, 9)) + at(x + 2 * cw, y + 2 * ch, 9);
   return hog_value_from(res, nf);
 }
+
+// ------------------------------------------------------------------------------------------------
+// LDS of the two kernels that build a window's planes (host). A workgroup gets kHogLdsDefault bytes of dynamic LDS without
+// asking and at most kHogLdsMax (the LDS of one CU of gfx950) after the kernel has opted in.
+// ------------------------------------------------------------------------------------------------
+constexpr size_t kHogLdsDefault = 64 * 1024, kHogLdsMax = 160 * 1024;
+
+struct HogLdsPlan {
+  int planes_per_pass;  // k_hog_set_images: planes that go through LDS together; 0: the window is refused
+  int set_budget_kib;   // the budget that count was chosen under: 64 or 160
+  size_t set_bytes;     // k_hog_set_images' dynamic LDS with that count (of one plane per pass where the window is refused)
+  size_t mine_bytes;    // k_negmine_hog's dynamic LDS; cc_negminer_create refuses more than kHogLdsMax
+};
+
+// k_hog_set_images: magnitudes [H][W] float, the row sums of P planes [P][H][W + 1] float, bins [H][W] bytes.
+// k_negmine_hog: planes [10][H + 1][W + 1] float, magnitudes [H][W] float, bins [H][W] bytes.
+// Planes per setImage pass: all ten within 64 KB where they fit, else as many as fit there (no opt-in, several workgroups
+// per CU), else as many as 160 KB (one workgroup per CU) holds.
+inline HogLdsPlan hog_lds_plan(int W, int H) {
+  auto set_lds = [&](int P) { return (size_t)W * H * 4 + (size_t)P * H * (W + 1) * 4 + (size_t)W * H; };
+  HogLdsPlan p{0, 0, 0, (size_t)10 * (W + 1) * (H + 1) * 4 + (size_t)W * H * 5};
+  for (size_t budget : {kHogLdsDefault, kHogLdsMax}) {
+    int P = 10;
+    while (P > 0 && set_lds(P) > budget) P--;
+    p.planes_per_pass = P;
+    p.set_budget_kib = (int)(budget / 1024);
+    if (P > 0) break;
+  }
+  p.set_bytes = set_lds(std::max(p.planes_per_pass, 1));
+  return p;
+}
+
+// A kernel's opt-in to more than kHogLdsDefault bytes of dynamic LDS is an attribute of the kernel on a device, shared by
+// every object that launches it. It is only ever raised: an object created later with a smaller window must not take away
+// what an earlier one launches with. One instance per kernel; `device` is the calling thread's current device.
+class LdsOptIn {
+ public:
+  hipError_t raise(const void* kernel, int device, size_t bytes) {
+    if (bytes <= kHogLdsDefault) return hipSuccess;
+    std::lock_guard<std::mutex> lk(mu_);
+    const bool known = device >= 0 && device < kDevices;
+    if (known && set_[device] >= bytes) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && known) set_[device] = bytes;
+    return e;
+  }
+
+ private:
+  static constexpr int kDevices = 64;
+  std::mutex mu_;
+  size_t set_[kDevices] = {};
+};
 
 // ------------------------------------------------------------------------------------------------
 // setImage of one window by a workgroup (HOGfeatures.cpp:163-256). The caller places __syncthreads between the steps.

@@ -205,7 +205,7 @@ __device__ __forceinline__ float hog_mine_value(const float* P, const HogMineNod
   return hog_value_from(res, nf);
 }
 
-// LDS: planes [10][H0 + 1][W0 + 1] float, magnitudes [H0][W0] float, bins [H0][W0] bytes (hog_mine_lds_bytes)
+// LDS: planes [10][H0 + 1][W0 + 1] float, magnitudes [H0][W0] float, bins [H0][W0] bytes (hog_lds_plan, cc_hog_device.h)
 __global__ __launch_bounds__(HOG_MINE_THREADS) void k_negmine_hog(HogMineArgs A) {
   extern __shared__ float hog_lds[];
   const long long i = blockIdx.x;
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(HOG_MINE_THREADS) void k_negmine_hog(HogMineArgs A)
   if (lane == 0) A.pass[(size_t)blockIdx.y * A.n_windows + i] = pass;
 }
 
-static size_t hog_mine_lds_bytes(int W, int H) { return (size_t)10 * (W + 1) * (H + 1) * 4 + (size_t)W * H * 5; }
+static LdsOptIn g_negmine_hog_lds;  // k_negmine_hog's opt-in, shared by every HOG miner
 
 }  // namespace ccamd
 
@@ -357,12 +357,11 @@ cc_status cc_negminer_create(const cc_cascade* c, int device, cc_negminer** out)
   if (!haar && !hog && M.feature_type != CC_FEATURE_LBP)
     return set_error(CC_ERR_UNSUPPORTED, "cc_negminer_create: feature type %d", M.feature_type);
   if (hog) {
-    m->hog_lds = hog_mine_lds_bytes(M.win_w, M.win_h);
-    if (m->hog_lds > 160 * 1024)
-      return set_error(CC_ERR_UNSUPPORTED, "cc_negminer_create: HOG window %dx%d needs %zu bytes of LDS per window (limit %d)", M.win_w,
-                       M.win_h, m->hog_lds, 160 * 1024);
-    if (m->hog_lds > 64 * 1024)
-      CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_negmine_hog), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->hog_lds));
+    m->hog_lds = hog_lds_plan(M.win_w, M.win_h).mine_bytes;
+    if (m->hog_lds > kHogLdsMax)
+      return set_error(CC_ERR_UNSUPPORTED, "cc_negminer_create: HOG window %dx%d needs %zu bytes of LDS per window (limit %zu)", M.win_w,
+                       M.win_h, m->hog_lds, kHogLdsMax);
+    CC_HIP(g_negmine_hog_lds.raise(reinterpret_cast<const void*>(&k_negmine_hog), device, m->hog_lds));
     const int sw = M.win_w + 1, plane = sw * (M.win_h + 1);
     std::vector<HogMineNode> hn(M.node_feature.size());
     for (size_t i = 0; i < hn.size(); i++) {

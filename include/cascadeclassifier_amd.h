@@ -524,6 +524,12 @@ CC_API cc_status cc_eval_get_hog_sample(cc_evaluator* e, int idx, float* hist, f
  * device with the setImage kernel's per-pixel function; pair (dx, dy) at (dy + 255) * 511 + dx + 255. bin holds 261 121
  * bytes, mag 261 121 floats; *n receives 261 121. */
 CC_API cc_status cc_debug_hog_bins(int device, int32_t* n, uint8_t* bin, float* mag);
+/* Host only, no device: the LDS plan of a HOG window. *planes_per_pass: how many of the ten integral planes the setImage kernel
+ * takes through LDS together, 0 where cc_eval_create refuses the window; *set_budget_kib: the budget that count was chosen
+ * under, 64 (no opt-in) or 160; *set_bytes: the setImage kernel's dynamic LDS per workgroup with that count (with one plane per
+ * pass where the window is refused); *mine_bytes: the negative miner's dynamic LDS per window, which cc_negminer_create
+ * compares with 160 KiB. Any output may be NULL. */
+CC_API cc_status cc_debug_hog_lds(int win_w, int win_h, int* planes_per_pass, int* set_budget_kib, int64_t* set_bytes, int64_t* mine_bytes);
 /* Training-side cascade predict (CvCascadeClassifier::predict, cascadeclassifier.cpp:297-306 ->
  * boost.cpp:461-477 -> o_cvcascadeboosttree.cpp:16-39) of a stump cascade over stored samples:
  * out[s] = 1 if every stage passes else 0. Feature indices of `c` index the cascade's own <features> list. The cascade's

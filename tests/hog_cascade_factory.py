@@ -81,12 +81,38 @@ def stage_sums(weaks, vals):
     return acc
 
 
-def stage_walk(model, vals):
+def wave_stage_sums(weaks, vals):
+    """Stage sum per sample in the order of a 64-lane wavefront that shares a stage's STUMPS (walk_stages_wave,
+    cc_train_device.h, and wave_sum_f64, cc_eval_common.h): lane l adds the votes of stumps l, l + 64, ... in that order;
+    then every lane adds its neighbour's value in turn by quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror and
+    row_mirror (each lane then holds the total of its row of 16), lane 15 of a row is added into the next row for rows 1
+    and 3, lane 31 into rows 2 and 3, and lane 63 holds the result. Every addition is an IEEE double addition."""
+    n = vals.shape[1]
+    v = np.zeros((64, n), np.float64)
+    for t, (nodes, leaves) in enumerate(weaks):
+        assert len(nodes) == 1, "stumps only"
+        v[t % 64] = v[t % 64] + _tree_leaves(nodes, leaves, vals)
+    lane = np.arange(64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for src in (lane ^ 1, lane ^ 2, (lane & ~7) | (7 - (lane & 7)), (lane & ~15) | (15 - (lane & 15))):
+            v = v + v[src]
+        add = np.zeros_like(v)
+        add[16:32], add[48:64] = v[15], v[47]  # row_bcast15, rows 1 and 3
+        v = v + add
+        add = np.zeros_like(v)
+        add[32:64] = v[31]                     # row_bcast31, rows 2 and 3
+        v = v + add
+    return v[63]
+
+
+def stage_walk(model, vals, sums=stage_sums):
     """CvCascadeClassifier::predict of every sample: vals [n_features][n] from feature_values; model from parsed_model
-    (float32 values, stage threshold (float)t - 1e-5f). A stage fails iff its sum < threshold. Returns uint8 flags."""
+    (float32 values, stage threshold (float)t - 1e-5f). A stage fails iff its sum < threshold. Returns uint8 flags.
+    `sums` is the order the stage sum is formed in: tree order, as the reference does, unless a test asks what another
+    order would give."""
     alive = np.ones(vals.shape[1], bool)
     for thr, weaks in model["stages"]:
-        alive &= ~(stage_sums(weaks, vals) < float(thr))
+        alive &= ~(sums(weaks, vals) < float(thr))
     return alive.astype(np.uint8)
 
 
@@ -147,3 +173,89 @@ def hog_cascade(windows, seed=5, stage_sizes=(3, 5, 8), depth=1, pass_share=0.7)
         stages.append((thr, weaks))
         alive &= sums >= float(f32(thr - f32(1e-5)))
     return hog_xml(feats, stages, W, H), feats, stages
+
+
+def stage_passes(model, vals):
+    """Per stage, the samples that pass it given that they entered it: list of (entered, passed) boolean arrays."""
+    alive = np.ones(vals.shape[1], bool)
+    out = []
+    for thr, weaks in model["stages"]:
+        ok = ~(stage_sums(weaks, vals) < float(thr))
+        out.append((alive.copy(), alive & ok))
+        alive = alive & ok
+    return out
+
+
+def order_independent(stages, headroom=1.0):
+    """stage_sums_order_independent (cc_host.cpp) restated for a stump cascade: every leaf of a stage is a multiple of
+    q = 2^(emin - 24), emin the smallest binary exponent (frexp) among the stage's nonzero leaves; if the sum of the
+    stumps' larger magnitudes stays below 2^53 q, every partial sum in any order is an exact double."""
+    for _, weaks in parsed_model(stages)["stages"]:
+        emin, mag = None, 0.0
+        for nodes, leaves in weaks:
+            assert len(nodes) == 1 and len(leaves) == 2, "stumps only"
+            l, r = (float(v) for v in leaves)
+            if not (np.isfinite(l) and np.isfinite(r)):
+                return False
+            mag += max(abs(l), abs(r))
+            for v in (l, r):
+                if v != 0.0:
+                    e = int(np.frexp(v)[1])
+                    emin = e if emin is None else min(emin, e)
+        if emin is None:
+            continue
+        if mag * headroom / float(np.ldexp(1.0, emin - 24)) >= 9007199254740992.0:
+            return False
+    return True
+
+
+def stump_cascade(windows, stage_leaves, seed=5, pass_share=0.7):
+    """A stump cascade over `windows` (n, H, W) with given leaves: stage_leaves is a list of stages, each a list of
+    (left, right) per stump. Blocks and components are random catalog picks, node thresholds quantiles of the values on the
+    windows, stage thresholds the (1 - pass_share) quantile of the sequential double sums of the windows alive before the
+    stage. Returns (xml, feats, stages)."""
+    windows = np.asarray(windows, np.uint8)
+    H, W = windows.shape[1:]
+    rng = np.random.default_rng(seed)
+    feats = _pick_features(W, H, sum(len(s) for s in stage_leaves), rng)
+    hist, norm = hog.set_images(windows)
+    v = feature_values(feats, hist, norm)
+    stages, k = [], 0
+    alive = np.ones(windows.shape[0], bool)
+    for leaves in stage_leaves:
+        weaks = []
+        for l, r in leaves:
+            nz = v[k][v[k] > 0]
+            t = f32(np.quantile(nz, rng.uniform(0.3, 0.7))) if len(nz) else f32(0.5)
+            weaks.append(([(0, -1, k, t)], [f32(l), f32(r)]))
+            k += 1
+        sums = stage_sums(parsed_model([(0, weaks)])["stages"][0][1], v)
+        base = sums[alive] if alive.sum() > 20 else sums
+        thr = f32(np.quantile(base, 1 - pass_share))
+        stages.append((thr, weaks))
+        alive &= sums >= float(f32(thr - f32(1e-5)))
+    return hog_xml(feats, stages, W, H), feats, stages
+
+
+def parse_hog_xml(text):
+    """The layout hog_xml writes, read back without the library: (W, H, feats (n, 5) int32, stages) with stages a list of
+    (threshold, [(nodes, leaves)]), nodes = [(left, right, feature_idx, threshold)], every real as the float32 its text
+    rounds to."""
+    import xml.etree.ElementTree as ET
+    casc = ET.fromstring(text).find("cascade")
+    assert casc.find("featureType").text == "HOG" and casc.find("stageType").text == "BOOST"
+    W, H = int(casc.find("width").text), int(casc.find("height").text)
+    stages = []
+    for st in casc.find("stages"):
+        weaks = []
+        for wk in st.find("weakClassifiers"):
+            n = wk.find("internalNodes").text.split()
+            assert len(n) % 4 == 0
+            nodes = [(int(n[i]), int(n[i + 1]), int(n[i + 2]), f32(float(n[i + 3]))) for i in range(0, len(n), 4)]
+            leaves = [f32(float(t)) for t in wk.find("leafValues").text.split()]
+            weaks.append((nodes, leaves))
+        assert int(st.find("maxWeakCount").text) == len(weaks)
+        stages.append((f32(float(st.find("stageThreshold").text)), weaks))
+    assert int(casc.find("stageNum").text) == len(stages)
+    feats = np.array([[int(t) for t in f.find("rect").text.split()] for f in casc.find("features")], np.int32).reshape(-1, 5)
+    return W, H, feats, stages

@@ -9,6 +9,7 @@ import cascadeclassifier_amd as cc
 from cascadeclassifier_amd import _lib as L
 from cascadeclassifier_amd import evaluator as ev
 from oracle import oracle as orc
+from tests import hog_lds_cases as lds
 from tests import hog_restatement as hog
 from tests.util import read_vec
 
@@ -98,16 +99,42 @@ def test_bins_all_pairs():
     assert (_u(m) == _u(wm)).all()
 
 
-@pytest.mark.parametrize("win", [(16, 16), (24, 24), (32, 32), (75, 32), (70, 40)])
-def test_planes(win):
-    imgs = _windows(win, 12, sum(win))
-    e = _make(win, len(imgs))
-    e.setImages(imgs)
+def _assert_planes(e, imgs, where):
     for i in range(len(imgs)):
         h, nrm = e.get_sample(i)
         wh, wn = hog.set_image(imgs[i])
-        assert (_u(h) == _u(wh)).all(), (win, i)
-        assert (_u(nrm) == _u(wn)).all(), (win, i)
+        assert (_u(h) == _u(wh)).all(), (where, i)
+        assert (_u(nrm) == _u(wn)).all(), (where, i)
+
+
+# the windows at the edges of the setImage kernel's LDS plan (tests/hog_lds_cases.py, held to the library's own plan in
+# tests/test_hog_lds_host.py): ten and nine planes per pass, tall windows, one plane per pass inside 64 KiB, the first window
+# of the 160 KiB branch, the last windows accepted at all
+@pytest.mark.parametrize("win", [(16, 16), (24, 24), (32, 32), (75, 32), (70, 40)] + lds.EVAL_WINDOWS)
+def test_planes(win):
+    imgs = _windows(win, 6 if win in lds.EVAL_WINDOWS else 12, sum(win))
+    e = _make(win, len(imgs))
+    e.setImages(imgs)
+    _assert_planes(e, imgs, win)
+
+
+@pytest.mark.parametrize("order", ["large_first", "small_first"])
+def test_evaluators_of_two_sizes_share_the_kernel(order):
+    """k_hog_set_images' LDS opt-in belongs to the kernel, not to an evaluator: a 134x135 evaluator (163 350 B) and an 86x85
+    one (154 870 B), created and filled in either order; then the large one takes new windows and still gives the
+    restatement's planes, and so does the small one."""
+    large, small = (134, 135), (86, 85)
+    assert lds.eval_opts_in(large) and lds.eval_opts_in(small) and lds.TABLE[large][2] > lds.TABLE[small][2]
+    made = {}
+    for win in ((large, small) if order == "large_first" else (small, large)):
+        imgs = _windows(win, 4, sum(win))
+        made[win] = _make(win, len(imgs))
+        made[win].setImages(imgs)
+        _assert_planes(made[win], imgs, (order, win, "first"))
+    for win in (large, small):
+        again = _windows(win, 4, sum(win) + 1)
+        made[win].setImages(again)
+        _assert_planes(made[win], again, (order, win, "again"))
 
 
 def test_all_variables_barcode():

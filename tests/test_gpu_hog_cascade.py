@@ -15,87 +15,32 @@ from cascadeclassifier_amd import evaluator as ev
 from oracle import oracle as orc
 from tests import cascade_factory as cf
 from tests import hog_cascade_factory as hf
+from tests import hog_lds_cases as lds
+from tests import hog_mine_cases as mc
 from tests import hog_restatement as hog
+from tests.hog_mine_cases import BACKGROUNDS, predict_windows, reader_stream
+from tests.hog_mine_cases import cascade_for as _cascade_for
+from tests.hog_mine_cases import edges as _edges
 from tests.util import frame_natural, frame_uniform, read_vec
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-WINS = [(24, 24), (32, 32), (75, 32)]
+# 24x24, 32x32, 75x32, then the windows at the edges of the miner's LDS classes (tests/hog_lds_cases.py): tall, either side of
+# the 64 KiB opt-in, the largest the miner accepts. The inputs, the restatement and the conditions that make each case worth
+# running (tests/test_hog_mine_cases_host.py) are in tests/hog_mine_cases.py.
+WINS = mc.WINDOWS
 
 
-# ---------------------------------------------------------------------------------------------- restatements
-def reader_stream(src, W, H, ox, oy):
-    """NegReader's stream over one image (nextImg with the given offset, then get until the ladder ends): the ladder as
-    (lw, lh, nx, ny) per level and every window's pixels in stream order."""
-    src = np.ascontiguousarray(src, np.uint8)
-    rows, cols = src.shape
-    scale_factor, step = f32(1.4142135623730950488016887242097), f32(0.5)
-    scale = max(f32((f32(W) + f32(ox)) / f32(cols)), f32((f32(H) + f32(oy)) / f32(rows)))
-    img = orc.resize_linear_exact(src, int(f32(scale * f32(cols)) + f32(0.5)), int(f32(scale * f32(rows)) + f32(0.5)))
-    ladder, wins = [], []
-    px, py = ox, oy
-    nx = ny = 1
-    while True:
-        wins.append(img[py:py + H, px:px + W].copy())
-        if int(f32(f32(px) + f32(f32(1) + step) * f32(W))) < img.shape[1]:
-            px += int(f32(step * f32(W)))
-            if py == oy:
-                nx += 1
-        else:
-            px = ox
-            if int(f32(f32(py) + f32(f32(1) + step) * f32(H))) < img.shape[0]:
-                py += int(f32(step * f32(H)))
-                ny += 1
-            else:
-                ladder.append((img.shape[1], img.shape[0], nx, ny))
-                nx = ny = 1
-                py = oy
-                scale = f32(scale * scale_factor)
-                if scale <= f32(1):
-                    img = orc.resize_linear_exact(src, int(f32(scale * f32(cols))), int(f32(scale * f32(rows))))
-                else:
-                    break
-    return ladder, np.stack(wins)
-
-
-def predict_windows(feats, stages, windows):
-    """setImage of each window + the trainer's stage walk."""
-    hist, norm = hog.set_images(windows)
-    return hf.stage_walk(hf.parsed_model(stages), hf.feature_values(feats, hist, norm))
-
-
-def _reference_negative():  # test_integration.cpp:57-64
-    r, c = np.mgrid[0:128, 0:256]
-    return ((r * 7 + c * 13) & 0xFF).astype(np.uint8)
-
-
-def _edges(w, h, seed):
-    """High-contrast patches with edges everywhere: a window's outer ring sees different gradients than the level does."""
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:h, 0:w]
-    img = np.where(((x // 5) + (y // 7)) % 2 == 0, 250, 5).astype(np.uint8)
-    img[rng.random((h, w)) < 0.05] = 128
-    return img
-
-
-BACKGROUNDS = [("synthetic", _reference_negative(), 0, 0), ("natural", frame_natural(333, 211, 41), 5, 3),
-               ("edges", _edges(240, 160, 7), 11, 2)]
+def _id(win):
+    return "%dx%d" % win
 
 
 def _accept_all_haar(W, H):
     feat = orc.make_haar_feature(False, [(0, 0, 4, 4, -1.0), (0, 0, 2, 2, 4.0)])
     stages = [(-1e30, [([(0, -1, 0, 0.0)], [1.0, 1.0])])]
     return cf.haar_xml(np.array([feat]).reshape(1), stages, mode="BASIC", W=W, H=H)
-
-
-def _cascade_for(W, H, depth, seed, stage_sizes=(3, 4, 6)):
-    """A cascade calibrated on the stream windows of the test backgrounds, so that a sizeable share passes."""
-    wins = np.concatenate([reader_stream(img, W, H, ox, oy)[1] for _, img, ox, oy in BACKGROUNDS])
-    rng = np.random.default_rng(seed)
-    sel = wins[rng.choice(len(wins), min(len(wins), 400), replace=False)]
-    return hf.hog_cascade(sel, seed=seed, stage_sizes=stage_sizes, depth=depth, pass_share=0.75)
 
 
 def _classifier(xml, tmp_path, name):
@@ -108,25 +53,28 @@ def _classifier(xml, tmp_path, name):
 
 # ---------------------------------------------------------------------------------------------- predict on stored samples
 @pytest.mark.parametrize("depth", [1, 2], ids=["stumps", "trees"])
-@pytest.mark.parametrize("win", WINS, ids=["24x24", "32x32", "75x32"])
+@pytest.mark.parametrize("win", WINS, ids=_id)
 def test_predict_cascade_equals_stage_walk(win, depth, tmp_path):
     W, H = win
-    if win == (75, 32):
-        samples = read_vec(os.path.join(ROOT, "tests", "golden", "barcode.vec"))
-    elif win == (24, 24):
-        samples = frame_uniform(24, 24 * 20000, 12).reshape(20000, 24, 24)
-        samples[::3] = samples[::3] // 4 + 90  # lower-contrast third
-    else:
-        samples = np.stack([frame_natural(W * 3, H * 2, 5 + k)[k % H:k % H + H, (3 * k) % W:(3 * k) % W + W] for k in range(600)])
     rng = np.random.default_rng(W * 7 + depth)
-    calib = samples[rng.choice(len(samples), min(len(samples), 400), replace=False)]
-    xml, feats, stages = hf.hog_cascade(calib, seed=W + depth, stage_sizes=(4, 6, 9), depth=depth, pass_share=0.7)
+    if win in lds.MINER_WINDOWS:  # 200 samples; the 10-90 % pass share is asserted in tests/test_hog_mine_cases_host.py
+        samples, xml, feats, stages, want = mc.predict_case(win, depth)
+    else:
+        if win == (75, 32):
+            samples = read_vec(os.path.join(ROOT, "tests", "golden", "barcode.vec"))
+        elif win == (24, 24):
+            samples = frame_uniform(24, 24 * 20000, 12).reshape(20000, 24, 24)
+            samples[::3] = samples[::3] // 4 + 90  # lower-contrast third
+        else:
+            samples = np.stack([frame_natural(W * 3, H * 2, 5 + k)[k % H:k % H + H, (3 * k) % W:(3 * k) % W + W] for k in range(600)])
+        calib = samples[rng.choice(len(samples), min(len(samples), 400), replace=False)]
+        xml, feats, stages = hf.hog_cascade(calib, seed=W + depth, stage_sizes=(4, 6, 9), depth=depth, pass_share=0.7)
+        want = predict_windows(feats, stages, samples)
     c = _classifier(xml, tmp_path, "hog.xml")
     n = len(samples)
     e = cc.CvFeatureEvaluator.create(ev.HOG)
     e.init(cc.CvFeatureParams.create(ev.HOG), n, win)
     e.setImages(samples)
-    want = predict_windows(feats, stages, samples)
     assert 0 < want.sum() < n
     got = e.predict_cascade(c)
     assert (got == want).all(), f"{(got != want).sum()} of {n} samples differ"
@@ -150,7 +98,7 @@ def test_predict_cascade_type_and_window_mismatch(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- negative mining
-@pytest.mark.parametrize("win", WINS, ids=["24x24", "32x32", "75x32"])
+@pytest.mark.parametrize("win", WINS, ids=_id)
 def test_reader_restatement_matches_plan_and_oracle(win, tmp_path):
     """The test's reader walk is itself checked: its ladder is cc_negminer_plan's, and its windows are the pixels the
     oracle's literal reader loop keeps with an accept-all Haar cascade of the same window size."""
@@ -159,8 +107,7 @@ def test_reader_restatement_matches_plan_and_oracle(win, tmp_path):
     o = orc.load_cascade_xml(str(tmp_path / "all.xml"))
     xml, _, _ = _cascade_for(W, H, 1, seed=3, stage_sizes=(2,))
     m = cc.NegativeMiner(_classifier(xml, tmp_path, "hog.xml"))
-    for _, img, ox, oy in BACKGROUNDS:
-        ladder, wins = reader_stream(img, W, H, ox, oy)
+    for _, img, ox, oy, ladder, wins in mc.streams(win):
         plan = m.plan(img.shape[1], img.shape[0], ox, oy)
         assert plan["levels"] == ladder and plan["n_windows"] == len(wins)
         flags, pix, _ = orc.negmine_image(o, img, ox, oy, max_keep=len(wins) + 1)
@@ -168,23 +115,50 @@ def test_reader_restatement_matches_plan_and_oracle(win, tmp_path):
         assert len(cc.NegativeMiner(haar).run(img, ox, oy, max_keep=0)[0]) == len(wins)
 
 
-@pytest.mark.parametrize("depth", [1, 2], ids=["stumps", "trees"])
-@pytest.mark.parametrize("win", WINS, ids=["24x24", "32x32", "75x32"])
-def test_negative_mining_matches_reader_loop(win, depth, tmp_path):
-    W, H = win
-    xml, feats, stages = _cascade_for(W, H, depth, seed=W + 11 * depth)
-    m = cc.NegativeMiner(_classifier(xml, tmp_path, "hog.xml"))
+def _assert_mined(m, win, flags):
+    """The miner's flags, kept positions and kept pixels on every background of the window against the restatement's flags."""
     total = 0
-    for name, img, ox, oy in BACKGROUNDS:
-        _, wins = reader_stream(img, W, H, ox, oy)
-        want = predict_windows(feats, stages, wins)
+    for (name, img, ox, oy, _, wins), want in zip(mc.streams(win), flags):
         keep = 25
         got_f, got_p, got_i = m.run(img, ox, oy, max_keep=keep)
         assert got_f.shape == want.shape and (got_f == want).all(), f"{name}: {(got_f != want).sum()} of {len(want)} windows differ"
         want_i = np.nonzero(want)[0][:keep]
         assert (got_i == want_i).all() and (got_p == wins[want_i]).all(), name
         total += int(want.sum())
-    assert 0 < total
+    assert 0 < total < sum(len(f) for f in flags)
+
+
+@pytest.mark.parametrize("depth", [1, 2], ids=["stumps", "trees"])
+@pytest.mark.parametrize("win", WINS, ids=_id)
+def test_negative_mining_matches_reader_loop(win, depth, tmp_path):
+    xml, _, _, flags = mc.mining_case(win, depth)
+    _assert_mined(cc.NegativeMiner(_classifier(xml, tmp_path, "hog.xml")), win, flags)
+
+
+def test_negative_mining_with_long_stages(tmp_path):
+    """Stages of 70 and 130 stumps: in the wavefront walk (the cascade is order-independent) every lane takes a second and a
+    third stump of a stage. Both long stages reject and pass windows (tests/test_hog_mine_cases_host.py)."""
+    xml, _, stages, flags, counts = mc.long_stage_case()
+    assert hf.order_independent(stages) and all(p > 0 and e - p > 0 for e, p in counts[1:])
+    _assert_mined(cc.NegativeMiner(_classifier(xml, tmp_path, "hog.xml")), (24, 24), flags)
+
+
+def test_negative_mining_with_order_dependent_stumps(tmp_path):
+    """A stump cascade whose leaves (+2^80, a1, -2^80, a3, then more small votes) fail the order-independence proof: the
+    miner must walk it in one lane, in tree order. Summed in the order of a wavefront that shares the stumps
+    (hf.wave_stage_sums) a3's vote is lost as well as a1's and the same windows get other flags, so a miner that took the
+    wavefront walk here fails this test; so does one that sums in reversed order."""
+    xml, feats, stages, fwd, rev, wave = mc.order_dependent_case()
+    assert not hf.order_independent(stages)
+    assert (np.concatenate(fwd) != np.concatenate(wave)).any() and (np.concatenate(fwd) != np.concatenate(rev)).any()
+    assert (fwd[1] != wave[1]).any()  # also on the stored samples below
+    c = _classifier(xml, tmp_path, "hog.xml")
+    _assert_mined(cc.NegativeMiner(c), (24, 24), fwd)
+    wins = mc.streams((24, 24))[1][5]  # k_hog_predict's walk of the same cascade on stored samples
+    e = cc.CvFeatureEvaluator.create(ev.HOG)
+    e.init(cc.CvFeatureParams.create(ev.HOG), len(wins), (24, 24))
+    e.setImages(wins)
+    assert (e.predict_cascade(c) == fwd[1]).all()
 
 
 def test_window_border_is_the_copy_not_the_level():
@@ -263,3 +237,38 @@ def test_refusals(tmp_path):
     with pytest.raises(cc.CascadeError) as err:
         cc.NegativeMiner(cb)
     assert err.value.status == L.CC_ERR_UNSUPPORTED and "LDS" in str(err.value)
+
+
+def _one_stump(W, H):
+    c = cc.CascadeClassifier()
+    assert c.load_from_string(hf.hog_xml(np.array([[0, 0, 8, 8, 0]], np.int32), [(-1.0, [([(0, -1, 0, 0.5)], [1.0, -1.0])])], W, H))
+    return c
+
+
+def test_miner_refuses_the_first_window_past_its_lds(tmp_path):
+    """The last windows whose planes fit 160 KiB of LDS are accepted, the next ones refused (tests/hog_lds_cases.py), and a
+    refusal leaves the library able to mine. At height 40 the planes of 86, 87 and 88 columns fit (159 880, 161 720 and
+    163 560 B of 163 840); 89 columns (165 400 B) are the first that do not."""
+    for win in lds.MINER_LAST_ACCEPTED + [(86, 40), (87, 40)]:
+        assert lds.miner_accepts(win)
+        assert cc.NegativeMiner(_one_stump(*win)) is not None
+    for win in lds.MINER_FIRST_REFUSED:
+        assert not lds.miner_accepts(win)
+        with pytest.raises(cc.CascadeError) as err:
+            cc.NegativeMiner(_one_stump(*win))
+        assert err.value.status == L.CC_ERR_UNSUPPORTED and "LDS" in str(err.value), win
+    xml, _, _, flags = mc.mining_case((24, 24), 1)
+    _assert_mined(cc.NegativeMiner(_classifier(xml, tmp_path, "hog.xml")), (24, 24), flags)
+
+
+@pytest.mark.parametrize("order", ["large_first", "small_first"])
+def test_miners_of_two_sizes_share_the_kernel(order, tmp_path):
+    """k_negmine_hog's LDS opt-in belongs to the kernel, not to a miner: a 59x59 miner (161 405 B) and a 75x32 miner
+    (112 320 B) created in either order both mine what the restatement says, the large one also after the small one ran."""
+    large, small = (59, 59), (75, 32)
+    assert lds.miner_opts_in(large) and lds.miner_opts_in(small) and lds.TABLE[large][3] > lds.TABLE[small][3]
+    miners = {}
+    for win in ((large, small) if order == "large_first" else (small, large)):
+        miners[win] = cc.NegativeMiner(_classifier(mc.mining_case(win, 1)[0], tmp_path, "hog_%dx%d.xml" % win))
+    for win in (large, small, large):
+        _assert_mined(miners[win], win, mc.mining_case(win, 1)[3])

@@ -7,7 +7,8 @@ restatement (tests/hog_restatement.py). Each test goes past one point where the 
   of parts per variable at N = 100 000 (97 on 256 CUs; CCAMD_SPLIT_CAT_PARTS cannot go past 64);
 * calc_batch_sorted with 4-byte indices (2-byte indices refused past 65 536);
 * negative-mining batches of several 8 MiB pieces (cc_negmine.hip mine_images);
-* HOG windows whose setImage kernel needs more than 64 KB of LDS;
+* HOG windows whose setImage kernel needs more than 64 KB of LDS, and the windows at the edges of its LDS plan
+  (tests/hog_lds_cases.py);
 * more than 4 096 queued setImage windows (the queue is flushed while calls still arrive).
 
 Samples j < N - 65 536 are copied to j + 65 536 with the opposite label and a very different weight: an index truncated
@@ -18,9 +19,12 @@ import numpy as np
 import pytest
 
 import cascadeclassifier_amd as cc
+from cascadeclassifier_amd import _lib as L
 from cascadeclassifier_amd import evaluator as ev
 from oracle import oracle as orc
 from tests import cascade_factory as cf
+from tests import hog_lds_cases as lds
+from tests import hog_mine_cases as mc
 from tests import hog_restatement as hog
 from tests.test_gpu_negmine import _truncated
 from tests.test_gpu_split import _samples
@@ -426,6 +430,8 @@ def _hog_windows(win, n, seed):
 @pytest.mark.parametrize("win", [(128, 64), (96, 96), (128, 128)])
 def test_hog_windows_beyond_64k_of_lds(win):
     """128x64 and 96x96 take three planes per LDS pass (140 032 and 157 824 B), 128x128 one (147 968 B)."""
+    want_plan = {(128, 64): (3, 160, 140032), (96, 96): (3, 160, 157824), (128, 128): (1, 160, 147968)}[win]
+    assert lds.exported(*win)[:3] == want_plan == lds.TABLE[win][:3]
     imgs = _hog_windows(win, 4, sum(win))
     e = cc.CvFeatureEvaluator.create(ev.HOG)
     e.init(cc.CvFeatureParams.create(ev.HOG), len(imgs), win)
@@ -441,10 +447,85 @@ def test_hog_windows_beyond_64k_of_lds(win):
     assert (_u(got) == _u(want)).all(), f"{int((_u(got) != _u(want)).sum())} values differ"
 
 
+def _var_ranges(n_blocks, seed):
+    """Variable ranges for windows whose every variable is too much for the numpy loop: the first 20 blocks, the last 20, and
+    8 runs of 5 blocks at seeded places (40 blocks). Each range starts and ends inside a block."""
+    rng = np.random.default_rng(seed)
+    starts = [0, n_blocks - 20] + sorted(int(b) for b in rng.choice(np.arange(20, n_blocks - 25), 8, replace=False))
+    return [(b * 36 + 5 + 3 * k, (b + (20 if k < 2 else 5)) * 36 - 7 - k) for k, b in enumerate(starts)]
+
+
+@pytest.mark.parametrize("win", lds.EVAL_WINDOWS, ids=lambda w: "%dx%d" % w)
+def test_hog_windows_at_the_edges_of_the_lds_plan(win):
+    """The setImage plan at each budget's edge (tests/hog_lds_cases.py; the classes are asserted in tests/test_hog_lds_host.py):
+    37x37 ten planes per pass, 38x38 and 24x60 nine, 32x75 five, 85x85 one inside 64 KiB, 86x85 four of 160 KiB, 134x135 and
+    135x134 one of 160 KiB and the last windows accepted. Planes bitwise; every variable up to 86x85, ranges beyond."""
+    assert lds.exported(*win) == lds.TABLE[win] and lds.eval_accepts(win)
+    imgs = _hog_windows(win, 5, sum(win))
+    e = cc.CvFeatureEvaluator.create(ev.HOG)
+    e.init(cc.CvFeatureParams.create(ev.HOG), len(imgs), win)
+    e.setImages(imgs)
+    hist, norm = hog.set_images(imgs)
+    for i in range(len(imgs)):
+        h, nrm = e.get_sample(i)
+        assert (_u(h) == _u(hist[i])).all() and (_u(nrm) == _u(norm[i])).all(), (win, i)
+    cat = hog.catalog(*win)
+    nv = e.getNumVariables()
+    assert nv == 36 * len(cat)
+    if win not in lds.EVAL_LAST_ACCEPTED:
+        assert nv <= 47952  # 86x85: 1 332 blocks
+        got = e.calc_batch(0, nv)
+        want = hog.eval_vars(cat, hist, norm)
+        assert (_u(got) == _u(want)).all(), f"{int((_u(got) != _u(want)).sum())} values differ"
+        return
+    assert len(cat) == 5728 and nv == 206208
+    new = _hog_windows(win, 4, sum(win) + 9)[3]
+    e.setImage(new, 0, 2)  # the host mirror of a window set through setImage
+    h_new, n_new = hog.set_images(new[None])
+    rng = np.random.default_rng(sum(win))
+    for vb, ve in _var_ranges(len(cat), sum(win)):
+        assert vb % 36 != 0 and ve % 36 != 0
+        want = hog.eval_vars(cat, hist, norm, vb, ve)
+        got = e.calc_batch(vb, ve, sample_idx=np.array([0, 1, 3, 4], np.int32))
+        assert (_u(got) == _u(want[:, [0, 1, 3, 4]])).all(), (vb, ve)
+        vis = np.sort(rng.choice(np.arange(vb, ve), 40, replace=False))
+        mirror = np.array([e(int(vi), 2) for vi in vis], np.float32)
+        assert (_u(mirror) == _u(hog.eval_vars(cat, h_new, n_new, vb, ve)[vis - vb, 0])).all(), (vb, ve)
+    h, nrm = e.get_sample(2)  # and the device's copy of that window
+    assert (_u(h) == _u(h_new[0])).all() and (_u(nrm) == _u(n_new[0])).all()
+
+
+def test_hog_predict_at_the_first_window_of_the_160k_branch(tmp_path):
+    """predict_cascade with a HOG stump cascade at 86x85 (planes of 299 280 B per sample) against the restatement's walk.
+    The case and its 10-90 % pass share: tests/hog_mine_cases.py, tests/test_hog_mine_cases_host.py."""
+    win = (86, 85)
+    samples, xml, _, _, want = mc.predict_case_86x85()
+    assert 0 < want.sum() < len(samples)
+    path = str(tmp_path / "hog.xml")
+    open(path, "w").write(xml)
+    c = cc.CascadeClassifier(path)
+    assert not c.empty(), getattr(c, "load_error", "")
+    e = cc.CvFeatureEvaluator.create(ev.HOG)
+    e.init(cc.CvFeatureParams.create(ev.HOG), len(samples), win)
+    e.setImages(samples)
+    assert (e.predict_cascade(c) == want).all()
+
+
 def test_hog_window_too_large_for_lds():
     e = cc.CvFeatureEvaluator.create(ev.HOG)
-    with pytest.raises(cc.CascadeError):
-        e.init(cc.CvFeatureParams.create(ev.HOG), 2, (160, 160))
+    for win in [(160, 160)] + lds.EVAL_FIRST_REFUSED:  # 135x135 and 136x134: the first windows past 134x135
+        assert not lds.eval_accepts(win)
+        with pytest.raises(cc.CascadeError) as err:
+            e.init(cc.CvFeatureParams.create(ev.HOG), 2, win)
+        assert err.value.status == L.CC_ERR_UNSUPPORTED and "LDS" in str(err.value), win
+    for win in lds.EVAL_LAST_ACCEPTED:
+        assert lds.eval_accepts(win)
+        e.init(cc.CvFeatureParams.create(ev.HOG), 2, win)
+    imgs = _hog_windows((24, 24), 4, 3)  # and after a refusal an evaluator still works
+    e.init(cc.CvFeatureParams.create(ev.HOG), len(imgs), (24, 24))
+    e.setImages(imgs)
+    hist, norm = hog.set_images(imgs)
+    assert (_u(e.calc_batch(0, e.getNumVariables())) == _u(hog.eval_vars(hog.catalog(24, 24), hist, norm))).all()
 
 
 # ---- 7. the setImage queue past 4 096 windows ------------------------------------------------------------------------
