@@ -201,6 +201,12 @@ SIGNATURES = {
     "cc_debug_eval_tile_samples": (_i, [_vp]),
     "cc_eval_presort": (_i, [_vp, _i]),
     "cc_eval_presort_range": (_i, [_vp, _i, _i, _i]),
+    "cc_presort_plan": (_i, [_i, _i, _i, C.c_uint64, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_uint64)]),
+    "cc_eval_presort_split": (_i, [_vp, _i, _i, _i, _i, _i]),
+    "cc_eval_table_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "cc_eval_presort_budget": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "cc_eval_stream_profile": (_i, [_vp, _i]),
+    "cc_eval_stream_phase_ms": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "cc_eval_find_best_split": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _d, _i, _i, C.POINTER(Split), _vp, _vp]),
     "cc_boost_create": (_i, [_vp, _i, C.POINTER(BoostParams), _pp]),
     "cc_boost_create_depth": (_i, [_vp, _i, C.POINTER(BoostParams), _i, _pp]),

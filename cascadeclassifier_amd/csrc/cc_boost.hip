@@ -207,8 +207,12 @@ __global__ __launch_bounds__(1024) void k_boost_argmax(const double* __restrict_
 // direction holds at k has as its rank in the node's sorted order the running count of such entries before it (ballot
 // within a wavefront, carried across wavefronts and chunks): left iff rank <= split_point (calc_node_dir,
 // o_cvboostree.cpp:130-144). A sample that predict holds at k goes left iff value <= ord_c.
+// After a split presort only the variables below `resident` have a row in the tables; a streamed winner's row is the
+// winner row its chunk left behind (k_stream_winner, cc_split.hip): one entry per rank. Which of the two is read is
+// decided here, from rec->var.
 template <class TI>
-__global__ __launch_bounds__(1024) void k_boost_apply_ord(const float* __restrict__ sv, const TI* __restrict__ si, int n,
+__global__ __launch_bounds__(1024) void k_boost_apply_ord(const float* __restrict__ sv, const TI* __restrict__ si, int n, int resident,
+                                                          const float* __restrict__ win_val, const TI* __restrict__ win_idx,
                                                           const uint8_t* __restrict__ mask, const SplitRec* __restrict__ rec, int k, int left_id,
                                                           int* __restrict__ node_dir, int* __restrict__ node_pred) {
   __shared__ int wave_cnt[16];
@@ -216,7 +220,12 @@ __global__ __launch_bounds__(1024) void k_boost_apply_ord(const float* __restric
   const int f = rec->var, split_point = rec->split_point;
   if (f < 0) return;
   const float ord_c = rec->ord_c;
-  const size_t base = (size_t)(f >> 6) * n * 64 + (f & 63);
+  const bool streamed = f >= resident;
+  const size_t base = streamed ? 0 : (size_t)(f >> 6) * n * 64 + (f & 63), stride = streamed ? 1 : 64;
+  if (streamed) {
+    sv = win_val;
+    si = win_idx;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0) carried = 0;
   __syncthreads();
@@ -226,8 +235,8 @@ __global__ __launch_bounds__(1024) void k_boost_apply_ord(const float* __restric
     float v = 0.f;
     bool act = false, pred = false, ok = false;
     if (r < n) {
-      idx = (unsigned)si[base + (size_t)r * 64];
-      v = sv[base + (size_t)r * 64];
+      idx = (unsigned)si[base + (size_t)r * stride];
+      v = sv[base + (size_t)r * stride];
       ok = idx < (unsigned)n;  // always, with presort's tables; never touch anything outside the arrays
       if (ok) {
         act = k == 0 ? mask[idx] != 0 : node_dir[idx] == k;
@@ -594,7 +603,8 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
     if (!b->categorical) {
       const NodeRec& r = tree[(size_t)k].rec;
       const double w0 = r.s[0], w1 = b->classifier ? r.s[1] : 0.0;
-      if (cc_status s = split_launch_ordered(e, mode, form, w0, w1, tree[(size_t)k].value * w0); s != CC_OK) return s;
+      // after a split presort: the head, then the streamed chunks, the leader so far and its sorted row kept on the device
+      if (cc_status s = split_launch_ordered(e, mode, form, w0, w1, tree[(size_t)k].value * w0, true); s != CC_OK) return s;
       const size_t fpad = ((size_t)F + 63) / 64 * 64;
       const OrdResult dev(e->d_split_out.p, fpad);
       (void)hipEventRecord(b->ev[2], st);
@@ -602,11 +612,12 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
       (void)hipEventRecord(b->ev[3], st);
       // 4. directions and the predict rule
       if (idx16)
-        hipLaunchKernelGGL(k_boost_apply_ord<uint16_t>, dim3(1), dim3(1024), 0, st, e->d_sorted_val.p, e->d_sorted_idx16.p, n, b->mask.p, b->d_split(), k,
-                           left_id, b->node_dir.p, b->node_pred.p);
+        hipLaunchKernelGGL(k_boost_apply_ord<uint16_t>, dim3(1), dim3(1024), 0, st, e->d_sorted_val.p, e->d_sorted_idx16.p, n, e->presort_resident,
+                           e->d_win_val.p, reinterpret_cast<const uint16_t*>(e->d_win_idx.p), b->mask.p, b->d_split(), k, left_id, b->node_dir.p,
+                           b->node_pred.p);
       else
-        hipLaunchKernelGGL(k_boost_apply_ord<int32_t>, dim3(1), dim3(1024), 0, st, e->d_sorted_val.p, e->d_sorted_idx32.p, n, b->mask.p, b->d_split(), k,
-                           left_id, b->node_dir.p, b->node_pred.p);
+        hipLaunchKernelGGL(k_boost_apply_ord<int32_t>, dim3(1), dim3(1024), 0, st, e->d_sorted_val.p, e->d_sorted_idx32.p, n, e->presort_resident,
+                           e->d_win_val.p, e->d_win_idx.p, b->mask.p, b->d_split(), k, left_id, b->node_dir.p, b->node_pred.p);
       CC_HIP(hipGetLastError());
     } else {
       cc_split sp;
@@ -640,11 +651,8 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
     CC_HIP(hipStreamSynchronize(st));
     SplitRec sr;
     std::memcpy(&sr, pin, sizeof(sr));
-    {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, e->ev_a.e, e->ev_b.e) == hipSuccess) e->last_ms = ms;
-      b->last_ms[1] += e->last_ms;
-    }
+    // the categorical search has noted its own time; the ordered one, head and streamed chunks, is read here
+    b->last_ms[1] += b->categorical ? e->last_ms : split_search_ms(e);
     if (!b->categorical) {
       if (k != 0) b->last_ms[0] += span(0, 1);
       b->last_ms[2] += span(2, 3);

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -133,8 +134,36 @@ struct OrdResult {
 // The form cc_eval_find_best_split picks for class labels or responses of +-1 over N presorted samples.
 TableForm split_table_form_unit(int N);
 // Both search the presorted variables over a node table that is already in e->d_split_tab. Caller holds e->mu.
-// Ordered: mode 0 regression, 1 GINI, 2 MISCLASS; the per-variable results stay in e->d_split_out (OrdResult).
-cc_status split_launch_ordered(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0);
+// Ordered: mode 0 regression, 1 GINI, 2 MISCLASS; the per-variable results stay in e->d_split_out (OrdResult). After a split
+// presort (cc_eval_presort_split) the resident head is searched first, then the tail chunk by chunk: evaluated, sorted,
+// interleaved into the chunk table and searched by the same kernel, all queued on e->stream without a host wait. With
+// track_winner the best variable so far (k_boost_argmax's rule) is kept in e->d_win_state after the head and after every
+// chunk, and a chunk that holds it leaves that variable's sorted row in e->d_win_val / e->d_win_idx.
+cc_status split_launch_ordered(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0,
+                               bool track_winner = false);
+// Device time of the last split_launch_ordered (head and streamed chunks); the stream has been synchronised.
+double split_search_ms(cc_evaluator* e);
+// Stable sort of the rows of e->d_out (one variable per row of N values, at most FB rows) into keys_out / sorted. Owns
+// the scratch of both sorts; that of the device-wide segmented sort is built when a pass first needs it.
+struct RowSorter {
+  cc_evaluator* e;
+  int N, FB;
+  DevBuf<float> keys_out;
+  DevBuf<int> sorted, iota, offsets;
+  DevBuf<char> temp;
+  bool segmented_ready = false;
+
+  RowSorter(cc_evaluator* e_, int N_, int FB_) : e(e_), N(N_), FB(FB_) {}
+  cc_status init();
+  cc_status prepare_segmented();
+  cc_status sort(int nf);
+  size_t bytes() const { return keys_out.n * 4 + sorted.n * 4 + iota.n * 4 + offsets.n * 4 + temp.n; }
+};
+// The best variable so far of a streamed search: k_boost_argmax's (quality, variable), quality 0 and variable -1 for none.
+struct StreamBest {
+  int var;
+  float quality;
+};
 // Categorical: node = stored samples in increasing order; the winner as cc_eval_find_best_split reports it.
 cc_status split_categorical_from_table(cc_evaluator* e, bool is_classifier, bool gini, TableForm form, cc_split* out);
 
@@ -193,6 +222,24 @@ struct cc_evaluator {
   int presort_f0 = 0, presort_f1 = 0;    // variables covered by the tables
   ccamd::DevBuf<double> d_split_tab, d_split_out;
   ccamd::DevBuf<int32_t> d_split_idx;
+  // split presort (cc_eval_presort_split): variables [0, presort_resident) of the range have tables; [presort_resident, F)
+  // are evaluated, sorted and searched presort_chunk at a time at every node (0: nothing is streamed). The chunk scratch
+  // lives as long as the split: the row sorter (with d_out), one chunk table in the resident layout and the winner row.
+  int presort_resident = 0, presort_chunk = 0;
+  std::unique_ptr<ccamd::RowSorter> stream_rows;
+  ccamd::DevBuf<float> d_chunk_val;
+  ccamd::DevBuf<uint16_t> d_chunk_idx16;
+  ccamd::DevBuf<int32_t> d_chunk_idx32;
+  ccamd::DevBuf<float> d_win_val;    // the streamed winner's sorted values, [presort_n] ...
+  ccamd::DevBuf<int32_t> d_win_idx;  // ... and sample numbers, in the tables' width (16- or 32-bit)
+  ccamd::DevBuf<ccamd::StreamBest> d_win_state;
+  ccamd::OwnEvent ev_stream_a;  // start of a streamed search (launch_batch re-records ev_a for every chunk)
+  // cc_eval_stream_profile: six events per chunk (before evaluate, after evaluate, sort, interleave, search, winner) and the
+  // sums of their distances over the last streamed search, read once the stream has been synchronised (split_search_ms)
+  bool stream_profile = false;
+  std::vector<ccamd::OwnEvent> stream_ev;
+  size_t stream_ev_used = 0;
+  double stream_phase_ms[5] = {};
   ccamd::OwnEvent ev_piece[8];  // categorical search: one per piece of the sums on its way back
   // ---- HOG (cc_hog.hip) ----
   // catalog blocks [n][4] = x, y, cell w, cell h; samples.hog holds [max_samples][cols][10] (9 bins, then norm); nfeat counts

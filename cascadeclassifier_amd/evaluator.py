@@ -21,6 +21,16 @@ def _vp(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def presort_plan(feature_type, n_vars, n_samples, budget_bytes):
+    """cc_presort_plan (host arithmetic; no device unless budget_bytes is 0 = the device's free memory): how a presort of
+    n_vars variables over n_samples fits budget_bytes of device memory. Returns (resident_vars, chunk_vars, bytes_needed);
+    chunk_vars is 0 when every table fits. Raises CascadeError (CC_ERR_UNSUPPORTED) for a budget below one chunk of 64
+    variables, naming the smallest budget that works, and for LBP tables that do not fit."""
+    r, c, b = C.c_int(0), C.c_int(0), C.c_uint64(0)
+    L.check(L.lib().cc_presort_plan(int(feature_type), int(n_vars), int(n_samples), int(budget_bytes), C.byref(r), C.byref(c), C.byref(b)))
+    return r.value, c.value, b.value
+
+
 class CvFeatureParams:
     """CvFeatureParams / CvHaarFeatureParams / CvLBPFeatureParams / CvHOGFeatureParams (haarfeatures.h:31-51,
     lbpfeatures.h:22-26, HOGfeatures.cpp:9-14)."""
@@ -141,12 +151,60 @@ class CvFeatureEvaluator:
         return nf.value, nc.value
 
     # ---- best-split search of a boosted-tree node (CvDTree::find_best_split, o_cvdtree.cpp:313-357)
-    def presort(self, n_samples=None, fi_begin=0, fi_end=None):
+    def presort(self, n_samples=None, fi_begin=0, fi_end=None, *, resident_vars=None, chunk_vars=None, budget_bytes=None):
         """Evaluate features [fi_begin, fi_end) (default: all) on stored samples [0, n_samples) and keep the sorted
-        order (Haar) / the category codes (LBP) resident on the device; call again whenever the stored samples change."""
+        order (Haar, HOG) / the category codes (LBP) resident on the device; call again whenever the stored samples change.
+
+        Past the memory limit (ordered variables; cc_eval_presort_split): resident_vars of the range's variables keep
+        their tables, the others are evaluated, sorted and searched chunk_vars at a time at every node, with results
+        bit-identical to the resident presort. budget_bytes plans the two numbers (presort_plan; 0: the free device
+        memory plus what this evaluator already holds for tables). Returns (resident_vars, chunk_vars) as used, or None
+        for the plain call with all three left at None."""
         n = self.maxSampleCount if n_samples is None else int(n_samples)
         self._presorted = (int(fi_begin), self.getNumVariables() if fi_end is None else int(fi_end))
-        L.check(L.lib().cc_eval_presort_range(self._e, self._presorted[0], self._presorted[1], n))
+        f0, f1 = self._presorted
+        if resident_vars is None and chunk_vars is None and budget_bytes is None:
+            L.check(L.lib().cc_eval_presort_range(self._e, f0, f1, n))
+            return None
+        if budget_bytes is not None:
+            if resident_vars is not None or chunk_vars is not None:
+                raise ValueError("presort: budget_bytes plans resident_vars and chunk_vars; give either the budget or the two")
+            resident_vars, chunk_vars, _ = self.presort_plan(n, f1 - f0, budget_bytes)
+        if resident_vars is None:
+            raise ValueError("presort: chunk_vars needs resident_vars")
+        if chunk_vars is None:
+            chunk_vars = 64
+        L.check(L.lib().cc_eval_presort_split(self._e, f0, f1, n, int(resident_vars), int(chunk_vars)))
+        return int(resident_vars), int(chunk_vars)
+
+    def presort_plan(self, n_samples, n_vars=None, budget_bytes=0):
+        """cc_presort_plan for this evaluator's feature type: (resident_vars, chunk_vars, bytes_needed) of a presort of
+        n_vars variables (default: all) over n_samples within budget_bytes; chunk_vars is 0 when everything fits.
+        budget_bytes = 0: the free device memory plus table_bytes()."""
+        nv = self.getNumVariables() if n_vars is None else int(n_vars)
+        budget = C.c_uint64(int(budget_bytes))
+        if budget.value == 0:
+            L.check(L.lib().cc_eval_presort_budget(self._e, C.byref(budget)))
+        return presort_plan(self.feature_type, nv, n_samples, budget.value)
+
+    def table_bytes(self) -> int:
+        """Device bytes held for sorted tables plus streaming scratch (cc_eval_table_bytes)."""
+        b = C.c_uint64(0)
+        L.check(L.lib().cc_eval_table_bytes(self._e, C.byref(b)))
+        return b.value
+
+    STREAM_PHASES = ("evaluate", "sort", "interleave", "search", "winner")
+
+    def stream_profile(self, enable=True):
+        """Events between the steps of every streamed chunk (cc_eval_stream_profile); read them with stream_phase_ms."""
+        L.check(L.lib().cc_eval_stream_profile(self._e, 1 if enable else 0))
+
+    def stream_phase_ms(self) -> dict:
+        """Device time of the last streamed search by step, summed over its chunks (cc_eval_stream_phase_ms)."""
+        ms = np.zeros(len(self.STREAM_PHASES), np.float64)
+        k = C.c_int(0)
+        L.check(L.lib().cc_eval_stream_phase_ms(self._e, _vp(ms), len(ms), C.byref(k)))
+        return dict(zip(self.STREAM_PHASES, ms.tolist()))
 
     def find_best_split(self, weights, *, responses=None, class_labels=None, sample_idx=None, node_value=0.0,
                         boost_type=BOOST_GENTLE, split_criteria=0, per_var=False):

@@ -130,13 +130,18 @@ class BackgroundReader:
 
 def train_cascade(positives, backgrounds, num_pos, num_neg, num_stages, *, feature_type=HAAR, win=(24, 24), haar_mode=BASIC,
                   boost_type=BOOST_GENTLE, min_hit_rate=0.995, max_false_alarm=0.5, weight_trim_rate=0.95, max_weak_count=100,
-                  acceptance_ratio_break_value=-1.0, device=0, max_batch=256, on_stage=None, max_depth=1):
+                  acceptance_ratio_break_value=-1.0, device=0, max_batch=256, on_stage=None, max_depth=1, table_budget_bytes=None):
     """CvCascadeClassifier::train (cascadeclassifier.cpp:203-284) for stages of weak trees with at most max_depth levels of
     splits (the reference's -maxDepth; 1: stumps). positives: [n][win_h][win_w]
     uint8, taken from the first one again for every stage; backgrounds: 2-D uint8 images, read as NegReader reads its list.
     Returns (cascade or None, stage records, end reason); a record holds pos_count, pos_consumed, neg_count, neg_consumed,
     acceptance_ratio and, for a trained stage, weak (the records of CascadeBoost.train_stage). on_stage(i, record, cascade)
-    is called after every trained stage. Raises ValueError when the positives run out before num_pos of them pass."""
+    is called after every trained stage. Raises ValueError when the positives run out before num_pos of them pass.
+    table_budget_bytes: device memory every stage's presort may use for sorted tables and streaming scratch (0: what is
+    free); variables whose tables do not fit are evaluated and sorted again at every node, and the trained cascade is the
+    same. None: all tables resident, or an error when they do not fit. The reference's -precalcValBufSize and
+    -precalcIdxBufSize size two host caches in MB, one for values and one for sorted indices; here one budget in bytes
+    covers both."""
     positives = np.ascontiguousarray(positives, np.uint8)
     win = (int(win[0]), int(win[1]))
     if num_pos < 1 or num_neg < 0 or max_batch < 1 or max_depth < 1:
@@ -179,7 +184,10 @@ def train_cascade(positives, backgrounds, num_pos, num_neg, num_stages, *, featu
             end = END_ACCEPTANCE_BREAK
             break
         n = pos_count + neg_count
-        e.presort(n)
+        if table_budget_bytes is None:
+            e.presort(n)
+        else:
+            e.presort(n, budget_bytes=table_budget_bytes)
         weak = CascadeBoost(e, n, boost_type=boost_type, weight_trim_rate=weight_trim_rate, min_hit_rate=min_hit_rate,
                             max_false_alarm=max_false_alarm, max_weak_count=max_weak_count, max_depth=max_depth).train_stage()
         if not any(w["trained"] for w in weak):

@@ -626,6 +626,53 @@ typedef struct cc_split {
  */
 CC_API cc_status cc_eval_presort(cc_evaluator* e, int n_samples);
 CC_API cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n_samples);
+/*    Past the memory limit: a resident head and a streamed tail (ordered variables: Haar, HOG). cc_eval_presort(_range)
+ *    refuses with CC_ERR_UNSUPPORTED when the tables of all variables do not fit the device. The reference never does: its
+ *    -precalcValBufSize / -precalcIdxBufSize caches hold a head of the catalog, and CvCascadeBoostTrainData::
+ *    get_ord_var_data evaluates and sorts every variable beyond them again at every node
+ *    (o_cvcascadeboosttraindata.cpp:403-461, the uncached branch :437-458). cc_eval_presort_split does the same on the
+ *    device: the first resident_vars variables of [fi_begin, fi_end) keep their tables exactly as cc_eval_presort_range
+ *    builds them; the others are evaluated, sorted and searched chunk_vars at a time at every node, through the same
+ *    kernels and the same [group][rank][64] layout. Every result -- cc_eval_find_best_split's winner and per-variable
+ *    outputs, every record and the whole per-sample state of a cc_boost over it -- is bit-identical to a run with all
+ *    tables resident: equal values keep increasing sample order in both (the reference's uncached branch uses an unstable
+ *    std::sort; its tie order is not followed).
+ *      resident_vars: a multiple of 64 in [0, F], or F = fi_end - fi_begin, which is cc_eval_presort_range itself.
+ *      chunk_vars: a multiple of 64, at least 64; ignored when resident_vars == F; cut down to the tail's size and to
+ *        2^28 values per pass, as a pass of the full presort.
+ *      LBP: only resident_vars == F; anything else is CC_ERR_UNSUPPORTED (categorical variables are not streamed).
+ *    The chunk scratch (16 B per value of a chunk, one chunk table, one winner row of 8 B per sample) stays with the
+ *    evaluator until the next presort. A cc_boost created over a split presort needs nothing else: per searched node the
+ *    head, then the chunks, with no host wait in between.
+ *
+ *    cc_presort_plan chooses the two numbers for a budget in bytes. Host arithmetic only (no device, unless budget_bytes
+ *    is 0 = the calling thread's device's free memory). With N samples, F variables, per = 4 + (N <= 65 536 ? 2 : 4):
+ *      everything resident:  ceil64(F) * N * per + min(F, P) * N * 16,  P = max(64, floor64(2^28 / N))   (as cc_eval_presort)
+ *      split (R, C):         head(R) + chunk(C) + 8 * N
+ *        head(R)  = R == 0 ? 0 : (R * N + 64 * 64) * per        (64 ranks of read-ahead padding)
+ *        chunk(C) = C * N * 16 + (C * N + 64 * 64) * per        (values, sorted keys, sorted indices, iota; the chunk table)
+ *    If everything fits: *resident_vars = F, *chunk_vars = 0. If all but the last group does, split(Rmax, 64) <= budget
+ *    with Rmax = the largest multiple of 64 below F: (Rmax, 64). Otherwise C = the largest multiple of 64 up to
+ *    min(ceil64(F), P) with split(0, C) <= budget, and, once C has reached that bound, R = the largest multiple of 64
+ *    up to Rmax with split(R, C) <= budget (0 before). *resident_vars never shrinks as the budget grows.
+ *    *bytes_needed <= budget is what the plan holds. A budget below split(0, 64) is CC_ERR_UNSUPPORTED; the message names
+ *    that minimum. LBP: all resident or CC_ERR_UNSUPPORTED. Beyond 24 576 samples a row is sorted by the device-wide
+ *    segmented sort, whose temporary storage comes on top of both sums, as it does for cc_eval_presort.
+ *
+ *    cc_eval_table_bytes: device bytes the evaluator holds for sorted tables plus streaming scratch.
+ *    cc_eval_presort_budget: free device memory now plus cc_eval_table_bytes -- what a presort of this evaluator can use.
+ *    cc_eval_stream_profile(e, 1) puts events between the steps of every streamed chunk (no host wait is added);
+ *    cc_eval_stream_phase_ms then gives the device time of the last streamed search by step, summed over its chunks:
+ *    evaluate, sort, interleave, search, winner (*n_parts = 5; tools/bench_boost_streamed.py).
+ */
+CC_API cc_status cc_presort_plan(int feature_type, int n_vars, int n_samples, uint64_t budget_bytes, int* resident_vars,
+                                 int* chunk_vars, uint64_t* bytes_needed);
+CC_API cc_status cc_eval_presort_split(cc_evaluator* e, int fi_begin, int fi_end, int n_samples, int resident_vars,
+                                       int chunk_vars);
+CC_API cc_status cc_eval_table_bytes(cc_evaluator* e, uint64_t* bytes);
+CC_API cc_status cc_eval_presort_budget(cc_evaluator* e, uint64_t* bytes);
+CC_API cc_status cc_eval_stream_profile(cc_evaluator* e, int enable);
+CC_API cc_status cc_eval_stream_phase_ms(cc_evaluator* e, double* ms, int cap, int* n_parts);
 CC_API cc_status cc_eval_find_best_split(cc_evaluator* e, const int32_t* sample_idx, int n, const double* weights,
                                          const float* responses, const int32_t* class_labels, double node_value,
                                          int boost_type, int split_criteria, cc_split* out, double* per_var_quality,
