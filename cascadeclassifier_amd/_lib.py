@@ -106,6 +106,10 @@ class TestsetItem(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("iteration", "bg_image", "x", "y", "width", "height")]
 
 
+class InfoRecord(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("image", "x", "y", "width", "height")]
+
+
 class SampleBgReader(C.Structure):
     _fields_ = [("sizes", C.c_void_p), ("n_images", C.c_int32)] + \
                [(n, C.c_int32) for n in ("have", "round", "last", "off_x", "off_y", "pt_x", "pt_y", "cur_w", "cur_h")] + \
@@ -248,6 +252,10 @@ SIGNATURES = {
     "cc_testset_plan": (_i, [_i, _i, _i, _i, C.POINTER(SampleParams), C.POINTER(C.c_uint64), C.POINTER(SampleBgReader),
                              C.POINTER(_d), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _vp, _vp]),
     "cc_sampler_render_testset": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz]),
+    "cc_area_tab": (_i, [_i, _i, C.POINTER(_d), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _i, C.POINTER(C.c_int32)]),
+    "cc_samples_from_info": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "cc_samples_from_info_last_ms": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "cc_resize_area_u8": (_i, [_i, _vp, _i, _i, _sz, _vp, _i, _i]),
 }
 CC_FILL_FILLED, CC_FILL_RATIO, CC_FILL_EXHAUSTED = 0, 1, 2
 CC_SAMPLE_RANDOM_INVERT = 0x7FFFFFFF

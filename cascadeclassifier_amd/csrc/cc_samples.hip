@@ -12,7 +12,10 @@
 // the canvas only 4 image pixels and the 4x4 mask pixels under the blur of those 4 are ever read: the kernel evaluates
 // exactly these and the canvas does not exist. A canvas pixel is a pure function of (x, y), the coefficients and the span of
 // row y; the spans are the one sequential part (x_min += k_left, row after row) and come from the host.
-// This translation unit is compiled with -ffp-contract=off: a fused multiply-add in the warp changes bytes.
+// The tool's -info mode (cvCreateTrainingSamplesFromInfo: annotated rectangles cut out and resized to the window) has no
+// random draw and no plan: cc_area_tab states one axis of INTER_AREA on the host, k_info_render resizes a batch of
+// rectangles of any sizes (copy, exact bilinear, integer-ratio and general area) with one thread per window pixel.
+// This translation unit is compiled with -ffp-contract=off: a fused multiply-add in the warp or in the area sums changes bytes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -477,6 +480,108 @@ __global__ __launch_bounds__(256) void k_warp_dense(const uint8_t* __restrict__ 
   dst[(size_t)y * dstride + x] = (uint8_t)warp_sample(src, sw, sh, sstride, warp_coord(c, x, y, sw, sh));
 }
 
+// ------------------------------------------------------------------------------------------------
+// The -info mode (cvCreateTrainingSamplesFromInfo, utility.cpp:1125-1232): annotated rectangles resized to the window
+// ------------------------------------------------------------------------------------------------
+// How resize(src(Rect), sample, Size(dw, dh), 0, 0, sw >= dw && sh >= dh ? INTER_AREA : INTER_LINEAR_EXACT) treats one
+// rectangle (:1205-1208, and cv::resize's own same-size copy and integer-ratio fast path).
+enum InfoMode { INFO_COPY = 0, INFO_LINEAR = 1, INFO_AREA_FAST = 2, INFO_AREA = 3 };
+
+// One record of a batch: the first byte of its rectangle in the batch's image buffer, that image's row pitch in bytes, the
+// rectangle's sides and its InfoMode. The rectangle alone is the source: nothing outside it is read.
+struct InfoSlot {
+  size_t src;
+  int32_t pitch, w, h, mode;
+};
+
+__device__ __forceinline__ uint8_t saturate_round_u8(float v) {  // saturate_cast<uchar>(cvRound(v)): half to even
+  return (uint8_t)min(max(__float2int_rn(v), 0), 255);
+}
+
+// One window pixel (dx, dy) of an sw x sh rectangle at S.
+__device__ __forceinline__ uint8_t info_pixel(const uint8_t* __restrict__ S, size_t pitch, int sw, int sh, int dw, int dh, int mode, int dx,
+                                              int dy) {
+  if (mode == INFO_COPY) return S[(size_t)dy * pitch + dx];
+  if (mode == INFO_LINEAR) {  // two taps per axis, the border replicated at the rectangle's edge
+    int32_t x0, y0;
+    uint16_t wx1, wy1;
+    linear_exact_tap(sw, dw, dx, x0, wx1);
+    linear_exact_tap(sh, dh, dy, y0, wy1);
+    const int x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1);
+    const uint8_t* r0 = S + (size_t)y0 * pitch;
+    const uint8_t* r1 = S + (size_t)y1 * pitch;
+    const unsigned wx0 = 256u - wx1, wy0 = 256u - wy1;
+    return (uint8_t)resize_lerp_v(wy0, wy1, resize_lerp_h(wx0, wx1, r0[x0], r0[x1]), resize_lerp_h(wx0, wx1, r1[x0], r1[x1]));
+  }
+  const AreaAxis ax = area_axis(sw, dw), ay = area_axis(sh, dh);
+  if (mode == INFO_AREA_FAST) {  // sw == iscale_x * dw and sh == iscale_y * dh (checked on the host): the block is inside
+    const int kx = ax.iscale, ky = ay.iscale;
+    const uint8_t* p = S + (size_t)(dy * ky) * pitch + (size_t)(dx * kx);
+    if (kx == 2 && ky == 2) return (uint8_t)((p[0] + p[1] + p[pitch] + p[pitch + 1] + 2) >> 2);
+    int sum = 0;  // below 2^31: the host refuses iscale_x * iscale_y * 255 >= 2^31
+    for (int j = 0; j < ky; j++) {
+      const uint8_t* r = p + (size_t)j * pitch;
+      for (int i = 0; i < kx; i++) sum += r[i];
+    }
+    const float scale = 1.f / (float)(kx * ky);
+    return saturate_round_u8((float)sum * scale);
+  }
+  // General path, float, in the table's order: per y entry the left-to-right sum over the x entries, then sum += beta * buf.
+  // (The first y entry assigns beta * buf; adding it to 0 gives the same float.)
+  const AreaCell cx = area_cell(sw, ax.scale, dx), cy = area_cell(sh, ay.scale, dy);
+  float sum = 0.f;
+  auto add_row = [&](int sy, float beta) {
+    const uint8_t* r = S + (size_t)sy * pitch;
+    float buf = 0.f;
+    if (cx.left) buf += (float)r[cx.s1 - 1] * cx.a_left;
+    for (int sx = cx.s1; sx < cx.s2; sx++) buf += (float)r[sx] * cx.a_mid;
+    if (cx.right) buf += (float)r[cx.s2] * cx.a_right;
+    sum += beta * buf;
+  };
+  if (cy.left) add_row(cy.s1 - 1, cy.a_left);
+  for (int sy = cy.s1; sy < cy.s2; sy++) add_row(sy, cy.a_mid);
+  if (cy.right) add_row(cy.s2, cy.a_right);
+  return saturate_round_u8(sum);
+}
+
+// A batch of rectangles of different sizes and modes: block = one 256-pixel tile of one record's window, tiles[blockIdx.x] =
+// (record, first pixel of the tile in the window's row-major order); thread = one window pixel, lanes along dx. The grid has
+// exactly as many blocks as tiles.
+__global__ __launch_bounds__(256) void k_info_render(const uint8_t* __restrict__ images, const InfoSlot* __restrict__ slots,
+                                                     const int2* __restrict__ tiles, int dw, int dh, uint8_t* __restrict__ out) {
+  const int2 tile = tiles[blockIdx.x];
+  const int p = tile.y + threadIdx.x;
+  if (p >= dw * dh) return;
+  const InfoSlot L = slots[tile.x];
+  const int dy = p / dw, dx = p - dy * dw;
+  out[(size_t)tile.x * dw * dh + p] = info_pixel(images + L.src, (size_t)L.pitch, L.w, L.h, dw, dh, L.mode, dx, dy);
+}
+
+// Limits of the -info mode: image and rectangle sides 1..8192, window sides 1..4096 (a window has at most 2^24 pixels and
+// 65536 tiles; every index product fits an int32).
+constexpr int INFO_SIDE_MAX = 8192;
+
+// The InfoMode of an sw x sh rectangle for a dw x dh window, or -1 with *why set.
+static int info_mode(int sw, int sh, int dw, int dh, const char** why) {
+  if (sw == dw && sh == dh) return INFO_COPY;
+  if (!(sw >= dw && sh >= dh)) return INFO_LINEAR;
+  const AreaAxis ax = area_axis(sw, dw), ay = area_axis(sh, dh);
+  if (!(ax.integer && ay.integer)) return INFO_AREA;
+  // the fast path sums a block into an int: the reference's sum would overflow from iscale_x * iscale_y * 255 = 2^31 on
+  if ((int64_t)ax.iscale * ay.iscale * 255 >= ((int64_t)1 << 31)) {
+    *why = "the integer-ratio block sum passes 2^31";
+    return -1;
+  }
+  // an integer scale of sides this small means an exact multiple; the kernel's block reads rely on it
+  if ((int64_t)ax.iscale * dw != sw || (int64_t)ay.iscale * dh != sh) {
+    *why = "integer ratio without an exact multiple";
+    return -1;
+  }
+  return INFO_AREA_FAST;
+}
+
+static thread_local double g_info_ms[3] = {0.0, 0.0, 0.0};  // upload, kernel, copy back of the thread's last call
+
 }  // namespace ccamd
 
 using namespace ccamd;
@@ -850,6 +955,151 @@ cc_status cc_warp_perspective_u8(int device, const uint8_t* src, int sw, int sh,
   CC_HIP(hipMemcpy2DAsync(dst, dstride, d_dst.p, dw, dw, dh, hipMemcpyDeviceToHost, own.s));
   CC_HIP(hipStreamSynchronize(own.s));  // c and spans are host memory of this frame: nothing outlives the call
   return CC_OK;
+}
+
+cc_status cc_area_tab(int ssize, int dsize, double* scale, int32_t* iscale, int32_t* is_integer, int32_t* dst_index, int32_t* src_index,
+                      float* alpha, int capacity, int32_t* n_entries) {
+  // an area resize shrinks or keeps: 1 <= dsize <= ssize <= 8192
+  if (ssize < 1 || dsize < 1 || dsize > ssize || ssize > INFO_SIDE_MAX || capacity < 0 || !n_entries ||
+      (capacity && (!dst_index || !src_index || !alpha)))
+    return set_error(CC_ERR_INVALID_ARG, "cc_area_tab: bad argument (1 <= dsize <= ssize <= %d)", INFO_SIDE_MAX);
+  const AreaAxis a = area_axis(ssize, dsize);
+  if (scale) *scale = a.scale;
+  if (iscale) *iscale = a.iscale;
+  if (is_integer) *is_integer = a.integer ? 1 : 0;
+  int k = 0;
+  auto emit = [&](int d, int s, float w) {
+    if (k < capacity) dst_index[k] = d, src_index[k] = s, alpha[k] = w;
+    k++;
+  };
+  for (int d = 0; d < dsize; d++) {
+    const AreaCell c = area_cell(ssize, a.scale, d);
+    if (c.left) emit(d, c.s1 - 1, c.a_left);
+    for (int s = c.s1; s < c.s2; s++) emit(d, s, c.a_mid);
+    if (c.right) emit(d, c.s2, c.a_right);
+  }
+  *n_entries = k;
+  if (k > capacity) return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_area_tab: %d entries, room for %d", k, capacity);
+  return CC_OK;
+}
+
+cc_status cc_samples_from_info(int device, const uint8_t* const* images, const int32_t* widths, const int32_t* heights,
+                               const size_t* strides, int n_images, const cc_info_record* records, int n, int win_w, int win_h,
+                               int max_batch, uint8_t* out_host, void* out_device) {
+  g_info_ms[0] = g_info_ms[1] = g_info_ms[2] = 0.0;
+  if (n < 0 || n_images < 0 || (n_images && (!images || !widths || !heights || !strides)) || (n && (!records || (!out_host && !out_device))))
+    return set_error(CC_ERR_INVALID_ARG, "cc_samples_from_info: bad argument");
+  // window sides 1..4096
+  if (win_w < 1 || win_h < 1 || win_w > SAMPLE_WIN_MAX || win_h > SAMPLE_WIN_MAX)
+    return set_error(CC_ERR_INVALID_ARG, "cc_samples_from_info: window sides 1..%d", SAMPLE_WIN_MAX);
+  // image sides 1..8192, and with them a rectangle's
+  for (int i = 0; i < n_images; i++)
+    if (!images[i] || widths[i] < 1 || heights[i] < 1 || widths[i] > INFO_SIDE_MAX || heights[i] > INFO_SIDE_MAX || strides[i] < (size_t)widths[i])
+      return set_error(CC_ERR_INVALID_ARG, "cc_samples_from_info: image %d: sides 1..%d, stride at least the width", i, INFO_SIDE_MAX);
+  std::vector<int32_t> modes((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const cc_info_record& R = records[i];
+    if (R.image < 0 || R.image >= n_images)
+      return set_error(CC_ERR_INVALID_ARG, "cc_samples_from_info: record %d: image %d of %d", i, R.image, n_images);
+    // the kernel reads rows y .. y + height - 1, columns x .. x + width - 1 of the image: all of them must be inside
+    const int iw = widths[R.image], ih = heights[R.image];
+    if (R.width < 1 || R.height < 1 || R.x < 0 || R.y < 0 || R.x > iw - R.width || R.y > ih - R.height)
+      return set_error(CC_ERR_INVALID_ARG, "cc_samples_from_info: record %d: rectangle %d x %d at (%d, %d) leaves its %d x %d image", i,
+                       R.width, R.height, R.x, R.y, iw, ih);
+    const char* why = nullptr;
+    modes[i] = info_mode(R.width, R.height, win_w, win_h, &why);
+    if (modes[i] < 0)
+      return set_error(CC_ERR_INVALID_ARG, "cc_samples_from_info: record %d: %d x %d to %d x %d: %s", i, R.width, R.height, win_w, win_h, why);
+  }
+  cc_status st = ensure_device(device);
+  if (st != CC_OK) return st;
+  if (n == 0) return CC_OK;
+  OwnStream own;
+  CC_HIP(own.create());
+  hipStream_t q = own.s;
+  OwnEvent ev[4];
+  for (OwnEvent& e : ev) CC_HIP(e.create());
+  // Batch: consecutive records are added while what the batch allocates (each image it names once, slot, tiles and, without
+  // a device output, the windows) stays within a quarter of the free memory, at most 2^20 records and 2^24 tiles (a window
+  // has at most 65536), and at most max_batch records when the caller gives one. One record always goes.
+  size_t free_b = 0, total_b = 0;
+  CC_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = free_b / 4, max_tiles = (size_t)1 << 24, max_records = (size_t)1 << 20;
+  const size_t area = (size_t)win_w * win_h, nt = (area + 255) / 256;
+  DevBuf<uint8_t> d_images, d_out;
+  DevBuf<InfoSlot> d_slots;
+  DevBuf<int2> d_tiles;
+  std::vector<InfoSlot> slots;
+  std::vector<int2> tiles;
+  std::vector<int64_t> where((size_t)n_images, -1);  // an image's offset in this batch's buffer
+  std::vector<int> used;
+  for (size_t first = 0; first < (size_t)n;) {
+    slots.clear();
+    tiles.clear();
+    for (int i : used) where[i] = -1;
+    used.clear();
+    size_t bytes = 0, image_bytes = 0;
+    while (first + slots.size() < (size_t)n) {
+      const size_t i = first + slots.size();
+      const cc_info_record& R = records[i];
+      const size_t img = where[R.image] < 0 ? (size_t)widths[R.image] * heights[R.image] : 0;
+      const size_t need = img + sizeof(InfoSlot) + nt * sizeof(int2) + (out_device ? 0 : area);
+      if (!slots.empty() && (bytes + need > budget || tiles.size() + nt > max_tiles || slots.size() >= max_records ||
+                             (max_batch > 0 && slots.size() >= (size_t)max_batch)))
+        break;
+      if (where[R.image] < 0) {
+        where[R.image] = (int64_t)image_bytes;
+        used.push_back(R.image);
+        image_bytes += img;
+      }
+      InfoSlot L;
+      L.pitch = widths[R.image];  // the device copy is dense
+      L.src = (size_t)where[R.image] + (size_t)R.y * L.pitch + R.x;
+      L.w = R.width, L.h = R.height, L.mode = modes[i];
+      for (size_t t = 0; t < nt; t++) tiles.push_back(make_int2((int)slots.size(), (int)(t * 256)));
+      slots.push_back(L);
+      bytes += need;
+    }
+    const size_t nb = slots.size();
+    CC_HIP(d_images.ensure(image_bytes));
+    if (!out_device) CC_HIP(d_out.ensure(nb * area));
+    uint8_t* base = out_device ? (uint8_t*)out_device + first * area : d_out.p;
+    CC_HIP(hipEventRecord(ev[0].e, q));
+    for (int i : used)
+      CC_HIP(hipMemcpy2DAsync(d_images.p + where[i], widths[i], images[i], strides[i], widths[i], heights[i], hipMemcpyHostToDevice, q));
+    CC_HIP(d_slots.upload(slots, q));
+    CC_HIP(d_tiles.upload(tiles, q));
+    CC_HIP(hipEventRecord(ev[1].e, q));
+    hipLaunchKernelGGL(k_info_render, dim3((unsigned)tiles.size()), dim3(256), 0, q, d_images.p, d_slots.p, d_tiles.p, win_w, win_h, base);
+    CC_HIP(hipGetLastError());
+    CC_HIP(hipEventRecord(ev[2].e, q));
+    if (out_host) CC_HIP(hipMemcpyAsync(out_host + first * area, base, nb * area, hipMemcpyDeviceToHost, q));
+    CC_HIP(hipEventRecord(ev[3].e, q));
+    CC_HIP(hipStreamSynchronize(q));  // slots and tiles are host memory of this frame, the device buffers are reused
+    for (int k = 0; k < 3; k++) {
+      float ms = 0.f;
+      CC_HIP(hipEventElapsedTime(&ms, ev[k].e, ev[k + 1].e));
+      g_info_ms[k] += (double)ms;
+    }
+    first += nb;
+  }
+  return CC_OK;
+}
+
+cc_status cc_samples_from_info_last_ms(double* upload_ms, double* kernel_ms, double* download_ms) {
+  if (upload_ms) *upload_ms = g_info_ms[0];
+  if (kernel_ms) *kernel_ms = g_info_ms[1];
+  if (download_ms) *download_ms = g_info_ms[2];
+  return CC_OK;
+}
+
+cc_status cc_resize_area_u8(int device, const uint8_t* src, int w, int h, size_t stride, uint8_t* dst, int dw, int dh) {
+  // INTER_AREA proper: the window is no larger than the source on either axis (cv::resize would interpolate otherwise)
+  if (!src || !dst || w < 1 || h < 1 || dw < 1 || dh < 1 || dw > w || dh > h)
+    return set_error(CC_ERR_INVALID_ARG, "cc_resize_area_u8: bad argument (1 <= dw <= w, 1 <= dh <= h)");
+  const int32_t iw = w, ih = h;
+  const cc_info_record whole = {0, 0, 0, w, h};
+  return cc_samples_from_info(device, &src, &iw, &ih, &stride, 1, &whole, 1, dw, dh, 0, dst, nullptr);
 }
 
 }  // extern "C"

@@ -191,6 +191,18 @@ def resize_linear_exact(img, dw, dh, device=0):
     return dst
 
 
+def resize_area(img, dw, dh, device=0):
+    """cv::resize INTER_AREA of a gray (h, w) uint8 image to dw x dh (cc_resize_area_u8: neither side may grow). Rows may be
+    strided (a view of a wider array): the stride is passed on as it is."""
+    img = np.asarray(img)
+    if img.ndim != 2 or img.dtype != np.uint8 or (img.shape[1] > 1 and img.strides[1] != 1) or img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img, np.uint8)
+    h, w = img.shape
+    dst = np.empty((max(dh, 0), max(dw, 0)), np.uint8)
+    L.check(L.lib().cc_resize_area_u8(device, _vp(img), w, h, img.strides[0], _vp(dst), dw, dh))
+    return dst
+
+
 class CascadeClassifier:
     """cv2.CascadeClassifier-shaped front end. load()/empty()/detectMultiScale() as the reference's tools call them."""
 

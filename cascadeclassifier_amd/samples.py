@@ -10,11 +10,18 @@ The tool's test mode (cvCreateTestSamples: one distorted copy pasted into a rand
 ground truth in an info file) is cc_testset_plan + cc_sampler_render_testset, create_test_samples here and
 
     python -m cascadeclassifier_amd.samples -img object.pgm -bg bg.txt -info out/info.dat [-maxscale 4]
+
+The tool's -info mode (cvCreateTrainingSamplesFromInfo: every rectangle an info file annotates, cut out of its image and
+resized to the window, INTER_AREA when it shrinks on both axes and INTER_LINEAR_EXACT otherwise) is scan_info +
+cc_samples_from_info, create_samples_from_info here and
+
+    python -m cascadeclassifier_amd.samples -info annotations.dat -vec positives.vec -w 24 -h 24
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import sys
 
 import numpy as np
@@ -293,6 +300,136 @@ def create_test_samples(info_path: str, image, backgrounds, num: int = 1000, w: 
     return [smp[0] for smp in samples], np.array([smp[1] for smp in samples], np.int32).reshape(-1, 4)
 
 
+def area_tab(ssize: int, dsize: int):
+    """Host only (cc_area_tab): one axis of cv::resize INTER_AREA from ssize to dsize pixels as (scale, iscale, integer,
+    dst_index, src_index, alpha): entry k adds alpha[k] * source[src_index[k]] to destination dst_index[k]."""
+    cap = 2 * max(int(ssize), 1)
+    di, si, al = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+    scale, iscale, integer, n = C.c_double(0.0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    L.check(L.lib().cc_area_tab(ssize, dsize, C.byref(scale), C.byref(iscale), C.byref(integer), _vp(di), _vp(si), _vp(al), cap,
+                                C.byref(n)))
+    return scale.value, iscale.value, bool(integer.value), di[:n.value], si[:n.value], al[:n.value]
+
+
+class _Scanner:
+    """The token stream fscanf sees: "%s" takes a run of non-blank characters, "%d" an optional sign and digits from the
+    front of one and leaves the rest (and anything that does not start like a number) where it is."""
+    _INT = re.compile(r"[+-]?\d+")
+
+    def __init__(self, text: str):
+        self.tok, self.pos = text.split(), 0
+
+    def word(self):
+        if self.pos >= len(self.tok):
+            return None
+        self.pos += 1
+        return self.tok[self.pos - 1]
+
+    def integer(self):
+        if self.pos >= len(self.tok):
+            return None
+        t = self.tok[self.pos]
+        m = self._INT.match(t)
+        if not m:
+            return None
+        if m.end() < len(t):
+            self.tok[self.pos] = t[m.end():]
+        else:
+            self.pos += 1
+        return int(m.group())
+
+
+def scan_info(info_path: str, num: int = 1000):
+    """The fscanf walk of cvCreateTrainingSamplesFromInfo (utility.cpp:1189-1226) over an info file, without its pixels:
+    (entries, bad). entries: (name, [(x, y, w, h), ...]) per entry the walk visits, names as written, `num` rectangles in
+    all at most (a count that runs past num is cut). bad: None, or the 1-based number of the entry whose rectangles did
+    not parse (end of file inside an entry included); that entry's earlier rectangles are kept and the walk ends there, as
+    the tool's does. Unlike read_info this is a token stream: white space of any kind separates, lines mean nothing.
+    Where the tool's loop would spin for ever -- the file ends before num rectangles -- the walk ends."""
+    sc = _Scanner(open(info_path).read())
+    entries, total, entry = [], 0, 1
+    while total < num:
+        name = sc.word()
+        if name is None:  # end of file: the tool reads count = 0 again and again
+            break
+        count = sc.integer()
+        rects = []
+        bad = False
+        for _ in range(count or 0):  # a name without a count has none, as fscanf(...) != 2 leaves count at 0
+            if total >= num:
+                break
+            r = [sc.integer() for _ in range(4)]
+            if None in r:  # fscanf stops at the first field that fails
+                bad = True
+                break
+            rects.append(tuple(r))
+            total += 1
+        entries.append((name, rects))
+        if bad:
+            return entries, entry
+        entry += 1
+    return entries, None
+
+
+def samples_from_info(images, records, win, device: int = 0, max_batch: int = 0, device_out=None, host: bool = True):
+    """cc_samples_from_info: records (image, x, y, width, height) cut out of `images` (gray (h, w) uint8 arrays; rows may be
+    strided) and resized to the window win = (w, h): INTER_AREA when the rectangle is at least the window on both axes,
+    else INTER_LINEAR_EXACT, the rectangle alone being the source. Returns (n, h, w) uint8, or None when host is False.
+    device_out: a device pointer that receives the same (n, h, w) stack. max_batch > 0 caps the records per launch."""
+    w, h = win
+    imgs = []
+    for a in images:
+        a = np.asarray(a)
+        if a.ndim != 2 or a.dtype != np.uint8:
+            raise ValueError("samples_from_info: gray images (h, w) of uint8 are required")
+        if a.shape[1] > 1 and a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+            a = np.ascontiguousarray(a)
+        imgs.append(a)
+    recs = np.ascontiguousarray(records, np.int32).reshape(-1, 5)
+    n = len(recs)
+    ptrs = (C.c_void_p * max(len(imgs), 1))(*[a.ctypes.data for a in imgs])
+    ws = np.array([a.shape[1] for a in imgs], np.int32)
+    hs = np.array([a.shape[0] for a in imgs], np.int32)
+    strides = np.array([a.strides[0] for a in imgs], np.uintp)
+    out = np.empty((n, h, w), np.uint8) if host and w > 0 and h > 0 else None
+    L.check(L.lib().cc_samples_from_info(device, C.cast(ptrs, C.c_void_p), _vp(ws), _vp(hs), _vp(strides), len(imgs), _vp(recs), n, w, h,
+                                         max_batch, _vp(out) if out is not None else None,
+                                         C.c_void_p(device_out) if device_out is not None else None))
+    return out
+
+
+def create_samples_from_info(vec_path: str, info_path: str, num: int = 1000, w: int = 24, h: int = 24, device: int = 0,
+                             max_batch: int = 0) -> np.ndarray:
+    """cvCreateTrainingSamplesFromInfo: the first `num` annotated rectangles of info_path, each cut out of its image (.pgm or
+    .npy, named relative to the info file) and resized to w x h, written to vec_path and returned as (n, h, w) uint8.
+    A malformed entry ends the run as in the tool: what precedes it is kept and "<info>(<entry>) : parse error" goes to
+    stderr. Three deliberate differences: the run ends at the end of the file (the tool's loop spins there for ever); the
+    .vec header holds the number of samples written (the tool writes num whatever it made); an image that is missing or
+    unreadable raises, naming the file (the tool asserts). An image is read only when a rectangle needs it."""
+    entries, bad = scan_info(info_path, num)
+    base = os.path.dirname(info_path)
+    index, images, records = {}, [], []
+    for name, rects in entries:
+        if not rects:
+            continue
+        path = os.path.join(base, name)
+        if path not in index:
+            try:
+                img = read_gray(path)
+            except Exception as e:
+                raise ValueError(f"{info_path}: image {path} cannot be read: {e}") from e
+            index[path] = len(images)
+            images.append(img)
+        records += [(index[path],) + r for r in rects]
+    if bad is not None:
+        sys.stderr.write(f"{info_path}({bad}) : parse error")
+    out = samples_from_info(images, np.array(records, np.int64).reshape(-1, 5).clip(-2 ** 31, 2 ** 31 - 1), (w, h), device, max_batch)
+    if os.path.dirname(vec_path):
+        os.makedirs(os.path.dirname(vec_path), exist_ok=True)  # icvMkDir
+    vec_write(vec_path, out, w, h)
+    return out
+
+
 def warp_perspective(src, dst, quad, device: int = 0) -> np.ndarray:
     """cvWarpPerspective of the tool: src mapped into the quadrangle quad (4 x 2, x y) of dst, in place; returns dst."""
     src = np.ascontiguousarray(src, np.uint8)
@@ -338,14 +475,16 @@ def read_background_list(path: str):
 
 
 def parse_args(argv=None):
-    """(mode, options) of a command line: the mode is chosen as createsamples.cpp:184-198 does -- "training" (-img and
-    -vec: a .vec of distorted copies) before "test" (-img, -bg and -info: test images and their info file)."""
+    """(mode, options) of a command line: the mode is chosen as createsamples.cpp:184-212 does -- "training" (-img and
+    -vec: a .vec of distorted copies) before "test" (-img, -bg and -info: test images and their info file) before
+    "from_info" (-info and -vec without -img: a .vec of annotated rectangles)."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m cascadeclassifier_amd.samples", add_help=False,
-                                 description="createsamples: a .vec of distorted copies of one image (-img -vec), or test "
-                                             "images with one copy pasted into each background (-img -bg -info)")
+                                 description="createsamples: a .vec of distorted copies of one image (-img -vec), test "
+                                             "images with one copy pasted into each background (-img -bg -info), or a .vec "
+                                             "of the rectangles an info file annotates (-info -vec)")
     ap.add_argument("--help", action="help")
-    ap.add_argument("-img", required=True)
+    ap.add_argument("-img")
     ap.add_argument("-vec")
     ap.add_argument("-info")
     ap.add_argument("-maxscale", type=float, default=-1.0)
@@ -363,16 +502,23 @@ def parse_args(argv=None):
     ap.add_argument("-h", type=int, default=24)
     ap.add_argument("-rngseed", type=int, default=12345)
     a = ap.parse_args(argv)
-    if a.vec:
+    if a.img and a.vec:
         return "training", a
-    if a.bg and a.info:
+    if a.img and a.bg and a.info:
         return "test", a
-    ap.error("nothing to do: give -vec (training samples), or -bg and -info (test images)")
+    if a.info and a.vec:
+        return "from_info", a
+    ap.error("nothing to do: give -img and -vec (training samples), -img, -bg and -info (test images), or -info and -vec "
+             "(samples from annotated images)")
 
 
 def main(argv=None) -> int:
     mode, a = parse_args(argv)
     invert = RANDOM_INVERT if a.randinv else 1 if a.inv else 0
+    if mode == "from_info":
+        out = create_samples_from_info(a.vec, a.info, a.num, a.w, a.h)
+        print(f"{a.vec}: {len(out)} samples of {a.w} x {a.h}")
+        return 0
     if mode == "test":
         images, _ = create_test_samples(a.info, read_gray(a.img), read_background_list(a.bg), a.num, a.w, a.h, maxscale=a.maxscale,
                                         bgcolor=a.bgcolor, bgthreshold=a.bgthresh, invert=invert, maxintensitydev=a.maxidev,

@@ -350,6 +350,11 @@ CC_API cc_status cc_integral_u8(int device, const uint8_t* img, int width, int h
                                 int32_t* sqsum, int32_t* tilted);
 CC_API cc_status cc_resize_linear_exact_u8(int device, const uint8_t* src, int sw, int sh, size_t sstride, uint8_t* dst,
                                            int dw, int dh, size_t dstride);
+/* cv::resize INTER_AREA of one 8-bit single-channel HOST image to dw x dh (dst: dh rows of dw bytes, dense), with the kernel
+ * and the arithmetic of the -info mode (section 8: same-size copy, the integer-ratio fast path, the general float path).
+ * 1 <= dw <= w <= 8192, 1 <= dh <= h <= 8192, dw and dh at most 4096; an integer ratio whose block sum could pass 2^31 is
+ * CC_ERR_INVALID_ARG. */
+CC_API cc_status cc_resize_area_u8(int device, const uint8_t* src, int w, int h, size_t stride, uint8_t* dst, int dw, int dh);
 /* cvWarpPerspective of the sample tool (tools/createsamples/utility.cpp:225-417) on one HOST image: the source is mapped
  * into the quadrangle quad[4][2] (x, y per vertex, in order) of the caller-initialised dst; pixels outside the quadrangle's
  * row spans keep their value. Coefficients and spans come from the host arithmetic of cc_sample_plan (section 8), the pixels
@@ -865,6 +870,9 @@ CC_API cc_status cc_gather_fetch(const cc_comm* c, cc_rect* out, int cap_rects, 
  *    the warp's pixels (:351-387), GaussianBlur, the two resizes and the blend (:650-671) -> cc_sampler_render (device).
  *    The random numbers are cv::RNG's (seed 12345 in the tool, createsamples.cpp:88,158): with the tool's image and
  *    options the samples are the tool's, byte for byte.
+ *    The tool's other two modes follow below: test images with their info file (cc_testset_plan,
+ *    cc_sampler_render_testset) and positives cut from annotated images (-info to .vec: cc_area_tab, cc_samples_from_info;
+ *    cc_resize_area_u8 of section 3 is its resize alone).
  * ============================================================================================ */
 #define CC_SAMPLE_RANDOM_INVERT 0x7FFFFFFF /* CV_RANDOM_INVERT */
 typedef struct cc_sample_params {
@@ -971,6 +979,45 @@ CC_API cc_status cc_testset_plan(int src_w, int src_h, int win_w, int win_h, con
 CC_API cc_status cc_sampler_render_testset(cc_sampler* s, const cc_testset_item* items, const cc_sample_record* records,
                                            const int32_t* spans, int n, int max_batch, uint8_t* const* out_host, void* out_device,
                                            size_t frame_stride);
+
+/* The -info mode of the tool: positives from annotated images. Replaces cvCreateTrainingSamplesFromInfo
+ * (tools/createsamples/utility.cpp:1125-1232; chosen in createsamples.cpp:201-208 by -info and -vec without -img): every
+ * annotated rectangle is cut out of its image and resized to the window,
+ *   resize(src(Rect(x, y, width, height)), sample, Size(w, h), 0, 0, width >= w && height >= h ? INTER_AREA : INTER_LINEAR_EXACT).
+ * The fscanf walk over the info file and the .vec are host file IO (samples.py); the pixels -> cc_samples_from_info (device).
+ * The source of a resize is the rectangle alone (a Mat view): the bilinear branch replicates the border at the rectangle's
+ * edge. The INTER_AREA arithmetic is OpenCV's (4.6.0 resize.cpp), restated in DESIGN.md 4.15 from knowledge of that code and
+ * not pinned against OpenCV's bytes: same size is a copy; integer ratios on both axes sum the block in an int (2 x 2:
+ * (a + b + c + d + 2) >> 2, else cvRound((float)sum * (1.f / area))); every other case weighs whole and partial source pixels
+ * per axis with the table cc_area_tab returns, in float, in the table's order. */
+typedef struct cc_info_record {
+  int32_t image;               /* index into the image list */
+  int32_t x, y, width, height; /* the annotated rectangle in that image */
+} cc_info_record;
+
+/* Host only, no device: one axis of INTER_AREA from ssize to dsize pixels, 1 <= dsize <= ssize <= 8192.
+ * *scale = 1 / ((double)dsize / ssize), *iscale = (int)*scale, *is_integer = |*scale - *iscale| < DBL_EPSILON (both axes
+ * integer: the fast path, which does not use the table). The table is computeResizeAreaTab's: entry k adds
+ * alpha[k] * source[src_index[k]] to destination dst_index[k]; at most 2 * ssize entries. Any output but n_entries may be
+ * NULL (the three arrays only with capacity 0). More than `capacity` entries: CC_ERR_BUFFER_TOO_SMALL with *n_entries set. */
+CC_API cc_status cc_area_tab(int ssize, int dsize, double* scale, int32_t* iscale, int32_t* is_integer, int32_t* dst_index,
+                             int32_t* src_index, float* alpha, int capacity, int32_t* n_entries);
+
+/* Resizes n annotated rectangles to win_w x win_h windows. images / widths / heights / strides: n_images HOST images (row
+ * stride in bytes). Output: out_host (n * win_h * win_w bytes, host), out_device (as many bytes of device memory), or both;
+ * at least one when n > 0. One grid per batch covers rectangles of different sizes and both branches (a table of 256-pixel
+ * tiles, one thread per window pixel). A batch is a run of consecutive records whose images, each uploaded once per batch,
+ * fit a quarter of the free device memory, at most max_batch records when max_batch > 0.
+ * Limits: image (and so rectangle) sides 1..8192, window sides 1..4096. CC_ERR_INVALID_ARG, naming the record: an image
+ * index outside the list; a rectangle with a side under 1 or not inside its image (the tool's src(Rect) asserts); integer
+ * ratios with iscale_x * iscale_y * 255 >= 2^31 (the reference's int sum would overflow). All of this is checked before
+ * the device is touched; nothing is written then. */
+CC_API cc_status cc_samples_from_info(int device, const uint8_t* const* images, const int32_t* widths, const int32_t* heights,
+                                      const size_t* strides, int n_images, const cc_info_record* records, int n, int win_w,
+                                      int win_h, int max_batch, uint8_t* out_host, void* out_device);
+/* Stream time of the calling thread's last cc_samples_from_info in ms, summed over its batches: image and table upload, the
+ * kernel, the copy back to out_host. Any pointer may be NULL. */
+CC_API cc_status cc_samples_from_info_last_ms(double* upload_ms, double* kernel_ms, double* download_ms);
 
 #ifdef __cplusplus
 }
