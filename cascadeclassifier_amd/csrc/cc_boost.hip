@@ -505,16 +505,12 @@ struct cc_boost {
   DevBuf<char> cub_temp, recs;  // recs: the root's NodeRec, SplitRec, TailRec
   size_t cub_w_bytes = 0, cub_f_bytes = 0;
   PinnedBuf pin, pin_value;
-  hipEvent_t ev[12] = {};
+  OwnEvent ev[10];  // marks between the parts of a round
   double last_ms[8] = {};  // device time of the last round's parts (cc_boost_last_round_ms)
   NodeRec* d_root() { return reinterpret_cast<NodeRec*>(recs.p); }
   SplitRec* d_split() { return reinterpret_cast<SplitRec*>(recs.p + 64); }
   TailRec* d_tail() { return reinterpret_cast<TailRec*>(recs.p + 192); }
   size_t max_nodes() const { return 2 * (size_t)n + 1; }  // every leaf holds a sample: at most 2 n - 1 nodes
-  ~cc_boost() {
-    for (hipEvent_t& x : ev)
-      if (x) (void)hipEventDestroy(x);
-  }
 };
 static_assert(sizeof(NodeRec) <= 64 &&sizeof(SplitRec) <= 128 && sizeof(TailRec) <= 64, "record slots");
 
@@ -558,7 +554,7 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
   };
   auto span = [&](int a, int c) {
     float ms = 0;
-    return hipEventElapsedTime(&ms, b->ev[a], b->ev[c]) == hipSuccess ? (double)ms : 0.0;
+    return hipEventElapsedTime(&ms, b->ev[a].e, b->ev[c].e) == hipSuccess ? (double)ms : 0.0;
   };
 
   // 1. the root: node numbers, node table and calc_node_value
@@ -566,11 +562,11 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
   const int form8 = form == TABLE_LDS8 ? 1 : 0;
   CC_HIP(e->d_split_tab.ensure((size_t)n * 2));
   const AbsentEntry absent = b->categorical ? ABSENT_CATEGORICAL : ABSENT_ORDERED;
-  (void)hipEventRecord(b->ev[0], st);
+  (void)hipEventRecord(b->ev[0].e, st);
   hipLaunchKernelGGL(b->classifier ? k_boost_root<true> : k_boost_root<false>, dim3(1), dim3(BOOST_THREADS), 0, st, n, b->w.p, b->mask.p, b->y.p, form8,
                      absent, e->d_split_tab.p, b->d_root());
   CC_HIP(hipGetLastError());
-  (void)hipEventRecord(b->ev[1], st);
+  (void)hipEventRecord(b->ev[1].e, st);
   CC_HIP(hipMemcpyAsync(pin, b->d_root(), sizeof(NodeRec), hipMemcpyDeviceToHost, st));
   CC_HIP(hipStreamSynchronize(st));
   std::vector<TreeNode> tree(1);
@@ -584,18 +580,17 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
   // 3. - 5. CvDTree::try_split_node for every node that is not a leaf; siblings are independent, left first as the reference
   const int mode = !b->classifier ? 0 : (b->gini ? 1 : 2);
   const int F = e->presort_f1 - e->presort_f0;
-  const bool idx16 = n <= 65536;
   std::vector<int> todo(1, 0);
   while (!todo.empty()) {
     const int k = todo.back();
     todo.pop_back();
     if (k != 0) {
       if (is_leaf(tree[(size_t)k])) continue;
-      (void)hipEventRecord(b->ev[0], st);
+      (void)hipEventRecord(b->ev[0].e, st);
       hipLaunchKernelGGL(b->classifier ? k_boost_table<true> : k_boost_table<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, b->w.p, b->y.p,
                          b->node_dir.p, k, form8, absent, e->d_split_tab.p);
       CC_HIP(hipGetLastError());
-      (void)hipEventRecord(b->ev[1], st);
+      (void)hipEventRecord(b->ev[1].e, st);
     }
     const int left_id = (int)tree.size();
     if ((size_t)left_id + 2 > b->max_nodes()) return set_error(CC_ERR_HIP, "cc_boost_round: the tree outgrew its %d samples", n);
@@ -607,17 +602,15 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
       if (cc_status s = split_launch_ordered(e, mode, form, w0, w1, tree[(size_t)k].value * w0, true); s != CC_OK) return s;
       const size_t fpad = ((size_t)F + 63) / 64 * 64;
       const OrdResult dev(e->d_split_out.p, fpad);
-      (void)hipEventRecord(b->ev[2], st);
+      (void)hipEventRecord(b->ev[2].e, st);
       hipLaunchKernelGGL(k_boost_argmax, dim3(1), dim3(1024), 0, st, dev.best_val, dev.best_i, dev.best_vl, dev.best_vr, F, b->d_split());
-      (void)hipEventRecord(b->ev[3], st);
+      (void)hipEventRecord(b->ev[3].e, st);
       // 4. directions and the predict rule
-      if (idx16)
-        hipLaunchKernelGGL(k_boost_apply_ord<uint16_t>, dim3(1), dim3(1024), 0, st, e->d_sorted_val.p, e->d_sorted_idx16.p, n, e->presort_resident,
-                           e->d_win_val.p, reinterpret_cast<const uint16_t*>(e->d_win_idx.p), b->mask.p, b->d_split(), k, left_id, b->node_dir.p,
-                           b->node_pred.p);
-      else
-        hipLaunchKernelGGL(k_boost_apply_ord<int32_t>, dim3(1), dim3(1024), 0, st, e->d_sorted_val.p, e->d_sorted_idx32.p, n, e->presort_resident,
-                           e->d_win_val.p, e->d_win_idx.p, b->mask.p, b->d_split(), k, left_id, b->node_dir.p, b->node_pred.p);
+      with_index_type(wide_index((size_t)n), [&](auto ti) {
+        using TI = decltype(ti);
+        hipLaunchKernelGGL(k_boost_apply_ord<TI>, dim3(1), dim3(1024), 0, st, e->head.val.p, static_cast<const TI*>(e->head.idx()), n, e->presort_resident,
+                           e->d_win_val.p, reinterpret_cast<const TI*>(e->d_win_idx.p), b->mask.p, b->d_split(), k, left_id, b->node_dir.p, b->node_pred.p);
+      });
       CC_HIP(hipGetLastError());
     } else {
       cc_split sp;
@@ -634,19 +627,19 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
       std::memcpy(nd.subset, sp.subset, sizeof(sp.subset));
       Subset subset;
       std::memcpy(subset.w, sp.subset, sizeof(sp.subset));
-      (void)hipEventRecord(b->ev[3], st);
+      (void)hipEventRecord(b->ev[3].e, st);
       hipLaunchKernelGGL(k_boost_apply_cat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, e->d_codes.p + (size_t)(sp.var_idx - e->presort_f0) * n, n,
                          b->mask.p, subset, k, left_id, b->node_dir.p, b->node_pred.p);
       CC_HIP(hipGetLastError());
     }
-    (void)hipEventRecord(b->ev[4], st);
+    (void)hipEventRecord(b->ev[4].e, st);
     // 5. calc_node_value of the children
     // children at the depth limit are leaves whatever their risk
     const bool risk = !b->classifier && tree[(size_t)k].depth + 1 < b->max_depth;
     hipLaunchKernelGGL((b->classifier ? k_boost_children<true, false> : risk ? k_boost_children<false, true> : k_boost_children<false, false>), dim3(1),
                        dim3(BOOST_THREADS), 0, st, n, b->w.p, b->y.p, b->node_dir.p, left_id, b->categorical ? 0 : 1, b->d_split());
     CC_HIP(hipGetLastError());
-    (void)hipEventRecord(b->ev[5], st);
+    (void)hipEventRecord(b->ev[5].e, st);
     CC_HIP(hipMemcpyAsync(pin, b->d_split(), sizeof(SplitRec), hipMemcpyDeviceToHost, st));
     CC_HIP(hipStreamSynchronize(st));
     SplitRec sr;
@@ -705,7 +698,7 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
   U.scale_c = 1.0;
   U.scale1 = 1.0;
   U.tail = b->d_tail();
-  (void)hipEventRecord(b->ev[6], st);
+  (void)hipEventRecord(b->ev[6].e, st);
   if (b->p.boost_type != 0) {
     hipLaunchKernelGGL(k_boost_update_exp, dim3(1), dim3(BOOST_THREADS), 0, st, U);
     CC_HIP(hipGetLastError());
@@ -725,7 +718,7 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
     CC_HIP(hipGetLastError());
     for (TreeNode& nd : tree) nd.value *= Cc;  // tree->scale(C)
   }
-  (void)hipEventRecord(b->ev[7], st);
+  (void)hipEventRecord(b->ev[7].e, st);
   b->n_weak++;
   out->trained = 1;
   out->left_value = tree[(size_t)root.left].value;
@@ -742,7 +735,7 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
     hipLaunchKernelGGL(k_boost_trim, dim3(1), dim3(BOOST_THREADS), 0, st, n, b->sort_out.p, b->w.p, b->p.weight_trim_rate, b->mask.p, b->d_tail());
     CC_HIP(hipGetLastError());
   }
-  (void)hipEventRecord(b->ev[8], st);
+  (void)hipEventRecord(b->ev[8].e, st);
   // 9. isErrDesired
   const int threshold_idx = (int)((1.0F - b->p.min_hit_rate) * b->n_pos);
   if (b->n_pos > 0) {
@@ -752,7 +745,7 @@ static cc_status boost_round_locked(cc_boost* b, cc_weak* out) {
                        b->stage_sum.p, b->d_tail());
     CC_HIP(hipGetLastError());
   }
-  (void)hipEventRecord(b->ev[9], st);
+  (void)hipEventRecord(b->ev[9].e, st);
   CC_HIP(hipMemcpyAsync(pin, b->d_tail(), sizeof(TailRec), hipMemcpyDeviceToHost, st));
   CC_HIP(hipStreamSynchronize(st));
   TailRec tr;
@@ -846,7 +839,7 @@ cc_status cc_boost_create_depth(cc_evaluator* e, int n_samples, const cc_boost_p
   CC_HIP(b->recs.ensure(256));
   CC_HIP(b->pin.ensure(256));
   CC_HIP(hipMemsetAsync(b->recs.p, 0, 256, st));
-  for (hipEvent_t& x : b->ev) CC_HIP(hipEventCreate(&x));
+  for (OwnEvent& x : b->ev) CC_HIP(x.create());
   CC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, b->cub_w_bytes, static_cast<const unsigned long long*>(nullptr), static_cast<unsigned long long*>(nullptr), n,
                                            0, 64, st));
   CC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, b->cub_f_bytes, static_cast<const float*>(nullptr), static_cast<float*>(nullptr), std::max(1, b->n_pos), 0,

@@ -501,7 +501,7 @@ cc_status cc_eval_calc_batch_sorted(cc_evaluator* e, int fi_begin, int fi_end, i
   st = launch_batch(e, haar, haar ? (const void*)e->d_haar.p : (const void*)e->d_lbp.p, fi_begin, fi_end, nullptr, n_samples, e->d_out.p, 1, 0);
   if (st != CC_OK) return st;
   bool sorted_in_blocks = false;
-  if (n_samples <= sort_rows_block_limit()) {  // one block per row, the row in registers + LDS (cc_split.hip)
+  if (n_samples <= sort_rows_block_limit()) {  // one block per row, the row in registers + LDS (cc_presort.hip)
     if (sort_rows_block(e->d_out.p, nf, n_samples, keys_out.p, sorted.p, e->stream.s) == hipSuccess)
       sorted_in_blocks = true;
     else

@@ -1,6 +1,7 @@
 // Shared by the training-side translation units: cc_eval_store.hip (the evaluator and its samples), cc_eval_calc.hip (bulk
-// operator()), cc_eval_predict.hip (cascade predict), cc_hog.hip, cc_fill.hip, cc_split.hip (best-split search) and
-// cc_boost.hip: device-side feature records, the evaluator handle and the helpers more than one of them uses.
+// operator()), cc_eval_predict.hip (cascade predict), cc_hog.hip, cc_fill.hip, cc_presort.hip (the sorted tables and their
+// memory), cc_split.hip (best-split search) and cc_boost.hip: device-side feature records, the evaluator handle and the
+// helpers more than one of them uses.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,10 +33,6 @@ struct SampleTables {
 };
 
 cc_status eval_device(cc_evaluator* e);
-// Stable sort of every row of [rows][n] with the sample position as the value, one block per row (cc_split.hip); only for
-// n <= sort_rows_block_limit(): larger rows take the device-wide segmented sort at the call site.
-int sort_rows_block_limit();
-hipError_t sort_rows_block(const float* vals, int rows, int n, float* keys_out, int* idx_out, hipStream_t st);
 
 // ---- the evaluator and its samples (cc_eval_store.hip) -------------------------------------------
 // Sends the images queued by cc_eval_set_image to the device (runs of consecutive sample indices, one launch per run).
@@ -106,6 +103,61 @@ cc_status hog_predict(cc_evaluator* e, const SampleTables& t, const Cascade& m, 
 void hog_host_planes(const cc_evaluator* e, const uint8_t* px, std::vector<float>& planes);
 float hog_host_value(const cc_evaluator* e, const float* planes, int vi);
 
+// ---- the sorted tables (cc_presort.hip) as the split search and the booster read them -------------
+// Stable sort of every row of [rows][n] with the sample position as the value, one block per row; only for
+// n <= sort_rows_block_limit(): larger rows take the device-wide segmented sort at the call site.
+int sort_rows_block_limit();
+hipError_t sort_rows_block(const float* vals, int rows, int n, float* keys_out, int* idx_out, hipStream_t st);
+// Stable sort of the rows of e->d_out (one variable per row of N values, at most FB rows) into keys_out / sorted. Owns
+// the scratch of both sorts; that of the device-wide segmented sort is built when a pass first needs it.
+struct RowSorter {
+  cc_evaluator* e;
+  int N, FB;
+  DevBuf<float> keys_out;
+  DevBuf<int> sorted, iota, offsets;
+  DevBuf<char> temp;
+  bool segmented_ready = false;
+
+  RowSorter(cc_evaluator* e_, int N_, int FB_) : e(e_), N(N_), FB(FB_) {}
+  cc_status init();
+  cc_status prepare_segmented();
+  cc_status sort(int nf);
+  size_t bytes() const { return keys_out.n * 4 + sorted.n * 4 + iota.n * 4 + offsets.n * 4 + temp.n; }
+};
+// Zeroed ranks behind a table's last group, read ahead into without bounds checks: k_split_ord_lean up to 3 chunks of 16 ranks;
+// k_split_cat_sorted, on a trip that starts at rank r0 < n_pre, DEPTH chunks and the DEPTH after them (to r0 + 2 * DEPTH * UNROLL - 1).
+constexpr int SPLIT_TABLE_PAD_RANKS = 64;
+constexpr int SPLIT_CAT_UNROLL = 16;  // ranks per chunk: four 16-byte loads per lane
+constexpr int SPLIT_CAT_DEPTH = 6;    // chunks whose loads are in flight (one wavefront per SIMD: latency is hidden by distance, not by occupancy)
+constexpr int SPLIT_CAT_PAD_RANKS = (2 * SPLIT_CAT_DEPTH + 1) * SPLIT_CAT_UNROLL;
+// Sample numbers take 16 bits in a table while they fit, 32 otherwise.
+inline bool wide_index(size_t n_samples) { return n_samples > 65536; }
+// The one place where that width becomes the TI of a kernel launch: f gets a value of the sample-number type.
+template <class F>
+auto with_index_type(bool wide, F&& f) { return wide ? f(int32_t{}) : f(uint16_t{}); }
+// Sorted values and sample numbers of ordered variables, [group][rank][64], with SPLIT_TABLE_PAD_RANKS zeroed ranks behind
+// the last group: the resident tables of a presort and the chunk table of a streamed search.
+struct SortedTable {
+  DevBuf<float> val;
+  DevBuf<uint16_t> idx16;
+  DevBuf<int32_t> idx32;
+  bool wide = false;  // which of the two holds the sample numbers
+  static constexpr size_t PAD = (size_t)SPLIT_TABLE_PAD_RANKS * 64;
+  // Room for `entries` and the padding, which is zeroed on st. Grows only; the index buffer of the other width stays.
+  cc_status alloc(size_t entries, bool wide_, hipStream_t st);
+  cc_status zero_padding(size_t entries, hipStream_t st);  // behind `entries`, which may be fewer than alloc was given
+  // Gives back every buffer of more than `keep` elements and the index buffer of the other width; all of them by default.
+  void release(size_t keep = 0, bool wide_ = false);
+  size_t bytes() const { return val.n * 4 + idx16.n * 2 + idx32.n * 4; }
+  void* idx() const { return wide ? (void*)idx32.p : (void*)idx16.p; }  // the kernels read it as const TI*; k_interleave writes it
+};
+// One pass of a presort or of a streamed search, on e->stream: evaluates the ordered variables [fb, fb + nf) on rows.N stored samples
+// (launch_batch into e->d_out), sorts the rows and interleaves them into t from group group0 on. `mark`, if set, is called before
+// each of the three steps (the streamed search's profiling events). Caller holds e->mu.
+cc_status fill_sorted_table(cc_evaluator* e, RowSorter& rows, int fb, int nf, SortedTable& t, size_t group0, cc_status (*mark)(cc_evaluator*));
+// LBP's (code, sample)-sorted table is built by a presort and searched by a node, unless CCAMD_SPLIT_CAT_STREAM is set
+// (test hook: the streamed codes of k_split_cat only). Read at every call: tests compare the two paths.
+bool cat_sorted_table_enabled();
 
 // ---- the split search (cc_split.hip) as the booster (cc_boost.hip) enters it ---------------------
 // per stored sample: weight and (regression) response * weight or (classification) class; w < 0 marks "not in the node"
@@ -143,22 +195,6 @@ cc_status split_launch_ordered(cc_evaluator* e, int mode, TableForm form, double
                                bool track_winner = false);
 // Device time of the last split_launch_ordered (head and streamed chunks); the stream has been synchronised.
 double split_search_ms(cc_evaluator* e);
-// Stable sort of the rows of e->d_out (one variable per row of N values, at most FB rows) into keys_out / sorted. Owns
-// the scratch of both sorts; that of the device-wide segmented sort is built when a pass first needs it.
-struct RowSorter {
-  cc_evaluator* e;
-  int N, FB;
-  DevBuf<float> keys_out;
-  DevBuf<int> sorted, iota, offsets;
-  DevBuf<char> temp;
-  bool segmented_ready = false;
-
-  RowSorter(cc_evaluator* e_, int N_, int FB_) : e(e_), N(N_), FB(FB_) {}
-  cc_status init();
-  cc_status prepare_segmented();
-  cc_status sort(int nf);
-  size_t bytes() const { return keys_out.n * 4 + sorted.n * 4 + iota.n * 4 + offsets.n * 4 + temp.n; }
-};
 // The best variable so far of a streamed search: k_boost_argmax's (quality, variable), quality 0 and variable -1 for none.
 struct StreamBest {
   int var;
@@ -209,12 +245,10 @@ struct cc_evaluator {
   ccamd::PinnedBuf pin_in, pin_out;
   ccamd::OwnEvent ev_a, ev_b;
   double last_ms = 0;
-  // ---- split search (cc_split.hip) ----
+  // ---- presort (cc_presort.hip) and split search (cc_split.hip) ----
   // resident tables (cc_eval_presort): per group of 64 features the sorted values and sample indices, interleaved so that
   // lane = feature reads are coalesced: [group][rank][64]
-  ccamd::DevBuf<float> d_sorted_val;
-  ccamd::DevBuf<uint16_t> d_sorted_idx16;
-  ccamd::DevBuf<int32_t> d_sorted_idx32;
+  ccamd::SortedTable head;
   ccamd::DevBuf<uint8_t> d_codes;  // LBP: [feature][sample] codes
   int cat_sorted_n = 0;                  // samples per variable in d_cat_sorted (0: not built)
   ccamd::DevBuf<uint32_t> d_cat_sorted;  // LBP: (sample << 8 | code) in (code, sample) order, [group][rank][64]
@@ -227,10 +261,8 @@ struct cc_evaluator {
   // lives as long as the split: the row sorter (with d_out), one chunk table in the resident layout and the winner row.
   int presort_resident = 0, presort_chunk = 0;
   std::unique_ptr<ccamd::RowSorter> stream_rows;
-  ccamd::DevBuf<float> d_chunk_val;
-  ccamd::DevBuf<uint16_t> d_chunk_idx16;
-  ccamd::DevBuf<int32_t> d_chunk_idx32;
-  ccamd::DevBuf<float> d_win_val;    // the streamed winner's sorted values, [presort_n] ...
+  ccamd::SortedTable chunk;
+  ccamd::DevBuf<float> d_win_val;   // the streamed winner's sorted values, [presort_n] ...
   ccamd::DevBuf<int32_t> d_win_idx;  // ... and sample numbers, in the tables' width (16- or 32-bit)
   ccamd::DevBuf<ccamd::StreamBest> d_win_state;
   ccamd::OwnEvent ev_stream_a;  // start of a streamed search (launch_batch re-records ev_a for every chunk)

@@ -10,14 +10,11 @@
 // what the reference does beyond its caches (get_ord_var_data's uncached branch, o_cvcascadeboosttraindata.cpp:437-458):
 // evaluate, sort and search them again at every node, chunk by chunk through the same kernels.
 //
-// Data layout in HBM (cc_eval_presort): variables in groups of 64; per group the sorted values (f32) and sample indices
-// (u16 when n_samples <= 65 536, else i32) are interleaved [group][rank][64 lanes], so that lane = variable reads of
-// one rank are one coalesced 256-B / 128-B segment. LBP: category codes u8 [variable][sample].
+// The tables, their layout in HBM ([group][rank][64 lanes]: SortedTable) and their memory are cc_presort.hip's; the kernels
+// and the searches over them are here.
 //
 // The running sums of the reference are sequential double additions in sorted order; they are reproduced bit for bit by
 // giving each variable to one thread. Parallelism comes from the 10^5 variables, not from the scan.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
@@ -31,112 +28,6 @@
 #include "cc_eval_internal.h"
 
 namespace ccamd {
-
-// ------------------------------------------------------------------------------------------------
-// [rows][n] row-major (one sorted variable per row) -> [group][rank][64]
-// ------------------------------------------------------------------------------------------------
-template <class TI>
-__global__ __launch_bounds__(256) void k_interleave(const float* __restrict__ vals, const int* __restrict__ idx, int rows, int n,
-                                                    float* __restrict__ out_val, TI* __restrict__ out_idx, size_t group0) {
-  __shared__ float tv[64][65];
-  __shared__ int ti[64][65];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r0 = blockIdx.x * 64, g = blockIdx.y;
-  for (int j = wave; j < 64; j += 4) {
-    const int row = g * 64 + j;
-    float v = 0.f;
-    int s = 0;
-    if (row < rows && r0 + lane < n) {
-      v = vals[(size_t)row * n + r0 + lane];
-      s = idx[(size_t)row * n + r0 + lane];
-    }
-    tv[j][lane] = v;
-    ti[j][lane] = s;
-  }
-  __syncthreads();
-  for (int rr = wave; rr < 64; rr += 4) {
-    if (r0 + rr >= n) break;
-    const size_t o = ((group0 + g) * (size_t)n + r0 + rr) * 64 + lane;
-    out_val[o] = tv[lane][rr];
-    out_idx[o] = (TI)ti[lane][rr];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Stable sort of every row of [rows][n] (one variable per row) with the sample position as the value: one block of 1024
-// threads per row, the whole row in registers + LDS (hipcub::BlockRadixSort: LSD radix, stable -- equal values keep
-// increasing sample order, what std::stable_sort over (value, index) gives the reference,
-// o_cvcascadeboosttraindata.cpp:582-596). A row of a boosting stage (<= 24 576 samples) fits a CU's LDS, so it is read
-// once and written once: 8 B + 8 B per element instead of the ~70 B of a device-wide segmented radix sort's four passes.
-// ------------------------------------------------------------------------------------------------
-constexpr int SORT_THREADS = 1024;
-template <int ITEMS>
-struct RowSort {
-  using Sort = hipcub::BlockRadixSort<float, SORT_THREADS, ITEMS, unsigned short>;
-  static constexpr size_t lds_bytes = sizeof(typename Sort::TempStorage);
-};
-template <int ITEMS>
-__global__ __launch_bounds__(SORT_THREADS) void k_sort_rows_block(const float* __restrict__ vals, int rows, int n, float* __restrict__ keys_out,
-                                                                  int* __restrict__ idx_out) {
-  extern __shared__ __attribute__((aligned(16))) char sort_lds[];
-  using Sort = typename RowSort<ITEMS>::Sort;
-  typename Sort::TempStorage& temp = *reinterpret_cast<typename Sort::TempStorage*>(sort_lds);
-  const int row = blockIdx.x;
-  if (row >= rows) return;
-  const float* src = vals + (size_t)row * n;
-  float key[ITEMS];
-  unsigned short val[ITEMS];
-#pragma unroll
-  for (int i = 0; i < ITEMS; i++) {  // blocked arrangement: thread t owns positions t * ITEMS ..
-    const int pos = (int)threadIdx.x * ITEMS + i;
-    // padding = +inf: sorts behind every finite value. Precondition: no NaN among the values (a NaN's radix key sorts behind
-    // +inf and would push padding into the first n ranks). The evaluators cannot produce one: Haar values are finite sums
-    // divided by a positive norm factor or 0 when it is 0 (haarfeatures.h:108-112), LBP codes are 0..255.
-    key[i] = pos < n ? src[pos] : __int_as_float(0x7f800000);
-    val[i] = (unsigned short)pos;
-  }
-  Sort(temp).SortBlockedToStriped(key, val);
-#pragma unroll
-  for (int i = 0; i < ITEMS; i++) {  // striped: rank = i * 1024 + t, consecutive lanes write consecutive ranks
-    const int rank = i * SORT_THREADS + (int)threadIdx.x;
-    if (rank < n) {
-      keys_out[(size_t)row * n + rank] = key[i];
-      idx_out[(size_t)row * n + rank] = (int)val[i];
-    }
-  }
-}
-template <int ITEMS>
-static hipError_t launch_sort_rows_block(const float* vals, int rows, int n, float* keys_out, int* idx_out, hipStream_t st) {
-  constexpr size_t lds = RowSort<ITEMS>::lds_bytes;
-  if (lds > 64 * 1024) {
-    // The opt-in is per device and cheap: set it on every launch (a process-wide "done" flag, as round 3 kept, leaves the
-    // second device of a process without it, and is not thread-safe).
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sort_rows_block<ITEMS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((k_sort_rows_block<ITEMS>), dim3((unsigned)rows), dim3(SORT_THREADS), lds, st, vals, rows, n, keys_out, idx_out);
-  return hipGetLastError();
-}
-
-int sort_rows_block_limit() { return SORT_THREADS * 24; }
-hipError_t sort_rows_block(const float* vals, int rows, int n, float* keys_out, int* idx_out, hipStream_t st) {
-  if (n <= SORT_THREADS * 4) return launch_sort_rows_block<4>(vals, rows, n, keys_out, idx_out, st);
-  if (n <= SORT_THREADS * 8) return launch_sort_rows_block<8>(vals, rows, n, keys_out, idx_out, st);
-  if (n <= SORT_THREADS * 12) return launch_sort_rows_block<12>(vals, rows, n, keys_out, idx_out, st);
-  if (n <= SORT_THREADS * 16) return launch_sort_rows_block<16>(vals, rows, n, keys_out, idx_out, st);
-  if (n <= SORT_THREADS * 20) return launch_sort_rows_block<20>(vals, rows, n, keys_out, idx_out, st);
-  return launch_sort_rows_block<24>(vals, rows, n, keys_out, idx_out, st);
-}
-
-__global__ void k_codes_u8(const float* __restrict__ in, uint8_t* __restrict__ out, size_t total) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < total) out[i] = (uint8_t)(int)in[i];
-}
-
-__global__ void k_iota_rows2(int* __restrict__ v, size_t total, int n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < total) v[i] = (int)(i % (size_t)n);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Ordered variables: one thread per variable walks its sorted samples.
@@ -311,8 +202,6 @@ __global__ __launch_bounds__(1024) void k_split_ord(SplitOrdArgs A) {
 // Operation order of every sum and of the quality expression is the reference's (o_cvboostree.cpp:361-426, :192-238).
 // ------------------------------------------------------------------------------------------------
 constexpr int SPLIT_LEAN_WAVES = 12;  // wavefronts per block at most: 3 per SIMD, i.e. 168 VGPRs for the two chunks of table reads in flight
-constexpr int SPLIT_TABLE_PAD_RANKS = 64;  // the sorted tables are allocated (and zeroed) this many ranks beyond the last group's end:
-                                           // the lean kernel reads up to 3 chunks ahead without bounds checks
 template <int MODE, class TI>
 __global__ __launch_bounds__(64 * SPLIT_LEAN_WAVES) void k_split_ord_lean(SplitOrdArgs A) {
   extern __shared__ double l_tab[];
@@ -533,11 +422,6 @@ struct SplitCatArgs {
   int part_len;  // ... of this many ranks (a multiple of SPLIT_CAT_DEPTH * SPLIT_CAT_UNROLL)
   double* hist;
 };
-constexpr int SPLIT_CAT_UNROLL = 16;  // ranks per chunk: four 16-byte loads per lane
-constexpr int SPLIT_CAT_DEPTH = 6;    // chunks whose loads are in flight (one wavefront per SIMD: latency is hidden by distance, not by occupancy)
-// zeroed ranks behind the table: read-ahead without bounds checks. A trip that starts at rank r0 < n_pre consumes DEPTH chunks and
-// requests the DEPTH after them: ranks up to r0 + 2 * DEPTH * UNROLL - 1.
-constexpr int SPLIT_CAT_PAD_RANKS = (2 * SPLIT_CAT_DEPTH + 1) * SPLIT_CAT_UNROLL;
 // Table layout: [group][rank / 4][64 lanes][4 ranks] -- a lane reads four consecutive ranks of its variable with one 16-byte
 // load, a wavefront 1 KB per load instruction. Per-sample table: a sample outside the node is stored as +0.0 (8-byte form:
 // response * w, or w with the class in the sign bit) or {0, 0} (16-byte form), so it takes no test at all.
@@ -649,26 +533,6 @@ __global__ __launch_bounds__(256) void k_split_cat_sorted(SplitCatArgs A) {
   }
 }
 
-// [rows][n] sorted codes (as floats) and sample positions -> (sample << 8 | code) as [group][rank / 4][64][4]
-__global__ __launch_bounds__(256) void k_interleave_cat(const float* __restrict__ vals, const int* __restrict__ idx, int rows, int n,
-                                                        uint32_t* __restrict__ out, size_t group0) {
-  __shared__ uint32_t tv[64][65];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r0 = blockIdx.x * 64, g = blockIdx.y;
-  for (int j = wave; j < 64; j += 4) {
-    const int row = g * 64 + j;
-    uint32_t v = 0;
-    if (row < rows && r0 + lane < n) v = ((uint32_t)idx[(size_t)row * n + r0 + lane] << 8) | ((uint32_t)(int)vals[(size_t)row * n + r0 + lane] & 255u);
-    tv[j][lane] = v;
-  }
-  __syncthreads();
-  const size_t n4 = ((size_t)n + 3) >> 2;
-  for (int rr = wave; rr < 64; rr += 4) {  // [group][rank / 4][lane][rank % 4]; r0 is a multiple of 64
-    if (r0 + rr >= n) break;
-    out[(((group0 + g) * n4 + ((r0 + rr) >> 2)) * 64 + lane) * 4 + (rr & 3)] = tv[lane][rr];
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Streamed tail (cc_eval_presort_split): the best variable so far, kept on the device while the chunks of a node's search
 // go by. One block reduces the variables [v0, v1) just searched by k_boost_argmax's rule (cc_boost.hip; pick_winner's,
@@ -750,152 +614,6 @@ template <class Args>
 static cc_status launch(void (*kernel)(Args), unsigned blocks, unsigned threads, size_t lds, hipStream_t stream, const Args& args) {
   if (lds > 64 * 1024) CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, stream, args);
-  CC_HIP(hipGetLastError());
-  return CC_OK;
-}
-
-// RowSorter (cc_eval_internal.h): the scratch of one pass and its two sorts.
-cc_status RowSorter::init() {
-  CC_HIP(e->d_out.ensure((size_t)FB * N));
-  CC_HIP(keys_out.ensure((size_t)FB * N));
-  CC_HIP(sorted.ensure((size_t)FB * N));
-  return CC_OK;
-}
-cc_status RowSorter::prepare_segmented() {
-  if (segmented_ready) return CC_OK;
-  const size_t cap = (size_t)FB * N;
-  CC_HIP(iota.ensure(cap));
-  CC_HIP(offsets.ensure((size_t)FB + 1));
-  std::vector<int> off((size_t)FB + 1);
-  for (int i = 0; i <= FB; i++) off[(size_t)i] = (int)((size_t)i * N);
-  CC_HIP(hipMemcpyAsync(offsets.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, e->stream.s));
-  CC_HIP(hipStreamSynchronize(e->stream.s));  // `off` is pageable and about to go out of scope
-  hipLaunchKernelGGL(k_iota_rows2, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, e->stream.s, iota.p, cap, N);
-  segmented_ready = true;
-  return CC_OK;
-}
-cc_status RowSorter::sort(int nf) {
-  if (N <= sort_rows_block_limit()) {  // a row fits one block: sorted in LDS, read once and written once
-    // a part that refuses the ~100 KB LDS request (or the launch) takes the device-wide sort below instead of failing
-    if (sort_rows_block(e->d_out.p, nf, N, keys_out.p, sorted.p, e->stream.s) == hipSuccess) return CC_OK;
-    (void)hipGetLastError();
-  }
-  if (cc_status st = prepare_segmented(); st != CC_OK) return st;
-  const size_t total = (size_t)nf * N;
-  size_t temp_bytes = 0;
-  CC_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, temp_bytes, e->d_out.p, keys_out.p, iota.p, sorted.p, (int)total, nf, offsets.p,
-                                                     offsets.p + 1, 0, 32, e->stream.s));
-  CC_HIP(temp.ensure(std::max<size_t>(temp_bytes, 1)));
-  // stable: equal values keep increasing sample order
-  CC_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(temp.p, temp_bytes, e->d_out.p, keys_out.p, iota.p, sorted.p, (int)total, nf, offsets.p,
-                                                     offsets.p + 1, 0, 32, e->stream.s));
-  return CC_OK;
-}
-
-// ---- what a presort costs in device memory ---------------------------------------------------
-// variables per pass: whole groups of 64, at most 2^28 values per scratch array (cc_eval_presort_range's FB before its min with F)
-static size_t pass_vars_rule(size_t N) { return std::max<size_t>(64, (((size_t)1 << 28) / N) / 64 * 64); }
-struct PresortCosts {
-  using u128 = unsigned __int128;
-  u128 N, per;  // samples; bytes of a table entry: a float and a 16- or 32-bit sample number
-  explicit PresortCosts(size_t n) : N(n), per(4 + (n <= 65536 ? 2 : 4)) {}
-  // all tables resident plus one pass's scratch: presort_memory_check's sum for ordered variables
-  u128 resident(size_t F) const { return (u128)((F + 63) / 64 * 64) * N * per + (u128)std::min(F, pass_vars_rule((size_t)N)) * N * 16; }
-  // a head of R variables (a multiple of 64) with its read-ahead padding; nothing for no head
-  u128 head(size_t R) const { return R ? ((u128)R * N + (u128)SPLIT_TABLE_PAD_RANKS * 64) * per : 0; }
-  // one chunk of C variables: values, sorted keys, sorted indices and iota (16 B per value, as RowSorter), and the chunk
-  // table with its read-ahead padding
-  u128 chunk(size_t C) const { return (u128)C * N * 16 + ((u128)C * N + (u128)SPLIT_TABLE_PAD_RANKS * 64) * per; }
-  u128 winner() const { return N * 8; }  // the winner row: a float and up to 4 bytes of sample number per sample
-  u128 split(size_t R, size_t C) const { return head(R) + chunk(C) + winner(); }
-};
-// What the evaluator holds for sorted tables and, while a split presort lasts, for streaming.
-static size_t held_table_bytes(const cc_evaluator* e) {
-  size_t b = e->d_sorted_val.n * 4 + e->d_sorted_idx16.n * 2 + e->d_sorted_idx32.n * 4 + e->d_codes.n + e->d_cat_sorted.n * 4;
-  if (e->stream_rows)
-    b += e->d_out.n * 4 + e->stream_rows->bytes() + e->d_chunk_val.n * 4 + e->d_chunk_idx16.n * 2 + e->d_chunk_idx32.n * 4 + e->d_win_val.n * 4 +
-         e->d_win_idx.n * 4 + e->d_win_state.n * sizeof(StreamBest);
-  return b;
-}
-// A presort with every table resident streams nothing: the chunk scratch of an earlier split presort goes back.
-static void release_stream_scratch(cc_evaluator* e) {
-  e->stream_rows.reset();
-  e->d_chunk_val.release();
-  e->d_chunk_idx16.release();
-  e->d_chunk_idx32.release();
-  e->d_win_val.release();
-  e->d_win_idx.release();
-  e->presort_chunk = 0;
-}
-
-// The resident tables plus one pass's scratch have to fit what is free plus what the evaluator already holds for them
-// (the chunk scratch of an earlier split presort is given back first: this presort streams nothing).
-static cc_status presort_memory_check(cc_evaluator* e, bool haar, bool cat_table, int F, int N, int FB) {
-  release_stream_scratch(e);
-  const size_t groups = ((size_t)F + 63) / 64;
-  size_t free_b = 0, total_b = 0;
-  CC_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t resident = haar ? groups * 64 * (size_t)N * (4 + (N <= 65536 ? 2 : 4)) : (size_t)F * N + (cat_table ? groups * 64 * ((size_t)N + 3 + SPLIT_CAT_PAD_RANKS) * 4 : 0);
-  const size_t have = e->d_sorted_val.n * 4 + e->d_sorted_idx16.n * 2 + e->d_sorted_idx32.n * 4 + e->d_codes.n + e->d_cat_sorted.n * 4 + e->d_out.n * 4;
-  const size_t scratch = (size_t)FB * N * (haar || cat_table ? 16 : 4);
-  if (resident + scratch > free_b + have)
-    return set_error(CC_ERR_UNSUPPORTED, "cc_eval_presort: needs %.1f GB of device memory (%.1f GB free)",
-                     (double)(resident + scratch) / 1e9, (double)(free_b + have) / 1e9);
-  return CC_OK;
-}
-
-// Sorted values and sample numbers (TI: 16-bit while they fit) of the F ordered variables from fi_begin, [group][rank][64].
-template <class TI>
-static cc_status build_ordered_tables(cc_evaluator* e, RowSorter& rows, const void* feats, int fi_begin, int F, DevBuf<TI>& d_sorted_idx) {
-  const int N = rows.N, FB = rows.FB;
-  // tables + SPLIT_TABLE_PAD_RANKS ranks of zeroed padding behind the last group (read-ahead of k_split_ord_lean)
-  const size_t used = ((size_t)F + 63) / 64 * 64 * (size_t)N, pad = (size_t)SPLIT_TABLE_PAD_RANKS * 64;
-  CC_HIP(e->d_sorted_val.ensure(used + pad));
-  CC_HIP(hipMemsetAsync(e->d_sorted_val.p + used, 0, pad * sizeof(float), e->stream.s));
-  CC_HIP(d_sorted_idx.ensure(used + pad));
-  CC_HIP(hipMemsetAsync(d_sorted_idx.p + used, 0, pad * sizeof(TI), e->stream.s));
-  for (int f0 = 0; f0 < F; f0 += FB) {
-    const int f1 = std::min(F, f0 + FB), nf = f1 - f0;
-    if (cc_status st = launch_batch(e, true, feats, fi_begin + f0, fi_begin + f1, nullptr, N, e->d_out.p, 1, 0); st != CC_OK) return st;
-    if (cc_status st = rows.sort(nf); st != CC_OK) return st;
-    hipLaunchKernelGGL((k_interleave<TI>), dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream.s, rows.keys_out.p,
-                       rows.sorted.p, nf, N, e->d_sorted_val.p, d_sorted_idx.p, (size_t)f0 / 64);
-    CC_HIP(hipGetLastError());
-  }
-  return CC_OK;
-}
-
-// Ordered variables (Haar, HOG), every table resident.
-template <class TI>
-static cc_status presort_ordered(cc_evaluator* e, RowSorter& rows, const void* feats, int fi_begin, int F, DevBuf<TI>& d_sorted_idx) {
-  e->presort_resident = F;
-  return build_ordered_tables(e, rows, feats, fi_begin, F, d_sorted_idx);
-}
-
-// Categorical variables (LBP): the codes [variable][sample] and, with cat_table, the (code, sample)-sorted table beside them.
-static cc_status presort_categorical(cc_evaluator* e, RowSorter& rows, const void* feats, int fi_begin, int F, bool cat_table) {
-  const int N = rows.N, FB = rows.FB;
-  e->presort_resident = F;
-  CC_HIP(e->d_codes.ensure((size_t)F * N));
-  if (cat_table) {
-    // ranks padded to a multiple of 4 per group (the tail of a group's last quad is never summed: r >= n_pre); zeroed
-    // padding behind the last group for the read-ahead
-    const size_t used = ((size_t)F + 63) / 64 * 64 * ((((size_t)N + 3) >> 2) << 2), pad = (size_t)SPLIT_CAT_PAD_RANKS * 64;
-    CC_HIP(e->d_cat_sorted.ensure(used + pad));
-    CC_HIP(hipMemsetAsync(e->d_cat_sorted.p, 0, (used + pad) * sizeof(uint32_t), e->stream.s));
-  }
-  for (int f0 = 0; f0 < F; f0 += FB) {
-    const int f1 = std::min(F, f0 + FB), nf = f1 - f0;
-    const size_t total = (size_t)nf * N;
-    CC_HIP(e->d_out.ensure(total));
-    if (cc_status st = launch_batch(e, false, feats, fi_begin + f0, fi_begin + f1, nullptr, N, e->d_out.p, 1, 0); st != CC_OK) return st;
-    hipLaunchKernelGGL(k_codes_u8, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream.s, e->d_out.p,
-                       e->d_codes.p + (size_t)f0 * N, total);
-    if (!cat_table) continue;
-    if (cc_status st = rows.sort(nf); st != CC_OK) return st;
-    hipLaunchKernelGGL(k_interleave_cat, dim3((unsigned)((N + 63) / 64), (unsigned)((nf + 63) / 64)), dim3(256), 0, e->stream.s, rows.keys_out.p,
-                       rows.sorted.p, nf, N, e->d_cat_sorted.p, (size_t)f0 / 64);
-  }
   CC_HIP(hipGetLastError());
   return CC_OK;
 }
@@ -1031,17 +749,15 @@ static int pick_winner(const SplitQuery& q, Found found, Quality quality, Point 
 
 // The ordered search of the presorted variables over the node table in d_split_tab (`form`; built by upload_node_table
 // or, on the device, by the booster): the per-variable results stay in d_split_out as OrdResult lays them out, between
-// ev_a and ev_b on the evaluator's stream.
-// One table of n_vars sorted variables ([group][rank][64] with its read-ahead padding: the resident table or a chunk's)
-// whose first variable is number var_offset (a multiple of 64) of the presorted range: results at that offset of OrdResult.
-static cc_status launch_ordered_table(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0, const float* sv,
-                                      const void* si, int n_vars, int var_offset) {
+// ev_a and ev_b on the evaluator's stream. One table of n_vars sorted variables (the resident table or a chunk's) whose
+// first variable is number var_offset (a multiple of 64) of the presorted range: results at that offset of OrdResult.
+static cc_status launch_ordered_table(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0, const SortedTable& t,
+                                      int n_vars, int var_offset) {
   const int N = e->presort_n, F = e->presort_f1 - e->presort_f0;
-  const bool idx16 = N <= 65536;
   const size_t groups = ((size_t)n_vars + 63) / 64, fpad = ((size_t)F + 63) / 64 * 64;
   const OrdResult dev(e->d_split_out.p, fpad);
   // in the struct's order: sv, si, tab, n_pre, n_vars, w_total0, w_total1, rsum0, best_val, best_i, best_vl, best_vr, n_groups, dbg_nogather
-  const SplitOrdArgs A{sv, si, reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), N, n_vars, w_total0, w_total1, rsum0,
+  const SplitOrdArgs A{t.val.p, t.idx(), reinterpret_cast<const SplitEntry*>(e->d_split_tab.p), N, n_vars, w_total0, w_total1, rsum0,
                        dev.best_val + var_offset, dev.best_i + var_offset, dev.best_vl + var_offset, dev.best_vr + var_offset, (int)groups,
                        std::getenv("CCAMD_DEBUG_SPLIT_NOGATHER") ? 1 : 0};
   // wavefronts per block: with the table in LDS one block owns a CU, so spread the groups evenly over the CUs
@@ -1055,81 +771,69 @@ static cc_status launch_ordered_table(cc_evaluator* e, int mode, TableForm form,
   }
   const unsigned blocks = (unsigned)((groups + wpb - 1) / wpb);
   (void)hipEventRecord(e->ev_a.e, e->stream.s);
-  if (cc_status st = launch(ordered_kernel(mode, form, idx16), blocks, 64u * wpb, table_lds(form, N), e->stream.s, A); st != CC_OK) return st;
+  if (cc_status st = launch(ordered_kernel(mode, form, !t.wide), blocks, 64u * wpb, table_lds(form, N), e->stream.s, A); st != CC_OK) return st;
   (void)hipEventRecord(e->ev_b.e, e->stream.s);
   return CC_OK;
 }
 
-// The leader after the variables [v0, v1) of OrdResult (k_stream_winner); tab_val / tab_idx: the chunk table they were
-// searched in, or NULL for the head, whose rows stay where they are.
-template <class TI>
-static cc_status launch_stream_winner(cc_evaluator* e, int v0, int v1, bool reset, const float* tab_val, const TI* tab_idx) {
-  const size_t fpad = ((size_t)(e->presort_f1 - e->presort_f0) + 63) / 64 * 64;
-  const OrdResult dev(e->d_split_out.p, fpad);
-  hipLaunchKernelGGL((k_stream_winner<TI>), dim3(1), dim3(1024), 0, e->stream.s, dev.best_val, dev.best_i, v0, v1, reset ? 1 : 0, tab_val, tab_idx,
-                     e->presort_n, e->d_win_state.p, e->d_win_val.p, reinterpret_cast<TI*>(e->d_win_idx.p));
+// The leader after the variables [v0, v1) of OrdResult (k_stream_winner); tab: the chunk table they were searched in, or
+// NULL for the head, whose rows stay where they are.
+static cc_status launch_stream_winner(cc_evaluator* e, int v0, int v1, bool reset, const SortedTable* tab) {
+  const OrdResult dev(e->d_split_out.p, ((size_t)(e->presort_f1 - e->presort_f0) + 63) / 64 * 64);
+  with_index_type(wide_index((size_t)e->presort_n), [&](auto ti) {
+    using TI = decltype(ti);
+    hipLaunchKernelGGL((k_stream_winner<TI>), dim3(1), dim3(1024), 0, e->stream.s, dev.best_val, dev.best_i, v0, v1, reset ? 1 : 0,
+                       tab ? tab->val.p : nullptr, tab ? static_cast<const TI*>(tab->idx()) : nullptr, e->presort_n, e->d_win_state.p, e->d_win_val.p,
+                       reinterpret_cast<TI*>(e->d_win_idx.p));
+  });
   CC_HIP(hipGetLastError());
   return CC_OK;
 }
 
+// cc_eval_stream_profile: one more event in the stream, no host wait
+static cc_status stream_mark(cc_evaluator* e) {
+  if (!e->stream_profile) return CC_OK;
+  if (e->stream_ev_used == e->stream_ev.size()) {
+    e->stream_ev.emplace_back();
+    CC_HIP(e->stream_ev.back().create());
+  }
+  CC_HIP(hipEventRecord(e->stream_ev[e->stream_ev_used++].e, e->stream.s));
+  return CC_OK;
+}
+
 // The streamed tail of a node's search: per chunk, in variable order, what cc_eval_presort does once per stage for a
-// resident variable -- evaluate (launch_batch), stable row sort (RowSorter), k_interleave into the chunk table -- then the
+// resident variable -- evaluate, stable row sort, k_interleave into the chunk table (fill_sorted_table) -- then the
 // ordered kernel over that table. The reference does the same for a variable outside its caches at every node
 // (CvCascadeBoostTrainData::get_ord_var_data, o_cvcascadeboosttraindata.cpp:437-458). Nothing waits on the host.
-template <class TI>
-static cc_status stream_ordered_tail(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0, bool track_winner,
-                                     DevBuf<TI>& d_chunk_idx) {
+static cc_status stream_ordered_tail(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0, bool track_winner) {
   const int N = e->presort_n, F = e->presort_f1 - e->presort_f0, R = e->presort_resident, C = e->presort_chunk;
-  RowSorter& rows = *e->stream_rows;
-  const size_t pad = (size_t)SPLIT_TABLE_PAD_RANKS * 64;
   if (track_winner && R > 0)
-    if (cc_status st = launch_stream_winner<TI>(e, 0, R, true, nullptr, nullptr); st != CC_OK) return st;
+    if (cc_status st = launch_stream_winner(e, 0, R, true, nullptr); st != CC_OK) return st;
   e->stream_ev_used = 0;
-  auto mark = [&]() -> cc_status {  // profiling only: one more event in the stream, no host wait
-    if (!e->stream_profile) return CC_OK;
-    if (e->stream_ev_used == e->stream_ev.size()) {
-      e->stream_ev.emplace_back();
-      CC_HIP(e->stream_ev.back().create());
-    }
-    CC_HIP(hipEventRecord(e->stream_ev[e->stream_ev_used++].e, e->stream.s));
-    return CC_OK;
-  };
   for (int c0 = R; c0 < F; c0 += C) {
     const int nf = std::min(C, F - c0);
-    if (cc_status st = mark(); st != CC_OK) return st;
-    if (cc_status st = launch_batch(e, true, e->d_haar.p, e->presort_f0 + c0, e->presort_f0 + c0 + nf, nullptr, N, e->d_out.p, 1, 0); st != CC_OK) return st;
-    if (cc_status st = mark(); st != CC_OK) return st;
-    if (cc_status st = rows.sort(nf); st != CC_OK) return st;
-    if (cc_status st = mark(); st != CC_OK) return st;
-    const size_t groups = ((size_t)nf + 63) / 64, used = groups * 64 * (size_t)N;
-    hipLaunchKernelGGL((k_interleave<TI>), dim3((unsigned)((N + 63) / 64), (unsigned)groups), dim3(256), 0, e->stream.s, rows.keys_out.p, rows.sorted.p, nf, N,
-                       e->d_chunk_val.p, d_chunk_idx.p, (size_t)0);
-    CC_HIP(hipGetLastError());
-    if (nf < C) {  // a short last chunk: the zeroed read-ahead padding stands behind ITS last group (a full chunk's was zeroed by the presort)
-      CC_HIP(hipMemsetAsync(e->d_chunk_val.p + used, 0, pad * sizeof(float), e->stream.s));
-      CC_HIP(hipMemsetAsync(d_chunk_idx.p + used, 0, pad * sizeof(TI), e->stream.s));
-    }
-    if (cc_status st = mark(); st != CC_OK) return st;
-    if (cc_status st = launch_ordered_table(e, mode, form, w_total0, w_total1, rsum0, e->d_chunk_val.p, d_chunk_idx.p, nf, c0); st != CC_OK) return st;
-    if (cc_status st = mark(); st != CC_OK) return st;
+    if (cc_status st = fill_sorted_table(e, *e->stream_rows, e->presort_f0 + c0, nf, e->chunk, 0, stream_mark); st != CC_OK) return st;
+    // a short last chunk: the zeroed read-ahead padding stands behind ITS last group (a full chunk's was zeroed by the presort)
+    if (nf < C)
+      if (cc_status st = e->chunk.zero_padding(((size_t)nf + 63) / 64 * 64 * (size_t)N, e->stream.s); st != CC_OK) return st;
+    if (cc_status st = stream_mark(e); st != CC_OK) return st;
+    if (cc_status st = launch_ordered_table(e, mode, form, w_total0, w_total1, rsum0, e->chunk, nf, c0); st != CC_OK) return st;
+    if (cc_status st = stream_mark(e); st != CC_OK) return st;
     if (track_winner)
-      if (cc_status st = launch_stream_winner<TI>(e, c0, c0 + nf, c0 == 0, e->d_chunk_val.p, d_chunk_idx.p); st != CC_OK) return st;
-    if (cc_status st = mark(); st != CC_OK) return st;
+      if (cc_status st = launch_stream_winner(e, c0, c0 + nf, c0 == 0, &e->chunk); st != CC_OK) return st;
+    if (cc_status st = stream_mark(e); st != CC_OK) return st;
   }
   return CC_OK;
 }
 
 cc_status ccamd::split_launch_ordered(cc_evaluator* e, int mode, TableForm form, double w_total0, double w_total1, double rsum0, bool track_winner) {
-  const int N = e->presort_n, F = e->presort_f1 - e->presort_f0, R = e->presort_resident;
-  const bool idx16 = N <= 65536;
+  const int F = e->presort_f1 - e->presort_f0, R = e->presort_resident;
   CC_HIP(e->d_split_out.ensure(((size_t)F + 63) / 64 * 64 * 3));  // OrdResult::bytes + slack
-  const void* head_idx = idx16 ? (const void*)e->d_sorted_idx16.p : (const void*)e->d_sorted_idx32.p;
-  if (R >= F) return launch_ordered_table(e, mode, form, w_total0, w_total1, rsum0, e->d_sorted_val.p, head_idx, F, 0);
+  if (R >= F) return launch_ordered_table(e, mode, form, w_total0, w_total1, rsum0, e->head, F, 0);
   (void)hipEventRecord(e->ev_stream_a.e, e->stream.s);
   if (R > 0)
-    if (cc_status st = launch_ordered_table(e, mode, form, w_total0, w_total1, rsum0, e->d_sorted_val.p, head_idx, R, 0); st != CC_OK) return st;
-  const cc_status st = idx16 ? stream_ordered_tail(e, mode, form, w_total0, w_total1, rsum0, track_winner, e->d_chunk_idx16)
-                             : stream_ordered_tail(e, mode, form, w_total0, w_total1, rsum0, track_winner, e->d_chunk_idx32);
+    if (cc_status st = launch_ordered_table(e, mode, form, w_total0, w_total1, rsum0, e->head, R, 0); st != CC_OK) return st;
+  const cc_status st = stream_ordered_tail(e, mode, form, w_total0, w_total1, rsum0, track_winner);
   (void)hipEventRecord(e->ev_b.e, e->stream.s);
   return st;
 }
@@ -1265,8 +969,7 @@ static cc_status search_categorical(const SplitQuery& q) {
   CC_HIP(q.e->d_split_out.ensure(hist_n));
   bool ascending = true;  // the node lists its samples in increasing order: what k_split_cat_sorted's exactness needs
   for (int i = 1; i < q.n && ascending && q.sample_idx; i++) ascending = q.sample_idx[i - 1] < q.sample_idx[i];
-  const bool stream_only = std::getenv("CCAMD_SPLIT_CAT_STREAM") != nullptr;  // read per call: tests compare the two paths
-  const bool sorted = ascending && q.e->cat_sorted_n == q.N && !stream_only;
+  const bool sorted = ascending && q.e->cat_sorted_n == q.N && cat_sorted_table_enabled();
   if (sorted) {
     const TableForm form = table_form(q);
     if (cc_status st = upload_node_table(q, form, &ABSENT_CATEGORICAL); st != CC_OK) return st;
@@ -1301,136 +1004,7 @@ static cc_status finish_categorical(const SplitQuery& q, size_t hist_n) {
   return CC_OK;
 }
 
-// The split presort of ordered variables with 16- or 32-bit sample numbers: head tables, chunk table, winner row.
-template <class TI>
-static cc_status presort_split_ordered(cc_evaluator* e, int fi_begin, int R, int C, DevBuf<TI>& d_sorted_idx, DevBuf<TI>& d_chunk_idx) {
-  RowSorter& rows = *e->stream_rows;
-  const size_t N = (size_t)rows.N, pad = (size_t)SPLIT_TABLE_PAD_RANKS * 64;
-  if (R > 0)
-    if (cc_status st = build_ordered_tables(e, rows, e->d_haar.p, fi_begin, R, d_sorted_idx); st != CC_OK) return st;
-  // the whole chunk table zeroed once: a full chunk's read-ahead padding is never written again
-  CC_HIP(e->d_chunk_val.ensure((size_t)C * N + pad));
-  CC_HIP(hipMemsetAsync(e->d_chunk_val.p, 0, ((size_t)C * N + pad) * sizeof(float), e->stream.s));
-  CC_HIP(d_chunk_idx.ensure((size_t)C * N + pad));
-  CC_HIP(hipMemsetAsync(d_chunk_idx.p, 0, ((size_t)C * N + pad) * sizeof(TI), e->stream.s));
-  CC_HIP(e->d_win_val.ensure(N));
-  CC_HIP(e->d_win_idx.ensure(N));
-  CC_HIP(e->d_win_state.ensure(1));
-  CC_HIP(hipMemsetAsync(e->d_win_val.p, 0, N * 4, e->stream.s));
-  CC_HIP(hipMemsetAsync(e->d_win_idx.p, 0, N * 4, e->stream.s));
-  CC_HIP(hipMemsetAsync(e->d_win_state.p, 0, sizeof(StreamBest), e->stream.s));
-  return CC_OK;
-}
-
 extern "C" {
-
-cc_status cc_eval_presort_range(cc_evaluator* e, int fi_begin, int fi_end, int n_samples) {
-  if (!e) return set_error(CC_ERR_INVALID_ARG, "cc_eval_presort: null evaluator");
-  if (n_samples < 1 || n_samples > e->max_samples)
-    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_presort: n_samples %d out of range (max_samples %d)", n_samples, e->max_samples);
-  if (fi_begin < 0 || fi_end > e->nfeat || fi_begin >= fi_end)
-    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_presort: features [%d, %d) out of range (%d)", fi_begin, fi_end, e->nfeat);
-  if (cc_status st = eval_device(e); st != CC_OK) return st;
-  std::lock_guard<std::mutex> lk(e->mu);
-  if (cc_status st = flush_pending_images(e); st != CC_OK) return st;
-  e->presort_n = 0;  // until the epilogue: a failure below leaves no tables to search
-  e->generation++;   // a booster created over the earlier tables refuses its next round
-  const bool haar = e->type != CC_FEATURE_LBP;  // HOG variables are ordered: the Haar tables (launch_batch dispatches HOG)
-  const int F = fi_end - fi_begin, N = n_samples;
-  const void* feats = haar ? (const void*)e->d_haar.p : (const void*)e->d_lbp.p;
-  // variables per pass: whole groups of 64, at most 2^28 values per scratch array
-  const int FB = (int)std::min<size_t>((size_t)F, std::max<size_t>(64, (((size_t)1 << 28) / (size_t)N) / 64 * 64));
-  // LBP keeps the (code, sample)-sorted table of k_split_cat_sorted beside the codes while sample numbers fit 24 bits
-  const bool no_cat_table = std::getenv("CCAMD_SPLIT_CAT_STREAM") != nullptr;  // A/B: round-1 categorical search only
-  const bool cat_table = !haar && N < (1 << 24) && !no_cat_table;
-  if (cc_status st = presort_memory_check(e, haar, cat_table, F, N, FB); st != CC_OK) return st;
-  RowSorter rows(e, N, FB);
-  if (haar || cat_table)
-    if (cc_status st = rows.init(); st != CC_OK) return st;
-  const cc_status st = !haar        ? presort_categorical(e, rows, feats, fi_begin, F, cat_table)
-                       : N <= 65536 ? presort_ordered(e, rows, feats, fi_begin, F, e->d_sorted_idx16)
-                                    : presort_ordered(e, rows, feats, fi_begin, F, e->d_sorted_idx32);
-  if (st != CC_OK) return st;
-  CC_HIP(hipStreamSynchronize(e->stream.s));
-  // epilogue: the tables are valid
-  e->presort_n = N;
-  e->presort_f0 = fi_begin;
-  e->presort_f1 = fi_end;
-  e->cat_sorted_n = cat_table ? N : 0;
-  return CC_OK;
-}
-
-cc_status cc_eval_presort(cc_evaluator* e, int n_samples) {
-  if (!e) return set_error(CC_ERR_INVALID_ARG, "cc_eval_presort: null evaluator");
-  return cc_eval_presort_range(e, 0, e->nfeat, n_samples);
-}
-
-cc_status cc_presort_plan(int feature_type, int n_vars, int n_samples, uint64_t budget_bytes, int* resident_vars, int* chunk_vars,
-                          uint64_t* bytes_needed) {
-  if (!resident_vars || !chunk_vars || !bytes_needed) return set_error(CC_ERR_INVALID_ARG, "cc_presort_plan: null argument");
-  if (feature_type != CC_FEATURE_HAAR && feature_type != CC_FEATURE_LBP && feature_type != CC_FEATURE_HOG)
-    return set_error(CC_ERR_INVALID_ARG, "cc_presort_plan: unknown feature type %d", feature_type);
-  if (n_vars < 1 || n_samples < 1) return set_error(CC_ERR_OUT_OF_RANGE, "cc_presort_plan: %d variables, %d samples", n_vars, n_samples);
-  *resident_vars = *chunk_vars = 0;
-  *bytes_needed = 0;
-  if (budget_bytes == 0) {  // what the device has free now
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-      (void)hipGetLastError();
-      return set_error(CC_ERR_NO_DEVICE, "cc_presort_plan: budget_bytes = 0 asks the device for its free memory, and there is no usable HIP device");
-    }
-    budget_bytes = free_b;
-  }
-  using u128 = PresortCosts::u128;
-  const size_t F = (size_t)n_vars, N = (size_t)n_samples;
-  const u128 budget = budget_bytes, top = ~(uint64_t)0;
-  if (feature_type == CC_FEATURE_LBP) {  // presort_memory_check's sum for categorical variables
-    const bool cat_table = N < ((size_t)1 << 24) && !std::getenv("CCAMD_SPLIT_CAT_STREAM");
-    const u128 need = (u128)F * N + (cat_table ? (u128)((F + 63) / 64 * 64) * (N + 3 + SPLIT_CAT_PAD_RANKS) * 4 : 0) +
-                      (u128)std::min(F, pass_vars_rule(N)) * N * (cat_table ? 16 : 4);
-    if (need > budget)
-      return set_error(CC_ERR_UNSUPPORTED, "cc_presort_plan: categorical variables are not streamed, and their tables need %.0f bytes (budget %.0f)",
-                       (double)need, (double)budget);
-    *resident_vars = n_vars;
-    *bytes_needed = (uint64_t)need;
-    return CC_OK;
-  }
-  const PresortCosts cost(N);
-  if (cost.resident(F) <= budget) {
-    *resident_vars = n_vars;
-    *bytes_needed = (uint64_t)cost.resident(F);
-    return CC_OK;
-  }
-  if (cost.split(0, 64) > budget)
-    return set_error(CC_ERR_UNSUPPORTED, "cc_presort_plan: a budget of %llu bytes holds neither every table nor one chunk of 64 variables x %d samples; the smallest budget that works is %llu",
-                     (unsigned long long)budget_bytes, n_samples, (unsigned long long)std::min({cost.split(0, 64), cost.resident(F), top}));
-  // Everything but the last group resident needs a chunk of 64 only (a chunk is never larger than the tail).
-  const size_t r_max = (F - 1) / 64 * 64;
-  if (cost.split(r_max, 64) <= budget) {
-    *resident_vars = (int)r_max;
-    *chunk_vars = 64;
-    *bytes_needed = (uint64_t)cost.split(r_max, 64);
-    return CC_OK;
-  }
-  // Otherwise the chunk first, up to the pass rule, and a head only beside a chunk of that size: a head that shrank
-  // whenever the chunk grew by a group would not be monotone in the budget. u128 sums: nothing below can wrap.
-  const size_t c_rule = std::min((F + 63) / 64 * 64, pass_vars_rule(N));
-  const u128 per_chunk_group = cost.chunk(128) - cost.chunk(64);  // 64 variables more
-  const size_t C = (size_t)std::min<u128>(c_rule, 64 + (budget - cost.split(0, 64)) / per_chunk_group * 64);
-  const u128 left = budget - cost.split(0, C), pad_bytes = cost.head(64) - (u128)64 * N * cost.per;
-  const size_t R = C == c_rule && left > pad_bytes ? (size_t)std::min<u128>((left - pad_bytes) / ((u128)64 * N * cost.per) * 64, (F - 1) / 64 * 64) : 0;
-  *resident_vars = (int)R;
-  *chunk_vars = (int)C;
-  *bytes_needed = (uint64_t)cost.split(R, C);
-  return CC_OK;
-}
-
-cc_status cc_eval_table_bytes(cc_evaluator* e, uint64_t* bytes) {
-  if (!e || !bytes) return set_error(CC_ERR_INVALID_ARG, "cc_eval_table_bytes: null argument");
-  std::lock_guard<std::mutex> lk(e->mu);
-  *bytes = held_table_bytes(e);
-  return CC_OK;
-}
 
 cc_status cc_eval_stream_profile(cc_evaluator* e, int enable) {
   if (!e) return set_error(CC_ERR_INVALID_ARG, "cc_eval_stream_profile: null evaluator");
@@ -1444,71 +1018,6 @@ cc_status cc_eval_stream_phase_ms(cc_evaluator* e, double* ms, int cap, int* n_p
   std::lock_guard<std::mutex> lk(e->mu);
   *n_parts = 5;
   for (int i = 0; i < 5 && i < cap; i++) ms[i] = e->stream_phase_ms[i];
-  return CC_OK;
-}
-
-cc_status cc_eval_presort_budget(cc_evaluator* e, uint64_t* bytes) {
-  if (!e || !bytes) return set_error(CC_ERR_INVALID_ARG, "cc_eval_presort_budget: null argument");
-  if (cc_status st = eval_device(e); st != CC_OK) return st;
-  std::lock_guard<std::mutex> lk(e->mu);
-  size_t free_b = 0, total_b = 0;
-  CC_HIP(hipMemGetInfo(&free_b, &total_b));
-  *bytes = (uint64_t)free_b + held_table_bytes(e);
-  return CC_OK;
-}
-
-cc_status cc_eval_presort_split(cc_evaluator* e, int fi_begin, int fi_end, int n_samples, int resident_vars, int chunk_vars) {
-  if (!e) return set_error(CC_ERR_INVALID_ARG, "cc_eval_presort_split: null evaluator");
-  if (n_samples < 1 || n_samples > e->max_samples)
-    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_presort_split: n_samples %d out of range (max_samples %d)", n_samples, e->max_samples);
-  if (fi_begin < 0 || fi_end > e->nfeat || fi_begin >= fi_end)
-    return set_error(CC_ERR_OUT_OF_RANGE, "cc_eval_presort_split: features [%d, %d) out of range (%d)", fi_begin, fi_end, e->nfeat);
-  const int F = fi_end - fi_begin, N = n_samples, R = resident_vars;
-  if (R == F) return cc_eval_presort_range(e, fi_begin, fi_end, n_samples);  // nothing is streamed: today's presort
-  if (R < 0 || R > F || R % 64 != 0)
-    return set_error(CC_ERR_INVALID_ARG, "cc_eval_presort_split: resident_vars %d is neither a multiple of 64 in [0, %d] nor %d", R, F, F);
-  if (chunk_vars < 64 || chunk_vars % 64 != 0)
-    return set_error(CC_ERR_INVALID_ARG, "cc_eval_presort_split: chunk_vars %d is not a multiple of 64 of at least 64", chunk_vars);
-  if (e->type == CC_FEATURE_LBP)
-    return set_error(CC_ERR_UNSUPPORTED, "cc_eval_presort_split: categorical variables are not streamed (LBP takes resident_vars = %d only)", F);
-  if (cc_status st = eval_device(e); st != CC_OK) return st;
-  std::lock_guard<std::mutex> lk(e->mu);
-  if (cc_status st = flush_pending_images(e); st != CC_OK) return st;
-  e->presort_n = 0;  // until the epilogue: a failure below leaves no tables to search
-  e->generation++;   // a booster created over the earlier tables refuses its next round
-  // no chunk larger than the tail or than a pass of the full presort (at most 2^28 values per scratch array)
-  const int C = (int)std::min<size_t>({(size_t)chunk_vars, ((size_t)(F - R) + 63) / 64 * 64, pass_vars_rule((size_t)N)});
-  // Exactly what the plan counts is held afterwards: larger buffers of an earlier presort go back first.
-  const PresortCosts cost((size_t)N);
-  const size_t pad = (size_t)SPLIT_TABLE_PAD_RANKS * 64, head_n = R ? (size_t)R * N + pad : 0, chunk_n = (size_t)C * N;
-  const bool idx16 = N <= 65536;
-  release_stream_scratch(e);
-  if (e->d_sorted_val.n > head_n) e->d_sorted_val.release();
-  if (e->d_sorted_idx16.n > (idx16 ? head_n : 0)) e->d_sorted_idx16.release();
-  if (e->d_sorted_idx32.n > (idx16 ? 0 : head_n)) e->d_sorted_idx32.release();
-  if (e->d_out.n > chunk_n) e->d_out.release();
-  size_t free_b = 0, total_b = 0;
-  CC_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t have = e->d_sorted_val.n * 4 + e->d_sorted_idx16.n * 2 + e->d_sorted_idx32.n * 4 + e->d_out.n * 4;
-  if (cost.split((size_t)R, (size_t)C) > (PresortCosts::u128)free_b + have)
-    return set_error(CC_ERR_UNSUPPORTED, "cc_eval_presort_split: needs %.1f GB of device memory (%.1f GB free)",
-                     (double)cost.split((size_t)R, (size_t)C) / 1e9, (double)(free_b + have) / 1e9);
-  if (!e->ev_stream_a.e) CC_HIP(e->ev_stream_a.create());
-  e->stream_rows.reset(new RowSorter(e, N, C));
-  if (cc_status st = e->stream_rows->init(); st != CC_OK) return st;
-  if (N > sort_rows_block_limit())  // the segmented sort's offsets and iota now, not inside the first node's search
-    if (cc_status st = e->stream_rows->prepare_segmented(); st != CC_OK) return st;
-  const cc_status st = idx16 ? presort_split_ordered(e, fi_begin, R, C, e->d_sorted_idx16, e->d_chunk_idx16)
-                             : presort_split_ordered(e, fi_begin, R, C, e->d_sorted_idx32, e->d_chunk_idx32);
-  if (st != CC_OK) return st;
-  CC_HIP(hipStreamSynchronize(e->stream.s));
-  // epilogue: the head's tables are valid
-  e->presort_n = N;
-  e->presort_f0 = fi_begin;
-  e->presort_f1 = fi_end;
-  e->cat_sorted_n = 0;
-  e->presort_resident = R;
-  e->presort_chunk = C;
   return CC_OK;
 }
 

@@ -1,4 +1,4 @@
-"""GPU tests of the split presort (cc_eval_presort_split; cc_split.hip, cc_boost.hip): a resident head of the presorted
+"""GPU tests of the split presort (cc_eval_presort_split; cc_presort.hip, cc_split.hip, cc_boost.hip): a resident head of the presorted
 range and a tail that is evaluated, sorted and searched chunk by chunk at every node. The contract is one line: every
 record, every tree and the whole per-sample state of every round are bit-identical to a run with all tables resident. Each
 case runs two evaluators with the same contents, one presorted as ever and one split, and compares them with tolerance
@@ -259,7 +259,36 @@ def test_train_cascade_within_a_table_budget():
         assert (getattr(ma, k) == getattr(mb, k)).all(), k
 
 
-# ---- 10. refusals and invalidation ------------------------------------------------------------------------------------------
+# ---- 10. what a split presort holds does not depend on what was held before ------------------------------------------------
+def test_split_presort_after_a_larger_resident_presort_holds_the_same(case200):
+    """A split presort (head 64, chunks of 64, 200 variables) on a fresh evaluator, and on one that first presorted the
+    whole 8x8 catalog: the larger tables go back, both hold the same bytes, and one Gentle round is equal."""
+    imgs, labels, _ = case200
+    a, b = (_evaluator(ev.HAAR, ev.BASIC, WIN, imgs, labels) for _ in range(2))
+    b.presort()
+    full = b.table_bytes()
+    for e in (a, b):
+        assert e.presort(N, F0, F0 + 200, resident_vars=64, chunk_vars=64) == (64, 64)
+    assert 0 < a.table_bytes() == b.table_bytes() < full
+    assert _rounds_equal(a, b, N, 1, "after a resident presort")[0]["trained"]
+
+
+def test_split_presort_after_one_of_the_other_index_width_holds_the_same():
+    """16-bit sample numbers (300 samples) and then 32-bit ones (65 537), and the reverse: the index buffer of the other
+    width goes back, and the evaluator holds what a fresh one holds after the second call alone. The 192 variables of
+    tests/test_gpu_training_sizes.py, a head of 64 and two chunks; one Gentle round is equal."""
+    big = 65537
+    imgs, labels = _samples(big, WIN, 17)
+    for first, then in ((N, big), (big, N)):
+        a, b = (_evaluator(ev.HAAR, ev.BASIC, WIN, imgs, labels) for _ in range(2))
+        assert b.presort(first, *HAAR_RANGE, resident_vars=64, chunk_vars=64) == (64, 64)
+        for e in (a, b):
+            assert e.presort(then, *HAAR_RANGE, resident_vars=64, chunk_vars=64) == (64, 64)
+        assert 0 < a.table_bytes() == b.table_bytes(), (first, then)
+        assert _rounds_equal(a, b, then, 1, ("width", first, then))[0]["trained"]
+
+
+# ---- 11. refusals and invalidation ------------------------------------------------------------------------------------------
 def test_refusals(case200):
     imgs, labels, _ = case200
     lbp = _evaluator(ev.LBP, 0, WIN, imgs, labels)

@@ -1,7 +1,7 @@
 """The training side past its size thresholds, compared exactly with the oracle (oracle/oracle.py) or, for HOG, with the
 restatement (tests/hog_restatement.py). Each test goes past one point where the device code changes path:
 
-* more than 65 536 presorted samples: 32-bit sorted indices (cc_split.hip, `idx16 = N <= 65536`), and presort in several
+* more than 65 536 presorted samples: 32-bit sorted indices (`wide_index`, cc_eval_internal.h), and presort in several
   passes of FB = 2^28 / N variables;
 * LBP sample numbers >= 2^16 in the packed (sample << 8 | code) entries of the categorical tables, and the default number
   of parts per variable at N = 100 000 (97 on 256 CUs; CCAMD_SPLIT_CAT_PARTS cannot go past 64);

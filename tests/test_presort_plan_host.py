@@ -1,7 +1,7 @@
 """cc_presort_plan (host arithmetic, no device): how a presort fits a budget of device memory. The sums are restated here
 from the header (include/cascadeclassifier_amd.h, section 6): with N samples, F variables, per = 4 + (2 or 4) bytes of a
 table entry, P = max(64, floor64(2^28 / N)) variables per pass and 64 ranks of read-ahead padding,
-    everything resident:  ceil64(F) * N * per + min(F, P) * N * 16        (presort_memory_check of cc_split.hip)
+    everything resident:  ceil64(F) * N * per + min(F, P) * N * 16        (PresortCosts of cc_presort.hip)
     split (R, C):         head(R) + chunk(C) + 8 * N
       head(R)  = R == 0 ? 0 : (R * N + 64 * 64) * per
       chunk(C) = C * N * 16 + (C * N + 64 * 64) * per
