@@ -21,6 +21,7 @@ CC_ERR_PARSE = -5
 CC_ERR_UNSUPPORTED = -6
 CC_ERR_BUFFER_TOO_SMALL = -7
 CC_ERR_OUT_OF_RANGE = -8
+CC_ERR_NO_TRAIN_PARAMS = -9
 
 CC_FEATURE_HAAR, CC_FEATURE_LBP, CC_FEATURE_HOG = 0, 1, 2
 CC_PIX_GRAY8, CC_PIX_BGR8, CC_PIX_BGRA8, CC_PIX_RGB8, CC_PIX_RGBA8, CC_PIX_RGB8_PLANAR = 0, 1, 2, 3, 4, 5
@@ -83,6 +84,13 @@ class TreeNode(C.Structure):
     _fields_ = [("left", C.c_int32), ("right", C.c_int32), ("depth", C.c_int32), ("n_samples", C.c_int32), ("var_idx", C.c_int32),
                 ("split_point", C.c_int32), ("quality", C.c_float), ("ord_c", C.c_float), ("subset", C.c_int32 * 8),
                 ("value", C.c_double)]
+
+
+class TrainParams(C.Structure):
+    _fields_ = [("feature_type", C.c_int32), ("win_w", C.c_int32), ("win_h", C.c_int32), ("boost_type", C.c_int32),
+                ("min_hit_rate", C.c_float), ("max_false_alarm", C.c_float), ("weight_trim_rate", C.c_double),
+                ("max_depth", C.c_int32), ("max_weak_count", C.c_int32), ("max_cat_count", C.c_int32), ("feat_size", C.c_int32),
+                ("haar_mode", C.c_int32)]
 
 
 class HaarFeatureC(C.Structure):
@@ -223,6 +231,12 @@ SIGNATURES = {
     "cc_debug_exp64": (_i, [_i, _vp, _i, _vp]),
     "cc_cascade_from_stumps": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _pp]),
     "cc_cascade_from_trees": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, C.POINTER(TreeNode), _vp, _pp]),
+    "cc_train_params_save_xml": (_i, [C.POINTER(TrainParams), C.c_char_p, C.c_char_p]),
+    "cc_train_params_load_xml": (_i, [C.c_char_p, C.POINTER(TrainParams)]),
+    "cc_cascade_train_params": (_i, [_vp, C.POINTER(TrainParams)]),
+    "cc_cascade_save_xml_params": (_i, [_vp, C.POINTER(TrainParams), C.c_char_p]),
+    "cc_stage_save_xml": (_i, [C.c_char_p, C.c_char_p, _i, C.c_float, _i, _vp, _i, C.POINTER(TreeNode), _vp]),
+    "cc_stage_load_xml": (_i, [C.c_char_p, _i, _i, C.POINTER(C.c_float), C.POINTER(_i), _vp, _i, C.POINTER(_i), C.POINTER(TreeNode), _i, _vp]),
     "cc_shard_range": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "cc_comm_unique_id": (_i, [_vp]),
     "cc_comm_create": (_i, [_i, _i, _i, _vp, _pp]),

@@ -73,6 +73,75 @@ std::string trimmed(const std::string& s) {
   return s.substr(a, b - a);
 }
 
+// a string value: FileStorage quotes one that would not read back as a string otherwise
+std::string string_value(const XmlNode* n) {
+  std::string s = n ? trimmed(n->text) : std::string();
+  if (s.size() >= 2 && s.front() == '"' && s.back() == '"') s = s.substr(1, s.size() - 2);
+  return s;
+}
+
+const char* const kFeatureNames[3] = {"HAAR", "LBP", "HOG"};
+const char* const kBoostNames[4] = {"DAB", "RAB", "LB", "GAB"};  // CvBoost's DISCRETE, REAL, LOGIT, GENTLE
+const char* const kModeNames[3] = {"BASIC", "CORE", "ALL"};
+
+int name_index(const std::string& s, const char* const* names, int n) {
+  for (int i = 0; i < n; i++)
+    if (s == names[i]) return i;
+  return -1;
+}
+
+// The parameter block of a params.xml or a cascade.xml with the checks of CvCascadeParams::read (cascadeclassifier.cpp:48-73),
+// CvCascadeBoostParams::read (boost.cpp:73-95), CvFeatureParams::read (features.cpp:53-60) and CvHaarFeatureParams::read
+// (haarfeatures.cpp:38-52). `where` starts every message (the file's name).
+cc_status train_params_from_xml(const XmlNode& b, const char* where, cc_train_params& p) {
+  std::memset(&p, 0, sizeof(p));
+  if (string_value(b.child("stageType")) != "BOOST") return set_error(CC_ERR_PARSE, "%s: <stageType> must be BOOST", where);
+  p.feature_type = name_index(string_value(b.child("featureType")), kFeatureNames, 3);
+  if (p.feature_type < 0) return set_error(CC_ERR_PARSE, "%s: <featureType> must be HAAR, LBP or HOG", where);
+  if (!node_int(b.child("height"), p.win_h) || p.win_h <= 0) return set_error(CC_ERR_PARSE, "%s: <height> must be a positive integer", where);
+  if (!node_int(b.child("width"), p.win_w) || p.win_w <= 0) return set_error(CC_ERR_PARSE, "%s: <width> must be a positive integer", where);
+  const XmlNode* sp = b.child("stageParams");
+  if (!sp) return set_error(CC_ERR_PARSE, "%s: <stageParams> is missing", where);
+  if (!sp->child("boostType"))
+    return set_error(CC_ERR_NO_TRAIN_PARAMS, "%s: no training parameters (<stageParams> has no <boostType>)", where);
+  p.boost_type = name_index(string_value(sp->child("boostType")), kBoostNames, 4);
+  if (p.boost_type < 0) return set_error(CC_ERR_PARSE, "%s: <boostType> must be DAB, RAB, LB or GAB (unsupported Boost type)", where);
+  double hit = 0, fa = 0, trim = 0;
+  if (!node_double(sp->child("minHitRate"), hit) || !((float)hit > 0 && (float)hit <= 1))
+    return set_error(CC_ERR_PARSE, "%s: <minHitRate> must lie in (0, 1] (bad parameters range)", where);
+  if (!node_double(sp->child("maxFalseAlarm"), fa) || !((float)fa > 0 && (float)fa <= 1))
+    return set_error(CC_ERR_PARSE, "%s: <maxFalseAlarm> must lie in (0, 1] (bad parameters range)", where);
+  if (!node_double(sp->child("weightTrimRate"), trim) || !(trim > 0 && trim <= 1))
+    return set_error(CC_ERR_PARSE, "%s: <weightTrimRate> must lie in (0, 1] (bad parameters range)", where);
+  p.min_hit_rate = (float)hit;
+  p.max_false_alarm = (float)fa;
+  p.weight_trim_rate = trim;
+  if (!node_int(sp->child("maxDepth"), p.max_depth) || p.max_depth <= 0)
+    return set_error(CC_ERR_PARSE, "%s: <maxDepth> must be a positive integer (bad parameters range)", where);
+  if (!node_int(sp->child("maxWeakCount"), p.max_weak_count) || p.max_weak_count <= 0)
+    return set_error(CC_ERR_PARSE, "%s: <maxWeakCount> must be a positive integer (bad parameters range)", where);
+  const XmlNode* fp = b.child("featureParams");
+  if (!fp) fp = b.child("featuhreParams");  // historical typo carried by some stock files
+  if (!fp) return set_error(CC_ERR_PARSE, "%s: <featureParams> is missing", where);
+  p.max_cat_count = p.feature_type == CC_FEATURE_LBP ? 256 : 0;
+  p.feat_size = p.feature_type == CC_FEATURE_HOG ? 36 : 1;
+  if (fp->child("maxCatCount") && (!node_int(fp->child("maxCatCount"), p.max_cat_count) || p.max_cat_count < 0))
+    return set_error(CC_ERR_PARSE, "%s: <maxCatCount> must be an integer >= 0", where);
+  if (fp->child("featSize") && (!node_int(fp->child("featSize"), p.feat_size) || p.feat_size < 1))
+    return set_error(CC_ERR_PARSE, "%s: <featSize> must be an integer >= 1", where);
+  if (p.feature_type == CC_FEATURE_HAAR) {
+    p.haar_mode = name_index(string_value(fp->child("mode")), kModeNames, 3);
+    if (p.haar_mode < 0) return set_error(CC_ERR_PARSE, "%s: <mode> must be BASIC, CORE or ALL", where);
+  }
+  return CC_OK;
+}
+
+// the object under <opencv_storage> (FileStorage::getFirstTopLevelNode), or the root itself
+const XmlNode* first_top_level(const XmlNode& root) {
+  if (root.name != "opencv_storage") return &root;
+  return root.children.empty() ? nullptr : &root.children[0];
+}
+
 }  // namespace
 
 cc_status cascade_from_xml(const XmlNode& root, Cascade& c) {
@@ -280,6 +349,12 @@ cc_status cascade_from_xml(const XmlNode& root, Cascade& c) {
       c.stump_right.push_back(c.leaves[l0 + 1]);
     }
   }
+  // the training parameters, where the file holds a whole block that passes the trainer's checks; the model does not depend on them
+  cc_train_params tp;
+  if (train_params_from_xml(*casc, "cascade XML", tp) == CC_OK && tp.feature_type == c.feature_type && tp.win_w == c.win_w && tp.win_h == c.win_h) {
+    c.has_train_params = true;
+    c.train_params = tp;
+  }
   return CC_OK;
 }
 
@@ -446,61 +521,71 @@ cc_status cascade_from_nodes(const char* who, int feature_type, int haar_mode, i
   *out = c.release();
   return CC_OK;
 }
-}  // namespace
-
-extern "C" {
-
-cc_status cc_cascade_load_xml_mem(const char* text, size_t len, cc_cascade** out) {
-  const CNumericLocale c_numbers;  // "%.8e" / strtod must not follow the host program's LC_NUMERIC
-  if (!text || !out) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_load_xml_mem: null argument");
-  *out = nullptr;
-  XmlNode root;
-  std::string err;
-  if (!xml_parse(text, len, root, err)) return set_error(CC_ERR_PARSE, "cascade XML: %s", err.c_str());
-  cc_cascade* c = new cc_cascade();
-  cc_status st = cascade_from_xml(root, c->m);
-  if (st != CC_OK) {
-    delete c;
-    return st;
-  }
-  *out = c;
-  return CC_OK;
-}
-
-cc_status cc_cascade_load_xml(const char* path, cc_cascade** out) {
-  if (!path || !out) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_load_xml: null argument");
-  *out = nullptr;
+cc_status parse_xml_file(const char* path, XmlNode& root) {
   std::ifstream f(path, std::ios::binary);
   if (!f) return set_error(CC_ERR_IO, "cannot open '%s'", path);
   std::stringstream ss;
   ss << f.rdbuf();
-  std::string s = ss.str();
-  return cc_cascade_load_xml_mem(s.data(), s.size(), out);
+  const std::string s = ss.str();
+  std::string err;
+  if (!xml_parse(s.data(), s.size(), root, err)) return set_error(CC_ERR_PARSE, "%s: %s", path, err.c_str());
+  return CC_OK;
 }
 
-void cc_cascade_destroy(cc_cascade* c) { delete c; }
+// FileStorage::getDefaultObjectName: the file's name without directory and extension, made an identifier
+std::string default_object_name(const char* path) {
+  std::string s(path);
+  const size_t slash = s.find_last_of("/\\");
+  if (slash != std::string::npos) s.erase(0, slash + 1);
+  if (s.size() > 3 && s.compare(s.size() - 3, 3, ".gz") == 0) s.erase(s.size() - 3);
+  const size_t dot = s.find_last_of('.');
+  if (dot != std::string::npos) s.erase(dot);
+  for (char& ch : s)
+    if (!std::isalnum((unsigned char)ch) && ch != '-' && ch != '_') ch = '_';
+  if (s.empty() || !(std::isalpha((unsigned char)s[0]) || s[0] == '_')) s.insert(s.begin(), '_');
+  return s;
+}
 
-cc_status cc_cascade_save_xml(const cc_cascade* c, const char* path) {
+cc_status check_param_names(const char* who, const cc_train_params& p) {
+  if (p.feature_type < 0 || p.feature_type > 2) return set_error(CC_ERR_INVALID_ARG, "%s: unknown feature type %d", who, p.feature_type);
+  if (p.boost_type < 0 || p.boost_type > 3) return set_error(CC_ERR_INVALID_ARG, "%s: unknown boost type %d", who, p.boost_type);
+  if (p.feature_type == CC_FEATURE_HAAR && (p.haar_mode < 0 || p.haar_mode > 2)) return set_error(CC_ERR_INVALID_ARG, "%s: unknown Haar mode %d", who, p.haar_mode);
+  return CC_OK;
+}
+
+// <stageType> .. <featureParams>: CvCascadeParams::write (cascadeclassifier.cpp:33-46) and the two blocks of writeParams (:359-364),
+// at the depth params.xml and cascade.xml hold them. p == nullptr: the short blocks cc_cascade_save_xml writes, from the last three arguments.
+void write_params_text(std::ostringstream& o, int feature_type, int win_w, int win_h, const cc_train_params* p, int max_weak, int max_cat, int feat_size) {
+  o << "  <stageType>BOOST</stageType>\n  <featureType>" << kFeatureNames[feature_type] << "</featureType>\n";
+  o << "  <height>" << win_h << "</height>\n  <width>" << win_w << "</width>\n";
+  o << "  <stageParams>\n";
+  if (p) {  // CvCascadeBoostParams::write, boost.cpp:58-71
+    o << "    <boostType>" << kBoostNames[p->boost_type] << "</boostType>\n    <minHitRate>" << real_text(p->min_hit_rate) << "</minHitRate>\n";
+    o << "    <maxFalseAlarm>" << real_text(p->max_false_alarm) << "</maxFalseAlarm>\n    <weightTrimRate>" << real_text_d(p->weight_trim_rate)
+      << "</weightTrimRate>\n    <maxDepth>" << p->max_depth << "</maxDepth>\n";
+  }
+  o << "    <maxWeakCount>" << (p ? p->max_weak_count : max_weak) << "</maxWeakCount></stageParams>\n";
+  o << "  <featureParams>\n    <maxCatCount>" << (p ? p->max_cat_count : max_cat) << "</maxCatCount>\n    <featSize>" << (p ? p->feat_size : feat_size)
+    << "</featSize>";
+  if (p && feature_type == CC_FEATURE_HAAR) o << "\n    <mode>" << kModeNames[p->haar_mode] << "</mode>";  // haarfeatures.cpp:28-36
+  o << "</featureParams>\n";
+}
+
+// cc_cascade_save_xml (p == nullptr) and cc_cascade_save_xml_params
+cc_status save_cascade_xml(const char* who, const Cascade& m, const cc_train_params* p, const char* path) {
   const CNumericLocale c_numbers;  // "%.8e" / strtod must not follow the host program's LC_NUMERIC
-  if (!c || !path) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_save_xml: null argument");
-  const Cascade& m = c->m;
   const bool haar = m.feature_type == CC_FEATURE_HAAR, hog = m.feature_type == CC_FEATURE_HOG;
   std::ostringstream o;
   int max_weak = 0;
   for (int n : m.stage_ntrees) max_weak = std::max(max_weak, n);
   o << "<?xml version=\"1.0\"?>\n<opencv_storage>\n<cascade>\n";
-  o << "  <stageType>BOOST</stageType>\n  <featureType>" << (haar ? "HAAR" : hog ? "HOG" : "LBP") << "</featureType>\n";
-  o << "  <height>" << m.win_h << "</height>\n  <width>" << m.win_w << "</width>\n";
-  o << "  <stageParams>\n    <maxWeakCount>" << max_weak << "</maxWeakCount></stageParams>\n";
-  o << "  <featureParams>\n    <maxCatCount>" << m.max_cat_count << "</maxCatCount>\n    <featSize>" << (hog ? 36 : 1)
-    << "</featSize></featureParams>\n";
+  write_params_text(o, m.feature_type, m.win_w, m.win_h, p, max_weak, m.max_cat_count, hog ? 36 : 1);
   o << "  <stageNum>" << m.stage_ntrees.size() << "</stageNum>\n  <stages>\n";
   for (size_t s = 0; s < m.stage_ntrees.size(); s++) {
     // the model keeps (float)stageThreshold - 1e-5f; write back a value that parses to the same float after the
     // reader subtracts the epsilon again: search the neighbourhood of thr + 1e-5f
     float t;
-    if (!stage_threshold_preimage(m.stage_threshold[s], t))
-      return set_error(CC_ERR_UNSUPPORTED, "cc_cascade_save_xml: stage threshold %zu has no float pre-image", s);
+    if (!stage_threshold_preimage(m.stage_threshold[s], t)) return set_error(CC_ERR_UNSUPPORTED, "%s: stage threshold %zu has no float pre-image", who, s);
     o << "    <_>\n      <maxWeakCount>" << m.stage_ntrees[s] << "</maxWeakCount>\n      <stageThreshold>" << real_text(t)
       << "</stageThreshold>\n      <weakClassifiers>\n";
     for (int i = 0; i < m.stage_ntrees[s]; i++) {
@@ -542,6 +627,206 @@ cc_status cc_cascade_save_xml(const cc_cascade* c, const char* path) {
   }
   o << "  </features>\n</cascade>\n</opencv_storage>\n";
   return write_text_file(path, o.str());
+}
+
+}  // namespace
+
+extern "C" {
+
+cc_status cc_cascade_load_xml_mem(const char* text, size_t len, cc_cascade** out) {
+  const CNumericLocale c_numbers;  // "%.8e" / strtod must not follow the host program's LC_NUMERIC
+  if (!text || !out) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_load_xml_mem: null argument");
+  *out = nullptr;
+  XmlNode root;
+  std::string err;
+  if (!xml_parse(text, len, root, err)) return set_error(CC_ERR_PARSE, "cascade XML: %s", err.c_str());
+  cc_cascade* c = new cc_cascade();
+  cc_status st = cascade_from_xml(root, c->m);
+  if (st != CC_OK) {
+    delete c;
+    return st;
+  }
+  *out = c;
+  return CC_OK;
+}
+
+cc_status cc_cascade_load_xml(const char* path, cc_cascade** out) {
+  if (!path || !out) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_load_xml: null argument");
+  *out = nullptr;
+  std::ifstream f(path, std::ios::binary);
+  if (!f) return set_error(CC_ERR_IO, "cannot open '%s'", path);
+  std::stringstream ss;
+  ss << f.rdbuf();
+  std::string s = ss.str();
+  return cc_cascade_load_xml_mem(s.data(), s.size(), out);
+}
+
+void cc_cascade_destroy(cc_cascade* c) { delete c; }
+
+cc_status cc_cascade_save_xml(const cc_cascade* c, const char* path) {
+  if (!c || !path) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_save_xml: null argument");
+  return save_cascade_xml("cc_cascade_save_xml", c->m, nullptr, path);
+}
+
+cc_status cc_cascade_save_xml_params(const cc_cascade* c, const cc_train_params* p, const char* path) {
+  const char* who = "cc_cascade_save_xml_params";
+  if (!c || !p || !path) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
+  if (cc_status st = check_param_names(who, *p); st != CC_OK) return st;
+  if (p->feature_type != c->m.feature_type || p->win_w != c->m.win_w || p->win_h != c->m.win_h)
+    return set_error(CC_ERR_INVALID_ARG, "%s: the parameters are for feature type %d and a %dx%d window, the cascade has %d and %dx%d", who,
+                     p->feature_type, p->win_w, p->win_h, c->m.feature_type, c->m.win_w, c->m.win_h);
+  return save_cascade_xml(who, c->m, p, path);
+}
+
+cc_status cc_cascade_train_params(const cc_cascade* c, cc_train_params* out) {
+  if (!c || !out) return set_error(CC_ERR_INVALID_ARG, "cc_cascade_train_params: null argument");
+  if (!c->m.has_train_params) return set_error(CC_ERR_NO_TRAIN_PARAMS, "cc_cascade_train_params: the cascade carries no training parameters");
+  *out = c->m.train_params;
+  return CC_OK;
+}
+
+cc_status cc_train_params_save_xml(const cc_train_params* p, const char* path, const char* object_name) {
+  const CNumericLocale c_numbers;
+  const char* who = "cc_train_params_save_xml";
+  if (!p || !path) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
+  if (cc_status st = check_param_names(who, *p); st != CC_OK) return st;
+  const std::string name = object_name ? object_name : default_object_name(path);
+  std::ostringstream o;
+  o << "<?xml version=\"1.0\"?>\n<opencv_storage>\n<" << name << ">\n";
+  write_params_text(o, p->feature_type, p->win_w, p->win_h, p, 0, 0, 0);
+  // FileStorage closes a map on the line of its last entry
+  std::string text = o.str();
+  text.pop_back();
+  text += "</" + name + ">\n</opencv_storage>\n";
+  return write_text_file(path, text);
+}
+
+cc_status cc_train_params_load_xml(const char* path, cc_train_params* out) {
+  const CNumericLocale c_numbers;
+  if (!path || !out) return set_error(CC_ERR_INVALID_ARG, "cc_train_params_load_xml: null argument");
+  XmlNode root;
+  if (cc_status st = parse_xml_file(path, root); st != CC_OK) return st;
+  const XmlNode* top = first_top_level(root);
+  if (!top) return set_error(CC_ERR_PARSE, "%s: <opencv_storage> is empty", path);
+  return train_params_from_xml(*top, path, *out);
+}
+
+cc_status cc_stage_save_xml(const char* path, const char* object_name, int max_cat_count, float stage_threshold, int n_weak,
+                            const int32_t* n_nodes, int n_nodes_total, const cc_tree_node* nodes, const float* leaves) {
+  const CNumericLocale c_numbers;
+  const char* who = "cc_stage_save_xml";
+  if (!path || !n_nodes || !nodes || !leaves) return set_error(CC_ERR_INVALID_ARG, "%s: null argument", who);
+  if (max_cat_count < 0 || max_cat_count > 256) return set_error(CC_ERR_INVALID_ARG, "%s: max_cat_count %d outside [0, 256]", who, max_cat_count);
+  if (n_weak < 1) return set_error(CC_ERR_INVALID_ARG, "%s: a stage has at least one weak classifier", who);
+  const int words = (max_cat_count + 31) / 32;
+  size_t total = 0;
+  for (int t = 0; t < n_weak; t++) {
+    if (n_nodes[t] < 1) return set_error(CC_ERR_INVALID_ARG, "%s: weak classifier %d has %d nodes", who, t, n_nodes[t]);
+    total += (size_t)n_nodes[t];
+  }
+  if (n_nodes_total < 0 || total != (size_t)n_nodes_total)
+    return set_error(CC_ERR_INVALID_ARG, "%s: n_nodes adds up to %zu nodes, %d were given", who, total, n_nodes_total);
+  const std::string name = object_name ? object_name : default_object_name(path);
+  std::ostringstream o;
+  o << "<?xml version=\"1.0\"?>\n<opencv_storage>\n<" << name << ">\n";
+  o << "  <maxWeakCount>" << n_weak << "</maxWeakCount>\n  <stageThreshold>" << real_text(stage_threshold) << "</stageThreshold>\n  <weakClassifiers>\n";
+  size_t k = 0;
+  for (int t = 0; t < n_weak; t++) {
+    const int nn = n_nodes[t];
+    o << "    <_>\n      <internalNodes>\n       ";
+    for (int j = 0; j < nn; j++) {
+      const cc_tree_node& nd = nodes[k + (size_t)j];
+      // what the reader asks of child references: inside the tree, and an internal child behind its parent
+      if (nd.left >= nn || nd.right >= nn || nd.left < -nn || nd.right < -nn || (nd.left > 0 && nd.left <= j) || (nd.right > 0 && nd.right <= j))
+        return set_error(CC_ERR_OUT_OF_RANGE, "%s: child index of node %d of weak classifier %d out of range", who, j, t);
+      if (nd.var_idx < 0) return set_error(CC_ERR_OUT_OF_RANGE, "%s: variable %d of weak classifier %d", who, nd.var_idx, t);
+      o << " " << nd.left << " " << nd.right << " " << nd.var_idx;
+      if (words > 0)
+        for (int w = 0; w < words; w++) o << " " << nd.subset[w];
+      else
+        o << " " << real_text(nd.ord_c);
+    }
+    o << "</internalNodes>\n      <leafValues>\n       ";
+    for (int j = 0; j < nn + 1; j++) o << " " << real_text(leaves[k + (size_t)t + (size_t)j]);
+    o << "</leafValues></_>\n";
+    k += (size_t)nn;
+  }
+  o << "  </weakClassifiers></" << name << ">\n</opencv_storage>\n";
+  return write_text_file(path, o.str());
+}
+
+cc_status cc_stage_load_xml(const char* path, int max_cat_count, int n_variables, float* stage_threshold, int* n_weak, int32_t* n_nodes,
+                            int weak_cap, int* n_nodes_total, cc_tree_node* nodes, int node_cap, float* leaves) {
+  const CNumericLocale c_numbers;
+  if (!path || !stage_threshold || !n_weak || !n_nodes_total) return set_error(CC_ERR_INVALID_ARG, "cc_stage_load_xml: null argument");
+  if (max_cat_count < 0 || max_cat_count > 256) return set_error(CC_ERR_INVALID_ARG, "cc_stage_load_xml: max_cat_count %d outside [0, 256]", max_cat_count);
+  *n_weak = *n_nodes_total = 0;
+  XmlNode root;
+  if (cc_status st = parse_xml_file(path, root); st != CC_OK) return st;
+  const XmlNode* top = first_top_level(root);
+  if (!top) return set_error(CC_ERR_PARSE, "%s: <opencv_storage> is empty", path);
+  const int words = (max_cat_count + 31) / 32, step = 3 + (words > 0 ? words : 1);
+  double thr = 0;
+  if (!node_double(top->child("stageThreshold"), thr)) return set_error(CC_ERR_PARSE, "%s: bad or missing <stageThreshold>", path);
+  const XmlNode* weak = top->child("weakClassifiers");
+  if (!weak) return set_error(CC_ERR_PARSE, "%s: <weakClassifiers> is missing", path);
+  std::vector<int32_t> counts;
+  std::vector<cc_tree_node> all;
+  std::vector<float> lv;
+  std::vector<std::string> tk, lt;
+  for (const XmlNode& wn : weak->children) {
+    if (wn.name != "_") continue;
+    const int t = (int)counts.size();
+    const XmlNode* in = wn.child("internalNodes");
+    const XmlNode* ln = wn.child("leafValues");
+    if (!in) return set_error(CC_ERR_PARSE, "%s: weak classifier %d has no <internalNodes>", path, t);
+    if (!ln) return set_error(CC_ERR_PARSE, "%s: weak classifier %d has no <leafValues>", path, t);
+    split_tokens(in->text, tk);
+    if (tk.empty() || tk.size() % (size_t)step)
+      return set_error(CC_ERR_PARSE, "%s: <internalNodes> of weak classifier %d holds %zu numbers, no multiple of the node step %d", path, t, tk.size(), step);
+    const int nn = (int)(tk.size() / (size_t)step);
+    split_tokens(ln->text, lt);
+    if ((int)lt.size() != nn + 1)
+      return set_error(CC_ERR_PARSE, "%s: <leafValues> of weak classifier %d holds %zu values, a tree of %d nodes has %d", path, t, lt.size(), nn, nn + 1);
+    for (int j = 0; j < nn; j++) {
+      const std::string* f = &tk[(size_t)j * (size_t)step];
+      cc_tree_node nd;
+      std::memset(&nd, 0, sizeof(nd));
+      if (!to_int(f[0], nd.left) || !to_int(f[1], nd.right) || !to_int(f[2], nd.var_idx))
+        return set_error(CC_ERR_PARSE, "%s: <internalNodes> of weak classifier %d: node %d is malformed", path, t, j);
+      if (nd.left >= nn || nd.right >= nn || nd.left < -nn || nd.right < -nn)
+        return set_error(CC_ERR_PARSE, "%s: <internalNodes> of weak classifier %d: a child of node %d lies outside the tree", path, t, j);
+      if ((nd.left > 0 && nd.left <= j) || (nd.right > 0 && nd.right <= j))
+        return set_error(CC_ERR_PARSE, "%s: <internalNodes> of weak classifier %d: a child of node %d does not lie behind it (cycle)", path, t, j);
+      if (nd.var_idx < 0 || (n_variables > 0 && nd.var_idx >= n_variables))
+        return set_error(CC_ERR_PARSE, "%s: <internalNodes> of weak classifier %d: featureIdx %d outside [0, %d)", path, t, nd.var_idx, n_variables);
+      if (words > 0) {
+        for (int w = 0; w < words; w++)
+          if (!to_int(f[3 + w], nd.subset[w])) return set_error(CC_ERR_PARSE, "%s: <internalNodes> of weak classifier %d: malformed category subset", path, t);
+      } else {
+        double c = 0;
+        if (!to_double(f[3], c)) return set_error(CC_ERR_PARSE, "%s: <internalNodes> of weak classifier %d: malformed threshold", path, t);
+        nd.ord_c = (float)c;
+      }
+      all.push_back(nd);
+    }
+    for (const std::string& s : lt) {
+      double v = 0;
+      if (!to_double(s, v)) return set_error(CC_ERR_PARSE, "%s: <leafValues> of weak classifier %d: malformed value", path, t);
+      lv.push_back((float)v);
+    }
+    counts.push_back(nn);
+  }
+  if (counts.empty()) return set_error(CC_ERR_PARSE, "%s: <weakClassifiers> holds no weak classifier", path);
+  *stage_threshold = (float)thr;
+  *n_weak = (int)counts.size();
+  *n_nodes_total = (int)all.size();
+  if (!n_nodes || !nodes || !leaves || weak_cap < *n_weak || node_cap < *n_nodes_total)
+    return set_error(CC_ERR_BUFFER_TOO_SMALL, "cc_stage_load_xml: %d weak classifiers with %d nodes need larger buffers", *n_weak, *n_nodes_total);
+  std::copy(counts.begin(), counts.end(), n_nodes);
+  std::copy(all.begin(), all.end(), nodes);
+  std::copy(lv.begin(), lv.end(), leaves);
+  return CC_OK;
 }
 
 cc_status cc_cascade_save_xml_legacy(const cc_cascade* c, const char* path) {

@@ -79,6 +79,9 @@ struct Cascade {
   std::vector<int32_t> haar_tilted;  // [n]
   std::vector<int32_t> lbp_rects;    // [n][4]
   std::vector<int32_t> hog_feats;    // [n][5]: x, y, cell w, cell h of the block's cell 0, component in [0, 36)
+  // the training parameters the file carried, when it carried a whole block of them (section 6d of the header)
+  bool has_train_params = false;
+  cc_train_params train_params = {};
   int n_features() const {
     return feature_type == CC_FEATURE_HAAR ? (int)haar_tilted.size()
            : feature_type == CC_FEATURE_HOG ? (int)(hog_feats.size() / 5)

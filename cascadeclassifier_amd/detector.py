@@ -288,11 +288,29 @@ class CascadeClassifier:
     def empty(self) -> bool:
         return not self._c
 
-    def save(self, filename: str, baseFormat: bool = False):
+    def save(self, filename: str, baseFormat: bool = False, params=None):
         """Write the model back as a cascade.xml: the new-format layout of CvCascadeClassifier::save, or with
-        baseFormat=True its legacy "opencv-haar-classifier" layout (cascadeclassifier.cpp:439-531; Haar only)."""
-        fn = L.lib().cc_cascade_save_xml_legacy if baseFormat else L.lib().cc_cascade_save_xml
-        L.check(fn(self._c, filename.encode()))
+        baseFormat=True its legacy "opencv-haar-classifier" layout (cascadeclassifier.cpp:439-531; Haar only). params (a
+        traincascade.TrainParams or a dict of its fields, as train_params() returns it): the new-format file carries the
+        whole <stageParams> / <featureParams> block of writeParams (cc_cascade_save_xml_params); the legacy layout has no
+        place for it."""
+        if baseFormat or params is None:
+            fn = L.lib().cc_cascade_save_xml_legacy if baseFormat else L.lib().cc_cascade_save_xml
+            L.check(fn(self._c, filename.encode()))
+            return
+        fields = params if isinstance(params, dict) else params.as_dict()
+        p = L.TrainParams(**{n: fields[n] for n, _ in L.TrainParams._fields_})
+        L.check(L.lib().cc_cascade_save_xml_params(self._c, C.byref(p), filename.encode()))
+
+    def train_params(self):
+        """The training parameters the loaded cascade.xml carried, as a dict of cc_train_params' fields, or None when the
+        file had none (cc_cascade_train_params)."""
+        p = L.TrainParams()
+        st = L.lib().cc_cascade_train_params(self._c, C.byref(p))
+        if st == L.CC_ERR_NO_TRAIN_PARAMS:
+            return None
+        L.check(st)
+        return {n: getattr(p, n) for n, _ in p._fields_}
 
     def info(self) -> dict:
         ci = L.CascadeInfo()

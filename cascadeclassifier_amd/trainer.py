@@ -5,6 +5,7 @@ CvFeatureEvaluator.fill_passed, the negatives through NegativeMiner.fill, a stag
 from __future__ import annotations
 
 import math
+import time
 
 import numpy as np
 
@@ -127,10 +128,98 @@ class BackgroundReader:
     def state(self):
         return {"last": self.last, "round": self.round, "current": self.current, "offset": self.offset, "position": self.position}
 
+    def restore(self, state):
+        """The inverse of state(), for a reader over the same list and window: afterwards the reader hands out the windows
+        the reader that gave `state` would have handed out next. ValueError for a state that cannot belong to this list:
+        `last` or `round` out of range, an open image that does not follow from them (`last` stands behind the open image,
+        and `round` fixes its offset), an image too small for the window at that offset, or a position behind the image's
+        stream. Nothing changes when it raises."""
+        try:
+            last, rnd, position = int(state["last"]), int(state["round"]), int(state["position"])
+            current = None if state["current"] is None else int(state["current"])
+            offset = tuple(int(v) for v in state["offset"])
+        except (KeyError, TypeError, ValueError) as err:
+            raise ValueError("BackgroundReader.restore: malformed state (%s)" % err) from None
+        W, H = self.win
+        count = len(self.images)
+        if not 0 <= last < count or not 0 <= rnd < W * H or len(offset) != 2:
+            raise ValueError("BackgroundReader.restore: last %d / round %d do not fit %d images and a %dx%d window" % (last, rnd, count, W, H))
+        if current is None:
+            if (last, rnd, offset, position) != (0, 0, (0, 0), 0):
+                raise ValueError("BackgroundReader.restore: a reader that has opened no image stands at its start")
+        else:
+            if not 0 <= current < count or last != (current + 1) % count:
+                raise ValueError("BackgroundReader.restore: image %d is not the one in front of last = %d" % (current, last))
+            rows, cols = self.images[current].shape
+            if offset != (min(rnd % W, cols - W), min(rnd // W, rows - H)) or min(offset) < 0:
+                raise ValueError("BackgroundReader.restore: offset %s is not the one of round %d in image %d (%dx%d)" % (offset, rnd, current, cols, rows))
+            if not 0 <= position < self.stream_length(current, offset):
+                raise ValueError("BackgroundReader.restore: position %d behind the %d windows of image %d" %
+                                 (position, self.stream_length(current, offset), current))
+        self.last, self.round, self.current, self.offset, self.position = last, rnd, current, offset, position
+
+
+# ---- the transcript: the lines the reference prints while it trains, as std::cout prints their numbers ----
+
+def format_number(x) -> str:
+    """operator<< of a float or double at the stream's defaults: %g, 6 significant digits."""
+    return "%g" % float(x)
+
+
+def loaded_lines(n_loaded):
+    """cascadeclassifier.cpp:203-207"""
+    if n_loaded > 1:
+        return ["", "Stages 0-%d are loaded" % (n_loaded - 1)]
+    return ["", "Stage 0 is loaded"] if n_loaded == 1 else []
+
+
+def stage_begin_lines(i):
+    """cascadeclassifier.cpp:215-216"""
+    return ["", "===== TRAINING %d-stage =====" % i, "<BEGIN"]
+
+
+def fill_lines(record):
+    """updateTrainingSet's two lines (cascadeclassifier.cpp:315, :325); the second only when the set could be filled."""
+    out = ["POS count : consumed   %d : %d" % (record["pos_count"], record["pos_consumed"])]
+    if record["acceptance_ratio"] is not None:
+        out.append("NEG count : acceptanceRatio    %d : %s" % (record["neg_count"], format_number(record["acceptance_ratio"])))
+    return out
+
+
+END_MESSAGES = {
+    END_CANNOT_FILL: "Train dataset for temp stage can not be filled. Branch training terminated.",
+    END_LEAF_FA_RATE: "Required leaf false alarm rate achieved. Branch training terminated.",
+    END_ACCEPTANCE_BREAK: "The required acceptanceRatio for the model has been reached to avoid overfitting of trainingdata. "
+                          "Branch training terminated.",
+}
+_TABLE_RULE = "+----+---------+---------+"
+_STOP_NO_ACTIVE = 3  # CascadeBoost.STOP_NO_ACTIVE: the round ended before isErrDesired, which prints the row
+
+
+def boost_lines(weak, precalc_seconds=0):
+    """What CvCascadeBoost::train prints for one stage: the presort's whole seconds (o_cvcascadeboosttraindata.cpp), the table of
+    isErrDesired (boost.cpp:429-431, :511-515) with one row per round that reached it, and END> (cascadeclassifier.cpp:240)."""
+    out = ["Precalculation time: %s" % format_number(int(precalc_seconds)), _TABLE_RULE, "|  N |    HR   |    FA   |", _TABLE_RULE]
+    n = 0
+    for w in weak:
+        if not w["trained"]:
+            continue
+        n += 1
+        if w["stop"] != _STOP_NO_ACTIVE:
+            out += ["|%4d|%9s|%9s|" % (n, format_number(w["hit_rate"]), format_number(w["false_alarm"])), _TABLE_RULE]
+    return out + ["END>"]
+
+
+def time_line(seconds):
+    """cascadeclassifier.cpp:278-283"""
+    s = int(seconds)
+    return "Training until now has taken %d days %d hours %d minutes %d seconds." % (s // 86400, s // 3600 % 24, s // 60 % 60, s % 60)
+
 
 def train_cascade(positives, backgrounds, num_pos, num_neg, num_stages, *, feature_type=HAAR, win=(24, 24), haar_mode=BASIC,
                   boost_type=BOOST_GENTLE, min_hit_rate=0.995, max_false_alarm=0.5, weight_trim_rate=0.95, max_weak_count=100,
-                  acceptance_ratio_break_value=-1.0, device=0, max_batch=256, on_stage=None, max_depth=1, table_budget_bytes=None):
+                  acceptance_ratio_break_value=-1.0, device=0, max_batch=256, on_stage=None, max_depth=1, table_budget_bytes=None,
+                  initial_stages=None, reader=None, log=None):
     """CvCascadeClassifier::train (cascadeclassifier.cpp:203-284) for stages of weak trees with at most max_depth levels of
     splits (the reference's -maxDepth; 1: stumps). positives: [n][win_h][win_w]
     uint8, taken from the first one again for every stage; backgrounds: 2-D uint8 images, read as NegReader reads its list.
@@ -141,19 +230,41 @@ def train_cascade(positives, backgrounds, num_pos, num_neg, num_stages, *, featu
     free); variables whose tables do not fit are evaluated and sorted again at every node, and the trained cascade is the
     same. None: all tables resident, or an error when they do not fit. The reference's -precalcValBufSize and
     -precalcIdxBufSize size two host caches in MB, one for values and one for sorted indices; here one budget in bytes
-    covers both."""
+    covers both.
+    initial_stages: the stages an earlier run trained, a list of (stage_threshold, [weak dicts]) as from_stumps / from_trees
+    take them (traincascade.read_stage returns one). The loop starts behind them, like startNumStages (:203-213); with
+    num_stages of them or more nothing is trained and the cascade of the first num_stages is returned. The records cover the
+    iterations of this call only. reader: a BackgroundReader over `backgrounds` to go on with instead of a fresh one (its
+    state() inside on_stage is the state behind that stage). log: a callable that gets the reference's transcript, line by
+    line, at the points where the reference prints it."""
+    def say(make, *args):  # the lines are made only for a caller who reads them
+        if log is not None:
+            for line in make(*args):
+                log(line)
+
+    t0 = time.monotonic()
     positives = np.ascontiguousarray(positives, np.uint8)
     win = (int(win[0]), int(win[1]))
     if num_pos < 1 or num_neg < 0 or max_batch < 1 or max_depth < 1:
         raise ValueError("train_cascade: num_pos >= 1, num_neg >= 0, max_batch >= 1, max_depth >= 1")
-    reader = BackgroundReader(backgrounds, win)
+    if reader is None:
+        reader = BackgroundReader(backgrounds, win)
     e = CvFeatureEvaluator.create(feature_type, device)
     e.init(CvFeatureParams(feature_type, haar_mode), num_pos + num_neg, win)
-    miner = NegativeMiner.empty(feature_type, win, device)
+    stages = list(initial_stages or [])[:max(num_stages, 0)]
+
+    def build(stages):  # a record with "nodes" is a tree; one without is the stump of its own fields, for either builder
+        deep = max_depth > 1 or any("nodes" in w for _, ws in stages for w in ws)
+        return (CascadeClassifier.from_trees if deep else CascadeClassifier.from_stumps)(feature_type, win, stages, haar_mode=haar_mode, device=device)
+
+    cascade = build(stages) if stages else None
+    miner = NegativeMiner(cascade, device) if stages else NegativeMiner.empty(feature_type, win, device)
+    say(loaded_lines, len(stages))
     required_leaf_fa_rate = math.pow(float(np.float32(max_false_alarm)), float(num_stages)) / float(max_depth)  # cascadeclassifier.cpp:209-210
-    cascade, stages, records = None, [], []
+    records = []
     end = END_NUM_STAGES
-    for i in range(num_stages):
+    for i in range(len(stages), num_stages):
+        say(stage_begin_lines, i)
         # updateTrainingSet (:308-327)
         pos_count, pos_consumed = e.fill_passed(cascade, positives, 0, num_pos, 1)
         if pos_count < num_pos:  # PosReader::get raises when the file ends (imagestorage.cpp:173-174)
@@ -174,30 +285,35 @@ def train_cascade(positives, backgrounds, num_pos, num_neg, num_stages, *, featu
         records.append(record)
         if neg_count == 0 and not (neg_consumed > 0 and (float(neg_count) + 1) / float(neg_consumed) <= required_leaf_fa_rate):
             end = END_CANNOT_FILL
-            break
-        acceptance = 0.0 if neg_consumed == 0 else float(neg_count) / float(neg_consumed)
-        record["acceptance_ratio"] = acceptance
-        if acceptance <= required_leaf_fa_rate:
-            end = END_LEAF_FA_RATE
-            break
-        if acceptance <= acceptance_ratio_break_value and acceptance_ratio_break_value >= 0:
-            end = END_ACCEPTANCE_BREAK
+        else:
+            acceptance = 0.0 if neg_consumed == 0 else float(neg_count) / float(neg_consumed)
+            record["acceptance_ratio"] = acceptance
+            if acceptance <= required_leaf_fa_rate:
+                end = END_LEAF_FA_RATE
+            elif acceptance <= acceptance_ratio_break_value and acceptance_ratio_break_value >= 0:
+                end = END_ACCEPTANCE_BREAK
+        say(fill_lines, record)
+        if end != END_NUM_STAGES:
+            say(lambda: [END_MESSAGES[end]])
             break
         n = pos_count + neg_count
+        t_presort = time.monotonic()
         if table_budget_bytes is None:
             e.presort(n)
         else:
             e.presort(n, budget_bytes=table_budget_bytes)
+        t_presort = time.monotonic() - t_presort
         weak = CascadeBoost(e, n, boost_type=boost_type, weight_trim_rate=weight_trim_rate, min_hit_rate=min_hit_rate,
                             max_false_alarm=max_false_alarm, max_weak_count=max_weak_count, max_depth=max_depth).train_stage()
+        say(boost_lines, weak, t_presort)
         if not any(w["trained"] for w in weak):
             end = END_STAGE_NOT_TRAINED
             break
         record["weak"] = weak
         stages.append((weak[-1]["stage_threshold"], weak))
-        build = CascadeClassifier.from_trees if max_depth > 1 else CascadeClassifier.from_stumps
-        cascade = build(feature_type, win, stages, haar_mode=haar_mode, device=device)
+        cascade = build(stages)
         miner = NegativeMiner(cascade, device)
         if on_stage is not None:
             on_stage(i, record, cascade)
+        say(lambda: [time_line(time.monotonic() - t0)])
     return cascade, records, end

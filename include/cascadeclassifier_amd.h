@@ -42,7 +42,8 @@ enum {
   CC_ERR_PARSE = -5,            /* malformed cascade XML */
   CC_ERR_UNSUPPORTED = -6,      /* valid input the GPU path does not implement yet (message says which) */
   CC_ERR_BUFFER_TOO_SMALL = -7, /* output capacity too small; the required size is reported */
-  CC_ERR_OUT_OF_RANGE = -8
+  CC_ERR_OUT_OF_RANGE = -8,
+  CC_ERR_NO_TRAIN_PARAMS = -9   /* a cascade file or model without training parameters (section 6d); not a parse error */
 };
 
 CC_API const char* cc_last_error(void);
@@ -828,6 +829,65 @@ CC_API cc_status cc_debug_fill_select(int device, const uint8_t* flags, int64_t 
                                       int64_t consumed_before, double ratio, int* n_filled, int64_t* n_consumed, int* stop,
                                       int64_t* keep_index);
 CC_API int cc_debug_fill_scan_tile(void); /* positions per block of the scan */
+
+/* ============================================================================================
+ * 6d. The trainer's files: params.xml, stage<i>.xml and a cascade.xml that carries the training parameters.
+ *    Replaces the file side of CvCascadeClassifier::train / load (traincascade/lib/src/cascadeclassifier.cpp:247-275,
+ *    :359-364, :534-564): CvCascadeParams::write / read (:33-73), CvCascadeBoostParams::write / read (boost.cpp:58-95),
+ *    CvFeatureParams::write / read (features.cpp:47-60), CvHaarFeatureParams::write / read (haarfeatures.cpp:28-52),
+ *    CvCascadeBoost::write (boost.cpp:520-532) and CvCascadeBoostTree::write / read (o_cvcascadeboosttree.cpp:41-165).
+ *    Host code, no device needed. Tags, their order and their values follow those functions; the byte layout of OpenCV's
+ *    FileStorage (indentation, line wrapping, digits of a real) is NOT pinned, as for cascade.xml: there is no OpenCV to
+ *    compare with. Floats are written with 9 significant digits and doubles with 17, so every number parses back to
+ *    itself; all formatting and parsing runs under the "C" numeric locale.
+ * ============================================================================================ */
+typedef struct cc_train_params {
+  int32_t feature_type, win_w, win_h;  /* CC_FEATURE_*; <width>, <height> */
+  int32_t boost_type;                  /* CvBoost: DISCRETE 0 "DAB", REAL 1 "RAB", LOGIT 2 "LB", GENTLE 3 "GAB" */
+  float min_hit_rate, max_false_alarm; /* <minHitRate>, <maxFalseAlarm> */
+  double weight_trim_rate;             /* <weightTrimRate>: a double in the reference, and kept bit for bit */
+  int32_t max_depth, max_weak_count;
+  int32_t max_cat_count, feat_size;    /* LBP 256 / 1, HAAR 0 / 1, HOG 0 / 36 */
+  int32_t haar_mode;                   /* CC_HAAR_BASIC / CORE / ALL "BASIC|CORE|ALL"; written and read for HAAR only */
+} cc_train_params;
+
+/* params.xml: <stageType> <featureType> <height> <width>, <stageParams> { boostType minHitRate maxFalseAlarm weightTrimRate
+ * maxDepth maxWeakCount }, <featureParams> { maxCatCount featSize [mode] } inside one top-level element. object_name names
+ * that element; NULL: the name FileStorage::getDefaultObjectName derives from the file name ("params" for params.xml). The
+ * values are written as given; CC_ERR_INVALID_ARG for a feature type, boost type or Haar mode that has no name. */
+CC_API cc_status cc_train_params_save_xml(const cc_train_params* p, const char* path, const char* object_name);
+/* Reads the block back from a params.xml or from a cascade.xml (the first element under <opencv_storage>). Tolerated: the
+ * historical <featuhreParams>, type_id attributes, comments; a missing <featSize> / <maxCatCount> takes the feature type's
+ * default. The range checks of the three read()s fail with CC_ERR_PARSE and name the tag: stageType BOOST, featureType
+ * HAAR|LBP|HOG, height > 0, width > 0; boostType DAB|RAB|LB|GAB, minHitRate, maxFalseAlarm and weightTrimRate in (0, 1],
+ * maxDepth > 0, maxWeakCount > 0; maxCatCount >= 0, featSize >= 1, and for HAAR mode BASIC|CORE|ALL. A block whose
+ * <stageParams> has no <boostType> -- what cc_cascade_save_xml writes -- is CC_ERR_NO_TRAIN_PARAMS, not a parse error. */
+CC_API cc_status cc_train_params_load_xml(const char* path, cc_train_params* out);
+/* The training parameters a loaded cascade.xml carried: CC_OK, or CC_ERR_NO_TRAIN_PARAMS when the file had none that pass
+ * the checks above (loading the model does not depend on them) or the cascade was built by cc_cascade_from_stumps / _trees. */
+CC_API cc_status cc_cascade_train_params(const cc_cascade* c, cc_train_params* out);
+/* cc_cascade_save_xml with the whole <stageParams> / <featureParams> block of writeParams (cascadeclassifier.cpp:359-364)
+ * in place of its short one; every other byte is the same, and the file loads to the same model. feature_type and window
+ * of p must be the cascade's: CC_ERR_INVALID_ARG. */
+CC_API cc_status cc_cascade_save_xml_params(const cc_cascade* c, const cc_train_params* p, const char* path);
+
+/* stage<i>.xml, as tempStage->write(fs, Mat()) leaves it: <maxWeakCount> (the number of trees), <stageThreshold> (the
+ * trained threshold itself, NOT threshold - 1e-5f) and <weakClassifiers>, per tree <internalNodes> = per node "left right
+ * featureIdx (threshold | subset words)" and <leafValues>. featureIdx is the CATALOG index of the variable (HOG: the
+ * variable index): nothing is renumbered, the feature map is empty. The writer takes one stage of what
+ * cc_cascade_from_trees takes: n_weak trees, n_nodes[t] nodes each (left, right, var_idx and ord_c or subset are written),
+ * n_nodes_total nodes and n_nodes_total + n_weak leaves. max_cat_count > 0 (LBP: 256) writes (max_cat_count + 31) / 32 <= 8
+ * subset words per node, 0 the threshold. object_name as above ("stage3" for stage3.xml). */
+CC_API cc_status cc_stage_save_xml(const char* path, const char* object_name, int max_cat_count, float stage_threshold, int n_weak,
+                                   const int32_t* n_nodes, int n_nodes_total, const cc_tree_node* nodes, const float* leaves);
+/* Reads it back into the same arrays (the fields of a node that the file does not hold are 0). *n_weak and *n_nodes_total are
+ * always set when the file parses; with weak_cap < *n_weak, node_cap < *n_nodes_total or a NULL array the call returns
+ * CC_ERR_BUFFER_TOO_SMALL and fills nothing else (leaves needs *n_nodes_total + *n_weak entries). Refused with CC_ERR_PARSE,
+ * naming the file and the tag: an <internalNodes> length that is no multiple of the node step 3 + (subset words | 1), child
+ * references outside the tree or not behind their parent, a <leafValues> count other than nodes + 1, and -- with
+ * n_variables > 0, the catalog size -- a featureIdx outside [0, n_variables). */
+CC_API cc_status cc_stage_load_xml(const char* path, int max_cat_count, int n_variables, float* stage_threshold, int* n_weak,
+                                   int32_t* n_nodes, int weak_cap, int* n_nodes_total, cc_tree_node* nodes, int node_cap, float* leaves);
 
 /* ============================================================================================
  * 7. Multi-GPU: the gather of detections (BASELINE configs[3]).
