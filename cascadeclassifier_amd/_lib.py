@@ -183,6 +183,7 @@ SIGNATURES = {
     "cc_debug_vnf_check": (_i, [_i, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cc_debug_wave_int_tables": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cc_debug_spec_step1_plan": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "cc_debug_spec_step2_plan": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "cc_group_rectangles": (_i, [_vp, _i, _i, _d, _vp, _i, C.POINTER(_i)]),
     "cc_group_rectangles_device": (_i, [_i, _vp, _vp, _i, _i, _d, _vp, _i, _vp, C.POINTER(_i)]),
     "cc_group_rectangles_levels": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _i, C.POINTER(_i)]),

@@ -26,7 +26,12 @@ constexpr int TILE_X = 64;   // window origins per tile row = one wavefront = on
 constexpr int TILE_Y = CC_TILE_Y;   // window origin rows per tile
 constexpr int EVAL_THREADS = CC_EVAL_THREADS;  // wavefronts sharing one LDS tile (more waves per LDS byte = better latency hiding)
 constexpr int EVAL_WAVES = EVAL_THREADS / 64;
-constexpr int WIN_PER_THREAD = TILE_Y / EVAL_WAVES;  // window rows per thread in the dense phase
+// Window rows per thread in the dense phase. A tile height that is no multiple of the block's wavefronts (the run-time
+// STEP-2 Haar module: 10 rows) deals tile row r to wavefront r % EVAL_WAVES -- wavefront w walks rows w, w + EVAL_WAVES, ... --
+// and a wavefront skips, by a wave-uniform test, the round whose row lies beyond the tile (EvalTile::own_row / has_row).
+// Heights that are multiples keep wavefront w on rows w * WIN_PER_THREAD ...: the code of those builds is unchanged.
+constexpr int WIN_PER_THREAD = (TILE_Y + EVAL_WAVES - 1) / EVAL_WAVES;
+constexpr bool RAGGED_ROWS = TILE_Y % EVAL_WAVES != 0;
 // largest power of two <= EVAL_WAVES: the most slices the stump-split path cuts a stage into
 constexpr int SPEC_PARTS = EVAL_WAVES >= 8 ? 8 : EVAL_WAVES >= 4 ? 4 : EVAL_WAVES >= 2 ? 2 : 1;
 
@@ -140,12 +145,15 @@ __host__ __device__ inline int tile_words_padded(int tile_words) { return (tile_
 // u16[QUEUE_ROWS][32] + 3 x 32 class counters. tile_y: window rows per tile of the build in question (the run-time
 // specialised kernel may be compiled with another CC_TILE_Y than this translation unit).
 //
-// lean = the layout of the run-time specialised Haar module of STEP-1 tiles (CC_LEAN_LDS; no tilted tile), whose tall
+// lean = the layout of the run-time specialised Haar modules of one step each (CC_LEAN_LDS; no tilted tile), whose tall
 // tiles must not pay for side tables: integral tile + vnf [tile_y][TILE_X], every row rotated instead of padded (vnf_slot)
 // + the 2 queue tables + the counters. The tables grow towards each other from the two ends of their area -- row r of
 // table 0 is the area's r-th row of 32 entries, row r of table 1 its r-th row from the end -- and what the other layout
 // keeps in s_part lives in the part of that area that is dead at the time: the stump-split phase's partial sums in the gap
 // between the tables (lean_split_gap_bytes), the wave phases' window lists in the table that no longer receives windows.
+// This is THE sum: what the launcher requests and what EvalTile's pointers divide up. Nothing is added to it: the module of
+// STEP-2 tiles ends exactly on an allocation unit at 10 rows of a 24x24 window (lds_blocks_resident), and bytes put between
+// its queue tables beyond that were measured to cost a resident block (profiles/EXPERIMENTS.md 3.24).
 __host__ __device__ inline size_t eval_lds_bytes(int tile_words, bool tilted, bool haar = true, int tile_y = TILE_Y, bool lean = false) {
   if (lean) return (size_t)tile_words_padded(tile_words) * 4 + tile_y * TILE_X * 4 + 2 * (tile_y * TILE_X) * 2 + 3 * 32 * 4;
   return (size_t)tile_words_padded(tile_words) * 4 * (tilted ? 2 : 1) + PART_DOUBLES * 8 + (haar ? tile_y * VNF_PITCH * 4 : 0) +
@@ -161,6 +169,16 @@ __host__ __device__ inline int split_part_bytes(int ns) { return (ns - 1) * (EVA
 constexpr int CU_LDS_BYTES = 160 * 1024;
 __host__ __device__ inline int lds_blocks_per_cu(size_t lds_bytes) {
   const int n = (int)((size_t)CU_LDS_BYTES / (lds_bytes ? lds_bytes : 1)), cap = 32 / EVAL_WAVES;
+  return n > cap ? cap : n;
+}
+// The same with a block's request rounded up to units of 1 280 bytes (1 / 128 of the CU's LDS). Measured on the STEP-2 Haar
+// module (profiles/EXPERIMENTS.md 3.24): requests of 31 072, 31 792 and 32 000 bytes (25 units) run five blocks to a CU,
+// 32 256, 32 512 and 32 768 bytes (26 units) run four, although 5 x 32 768 is the CU's 160 KiB and the runtime's occupancy
+// query answers 5 for all of them. The height of the STEP-2 module is chosen by this count.
+constexpr int LDS_ALLOC_BYTES = 1280;
+__host__ __device__ inline int lds_blocks_resident(size_t lds_bytes) {
+  const size_t units = (lds_bytes + LDS_ALLOC_BYTES - 1) / LDS_ALLOC_BYTES;
+  const int n = (int)((size_t)(CU_LDS_BYTES / LDS_ALLOC_BYTES) / (units ? units : 1)), cap = 32 / EVAL_WAVES;
   return n > cap ? cap : n;
 }
 

@@ -384,9 +384,9 @@ struct EvalTile {
   const int W0 = A.W0, H0 = A.H0;
 #endif
   const Geom G{W0, H0};
-  // lean LDS layout (eval_lds_bytes): the run-time specialised Haar module of STEP-1 tiles, compiled with CC_LEAN_LDS
+  // lean LDS layout (eval_lds_bytes): the run-time specialised Haar modules of one step each, compiled with CC_LEAN_LDS
 #ifdef CC_LEAN_LDS
-  static constexpr bool kLean = HAAR && !TREES && STEP == 1;
+  static constexpr bool kLean = HAAR && !TREES;
 #else
   static constexpr bool kLean = false;
 #endif
@@ -418,6 +418,10 @@ struct EvalTile {
   __device__ __forceinline__ EvalTile(const EvalArgs& A_, int32_t* lds_, const int4 T_, const ScaleDev& S_) : A(A_), lds(lds_), T(T_), S(S_) {}
 
   // ---- the rules the phases share ---------------------------------------------------------------------------------
+  // Tile row of this wavefront's k-th round of the staging and dense phases, and whether the tile has that row (wave-uniform;
+  // only the last round of a height that is no multiple of the wavefronts can lie beyond the tile). See WIN_PER_THREAD.
+  __device__ __forceinline__ int own_row(int k) const { return RAGGED_ROWS ? wave + k * EVAL_WAVES : wave * WIN_PER_THREAD + k; }
+  __device__ __forceinline__ bool has_row(int k) const { return !RAGGED_ROWS || k < WIN_PER_THREAD - 1 || own_row(k) < TILE_Y; }
   __device__ __forceinline__ void stamp(int slot) const {  // wavefront 0 only; the buffer is read by nothing but the experiment's host code
     if (A.stamps && threadIdx.x == 0)
       A.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * STAMP_SLOTS + slot] = __builtin_amdgcn_s_memtime();
@@ -623,10 +627,10 @@ struct EvalTile {
 #pragma unroll
     for (int k = 0; k < WIN_PER_THREAD; k++) {
       sq_raw[k][0] = sq_raw[k][1] = sq_raw[k][2] = sq_raw[k][3] = 0;
-      if (HAAR) {
+      if (HAAR && has_row(k)) {
         // windows outside the grid read the last grid window's corners (unconditional loads: a branch here would make the
         // compiler wait for the data on the spot); they are never alive
-        const int gx = min(gx0 + lane, S.nx - 1), gy = min(gy0 + wave * WIN_PER_THREAD + k, S.ny - 1);
+        const int gx = min(gx0 + lane, S.nx - 1), gy = min(gy0 + own_row(k), S.ny - 1);
         const unsigned* sq = reinterpret_cast<const unsigned*>(A.integ + ((size_t)frame * A.nchan + 1) * A.int_frame_elems + S.int_ofs);
         const int nrx = W0 - 2, nry = H0 - 2;
         size_t q0;
@@ -672,7 +676,8 @@ struct EvalTile {
     [[maybe_unused]] const int nt0 = stage_ntrees[0];
 #pragma unroll 1
     for (int k = 0; k < WIN_PER_THREAD; k++) {
-      const int ly = wave * WIN_PER_THREAD + k;
+      if (!has_row(k)) continue;
+      const int ly = own_row(k);
       const int32_t* b = lds + (ly * STEP) * G.row_stride + lane;
       const bool alive = gx < S.nx && gy0 + ly < S.ny;
       double acc = 0.;
@@ -694,11 +699,11 @@ struct EvalTile {
     const int gx = gx0 + lane;
 #pragma unroll
     for (int k = 0; k < WIN_PER_THREAD; k++) {
-      const int ly = wave * WIN_PER_THREAD + k;
+      const int ly = own_row(k);
       const int gy = gy0 + ly;
       base[k] = (ly * STEP) * G.row_stride + lane;
       vnf[k] = 1.f;
-      alive[k] = gx < S.nx && gy < S.ny;
+      alive[k] = has_row(k) && gx < S.nx && gy < S.ny;
       if (HAAR) {
         const bool in_grid = alive[k];
         alive[k] = false;
@@ -750,11 +755,12 @@ struct EvalTile {
         }
       } else {
 #ifdef CC_SPEC_STAGES  // the generated stage 0: the two rows of a thread together where the tile gives it two
-        if constexpr (WIN_PER_THREAD == 2) {
+        if constexpr (WIN_PER_THREAD == 2 && !RAGGED_ROWS) {
           spec_stage0_x2<STEP>(lds + base[0], lds + base[1], vnf[0], vnf[1], acc[0], acc[1]);
         } else {
 #pragma unroll
-          for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] = spec_stage<STEP>(0, 0, SPEC_PARTS, lds + base[k], vnf[k]);
+          for (int k = 0; k < WIN_PER_THREAD; k++)
+            if (has_row(k)) acc[k] = spec_stage<STEP>(0, 0, SPEC_PARTS, lds + base[k], vnf[k]);
         }
 #else
         if constexpr (HAAR) {
@@ -763,13 +769,15 @@ struct EvalTile {
           for (int i = 0; i < nt; i++) {
             const Stump nxt = load_record(stumps + min(i + 1, nt - 1));
 #pragma unroll
-            for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] += stump_vote(LdsReader{lds + base[k]}, cur, vnf[k]);
+            for (int k = 0; k < WIN_PER_THREAD; k++)
+              if (has_row(k)) acc[k] += stump_vote(LdsReader{lds + base[k]}, cur, vnf[k]);
             cur = nxt;
           }
         } else {
           for (int i = 0; i < nt; i++) {
 #pragma unroll
-            for (int k = 0; k < WIN_PER_THREAD; k++) acc[k] += stump_vote(LdsReader{lds + base[k]}, stumps + i, vnf[k]);
+            for (int k = 0; k < WIN_PER_THREAD; k++)
+              if (has_row(k)) acc[k] += stump_vote(LdsReader{lds + base[k]}, stumps + i, vnf[k]);
           }
         }
 #endif
@@ -779,11 +787,13 @@ struct EvalTile {
     unsigned long long* const mask_col = mask_column();
     bool pass_k[WIN_PER_THREAD];
 #pragma unroll
-    for (int k = 0; k < WIN_PER_THREAD; k++) pass_k[k] = stage0_outcome(wave * WIN_PER_THREAD + k, alive[k], acc[k], thr, mask_col);
+    for (int k = 0; k < WIN_PER_THREAD; k++)  // (a row beyond the tile is another block's: no mask word, nothing delivered)
+      pass_k[k] = has_row(k) && stage0_outcome(own_row(k), alive[k], acc[k], thr, mask_col);
     const bool last_group = A.nstages == 1;
 #pragma unroll
     for (int k = 0; k < WIN_PER_THREAD; k++) {
-      const int id = (wave * WIN_PER_THREAD + k) * 64 + lane;
+      if (!has_row(k)) continue;
+      const int id = own_row(k) * 64 + lane;
       if (HAAR && pass_k[k] && !last_group) s_vnf[vnf_slot(id)] = vnf[k];  // LBP blocks have no s_vnf area (eval_lds_bytes)
       deliver(pass_k[k], id, acc[k], last_group, 1);
     }

@@ -635,7 +635,8 @@ static const char kSpecPrelude[] =
 //   block to fill their wavefronts with; at 26 KB per block six blocks fit a CU (6 wavefronts per SIMD: 80 VGPRs).
 //   Stock LBP cascade, ms per 32 Full-HD frames alone (round-4 run, script not kept): 8 rows 4.90, 12 rows 4.25, 16 rows 3.96, 20 rows 3.78,
 //   24 rows 3.85, 32 rows 4.12 (each at its best register budget).
-// * Haar kernels with 32-bit tiles: TWO modules, one per step -- 20 rows for the STEP-1 tiles, 8 for the STEP-2 tiles. A
+// * Haar kernels with 32-bit tiles: TWO modules, one per step -- 20 rows for the STEP-1 tiles, 10 for the STEP-2 tiles
+//   (spec_step2_rows; 8 in the padded layout until profiles/EXPERIMENTS.md 3.24). A
 //   STEP-1 tile is a third of a STEP-2 tile (12.7 KB against 24 KB at 12 rows), but one launch requests the larger of the two
 //   for every block. ms per 32 Full-HD frames alone, one run (round-4 run, script not kept): one module at 8 rows 8.35; two
 //   modules at 8 / 8 rows 7.82, 12 / 8 rows 7.32, 12 / 12 rows 7.49, 16 / 12 rows 7.77, 12 / 16 rows 8.11 (STEP-1 / STEP-2; a
@@ -643,21 +644,29 @@ static const char kSpecPrelude[] =
 //   register budget for the blocks its own request allows, and a wave_below of its own (spec_wave_below); for a 24x24 window
 //   12 / 16 / 20 / 24 rows are 19.2 / 22.7 / 26.1 / 29.6 KB per block = 8 / 7 / 6 / 5 blocks per CU, and its launch takes
 //   2.61 / 2.97 / 2.45 / 2.77 ms per 32 frames (2.78 / 2.99 / 2.65 / 3.09 with the padded layout at 7 / 6 / 5 / 4 blocks;
-//   profiles/EXPERIMENTS.md 3.22). Larger windows: spec_step1_rows.
+//   profiles/EXPERIMENTS.md 3.22). Larger windows: spec_step1_rows. The STEP-2 module has the same layout and the detector's
+//   wave_below; its launch takes 4.24 ms at 8 rows padded, 4.33 / 4.20 / 4.05 / 4.48 / 4.33 ms at 8 / 9 / 10 / 11 / 12 rows lean.
 // * everything else (Haar with 16-bit tiles): one module at the library's 8 rows.
-// CCAMD_SPEC_TILE_Y sets every module's rows, CCAMD_SPEC_TILE_Y1 / _Y2 the STEP-1 / STEP-2 module's, CCAMD_SPEC_ONE_MODULE=1
+// CCAMD_SPEC_TILE_Y sets every module's rows, CCAMD_SPEC_TILE_Y1 / _Y2 the STEP-1 / STEP-2 module's (the Haar STEP-2 module: any
+// height from 8 to 12), CCAMD_SPEC_ONE_MODULE=1
 // forces a single module (tuning).
 struct SpecModulePlan {
   int only_step, tile_y;
 };
-// The Haar module of STEP-1 tiles takes the lean LDS layout (eval_lds_bytes; compiled with CC_LEAN_LDS): it is the one
-// module whose tiles grow tall. (Tilted cascades never get a module per step.)
+// The Haar modules of one step each take the lean LDS layout (eval_lds_bytes; compiled with CC_LEAN_LDS): their tiles grow
+// taller than the library's. (Tilted cascades never get a module per step.)
 static bool spec_lean_lds(const Cascade& m, int tmode, int only_step) {
-  return only_step == 1 && tmode == TILE_32 && m.feature_type == CC_FEATURE_HAAR && !m.has_tilted;
+  return (only_step == 1 || only_step == 2) && tmode == TILE_32 && m.feature_type == CC_FEATURE_HAAR && !m.has_tilted;
 }
-// LDS request of one block of the STEP-1 Haar module at `tile_y` window rows.
+// LDS request of one block of the STEP-1 / STEP-2 Haar module at `tile_y` window rows (lean layout).
 static size_t spec_step1_lds(const Cascade& m, int tile_y) {
   return eval_lds_bytes(TileGeom<1>(m.win_w, m.win_h, tile_y).words(), false, true, tile_y, true);
+}
+static size_t spec_step2_lds(const Cascade& m, int tile_y) {
+  return eval_lds_bytes(TileGeom<2>(m.win_w, m.win_h, tile_y).words(), false, true, tile_y, true);
+}
+static size_t spec_lean_request(const Cascade& m, int only_step, int tile_y) {
+  return only_step == 2 ? spec_step2_lds(m, tile_y) : spec_step1_lds(m, tile_y);
 }
 // Window rows of the STEP-1 Haar module's tiles: `want`, or for windows whose tile is too large for that, the tallest
 // height below it (a multiple of the block's wavefronts) that still lets kSpecStep1MinBlocks blocks share a CU -- below that
@@ -670,25 +679,51 @@ static int spec_step1_rows(const Cascade& m, int want) {
   while (ty - EVAL_WAVES >= TILE_Y && lds_blocks_per_cu(spec_step1_lds(m, ty)) < kSpecStep1MinBlocks) ty -= EVAL_WAVES;
   return ty;
 }
+// Window rows of the STEP-2 Haar module's tiles: the tallest height from the library's TILE_Y up to kSpecStep2MaxRows whose
+// lean request runs as many blocks on a CU as the lean request at TILE_Y rows does, counted in allocation units
+// (lds_blocks_resident). 24x24: 10 rows, 32 000 bytes = 25 units, 5 blocks like the 8 rows before them; 11 rows are 27 units
+// and 4 blocks. A taller tile pools more windows per block -- fuller table rows in the compacted stages, the per-block work
+// of every stage paid once per more windows -- and a STEP-2 tile that costs a resident block for it has never paid
+// (profiles/EXPERIMENTS.md 3.2, 3.24). The lean request at TILE_Y rows is below the padded one of the module it replaces, so
+// no window size ends with fewer blocks than it had. Any height is allowed: see WIN_PER_THREAD for heights that are no
+// multiple of the block's wavefronts.
+constexpr int kSpecStep2MaxRows = 12;
+static int spec_step2_rows(const Cascade& m) {
+  const int blocks = lds_blocks_resident(spec_step2_lds(m, TILE_Y));
+  if (blocks < 1) return TILE_Y;  // a window whose 8-row tile exceeds the CU's LDS: no height helps
+  int ty = TILE_Y;
+  while (ty + 1 <= kSpecStep2MaxRows && lds_blocks_resident(spec_step2_lds(m, ty + 1)) >= blocks) ty++;
+  return ty;
+}
+// Blocks per CU a lean module's register budget is compiled for.
+static int spec_lean_blocks(const Cascade& m, int only_step, int tile_y) {
+  return only_step == 2 ? lds_blocks_resident(spec_step2_lds(m, tile_y)) : lds_blocks_per_cu(spec_step1_lds(m, tile_y));
+}
 // EvalArgs::wave_below of one module. The detector's value (configure_detector: 24) was tuned on tiles of 8 window rows. The
 // module of STEP-1 tiles pools 768 and more windows per block, and its blocks reach the wave phase with more windows each:
 // kStep1WaveBelow for tiles of 12 rows and more (measured at 12 and 20 rows: 16 +4.9 / +3.2 %, 24 0, 32 -1.2 / -1.8 %, 40 and
 // 56 at 20 rows -0.4 / -0.5 %; profiles/EXPERIMENTS.md 3.22). -1 = the detector's value: every other module, a wave phase
-// that is off, and under CCAMD_WAVE_BELOW (which then holds for all modules). CCAMD_WAVE_BELOW1: the STEP-1 module's value (tuning).
+// that is off, and under CCAMD_WAVE_BELOW (which then holds for all modules). CCAMD_WAVE_BELOW1 / CCAMD_WAVE_BELOW2: the STEP-1 /
+// STEP-2 module's value (tuning).
 constexpr int kStep1WaveBelow = 32;
 int spec_wave_below(int detector_value, int only_step, int tile_y) {
-  if (only_step != 1 || detector_value <= 0) return -1;
-  if (const char* e = std::getenv("CCAMD_WAVE_BELOW1")) return std::max(0, std::min(64, std::atoi(e)));
+  if ((only_step != 1 && only_step != 2) || detector_value <= 0) return -1;
+  if (const char* e = std::getenv(only_step == 1 ? "CCAMD_WAVE_BELOW1" : "CCAMD_WAVE_BELOW2")) return std::max(0, std::min(64, std::atoi(e)));
+  // the STEP-2 module keeps the detector's value: at 10 rows 32 and 40 are within the spread of 24 (profiles/EXPERIMENTS.md 3.24)
+  if (only_step == 2) return -1;
   if (std::getenv("CCAMD_WAVE_BELOW") || tile_y < 12) return -1;
   return std::max(detector_value, kStep1WaveBelow);
 }
 
 static std::vector<SpecModulePlan> spec_modules(const Cascade& m, int tmode) {
-  auto valid = [&](int ty) { return ty >= EVAL_WAVES && ty <= 32 && ty % EVAL_WAVES == 0; };
-  auto env_rows = [&](const char* name, int dflt) {
+  // the STEP-2 Haar module takes any height from the library's to kSpecStep2MaxRows, every other module whole rows per wavefront
+  auto valid = [&](int ty, bool any_height) {
+    return any_height ? ty >= TILE_Y && ty <= kSpecStep2MaxRows : ty >= EVAL_WAVES && ty <= 32 && ty % EVAL_WAVES == 0;
+  };
+  auto env_rows = [&](const char* name, int dflt, bool any_height = false) {
     const char* e = std::getenv(name);
     const int v = e ? std::atoi(e) : dflt;
-    return valid(v) ? v : dflt;
+    return valid(v, any_height) ? v : dflt;
   };
   // (cascades with tilted features keep the library's tile height: their records and generated offsets carry the distance
   // between the sum tile and the tilted tile behind it, which depends on the tile's rows)
@@ -699,7 +734,8 @@ static std::vector<SpecModulePlan> spec_modules(const Cascade& m, int tmode) {
   const int all = env_rows("CCAMD_SPEC_TILE_Y", lbp16 ? 20 : TILE_Y);
   const bool two = (haar32 || std::getenv("CCAMD_SPEC_TWO_MODULES")) && !std::getenv("CCAMD_SPEC_ONE_MODULE");
   if (!two) return {{0, all}};
-  return {{2, env_rows("CCAMD_SPEC_TILE_Y2", all)}, {1, env_rows("CCAMD_SPEC_TILE_Y1", (haar32 && !rows_given) ? spec_step1_rows(m, kSpecStep1Rows) : all)}};
+  const bool lean2 = spec_lean_lds(m, tmode, 2);
+  return {{2, env_rows("CCAMD_SPEC_TILE_Y2", (lean2 && !rows_given) ? spec_step2_rows(m) : all, lean2)}, {1, env_rows("CCAMD_SPEC_TILE_Y1", (haar32 && !rows_given) ? spec_step1_rows(m, kSpecStep1Rows) : all)}};
 }
 
 // lean_blocks: 0, or this is the module with the lean LDS layout and its LDS request lets that many blocks share a CU.
@@ -717,7 +753,7 @@ static cc_status compile_specialised(const std::string& src, const std::string& 
   int min_waves = tile16 ? (tile_y >= 20 ? 6 : 7) : CC_EVAL_MIN_WAVES_PER_EU;
   if (lean_blocks > 0) {
     min_waves = std::max(1, std::min(8, lean_blocks * EVAL_WAVES / 4));
-    if (const char* e = std::getenv("CCAMD_SPEC_WAVES1")) min_waves = std::max(1, std::min(8, std::atoi(e)));
+    if (const char* e = only_step == 1 ? std::getenv("CCAMD_SPEC_WAVES1") : nullptr) min_waves = std::max(1, std::min(8, std::atoi(e)));
   }
   const std::string o_w = "-DCC_EVAL_MIN_WAVES_PER_EU=" + std::to_string(min_waves);
   const std::string o_step = "-DCC_ONLY_STEP=" + std::to_string(only_step);
@@ -874,7 +910,7 @@ cc_status spec_build(const Cascade& m, int n_stages, const std::string& arch, st
     SpecCode c;
     c.only_step = mp.only_step;
     c.tile_y = mp.tile_y;
-    const int lean_blocks = spec_lean_lds(m, tmode, mp.only_step) ? std::max(1, lds_blocks_per_cu(spec_step1_lds(m, mp.tile_y))) : 0;
+    const int lean_blocks = spec_lean_lds(m, tmode, mp.only_step) ? std::max(1, spec_lean_blocks(m, mp.only_step, mp.tile_y)) : 0;
     const cc_status st = compile_specialised(src, arch, k, m.feature_type == CC_FEATURE_LBP, tmode, mp.tile_y, mp.only_step, m.win_w, m.win_h, lean_blocks, c.code);
     if (st != CC_OK) return st;
     codes.push_back(std::move(c));
@@ -909,7 +945,7 @@ cc_status spec_load(const Cascade& m, const std::vector<SpecCode>& codes, int tm
       const TileGeom<1> G1(m.win_w, m.win_h, ty);
       const TileGeom<2> G2(m.win_w, m.win_h, ty);
       const int words = step == 1 ? G1.words() : step == 2 ? G2.words() : std::max(G1.words(), G2.words());
-      x.lds = spec_lean_lds(m, tmode, step) ? spec_step1_lds(m, ty) : eval_lds_bytes(words, m.has_tilted, haar_k, ty);
+      x.lds = spec_lean_lds(m, tmode, step) ? spec_lean_request(m, step, ty) : eval_lds_bytes(words, m.has_tilted, haar_k, ty);
     } else if (tmode == TILE_16) {  // STEP-1 tile in 32 bits, STEP-2 tile in 16 bits
       const TileGeom<1> G1(m.win_w, m.win_h, ty);
       const TileGeom16 G2(m.win_w, m.win_h, ty);
@@ -924,10 +960,11 @@ cc_status spec_load(const Cascade& m, const std::vector<SpecCode>& codes, int tm
       }
     }
     if (std::getenv("CCAMD_TRACE_HOST")) {  // what the specialised kernel's footprint allows per CU
-      int nb = 0;
+      int nb = 0, scratch = -1;
       if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, x.fn, EVAL_THREADS, x.lds) != hipSuccess) (void)hipGetLastError();
-      std::fprintf(stderr, "[ccamd host] specialised kernel: tile mode %d, tiles of step %d (0 = all), %d window rows, %zu bytes of LDS per block, %d resident blocks per CU\n",
-                   tmode, c.only_step, ty, x.lds, nb);
+      if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, x.fn) != hipSuccess) (void)hipGetLastError();
+      std::fprintf(stderr, "[ccamd host] specialised kernel: tile mode %d, tiles of step %d (0 = all), %d window rows, %zu bytes of LDS per block, %d resident blocks per CU, %d bytes of scratch per lane\n",
+                   tmode, c.only_step, ty, x.lds, nb, scratch);
     }
     out[n++] = x;
   }
@@ -956,6 +993,25 @@ cc_status cc_debug_spec_step1_plan(const cc_cascade* c, int rows_wanted, int wav
   if (blocks_per_cu) *blocks_per_cu = lds_blocks_per_cu(lds);
   if (wave_below) {
     const int w = spec_wave_below(wave_below_detector, 1, ty);
+    *wave_below = w >= 0 ? w : wave_below_detector;
+  }
+  return CC_OK;
+}
+
+cc_status cc_debug_spec_step2_plan(const cc_cascade* c, int rows_wanted, int wave_below_detector, int* rows, size_t* lds_bytes, int* blocks_per_cu,
+                                   int* wave_below) {
+  if (!c) return set_error(CC_ERR_INVALID_ARG, "cc_debug_spec_step2_plan: null cascade");
+  if (cc_status hs = refuse_hog(c->m, "cc_debug_spec_step2_plan"); hs != CC_OK) return hs;
+  if (c->m.max_nodes_per_tree > 1 || !spec_lean_lds(c->m, TILE_32, 2))
+    return set_error(CC_ERR_UNSUPPORTED, "cc_debug_spec_step2_plan: upright Haar stump cascades only");
+  const int ty = rows_wanted > 0 ? rows_wanted : spec_step2_rows(c->m);
+  if (ty < TILE_Y || ty > kSpecStep2MaxRows) return set_error(CC_ERR_INVALID_ARG, "cc_debug_spec_step2_plan: %d window rows per tile", ty);
+  const size_t lds = spec_step2_lds(c->m, ty);
+  if (rows) *rows = ty;
+  if (lds_bytes) *lds_bytes = lds;
+  if (blocks_per_cu) *blocks_per_cu = lds_blocks_resident(lds);
+  if (wave_below) {
+    const int w = spec_wave_below(wave_below_detector, 2, ty);
     *wave_below = w >= 0 ? w : wave_below_detector;
   }
   return CC_OK;

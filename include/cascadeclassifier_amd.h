@@ -399,6 +399,11 @@ CC_API cc_status cc_debug_wave_int_tables(const cc_cascade* c, double* q, int32_
  * CC_ERR_UNSUPPORTED for cascades that do not get such a module (LBP, HOG, trees, tilted features). */
 CC_API cc_status cc_debug_spec_step1_plan(const cc_cascade* c, int rows_wanted, int wave_below_detector, int* rows, size_t* lds_bytes,
                                           int* blocks_per_cu, int* wave_below);
+/* The same for the module of STEP-2 tiles. rows_wanted > 0: any height from 8 to 12, as CCAMD_SPEC_TILE_Y2 would ask for;
+ * <= 0: the library's choice, the tallest such height at which as many blocks share a CU as at 8 rows. *blocks_per_cu counts
+ * the request in LDS allocation units of 1 280 bytes (lds_blocks_resident). */
+CC_API cc_status cc_debug_spec_step2_plan(const cc_cascade* c, int rows_wanted, int wave_below_detector, int* rows, size_t* lds_bytes,
+                                          int* blocks_per_cu, int* wave_below);
 /* Host-side (tiny, serial in the reference too): cv::groupRectangles(rects, group_threshold, eps). */
 CC_API cc_status cc_group_rectangles(const cc_rect* rects, int n, int group_threshold, double eps, cc_rect* out, int cap,
                                      int* n_out);
