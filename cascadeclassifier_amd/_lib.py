@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CCAMD_LIB selects another build of the same library (tuning experiments); the default is the in-tree build.
 LIB_PATH = os.environ.get("CCAMD_LIB") or os.path.join(_HERE, "lib", "libcascadeclassifier_amd.so")
@@ -318,3 +320,17 @@ def check(status: int) -> int:
     if status != CC_OK:
         raise CascadeError(status, lib().cc_last_error().decode("utf-8", "replace"))
     return status
+
+
+def pack_trees(weak):
+    """(n_nodes, TreeNode array, leaves) of weak records, as cc_cascade_from_trees and cc_stage_save_xml take them: a record with
+    "nodes" (and "leaves") is a tree, any other the stump left=0, right=-1 of its own fields. Leaves and thresholds are cast to
+    float, as the writer does; the caller has dropped the records with trained == False."""
+    trees = [(w["nodes"], w["leaves"]) if "nodes" in w else ([dict(w, left=0, right=-1)], [w["left_value"], w["right_value"]]) for w in weak]
+    n_nodes = np.array([len(nodes) for nodes, _ in trees], np.int32)
+    flat = (TreeNode * max(1, int(n_nodes.sum())))()
+    for k, nd in enumerate(nd for nodes, _ in trees for nd in nodes):
+        flat[k].left, flat[k].right, flat[k].var_idx = int(nd["left"]), int(nd["right"]), int(nd["var_idx"])
+        flat[k].ord_c = float(np.float32(nd.get("ord_c", 0.0)))
+        flat[k].subset[:] = [int(v) for v in np.asarray(nd.get("subset", np.zeros(8)), np.int64).astype(np.int32)]
+    return n_nodes, flat, np.array([np.float32(v) for _, lv in trees for v in lv], np.float32)

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <iosfwd>
 #include <string>
 #include <vector>
 
@@ -88,7 +89,48 @@ struct Cascade {
                                             : (int)(lbp_rects.size() / 4);
   }
 };
-cc_status cascade_from_xml(const XmlNode& root, Cascade& out);
+cc_status cascade_from_xml(const XmlNode& root, Cascade& out);  // cc_cascade_xml.cpp
+
+// ---- text of the files: tokens, numbers, names (cc_cascade.cpp) ----------------------------------
+void split_tokens(const std::string& s, std::vector<std::string>& out);
+bool to_int(const std::string& t, int32_t& v);  // also integral reals ("6.")
+bool to_double(const std::string& t, double& v);
+bool node_int(const XmlNode* n, int32_t& v);  // false for a missing node or one that is not a single number
+bool node_double(const XmlNode* n, double& v);
+std::string trimmed(const std::string& s);
+extern const char* const kFeatureNames[3];  // HAAR, LBP, HOG
+extern const char* const kBoostNames[4];    // CvBoost's DISCRETE, REAL, LOGIT, GENTLE
+extern const char* const kModeNames[3];     // BASIC, CORE, ALL
+int name_index(const std::string& s, const char* const* names, int n);  // -1: none
+// FileStorage prints float reals with "%.8e", doubles with "%.16e", and integral reals as "2."
+std::string real_text(float v);
+std::string real_text_d(double v);
+cc_status read_text_file(const char* path, std::string& text);
+cc_status write_text_file(const char* path, const std::string& text);
+
+// ---- trees: what every reader, writer and builder of them shares (cc_cascade.cpp) -----------------
+// The child-reference rule. Node j of a tree of nn nodes names a child > 0 (an internal node of this tree) or <= 0 (leaf
+// -child of its nn + 1 leaves). A child lies inside the tree, and an internal child lies behind its parent: the writer
+// numbers nodes breadth-first, and insisting on it makes every walk of the tree end (a cycle would hang a kernel).
+// nullptr: the references are good; else what is wrong with them, to follow "a child of node j ".
+const char* child_ref_fault(int32_t left, int32_t right, int j, int nn);
+// n_nodes[t] >= 1 for each of n_trees trees (nullptr: one node each), n_nodes_total their sum: CC_ERR_INVALID_ARG otherwise
+cc_status check_node_counts(const char* who, const int32_t* n_nodes, size_t n_trees, int n_nodes_total);
+// The <_> of weak classifier t: "left right featureIdx (threshold | subset_words words)" per node of <internalNodes> and
+// one more <leafValues> than nodes, appended to nodes (left, right, var_idx, ord_c or subset; the rest 0) and leaves.
+// featureIdx lies in [0, feature_bound), feature_bound 0: in [0, inf). CC_ERR_PARSE with messages behind "where: ".
+cc_status read_weak_xml(const XmlNode& wn, int subset_words, int feature_bound, const char* where, int t, std::vector<cc_tree_node>& nodes,
+                        std::vector<float>& leaves);
+// The same <_>, written `indent` spaces deep as FileStorage lays it out.
+void write_weak_xml(std::ostream& o, int indent, const cc_tree_node* nodes, int nn, int subset_words, const float* leaves);
+// One more tree behind the model's trees; var_map (nullptr: none) renumbers var_idx. The nodes have passed child_ref_fault.
+void append_tree(Cascade& c, const cc_tree_node* nodes, int nn, const float* leaves, const int32_t* var_map);
+void build_stump_view(Cascade& c);  // once every tree is appended; does nothing unless each has one node
+
+// ---- the parameter block of params.xml and cascade.xml (cc_trainfiles.cpp) -------------------------
+cc_status train_params_from_xml(const XmlNode& block, const char* where, cc_train_params& p);
+cc_status check_param_names(const char* who, const cc_train_params& p);
+void write_params_text(std::ostream& o, int feature_type, int win_w, int win_h, const cc_train_params* p, int max_weak, int max_cat, int feat_size);
 
 // ---- pyramid geometry (host) --------------------------------------------------------------------
 struct ScaleGeom {

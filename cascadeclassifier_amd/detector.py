@@ -264,24 +264,9 @@ class CascadeClassifier:
         weaks = [[w for w in ws if w.get("trained", True)] for _, ws in stages]
         n_weak = np.array([len(ws) for ws in weaks], np.int32)
         thr = np.array([np.float32(t) for t, _ in stages], np.float32)
-        trees = []
-        for w in (w for ws in weaks for w in ws):
-            if "nodes" in w:
-                trees.append((w["nodes"], w["leaves"]))
-            else:
-                trees.append(([dict(w, left=0, right=-1)], [w["left_value"], w["right_value"]]))
-        n_nodes = np.array([len(nodes) for nodes, _ in trees], np.int32)
-        flat = (L.TreeNode * max(1, int(n_nodes.sum())))()
-        k = 0
-        for nodes, _ in trees:
-            for nd in nodes:
-                flat[k].left, flat[k].right, flat[k].var_idx = int(nd["left"]), int(nd["right"]), int(nd["var_idx"])
-                flat[k].ord_c = float(np.float32(nd.get("ord_c", 0.0)))
-                flat[k].subset[:] = [int(v) for v in np.asarray(nd.get("subset", np.zeros(8)), np.int64).astype(np.int32)]
-                k += 1
-        leaves = np.array([np.float32(v) for _, lv in trees for v in lv], np.float32)
+        n_nodes, flat, leaves = L.pack_trees([w for ws in weaks for w in ws])
         self = cls(None, device, max_batch)
-        L.check(L.lib().cc_cascade_from_trees(int(feature_type), int(haar_mode), int(win[0]), int(win[1]), len(n_weak), _vp(n_weak), len(trees),
+        L.check(L.lib().cc_cascade_from_trees(int(feature_type), int(haar_mode), int(win[0]), int(win[1]), len(n_weak), _vp(n_weak), len(n_nodes),
                                               _vp(thr), _vp(n_nodes), int(n_nodes.sum()), flat, _vp(leaves), C.byref(self._c)))
         return self
 

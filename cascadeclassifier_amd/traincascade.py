@@ -109,24 +109,9 @@ def write_stage(path: str, stage, feature_type, object_name: str | None = None):
     trained == False are skipped, one with "nodes" and "leaves" is a tree, any other the stump of its own fields. Variable
     indices are written as they are (catalog indices); leaves and thresholds are cast to float as the writer does."""
     thr, weak = stage
-    trees = []
-    for w in (w for w in weak if w.get("trained", True)):
-        if "nodes" in w:
-            trees.append((w["nodes"], w["leaves"]))
-        else:
-            trees.append(([dict(w, left=0, right=-1)], [w["left_value"], w["right_value"]]))
-    n_nodes = np.array([len(nodes) for nodes, _ in trees], np.int32)
-    flat = (L.TreeNode * max(1, int(n_nodes.sum())))()
-    k = 0
-    for nodes, _ in trees:
-        for nd in nodes:
-            flat[k].left, flat[k].right, flat[k].var_idx = int(nd["left"]), int(nd["right"]), int(nd["var_idx"])
-            flat[k].ord_c = float(np.float32(nd.get("ord_c", 0.0)))
-            flat[k].subset[:] = [int(v) for v in np.asarray(nd.get("subset", np.zeros(8)), np.int64).astype(np.int32)]
-            k += 1
-    leaves = np.array([np.float32(v) for _, lv in trees for v in lv], np.float32)
+    n_nodes, flat, leaves = L.pack_trees([w for w in weak if w.get("trained", True)])
     L.check(L.lib().cc_stage_save_xml(path.encode(), None if object_name is None else object_name.encode(), _max_cat_count(feature_type),
-                                      float(np.float32(thr)), len(trees), n_nodes.ctypes.data_as(C.c_void_p), int(n_nodes.sum()), flat,
+                                      float(np.float32(thr)), len(n_nodes), n_nodes.ctypes.data_as(C.c_void_p), int(n_nodes.sum()), flat,
                                       leaves.ctypes.data_as(C.c_void_p)))
 
 

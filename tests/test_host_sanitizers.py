@@ -2,32 +2,19 @@
 XML reader on thousands of mutated files, the .vec reader on truncated / corrupted files, grouping and the scale plan on
 hostile arguments. tests/cpp/fuzz_host.cpp is compiled with g++ against the product's host sources."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import cascade_factory as cf
+from tests.host_build import build_program
 from tests.util import frame_natural
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cascadeclassifier_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def fuzz_bin(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    out = str(tmp_path_factory.mktemp("fuzz") / "fuzz_host")
-    cmd = ["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1", "-I" + os.path.join(ROOT, "include"),
-           "-I" + CSRC, os.path.join(ROOT, "tests", "cpp", "fuzz_host.cpp")] + [os.path.join(CSRC, f) for f in ("cc_xml.cpp", "cc_cascade.cpp", "cc_host.cpp")] + \
-          ["-o", out, "-pthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr:
-        pytest.skip("sanitizer runtime not installed")
-    assert r.returncode == 0, r.stderr
-    return out
+    return build_program("fuzz_host", tmp_path_factory.mktemp("fuzz"))
 
 
 @pytest.mark.parametrize("which", ["lbp", "haar_trees", "lbp_trees"])

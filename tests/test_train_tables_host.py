@@ -2,28 +2,17 @@
 program (own main, no device call) that builds the plain-offset catalogs and the node records of k_predict and checks every
 offset and child index. CPU only."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 
 from tests import cascade_factory as cf
+from tests.host_build import build_program
 from tests.util import frame_natural, truncated_cascade
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cascadeclassifier_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def test_train_tables_host_program_runs_clean(tmp_path, haar_xml, lbp_xml):
-    hipcc = HIPCC if os.path.exists(HIPCC) else (shutil.which("hipcc") or HIPCC)
-    exe = os.path.join(str(tmp_path), "train_tables_host")
-    cmd = [hipcc, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Xarch_host",
-           "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-           os.path.join(ROOT, "tests", "cpp", "train_tables_host.cpp")] + [os.path.join(CSRC, f) for f in ("cc_xml.cpp", "cc_cascade.cpp", "cc_host.cpp")] + \
-          ["-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = build_program("train_tables_host", tmp_path, hip_host_only=True)
     img = frame_natural(320, 240, 3)
     wins = np.stack([img[y:y + 24, x:x + 24] for y in range(0, 200, 9) for x in range(0, 280, 11)])
     made = {"haar_trees.xml": cf.haar_tree_cascade(wins, with_tilted=True), "lbp_trees.xml": cf.lbp_tree_cascade(),

@@ -1,29 +1,16 @@
 """The readers and writers of the trainer's files (params.xml, stage<i>.xml; section 6d of the C ABI) under
 AddressSanitizer + UBSan, as tests/test_host_sanitizers.py holds the cascade reader: tests/cpp/fuzz_trainfiles.cpp is a
 stand-alone program compiled with g++ against the product's host sources and run on the CPU."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cascadeclassifier_amd", "csrc")
+from tests.host_build import build_program
 
 
 @pytest.fixture(scope="module")
 def fuzz_bin(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    out = str(tmp_path_factory.mktemp("fuzz") / "fuzz_trainfiles")
-    cmd = ["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1", "-I" + os.path.join(ROOT, "include"),
-           "-I" + CSRC, os.path.join(ROOT, "tests", "cpp", "fuzz_trainfiles.cpp")] + [os.path.join(CSRC, f) for f in ("cc_xml.cpp", "cc_cascade.cpp", "cc_host.cpp")] + \
-          ["-o", out, "-pthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr:
-        pytest.skip("sanitizer runtime not installed")
-    assert r.returncode == 0, r.stderr
-    return out
+    return build_program("fuzz_trainfiles", tmp_path_factory.mktemp("fuzz"))
 
 
 def test_mutated_training_files_never_trip_a_sanitizer(fuzz_bin, tmp_path):
